@@ -7,7 +7,11 @@ resident in HBM, decoded for exactly 50 iterations (Eb/N0 = 0 dB: far below thre
 frame converges -- the fixed-work operating point P1 of SURVEY.md section 8(d); the run
 asserts that every frame used all iterations).  Prints ONE JSON line on rank 0.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the line; --dump-outputs DIR also writes what the last
+timed step returned (dump_outputs).  Everything else is measured with --full only: the event-bracketed region and the
+`roofline` block it feeds, and the secondary blocks below.
 
 `--gpus N` with N > 1 and no torchrun environment: this process starts the N ranks itself (a child
 `python -m torch.distributed.run --nproc-per-node N bench.py ...`, one rank per GPU) before it has
@@ -18,7 +22,7 @@ equal WORLD_SIZE.  The multi-GPU run is N independent workers (reference:
 main thread): no collective on the decode path, one all-reduce of the six error counters (48 bytes)
 and one of the elapsed time after the timed region.
 
-Secondary blocks on rank 0 at N = 1 (never `value`): `realistic` (Eb/N0 = 2 dB, early termination),
+Secondary blocks on rank 0 at N = 1 with --full (never `value`): `realistic` (Eb/N0 = 2 dB, early termination),
 `config3` (BASELINE.json configs[2]: 5G NR BG1 Zc=384, HLTanhf32, batch 8192) and `cpu_baseline`.
 """
 import argparse
@@ -67,7 +71,7 @@ def parse_args(argv=None):
                          "child passes: minutes)")
     ap.add_argument("--no-live-traffic", action="store_true",
                     help="quote profiles/hbm_traffic.json for the headline kernel's roofline.traffic instead of measuring it in "
-                         "this run (default: two rocprofv3 --pmc child passes of one step each, about a minute)")
+                         "this run (--full's default: two rocprofv3 --pmc child passes of one step each, about a minute)")
     ap.add_argument("--share-device", action="store_true",
                     help="REHEARSAL of the N-rank path on a one-GPU box (never a throughput number, the line says so): the N "
                          "ranks are N real decoder processes that all use GPU 0, each decodes batch/N frames of the one frame "
@@ -81,6 +85,15 @@ def parse_args(argv=None):
     ap.add_argument("--stub", action="store_true",
                     help="launcher self-test (tests/test_distributed_gloo.py): CPU ranks over gloo and a stand-in "
                          "for the decoder; the line it prints says so and is not a measurement")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the event-bracketed region and the roofline block it feeds "
+                         "(with the counter passes unless --no-live-traffic), and on rank 0 the secondary blocks `realistic`, "
+                         "`config3` and `cpu_baseline` (each subject to its --no-* flag).  Without it a run sets up, warms "
+                         "up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32; rank 0's frames): iterations.npy (every frame), bits.npy (the hard decisions of a fixed, "
+                         "seeded sample of frames, at most 32 MiB) and bits_frames.npy (their frame indices)")
     return ap.parse_args(argv)
 
 
@@ -95,11 +108,16 @@ def _free_port():
 
 
 def launch_ranks(args):
-    """Parent of an N-GPU run.  Nothing here touches a GPU (no HIP call, no torch.cuda use beyond
-    counting devices), and the ranks are a child process, never an exec of this one."""
+    """Parent of an N-GPU run.  Nothing here touches a GPU (no HIP call; the devices are counted by a
+    short-lived child), and the ranks are a child process, never an exec of this one."""
     if not args.stub:
-        import torch
-        have = torch.cuda.device_count()      # does not initialise the GPU
+        # counted by a short-lived child: counting opens the device, and this process must not hold it while the ranks run
+        # (a shared machine may limit how many processes hold one GPU at once)
+        r = subprocess.run([sys.executable, "-c", "import torch; print(torch.cuda.device_count())"], capture_output=True, text=True)
+        if r.returncode != 0 or not r.stdout.split():
+            print(f"bench.py: could not count the GPUs: {r.stderr[-2000:]}", file=sys.stderr)
+            return 2
+        have = int(r.stdout.split()[-1])
         if have < (1 if args.share_device else args.gpus):
             print(f"bench.py: --gpus {args.gpus} requested but only {have} GPU(s) are visible", file=sys.stderr)
             return 2
@@ -110,10 +128,12 @@ def launch_ranks(args):
     for flag, on in (("--no-cpu-baseline", args.no_cpu_baseline), ("--no-realistic", args.no_realistic),
                      ("--no-config3", args.no_config3), ("--live-traffic", args.live_traffic),
                      ("--no-live-traffic", args.no_live_traffic), ("--stub", args.stub),
-                     ("--share-device", args.share_device), ("--no-affinity", args.no_affinity)):
+                     ("--share-device", args.share_device), ("--no-affinity", args.no_affinity), ("--full", args.full)):
         if on:
             cmd.append(flag)
     cmd += ["--workload", args.workload]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "4")
@@ -299,14 +319,19 @@ def main(argv=None):
     barrier()
     elapsed = time.perf_counter() - t0
     lanes, group_cw = (1, min(B, 4096)) if stub else (max(dec.get("last_lanes"), 1), dec.get("last_group"))
-    # The kernels' own durations: the same K steps again with the library's HIP events around every check-node /
+    # what the last timed step returned to its caller
+    its_np = its.cpu().numpy()
+    bits_np = bits.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, bits_np, its_np)
+    # --full: the kernels' own durations: the same K steps again with the library's HIP events around every check-node /
     # variable-node launch, recorded on the launch stream.  (With those brackets in place the lanes no longer overlap
     # usefully, so the library runs a profiled call as ONE lane: a launch then covers the whole group and its time is
     # the kernel's own.  Timing the bracketed region instead of the clean one would report the slower of the two.)
     cn_launches = vn_launches = 0
     cn_ms = vn_ms = 0.0
     elapsed_prof, prof_group = 0.0, min(B, 4096)
-    if not stub:
+    if args.full and not stub:
         dec.set("profiling", 1)
         dec.kernel_stats(0, reset=True)
         dec.kernel_stats(1, reset=True)
@@ -338,11 +363,10 @@ def main(argv=None):
     per_rank = [{"rank": int(r[0]), "device": int(r[6]), "ms_per_step": r[1] / max(args.steps, 1) * 1e3,
                  "codewords_per_s": B * args.steps / r[1] if r[1] > 0 else None, "setup_s": r[2],
                  "host_enqueue_ms_per_step": r[3] / max(args.steps, 1) * 1e3,
-                 "check_launch_us": r[4] * 1e3, "variable_phase_us": r[5] * 1e3,
+                 # the bracketed region's launch times (--full only)
+                 "check_launch_us": r[4] * 1e3 if args.full else None, "variable_phase_us": r[5] * 1e3 if args.full else None,
                  "numa_node": int(r[7]), "pinned_cpus": int(r[8])} for r in sorted(per_rank_rows)]
 
-    its_np = its.cpu().numpy()
-    bits_np = bits.cpu().numpy()
     # P1 contract: every frame ran all iterations (none converged)
     if args.workload == "config2" or stub:
         assert (its_np == -1).all(), "fixed-work operating point violated: some frames converged"
@@ -376,7 +400,7 @@ def main(argv=None):
     m_rows = 0 if stub else dec.get("m")
     cn_kernel = "cn_minsum_rec_kernel" if recw else "cn_minsum_lfree_kernel"
     byte_model = None
-    if not stub:
+    if args.full and not stub:
         deg = np.array(alist.split("\n")[2].split(), dtype=np.int64)   # alist line 3: the column weights
         n_free = int((deg <= 2).sum())
         e_keep = int(deg[deg > 2].sum())
@@ -402,11 +426,11 @@ def main(argv=None):
 
     traffic_iter, traffic_by_kernel, traffic_source = None, None, None
     tpath = os.path.join(ROOT, "profiles", "hbm_traffic.json")
-    if not stub and world == 1 and not in_rank and not args.no_live_traffic and recw:
+    if args.full and not stub and world == 1 and not in_rank and not args.no_live_traffic and recw:
         traffic_by_kernel, traffic_source = live_traffic(B)
         if traffic_by_kernel:
             traffic_iter = sum(traffic_by_kernel.values())
-    if traffic_iter is None and not stub and os.path.exists(tpath):
+    if args.full and traffic_iter is None and not stub and os.path.exists(tpath):
         try:
             t = json.load(open(tpath))
             cn_b, vn_b = t.get(cn_kernel + "_bytes_per_launch"), t.get("vn_kernel_bytes_per_launch")
@@ -508,11 +532,15 @@ def main(argv=None):
         out["share_device"] = bool(share)
         if share:
             out["data"] += "; rehearsal: all ranks on one GPU"
+    if not args.full:
+        # a plain run: the bracketed region did not run, so there are no launch times for a roofline
+        out["roofline"] = None
+        del out["regions"]["bracketed"]
     if stub:
         out["data"] = "stub (no decoder ran: launcher self-test, not a measurement)"
         out["roofline"] = None
         out["config"]["workload"] = "stub"
-    elif not share and args.workload == "config2":
+    elif args.full and not share and args.workload == "config2":
         # secondary, not `value`: the realistic operating point P2 (Eb/N0 = 2 dB, syndrome early
         # termination active), one untimed-warm pass over a fresh batch on rank 0
         if not args.no_realistic:
@@ -625,6 +653,22 @@ def live_config3_counters():
             return None, None
         tot[counter] = s_sum / s_n
     return (2.0 * tot["FETCH_SIZE"] + tot["WRITE_SIZE"]) * 1024.0, tot["SQ_INSTS_VALU"]
+
+
+DUMP_BITS_BYTES = 32 << 20    # --dump-outputs: the sample of hard-decision rows stays below this (float32)
+
+
+def dump_outputs(path, bits_np, its_np):
+    """--dump-outputs: what the last timed step returned to its caller, as float32 .npy files -- every frame's iteration
+    count, and the hard decisions of a fixed, seeded sample of frames (as many as DUMP_BITS_BYTES holds) with their frame
+    indices.  The frames are seeded, so two builds run with the same arguments can be compared output for output."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    b, k = bits_np.shape
+    rows = np.sort(np.random.default_rng(0).choice(b, size=max(1, min(b, DUMP_BITS_BYTES // (4 * k))), replace=False))
+    np.save(os.path.join(path, "iterations.npy"), its_np.astype(np.float32))
+    np.save(os.path.join(path, "bits.npy"), bits_np[rows].astype(np.float32))
+    np.save(os.path.join(path, "bits_frames.npy"), rows.astype(np.float32))
 
 
 def make_frames(alist, impl, batch, ebn0_db, seed, device, device_index, first_frame=0, pool=FRAME_POOL):

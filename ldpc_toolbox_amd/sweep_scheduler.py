@@ -22,7 +22,7 @@ assignment and one all_gather_object).
 than 64 groups.  Batch b covers the same frame indices whoever decodes it -- one rank alone or N ranks a shard each --
 the generator's noise is a pure function of (seed, frame index, position), and the stop rule is evaluated between batches
 on the point's total counters.  So every counter column of every row equals the one-rank run's (tests:
-tests/test_distributed_gloo.py with two gloo ranks, tests/test_gpu_launcher.py with eight real ranks on one GPU).
+tests/test_distributed_gloo.py with two gloo ranks, tests/test_gpu_launcher.py with four real ranks on one GPU).
 The time-based stop rules (--min-time / --max-time) are honoured (phase A: the owner's clock, phase B: rank 0's) but make
 a table depend on the machine, as they do in the reference.
 

@@ -13,6 +13,7 @@ import numpy as np
 import pytest
 
 import ldpc_toolbox_amd as lt
+from experiments_build import on_experiments_build
 from frames import alist, awgn_frames
 
 pytestmark = pytest.mark.gpu
@@ -104,11 +105,10 @@ def test_group_that_finishes_inside_the_variable_node_launch(oracle, batch):
                 assert np.array_equal(a, b), (batch, rep, "host entry" if host else "device entry", name, where(a, b))
 
 
+@on_experiments_build
 def test_streaming_record_variant_is_deterministic():
-    """the STREAM instantiation (continuous batching through the simulator; -DLDPC_EXPERIMENTS builds only since round 5):
-    same counters 20 times"""
-    if lt.LdpcDecoder(alist("ar4ja:1/2:1024"), "Minsumf32").get("experiments") != 1:
-        pytest.skip("continuous batching exists in -DLDPC_EXPERIMENTS builds only")
+    """the STREAM instantiation (continuous batching through the simulator; -DLDPC_EXPERIMENTS builds only since round 5,
+    so the test runs on that build): same counters 20 times"""
     s = lt.Simulator(alist("dvbs2:R1_2short"), "Minsumf32", "", device=0, pool_size=16, pool_seed=9)
     s.set("records", 2)
     s.set("streaming", 1)

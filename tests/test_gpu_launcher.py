@@ -13,6 +13,9 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# ranks of the one-GPU rehearsals below: every rank is one more process with the GPU open beside this one, and a shared
+# test box admits only a few of those at once
+RANKS = 4
 
 
 def _free_port():
@@ -39,7 +42,7 @@ def _bench(argv, env=None, timeout=900):
 
 
 def test_forced_launch_runs_one_rccl_rank_and_matches_the_in_process_run():
-    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1024", "--no-cpu-baseline", "--no-realistic",
+    common = ["--gpus", "1", "--steps", "3", "--warmup", "1", "--batch", "1024", "--full", "--no-cpu-baseline", "--no-realistic",
               "--no-config3", "--no-live-traffic"]
     plain, _ = _bench(common)
     forced, r = _bench(common, env={"LDPC_BENCH_FORCE_LAUNCH": "1", "NCCL_DEBUG": "VERSION"})
@@ -58,32 +61,32 @@ def test_forced_launch_runs_one_rccl_rank_and_matches_the_in_process_run():
 
 
 @pytest.mark.parametrize("workload", ["config2", "config3"])
-def test_eight_real_ranks_share_one_gpu(workload):
-    """Eight REAL decoder processes at once -- the shape of the 8-GPU run (reference:
+def test_four_real_ranks_share_one_gpu(workload):
+    """Four REAL decoder processes at once -- the shape of the 8-GPU run (reference:
     /root/reference/src/simulation/ber.rs:304-342, one decoder per worker, counters folded by the parent) rehearsed on
-    the one GPU a test box has: `bench.py --gpus 8 --share-device` starts eight ranks through the same launcher, every
-    rank builds its own decoder on GPU 0, pins itself to its share of the CPUs, decodes frames [r*512, (r+1)*512) of the
+    the one GPU a test box has: `bench.py --gpus 4 --share-device` starts four ranks through the same launcher, every
+    rank builds its own decoder on GPU 0, pins itself to its share of the CPUs, decodes frames [r*1024, (r+1)*1024) of the
     one frame stream, and the six counters are summed over gloo.  The sums equal those of ONE process decoding frames
-    [0, 4096).  (Config 3: the layered schedule, two lanes x 35 launches per iteration per process -- sixteen enqueuing
+    [0, 4096).  (Config 3: the layered schedule, two lanes x 35 launches per iteration per process -- eight enqueuing
     threads and their progress pollers at once.)  Not a throughput measurement; the line says so."""
     common = ["--steps", "2", "--warmup", "1", "--batch", "4096", "--workload", workload, "--no-cpu-baseline", "--no-realistic",
               "--no-config3", "--no-live-traffic"]
     one, _ = _bench(["--gpus", "1"] + common)
-    eight, r = _bench(["--gpus", "8", "--share-device"] + common)
-    assert eight["n_gpus"] == 8 and eight["share_device"] is True and eight["launch"]["process_group"] == "gloo"
-    assert "REHEARSAL" in eight["config"]["workload"] and eight["roofline"] is None
-    assert eight["ber"]["num_frames"] == 4096 and eight["ber"] == one["ber"], (eight["ber"], one["ber"])
-    aff = eight["launch"]["cpu_affinity_rank0"]
-    assert aff and "error" not in aff and aff["ranks_on_node"] == 8 and aff["cpus"] >= 1, aff
-    # every rank's own figures are in the line: eight rows, ranks 0..7, each with its own clock and kernel times
-    rows = eight["launch"]["per_rank"]
-    assert [r["rank"] for r in rows] == list(range(8)) and all(r["ms_per_step"] > 0 and r["codewords_per_s"] > 0 for r in rows)
+    shared, r = _bench(["--gpus", str(RANKS), "--share-device"] + common)
+    assert shared["n_gpus"] == RANKS and shared["share_device"] is True and shared["launch"]["process_group"] == "gloo"
+    assert "REHEARSAL" in shared["config"]["workload"] and shared["roofline"] is None
+    assert shared["ber"]["num_frames"] == 4096 and shared["ber"] == one["ber"], (shared["ber"], one["ber"])
+    aff = shared["launch"]["cpu_affinity_rank0"]
+    assert aff and "error" not in aff and aff["ranks_on_node"] == RANKS and aff["cpus"] >= 1, aff
+    # every rank's own figures are in the line: one row per rank, ranks 0..RANKS-1, each with its own clock
+    rows = shared["launch"]["per_rank"]
+    assert [r["rank"] for r in rows] == list(range(RANKS)) and all(r["ms_per_step"] > 0 and r["codewords_per_s"] > 0 for r in rows)
     assert all(r["pinned_cpus"] >= 1 and r["numa_node"] == rows[0]["numa_node"] for r in rows)
-    assert eight["launch"]["slowest_rank"] in range(8)
-    assert eight["launch"]["min_rank_rate_times_ranks"] <= eight["launch"]["sum_of_rank_rates"] * (1 + 1e-9)
+    assert shared["launch"]["slowest_rank"] in range(RANKS)
+    assert shared["launch"]["min_rank_rate_times_ranks"] <= shared["launch"]["sum_of_rank_rates"] * (1 + 1e-9)
     assert len(one["launch"]["per_rank"]) == 1
-    print(workload, "enqueue ms/step: 1 process", one["launch"]["host_enqueue_ms_per_step"], "8 processes",
-          eight["launch"]["host_enqueue_ms_per_step"])
+    print(workload, "enqueue ms/step: 1 process", one["launch"]["host_enqueue_ms_per_step"], f"{RANKS} processes",
+          shared["launch"]["host_enqueue_ms_per_step"])
 
 
 def _table(path):
@@ -122,11 +125,11 @@ def test_ber_sweep_under_a_one_rank_rccl_group_matches_the_in_process_sweep(tmp_
     assert "Number of GPUs: 1" in open(forced).read()
 
 
-def test_ber_sweep_with_eight_ranks_sharing_one_gpu_matches_the_in_process_sweep(tmp_path):
+def test_ber_sweep_with_four_ranks_sharing_one_gpu_matches_the_in_process_sweep(tmp_path):
     """BASELINE config 5's shape -- the sweep over N ranks, every batch's frame indices sharded contiguously, the counters
-    summed between batches, the stop rule (/root/reference/src/simulation/ber.rs:522-531) decided on the sums -- with EIGHT
-    real ranks: `python -m torch.distributed.run --nproc-per-node 8 -m ldpc_toolbox_amd.ber ... --share-device` (every rank
-    its own Simulator on GPU 0, gloo).  With the per-GPU batch an eighth of the in-process run's the ranks decode exactly
+    summed between batches, the stop rule (the reference's src/simulation/ber.rs:522-531) decided on the sums -- with FOUR
+    real ranks: `python -m torch.distributed.run --nproc-per-node 4 -m ldpc_toolbox_amd.ber ... --share-device` (every rank
+    its own Simulator on GPU 0, gloo).  With the per-GPU batch a quarter of the in-process run's the ranks decode exactly
     the same frames batch by batch, so the two tables agree in every counter column."""
     base = ["--code", "dvbs2:R1_2short", "--decoder", "Minsumf32", "--min-ebn0", "1.2", "--max-ebn0", "1.8", "--step-ebn0", "0.3",
             "--max-iter", "40", "--frame-errors", "60", "--max-frames", "65536", "--seed", "11"]
@@ -137,12 +140,12 @@ def test_ber_sweep_with_eight_ranks_sharing_one_gpu_matches_the_in_process_sweep
     e = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for v in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(v, None)
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(RANKS), "--master-addr",
                         "127.0.0.1", "--master-port", str(_free_port()), "-m", "ldpc_toolbox_amd.ber"] + base +
-                       ["--frames-per-batch", "512", "--share-device", "--output-file", str(shared)],
+                       ["--frames-per-batch", str(4096 // RANKS), "--share-device", "--output-file", str(shared)],
                        capture_output=True, text=True, timeout=1200, env=e, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
-    assert "process group: gloo with 8 rank(s)" in r.stdout
+    assert f"process group: gloo with {RANKS} rank(s)" in r.stdout
     a, b = _table(plain), _table(shared)
     assert len(a) == 3 and a == b, (a, b)
 
@@ -151,11 +154,11 @@ def _dir_tables(d):
     return {f: _table(os.path.join(d, f)) for f in sorted(os.listdir(d))}
 
 
-def test_multi_code_sweep_job_with_eight_ranks_sharing_one_gpu_matches_the_one_rank_job(tmp_path):
+def test_multi_code_sweep_job_with_four_ranks_sharing_one_gpu_matches_the_one_rank_job(tmp_path):
     """BASELINE.json configs[4] as ONE N-rank job (ldpc_toolbox_amd/sweep_scheduler.py): `python -m torch.distributed.run
-    --nproc-per-node 8 -m ldpc_toolbox_amd.ber --codes ... --grid waterfall --share-device` -- the per-code pre-scans and
+    --nproc-per-node 4 -m ldpc_toolbox_amd.ber --codes ... --grid waterfall --share-device` -- the per-code pre-scans and
     the cheap (code, Eb/N0) points go to ranks whole from a queue in the process group's store, the points that need many
-    frames are frame-sharded over all eight ranks -- against the same job in this process on one rank: the pre-scan
+    frames are frame-sharded over all four ranks -- against the same job in this process on one rank: the pre-scan
     places the same grids and every counter column of every row of every code's result file is equal
     (reference: /root/reference/src/simulation/ber.rs:304-342, 522-531; SURVEY.md section 8(e): both splits)."""
     # (short frames: a group of the decoder is 16384 of them, so "needs more than 8 groups" shares the points beyond 131072
@@ -165,18 +168,18 @@ def test_multi_code_sweep_job_with_eight_ranks_sharing_one_gpu_matches_the_one_r
     from ldpc_toolbox_amd import ber
     one = tmp_path / "one"
     ber.main(base + ["--output-dir", str(one)])
-    eight = tmp_path / "eight"
+    shared = tmp_path / "shared"
     e = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""))
     for v in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         e.pop(v, None)
-    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8", "--master-addr",
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(RANKS), "--master-addr",
                         "127.0.0.1", "--master-port", str(_free_port()), "-m", "ldpc_toolbox_amd.ber"] + base +
-                       ["--share-device", "--verbose", "--output-dir", str(eight)],
+                       ["--share-device", "--verbose", "--output-dir", str(shared)],
                        capture_output=True, text=True, timeout=1500, env=e, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-3000:], r.stderr[-3000:])
-    assert "process group: gloo with 8 rank(s)" in r.stdout
+    assert f"process group: gloo with {RANKS} rank(s)" in r.stdout
     assert "queue: store" in r.stdout, r.stdout[-2000:]
-    a, b = _dir_tables(one), _dir_tables(eight)
+    a, b = _dir_tables(one), _dir_tables(shared)
     assert sorted(a) == sorted(b) and len(a) == 3
     for f in a:
         assert len(a[f]) == 8 and a[f] == b[f], (f, a[f], b[f])

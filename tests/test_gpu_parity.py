@@ -13,19 +13,15 @@ import numpy as np
 import pytest
 
 import ldpc_toolbox_amd as lt
+from experiments_build import on_experiments_build
 from frames import alist, awgn_frames
 
 pytestmark = pytest.mark.gpu
 
 
-def experiments_build():
-    """True when the loaded library was built with -DLDPC_EXPERIMENTS (tools/ab_variants.sh build exp -DLDPC_EXPERIMENTS;
-    LDPC_TOOLBOX_LIB selects it): it carries the opt-in forms the product left behind in round 5 -- the slice-persistent
-    layered kernel and continuous batching -- and their tests run only there."""
-    return lt.LdpcDecoder(alist("ar4ja:1/2:1024"), "Minsumf32").get("experiments") == 1
-
-
-needs_experiments = pytest.mark.skipif("not experiments_build()", reason="opt-in form that only -DLDPC_EXPERIMENTS builds carry")
+# the opt-in forms the product left behind in round 5 (the slice-persistent layered kernel, continuous batching) exist in
+# the -DLDPC_EXPERIMENTS build only: their tests run on it (tests/experiments_build.py)
+needs_experiments = on_experiments_build
 
 
 def run_both(oracle, spec, impl, batch, ebn0, max_iter, seed, puncturing="", group=None):
@@ -91,8 +87,7 @@ def test_toy_all_implementations_match_oracle(oracle, toy_h, impl):
                                               ("dvbs2:R1_2short", "", 1.6),
                                               ("nr5g:2:24", "", 1.0)])
 def test_minsum_bit_exact(oracle, impl, spec, punct, ebn0):
-    if impl.startswith("HL") and spec.startswith("dvbs2"):
-        pytest.skip("layered schedule on a staircase code is a length-m serial chain (SURVEY F9)")
+    # (HL on the staircase code: a length-m serial chain of layers, SURVEY F9 -- slow, and exact like the others)
     batch = 200
     msgs, (bits, its, post), (obits, oits, opost) = run_both(oracle, spec, impl, batch, ebn0, 30, seed=11,
                                                             puncturing=punct)
