@@ -218,7 +218,8 @@ int32_t ldpc_toolbox_sim_generate(void *sim, double ebn0_db, uint64_t seed, uint
 int32_t ldpc_toolbox_sim_pool(void *sim, uint8_t *messages, uint8_t *tx_bits);
 /* "k", "n", "n_tx", "pool", "modulation", "interleaving"; "preferred_batch" (frames per run call that fill one
  * group of the decoder: 4096, more for small graphs); of the last run call: "pooled_frames" (frames that went
- * through the straggler pool, below), "streamed_frames", "stream_iterations".  returns 0 or -1. */
+ * through the straggler pool, below); "streamed_frames" and "stream_iterations" are accepted and read 0.
+ * returns 0 or -1. */
 int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value);
 /* "modulation": bits per symbol, 1 = BPSK (default), 3 = 8PSK with the DVB-S2 Gray mapping and the
  * exact max* demodulator (src/simulation/modulation.rs:144-288; n_tx must be a multiple of 3).
@@ -229,7 +230,7 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value);
  * reduced iteration budget and the frames that have not converged by then are pooled and decoded together with the
  * full budget -- per frame the result of one full-budget decode, so the counters do not depend on it; it spares every
  * chunk the nearly empty iterations its few slow frames would otherwise drag it through.
- * "streaming" (0/1, default 0): continuous batching for flooding Minsumf32 (exact, slower in this layout).
+ * "streaming" is accepted and has no effect (continuous batching measured slower than drained chunks and was removed).
  * Any other key is forwarded to the simulator's decoder (see ldpc_toolbox_decoder_set).
  * returns 0, or -1 (unknown key / unusable value, message via ldpc_toolbox_last_error). */
 int32_t ldpc_toolbox_sim_set(void *sim, const char *key, int64_t value);

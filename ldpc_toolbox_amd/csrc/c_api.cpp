@@ -402,14 +402,8 @@ int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value)
     *value = static_cast<int64_t>(d.preferred_group(size_t(1) << 20));
   else if (k == "row_records")
     *value = d.row_records();
-  else if (k == "last_persist")
-    *value = d.last_persist();
-  else if (k == "experiments")  // 1: a -DLDPC_EXPERIMENTS build (carries the opt-in forms the product left behind)
-#ifdef LDPC_EXPERIMENTS
-    *value = 1;
-#else
+  else if (k == "last_persist" || k == "experiments")  // (the removed experiment builds: always 0)
     *value = 0;
-#endif
   else
     return -1;
   return 0;
@@ -520,14 +514,12 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value) {
     *value = s->modulation();
   else if (k == "interleaving")
     *value = s->interleaving();
-  else if (k == "streamed_frames")
-    *value = static_cast<int64_t>(s->streamed_frames());
+  else if (k == "streamed_frames" || k == "stream_iterations")  // (continuous batching: profiles/r03_continuous_batching.txt)
+    *value = 0;
   else if (k == "pooled_frames")  // frames of the last run() call that went through the straggler pool
     *value = static_cast<int64_t>(s->pooled_frames());
   else if (k == "preferred_batch")  // frames per run() call that fill one group of the decoder (4096; more for small graphs)
     *value = static_cast<int64_t>(s->decoder()->preferred_group(size_t(1) << 20));
-  else if (k == "stream_iterations")
-    *value = static_cast<int64_t>(s->decoder()->last_stream_iterations());
   else
     return -1;
   return 0;
@@ -545,10 +537,7 @@ int32_t ldpc_toolbox_sim_set(void *sim, const char *key, int64_t value) {
     s->set_pooling(value != 0);
     return 0;
   }
-  if (k == "streaming") {  // 0: every chunk of 4096 frames is decoded to the end before the next starts
-    s->set_streaming(value != 0);
-    return 0;
-  }
+  if (k == "streaming") return 0;  // accepted, no effect (continuous batching: profiles/r03_continuous_batching.txt)
   if (k == "modulation" || k == "interleaving") {
     g_last_error.clear();
     const bool ok = k == "modulation" ? s->set_modulation(static_cast<int>(value)) : s->set_interleaving(value);

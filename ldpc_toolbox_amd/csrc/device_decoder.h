@@ -17,7 +17,6 @@
 
 #include <algorithm>
 #include <cstddef>
-#include <functional>
 #include <cstdint>
 #include <string>
 #include <vector>
@@ -56,8 +55,6 @@ class DeviceDecoder {
   uint32_t last_lanes() const { return last_lanes_; }
   uint64_t last_pooled() const { return last_pooled_; }   // frames of the last call that went through the straggler pool
   size_t last_group() const { return last_group_; }
-  // slice width (32 / 64 codewords) of the slice-persistent layered kernel in the last call, 0 = per-level launches
-  uint32_t last_persist() const { return last_persist_; }
   // words per check-row record when the flooding min-sum path keeps row records (kernels.hip.h,
   // cn_minsum_rec_kernel), 0 when it keeps per-edge messages
   uint32_t row_records() const { return (rec_ready_ && records_wanted() && opt_lfree_ && !opt_staged_minsum_) ? rec_w_ : 0; }
@@ -70,7 +67,7 @@ class DeviceDecoder {
   void set_min_group(size_t g) { min_group_ = g; }
   // codewords per group a call of `batch` codewords is cut into (the set value, else a default that grows for small graphs)
   size_t preferred_group(size_t batch) const { return pick_group(batch); }
-  // The 26 options of set_option (round 6; with the four experiment-only keys 30 where there were 54: the tuning knobs whose alternatives had all been measured within a
+  // The 26 options of set_option (round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
   // percent are constants now, see kStreamBlock ... below).  Results never depend on any of them; each selects between
   // forms that tests/ compare bit for bit.  returns false for an unknown key.
   //   which kernels run   "lfree" (0: plain flooding min-sum kernels), "records" (0 / 1 / 2: per-edge messages / row records
@@ -88,8 +85,7 @@ class DeviceDecoder {
   //                       host ignores the progress word), "throttle" (a call on the caller's stream may pace itself),
   //                       "pooling" (straggler pooling inside the batch entries: below)
   // plus "group_size" and "profiling" at the C ABI.  LDPC_TOOLBOX_{GROUP, WAVES, VEC, STAGED_MINSUM} set four of them at
-  // construction.  (Builds made with -DLDPC_EXPERIMENTS additionally know "rec_dbg", "lat_debug" -- timing experiments that
-  // skip stores or gathers and give WRONG results --, "hl_persist" and "hl_slice"; the product refuses them.)
+  // construction.
   bool set_option(const std::string &key, int64_t value);
   void set_profiling(bool on);
   KernelStat kernel_stat(int kind);
@@ -106,21 +102,6 @@ class DeviceDecoder {
   int decode_device(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations,
                     uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior,
                     hipStream_t stream);
-
-  // Continuous batching (the reference's workers produce frames until the stop rule fires, ber.rs:297-368): decodes
-  // a stream of `total` codewords whose LLR rows are produced on demand, keeping every slot of one group busy -- a
-  // slot whose codeword has finished is handed the next codeword of the stream at the next harvest (every few
-  // iterations), so the chip stays full until the stream ends.  Per codeword the result is exactly that of the batch
-  // entries.  source(first_count, dst, stream) must enqueue, on `stream`, kernels that read the device words
-  // first_count[0] (index of the first codeword wanted) and first_count[1] (how many, at most stream_group()) and
-  // write their LLR rows [count][input_len()] f32 to dst.  bits [total][out_len], iterations [total]: device memory.
-  // Flooding Minsumf32 with row records only (stream_capable()); synchronous.
-  bool stream_capable() const;
-  size_t stream_group() const { return 4096; }
-  uint64_t last_stream_iterations() const { return last_stream_iterations_; }  // group iterations of the last decode_stream
-  int decode_stream(const std::function<void(const uint64_t *first_count, float *dst, hipStream_t stream)> &source,
-                    float *staging, size_t total, uint32_t max_iterations, uint8_t *bits, size_t out_len,
-                    int32_t *iterations);
 
   // Same contract with host pointers: staged through device buffers group by group.
   int decode_host(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations,
@@ -179,7 +160,6 @@ class DeviceDecoder {
   uint32_t opt_latency_ = 32;
   static constexpr int kLatencyRetry = -100;  // decode_latency: redo the call with the batched kernels
   static constexpr uint32_t opt_serial_levels_default() { return 512; }
-  [[maybe_unused]] uint32_t opt_lat_debug_ = 0;  // "lat_debug" (-DLDPC_EXPERIMENTS builds only): timing probes of the small-batch kernel
   int decode_latency(const void *llrs, bool llrs_f64, bool host_pointers, size_t batch, uint32_t max_iterations,
                      uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior, hipStream_t stream);
   uint32_t lane_count() const;
@@ -237,9 +217,6 @@ class DeviceDecoder {
   uint32_t opt_rec_run_ = 8;
   static constexpr uint32_t kStreamEvents = 8, kStreamAhead = 4;
   hipEvent_t stream_events_[kStreamEvents] = {};
-  static constexpr uint32_t kStreamHarvest = 2;  // iterations between two harvests of decode_stream (experiment builds)
-  uint64_t last_stream_iterations_ = 0;
-  uint32_t opt_rec_dbg_ = 0;  // "rec_dbg": timing experiments of the record kernel (skips stores / gathers: wrong results)
   bool opt_compact_ = true;
   // schedule of the compaction checkpoints ("compact_first", "compact_every": 0 = 6 and 2 for flooding, 3 and 1 for the
   // layered schedule)
@@ -256,16 +233,6 @@ class DeviceDecoder {
   bool opt_hl_records_ = true;  // "hl_records": layered min-sum keeps a row's messages as one record (0 = per-edge R)
   std::vector<uint32_t> level_maxdeg_;
   std::vector<uint32_t> level_rec_ptr_;  // [n_levels] first word of a level's records in d_level_recs_
-  // slice-persistent layered kernel (kernels.hip.h, hl_slice_kernel; f32 Tanh rule): one launch per iteration; a
-  // workgroup owns a slice of 32 or 64 codewords and walks the dependency levels itself.  Task tables for the two slice
-  // widths ([0]: 32 codewords, two rows -- or the two halves of a long row -- per wavefront task; [1]: 64, one row).
-  // "hl_persist": 0 = one launch per level (default: round 4 measured the persistent form level with it at fixed work and
-  // behind it with early termination, profiles/r04_slice_persistent.txt), 1 / 2 = wherever the kernel can run;
-  // "hl_slice": 0 = automatic, 32 or 64
-  uint32_t *d_slice_tasks_[2] = {nullptr, nullptr}, *d_slice_task_ptr_[2] = {nullptr, nullptr};
-  [[maybe_unused]] uint32_t opt_hl_persist_ = 0, opt_hl_slice_ = 0;  // (-DLDPC_EXPERIMENTS builds)
-  [[maybe_unused]] bool slice_fits_[2] = {false, false};  // every row of the graph fits a task of that slice width
-  uint32_t last_persist_ = 0;  // slice width the last layered group ran with (0: per-level launches)
   bool lfree_ready_ = false, opt_lfree_ = true;
   std::vector<uint32_t> level_ptr_;
   // depuncture map: source block of every pattern block, -1 = punctured

@@ -110,10 +110,6 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
         aux[g.col_edge[s0 + 1]] = g.col_edge[s0];
       }
     }
-#ifdef LDPC_EXPERIMENTS
-    if (std::getenv("LDPC_DBG_VNSEQ"))  // timing experiment (wrong results): the variable-node pass reads its messages in order
-      for (size_t j = 0; j < keep_edge.size(); j++) keep_edge[j] = static_cast<uint32_t>(j);
-#endif
     if (!free_var.empty() && !keep_var.empty() && g.n_edges < dev::kAuxSingle) {
       d->n_keep_ = static_cast<uint32_t>(keep_var.size());
       d->n_free_ = static_cast<uint32_t>(free_var.size());
@@ -252,7 +248,6 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
   }
   if (ok && impl.schedule == Schedule::Layered) {
     const LevelTables lt = build_levels(g.row_ptr, g.edge_col, g.n_rows, g.n_cols);
-    [[maybe_unused]] const uint32_t n_levels = static_cast<uint32_t>(lt.maxdeg.size());
     d->level_ptr_ = lt.level_ptr;
     d->level_maxdeg_ = lt.maxdeg;
     ok = upload(lt.rows, &d->d_level_rows_);
@@ -268,17 +263,6 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
         ok = upload(build_level_recs(all, g.row_ptr, g.edge_col).words, &d->d_serial_recs_);
       }
     }
-#ifdef LDPC_EXPERIMENTS
-    // task tables of the slice-persistent kernel (kernels.hip.h, hl_slice_kernel): the Tanh rule in f32 (a row of its
-    // can be shared by two lanes; the other rules keep one launch per level for now)
-    if (ok && n_levels <= opt_serial_levels_default() && !impl.i8 && !impl.f64 && impl.rule == Rule::Tanh) {
-      for (int k = 0; ok && k < 2; k++) {
-        const SliceTasks st = build_slice_tasks(lt, g.row_ptr, g.edge_col, k == 0 ? 2u : 1u, true);
-        d->slice_fits_[k] = st.fits;
-        ok = upload(st.tasks, &d->d_slice_tasks_[k]) && upload(st.task_ptr, &d->d_slice_task_ptr_[k]);
-      }
-    }
-#endif
   }
 
   // small-batch path with a lane per edge (latency_edge.hip.h): the rows are packed, whole, into chunks of at most 64
@@ -397,9 +381,7 @@ DeviceDecoder::~DeviceDecoder() {
   for (void *p : {(void *)d_row_ptr_, (void *)d_edge_col_, (void *)d_col_ptr_, (void *)d_col_edge_,
                   (void *)d_level_rows_, (void *)d_level_recs_, (void *)d_serial_recs_, (void *)d_row_recs_, (void *)d_src_block_, (void *)d_edge_aux_, (void *)d_keep_var_,
                   (void *)d_keep_ptr_, (void *)d_keep_edge_, (void *)d_free_var_, (void *)d_free_ptr_,
-                  (void *)d_free_edge_, (void *)d_edge_peer_, (void *)d_free_rs_, (void *)d_keep_pos_,
-                  (void *)d_slice_tasks_[0], (void *)d_slice_tasks_[1], (void *)d_slice_task_ptr_[0],
-                  (void *)d_slice_task_ptr_[1]})
+                  (void *)d_free_edge_, (void *)d_edge_peer_, (void *)d_free_rs_, (void *)d_keep_pos_})
     if (p) (void)hipFree(p);
   for (auto e : stream_events_)
     if (e) (void)hipEventDestroy(e);
@@ -429,12 +411,6 @@ bool DeviceDecoder::set_option(const std::string &key, int64_t value) {
     opt_records_ = v != 0 ? (v >= 2 ? 2 : 1) : 0;  // 2: also where the graph's peers are distant rows
   else if (key == "rec_run")
     opt_rec_run_ = std::max<uint32_t>(v, 1);
-#ifdef LDPC_EXPERIMENTS
-  else if (key == "rec_dbg")
-    opt_rec_dbg_ = v;
-  else if (key == "lat_debug")
-    opt_lat_debug_ = v;
-#endif
   else if (key == "rec_quiet")
     opt_rec_quiet_ = v != 0;
   else if (key == "vn_event")
@@ -451,12 +427,6 @@ bool DeviceDecoder::set_option(const std::string &key, int64_t value) {
     opt_cn_reg_ = v;
   else if (key == "hl_records")
     opt_hl_records_ = v != 0;
-#ifdef LDPC_EXPERIMENTS  // the slice-persistent layered kernel exists in experiment builds only (round 5)
-  else if (key == "hl_persist")
-    opt_hl_persist_ = std::min<uint32_t>(v, 2);
-  else if (key == "hl_slice")
-    opt_hl_slice_ = (v == 32 || v == 64) ? v : 0;
-#endif
   else if (key == "lane_threads")
     opt_lane_threads_ = v != 0;
   else if (key == "throttle")
@@ -610,6 +580,7 @@ int DeviceDecoder::ensure_workspace(Workspace &w, size_t G, void *place, size_t 
   const size_t o_perm = carve(4 * G * sizeof(uint32_t) + 1024);
   const size_t o_raw = carve(n_ * W * sizeof(uint64_t));
   const size_t o_hard = carve(n_ * W * sizeof(uint64_t));
+  // (flags: seven rows of G words are used; the carve keeps the size the slab's layout was measured with)
   const size_t o_flags = carve(9 * G * sizeof(uint32_t) + 1024);
   if (need) {
     *need = off;
@@ -654,9 +625,6 @@ int DeviceDecoder::ensure_workspace(Workspace &w, size_t G, void *place, size_t 
   w.n_active = flags + 4 * G;
   w.scratch_flags = flags + 4 * G + 64;
   w.slice_state = flags + 6 * G;
-  w.it0 = flags + 7 * G;
-  w.holes = flags + 8 * G;
-  w.stream_plan = reinterpret_cast<dev::StreamPlan *>(flags + 9 * G + 64);
   if (std::getenv("LDPC_TOOLBOX_DEBUG"))
     std::fprintf(stderr, "ldpc_toolbox (hip): workspace G=%zu slab=%p bytes=%zu msg=+%zx post=+%zx chan=+%zx\n", G,
                  w.slab, off, o_msg, o_post, o_chan);
@@ -1373,28 +1341,6 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
   finish();
   return rc;
 }
-
-// ---- continuous batching -----------------------------------------------------------------------
-// (exact -- same counters as drained batches and the CPU checker -- and slower in this layout: 0.64-0.69 of the
-// iteration-proportional bound against 0.75-0.81, profiles/r03_continuous_batching.txt.  Since round 5 only builds with
-// -DLDPC_EXPERIMENTS carry it; in the product stream_capable() is false and the simulator's "streaming" option changes nothing.)
-bool DeviceDecoder::stream_capable() const {
-#ifdef LDPC_EXPERIMENTS
-  return impl_.schedule == Schedule::Flooding && impl_.rule == Rule::Minsum && !impl_.f64 && !impl_.i8 && rec_ready_ &&
-         lfree_ready_ && records_wanted() && opt_lfree_ && !opt_staged_minsum_;
-#else
-  return false;
-#endif
-}
-
-#ifndef LDPC_EXPERIMENTS
-int DeviceDecoder::decode_stream(const std::function<void(const uint64_t *, float *, hipStream_t)> &, float *, size_t total,
-                                 uint32_t, uint8_t *, size_t, int32_t *) {
-  if (total == 0) return 0;
-  fail("decode_stream: continuous batching is an experiment build's feature (-DLDPC_EXPERIMENTS)");
-  return -3;
-}
-#endif  // (the experiment builds' decode_stream: decode_stream.hip.h, compiled with the f32 kernels)
 
 // ---- syndrome operator ----------------------------------------------------------------------
 

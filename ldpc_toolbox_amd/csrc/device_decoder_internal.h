@@ -47,8 +47,7 @@ struct DeviceDecoder::Workspace {
   uint32_t *perm = nullptr, *slot_cw = nullptr, *slot_tmp = nullptr, *fill_cw = nullptr, *n_slots = nullptr;
   dev::CompactPlan *plan = nullptr;
   uint32_t *done = nullptr, *unsat0 = nullptr, *unsat1 = nullptr, *n_active = nullptr, *scratch_flags = nullptr,
-           *slice_state = nullptr, *it0 = nullptr, *holes = nullptr;
-  dev::StreamPlan *stream_plan = nullptr;
+           *slice_state = nullptr;
   int32_t *iters = nullptr;
   // progress word (pinned host memory, mapped into the device): kernels.hip.h, State::publish
   uint64_t *h_flag = nullptr, *d_flag = nullptr;
@@ -247,7 +246,6 @@ inline Tiling make_tiling(uint32_t G, uint32_t tile, uint32_t slice, uint32_t no
 
 // per-call launch tunables (never affect results)
 struct Knobs {
-  uint32_t rec_dbg = 0;
   bool rec_long = true;  // some row has more than 8 edges
   bool fast = false;  // "@fast" implementation: the approximate Tanh / Phi rule variants
   void *row_scratch = nullptr;  // non-null: the LDS-staged kernels keep their columns there (rows beyond the LDS)

@@ -95,22 +95,8 @@ EM_FN float fdiv_v(float a, float b) {
   return a / b;
 #endif
 }
-// per-site choice (overridable on the command line of the check tool to search for the shortest)
-#ifndef EM_FDIV_EXPM1
-#define EM_FDIV_EXPM1 2
-#endif
-#ifndef EM_FDIV_TANH
-#define EM_FDIV_TANH 2
-#endif
-#ifndef EM_FDIV_L1P_C
-#define EM_FDIV_L1P_C 4
-#endif
-#ifndef EM_FDIV_L1P_S
-#define EM_FDIV_L1P_S 2
-#endif
-#ifndef EM_FDIV_ATANH
-#define EM_FDIV_ATANH 2
-#endif
+// per-site choice
+constexpr int kFdivExpm1 = 2, kFdivTanh = 2, kFdivL1pC = 4, kFdivL1pS = 2, kFdivAtanh = 2;
 EM_FN float fdiv(float a, float b) { return fdiv_v<0>(a, b); }
 
 // glibc 2.35 sysdeps/ieee754/flt-32/e_expf.c, FMA build
@@ -273,7 +259,7 @@ EM_FN float log1pf(float x) {
   int32_t hu = static_cast<int32_t>(as_u32(u0));
   int32_t k = (hu >> 23) - 127;
   float c = (k > 0) ? 1.0f - (u0 - x) : x - (u0 - 1.0f);
-  c = fdiv_v<EM_FDIV_L1P_C>(c, u0);
+  c = fdiv_v<kFdivL1pC>(c, u0);
   hu &= 0x007fffff;
   const bool low = hu < 0x3504f7;
   k += low ? 0 : 1;
@@ -284,7 +270,7 @@ EM_FN float log1pf(float x) {
   k = direct ? 0 : k;
   c = direct ? 0.0f : c;
   const float hfsq = 0.5f * f * f;
-  const float s = fdiv_v<EM_FDIV_L1P_S>(f, 2.0f + f);
+  const float s = fdiv_v<kFdivL1pS>(f, 2.0f + f);
   const float z = s * s;
   const float R = z * (Lp1 + z * (Lp2 + z * (Lp3 + z * (Lp4 + z * (Lp5 + z * (Lp6 + z * Lp7))))));
   const float kf = static_cast<float>(k);
@@ -330,12 +316,12 @@ EM_FN float corrf(float a) {
   // 1 + y = 2 exactly (a = 0) or within 2^-20 of a power of two: the source's |f| < 2^-20 class
   if (!direct && ((hb >> 23) != 127u || hu2 == 0u)) return log1pf(y);
   float c = y - (u0 - 1.0f);
-  c = fdiv_v<EM_FDIV_L1P_C>(c, u0);
+  c = fdiv_v<kFdivL1pC>(c, u0);
   const float u = as_f32(hu | (low ? 0x3f800000u : 0x3f000000u));
   const float f = direct ? y : u - 1.0f;
   const bool kzero = direct || low;
   const float hfsq = 0.5f * f * f;
-  const float s = fdiv_v<EM_FDIV_L1P_S>(f, 2.0f + f);
+  const float s = fdiv_v<kFdivL1pS>(f, 2.0f + f);
   const float z = s * s;
   const float R = z * (Lp1 + z * (Lp2 + z * (Lp3 + z * (Lp4 + z * (Lp5 + z * (Lp6 + z * Lp7))))));
   const float r0 = f - (hfsq - s * (hfsq + R));
@@ -451,7 +437,7 @@ EM_FN float expm1f(float x) {
   const float hxs = xr * hfx;
   const float r1 = one + hxs * (Q1 + hxs * (Q2 + hxs * (Q3 + hxs * (Q4 + hxs * Q5))));
   const float t = 3.0f - r1 * hfx;
-  const float e = hxs * fdiv_v<EM_FDIV_EXPM1>(r1 - t, 6.0f - xr * t);
+  const float e = hxs * fdiv_v<kFdivExpm1>(r1 - t, 6.0f - xr * t);
   // reconstruction candidates
   const float r0 = xr - (xr * e - hxs);                                  // k == 0
   const float e2 = (xr * (e - c) - c) - hxs;
@@ -507,7 +493,7 @@ EM_FN float tanhf(float x) {
   const float hxs = xr * hfx;
   const float r1 = one + hxs * (Q1 + hxs * (Q2 + hxs * (Q3 + hxs * (Q4 + hxs * Q5))));
   const float t3 = 3.0f - r1 * hfx;
-  const float e = hxs * fdiv_v<EM_FDIV_EXPM1>(r1 - t3, 6.0f - xr * t3);
+  const float e = hxs * fdiv_v<kFdivExpm1>(r1 - t3, 6.0f - xr * t3);
   const float r0 = xr - (xr * e - hxs);                                   // k == 0
   const float e2 = (xr * (e - c) - c) - hxs;
   const float rm1 = 0.5f * (xr - e2) - 0.5f;                              // k == -1
@@ -525,7 +511,7 @@ EM_FN float tanhf(float x) {
   const float r_small = (k == 0) ? r0 : ((k == -1) ? rm1 : ya);
   float t = big ? r_big : r_small;
   t = (hx < 0x33000000u) ? arg : t;                                       // |arg| < 2^-25: expm1f returns its argument
-  const float q = fdiv_v<EM_FDIV_TANH>(big ? 2.0f : -t, t + 2.0f);
+  const float q = fdiv_v<kFdivTanh>(big ? 2.0f : -t, t + 2.0f);
   float z = big ? one - q : q;                                            // z >= +0
   z = sat ? one : z;                                                      // one - tiny
   const float r = as_f32(as_u32(z) | (jx & 0x80000000u));
@@ -562,7 +548,7 @@ EM_FN float phif(float x) {
   const float hxs = xr * hfx;
   const float r1 = one + hxs * (Q1 + hxs * (Q2 + hxs * (Q3 + hxs * (Q4 + hxs * Q5))));
   const float t3 = 3.0f - r1 * hfx;
-  const float e = hxs * fdiv_v<EM_FDIV_EXPM1>(r1 - t3, 6.0f - xr * t3);
+  const float e = hxs * fdiv_v<kFdivExpm1>(r1 - t3, 6.0f - xr * t3);
   const float r0 = xr - (xr * e - hxs);
   const float e2 = (xr * (e - c) - c) - hxs;
   const float rm1 = 0.5f * (xr - e2) - 0.5f;
@@ -580,7 +566,7 @@ EM_FN float phif(float x) {
   const float r_small = (k == 0) ? r0 : ((k == -1) ? rm1 : ya);
   float t = big ? r_big : r_small;
   t = (hx < 0x33000000u) ? arg : t;
-  const float q = fdiv_v<EM_FDIV_TANH>(big ? 2.0f : -t, t + 2.0f);
+  const float q = fdiv_v<kFdivTanh>(big ? 2.0f : -t, t + 2.0f);
   float th = big ? one - q : q;
   th = sat ? one : th;
   // logf(th), th normal in (0, 1]
@@ -633,7 +619,7 @@ EM_FN float tanhf_c9(float x) {
   const float hxs = xr * hfx;
   const float r1 = one + hxs * (Q1 + hxs * (Q2 + hxs * (Q3 + hxs * (Q4 + hxs * Q5))));
   const float t3 = 3.0f - r1 * hfx;
-  const float e = hxs * fdiv_v<EM_FDIV_EXPM1>(r1 - t3, 6.0f - xr * t3);
+  const float e = hxs * fdiv_v<kFdivExpm1>(r1 - t3, 6.0f - xr * t3);
   const float r0 = xr - (xr * e - hxs);                                   // k == 0
   const float e2 = (xr * (e - c) - c) - hxs;
   const float rm1 = 0.5f * (xr - e2) - 0.5f;                              // k == -1
@@ -650,7 +636,7 @@ EM_FN float tanhf_c9(float x) {
   const float r_small = (k == 0) ? r0 : ((k == -1) ? rm1 : ya);
   float t = big ? r_big : r_small;
   t = (hx < 0x33000000u) ? arg : t;                                       // |arg| < 2^-25: expm1f returns its argument
-  const float q = fdiv_v<EM_FDIV_TANH>(big ? 2.0f : -t, t + 2.0f);
+  const float q = fdiv_v<kFdivTanh>(big ? 2.0f : -t, t + 2.0f);
   const float z = big ? one - q : q;                                      // z >= +0
   return as_f32(as_u32(z) | (jx & 0x80000000u));
 }
@@ -661,11 +647,11 @@ EM_FN float atanh_rs(float x) {
   // +-1, beyond, NaN: IEEE division
   if (!(__builtin_fabsf(x) < 1.0f)) return 0.5f * log1pf((2.0f * x) / (1.0f - x));
   // +-0: the quotient is the argument itself (the short sequence would lose the sign of a zero quotient)
-  const float q = fdiv_v<EM_FDIV_ATANH>(2.0f * x, 1.0f - x);
+  const float q = fdiv_v<kFdivAtanh>(2.0f * x, 1.0f - x);
   return 0.5f * log1pf((x == 0.0f) ? x : q);
 }
 
-// atanh_rs without its rare classes, for callers that unroll it many times (the slice-persistent layered kernel): one
+// atanh_rs without its rare classes, for callers that unroll it many times (round 4's slice-persistent layered kernel): one
 // straight line of selects.  *rare is set for the arguments this line does not cover -- NaN or |x| >= 1, a quotient
 // 2x / (1 - x) at or below -1 or beyond log1pf's huge class, and log1pf's "reduced argument within 2^-20 of a power of
 // two" class -- and the caller then takes atanh_rs(x) instead (the value returned here is unspecified).  log1pf's tiny
@@ -677,7 +663,7 @@ EM_FN float atanh_rs_main(float x, bool *rare) {
   const float Lp1 = 6.6666668653e-01f, Lp2 = 4.0000000596e-01f, Lp3 = 2.8571429849e-01f,
               Lp4 = 2.2222198546e-01f, Lp5 = 1.8183572590e-01f, Lp6 = 1.5313838422e-01f,
               Lp7 = 1.4798198640e-01f;
-  const float q = fdiv_v<EM_FDIV_ATANH>(2.0f * x, 1.0f - x);
+  const float q = fdiv_v<kFdivAtanh>(2.0f * x, 1.0f - x);
   const float a = (x == 0.0f) ? x : q;  // log1pf's argument
   const int32_t hx = static_cast<int32_t>(as_u32(a));
   const int32_t ax = hx & 0x7fffffff;
@@ -688,7 +674,7 @@ EM_FN float atanh_rs_main(float x, bool *rare) {
   int32_t hu = static_cast<int32_t>(as_u32(u0));
   int32_t k = (hu >> 23) - 127;
   float c = (k > 0) ? 1.0f - (u0 - a) : a - (u0 - 1.0f);
-  c = fdiv_v<EM_FDIV_L1P_C>(c, u0);
+  c = fdiv_v<kFdivL1pC>(c, u0);
   hu &= 0x007fffff;
   const bool low = hu < 0x3504f7;
   k += low ? 0 : 1;
@@ -699,7 +685,7 @@ EM_FN float atanh_rs_main(float x, bool *rare) {
   k = direct ? 0 : k;
   c = direct ? 0.0f : c;
   const float hfsq = 0.5f * f * f;
-  const float s = fdiv_v<EM_FDIV_L1P_S>(f, 2.0f + f);
+  const float s = fdiv_v<kFdivL1pS>(f, 2.0f + f);
   const float z = s * s;
   const float R = z * (Lp1 + z * (Lp2 + z * (Lp3 + z * (Lp4 + z * (Lp5 + z * (Lp6 + z * Lp7))))));
   const float kf = static_cast<float>(k);

@@ -23,21 +23,9 @@
 #include "exact_math.h"
 #include "fast_div.h"
 
-// Timing-experiment switches (skip stores / gathers: WRONG results) exist only in builds made with
-// EXTRA_HIPFLAGS=-DLDPC_EXPERIMENTS (tools/records_ab.py, tools/latency_probe.py); the product carries neither the
-// kernel parameter nor the tests on it.
-#ifdef LDPC_EXPERIMENTS
-#define LDPC_DBG_PARAM(name) , uint32_t name
-#define LDPC_DBG_ARG(x) , x
-#else
-#define LDPC_DBG_PARAM(name)
-#define LDPC_DBG_ARG(x)
-#endif
-
 // The kernels, by schedule.  Every translation unit of the library includes this header (device_decoder_internal.h); a kernel is
 // compiled where it is launched: the float rules in run_group_f32.hip / run_group_f64.hip, the group kernels in device_decoder.hip.
 #include "kernels_common.hip.h"
 #include "kernels_flooding.hip.h"
 #include "kernels_layered.hip.h"
 #include "kernels_group.hip.h"
-#include "kernels_experiments.hip.h"

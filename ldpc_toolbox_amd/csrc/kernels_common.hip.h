@@ -171,7 +171,7 @@ struct State {
   // 1 = the first ones just have (vn_kernel sets it; vn_free_rec_kernel's event mode rebuilds their L-free
   // posteriors from the records), 2 = stored by the check-node kernel every iteration from now on
   uint32_t *slice_state;
-  // Continuous batching (DeviceDecoder::decode_stream), or null: the group never drains -- a slot whose codeword
+  // Continuous batching (no longer built: profiles/r03_continuous_batching.txt), else null: the group never drains -- a slot whose codeword
   // has finished is handed a fresh one at the next harvest -- so every slot counts its own iterations:
   // it0[slot] = group iterations completed when the slot's codeword started, max_it = the per-codeword limit
   const uint32_t *it0;
@@ -200,30 +200,17 @@ __device__ __forceinline__ double m_min(double a, double b) { return fmin(a, b);
 __device__ __forceinline__ float m_max(float a, float b) { return fmaxf(a, b); }
 __device__ __forceinline__ double m_max(double a, double b) { return fmax(a, b); }
 // transcendentals: glibc-identical (exact_math.h) in both precisions, so every rule matches the CPU bit for bit
-#ifdef LDPC_TRIVIAL_MATH
-// measurement builds only (tools/ab_variants.sh): the rules' structure with the f32 functions replaced by
-// one multiplication each, to read the kernels' instruction count and time WITHOUT the functions.  Wrong results.
-__device__ __forceinline__ float m_tanh(float x) { return 0.25f * x; }
-__device__ __forceinline__ float m_log(float x) { return 0.5f * x; }
-__device__ __forceinline__ float m_exp(float x) { return 0.5f * x; }
-__device__ __forceinline__ float m_log1p(float x) { return 0.5f * x; }
-#else
 __device__ __forceinline__ float m_tanh(float x) { return em::tanhf(x); }
 __device__ __forceinline__ float m_log(float x) { return em::logf(x); }
 __device__ __forceinline__ float m_exp(float x) { return em::expf(x); }
 __device__ __forceinline__ float m_log1p(float x) { return em::log1pf(x); }
-#endif
 __device__ __forceinline__ double m_tanh(double x) { return em::tanh(x); }
 __device__ __forceinline__ double m_log(double x) { return em::log(x); }
 __device__ __forceinline__ double m_exp(double x) { return em::exp(x); }
 __device__ __forceinline__ double m_log1p(double x) { return em::log1p(x); }
 // ln_1p(exp(-a)), a >= 0: the min* correction term (f32: the fused form)
 __device__ __forceinline__ double m_corr(double a) { return m_log1p(m_exp(-a)); }
-#ifdef LDPC_TRIVIAL_MATH
-__device__ __forceinline__ float m_corr(float a) { return 0.25f * a; }
-#else
 __device__ __forceinline__ float m_corr(float a) { return em::corrf(a); }
-#endif
 
 template <typename T>
 struct Limits;
@@ -250,33 +237,21 @@ __device__ __forceinline__ T phi_fn(T x) {
   x = m_max(x, Limits<T>::phi_min_x);
   return -(m_log(m_tanh(T(0.5) * x)));
 }
-#ifndef LDPC_TRIVIAL_MATH
 // the fused forms (exact_math.h): the same operations per lane, one straight line instead of three functions' branches
 template <>
 __device__ __forceinline__ float phi_fn<float>(float x) {
   return em::phif(x);
 }
-#ifndef LDPC_GENERIC_PHI64  // (A/B builds: -DLDPC_GENERIC_PHI64 keeps -log(tanh(.)) as three calls, round 5's form)
 template <>
 __device__ __forceinline__ double phi_fn<double>(double x) {
   return em::phi(x);
 }
-#endif
-#endif
 
 // Rust std atanh: 0.5 * ln_1p(2x / (1 - x))
 // tanh of an argument the Tanh rule has clamped to +-tanh_clamp: f32 takes the branch-free form
 __device__ __forceinline__ double m_tanh_clamped(double x) { return m_tanh(x); }
-#if defined(LDPC_TRIVIAL_MATH) || defined(LDPC_GENERIC_TANH)
-__device__ __forceinline__ float m_tanh_clamped(float x) { return m_tanh(x); }
-#else
 __device__ __forceinline__ float m_tanh_clamped(float x) { return em::tanhf_c9(x); }
-#endif
-#ifdef LDPC_TRIVIAL_MATH
-__device__ __forceinline__ float atanh_rs(float x) { return 0.5f * x; }
-#else
 __device__ __forceinline__ float atanh_rs(float x) { return em::atanh_rs(x); }
-#endif
 __device__ __forceinline__ double atanh_rs(double x) { return 0.5 * m_log1p((2.0 * x) / (1.0 - x)); }
 // 2 atanh(p) as the Tanh rule forms it (arithmetic.rs:376).  (The straight-line atanh of the slice kernel --
 // exact_math.h, atanh_rs_main, rare arguments redone per wavefront -- was tried here too, where the function is

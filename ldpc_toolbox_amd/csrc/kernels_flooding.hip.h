@@ -338,11 +338,7 @@ enum : uint32_t { kPeerKeep = 0x80000000u, kPeerPosMask = 0x7FFFFFFFu, kPeerWrit
 // behind it -- at least one wait state behind the store -- wherever the scheduler moves things.  The build checks the
 // result in the code object itself (tools/mb/store_hazard_scan.py, `make lint`, tests/test_isa_lint.py).
 typedef uint32_t store_u32x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void store_data_pad(const store_u32x4 &data) {
-#ifndef LDPC_NO_STORE_PAD
-  asm volatile("s_nop 0" ::"v"(data));
-#endif
-}
+__device__ __forceinline__ void store_data_pad(const store_u32x4 &data) { asm volatile("s_nop 0" ::"v"(data)); }
 
 // [row][tile] accesses of a whole Pack through a buffer descriptor: SGPR row offset, one constant VGPR lane offset
 template <typename T, int VEC, bool NT>
@@ -401,11 +397,6 @@ struct RowRec {
   }
 };
 
-#ifdef LDPC_REC_WAVES
-#define LDPC_REC_OCC __attribute__((amdgpu_waves_per_eu(LDPC_REC_WAVES, 8)))
-#else
-#define LDPC_REC_OCC
-#endif
 // U: edges of a row whose data loads are issued together with the next record's (rows longer than U take
 // further rounds); the graph tables must be padded by U entries (the index fetch of a row reads U of them).
 // Wavefronts walk runs of `run` consecutive rows, even runs upwards and odd runs downwards: the two records at
@@ -417,12 +408,9 @@ struct RowRec {
 // LONG: some row has more than U edges (further rounds of U loads; compiled out otherwise: the extra code costs the
 // short-row case 2 % in registers and scheduling).
 template <typename T, int VEC, int RECW, int U, bool FIRST, bool NT, bool STREAM = false, bool LONG = true>
-__global__ __launch_bounds__(256) LDPC_REC_OCC void cn_minsum_rec_kernel(
+__global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     Graph g, Sched sc, State st, const T *__restrict__ chan, T *__restrict__ post, const T *__restrict__ rec_in,
-    T *__restrict__ rec_out, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t run LDPC_DBG_PARAM(dbg)) {
-#ifndef LDPC_EXPERIMENTS
-  constexpr uint32_t dbg = 0;
-#endif
+    T *__restrict__ rec_out, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t run) {
   typedef typename RecWord<T>::type W;
   if (group_finished(st)) return;  // (publishes the progress word when the launch carries one: a paced host follows it)
   const TablePtr row_ptr = table_ptr(g.row_ptr);
@@ -459,7 +447,7 @@ __global__ __launch_bounds__(256) LDPC_REC_OCC void cn_minsum_rec_kernel(
     write_post = st.slice_state[chunk];
     if (write_post == 1 && node0 == 0 && lane == 0) st.slice_state[chunk] = 2;
   }
-  if (FIRST || (dbg & 8u)) write_post = 0;
+  if (FIRST) write_post = 0;
   // the wavefront's slice of every [row][tile] array behind a buffer descriptor: a row access is an SGPR offset
   const uint32_t row_bytes = tile * uint32_t(sizeof(T)), lane_off = lane * uint32_t(VEC * sizeof(T));
   const uint32_t in_tile = in_tile_of(b0, sc) * uint32_t(sizeof(T));
@@ -506,7 +494,7 @@ __global__ __launch_bounds__(256) LDPC_REC_OCC void cn_minsum_rec_kernel(
       for (int u = 0; u < U; u++)
         if (uint32_t(u) < d)
           lv[u] = buf_load<T, VEC, false>((peers[u] & kPeerKeep) ? b_post : b_chan, lane_off,
-                                          ((dbg & 4u) ? uint32_t(u) : cols[u]) * row_bytes);
+                                          cols[u] * row_bytes);
       // the next row's indices and the range of the row after it: scalar loads that complete while this row's
       // data is in flight
       uint32_t nne0 = 0, nne1 = 0, ncols[U], npeers[U];
@@ -638,13 +626,10 @@ __global__ __launch_bounds__(256) LDPC_REC_OCC void cn_minsum_rec_kernel(
         // differed from run to run.  Round 5 found why -- the gfx950 store-data hazard described at store_data_pad above, a
         // `v_and_b32 v2, ...` issued right behind `buffer_store_dwordx4 v[0:3], ...` -- so the condition is gone: every 128-bit
         // buffer store carries its pad and the build lints the code object.)
-#ifdef LDPC_EXPERIMENTS
-        if (!(dbg & 2u))
-#endif
         out.template store<NT>(b_rout, lane_off, c * rec_bytes, row_bytes);
         // per-edge messages for the variables the variable-node kernel walks, at the position it reads them from
         auto send = [&](uint32_t slot, uint32_t peer) {
-          if (!(peer & kPeerKeep) || (dbg & 1u)) return;  // wave-uniform
+          if (!(peer & kPeerKeep)) return;  // wave-uniform
           Pack<T, VEC> o;
 #pragma unroll
           for (int k = 0; k < VEC; k++) o.v[k] = out.value(slot, k);

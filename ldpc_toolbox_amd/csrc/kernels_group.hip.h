@@ -500,26 +500,6 @@ __global__ void compact_commit_kernel(State st, const CompactPlan *plan, uint32_
 }
 #endif  // LDPC_GROUP_KERNELS_TU
 
-// ---------------------------------------------------------------------------------------
-// Continuous batching (DeviceDecoder::decode_stream; the reference's workers produce frames until the stop rule
-// fires, /root/reference/src/simulation/ber.rs:297-368, 522-531).  The group never drains: every `harvest`
-//   emit    (retire_only) writes the results of the finished codewords to the caller's rows
-//   plan    lists the free slots (finished codewords and slots never filled) and hands the next codewords of
-//           the stream to them, as many as are left; publishes the progress for the host
-//   source  (the caller's kernels) produces those codewords' LLR rows in a staging buffer
-//   ingest  moves the rows into the freed slots' columns of chan / post and restarts the slots' state
-// A refilled slot needs no other preparation: its first check-node pass reads no messages (STREAM).
-// ---------------------------------------------------------------------------------------
-struct StreamPlan {
-  uint64_t first;      // index of the first codeword handed out by this harvest (what the source kernels read, with count)
-  uint64_t count;      // codewords handed out by this harvest
-  uint64_t next;       // codewords handed out so far
-  uint64_t retired;    // codewords whose results have been written
-  uint64_t total;      // codewords of the stream
-  uint32_t always;     // = 1: the flag emit_kernel's retire mode looks at
-  uint32_t pad;
-};
-
 #ifdef LDPC_GROUP_KERNELS_TU  // straggler pooling of the batch entries (DeviceDecoder::decode_device_pooled): three small kernels
 // Iteration counts of a chunk -> the call's statistics and the indices of the chunk's stragglers.
 //   stats[0] += frames that converged, stats[1] += frames that failed with the FULL budget, stats[2] = stragglers so far

@@ -16,21 +16,15 @@ namespace dev {
 // ---------------------------------------------------------------------------------------
 // (f64: launched with at most 256 threads; telling the compiler so lifts its register cap from 128, where the 24-edge
 // register-resident variants spilled up to 65 registers to scratch.  f32 keeps the default bound: its variants fit.)
-#ifndef LDPC_HL_BOUNDS
 #define LDPC_HL_BOUNDS(T) __launch_bounds__(sizeof(T) == 8 ? 256 : 1024)
 // (register-resident f32 rows of at most 10 edges: 8 waves per SIMD asked for -- 64 registers -- where the compiler by
 // itself stops at 67-71 and 7 waves: config 3 35.2k -> 35.9k cw/s fixed work, 328k -> 340k at +2 dB, HLPhif32 +2 %.
 // Aminstar and Minstarapprox would spill for no gain (Minstarapprox: 0.211 -> 0.195 of the roofline) and keep the
 // compiler's choice, as do the 12-edge variants (up to 17 registers spilled at 64; no BASELINE graph has such levels).
-// A 20-edge bucket at 5-6 waves measured equal to the 24-edge one.
-// Experiment switch: -DLDPC_HL_REG_WAVES=1 restores the compiler's choice everywhere.)
-#ifndef LDPC_HL_REG_WAVES
-#define LDPC_HL_REG_WAVES 8
-#endif
+// A 20-edge bucket at 5-6 waves measured equal to the 24-edge one.)
 #define LDPC_HL_REG_BOUNDS(RULE, T, DMAX)                               \
   __launch_bounds__(sizeof(T) == 8 ? 256 : (DMAX <= 12 ? 256 : 1024),   \
-                    (sizeof(T) == 4 && DMAX <= 10 && RULE != kRuleAminstar && RULE != kRuleMinstarapprox) ? LDPC_HL_REG_WAVES : 1)
-#endif
+                    (sizeof(T) == 4 && DMAX <= 10 && RULE != kRuleAminstar && RULE != kRuleMinstarapprox) ? 8 : 1)
 // (SCRATCH: as in cn_staged_kernel -- rows beyond the LDS take per-wavefront columns in HBM)
 template <int RULE, typename T, bool FIRST, bool SCRATCH = false>
 __global__ LDPC_HL_BOUNDS(T) void hl_level_kernel(Graph g, Sched sc, State st, const uint32_t *__restrict__ level_rows,
@@ -192,13 +186,6 @@ __global__ LDPC_HL_REG_BOUNDS(RULE, T, DMAX) void hl_level_reg_kernel(Graph g, S
     if constexpr (kRecVecs == 2) w1 = recs[idx * kRecVecs + 1];
     const uint32_t d = w0[1];
     if (d == 0) continue;
-#ifdef LEVEL_EXP  // timing experiments only (tools/ab_variants.sh): 8 = every row reads the tile's first rows (cache hits)
-    if (LEVEL_EXP & 8) {
-#pragma unroll
-      for (int i = 0; i < DMAX; i++) (i + 2 < 16 ? w0[(i + 2) & 15] : w1[(i + 2) & 15]) = uint32_t(i);
-      w0[0] = 0;
-    }
-#endif
     const uint32_t roff = w0[0] * row_bytes;
     T q[DMAX], r[DMAX];
     for_slots<DMAX>(d, [&](auto slot) {
@@ -217,11 +204,8 @@ __global__ LDPC_HL_REG_BOUNDS(RULE, T, DMAX) void hl_level_reg_kernel(Graph g, S
       asm volatile("" : "+s"(idx2));
       u32x16 u0 = recs[idx2 * kRecVecs], u1 = u0;
       if constexpr (kRecVecs == 2) u1 = recs[idx2 * kRecVecs + 1];
-#ifdef LEVEL_EXP  // (8: and the stores go out of the buffers' range)
-      const uint32_t sbase = (LEVEL_EXP & 8) ? 0x80000000u : 0u;
-#else
+      // (the store offsets keep the form `0 + offset`: without it the compiler assigns some registers differently)
       constexpr uint32_t sbase = 0;
-#endif
       for_slots<DMAX>(d, [&](auto slot) {
         constexpr int i = decltype(slot)::value;
         const T o = out[i * S];
@@ -242,10 +226,7 @@ __global__ LDPC_HL_REG_BOUNDS(RULE, T, DMAX) void hl_level_reg_kernel(Graph g, S
 // the row's posterior and message values loaded in one burst through buffer descriptors, a straight-line block per degree.
 // Same arithmetic per row as cn_staged_kernel (flooding.rs:95-127): x_i = L - c2v_old (the channel value in the first
 // iteration), parity of the hard decisions, rule, new messages.
-#ifndef LDPC_CN_REG_WAVES
-#define LDPC_CN_REG_WAVES 8
-#endif
-#define LDPC_CN_REG_BOUNDS(T, DMAX) __launch_bounds__(256, (sizeof(T) == 4 && DMAX <= 10) ? LDPC_CN_REG_WAVES : 1)
+#define LDPC_CN_REG_BOUNDS(T, DMAX) __launch_bounds__(256, (sizeof(T) == 4 && DMAX <= 10) ? 8 : 1)
 template <int RULE, typename T, int DMAX, bool FIRST>
 __global__ LDPC_CN_REG_BOUNDS(T, DMAX) void cn_reg_kernel(Graph g, Sched sc, State st, const uint32_t *__restrict__ row_recs,
                               const T *__restrict__ L, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t dmax) {

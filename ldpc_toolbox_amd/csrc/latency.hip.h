@@ -68,59 +68,24 @@ struct LatencyState {  // 8 codeword slots (one per XCD) carved from one allocat
   size_t slot_bytes, off_post, off_msg, off_rawhard;
 };
 
-// Experiment switches (tools/ab_variants.sh builds; the defaults are what ships):
-//   LAT_LOAD_MODE  0 nontemporal loads, 1 agent-scope (sc1) loads, 2 plain loads (L1-cached: NOT coherent, timing only)
-//   LAT_SYNC_SCOPE the scope of the barrier's add and of the flag stores.  Workgroup scope = no sc1 bit: the
-//                  read-modify-write is still performed in the XCD's L2 (never in an L1) and the line stays
-//                  there, where the polls -- always sc1 loads, which bypass the L1 -- find it: 1.35 us per
-//                  barrier against 2.3 us with agent-scope adds, whose lines leave the L2 (measured,
-//                  tools/latency_probe.py).  Valid because every participant of a barrier is on ONE XCD.
-#ifndef LAT_LOAD_MODE
-#define LAT_LOAD_MODE 0
-#endif
-#ifndef LAT_SYNC_SCOPE
-#define LAT_SYNC_SCOPE __HIP_MEMORY_SCOPE_WORKGROUP
-#endif
+// The barrier's add and the flag stores have workgroup scope.  Workgroup scope = no sc1 bit: the read-modify-write is
+// still performed in the XCD's L2 (never in an L1) and the line stays there, where the polls -- always sc1 loads, which
+// bypass the L1 -- find it: 1.35 us per barrier against 2.3 us with agent-scope adds, whose lines leave the L2
+// (measured).  Valid because every participant of a barrier is on ONE XCD.
+constexpr int kLatSyncScope = __HIP_MEMORY_SCOPE_WORKGROUP;
 // every spin is bounded (some 50 ms): a barrier that cannot complete -- workgroups of the grid that do not
 // become resident because something else holds the CUs -- ends the kernel with LatencySync::error set instead
 // of hanging the device, and the host redoes the call with the batched kernels
 #define LAT_SPIN_LIMIT (1u << 16)
 
 __device__ __forceinline__ float lat_load(const float *p) {
-#if LAT_LOAD_MODE == 0
   return __builtin_nontemporal_load(p);  // bypasses the CU's L1: served by the XCD's L2
-#elif LAT_LOAD_MODE == 1
-  return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#else
-  return *p;
-#endif
 }
-__device__ __forceinline__ uint32_t lat_load(const uint8_t *p) {
-#if LAT_LOAD_MODE == 2
-  return *p;
-#else
-  return __builtin_nontemporal_load(p);
-#endif
-}
+__device__ __forceinline__ uint32_t lat_load(const uint8_t *p) { return __builtin_nontemporal_load(p); }
 
 // Buffer addressing for the per-codeword arrays: a wave-uniform descriptor (SGPRs) + a 32-bit byte offset per
 // lane, so a gather costs one VGPR and no 64-bit address arithmetic.  Loads carry the nontemporal bit (aux 2)
 // like lat_load; stores are plain (write-through to the L2).
-#ifdef LAT_NO_BUFFER  // bisecting aid: the same accessors over plain global pointers
-struct LatBuf {
-  char *p;
-};
-__device__ __forceinline__ LatBuf lat_buf(const void *p, uint32_t) { return LatBuf{const_cast<char *>(static_cast<const char *>(p))}; }
-__device__ __forceinline__ float lat_bload(const LatBuf &b, uint32_t byte_off, uint32_t soff = 0) {
-  return __builtin_nontemporal_load(reinterpret_cast<const float *>(b.p + byte_off + soff));
-}
-__device__ __forceinline__ uint32_t lat_bload_u8(const LatBuf &b, uint32_t byte_off) {
-  return __builtin_nontemporal_load(reinterpret_cast<const uint8_t *>(b.p + byte_off));
-}
-__device__ __forceinline__ void lat_bstore(const LatBuf &b, uint32_t byte_off, uint32_t soff, float v) {
-  *reinterpret_cast<float *>(b.p + byte_off + soff) = v;
-}
-#else
 struct LatBuf {
   __amdgpu_buffer_rsrc_t r;
 };
@@ -132,11 +97,7 @@ __device__ __forceinline__ LatBuf lat_buf(const void *p, uint32_t bytes) {
   return LatBuf{__builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<void *>(u), 0, static_cast<int>(bytes), 0x00020000)};
 }
 __device__ __forceinline__ float lat_bload(const LatBuf &b, uint32_t byte_off, uint32_t soff = 0) {
-#if LAT_LOAD_MODE == 2
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b.r, byte_off, soff, 0));
-#else
   return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(b.r, byte_off, soff, 2));
-#endif
 }
 __device__ __forceinline__ uint32_t lat_bload_u8(const LatBuf &b, uint32_t byte_off) {
   return __builtin_amdgcn_raw_buffer_load_b8(b.r, byte_off, 0, 2);
@@ -144,14 +105,13 @@ __device__ __forceinline__ uint32_t lat_bload_u8(const LatBuf &b, uint32_t byte_
 __device__ __forceinline__ void lat_bstore(const LatBuf &b, uint32_t byte_off, uint32_t soff, float v) {
   __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, v), b.r, byte_off, soff, 0);
 }
-#endif
 
 // polls always bypass the L1 (agent scope: an sc1 load, served by the L2 or beyond)
 __device__ __forceinline__ uint32_t lat_atomic_load(const uint32_t *p) {
   return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 __device__ __forceinline__ void lat_atomic_store(uint32_t *p, uint32_t v) {
-  __hip_atomic_store(p, v, __ATOMIC_RELAXED, LAT_SYNC_SCOPE);
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, kLatSyncScope);
 }
 // returns false when the spin ran out (and stays false: `*dead` short-cuts every later spin of this thread)
 __device__ __forceinline__ void lat_spin_until(const uint32_t *p, uint32_t target, uint32_t *error, bool *dead) {
@@ -186,7 +146,7 @@ __device__ __forceinline__ bool xcd_barrier(uint64_t (*shards)[16], uint32_t cou
     const uint32_t lane = threadIdx.x;
     if (lane == 0)
       __hip_atomic_fetch_add(&shards[slot & 7u][0], uint64_t(1) | (any ? (uint64_t(1) << (32 + 16 * parity)) : 0),
-                             __ATOMIC_RELAXED, LAT_SYNC_SCOPE);
+                             __ATOMIC_RELAXED, kLatSyncScope);
     // lane k < 8 watches shard k: complete when it has seen passed * (workgroups reporting to it) arrivals
     const uint32_t mine = lane < 8 ? (count + 7u - lane) / 8u : 0u;
     const uint32_t target = epoch->passed * mine;
@@ -329,11 +289,7 @@ template <bool FIRST, bool WRITE>
 __device__ __forceinline__ uint32_t latency_cn_phase(const LatencyTables &g, const LatArrays &A, uint32_t w0, uint32_t nwaves,
                                                      uint32_t lane, const LatRowCache &rc) {
   uint32_t odd = 0;
-#ifdef LAT_NO_CACHE
-  if (w0 < g.n_rslices) odd |= latency_cn_any<FIRST, WRITE>(g, A, rc.e0, rc.width, rc.deg, lane, nullptr);
-#else
   if (w0 < g.n_rslices) odd |= latency_cn_any<FIRST, WRITE>(g, A, rc.e0, rc.width, rc.deg, lane, &rc);
-#endif
   for (uint32_t sl = w0 + nwaves; sl < g.n_rslices; sl += nwaves) {
     const uint32_t e0 = lat_uniform(g.rslice_ptr[sl]), width = lat_uniform((g.rslice_ptr[sl + 1] - e0) >> 6);
     const uint32_t d = g.rdeg[sl * 64 + lane];
@@ -393,17 +349,6 @@ __device__ __forceinline__ float latency_vn_any(const LatencyTables &g, const La
 __device__ __forceinline__ void latency_vn_phase(const LatencyTables &g, const float *__restrict__ chan, const LatBuf &msg,
                                                  float *__restrict__ post, uint32_t w0, uint32_t nwaves, uint32_t lane,
                                                  const LatVarCache (&vc)[2]) {
-#ifdef LAT_NO_CACHE
-#pragma unroll
-  for (uint32_t i = 0; i < 2; i++) {
-    const uint32_t sl = w0 + i * nwaves;
-    if (sl < g.n_vslices) {
-      const uint32_t v = sl * 64 + lane;
-      const float s = latency_vn_any(g, msg, vc[i].k0, vc[i].width, vc[i].deg, lane, nullptr);
-      if (v < g.n) post[v] = vc[i].chan + s;
-    }
-  }
-#else
   float ms[2][8];
 #pragma unroll
   for (uint32_t i = 0; i < 2; i++) {
@@ -434,7 +379,6 @@ __device__ __forceinline__ void latency_vn_phase(const LatencyTables &g, const f
       if (v < g.n) post[v] = vc[i].chan + s;
     }
   }
-#endif
   for (uint32_t sl = w0 + 2 * nwaves; sl < g.n_vslices; sl += nwaves) {
     const uint32_t k0 = lat_uniform(g.vslice_ptr[sl]), width = lat_uniform((g.vslice_ptr[sl + 1] - k0) >> 6);
     const uint32_t v = sl * 64 + lane;
@@ -451,14 +395,7 @@ __global__ __launch_bounds__(1024) void latency_minsum_kernel(LatencyTables g, L
                                                               uint32_t input_len, uint32_t batch, uint32_t max_iterations,
                                                               uint8_t *__restrict__ bits, uint32_t out_len,
                                                               int32_t *__restrict__ iterations,
-                                                              SrcT *__restrict__ posterior, uint32_t *error_word LDPC_DBG_PARAM(debug_skip)) {
-#ifndef LDPC_EXPERIMENTS
-  constexpr uint32_t debug_skip = 0;
-#endif
-  // debug_skip (tools/latency_probe.py only; results are wrong when non-zero): bit 0 skips the check-node
-  // work, bit 1 the variable-node work, bit 2 the check-node phase's message stores, bit 3 redirects the
-  // posterior stores to a scratch row -- to time what is left (barriers are never skipped: a workgroup that
-  // ran ahead would take another exit and strand the others)
+                                                              SrcT *__restrict__ posterior, uint32_t *error_word) {
   __shared__ uint32_t s_slot, s_count, s_rank, s_nx;
   const uint32_t xcc = __builtin_amdgcn_s_getreg((3 << 11) | 20) & 7u;  // HW_REG_XCC_ID[3:0]
   if (threadIdx.x == 0) {
@@ -548,13 +485,12 @@ __global__ __launch_bounds__(1024) void latency_minsum_kernel(LatencyTables g, L
       const bool first = it == 1, last = it == max_iterations + 1;
       // check nodes: messages of iteration `it` (not when `last`) and the parity of the previous posterior's
       // hard decisions over every row (the raw input's when `first`)
-      uint32_t odd = 1;
-      if (debug_skip & 1u) {
-      } else if (first)
-        odd = (last || (debug_skip & 4u)) ? latency_cn_phase<true, false>(g, a_first, w0, nwaves, lane, rc)
+      uint32_t odd;
+      if (first)
+        odd = last ? latency_cn_phase<true, false>(g, a_first, w0, nwaves, lane, rc)
                    : latency_cn_phase<true, true>(g, a_first, w0, nwaves, lane, rc);
       else
-        odd = (last || (debug_skip & 4u)) ? latency_cn_phase<false, false>(g, a_iter, w0, nwaves, lane, rc)
+        odd = last ? latency_cn_phase<false, false>(g, a_iter, w0, nwaves, lane, rc)
                    : latency_cn_phase<false, true>(g, a_iter, w0, nwaves, lane, rc);
       const bool converged = !xcd_barrier(bar, count, my_slot, &epoch, error_word, odd);  // no row anywhere is odd
       if (converged) {
@@ -562,7 +498,7 @@ __global__ __launch_bounds__(1024) void latency_minsum_kernel(LatencyTables g, L
         break;
       }
       if (last) break;
-      if (!(debug_skip & 2u)) latency_vn_phase(g, chan, b_msg, (debug_skip & 8u) ? post + g.n + 64 : post, w0, nwaves, lane, vc);
+      latency_vn_phase(g, chan, b_msg, post, w0, nwaves, lane, vc);
       xcd_barrier(bar, count, my_slot, &epoch, error_word);
     }
 

@@ -97,12 +97,12 @@ int DeviceDecoder::decode_latency(const void *llrs, bool llrs_f64, bool host_poi
     dev::latency_minsum_kernel<double><<<grid, 1024, 0, s>>>(t, lp.slots, lp.d_sync, static_cast<const double *>(d_llrs),
                                                             static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
                                                             max_iterations, d_bits, static_cast<uint32_t>(out_len), d_iters,
-                                                            static_cast<double *>(d_post), o_err LDPC_DBG_ARG(opt_lat_debug_));
+                                                            static_cast<double *>(d_post), o_err);
   else
     dev::latency_minsum_kernel<float><<<grid, 1024, 0, s>>>(t, lp.slots, lp.d_sync, static_cast<const float *>(d_llrs),
                                                            static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
                                                            max_iterations, d_bits, static_cast<uint32_t>(out_len), d_iters,
-                                                           static_cast<float *>(d_post), o_err LDPC_DBG_ARG(opt_lat_debug_));
+                                                           static_cast<float *>(d_post), o_err);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s));
   if (*o_err != 0) {

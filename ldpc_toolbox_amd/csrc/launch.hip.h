@@ -62,10 +62,10 @@ struct Launch {
     // (eight loads in flight per lane; the four-load variant of earlier rounds, a tuning knob nothing selected, is gone)
     if (g_knobs.rec_long)
       dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, true><<<t.blocks, t.threads, 0, s>>>(
-          g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run LDPC_DBG_ARG(g_knobs.rec_dbg));
+          g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run);
     else
       dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, false><<<t.blocks, t.threads, 0, s>>>(
-          g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run LDPC_DBG_ARG(g_knobs.rec_dbg));
+          g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run);
   }
   template <int VEC, bool FIRST>
   static void cn_rec_w(uint32_t recw, const Tiling &t, hipStream_t s, const dev::Graph &g, const dev::State &st, const T *chan,
@@ -86,19 +86,6 @@ struct Launch {
     else
       cn_rec_w<1, FIRST>(recw, t, s, g, st, chan, post, rec_in, rec_out, msg, unsat, run);
   }
-#ifdef LDPC_EXPERIMENTS
-  // continuous batching: the STREAM variant (never FIRST), 8 loads in flight
-  static void cn_rec_stream(uint32_t vec, uint32_t recw, const Tiling &t, hipStream_t s, const dev::Graph &g, const dev::State &st,
-                            const T *chan, T *post, const T *rec_in, T *rec_out, T *msg, uint32_t *unsat, uint32_t run) {
-    constexpr int kMaxVec = sizeof(T) == 4 ? 4 : 2;
-    auto go = [&](auto k) { k<<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run LDPC_DBG_ARG(0u)); };
-    if (vec == 4 && kMaxVec == 4) {
-      if (recw == 3) go(dev::cn_minsum_rec_kernel<T, kMaxVec, 3, 8, false, true, true>); else go(dev::cn_minsum_rec_kernel<T, kMaxVec, 4, 8, false, true, true>);
-    } else {
-      if (recw == 3) go(dev::cn_minsum_rec_kernel<T, 2, 3, 8, false, true, true>); else go(dev::cn_minsum_rec_kernel<T, 2, 4, 8, false, true, true>);
-    }
-  }
-#endif
   static void vn_free_rec(uint32_t vec, uint32_t recw, const Tiling &t, hipStream_t s, const dev::Graph &g,
                           const dev::State &st, const uint32_t *free_rs, const T *chan, const T *rec, T *post,
                           int32_t event_iteration) {
@@ -308,37 +295,6 @@ struct Launch {
         break;
     }
   }
-
-  // layered, slice-persistent (hl_slice_kernel): one launch per iteration; f32 Tanh rule (and its "@fast" variant)
-  struct SliceLaunch {
-    uint32_t slice, blocks, columns, dmax, n_levels, tile;
-    size_t lds;
-    const uint32_t *tasks, *task_ptr;
-  };
-  static constexpr uint32_t kSliceThreads = 1024;
-#ifdef LDPC_EXPERIMENTS
-  template <int RULE, bool FIRST>
-  static void hl_slice_r(const SliceLaunch &p, hipStream_t s, const dev::Graph &g, const dev::State &st, T *Q, T *R) {
-    if constexpr (sizeof(T) == 4) {
-      auto launch = [&](auto k) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  static_cast<int>(p.lds));
-        k<<<p.blocks, kSliceThreads, p.lds, s>>>(g, st, p.tasks, p.task_ptr, p.n_levels, p.tile, Q, R, p.dmax, p.columns);
-      };
-      if (p.slice == 32)
-        launch(dev::hl_slice_kernel<RULE, T, 32, kSliceThreads, FIRST>);
-      else
-        launch(dev::hl_slice_kernel<RULE, T, 64, kSliceThreads, FIRST>);
-    }
-  }
-  template <bool FIRST>
-  static void hl_slice(const SliceLaunch &p, hipStream_t s, const dev::Graph &g, const dev::State &st, T *Q, T *R) {
-    if (g_knobs.fast)
-      hl_slice_r<dev::kRuleTanhFast, FIRST>(p, s, g, st, Q, R);
-    else
-      hl_slice_r<dev::kRuleTanh, FIRST>(p, s, g, st, Q, R);
-  }
-#endif
 
   // layered min-sum, streaming
   template <int VEC, bool FIRST>

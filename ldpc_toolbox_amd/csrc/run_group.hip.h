@@ -26,7 +26,6 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
   tile = std::max<uint32_t>(64, tile / 64 * 64);
   while (G % tile != 0) tile -= 64;
 
-  g_knobs.rec_dbg = opt_rec_dbg_;
   g_knobs.rec_long = max_row_weight_ > 8 || opt_rec_long_;
   g_knobs.fast = impl_.fast;
   g_knobs.row_scratch = nullptr;
@@ -313,48 +312,10 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
     const bool hl_rec = streaming && opt_hl_records_ && opt_hl_reg_ && max_row_weight_ <= (sizeof(T) == 4 ? 26u : 58u) &&
                         Launch<T>::hl_reg_bucket(max_row_weight_) != 0 && m_ * 3 <= e_ &&
                         uint64_t(std::max(n_, m_ * 3)) * tile * sizeof(T) < (1ull << 32);
-    // slice-persistent form (kernels.hip.h, hl_slice_kernel): one launch per iteration, a workgroup per codeword slice.
-    // Opt-in ("hl_persist"); for the f32 Tanh rule when every row fits a task and the slice's arrays stay below the
-    // kernel's out-of-range marks (2^31 bytes; a padding index times a row's bytes must not wrap: rows of at most 1 KiB).
-    typename Launch<T>::SliceLaunch sl{};
-#ifdef LDPC_EXPERIMENTS
-    if (sizeof(T) == 4 && impl_.rule == Rule::Tanh && opt_hl_persist_ && !serial && d_slice_tasks_[0] && tile % 64 == 0 &&
-        (tile & (tile - 1)) == 0 &&  // (a padding index times a 768-byte row would wrap INTO the arrays: power-of-two rows only)
-        tile * sizeof(T) <= 1024 && uint64_t(std::max(e_, n_)) * tile * sizeof(T) < (1ull << 31) && n_ < 0x003FFFFFu) {
-      // (slices of 64 codewords -- a whole wavefront per row -- when that still gives every CU a workgroup and no row
-      // needs splitting; else slices of 32)
-      const uint32_t width = opt_hl_slice_ ? opt_hl_slice_ : ((G / 64 >= 256 && slice_fits_[1]) ? 64u : 32u);
-      const int k = width == 32 ? 0 : 1;
-      const uint32_t dmax_lds = std::max<uint32_t>(max_row_weight_, 10);
-      const size_t lds_bytes = (size_t(dmax_lds) * sizeof(T) + 2 * 10 * 4) * Launch<T>::kSliceThreads + 16;
-      if (slice_fits_[k] && lds_bytes <= size_t(160) * 1024) {
-        sl.slice = width;
-        sl.blocks = G / width;
-        sl.columns = 1;
-        sl.dmax = dmax_lds;
-        sl.n_levels = n_levels;
-        sl.tile = tile;
-        sl.lds = lds_bytes;
-        sl.tasks = d_slice_tasks_[k];
-        sl.task_ptr = d_slice_task_ptr_[k];
-      }
-    }
-#endif
-    __atomic_store_n(&last_persist_, sl.slice, __ATOMIC_RELAXED);  // (both lanes' enqueuing threads pass here)
     for (uint32_t it = 1; it <= max_iterations; it++) {
       if (it > 1 && poll.finished(it)) break;
       const dev::State stp = ticked(it);
-#ifdef LDPC_EXPERIMENTS
-      if (sl.slice) {
-        timed_begin(kKernelLayer, s);
-        if (it == 1)
-          Launch<T>::template hl_slice<true>(sl, s, g, stp, post, msg);
-        else
-          Launch<T>::template hl_slice<false>(sl, s, g, stp, post, msg);
-        timed_end(kKernelLayer, s);
-      }
-#endif
-      for (uint32_t l = 0; l < (sl.slice ? 0u : n_launch); l++) {
+      for (uint32_t l = 0; l < n_launch; l++) {
         const dev::State &st = l == 0 ? stp : st0;
         const uint32_t r0 = serial ? 0 : level_ptr_[l], cnt = serial ? m : level_ptr_[l + 1] - level_ptr_[l];
         const uint32_t lmaxdeg = serial ? max_row_weight_ : level_maxdeg_[l];

@@ -37,9 +37,6 @@ class Simulator {
   int modulation() const { return bits_per_symbol_; }
   int64_t interleaving() const { return interleaving_; }
   DeviceDecoder *decoder() { return dec_.get(); }
-  // frames the last run() / run_bch() call put through the continuous-batching path (0: drained batches)
-  uint64_t streamed_frames() const { return streamed_frames_; }
-  void set_streaming(bool on) { streaming_ = on; }
   // straggler pooling (run_bch): 0 = every chunk runs the full iteration budget
   void set_pooling(bool on) {
     pooling_ = on;
@@ -84,10 +81,6 @@ class Simulator {
   int32_t *d_its_ = nullptr;
   unsigned long long *d_counters_ = nullptr;
   size_t cap_frames_ = 0, cap_llr_rows_ = 0;
-  uint64_t streamed_frames_ = 0;
-  // continuous batching is built and exact but does not pay in this data layout (profiles/r03_continuous_batching.txt:
-  // 0.64-0.69 of the iteration-proportional bound against 0.75-0.81 for drained batches with compaction): opt-in
-  bool streaming_ = false;
   // Straggler pooling: once a run() call has seen how many iterations its frames take, later chunks run a reduced
   // budget and the frames that have not converged by then are pooled and decoded together with the full budget --
   // instead of every chunk dragging its few slow (or failing) frames through launch-bound, nearly empty iterations

@@ -227,18 +227,12 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
   for (int i = 0; i < 9; i++) counters[i] = 0;
   if (frames == 0) return 0;
   SIM_TRY(hipSetDevice(device_));
-  // Continuous batching where the decoder offers it (flooding Minsumf32, BPSK): the frames of a chunk are produced
-  // on demand, straight into the slots that finished codewords free (DeviceDecoder::decode_stream); the chip stays
-  // full over the whole chunk instead of draining every 4096 frames.  Frame f is the same frame either way.
-  const bool streaming = streaming_ && stream_ && dec_->stream_capable() && bits_per_symbol_ == 1 && max_iterations > 0 &&
-                         frames > dec_->stream_group() && std::getenv("LDPC_TOOLBOX_NO_STREAM") == nullptr;
-  streamed_frames_ = 0;
-  // (drained path: a chunk is one group of the decoder -- 4096 frames, more for small graphs)
-  const size_t chunk = streaming ? std::min<size_t>(frames, 32768) : std::min<size_t>(frames, std::max<size_t>(dec_->preferred_group(frames), 4096));
-  if (int rc = ensure(chunk, streaming ? std::min<size_t>(chunk, 4096) : chunk)) return rc;
+  // a chunk is one group of the decoder -- 4096 frames, more for small graphs
+  const size_t chunk = std::min<size_t>(frames, std::max<size_t>(dec_->preferred_group(frames), 4096));
+  if (int rc = ensure(chunk, chunk)) return rc;
   SIM_TRY(hipMemsetAsync(d_counters_, 0, 9 * sizeof(unsigned long long), stream_));
   // straggler pooling (simulator.h): from the second chunk on, when the frames seen so far converge well within the budget
-  const bool track = pooling_ && !streaming && max_iterations >= 24;
+  const bool track = pooling_ && max_iterations >= 24;
   const bool can_pool = track && (frames > chunk || (budget_valid_ && budget_ebn0_ == ebn0_db && budget_max_it_ == max_iterations));
   pooled_frames_ = 0;
   if (can_pool) {
@@ -269,26 +263,10 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
   };
   for (size_t f0 = 0; f0 < frames; f0 += chunk) {
     const uint32_t nf = static_cast<uint32_t>(std::min(chunk, frames - f0));
-    if (streaming) {
-      float sigma, scale;
-      noise_params(ebn0_db, &sigma, &scale);
-      const uint64_t base = first_frame + f0;
-      const uint32_t n_tx = static_cast<uint32_t>(n_tx_);
-      auto source = [&](const uint64_t *first_count, float *dst, hipStream_t s) {
-        gen::awgn_llr_stream_kernel<<<8192, 256, 0, s>>>(d_tx_, pool_, n_tx, seed, base, first_count, sigma, scale, dst);
-      };
-      SIM_TRY(hipStreamSynchronize(stream_));  // (decode_stream runs on the decoder's own stream)
-      if (int rc = dec_->decode_stream(source, d_llrs_, nf, max_iterations, d_bits_, k_, d_its_)) {
-        error_ = dec_->last_error();
-        return rc;
-      }
-      streamed_frames_ += nf;
-    } else {
     launch_generator(ebn0_db, seed, first_frame + f0, nf);
     if (int rc = dec_->decode_device(d_llrs_, false, nf, budget, d_bits_, k_, d_its_, nullptr, stream_)) {
       error_ = dec_->last_error();
       return rc;
-    }
     }
     const bool reduced = budget < max_iterations;
     if (reduced)

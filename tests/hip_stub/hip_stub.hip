@@ -136,7 +136,6 @@ int state_arg(const std::string &name) {
                         "hl_level_reg_kernel", "hl_minsum_kernel", "hl_minsum_reg_kernel", "hl_minsum_rec_kernel", "cn_i8_kernel",
                         "hl_i8_kernel", "hl_i8_reg_kernel"})
     if (name.find(k) != std::string::npos) return 2;  // (Graph, Sched, State, ...)
-  if (name.find("hl_slice_kernel") != std::string::npos) return 1;  // (Graph, State, ...)
   if (name.find("compact_plan_kernel") != std::string::npos) return 0;
   return -1;
 }

@@ -13,7 +13,6 @@ import numpy as np
 import pytest
 
 import ldpc_toolbox_amd as lt
-from experiments_build import on_experiments_build
 from frames import alist, awgn_frames
 
 pytestmark = pytest.mark.gpu
@@ -103,21 +102,6 @@ def test_group_that_finishes_inside_the_variable_node_launch(oracle, batch):
         for host in (True, False):
             for name, a, b in zip(("bits", "iterations", "posterior"), decode(host), want):
                 assert np.array_equal(a, b), (batch, rep, "host entry" if host else "device entry", name, where(a, b))
-
-
-@on_experiments_build
-def test_streaming_record_variant_is_deterministic():
-    """the STREAM instantiation (continuous batching through the simulator; -DLDPC_EXPERIMENTS builds only since round 5,
-    so the test runs on that build): same counters 20 times"""
-    s = lt.Simulator(alist("dvbs2:R1_2short"), "Minsumf32", "", device=0, pool_size=16, pool_seed=9)
-    s.set("records", 2)
-    s.set("streaming", 1)
-    first = None
-    for rep in range(REPEATS):
-        c = list(s.run(1.5, seed=5, first_frame=3, frames=4096 + 1500, max_iterations=25))
-        assert s.get("streamed_frames") == 4096 + 1500
-        first = first or c
-        assert c == first, rep
 
 
 def test_one_wait_state_is_enough_behind_an_sgpr_soffset_store():

@@ -13,15 +13,9 @@ import numpy as np
 import pytest
 
 import ldpc_toolbox_amd as lt
-from experiments_build import on_experiments_build
 from frames import alist, awgn_frames
 
 pytestmark = pytest.mark.gpu
-
-
-# the opt-in forms the product left behind in round 5 (the slice-persistent layered kernel, continuous batching) exist in
-# the -DLDPC_EXPERIMENTS build only: their tests run on it (tests/experiments_build.py)
-needs_experiments = on_experiments_build
 
 
 def run_both(oracle, spec, impl, batch, ebn0, max_iter, seed, puncturing="", group=None):
@@ -966,44 +960,11 @@ def test_register_resident_flooding_tanh_rows_are_invisible(oracle, spec, impl, 
     assert (outs[0][1] >= 0).any()
 
 
-@pytest.mark.parametrize("spec,frames,ebn0", [("nr5g:1:16", 2304, 1.0), ("nr5g:2:24", 1100, 1.5), ("ar4ja:1/2:1024", 700, 1.8),
-                                              ("nr5g:1:384", 640, 0.5)])
-@needs_experiments
-def test_slice_persistent_layered_kernel_is_invisible(oracle, spec, frames, ebn0):
-    """`hl_persist` (opt-in): one launch per iteration in which a workgroup owns a slice of 32 codewords and walks the
-    dependency levels itself (software-pipelined loads, rows of more than ten edges shared by two lanes, the Tanh rule
-    in registers) gives bit for bit what one launch per level gives -- hard decisions, iteration counts, posteriors --
-    with one and two execution lanes, whole and ragged groups, with compaction; and the oracle agrees.
-    (5G NR BG1 has rows of 19 edges: the shared-row form; BG2 and AR4JA only short rows.)"""
-    msgs, llrs, full = awgn_frames(spec, frames, ebn0, 777)
-    dec = lt.LdpcDecoder(alist(spec), "HLTanhf32")
-    dec.set("latency", 0)                       # (the small-batch paths would take the 640-frame call)
-    want = None
-    for persist, lanes, group in ((0, 1, 4096), (1, 1, 4096), (1, 2, 512), (1, 2, 1024), (1, 1, 320)):
-        dec.set("hl_persist", persist)
-        dec.set("lanes", lanes)
-        dec.set("group_size", group)
-        got = dec.decode_batch(llrs, 12, want_posterior=True)
-        assert dec.get("last_persist") == (32 if persist else 0)
-        if want is None:
-            want = got
-        else:
-            for a, b in zip(want, got):
-                assert np.array_equal(a, b), (persist, lanes, group)
-    sub = slice(0, frames, 7)
-    ob_, oi_, op_ = oracle.decode_batch(oracle.Graph(alist(spec)), "HLTanhf32", full[sub], 12, threads=8)
-    assert np.array_equal(want[1][sub], oi_) and np.array_equal(want[0][sub], ob_)
-    assert np.array_equal(want[2][sub], op_.astype(np.float32))
-    assert (want[1] >= 0).any() and (want[1] < 0).any()
-
-
 def test_wrong_result_switches_are_not_in_the_product():
     """include/ldpc_toolbox.h promises that no tunable changes a result: the experiment switches that did are gone -- and
     so are the opt-in forms that measured level or behind (round 5): the slice-persistent layered kernel's options are
     unknown to the product, and "streaming" on the simulator changes nothing"""
     dec = lt.LdpcDecoder(alist("dvbs2:R1_2short"), "Minsumf32")
-    if dec.get("experiments"):
-        pytest.skip("an experiments build")
     for key in ("rec_dbg", "lat_debug", "hl_persist", "hl_slice"):
         with pytest.raises(KeyError):
             dec.set(key, 1)
@@ -1014,24 +975,6 @@ def test_wrong_result_switches_are_not_in_the_product():
     assert s.get("streamed_frames") == 0
     s.set("streaming", 0)
     assert np.array_equal(a, s.run(1.8, seed=3, first_frame=0, frames=4096 + 700, max_iterations=25))
-
-
-@needs_experiments
-def test_slice_persistent_kernel_is_off_by_default_and_refuses_what_it_cannot_run():
-    dec = lt.LdpcDecoder(alist("nr5g:1:16"), "HLTanhf32")
-    msgs, llrs, full = awgn_frames("nr5g:1:16", 256, 1.0, 3)
-    dec.set("latency", 0)
-    dec.decode_batch(llrs, 4)
-    assert dec.get("last_persist") == 0          # default: one launch per level
-    dec.set("hl_persist", 1)
-    dec.set("hl_slice", 64)                      # rows of 19 edges cannot be shared inside a 64-codeword slice
-    dec.decode_batch(llrs, 4)
-    assert dec.get("last_persist") == 0
-    other = lt.LdpcDecoder(alist("nr5g:1:16"), "HLPhif32")   # other rules keep the per-level launches
-    other.set("hl_persist", 1)
-    other.set("latency", 0)
-    other.decode_batch(llrs, 4)
-    assert other.get("last_persist") == 0
 
 
 @pytest.mark.parametrize("impl", ["HLMinsumf32", "HLMinsumf64", "HLTanhf64"])
@@ -1514,43 +1457,6 @@ def test_config5_simulator_on_dvbs2_normal_frames(oracle, spec, ebn0s, max_it):
         bits, its, _ = oracle.decode_batch(g, "Minsumf32", llrs, max_it, threads=32, want_posterior=False)
         st = sim.fold_statistics(ebn0, s.k, msgs[idx], bits, its, max_it, 1.0, bch_max_errors=12)
         assert np.array_equal(part, sharding.counters_from_statistics(st)), (spec, ebn0, part)
-
-
-@pytest.mark.parametrize("spec,punct,ebn0s", [("ar4ja:1/2:1024", "1,1,1,1,0", (1.6, 2.2, 3.0)), ("dvbs2:R1_2short", "", (1.5, 2.0))])
-@needs_experiments
-def test_continuous_batching_counts_the_same_frames_the_same_way(oracle, spec, punct, ebn0s):
-    """sim_run with "streaming" = 1 and more frames than one group streams them through the decoder (DeviceDecoder::decode_stream: a slot
-    whose codeword has finished is handed the next frame at the next harvest; the reference's workers likewise
-    produce frames until the stop rule fires, ber.rs:297-368).  Frame f is the same frame and decodes to the same
-    result whichever slot and iteration it starts in: the six counters equal those of the drained-batch path
-    (the default: the streaming path is exact but slower in this layout) and, on a sample, those of the oracle over the regenerated frames -- at a point where
-    most frames fail, in the waterfall, and where every frame converges early."""
-    from ldpc_toolbox_amd import sharding, simulation as sim
-    pattern = sim.parse_puncturing_pattern(punct) if punct else None
-    s = lt.Simulator(alist(spec), "Minsumf32", punct, device=0, pool_size=16, pool_seed=9)
-    s.set("records", 2)                        # (the streaming path is built on the row-record kernel)
-    msgs, tx = s.pool_data()
-    g = oracle.Graph(alist(spec))
-    for ebn0 in ebn0s:
-        frames = 4096 + 4096 + 1500            # more than two groups, ragged end
-        s.set("streaming", 1)
-        got = s.run(ebn0, seed=5, first_frame=123, frames=frames, max_iterations=25)
-        assert s.get("streamed_frames") == frames                 # it did take the streaming path
-        s.set("streaming", 0)
-        want = s.run(ebn0, seed=5, first_frame=123, frames=frames, max_iterations=25)
-        assert s.get("streamed_frames") == 0
-        assert np.array_equal(got, want), (ebn0, got, want)
-        assert got[0] == frames
-    # the oracle on the regenerated frames (small code only: it decodes them on the CPU)
-    if spec.startswith("ar4ja"):
-        frames = 5000
-        s.set("streaming", 1)
-        got = s.run(2.2, seed=6, first_frame=40, frames=frames, max_iterations=25)
-        assert s.get("streamed_frames") == frames
-        llrs, idx = oracle.generate_llrs(tx, s.rate, 2.2, 6, 40, frames)
-        bits, its, _ = oracle.decode_batch(g, "Minsumf32", sim.depuncture(llrs, pattern), 25, threads=8, want_posterior=False)
-        st = sim.fold_statistics(2.2, s.k, msgs[idx], bits, its, 25, 1.0)
-        assert np.array_equal(got, sharding.counters_from_statistics(st)), got
 
 
 @pytest.mark.parametrize("spec,punct,impl,ebn0s", [("ar4ja:1/2:1024", "1,1,1,1,0", "Minsumf32", (1.6, 2.0, 2.4, 3.0, 0.0)),

@@ -99,7 +99,7 @@ def test_product_does_not_link_the_oracle():
 
 def test_product_carries_no_wrong_result_switches():
     """the timing-experiment switches of earlier rounds (decoder options "rec_dbg" / "lat_debug", environment variable
-    LDPC_DBG_VNSEQ: they skip stores or scramble an edge order) are compiled only with -DLDPC_EXPERIMENTS; the shipped
+    LDPC_DBG_VNSEQ: they skip stores or scramble an edge order) are gone from the source; the shipped
     library knows none of the names (the GPU suite also checks that setting them fails)"""
     blob = open(_capi.LIB_PATH, "rb").read()
     # (round 5: nor the opt-in forms that never won -- the slice-persistent layered kernel, continuous batching)
@@ -111,8 +111,7 @@ def test_product_carries_no_wrong_result_switches():
 def test_kernels_keep_their_registers():
     """the gfx950 code objects of the built library (metadata notes, no GPU needed): no kernel spills registers to scratch
     memory except the single-launch small-batch kernel and the 10-edge layered rows that are known to (a kernel that silently starts to spill
-    loses a large factor: the f64 layered kernels did until round 4), and the slice-persistent layered kernel fits the
-    128 registers its 16-wave workgroups have"""
+    loses a large factor: the f64 layered kernels did until round 4)"""
     import sys
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     import kernel_resources
@@ -132,8 +131,6 @@ def test_kernels_keep_their_registers():
             assert spilled <= 2 and scratch <= 16, (name, spilled, scratch)
             continue
         assert scratch == 0 and spilled == 0, (name, spilled, scratch)
-        if "hl_slice_kernel" in name:      # (-DLDPC_EXPERIMENTS builds only)
-            assert vgpr + agpr <= 128, (name, vgpr, agpr)
 
 
 # ---- graph owner: alist ------------------------------------------------------------------------

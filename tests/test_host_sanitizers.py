@@ -35,11 +35,11 @@ def test_oracle_is_clean_under_asan_ubsan(tmp_path):
     assert "oracle sanitizer driver: ok" in r.stdout
 
 
-def test_layered_schedule_tables_under_asan_ubsan(tmp_path):
-    """dependency levels and the task records of the slice-persistent layered kernel (csrc/slice_tasks.h): every row in
-    exactly one task of its level, every edge in exactly one lane slot (the middle edge of an odd shared row in two),
-    out-of-range padding everywhere else -- for codes with short rows only, with rows of 19 (5G NR BG1: shared by two
-    lanes), with rows too long for any task (DVB-S2 short 8/9: the table says so), and a staircase code"""
+def test_layered_level_tables_under_asan_ubsan(tmp_path):
+    """dependency levels and the row records of the register-resident level kernels (csrc/slice_tasks.h): rows of one
+    level share no variable, levels follow the row order, and every record lists its row's first edge, degree and
+    variables -- for codes with short rows only, with rows of 19 (5G NR BG1), with rows too long for a record (DVB-S2
+    short 8/9), and a staircase code"""
     import ldpc_toolbox_amd as lt
     exe = str(tmp_path / "slice_tasks_driver")
     subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
@@ -61,7 +61,7 @@ def test_host_threads_are_clean_under_tsan(tmp_path):
     kernels publish the progress word.  Scenarios: every group runs all its iterations; the device "finishes" at
     iteration 3 / 1 (the enqueuing threads' early exits and pacing); a HIP call fails somewhere in the middle (the
     error returns of decode_host / decode_device with lane threads alive).  Round 4 found and fixed two unsynchronised
-    writes this way (skew_record_ and last_persist_ written by both lanes' threads)."""
+    writes this way (skew_record_ and another member written by both lanes' threads)."""
     out = str(tmp_path / "tsan")
     b = subprocess.run([os.path.join(ROOT, "tests", "hip_stub", "build.sh"), out], capture_output=True, text=True, timeout=900)
     assert b.returncode == 0, b.stdout[-2000:] + b.stderr[-4000:]

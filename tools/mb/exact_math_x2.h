@@ -81,7 +81,7 @@ EM_FN f32x2 tanhf_c9(f32x2 x) {
   const f32x2 hxs = xr * hfx;
   const f32x2 r1 = one + hxs * (Q1 + hxs * (Q2 + hxs * (Q3 + hxs * (Q4 + hxs * Q5))));
   const f32x2 t3 = 3.0f - r1 * hfx;
-  const f32x2 e = hxs * fdiv_v<EM_FDIV_EXPM1>(r1 - t3, 6.0f - xr * t3);
+  const f32x2 e = hxs * fdiv_v<kFdivExpm1>(r1 - t3, 6.0f - xr * t3);
   const f32x2 r0 = xr - (xr * e - hxs);
   const f32x2 e2 = (xr * (e - c) - c) - hxs;
   const f32x2 rm1 = 0.5f * (xr - e2) - 0.5f;
@@ -99,7 +99,7 @@ EM_FN f32x2 tanhf_c9(f32x2 x) {
   const f32x2 r_small = sel2(k == 0, r0, sel2(k == -1, rm1, ya));
   f32x2 t = sel2(big, r_big, r_small);
   t = sel2(hx < 0x33000000u, arg, t);
-  const f32x2 q = fdiv_v<EM_FDIV_TANH>(sel2(big, splat2(2.0f), -t), t + 2.0f);
+  const f32x2 q = fdiv_v<kFdivTanh>(sel2(big, splat2(2.0f), -t), t + 2.0f);
   const f32x2 z = sel2(big, one - q, q);
   return as_f32(as_u32(z) | (jx & 0x80000000u));
 }
@@ -127,7 +127,7 @@ EM_FN f32x2 log1pf(f32x2 x) {
   i32x2 hu = __builtin_bit_cast(i32x2, u0);
   i32x2 k = (hu >> 23) - 127;
   f32x2 c = sel2(k > 0, 1.0f - (u0 - x), x - (u0 - 1.0f));
-  c = fdiv_v<EM_FDIV_L1P_C>(c, u0);
+  c = fdiv_v<kFdivL1pC>(c, u0);
   hu &= 0x007fffff;
   const i32x2 low = hu < 0x3504f7;
   k += sel2(low, i32x2{0, 0}, i32x2{1, 1});
@@ -139,7 +139,7 @@ EM_FN f32x2 log1pf(f32x2 x) {
   k = sel2(direct, i32x2{0, 0}, k);
   c = sel2(direct, splat2(0.0f), c);
   const f32x2 hfsq = 0.5f * f * f;
-  const f32x2 s = fdiv_v<EM_FDIV_L1P_S>(f, 2.0f + f);
+  const f32x2 s = fdiv_v<kFdivL1pS>(f, 2.0f + f);
   const f32x2 z = s * s;
   const f32x2 R = z * (Lp1 + z * (Lp2 + z * (Lp3 + z * (Lp4 + z * (Lp5 + z * (Lp6 + z * Lp7))))));
   const f32x2 kf = __builtin_convertvector(k, f32x2);
@@ -150,7 +150,7 @@ EM_FN f32x2 log1pf(f32x2 x) {
 
 EM_FN f32x2 atanh_rs(f32x2 x) {
   if (!(__builtin_fabsf(x.x) < 1.0f && __builtin_fabsf(x.y) < 1.0f)) return atanh_pair_slow(x);
-  const f32x2 q = fdiv_v<EM_FDIV_ATANH>(2.0f * x, 1.0f - x);
+  const f32x2 q = fdiv_v<kFdivAtanh>(2.0f * x, 1.0f - x);
   return 0.5f * log1pf(sel2(x == 0.0f, x, q));
 }
 #endif  // HIP compilation

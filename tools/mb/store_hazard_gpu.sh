@@ -1,6 +1,6 @@
 #!/bin/bash
 # GPU box, round 5: (1) the standalone reproducer, (2) the determinism test at a size where stores queue up, on the product
-# library and on the experiment builds named on the command line (tools/ab_variants.sh build <tag> ...), (3) what the pad
+# library and on the builds named on the command line (lib/libldpc_toolbox_<tag>.so: make BUILD=... OUT=...), (3) what the pad
 # costs: the kernels that store 128-bit packs through buffer descriptors, timed on each build.  Output: gpurun_out/store_hazard/
 R=$(cd "$(dirname "$0")/../.." && pwd)
 OUT=$R/gpurun_out/store_hazard; mkdir -p $OUT
