@@ -43,6 +43,12 @@ extern "C" {
  * Minsumf32/Minsumf64/HLMinsumf32/HLMinsumf64 -- all 40 bit-identical to the reference decoder;
  * "Tanhf32@fast", "HLTanhf32@fast", "Phif32@fast", "HLPhif32@fast" are opt-in approximate variants on the
  * GPU's native exp2 / log2 / rcp, NOT bit-identical and never chosen unless named;
+ * [HL]NormMinsum{f32,f64}[:alpha] and [HL]OffsetMinsum{f32,f64}[:beta] are normalized and offset min-sum: the Minsum
+ * decoder, both schedules, except that the magnitude m a check row sends on an edge (the minimum of the other edges' |x|)
+ * becomes alpha * m (0 < alpha <= 1, default 0.75) or max(m - beta, 0) (beta >= 0, default 0.5), in the decoder's type,
+ * each result rounded once; the sign is plain min-sum's, so a magnitude clamped to zero sends +0.0 or -0.0.  The value
+ * is digits[.digits] (no sign, no exponent): "NormMinsumf32", "HLOffsetMinsumf64:0.3", "NormMinsumf32:0.8125@hip:1".
+ * "NormMinsumf32:1" and "OffsetMinsumf32:0" decode exactly as "Minsumf32"; there is no 8-bit and no "@fast" form;
  * an optional "@hip:N" suffix, last, selects GPU N); puncturing: "" or a pattern such as "1,1,1,0"
  * (src/cli/ber.rs:219-229).  Returns an opaque handle, or NULL on any error. */
 void *ldpc_toolbox_decoder_ctor(const char *alist_file_path, const char *implementation,
@@ -182,7 +188,8 @@ int32_t ldpc_toolbox_decoder_syndrome_device(void *decoder, const uint8_t *bits,
  * "last_lanes" / "last_group" (execution lanes and codewords per group of the last decode call),
  * "preferred_group" (codewords per group of a large call: "group_size" if set, else 4096, more for small graphs),
  * "row_records" (words per check-row record when flooding min-sum keeps a row's messages as
- * {min1, min2, flip bits, argmin}; 0 = per-edge messages).  returns 0 or -1 (unknown key). */
+ * {min1, min2, flip bits, argmin}; 0 = per-edge messages), "minsum_correction" (0: none, 1: normalized min-sum,
+ * 2: offset min-sum).  returns 0 or -1 (unknown key). */
 int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value);
 /* Tunables: "group_size" (codewords decoded together; 0 = automatic), "profiling" (0/1:
  * bracket the check/variable/layer launches with hipEvents), and 26 launch / execution choices -- "waves", "vec", "tile",

@@ -490,6 +490,8 @@ int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value)
     *value = static_cast<int64_t>(d.preferred_group(size_t(1) << 20));
   else if (k == "row_records")
     *value = d.row_records();
+  else if (k == "minsum_correction")
+    *value = static_cast<int64_t>(d.implementation().correction);
   else if (k == "last_persist" || k == "experiments")  // (the removed experiment builds: always 0)
     *value = 0;
   else

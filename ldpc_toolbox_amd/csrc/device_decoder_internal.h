@@ -244,11 +244,15 @@ inline Tiling make_tiling(uint32_t G, uint32_t tile, uint32_t slice, uint32_t no
   return t;
 }
 
-// per-call launch tunables (never affect results)
+// per-call launch choices (the tunables never affect results; `fast` and `corr` carry the implementation's arithmetic)
 struct Knobs {
   bool rec_long = true;  // some row has more than 8 edges
   bool fast = false;  // "@fast" implementation: the approximate Tanh / Phi rule variants
   void *row_scratch = nullptr;  // non-null: the LDS-staged kernels keep their columns there (rows beyond the LDS)
+  // normalized / offset min-sum (Implementation::correction; this one DOES decide results): every min-sum launch of the call
+  // takes its corrected form with c = max(alpha * m - beta, 0) (kernels_common.hip.h, MinsumCorr)
+  bool corr = false;
+  double alpha = 1.0, beta = 0.0;
 };
 inline thread_local Knobs g_knobs;  // set at the top of run_group for the launches of this call
 inline thread_local bool t_flood_pace = false;  // set by decode_device for the groups it starts: a one-lane call on the device-resident entry

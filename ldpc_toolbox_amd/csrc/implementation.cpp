@@ -1,5 +1,7 @@
 #include "implementation.h"
 
+#include <cmath>
+#include <cstdlib>
 #include <cstring>
 
 namespace ldpc {
@@ -14,6 +16,25 @@ const Stem kStems[] = {{"Phi", Rule::Phi},
                        {"Minstarapprox", Rule::Minstarapprox},
                        {"Aminstar", Rule::Aminstar},
                        {"Minsum", Rule::Minsum}};
+struct CorrectedStem {
+  const char *text;
+  Correction correction;
+  double dflt;
+};
+const CorrectedStem kCorrectedStems[] = {{"NormMinsum", Correction::Normalized, 0.75}, {"OffsetMinsum", Correction::Offset, 0.5}};
+
+// digits[.digits], nothing else (no sign, no exponent, no "inf"): what strtod is then allowed to see
+bool plain_decimal(const char *p) {
+  const char *q = p;
+  while (*q >= '0' && *q <= '9') q++;
+  if (q == p) return false;
+  if (*q == '.') {
+    const char *f = ++q;
+    while (*q >= '0' && *q <= '9') q++;
+    if (q == f) return false;
+  }
+  return *q == 0;
+}
 }  // namespace
 
 bool parse_implementation(const std::string &name, Implementation *out, std::string *err) {
@@ -23,6 +44,28 @@ bool parse_implementation(const std::string &name, Implementation *out, std::str
   if (std::strncmp(p, "HL", 2) == 0) {
     impl.schedule = Schedule::Layered;
     p += 2;
+  }
+  for (const CorrectedStem &s : kCorrectedStems) {
+    const size_t l = std::strlen(s.text);
+    if (std::strncmp(p, s.text, l) != 0) continue;
+    const char *suffix = p + l;
+    if (std::strncmp(suffix, "f32", 3) != 0 && std::strncmp(suffix, "f64", 3) != 0) break;  // (no 8-bit variants)
+    Implementation c = impl;
+    c.rule = Rule::Minsum;
+    c.f64 = suffix[1] == '6';
+    c.correction = s.correction;
+    c.correction_value = s.dflt;
+    suffix += 3;
+    if (*suffix == ':') {
+      if (!plain_decimal(suffix + 1)) break;
+      c.correction_value = std::strtod(suffix + 1, nullptr);
+    } else if (*suffix != 0) {
+      break;  // ("@fast" included: there is no approximate form of these)
+    }
+    const double v = c.correction_value;
+    if (!std::isfinite(v) || (s.correction == Correction::Normalized ? !(v > 0.0 && v <= 1.0) : !(v >= 0.0))) break;
+    *out = c;
+    return true;
   }
   for (const Stem &s : kStems) {
     const size_t l = std::strlen(s.text);
@@ -85,6 +128,14 @@ bool parse_puncturing_pattern(const std::string &text, std::vector<uint8_t> *out
 
 std::vector<std::string> fast_implementation_names() {
   return {"Tanhf32@fast", "HLTanhf32@fast", "Phif32@fast", "HLPhif32@fast"};
+}
+
+std::vector<std::string> corrected_minsum_implementation_names() {
+  std::vector<std::string> v;
+  for (const char *prefix : {"", "HL"})
+    for (const CorrectedStem &s : kCorrectedStems)
+      for (const char *suffix : {"f64", "f32"}) v.push_back(std::string(prefix) + s.text + suffix);
+  return v;
 }
 
 std::vector<std::string> implementation_names() {

@@ -6,7 +6,8 @@ namespace ldpc {
 namespace dev {
 
 enum : int { kRulePhi = 0, kRuleTanh = 1, kRuleMinstarapprox = 2, kRuleAminstar = 3, kRuleMinsum = 4,
-             kRuleTanhFast = 5, kRulePhiFast = 6 };  // "@fast": native exp2 / log2 / rcp, not bit-identical (f32 only)
+             kRuleTanhFast = 5, kRulePhiFast = 6,  // "@fast": native exp2 / log2 / rcp, not bit-identical (f32 only)
+             kRuleMinsumCorr = 7 };  // normalized / offset min-sum (MinsumCorr below): kRuleMinsum's fold, corrected magnitudes
 
 template <typename T, int VEC>
 struct alignas(sizeof(T) * VEC) Pack {
@@ -227,6 +228,31 @@ struct Limits<double> {
   __device__ static double inf() { return __builtin_huge_val(); }
 };
 
+// Normalized and offset min-sum ([HL]NormMinsum / [HL]OffsetMinsum).  m_i: the magnitude plain min-sum sends on edge i (the
+// fold from +inf with the NaN-ignoring minimum over the other edges' |x_j|), s_i: the parity of x_j < 0 over the other edges.
+//   normalized:  c_i = alpha * m_i            (0 < alpha <= 1)
+//   offset:      c_i = max(m_i - beta, 0)     (beta >= 0, finite)
+// and the message is c_i with the sign bit set iff s_i (a magnitude clamped to zero sends +0.0 or -0.0, as plain min-sum
+// does for a zero input).  Everything is T arithmetic, each result rounded once (the build sets -ffp-contract=off).  One form
+// serves both: c = max(alpha * m - beta, 0) with beta = 0 (normalized) or alpha = 1 (offset) -- 1 * m and x - 0 are exact and
+// x >= 0, so the two definitions come out bit for bit.  m is never NaN and never negative, alpha * m - beta is never -0.0
+// (+0 - 0 = +0), so the select below is the maximum, and +inf (a row of one edge) stays +inf.
+// The correction is a compile-time mode of the min-sum kernels (CORR, or RULE == kRuleMinsumCorr); alpha and beta are run-time
+// arguments.  It is applied ONCE PER ROW to min1 and min2, between the fold and the store: a row sends only these two
+// magnitudes, so correcting them is correcting every message of the row -- and a row record that holds the corrected pair
+// (RowRec) hands corrected messages to whoever reads it (RowRec::value: the row itself in the next iteration, the L-free
+// rebuild from the peer row's record, the carry between neighbouring rows, vn_free_rec_kernel, layered x = Qv - R).
+template <typename T>
+struct MinsumCorr {
+  T alpha, beta;
+};
+template <typename T>
+__device__ __forceinline__ T minsum_corrected(T m, const MinsumCorr<T> &mc) {
+  const T scaled = mc.alpha * m;
+  const T c = scaled - mc.beta;
+  return c > T(0.0) ? c : T(0.0);
+}
+
 // ---------------------------------------------------------------------------------------
 // Check-node rules on an LDS column: x[i*S], out[i*S], scr[i*S] for slot i of this thread.
 // ---------------------------------------------------------------------------------------
@@ -320,8 +346,9 @@ __device__ __forceinline__ bool tanh_products_by_degree(T *A, uint32_t d, uint32
 // Rules work on two LDS columns of the calling thread, A[i*S] and B[i*S]: on entry A holds the
 // d inputs x_i in slot order; on return the d outputs are in the column the function returns
 // (B, with x intact in A -- except Tanh, which works in A alone and leaves its outputs there).
+// (mc: read by kRuleMinsumCorr only)
 template <int RULE, typename T>
-__device__ __forceinline__ T *rule_check_node(T *A, T *B, uint32_t d, uint32_t S) {
+__device__ __forceinline__ T *rule_check_node(T *A, T *B, uint32_t d, uint32_t S, const MinsumCorr<T> &mc = MinsumCorr<T>{}) {
   if constexpr (RULE == kRulePhiFast) {
     // arithmetic.rs:214-246 with fast_phi
     uint32_t sign = 0;
@@ -400,7 +427,7 @@ __device__ __forceinline__ T *rule_check_node(T *A, T *B, uint32_t d, uint32_t S
       A[i * S] = two_atanh(product);
     }
     return A;
-  } else if constexpr (RULE == kRuleMinstarapprox || RULE == kRuleMinsum) {
+  } else if constexpr (RULE == kRuleMinstarapprox || RULE == kRuleMinsum || RULE == kRuleMinsumCorr) {
     // arithmetic.rs:487-521 (Minsum: same fold without the correction and the clamp,
     // SURVEY.md Appendix A.6)
     // out_i folds the other inputs in slot order.  The fold over the inputs before i is the same
@@ -408,9 +435,11 @@ __device__ __forceinline__ T *rule_check_node(T *A, T *B, uint32_t d, uint32_t S
     // evaluated per output -- half the work of the literal O(d^2) loop, same bits.
     // Minsum folds from +inf with the NaN-ignoring minimum (same value as starting from the first
     // magnitude for non-NaN inputs; matches the streaming kernels when inf - inf produced NaNs)
+    // kRuleMinsumCorr: the same fold; the magnitude is corrected where it leaves the fold (MinsumCorr above)
+    constexpr bool kMinsum = RULE == kRuleMinsum || RULE == kRuleMinsumCorr;
     uint32_t psign = 0;
-    bool phave = RULE == kRuleMinsum;
-    T pacc = RULE == kRuleMinsum ? Limits<T>::inf() : T(0.0);
+    bool phave = kMinsum;
+    T pacc = kMinsum ? Limits<T>::inf() : T(0.0);
     for (uint32_t i = 0; i < d; i++) {
       uint32_t sign = psign;
       bool have = phave;
@@ -422,12 +451,13 @@ __device__ __forceinline__ T *rule_check_node(T *A, T *B, uint32_t d, uint32_t S
         if (!have) {
           acc = v;
           have = true;
-        } else if constexpr (RULE == kRuleMinsum) {
+        } else if constexpr (kMinsum) {
           acc = m_min(v, acc);
         } else {
           acc = m_max(m_min(v, acc) - m_corr(m_abs(v - acc)), T(0.0));
         }
       }
+      if constexpr (RULE == kRuleMinsumCorr) acc = minsum_corrected(acc, mc);
       B[i * S] = (sign == 0) ? acc : -acc;
       // extend the prefix by input i
       T v = A[i * S];
@@ -436,7 +466,7 @@ __device__ __forceinline__ T *rule_check_node(T *A, T *B, uint32_t d, uint32_t S
       if (!phave) {
         pacc = v;
         phave = true;
-      } else if constexpr (RULE == kRuleMinsum) {
+      } else if constexpr (kMinsum) {
         pacc = m_min(v, pacc);
       } else {
         pacc = m_max(m_min(v, pacc) - m_corr(m_abs(v - pacc)), T(0.0));

@@ -82,8 +82,14 @@ int DeviceDecoder::decode_latency(const void *llrs, bool llrs_f64, bool host_poi
   if (lp.grid == 0) {
     int cus = 0, per_cu_f = 0, per_cu_d = 0;
     hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, dev::latency_minsum_kernel<float>, 1024, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, dev::latency_minsum_kernel<double>, 1024, 0);
+    // (the kernel this handle launches: the corrected form for a normalized / offset implementation)
+    const bool corr = impl_.correction != Correction::None;
+    if (e == hipSuccess)
+      e = corr ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, dev::latency_minsum_kernel_corr<float>, 1024, 0)
+               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, dev::latency_minsum_kernel<float>, 1024, 0);
+    if (e == hipSuccess)
+      e = corr ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, dev::latency_minsum_kernel_corr<double>, 1024, 0)
+               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, dev::latency_minsum_kernel<double>, 1024, 0);
     const int resident = e == hipSuccess ? cus * std::min(per_cu_f, per_cu_d) : 0;
     if (resident < 8) {  // cannot be co-resident in any useful number: this handle keeps the batched kernels
       opt_latency_ = 0;
@@ -93,16 +99,24 @@ int DeviceDecoder::decode_latency(const void *llrs, bool llrs_f64, bool host_poi
     lp.grid = static_cast<uint32_t>(std::min(resident, 256));
   }
   const uint32_t grid = lp.grid;
-  if (llrs_f64)
-    dev::latency_minsum_kernel<double><<<grid, 1024, 0, s>>>(t, lp.slots, lp.d_sync, static_cast<const double *>(d_llrs),
-                                                            static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
-                                                            max_iterations, d_bits, static_cast<uint32_t>(out_len), d_iters,
-                                                            static_cast<double *>(d_post), o_err);
-  else
-    dev::latency_minsum_kernel<float><<<grid, 1024, 0, s>>>(t, lp.slots, lp.d_sync, static_cast<const float *>(d_llrs),
-                                                           static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
-                                                           max_iterations, d_bits, static_cast<uint32_t>(out_len), d_iters,
-                                                           static_cast<float *>(d_post), o_err);
+  // one launch, four kernels: the caller's LLR type x plain / corrected arithmetic (a corrected implementation never takes
+  // the plain kernel)
+  auto go = [&](auto kernel, auto *src, auto *dst, auto... extra) {
+    kernel<<<grid, 1024, 0, s>>>(t, lp.slots, lp.d_sync, src, static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
+                                 max_iterations, d_bits, static_cast<uint32_t>(out_len), d_iters, dst, o_err, extra...);
+  };
+  const dev::MinsumCorr<float> mc{static_cast<float>(impl_.alpha()), static_cast<float>(impl_.beta())};
+  if (impl_.correction != Correction::None) {
+    if (llrs_f64)
+      go(dev::latency_minsum_kernel_corr<double>, static_cast<const double *>(d_llrs), static_cast<double *>(d_post), mc);
+    else
+      go(dev::latency_minsum_kernel_corr<float>, static_cast<const float *>(d_llrs), static_cast<float *>(d_post), mc);
+  } else {
+    if (llrs_f64)
+      go(dev::latency_minsum_kernel<double>, static_cast<const double *>(d_llrs), static_cast<double *>(d_post));
+    else
+      go(dev::latency_minsum_kernel<float>, static_cast<const float *>(d_llrs), static_cast<float *>(d_post));
+  }
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s));
   if (*o_err != 0) {
@@ -153,20 +167,27 @@ const void *edge_kernel_s(bool layered) {
                  : reinterpret_cast<const void *>(dev::latency_edge_kernel<RULE, T, SrcT, false>);
 }
 template <typename T, typename SrcT>
-const void *edge_kernel_r(Rule rule, bool layered) {
+const void *edge_kernel_r(Rule rule, bool corrected, bool layered) {
   switch (rule) {
     case Rule::Phi: return edge_kernel_s<dev::kRulePhi, T, SrcT>(layered);
     case Rule::Tanh: return edge_kernel_s<dev::kRuleTanh, T, SrcT>(layered);
     case Rule::Minstarapprox: return edge_kernel_s<dev::kRuleMinstarapprox, T, SrcT>(layered);
     case Rule::Aminstar: return edge_kernel_s<dev::kRuleAminstar, T, SrcT>(layered);
-    default: return edge_kernel_s<dev::kRuleMinsum, T, SrcT>(layered);
+    case Rule::Minsum:
+      // normalized / offset min-sum: latency_edge_kernel_corr (one more argument: dev::MinsumCorr<T>)
+      if (corrected)
+        return layered ? reinterpret_cast<const void *>(dev::latency_edge_kernel_corr<dev::kRuleMinsumCorr, T, SrcT, true>)
+                       : reinterpret_cast<const void *>(dev::latency_edge_kernel_corr<dev::kRuleMinsumCorr, T, SrcT, false>);
+      return edge_kernel_s<dev::kRuleMinsum, T, SrcT>(layered);
   }
+  return nullptr;  // (no such rule: the launch fails)
 }
-const void *edge_kernel(Rule rule, bool arith_i8, bool arith_f64, bool src_f64, bool layered) {
+const void *edge_kernel(Rule rule, bool corrected, bool arith_i8, bool arith_f64, bool src_f64, bool layered) {
   if (arith_i8)  // the rule (Minstarapprox / A-Min*) and its options are run-time arguments (dev::I8Opts)
     return src_f64 ? edge_kernel_s<dev::kRuleEdgeI8, int32_t, double>(layered) : edge_kernel_s<dev::kRuleEdgeI8, int32_t, float>(layered);
-  if (arith_f64) return src_f64 ? edge_kernel_r<double, double>(rule, layered) : edge_kernel_r<double, float>(rule, layered);
-  return src_f64 ? edge_kernel_r<float, double>(rule, layered) : edge_kernel_r<float, float>(rule, layered);
+  if (arith_f64)
+    return src_f64 ? edge_kernel_r<double, double>(rule, corrected, layered) : edge_kernel_r<double, float>(rule, corrected, layered);
+  return src_f64 ? edge_kernel_r<float, double>(rule, corrected, layered) : edge_kernel_r<float, float>(rule, corrected, layered);
 }
 }  // namespace
 
@@ -176,6 +197,7 @@ int DeviceDecoder::decode_latency_edge(const void *llrs, bool llrs_f64, bool hos
   std::lock_guard<std::mutex> one_at_a_time(g_latency_mutex);
   EdgeLatencyPath &lp = *lat_edge_;
   const size_t in_elem = llrs_f64 ? 8 : 4, elem = impl_.f64 ? 8 : 4;
+  const bool corrected = impl_.correction != Correction::None;
   const uint32_t n = static_cast<uint32_t>(n_), m = static_cast<uint32_t>(m_);
   last_lanes_ = 1;
   last_group_ = batch;
@@ -207,8 +229,8 @@ int DeviceDecoder::decode_latency_edge(const void *llrs, bool llrs_f64, bool hos
     // every workgroup of the persistent launch must be resident (see decode_latency)
     int cus = 0, per_cu_f = 0, per_cu_d = 0;
     hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, edge_kernel(impl_.rule, impl_.i8, impl_.f64, false, lp.layered), 1024, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, edge_kernel(impl_.rule, impl_.i8, impl_.f64, true, lp.layered), 1024, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, false, lp.layered), 1024, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, true, lp.layered), 1024, 0);
     const int resident = e == hipSuccess ? cus * std::min(per_cu_f, per_cu_d) : 0;
     if (resident < 8) {
       opt_latency_ = 0;
@@ -246,8 +268,17 @@ int DeviceDecoder::decode_latency_edge(const void *llrs, bool llrs_f64, bool hos
                        lp.d_lane_info, lp.d_var_ptr, lp.d_var_lane, d_src_block_, pattern_len_ ? n / pattern_len_ : 0};
   uint32_t in_len = static_cast<uint32_t>(input_len_), nb = static_cast<uint32_t>(batch), ol = static_cast<uint32_t>(out_len);
   dev::I8Opts i8o{impl_.rule == Rule::Aminstar, impl_.jones, impl_.hardlimit, impl_.deg1clip};
-  void *args[] = {&t, &lp.slots, &lp.d_sync, &d_llrs, &in_len, &nb, &max_iterations, &d_bits, &ol, &d_iters, &d_post, &o_err, &bundle, &i8o};
-  HIP_TRY(hipLaunchKernel(edge_kernel(impl_.rule, impl_.i8, impl_.f64, llrs_f64, lp.layered), dim3(lp.grid), dim3(1024), args, 0, s));
+  // the corrected kernels' last argument, in the decoder's type (the others take the first 14)
+  dev::MinsumCorr<float> mc_f{static_cast<float>(impl_.alpha()), static_cast<float>(impl_.beta())};
+  dev::MinsumCorr<double> mc_d{impl_.alpha(), impl_.beta()};
+  void *args[] = {&t, &lp.slots, &lp.d_sync, &d_llrs, &in_len, &nb, &max_iterations, &d_bits, &ol, &d_iters, &d_post, &o_err, &bundle, &i8o,
+                  impl_.f64 ? static_cast<void *>(&mc_d) : static_cast<void *>(&mc_f)};
+  const void *kernel = edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, llrs_f64, lp.layered);
+  if (kernel == nullptr) {
+    fail("internal error: no small-batch kernel for this rule");
+    return -3;
+  }
+  HIP_TRY(hipLaunchKernel(kernel, dim3(lp.grid), dim3(1024), args, 0, s));
   HIP_TRY(hipStreamSynchronize(s));
   if (*o_err != 0) {
     opt_latency_ = 0;  // see decode_latency

@@ -8,13 +8,19 @@ namespace ldpc {
 
 template <typename T>
 struct Launch {
+  // normalized / offset min-sum (g_knobs.corr): every min-sum launch below then takes the kernel's *_kernel_corr form with
+  // (alpha, beta) in the decoder's type -- there is no plain-arithmetic launch a corrected implementation could fall into
+  static dev::MinsumCorr<T> mc() { return dev::MinsumCorr<T>{static_cast<T>(g_knobs.alpha), static_cast<T>(g_knobs.beta)}; }
   // flooding min-sum check nodes: VEC x mask width x unroll x FIRST
   template <int VEC, typename MASK, bool FIRST>
   static void cn_minsum_u(const Tiling &t, hipStream_t s, const dev::Graph &g,
                           const dev::State &st, const T *L, T *msg, uint32_t *unsat) {
     // (eight loads in flight, nontemporal messages: the four-load and the cached-message variants were tuning knobs within
     // a percent of these, gone in round 6)
-    dev::cn_minsum_kernel<T, VEC, MASK, 8, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, L, msg, unsat);
+    if (g_knobs.corr)
+      dev::cn_minsum_kernel_corr<T, VEC, MASK, 8, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, L, msg, unsat, mc());
+    else
+      dev::cn_minsum_kernel<T, VEC, MASK, 8, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, L, msg, unsat);
   }
   template <int VEC, bool FIRST>
   static void cn_minsum_m(bool wide_mask, const Tiling &t, hipStream_t s, const dev::Graph &g,
@@ -29,8 +35,12 @@ struct Launch {
   static void cn_lfree_u(const Tiling &t, hipStream_t s, const dev::Graph &g, const dev::State &st, const T *chan,
                          T *post, const T *msg_in, T *msg_out, uint32_t *unsat) {
     // (four loads in flight, nontemporal stores, cached loads of the previous messages: what round 2 settled on)
-    dev::cn_minsum_lfree_kernel<T, VEC, MASK, 4, FIRST, true, false><<<t.blocks, t.threads, 0, s>>>(
-        g, t.sched, st, chan, post, msg_in, msg_out, unsat);
+    if (g_knobs.corr)
+      dev::cn_minsum_lfree_kernel_corr<T, VEC, MASK, 4, FIRST, true, false><<<t.blocks, t.threads, 0, s>>>(
+          g, t.sched, st, chan, post, msg_in, msg_out, unsat, mc());
+    else
+      dev::cn_minsum_lfree_kernel<T, VEC, MASK, 4, FIRST, true, false><<<t.blocks, t.threads, 0, s>>>(
+          g, t.sched, st, chan, post, msg_in, msg_out, unsat);
   }
   template <int VEC, bool FIRST>
   static void cn_lfree_m(bool wide_mask, const Tiling &t, hipStream_t s, const dev::Graph &g, const dev::State &st,
@@ -60,12 +70,21 @@ struct Launch {
     // (rows of at most 8 edges -- DVB-S2 up to rate 1/2, most 5G NR rows are longer -- take the variant without the
     // further-rounds code)
     // (eight loads in flight per lane; the four-load variant of earlier rounds, a tuning knob nothing selected, is gone)
-    if (g_knobs.rec_long)
-      dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, true><<<t.blocks, t.threads, 0, s>>>(
-          g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run);
-    else
-      dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, false><<<t.blocks, t.threads, 0, s>>>(
-          g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run);
+    if (g_knobs.rec_long) {
+      if (g_knobs.corr)
+        dev::cn_minsum_rec_kernel_corr<T, VEC, RECW, 8, FIRST, true, false, true><<<t.blocks, t.threads, 0, s>>>(
+            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run, mc());
+      else
+        dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, true><<<t.blocks, t.threads, 0, s>>>(
+            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run);
+    } else {
+      if (g_knobs.corr)
+        dev::cn_minsum_rec_kernel_corr<T, VEC, RECW, 8, FIRST, true, false, false><<<t.blocks, t.threads, 0, s>>>(
+            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run, mc());
+      else
+        dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, false><<<t.blocks, t.threads, 0, s>>>(
+            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run);
+    }
   }
   template <int VEC, bool FIRST>
   static void cn_rec_w(uint32_t recw, const Tiling &t, hipStream_t s, const dev::Graph &g, const dev::State &st, const T *chan,
@@ -112,6 +131,21 @@ struct Launch {
       cn_minsum_m<1, FIRST>(wide_mask, t, s, g, st, L, msg, unsat);
   }
 
+  // flooding, LDS-staged: normalized / offset min-sum (cn_staged_kernel_corr)
+  template <bool FIRST>
+  static void cn_staged_corr(const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g, const dev::State &st,
+                             const T *L, T *msg, uint32_t *unsat, uint32_t dmax) {
+    if (g_knobs.row_scratch) {
+      dev::cn_staged_kernel_corr<dev::kRuleMinsumCorr, T, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, L, msg, unsat, dmax,
+                                                                               static_cast<T *>(g_knobs.row_scratch), mc());
+      return;
+    }
+    auto k = dev::cn_staged_kernel_corr<dev::kRuleMinsumCorr, T, FIRST>;
+    if (lds > 48 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                static_cast<int>(lds));
+    k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, L, msg, unsat, dmax, nullptr, mc());
+  }
   // flooding, LDS-staged rules
   template <int RULE, bool FIRST>
   static void cn_staged_r(const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g, const dev::State &st,
@@ -173,7 +207,10 @@ struct Launch {
         cn_staged_r<dev::kRuleAminstar, FIRST>(reg_dmax, recs, t, lds, s, g, st, L, msg, unsat, dmax);
         break;
       case Rule::Minsum:
-        cn_staged_r<dev::kRuleMinsum, FIRST>(reg_dmax, recs, t, lds, s, g, st, L, msg, unsat, dmax);
+        if (g_knobs.corr)  // (reg_dmax is 0: the register-resident form is the Tanh rule's)
+          cn_staged_corr<FIRST>(t, lds, s, g, st, L, msg, unsat, dmax);
+        else
+          cn_staged_r<dev::kRuleMinsum, FIRST>(reg_dmax, recs, t, lds, s, g, st, L, msg, unsat, dmax);
         break;
     }
   }
@@ -262,6 +299,33 @@ struct Launch {
       k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax, nullptr);
     }
   }
+  // normalized / offset min-sum through the level kernels (hl_level_kernel_corr, hl_level_reg_kernel_corr)
+  template <bool FIRST>
+  static void hl_corr(uint32_t reg_dmax, const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g,
+                      const dev::State &st, const uint32_t *level_rows, uint32_t n_level, T *Q, T *R, uint32_t dmax) {
+    auto launch = [&](auto k) {
+      if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  static_cast<int>(lds));
+      k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax, mc());
+    };
+    if (reg_dmax == 10)
+      launch(dev::hl_level_reg_kernel_corr<dev::kRuleMinsumCorr, T, 10, FIRST>);
+    else if (reg_dmax == 12)
+      launch(dev::hl_level_reg_kernel_corr<dev::kRuleMinsumCorr, T, 12, FIRST>);
+    else if (reg_dmax == 24)
+      launch(dev::hl_level_reg_kernel_corr<dev::kRuleMinsumCorr, T, 24, FIRST>);
+    else if (g_knobs.row_scratch) {
+      dev::hl_level_kernel_corr<dev::kRuleMinsumCorr, T, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax,
+                                                                              static_cast<T *>(g_knobs.row_scratch), mc());
+    } else {
+      auto k = dev::hl_level_kernel_corr<dev::kRuleMinsumCorr, T, FIRST>;
+      if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  static_cast<int>(lds));
+      k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax, nullptr, mc());
+    }
+  }
   template <bool FIRST>
   static void hl(Rule rule, uint32_t reg_dmax, const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g,
                  const dev::State &st, const uint32_t *level_rows, uint32_t n_level, T *Q, T *R, uint32_t dmax) {
@@ -291,7 +355,10 @@ struct Launch {
         hl_rr<dev::kRuleAminstar, FIRST>(reg_dmax, t, lds, s, g, st, level_rows, n_level, Q, R, dmax);
         break;
       case Rule::Minsum:
-        hl_rr<dev::kRuleMinsum, FIRST>(reg_dmax, t, lds, s, g, st, level_rows, n_level, Q, R, dmax);
+        if (g_knobs.corr)
+          hl_corr<FIRST>(reg_dmax, t, lds, s, g, st, level_rows, n_level, Q, R, dmax);
+        else
+          hl_rr<dev::kRuleMinsum, FIRST>(reg_dmax, t, lds, s, g, st, level_rows, n_level, Q, R, dmax);
         break;
     }
   }
@@ -300,7 +367,10 @@ struct Launch {
   template <int VEC, bool FIRST>
   static void hl_minsum_v(const Tiling &t, hipStream_t s, const dev::Graph &g,
                           const dev::State &st, const uint32_t *level_rows, uint32_t n_level, T *Q, T *R) {
-    dev::hl_minsum_kernel<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+    if (g_knobs.corr)
+      dev::hl_minsum_kernel_corr<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
+    else
+      dev::hl_minsum_kernel<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
   }
   // register-resident rows: DMAX bucket of the level's largest row; vec capped so that the
   // 2 * DMAX * VEC values fit the register file with some occupancy left
@@ -321,20 +391,32 @@ struct Launch {
                               const dev::State &st, const uint32_t *level_rows, uint32_t n_level, T *Q, T *R) {
     switch (dmax) {
       case 8:
-        dev::hl_minsum_reg_kernel<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+        if (g_knobs.corr)
+          dev::hl_minsum_reg_kernel_corr<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
+        else
+          dev::hl_minsum_reg_kernel<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
         return true;
       case 12:
-        dev::hl_minsum_reg_kernel<T, VEC, 12, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+        if (g_knobs.corr)
+          dev::hl_minsum_reg_kernel_corr<T, VEC, 12, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
+        else
+          dev::hl_minsum_reg_kernel<T, VEC, 12, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
         return true;
       case 20:
         if constexpr (VEC * sizeof(T) <= 8) {
-          dev::hl_minsum_reg_kernel<T, VEC, 20, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+          if (g_knobs.corr)
+            dev::hl_minsum_reg_kernel_corr<T, VEC, 20, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
+          else
+            dev::hl_minsum_reg_kernel<T, VEC, 20, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
           return true;
         }
         return false;
       case 32:
         if constexpr (VEC * sizeof(T) <= 4) {
-          dev::hl_minsum_reg_kernel<T, VEC, 32, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+          if (g_knobs.corr)
+            dev::hl_minsum_reg_kernel_corr<T, VEC, 32, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
+          else
+            dev::hl_minsum_reg_kernel<T, VEC, 32, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
           return true;
         }
         return false;
@@ -363,20 +445,32 @@ struct Launch {
     constexpr uint32_t kWords = VEC * sizeof(T) / 4;
     switch (dmax) {
       case 8:
-        dev::hl_minsum_rec_kernel<T, VEC, 8, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
+        if (g_knobs.corr)
+          dev::hl_minsum_rec_kernel_corr<T, VEC, 8, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec, mc());
+        else
+          dev::hl_minsum_rec_kernel<T, VEC, 8, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
         return true;
       case 12:
-        dev::hl_minsum_rec_kernel<T, VEC, 12, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
+        if (g_knobs.corr)
+          dev::hl_minsum_rec_kernel_corr<T, VEC, 12, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec, mc());
+        else
+          dev::hl_minsum_rec_kernel<T, VEC, 12, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
         return true;
       case 20:
         if constexpr ((20 + 6) * kWords <= 112) {
-          dev::hl_minsum_rec_kernel<T, VEC, 20, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
+          if (g_knobs.corr)
+            dev::hl_minsum_rec_kernel_corr<T, VEC, 20, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec, mc());
+          else
+            dev::hl_minsum_rec_kernel<T, VEC, 20, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
           return true;
         }
         return false;
       case 32:
         if constexpr ((32 + 6) * kWords <= 112) {
-          dev::hl_minsum_rec_kernel<T, VEC, 32, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
+          if (g_knobs.corr)
+            dev::hl_minsum_rec_kernel_corr<T, VEC, 32, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec, mc());
+          else
+            dev::hl_minsum_rec_kernel<T, VEC, 32, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
           return true;
         }
         return false;

@@ -28,6 +28,9 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
 
   g_knobs.rec_long = max_row_weight_ > 8 || opt_rec_long_;
   g_knobs.fast = impl_.fast;
+  g_knobs.corr = impl_.correction != Correction::None;
+  g_knobs.alpha = impl_.alpha();
+  g_knobs.beta = impl_.beta();
   g_knobs.row_scratch = nullptr;
   dev::Graph g{d_row_ptr_, d_edge_col_, d_col_ptr_, d_col_edge_, m, n, static_cast<uint32_t>(e_),
                nullptr,    nullptr,     nullptr,    0,           d_edge_aux_, d_edge_peer_};

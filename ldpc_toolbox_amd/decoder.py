@@ -11,6 +11,8 @@ Names and argument meaning follow the reference so that tests read like its own:
 The batched calls (`decode_batch`, `decode_batch_device`) are the extension the GPU needs.
 """
 import ctypes as C
+import math
+import re
 from dataclasses import dataclass
 
 import numpy as np
@@ -29,6 +31,25 @@ ALL_IMPLEMENTATIONS = IMPLEMENTATIONS + I8_IMPLEMENTATIONS
 # opt-in approximate variants (native exp2 / log2 / rcp instead of the glibc-identical functions): NOT bit-identical to
 # the reference, never chosen unless asked for by name
 FAST_IMPLEMENTATIONS = ("Tanhf32@fast", "HLTanhf32@fast", "Phif32@fast", "HLPhif32@fast")
+# normalized and offset min-sum with their default values (alpha = 0.75, beta = 0.5): the Minsum decoder whose check
+# rows send alpha * m or max(m - beta, 0) instead of the magnitude m.  Any of them also takes ":value" -- digits[.digits],
+# 0 < alpha <= 1, beta >= 0 -- as in "NormMinsumf32:0.8125".  Not the reference's, so not part of ALL_IMPLEMENTATIONS.
+CORRECTED_MINSUM_IMPLEMENTATIONS = tuple(p + r + s for p in ("", "HL") for r in ("NormMinsum", "OffsetMinsum")
+                                         for s in ("f64", "f32"))
+_CORRECTED = re.compile(r"(?:HL)?(Norm|Offset)Minsumf(?:32|64)(?::([0-9]+(?:\.[0-9]+)?))?", re.ASCII)
+
+
+def corrected_minsum(name: str):
+    """("Norm" | "Offset", value) for a valid normalized / offset min-sum name, None for anything else (the rules of
+    csrc/implementation.cpp: the value is digits[.digits], 0 < alpha <= 1, beta >= 0 and finite)."""
+    m = _CORRECTED.fullmatch(name)
+    if not m:
+        return None
+    kind = m.group(1)
+    value = float(m.group(2)) if m.group(2) is not None else (0.75 if kind == "Norm" else 0.5)
+    if not math.isfinite(value) or (kind == "Norm" and not 0.0 < value <= 1.0):
+        return None
+    return kind, value
 
 
 class DecoderUnavailable(RuntimeError):
@@ -173,7 +194,7 @@ class DecoderImplementation:
     """FromStr / Display / DecoderFactory of the reference's enum (factory.rs:211-236)."""
 
     def __init__(self, name: str):
-        if name not in ALL_IMPLEMENTATIONS:
+        if name not in ALL_IMPLEMENTATIONS and corrected_minsum(name) is None:
             raise ValueError("invalid decoder implementation")  # factory.rs:221
         self.name = name
 
