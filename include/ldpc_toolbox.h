@@ -48,7 +48,15 @@ extern "C" {
  * becomes alpha * m (0 < alpha <= 1, default 0.75) or max(m - beta, 0) (beta >= 0, default 0.5), in the decoder's type,
  * each result rounded once; the sign is plain min-sum's, so a magnitude clamped to zero sends +0.0 or -0.0.  The value
  * is digits[.digits] (no sign, no exponent): "NormMinsumf32", "HLOffsetMinsumf64:0.3", "NormMinsumf32:0.8125@hip:1".
- * "NormMinsumf32:1" and "OffsetMinsumf32:0" decode exactly as "Minsumf32"; there is no 8-bit and no "@fast" form;
+ * "NormMinsumf32:1" and "OffsetMinsumf32:0" decode exactly as "Minsumf32"; there is no "@fast" form, and the 8-bit
+ * forms are spelled differently:
+ * [HL]Minsumi8[Norm|Offset][Jones][PartialHardLimit][Deg1Clip][:value] is 8-bit min-sum: Minstarapproxi8's quantised
+ * arithmetic (8 steps per LLR unit, clip at +-127), options and schedules -- with HL only PartialHardLimit -- with the
+ * check-node fold step reduced to min.  The magnitude m (0..127) becomes (a * m + 8) >> 4 with a = 16 * value in 1..16
+ * (Norm, default value 0.75) or max(m - b, 0) with b = 8 * value in 0..127 (Offset, default value 0.5), both products
+ * integers; the hard limit, if named, follows the correction.  A value is allowed only after Norm or Offset:
+ * "Minsumi8", "Minsumi8NormJones:0.8125", "HLMinsumi8OffsetPartialHardLimit".  "Minsumi8Norm:1" and "Minsumi8Offset:0"
+ * decode exactly as "Minsumi8"; "NormMinsumi8" and its like are invalid;
  * an optional "@hip:N" suffix, last, selects GPU N); puncturing: "" or a pattern such as "1,1,1,0"
  * (src/cli/ber.rs:219-229).  Returns an opaque handle, or NULL on any error. */
 void *ldpc_toolbox_decoder_ctor(const char *alist_file_path, const char *implementation,
@@ -189,7 +197,8 @@ int32_t ldpc_toolbox_decoder_syndrome_device(void *decoder, const uint8_t *bits,
  * "preferred_group" (codewords per group of a large call: "group_size" if set, else 4096, more for small graphs),
  * "row_records" (words per check-row record when flooding min-sum keeps a row's messages as
  * {min1, min2, flip bits, argmin}; 0 = per-edge messages), "minsum_correction" (0: none, 1: normalized min-sum,
- * 2: offset min-sum).  returns 0 or -1 (unknown key). */
+ * 2: offset min-sum), "minsum_correction_int" (the 8-bit min-sum names: the integer the kernels use, 16 * alpha or
+ * 8 * beta; 0 for every other name).  returns 0 or -1 (unknown key). */
 int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value);
 /* Tunables: "group_size" (codewords decoded together; 0 = automatic), "profiling" (0/1:
  * bracket the check/variable/layer launches with hipEvents), and 26 launch / execution choices -- "waves", "vec", "tile",

@@ -492,6 +492,8 @@ int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value)
     *value = d.row_records();
   else if (k == "minsum_correction")
     *value = static_cast<int64_t>(d.implementation().correction);
+  else if (k == "minsum_correction_int")  // the 8-bit min-sum names: a = 16 alpha or b = 8 beta, 0 for every other name
+    *value = d.implementation().correction_int;
   else if (k == "last_persist" || k == "experiments")  // (the removed experiment builds: always 0)
     *value = 0;
   else

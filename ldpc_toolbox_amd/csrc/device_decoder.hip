@@ -91,7 +91,7 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
   bool ok = upload(g.row_ptr, &d->d_row_ptr_) && upload(g.edge_col, &d->d_edge_col_) &&
             upload(g.col_ptr, &d->d_col_ptr_) && upload(g.col_edge, &d->d_col_edge_);
 
-  if (ok && impl.schedule == Schedule::Flooding && impl.rule == Rule::Minsum) {
+  if (ok && impl.schedule == Schedule::Flooding && impl.rule == Rule::Minsum && !impl.i8) {
     // L-free variables: degree 1 or 2 (kernels.hip.h, cn_minsum_lfree_kernel)
     std::vector<uint32_t> aux(std::max<uint32_t>(g.n_edges, 1), dev::kAuxNone);
     std::vector<uint32_t> keep_var, keep_ptr{0}, keep_edge, free_var, free_ptr{0}, free_edge;
@@ -121,7 +121,7 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
     }
     // row records (cn_minsum_rec_kernel): where the OTHER message of an L-free variable lives, as (row, slot)
     const uint32_t rec_bits = impl.f64 ? 64u : 32u, rec_packed = impl.f64 ? 58u : 26u;
-    if (ok && d->lfree_ready_ && !impl.i8 && g.max_row_weight <= rec_bits && g.n_rows < dev::kPeerSingle) {
+    if (ok && d->lfree_ready_ && g.max_row_weight <= rec_bits && g.n_rows < dev::kPeerSingle) {
       std::vector<uint32_t> rs(std::max<uint32_t>(g.n_edges, 1));  // edge -> row << 6 | slot
       for (uint32_t r = 0; r < g.n_rows; r++)
         for (uint32_t e = g.row_ptr[r]; e < g.row_ptr[r + 1]; e++) rs[e] = (r << 6) | (e - g.row_ptr[r]);
@@ -268,7 +268,8 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
   // small-batch path with a lane per edge (latency_edge.hip.h): the rows are packed, whole, into chunks of at most 64
   // lanes (one wavefront) -- level after level for the layered schedule, all rows in order for flooding, which also
   // gets the variables' edge lists (cols[v] order) as lane indices.  Flooding Minsumf32 keeps latency.hip.h's kernel.
-  if (ok && !impl.fast && g.max_row_weight <= 64 && g.n_rows > 0 && d->lat_ == nullptr &&
+  // (the 8-bit min-sum names take the batched kernels at every batch size: a min-sum row is cheap enough there)
+  if (ok && !impl.fast && !(impl.i8 && impl.rule == Rule::Minsum) && g.max_row_weight <= 64 && g.n_rows > 0 && d->lat_ == nullptr &&
       (impl.schedule == Schedule::Flooding || d->level_ptr_.size() <= size_t(opt_serial_levels_default()) + 1)) {
     auto *lp = new EdgeLatencyPath();
     lp->layered = impl.schedule == Schedule::Layered;

@@ -49,7 +49,7 @@ bool parse_implementation(const std::string &name, Implementation *out, std::str
     const size_t l = std::strlen(s.text);
     if (std::strncmp(p, s.text, l) != 0) continue;
     const char *suffix = p + l;
-    if (std::strncmp(suffix, "f32", 3) != 0 && std::strncmp(suffix, "f64", 3) != 0) break;  // (no 8-bit variants)
+    if (std::strncmp(suffix, "f32", 3) != 0 && std::strncmp(suffix, "f64", 3) != 0) break;  // (the 8-bit forms are spelled Minsumi8Norm / Minsumi8Offset)
     Implementation c = impl;
     c.rule = Rule::Minsum;
     c.f64 = suffix[1] == '6';
@@ -83,12 +83,24 @@ bool parse_implementation(const std::string &name, Implementation *out, std::str
       *out = impl;
       return true;
     }
-    if (std::strncmp(suffix, "i8", 2) == 0 && (s.rule == Rule::Minstarapprox || s.rule == Rule::Aminstar)) {
+    if (std::strncmp(suffix, "i8", 2) == 0 && s.rule != Rule::Phi && s.rule != Rule::Tanh) {
       // factory.rs:246-263, 270-275: optional Jones / PartialHardLimit / Deg1Clip, in this order;
       // the layered schedule exists only with and without PartialHardLimit
       const char *q = suffix + 2;
       impl.rule = s.rule;
       impl.i8 = true;
+      if (s.rule == Rule::Minsum) {
+        // Minsumi8[Norm|Offset]<options>[:value]: the correction follows "i8", its value the options
+        if (std::strncmp(q, "Norm", 4) == 0) {
+          impl.correction = Correction::Normalized;
+          impl.correction_value = 0.75;
+          q += 4;
+        } else if (std::strncmp(q, "Offset", 6) == 0) {
+          impl.correction = Correction::Offset;
+          impl.correction_value = 0.5;
+          q += 6;
+        }
+      }
       if (std::strncmp(q, "Jones", 5) == 0) {
         impl.jones = true;
         q += 5;
@@ -100,6 +112,17 @@ bool parse_implementation(const std::string &name, Implementation *out, std::str
       if (std::strncmp(q, "Deg1Clip", 8) == 0) {
         impl.deg1clip = true;
         q += 8;
+      }
+      if (*q == ':' && impl.correction != Correction::None && plain_decimal(q + 1)) {
+        impl.correction_value = std::strtod(q + 1, nullptr);
+        q += std::strlen(q);
+      }
+      if (impl.correction != Correction::None) {
+        // the kernels' integers: a = 16 alpha in 1..16, b = 8 beta in 0..127, exactly
+        const bool norm = impl.correction == Correction::Normalized;
+        const double scaled = impl.correction_value * (norm ? 16.0 : 8.0);
+        if (!(scaled >= (norm ? 1.0 : 0.0) && scaled <= (norm ? 16.0 : 127.0)) || scaled != std::floor(scaled)) break;
+        impl.correction_int = static_cast<int>(scaled);
       }
       if (*q == 0 && !(impl.schedule == Schedule::Layered && (impl.jones || impl.deg1clip))) {
         *out = impl;
@@ -135,6 +158,18 @@ std::vector<std::string> corrected_minsum_implementation_names() {
   for (const char *prefix : {"", "HL"})
     for (const CorrectedStem &s : kCorrectedStems)
       for (const char *suffix : {"f64", "f32"}) v.push_back(std::string(prefix) + s.text + suffix);
+  return v;
+}
+
+std::vector<std::string> minsum_i8_implementation_names() {
+  std::vector<std::string> v;
+  for (const char *base : {"Minsumi8", "Minsumi8Norm", "Minsumi8Offset"}) {
+    for (const char *j : {"", "Jones"})
+      for (const char *h : {"", "PartialHardLimit"})
+        for (const char *d : {"", "Deg1Clip"}) v.push_back(std::string(base) + j + h + d);
+    v.push_back(std::string("HL") + base);
+    v.push_back(std::string("HL") + base + "PartialHardLimit");
+  }
   return v;
 }
 

@@ -1,7 +1,9 @@
-// The 8-bit quantised rules: DeviceDecoder::run_group_i8 and every kernel it launches (kernels_i8.hip.h).
+// The 8-bit quantised rules: DeviceDecoder::run_group_i8 and every kernel it launches (kernels_i8.hip.h,
+// kernels_i8_minsum.hip.h).
 #define LDPC_I8_KERNELS_TU 1  // this translation unit compiles the 8-bit rules' one non-template kernel
 #include "device_decoder_internal.h"
 #include "kernels_i8.hip.h"
+#include "kernels_i8_minsum.hip.h"
 
 namespace ldpc {
 
@@ -31,6 +33,10 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
   const ProgressPoll poll{(opt_poll_ && w.d_flag) ? w.h_flag : nullptr, w.epoch, may_block,
                           t_pace_lead ? t_pace_lead : (impl_.schedule == Schedule::Layered ? 2u : 8u), s};
   const dev::I8Opts o{impl_.rule == Rule::Aminstar, impl_.jones, impl_.hardlimit, impl_.deg1clip};
+  // Minsumi8*: check nodes without LDS or scratch (kernels_i8_minsum.hip.h); a = 16 and b = 0 are the plain rule
+  const bool minsum = impl_.rule == Rule::Minsum;
+  const dev::I8MinsumOpts mo{impl_.hardlimit, impl_.correction == Correction::Normalized ? impl_.correction_int : 16,
+                             impl_.correction == Correction::Offset ? impl_.correction_int : 0};
 
   grp::init_group(s, w.done, w.iters, w.unsat0, w.unsat1, w.n_active, w.n_slots,
                                                          w.slot_cw, static_cast<uint32_t>(nb), G);
@@ -74,7 +80,11 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
   uint32_t threads = 256;
   size_t lds = 0;
   // rows beyond the LDS (more than 320 edges): the columns live in HBM, one region per wavefront of a small launch
-  const bool i8_fits = staged_block(2, max_row_weight_, 4, &threads, &lds) && lds + 32 <= 160 * 1024;
+  const bool i8_fits = minsum || (staged_block(2, max_row_weight_, 4, &threads, &lds) && lds + 32 <= 160 * 1024);
+  if (minsum) {
+    threads = 256;
+    lds = 0;
+  }
   if (!i8_fits) {
     threads = kScratchThreads;
     lds = 0;
@@ -82,7 +92,7 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
     if (int rc = ensure_row_scratch(w, waves_bound * 2 * max_row_weight_ * 64 * 4)) return rc;
   }
   uint32_t *const i8_scratch = static_cast<uint32_t *>(w.row_scratch);
-  lds += 32;  // the correction lookup table (kernels_i8.hip.h, i8_table_init)
+  if (!minsum) lds += 32;  // the correction lookup table (kernels_i8.hip.h, i8_table_init)
   auto set_lds = [&](const void *k) {
     if (lds > 48 * 1024)
       (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
@@ -104,7 +114,12 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
       uint32_t *unsat_out = unsat[it & 1];
       const dev::State stp = ticked(it);
       timed_begin(kKernelCheck, s);
-      if (!i8_fits) {
+      if (minsum) {
+        if (first)
+          dev::cn_i8_minsum_kernel<true><<<cn_t.blocks, cn_t.threads, 0, s>>>(g, cn_t.sched, stp, mo, chan, post, msg, unsat_out);
+        else
+          dev::cn_i8_minsum_kernel<false><<<cn_t.blocks, cn_t.threads, 0, s>>>(g, cn_t.sched, stp, mo, chan, post, msg, unsat_out);
+      } else if (!i8_fits) {
         if (first)
           dev::cn_i8_kernel<true, true><<<cn_t.blocks, cn_t.threads, 0, s>>>(g, cn_t.sched, stp, o, chan, post, msg, unsat_out,
                                                                              max_row_weight_, i8_scratch);
@@ -162,7 +177,7 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
         }
         const uint32_t lreg = !opt_hl_reg_ ? 0 : (ldmax <= 12 ? 12 : (ldmax <= 24 ? 24 : 0));
         const Tiling t = make_tiling(G, tile, 256, serial ? 1 : cnt, lthreads, lfits ? target_waves : std::min(target_waves, kScratchWaves));
-        if (!lfits && scratch_bytes_for(t, ldmax, 4) > w.row_scratch_bytes) {
+        if (!minsum && !lfits && scratch_bytes_for(t, ldmax, 4) > w.row_scratch_bytes) {
           fail("internal error: row scratch smaller than a level's launch");
           return -3;
         }
@@ -178,8 +193,28 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
                                       static_cast<int>(llds));
           k<<<t.blocks, t.threads, llds, s>>>(g, t.sched, st, o, d_level_rows_ + r0, cnt, post, msg, ldmax, scratch);
         };
+        auto launch_minsum = [&](auto k) {
+          const Tiling mt = make_tiling(G, tile, 256, serial ? 1 : cnt, serial ? 64 : 256, target_waves);
+          k<<<mt.blocks, mt.threads, 0, s>>>(g, mt.sched, st, mo, d_level_rows_ + r0, cnt, post, msg);
+        };
         timed_begin(kKernelLayer, s);
-        if (it == 1) {
+        if (minsum) {
+          if (it == 1) {
+            if (lreg == 12)
+              launch_minsum(dev::hl_i8_minsum_kernel<12, true>);
+            else if (lreg == 24)
+              launch_minsum(dev::hl_i8_minsum_kernel<24, true>);
+            else
+              launch_minsum(dev::hl_i8_minsum_kernel<0, true>);
+          } else {
+            if (lreg == 12)
+              launch_minsum(dev::hl_i8_minsum_kernel<12, false>);
+            else if (lreg == 24)
+              launch_minsum(dev::hl_i8_minsum_kernel<24, false>);
+            else
+              launch_minsum(dev::hl_i8_minsum_kernel<0, false>);
+          }
+        } else if (it == 1) {
           if (lreg == 12)
             launch(dev::hl_i8_reg_kernel<12, true>);
           else if (lreg == 24)

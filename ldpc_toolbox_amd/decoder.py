@@ -51,6 +51,33 @@ def corrected_minsum(name: str):
         return None
     return kind, value
 
+# 8-bit min-sum with the default values (alpha = 0.75, beta = 0.5): Minstarapproxi8's quantised arithmetic and options with
+# the check-node fold reduced to min, and the magnitude m (quantiser units) corrected in integers -- (a * m + 8) >> 4 with
+# a = 16 alpha, or max(m - b, 0) with b = 8 beta.  The names with Norm / Offset also take ":value" (digits[.digits]; 16 alpha
+# an integer in 1..16, 8 beta an integer in 0..127), as in "Minsumi8NormJones:0.8125".  Not part of ALL_IMPLEMENTATIONS.
+MINSUM_I8_IMPLEMENTATIONS = tuple(
+    n for b in ("Minsumi8", "Minsumi8Norm", "Minsumi8Offset")
+    for n in tuple(b + j + h + d for j in ("", "Jones") for h in ("", "PartialHardLimit") for d in ("", "Deg1Clip"))
+    + ("HL" + b, "HL" + b + "PartialHardLimit"))
+_MINSUM_I8 = re.compile(r"(HL)?Minsumi8(Norm|Offset)?(Jones)?(PartialHardLimit)?(Deg1Clip)?(?::([0-9]+(?:\.[0-9]+)?))?", re.ASCII)
+
+
+def minsum_i8(name: str):
+    """(None | "Norm" | "Offset", the kernels' integer a = 16 alpha or b = 8 beta, 0 for the plain rule) for a valid 8-bit
+    min-sum name, None for anything else (the rules of csrc/implementation.cpp)."""
+    m = _MINSUM_I8.fullmatch(name)
+    if not m:
+        return None
+    layered, kind, jones, _, deg1, value = m.groups()
+    if (layered and (jones or deg1)) or (value is not None and kind is None):
+        return None
+    if kind is None:
+        return None, 0
+    scaled = (float(value) if value is not None else (0.75 if kind == "Norm" else 0.5)) * (16.0 if kind == "Norm" else 8.0)
+    if scaled != math.floor(scaled) or not (1.0 if kind == "Norm" else 0.0) <= scaled <= (16.0 if kind == "Norm" else 127.0):
+        return None
+    return kind, int(scaled)
+
 
 class DecoderUnavailable(RuntimeError):
     """ctor returned NULL (no GPU, bad alist, unknown implementation, bad pattern)."""
@@ -194,7 +221,7 @@ class DecoderImplementation:
     """FromStr / Display / DecoderFactory of the reference's enum (factory.rs:211-236)."""
 
     def __init__(self, name: str):
-        if name not in ALL_IMPLEMENTATIONS and corrected_minsum(name) is None:
+        if name not in ALL_IMPLEMENTATIONS and corrected_minsum(name) is None and minsum_i8(name) is None:
             raise ValueError("invalid decoder implementation")  # factory.rs:221
         self.name = name
 
