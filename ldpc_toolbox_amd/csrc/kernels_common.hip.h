@@ -237,8 +237,12 @@ struct Limits<double> {
 // serves both: c = max(alpha * m - beta, 0) with beta = 0 (normalized) or alpha = 1 (offset) -- 1 * m and x - 0 are exact and
 // x >= 0, so the two definitions come out bit for bit.  m is never NaN and never negative, alpha * m - beta is never -0.0
 // (+0 - 0 = +0), so the select below is the maximum, and +inf (a row of one edge) stays +inf.
-// The correction is a compile-time mode of the min-sum kernels (CORR, or RULE == kRuleMinsumCorr); alpha and beta are run-time
-// arguments.  It is applied ONCE PER ROW to min1 and min2, between the fold and the store: a row sends only these two
+// The correction is a compile-time mode of the min-sum kernels; alpha and beta are run-time arguments.  Every kernel min-sum
+// can take ends in a template parameter pack and a matching argument pack (`typename... MC`, `MC... mc`): empty, it is the
+// plain kernel -- same signature, same kernel arguments, same name as a kernel without the pack; holding one MinsumCorr<T>, it
+// is the corrected instantiation x_kernel<..., MinsumCorr<T>> (CORR = sizeof...(MC) != 0, or RULE == kRuleMinsumCorr in the
+// kernels that take a rule; `mc...` expands to nothing or to the one argument of minsum_corrected / rule_check_node / rule_edge).
+// It is applied ONCE PER ROW to min1 and min2, between the fold and the store: a row sends only these two
 // magnitudes, so correcting them is correcting every message of the row -- and a row record that holds the corrected pair
 // (RowRec) hands corrected messages to whoever reads it (RowRec::value: the row itself in the next iteration, the L-free
 // rebuild from the peer row's record, the carry between neighbouring rows, vn_free_rec_kernel, layered x = Qv - R).
@@ -246,6 +250,9 @@ template <typename T>
 struct MinsumCorr {
   T alpha, beta;
 };
+// what a kernel's trailing pack may hold: nothing, or exactly one MinsumCorr<T>
+template <typename T, typename... MC>
+inline constexpr bool is_corr_pack = sizeof...(MC) == 0 || (sizeof...(MC) == 1 && (std::is_same<MC, MinsumCorr<T>>::value && ...));
 template <typename T>
 __device__ __forceinline__ T minsum_corrected(T m, const MinsumCorr<T> &mc) {
   const T scaled = mc.alpha * m;

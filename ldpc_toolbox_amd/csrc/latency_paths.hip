@@ -79,17 +79,25 @@ int DeviceDecoder::decode_latency(const void *llrs, bool llrs_f64, bool host_poi
   // one workgroup of 1024 threads per CU, all of them resident together (the kernel's census waits for all of them,
   // and derives how many share an XCD at run time): the grid is what the device can hold at once -- 256 on an
   // MI355X in SPX mode, fewer on a partitioned or smaller device -- and never more than 256
+  // plain / corrected arithmetic: f(auto... c) gets nothing or the kernel's last argument, and names the kernel
+  // latency_minsum_kernel<SrcT, decltype(c)...> (a corrected implementation never takes the plain kernel)
+  const dev::MinsumCorr<float> mc{static_cast<float>(impl_.alpha()), static_cast<float>(impl_.beta())};
+  auto with_corr = [&](auto f) {
+    if (impl_.correction != Correction::None)
+      f(mc);
+    else
+      f();
+  };
   if (lp.grid == 0) {
     int cus = 0, per_cu_f = 0, per_cu_d = 0;
     hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_);
-    // (the kernel this handle launches: the corrected form for a normalized / offset implementation)
-    const bool corr = impl_.correction != Correction::None;
-    if (e == hipSuccess)
-      e = corr ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, dev::latency_minsum_kernel_corr<float>, 1024, 0)
-               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, dev::latency_minsum_kernel<float>, 1024, 0);
-    if (e == hipSuccess)
-      e = corr ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, dev::latency_minsum_kernel_corr<double>, 1024, 0)
-               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, dev::latency_minsum_kernel<double>, 1024, 0);
+    // (of the kernel this handle launches)
+    with_corr([&](auto... c) {
+      if (e == hipSuccess)
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, dev::latency_minsum_kernel<float, decltype(c)...>, 1024, 0);
+      if (e == hipSuccess)
+        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, dev::latency_minsum_kernel<double, decltype(c)...>, 1024, 0);
+    });
     const int resident = e == hipSuccess ? cus * std::min(per_cu_f, per_cu_d) : 0;
     if (resident < 8) {  // cannot be co-resident in any useful number: this handle keeps the batched kernels
       opt_latency_ = 0;
@@ -99,24 +107,17 @@ int DeviceDecoder::decode_latency(const void *llrs, bool llrs_f64, bool host_poi
     lp.grid = static_cast<uint32_t>(std::min(resident, 256));
   }
   const uint32_t grid = lp.grid;
-  // one launch, four kernels: the caller's LLR type x plain / corrected arithmetic (a corrected implementation never takes
-  // the plain kernel)
-  auto go = [&](auto kernel, auto *src, auto *dst, auto... extra) {
-    kernel<<<grid, 1024, 0, s>>>(t, lp.slots, lp.d_sync, src, static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
-                                 max_iterations, d_bits, static_cast<uint32_t>(out_len), d_iters, dst, o_err, extra...);
-  };
-  const dev::MinsumCorr<float> mc{static_cast<float>(impl_.alpha()), static_cast<float>(impl_.beta())};
-  if (impl_.correction != Correction::None) {
+  // one launch, four kernels: the caller's LLR type x plain / corrected arithmetic
+  with_corr([&](auto... c) {
+    auto go = [&](auto kernel, auto *src, auto *dst) {
+      kernel<<<grid, 1024, 0, s>>>(t, lp.slots, lp.d_sync, src, static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
+                                   max_iterations, d_bits, static_cast<uint32_t>(out_len), d_iters, dst, o_err, c...);
+    };
     if (llrs_f64)
-      go(dev::latency_minsum_kernel_corr<double>, static_cast<const double *>(d_llrs), static_cast<double *>(d_post), mc);
+      go(dev::latency_minsum_kernel<double, decltype(c)...>, static_cast<const double *>(d_llrs), static_cast<double *>(d_post));
     else
-      go(dev::latency_minsum_kernel_corr<float>, static_cast<const float *>(d_llrs), static_cast<float *>(d_post), mc);
-  } else {
-    if (llrs_f64)
-      go(dev::latency_minsum_kernel<double>, static_cast<const double *>(d_llrs), static_cast<double *>(d_post));
-    else
-      go(dev::latency_minsum_kernel<float>, static_cast<const float *>(d_llrs), static_cast<float *>(d_post));
-  }
+      go(dev::latency_minsum_kernel<float, decltype(c)...>, static_cast<const float *>(d_llrs), static_cast<float *>(d_post));
+  });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s));
   if (*o_err != 0) {
@@ -161,10 +162,11 @@ size_t DeviceDecoder::edge_latency_limit() const {
 
 // the lane-per-edge path (latency_edge.hip.h): layered schedule, and flooding for everything but Minsumf32
 namespace {
-template <int RULE, typename T, typename SrcT>
+// (MC: dev::MinsumCorr<T> with kRuleMinsumCorr -- the kernel then has one more argument -- nothing otherwise)
+template <int RULE, typename T, typename SrcT, typename... MC>
 const void *edge_kernel_s(bool layered) {
-  return layered ? reinterpret_cast<const void *>(dev::latency_edge_kernel<RULE, T, SrcT, true>)
-                 : reinterpret_cast<const void *>(dev::latency_edge_kernel<RULE, T, SrcT, false>);
+  return layered ? reinterpret_cast<const void *>(dev::latency_edge_kernel<RULE, T, SrcT, true, MC...>)
+                 : reinterpret_cast<const void *>(dev::latency_edge_kernel<RULE, T, SrcT, false, MC...>);
 }
 template <typename T, typename SrcT>
 const void *edge_kernel_r(Rule rule, bool corrected, bool layered) {
@@ -174,11 +176,8 @@ const void *edge_kernel_r(Rule rule, bool corrected, bool layered) {
     case Rule::Minstarapprox: return edge_kernel_s<dev::kRuleMinstarapprox, T, SrcT>(layered);
     case Rule::Aminstar: return edge_kernel_s<dev::kRuleAminstar, T, SrcT>(layered);
     case Rule::Minsum:
-      // normalized / offset min-sum: latency_edge_kernel_corr (one more argument: dev::MinsumCorr<T>)
-      if (corrected)
-        return layered ? reinterpret_cast<const void *>(dev::latency_edge_kernel_corr<dev::kRuleMinsumCorr, T, SrcT, true>)
-                       : reinterpret_cast<const void *>(dev::latency_edge_kernel_corr<dev::kRuleMinsumCorr, T, SrcT, false>);
-      return edge_kernel_s<dev::kRuleMinsum, T, SrcT>(layered);
+      return corrected ? edge_kernel_s<dev::kRuleMinsumCorr, T, SrcT, dev::MinsumCorr<T>>(layered)
+                       : edge_kernel_s<dev::kRuleMinsum, T, SrcT>(layered);
   }
   return nullptr;  // (no such rule: the launch fails)
 }

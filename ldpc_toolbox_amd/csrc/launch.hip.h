@@ -8,19 +8,29 @@ namespace ldpc {
 
 template <typename T>
 struct Launch {
-  // normalized / offset min-sum (g_knobs.corr): every min-sum launch below then takes the kernel's *_kernel_corr form with
-  // (alpha, beta) in the decoder's type -- there is no plain-arithmetic launch a corrected implementation could fall into
+  // normalized / offset min-sum (g_knobs.corr): every min-sum launch below then takes the kernel's corrected instantiation
+  // x_kernel<..., dev::MinsumCorr<T>> with (alpha, beta) in the decoder's type -- there is no plain-arithmetic launch a
+  // corrected implementation could fall into
   static dev::MinsumCorr<T> mc() { return dev::MinsumCorr<T>{static_cast<T>(g_knobs.alpha), static_cast<T>(g_knobs.beta)}; }
+  // a min-sum launch, written once: launch(auto... mc) names its kernel with `decltype(mc)...` as the last template arguments
+  // and passes `mc...` last -- nothing for plain min-sum, mc() for the corrected forms
+  template <typename F>
+  static void with_corr(F &&launch) {
+    if (g_knobs.corr)
+      launch(mc());
+    else
+      launch();
+  }
   // flooding min-sum check nodes: VEC x mask width x unroll x FIRST
   template <int VEC, typename MASK, bool FIRST>
   static void cn_minsum_u(const Tiling &t, hipStream_t s, const dev::Graph &g,
                           const dev::State &st, const T *L, T *msg, uint32_t *unsat) {
     // (eight loads in flight, nontemporal messages: the four-load and the cached-message variants were tuning knobs within
     // a percent of these, gone in round 6)
-    if (g_knobs.corr)
-      dev::cn_minsum_kernel_corr<T, VEC, MASK, 8, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, L, msg, unsat, mc());
-    else
-      dev::cn_minsum_kernel<T, VEC, MASK, 8, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, L, msg, unsat);
+    with_corr([&](auto... mc) {
+      dev::cn_minsum_kernel<T, VEC, MASK, 8, FIRST, true, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+          g, t.sched, st, L, msg, unsat, mc...);
+    });
   }
   template <int VEC, bool FIRST>
   static void cn_minsum_m(bool wide_mask, const Tiling &t, hipStream_t s, const dev::Graph &g,
@@ -35,12 +45,10 @@ struct Launch {
   static void cn_lfree_u(const Tiling &t, hipStream_t s, const dev::Graph &g, const dev::State &st, const T *chan,
                          T *post, const T *msg_in, T *msg_out, uint32_t *unsat) {
     // (four loads in flight, nontemporal stores, cached loads of the previous messages: what round 2 settled on)
-    if (g_knobs.corr)
-      dev::cn_minsum_lfree_kernel_corr<T, VEC, MASK, 4, FIRST, true, false><<<t.blocks, t.threads, 0, s>>>(
-          g, t.sched, st, chan, post, msg_in, msg_out, unsat, mc());
-    else
-      dev::cn_minsum_lfree_kernel<T, VEC, MASK, 4, FIRST, true, false><<<t.blocks, t.threads, 0, s>>>(
-          g, t.sched, st, chan, post, msg_in, msg_out, unsat);
+    with_corr([&](auto... mc) {
+      dev::cn_minsum_lfree_kernel<T, VEC, MASK, 4, FIRST, true, false, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+          g, t.sched, st, chan, post, msg_in, msg_out, unsat, mc...);
+    });
   }
   template <int VEC, bool FIRST>
   static void cn_lfree_m(bool wide_mask, const Tiling &t, hipStream_t s, const dev::Graph &g, const dev::State &st,
@@ -71,19 +79,15 @@ struct Launch {
     // further-rounds code)
     // (eight loads in flight per lane; the four-load variant of earlier rounds, a tuning knob nothing selected, is gone)
     if (g_knobs.rec_long) {
-      if (g_knobs.corr)
-        dev::cn_minsum_rec_kernel_corr<T, VEC, RECW, 8, FIRST, true, false, true><<<t.blocks, t.threads, 0, s>>>(
-            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run, mc());
-      else
-        dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, true><<<t.blocks, t.threads, 0, s>>>(
-            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run);
+      with_corr([&](auto... mc) {
+        dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, true, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run, mc...);
+      });
     } else {
-      if (g_knobs.corr)
-        dev::cn_minsum_rec_kernel_corr<T, VEC, RECW, 8, FIRST, true, false, false><<<t.blocks, t.threads, 0, s>>>(
-            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run, mc());
-      else
-        dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, false><<<t.blocks, t.threads, 0, s>>>(
-            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run);
+      with_corr([&](auto... mc) {
+        dev::cn_minsum_rec_kernel<T, VEC, RECW, 8, FIRST, true, false, false, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+            g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run, mc...);
+      });
     }
   }
   template <int VEC, bool FIRST>
@@ -131,47 +135,42 @@ struct Launch {
       cn_minsum_m<1, FIRST>(wide_mask, t, s, g, st, L, msg, unsat);
   }
 
-  // flooding, LDS-staged: normalized / offset min-sum (cn_staged_kernel_corr)
-  template <bool FIRST>
-  static void cn_staged_corr(const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g, const dev::State &st,
-                             const T *L, T *msg, uint32_t *unsat, uint32_t dmax) {
-    if (g_knobs.row_scratch) {
-      dev::cn_staged_kernel_corr<dev::kRuleMinsumCorr, T, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, L, msg, unsat, dmax,
-                                                                               static_cast<T *>(g_knobs.row_scratch), mc());
-      return;
-    }
-    auto k = dev::cn_staged_kernel_corr<dev::kRuleMinsumCorr, T, FIRST>;
-    if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(lds));
-    k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, L, msg, unsat, dmax, nullptr, mc());
-  }
-  // flooding, LDS-staged rules
+  // flooding, LDS-staged rules (kRuleMinsumCorr: normalized / offset min-sum, the kernel's form with mc() as its last argument)
   template <int RULE, bool FIRST>
   static void cn_staged_r(const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g, const dev::State &st,
                           const T *L, T *msg, uint32_t *unsat, uint32_t dmax) {
-    if (g_knobs.row_scratch) {
-      dev::cn_staged_kernel<RULE, T, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, L, msg, unsat, dmax,
-                                                                                 static_cast<T *>(g_knobs.row_scratch));
-      return;
-    }
-    auto k = dev::cn_staged_kernel<RULE, T, FIRST>;
-    if (lds > 48 * 1024)
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                static_cast<int>(lds));
-    k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, L, msg, unsat, dmax, nullptr);
+    auto go = [&](auto... mc) {
+      if (g_knobs.row_scratch) {
+        dev::cn_staged_kernel<RULE, T, FIRST, true, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+            g, t.sched, st, L, msg, unsat, dmax, static_cast<T *>(g_knobs.row_scratch), mc...);
+        return;
+      }
+      auto k = dev::cn_staged_kernel<RULE, T, FIRST, false, decltype(mc)...>;
+      if (lds > 48 * 1024)
+        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  static_cast<int>(lds));
+      k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, L, msg, unsat, dmax, nullptr, mc...);
+    };
+    if constexpr (RULE == dev::kRuleMinsumCorr)
+      go(mc());
+    else
+      go();
   }
   // reg_dmax: 0 = cn_staged_kernel; 10 / 12 = cn_reg_kernel (the Tanh rule: rows of at most that many edges in registers; recs: their records)
   template <int RULE, bool FIRST>
   static void cn_staged_r(uint32_t reg_dmax, const uint32_t *recs, const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g,
                           const dev::State &st, const T *L, T *msg, uint32_t *unsat, uint32_t dmax) {
-    if (reg_dmax == 0) return cn_staged_r<RULE, FIRST>(t, lds, s, g, st, L, msg, unsat, dmax);
-    auto launch = [&](auto k) {
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
-      k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, recs, L, msg, unsat, dmax);
-    };
-    if constexpr (RULE == dev::kRuleTanh) {  // (the opt-in "@fast" variant keeps the LDS-staged kernel)
+    // (only the Tanh rule has the register-resident form -- its opt-in "@fast" variant does not; any other rule takes the
+    // LDS-staged kernel whatever reg_dmax says: no combination launches nothing)
+    if constexpr (RULE != dev::kRuleTanh) {
+      cn_staged_r<RULE, FIRST>(t, lds, s, g, st, L, msg, unsat, dmax);
+    } else {
+      if (reg_dmax == 0) return cn_staged_r<RULE, FIRST>(t, lds, s, g, st, L, msg, unsat, dmax);
+      auto launch = [&](auto k) {
+        if (lds > 48 * 1024)
+          (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize, static_cast<int>(lds));
+        k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, recs, L, msg, unsat, dmax);
+      };
       if (reg_dmax == 10)
         launch(dev::cn_reg_kernel<RULE, T, 10, FIRST>);
       else
@@ -208,7 +207,7 @@ struct Launch {
         break;
       case Rule::Minsum:
         if (g_knobs.corr)  // (reg_dmax is 0: the register-resident form is the Tanh rule's)
-          cn_staged_corr<FIRST>(t, lds, s, g, st, L, msg, unsat, dmax);
+          cn_staged_r<dev::kRuleMinsumCorr, FIRST>(reg_dmax, recs, t, lds, s, g, st, L, msg, unsat, dmax);
         else
           cn_staged_r<dev::kRuleMinsum, FIRST>(reg_dmax, recs, t, lds, s, g, st, L, msg, unsat, dmax);
         break;
@@ -276,55 +275,30 @@ struct Launch {
   template <int RULE, bool FIRST>
   static void hl_rr(uint32_t reg_dmax, const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g,
                     const dev::State &st, const uint32_t *level_rows, uint32_t n_level, T *Q, T *R, uint32_t dmax) {
-    auto launch = [&](auto k) {
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  static_cast<int>(lds));
-      k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax);
+    // (kRuleMinsumCorr: normalized / offset min-sum, the kernels' form with mc() as the last argument)
+    auto go = [&](auto... mc) {
+      auto launch = [&](auto k, auto... scratch) {  // (scratch: hl_level_kernel's argument before mc, none in hl_level_reg_kernel)
+        if (lds > 48 * 1024)
+          (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                    static_cast<int>(lds));
+        k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax, scratch..., mc...);
+      };
+      if (reg_dmax == 10)
+        launch(dev::hl_level_reg_kernel<RULE, T, 10, FIRST, decltype(mc)...>);
+      else if (reg_dmax == 12)
+        launch(dev::hl_level_reg_kernel<RULE, T, 12, FIRST, decltype(mc)...>);
+      else if (reg_dmax == 24)
+        launch(dev::hl_level_reg_kernel<RULE, T, 24, FIRST, decltype(mc)...>);
+      else if (g_knobs.row_scratch)
+        dev::hl_level_kernel<RULE, T, FIRST, true, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+            g, t.sched, st, level_rows, n_level, Q, R, dmax, static_cast<T *>(g_knobs.row_scratch), mc...);
+      else
+        launch(dev::hl_level_kernel<RULE, T, FIRST, false, decltype(mc)...>, nullptr);
     };
-    if (reg_dmax == 10)
-      launch(dev::hl_level_reg_kernel<RULE, T, 10, FIRST>);
-    else if (reg_dmax == 12)
-      launch(dev::hl_level_reg_kernel<RULE, T, 12, FIRST>);
-    else if (reg_dmax == 24)
-      launch(dev::hl_level_reg_kernel<RULE, T, 24, FIRST>);
-    else if (g_knobs.row_scratch) {
-      dev::hl_level_kernel<RULE, T, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax,
-                                                                                static_cast<T *>(g_knobs.row_scratch));
-    } else {
-      auto k = dev::hl_level_kernel<RULE, T, FIRST>;
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  static_cast<int>(lds));
-      k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax, nullptr);
-    }
-  }
-  // normalized / offset min-sum through the level kernels (hl_level_kernel_corr, hl_level_reg_kernel_corr)
-  template <bool FIRST>
-  static void hl_corr(uint32_t reg_dmax, const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g,
-                      const dev::State &st, const uint32_t *level_rows, uint32_t n_level, T *Q, T *R, uint32_t dmax) {
-    auto launch = [&](auto k) {
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  static_cast<int>(lds));
-      k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax, mc());
-    };
-    if (reg_dmax == 10)
-      launch(dev::hl_level_reg_kernel_corr<dev::kRuleMinsumCorr, T, 10, FIRST>);
-    else if (reg_dmax == 12)
-      launch(dev::hl_level_reg_kernel_corr<dev::kRuleMinsumCorr, T, 12, FIRST>);
-    else if (reg_dmax == 24)
-      launch(dev::hl_level_reg_kernel_corr<dev::kRuleMinsumCorr, T, 24, FIRST>);
-    else if (g_knobs.row_scratch) {
-      dev::hl_level_kernel_corr<dev::kRuleMinsumCorr, T, FIRST, true><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax,
-                                                                              static_cast<T *>(g_knobs.row_scratch), mc());
-    } else {
-      auto k = dev::hl_level_kernel_corr<dev::kRuleMinsumCorr, T, FIRST>;
-      if (lds > 48 * 1024)
-        (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  static_cast<int>(lds));
-      k<<<t.blocks, t.threads, lds, s>>>(g, t.sched, st, level_rows, n_level, Q, R, dmax, nullptr, mc());
-    }
+    if constexpr (RULE == dev::kRuleMinsumCorr)
+      go(mc());
+    else
+      go();
   }
   template <bool FIRST>
   static void hl(Rule rule, uint32_t reg_dmax, const Tiling &t, size_t lds, hipStream_t s, const dev::Graph &g,
@@ -356,7 +330,7 @@ struct Launch {
         break;
       case Rule::Minsum:
         if (g_knobs.corr)
-          hl_corr<FIRST>(reg_dmax, t, lds, s, g, st, level_rows, n_level, Q, R, dmax);
+          hl_rr<dev::kRuleMinsumCorr, FIRST>(reg_dmax, t, lds, s, g, st, level_rows, n_level, Q, R, dmax);
         else
           hl_rr<dev::kRuleMinsum, FIRST>(reg_dmax, t, lds, s, g, st, level_rows, n_level, Q, R, dmax);
         break;
@@ -367,10 +341,10 @@ struct Launch {
   template <int VEC, bool FIRST>
   static void hl_minsum_v(const Tiling &t, hipStream_t s, const dev::Graph &g,
                           const dev::State &st, const uint32_t *level_rows, uint32_t n_level, T *Q, T *R) {
-    if (g_knobs.corr)
-      dev::hl_minsum_kernel_corr<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
-    else
-      dev::hl_minsum_kernel<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+    with_corr([&](auto... mc) {
+      dev::hl_minsum_kernel<T, VEC, 8, FIRST, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+          g, t.sched, st, level_rows, n_level, Q, R, mc...);
+    });
   }
   // register-resident rows: DMAX bucket of the level's largest row; vec capped so that the
   // 2 * DMAX * VEC values fit the register file with some occupancy left
@@ -391,32 +365,32 @@ struct Launch {
                               const dev::State &st, const uint32_t *level_rows, uint32_t n_level, T *Q, T *R) {
     switch (dmax) {
       case 8:
-        if (g_knobs.corr)
-          dev::hl_minsum_reg_kernel_corr<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
-        else
-          dev::hl_minsum_reg_kernel<T, VEC, 8, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+        with_corr([&](auto... mc) {
+          dev::hl_minsum_reg_kernel<T, VEC, 8, FIRST, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+              g, t.sched, st, level_rows, n_level, Q, R, mc...);
+        });
         return true;
       case 12:
-        if (g_knobs.corr)
-          dev::hl_minsum_reg_kernel_corr<T, VEC, 12, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
-        else
-          dev::hl_minsum_reg_kernel<T, VEC, 12, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+        with_corr([&](auto... mc) {
+          dev::hl_minsum_reg_kernel<T, VEC, 12, FIRST, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+              g, t.sched, st, level_rows, n_level, Q, R, mc...);
+        });
         return true;
       case 20:
         if constexpr (VEC * sizeof(T) <= 8) {
-          if (g_knobs.corr)
-            dev::hl_minsum_reg_kernel_corr<T, VEC, 20, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
-          else
-            dev::hl_minsum_reg_kernel<T, VEC, 20, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+          with_corr([&](auto... mc) {
+            dev::hl_minsum_reg_kernel<T, VEC, 20, FIRST, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+                g, t.sched, st, level_rows, n_level, Q, R, mc...);
+          });
           return true;
         }
         return false;
       case 32:
         if constexpr (VEC * sizeof(T) <= 4) {
-          if (g_knobs.corr)
-            dev::hl_minsum_reg_kernel_corr<T, VEC, 32, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R, mc());
-          else
-            dev::hl_minsum_reg_kernel<T, VEC, 32, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, R);
+          with_corr([&](auto... mc) {
+            dev::hl_minsum_reg_kernel<T, VEC, 32, FIRST, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+                g, t.sched, st, level_rows, n_level, Q, R, mc...);
+          });
           return true;
         }
         return false;
@@ -445,32 +419,32 @@ struct Launch {
     constexpr uint32_t kWords = VEC * sizeof(T) / 4;
     switch (dmax) {
       case 8:
-        if (g_knobs.corr)
-          dev::hl_minsum_rec_kernel_corr<T, VEC, 8, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec, mc());
-        else
-          dev::hl_minsum_rec_kernel<T, VEC, 8, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
+        with_corr([&](auto... mc) {
+          dev::hl_minsum_rec_kernel<T, VEC, 8, 3, FIRST, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+              g, t.sched, st, level_rows, n_level, Q, rec, mc...);
+        });
         return true;
       case 12:
-        if (g_knobs.corr)
-          dev::hl_minsum_rec_kernel_corr<T, VEC, 12, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec, mc());
-        else
-          dev::hl_minsum_rec_kernel<T, VEC, 12, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
+        with_corr([&](auto... mc) {
+          dev::hl_minsum_rec_kernel<T, VEC, 12, 3, FIRST, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+              g, t.sched, st, level_rows, n_level, Q, rec, mc...);
+        });
         return true;
       case 20:
         if constexpr ((20 + 6) * kWords <= 112) {
-          if (g_knobs.corr)
-            dev::hl_minsum_rec_kernel_corr<T, VEC, 20, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec, mc());
-          else
-            dev::hl_minsum_rec_kernel<T, VEC, 20, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
+          with_corr([&](auto... mc) {
+            dev::hl_minsum_rec_kernel<T, VEC, 20, 3, FIRST, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+                g, t.sched, st, level_rows, n_level, Q, rec, mc...);
+          });
           return true;
         }
         return false;
       case 32:
         if constexpr ((32 + 6) * kWords <= 112) {
-          if (g_knobs.corr)
-            dev::hl_minsum_rec_kernel_corr<T, VEC, 32, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec, mc());
-          else
-            dev::hl_minsum_rec_kernel<T, VEC, 32, 3, FIRST><<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, level_rows, n_level, Q, rec);
+          with_corr([&](auto... mc) {
+            dev::hl_minsum_rec_kernel<T, VEC, 32, 3, FIRST, decltype(mc)...><<<t.blocks, t.threads, 0, s>>>(
+                g, t.sched, st, level_rows, n_level, Q, rec, mc...);
+          });
           return true;
         }
         return false;

@@ -1,7 +1,9 @@
 #!/usr/bin/env python3
 """Per-kernel digest of a built library's gfx950 code: {demangled kernel name: sha1 of its disassembly without addresses}.
 Used to check that a refactoring of the host code / a split into translation units left every kernel's instructions as
-they were:  tools/kernel_digest.py old.so new.so  -> kernels only in one, kernels whose code differs."""
+they were:  tools/kernel_digest.py old.so new.so  -> kernels only in one, kernels whose code differs.
+A third argument PATTERN=REPLACEMENT (a regular expression and its substitution) renames the first library's kernels before the
+comparison, for a change that renames kernels on purpose.  It is split at its first '=': PATTERN itself cannot contain one."""
 import hashlib
 import os
 import re
@@ -55,6 +57,12 @@ def digests(path):
 
 if __name__ == "__main__":
     a, b = digests(sys.argv[1]), digests(sys.argv[2])
+    if len(sys.argv) > 3:
+        pattern, replacement = sys.argv[3].split("=", 1)
+        renamed = {}
+        for k, v in a.items():
+            renamed.setdefault(re.sub(pattern, replacement, k), []).extend(v)
+        a = renamed
     only_a, only_b = sorted(set(a) - set(b)), sorted(set(b) - set(a))
     diff = sorted(k for k in set(a) & set(b) if sorted(a[k]) != sorted(b[k]))
     print(f"{sum(len(v) for v in a.values())} kernel bodies in {sys.argv[1]}, {sum(len(v) for v in b.values())} in {sys.argv[2]}")
