@@ -174,8 +174,10 @@ int32_t ldpc_toolbox_encoder_encode_batch_device(void *encoder, uint8_t *output,
                                                  void *hip_stream);
 
 /* Integer properties of an encoder: "k", "n", "output_len" (n, or the punctured length), "staircase" (1: the
- * accumulator encoder of the DVB-S2 family, 0: the dense generator), "device" (GPU of the batched entries; -1 while no
- * device state exists).  returns 0 or -1 (unknown key). */
+ * accumulator encoder of the DVB-S2 family, 0: the dense generator), "staircase_form" (how the batched entries encode
+ * a staircase code, a function of k alone that needs no device: 0 = 32 frames per word staged in LDS, 1 = 16 frames
+ * per word staged in LDS, 2 = gathered from global memory; -1 for every other code), "device" (GPU of the batched
+ * entries; -1 while no device state exists).  returns 0 or -1 (unknown key). */
 int32_t ldpc_toolbox_encoder_get(void *encoder, const char *key, int64_t *value);
 
 /* The syndrome test of the reference's decoders (src/decoder.rs:157-164, check_llrs: the parity

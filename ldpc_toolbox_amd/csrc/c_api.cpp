@@ -382,6 +382,8 @@ int32_t ldpc_toolbox_encoder_get(void *encoder, const char *key, int64_t *value)
     *value = h->out_len == SIZE_MAX ? -1 : static_cast<int64_t>(h->out_len);
   else if (k == "staircase")
     *value = h->enc.staircase() ? 1 : 0;
+  else if (k == "staircase_form")  // (which of launch_staircase's three forms a batched call takes; -1: not a staircase code)
+    *value = h->enc.staircase() ? ldpc::staircase_form(h->enc.k()) : -1;
   else if (k == "device")
     *value = h->dev ? h->dev->device() : -1;
   else

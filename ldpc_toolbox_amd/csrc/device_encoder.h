@@ -16,6 +16,19 @@
 
 namespace ldpc {
 
+// LDS a stair_scan_kernel workgroup may ask for: the 160 KiB of a gfx950 CU less its static words
+constexpr size_t kEncLdsBudget = 160 * 1024 - 1024;
+
+// How a staircase code of k message bits is encoded (launch_staircase; "staircase_form" of ldpc_toolbox_encoder_get).
+// A group's message words are staged in LDS, kp = k rounded up to 8 of them:
+//   0: 32 frames per word while 4 * kp bytes fit;
+//   1: 16 frames per word for the longest messages (DVB-S2 normal frames from rate 2/3 up);
+//   2: a message too long even for that is gathered from global memory, 32 frames per word.
+constexpr int staircase_form(size_t k) {
+  const size_t kp = (k + 7) / 8 * 8;
+  return kp * 4 <= kEncLdsBudget ? 0 : (kp * 2 <= kEncLdsBudget ? 1 : 2);
+}
+
 class DeviceEncoder {
  public:
   // Uploads the tables of `enc` to GPU `device`.  pattern: empty, or a pattern whose length divides n.

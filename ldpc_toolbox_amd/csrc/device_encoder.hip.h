@@ -13,8 +13,6 @@ namespace ldpc {
 namespace {
 // frames per pass of the staircase kernels (bounds the bit-packed work buffers: n / 8 bytes per frame)
 constexpr size_t kEncPassFrames = 4096;
-// LDS a stair_scan_kernel workgroup may ask for: the 160 KiB of a gfx950 CU less its static words
-constexpr size_t kEncLdsBudget = 160 * 1024 - 1024;
 }  // namespace
 
 bool DeviceEncoder::fail(const std::string &m, hipError_t e) {
@@ -138,10 +136,8 @@ static void enc_staircase_pass(const uint8_t *in, uint8_t *cw, uint32_t batch, u
 
 int DeviceEncoder::launch_staircase(const uint8_t *in, uint8_t *cw, size_t batch, hipStream_t s) {
   const uint32_t k = static_cast<uint32_t>(k_), n = static_cast<uint32_t>(n_);
-  // a group's message words in LDS: 32 frames per word while they fit, 16 for the longest messages (DVB-S2 normal frames
-  // from rate 2/3 up); a message too long even for that is gathered from global memory
   const uint32_t kp = (k + 7) / 8 * 8;
-  const int form = size_t(kp) * 4 <= kEncLdsBudget ? 0 : (size_t(kp) * 2 <= kEncLdsBudget ? 1 : 2);
+  const int form = staircase_form(k_);
   const size_t word = form == 1 ? 2 : 4, frames_per_group = 8 * word;
   const size_t pass = std::min(batch, kEncPassFrames), groups = (pass + frames_per_group - 1) / frames_per_group;
   if (int rc = grow(&d_packed_, &packed_bytes_, groups * kp * word + 16)) return rc;

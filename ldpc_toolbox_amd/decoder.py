@@ -262,6 +262,9 @@ class Encoder:
     n = property(lambda self: self.get("n"))
     output_len = property(lambda self: self.get("output_len"))
     staircase = property(lambda self: bool(self.get("staircase")))
+    # which form of the staircase kernels a batched call takes: 0 = 32 frames per word staged in LDS, 1 = 16 frames per
+    # word staged in LDS, 2 = gathered from global memory; -1 = not a staircase code
+    staircase_form = property(lambda self: self.get("staircase_form"))
     device = property(lambda self: self.get("device"))
 
     def encode(self, message, output_len: int):

@@ -51,6 +51,9 @@ def test_encoder_get(alist_of, pattern, expect):
     for key, value in expect.items():
         assert _get(enc._h, key) == (0, value), key
     assert (enc.k, enc.n, enc.output_len, enc.staircase) == (expect["k"], expect["n"], expect["output_len"], bool(expect["staircase"]))
+    # every one of these messages fits in LDS at 32 frames per word: form 0, and -1 for a code that is not a staircase
+    assert _get(enc._h, "staircase_form") == (0, 0 if expect["staircase"] else -1)
+    assert enc.staircase_form == (0 if expect["staircase"] else -1)
     # a handle from the plain constructor has no device state
     assert _get(enc._h, "device") == (0, -1) and enc.device == -1
     rc, v = _get(enc._h, "no_such_key")
