@@ -26,6 +26,8 @@
 
 namespace ldpc {
 
+struct GroupCall;
+
 struct KernelStat {
   uint64_t launches = 0;
   double total_ms = 0.0;
@@ -118,14 +120,13 @@ class DeviceDecoder {
  private:
   DeviceDecoder() = default;
   struct Workspace;
-  int run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, size_t nb, uint32_t max_iterations, uint8_t *bits,
-                   size_t out_len, int32_t *iterations, void *posterior, hipStream_t stream, bool may_block);
+  struct GroupFrame;
+  // one group of codewords (device_decoder_internal.h, GroupCall): run_any resolves the host's pacing and hands the group
+  // to the 8-bit rules or to the float rules in the decoder's precision
+  int run_group_i8(Workspace &w, const GroupCall &call);
   template <typename T>
-  int run_group(Workspace &w, const void *llrs, bool llrs_f64, size_t nb, uint32_t max_iterations, uint8_t *bits,
-                size_t out_len, int32_t *iterations, void *posterior, hipStream_t stream, bool may_block);
-  int run_any(Workspace &w, const void *llrs, bool llrs_f64, size_t nb, uint32_t max_iterations, uint8_t *bits,
-              size_t out_len, int32_t *iterations, void *posterior, hipStream_t stream, bool may_block,
-              bool own_thread = false);
+  int run_group(Workspace &w, const GroupCall &call);
+  int run_any(Workspace &w, const GroupCall &call);
   int ensure_workspace(Workspace &w, size_t group, void *place = nullptr, size_t *need = nullptr);
   int ensure_lanes(uint32_t lanes, size_t group);
   void release_joint();

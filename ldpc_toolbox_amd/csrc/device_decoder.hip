@@ -671,25 +671,25 @@ void DeviceDecoder::release_joint() {
   joint_second_ = 0;
 }
 
-int DeviceDecoder::run_any(Workspace &w, const void *llrs, bool llrs_f64, size_t nb, uint32_t max_iterations,
-                           uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior, hipStream_t s,
-                           bool may_block, bool own_thread) {
+int DeviceDecoder::run_any(Workspace &w, const GroupCall &call) {
+  GroupCall c = call;
+  const bool own_thread = c.own_thread;
   // The host may only wait on the device's progress where the call is synchronous anyway, and it
   // pays only for small groups of the layered schedule (dozens of short launches per iteration);
   // with flooding's two launches per iteration waiting costs more than the empty launches it saves,
   // and large groups keep the host free to fill both lanes -- unless every lane has its own enqueuing thread.
-  const bool may_wait = may_block;
-  may_block = may_block && opt_poll_ && impl_.schedule == Schedule::Layered && (own_thread || nb * n_ <= size_t(8) * 1000 * 1000);
+  const bool may_wait = c.may_block;
+  c.may_block = may_wait && opt_poll_ && impl_.schedule == Schedule::Layered && (own_thread || c.nb * n_ <= size_t(8) * 1000 * 1000);
   // A lane's own enqueuing thread always paces itself, one iteration ahead: the call cannot return before its threads
   // have enqueued everything anyway, and the command queue lets a thread run about four iterations ahead -- with early
   // termination that is four iterations of launches that return at once (35 each on 5G NR BG1, 5 us apiece) behind the
   // last real one.  Config 3 at +2 dB: 346 k -> 351 k codewords/s; fixed work unchanged (round 4).
-  t_pace_lead = opt_lead_;
+  c.pace_lead = opt_lead_;
   // (Only where the call may wait at all -- the library's own stream, host buffers, or option "throttle": a call that
   // merely enqueues on the CALLER's stream returns as soon as everything is enqueued, as include/ldpc_toolbox.h says.)
   if (own_thread && may_wait && opt_poll_ && impl_.schedule == Schedule::Layered && opt_lane_pace_) {
-    may_block = true;
-    if (!opt_lead_) t_pace_lead = 1;
+    c.may_block = true;
+    if (!opt_lead_) c.pace_lead = 1;
   }
   // Flooding where the call may wait -- the library's own stream (a NULL stream: synchronous anyway) or option "throttle"
   // (round 5; the simulation driver sets it): the host follows the group two iterations
@@ -700,14 +700,11 @@ int DeviceDecoder::run_any(Workspace &w, const void *llrs, bool llrs_f64, size_t
   // (One-lane calls of the device-resident entry, or a lane with an enqueuing thread of its own: one thread enqueuing both
   // lanes' groups in turn must not wait on the first; the host-buffer entry's calling thread stages the next group's copy
   // between its enqueues.)
-  if (impl_.schedule == Schedule::Flooding && !impl_.i8 && opt_poll_ && may_wait && !profiling_ && (t_flood_pace || own_thread)) {
-    may_block = true;
-    if (!opt_lead_) t_pace_lead = 2;
+  if (impl_.schedule == Schedule::Flooding && !impl_.i8 && opt_poll_ && may_wait && !profiling_ && (c.flood_pace || own_thread)) {
+    c.may_block = true;
+    if (!opt_lead_) c.pace_lead = 2;
   }
-  return impl_.i8 ? run_group_i8(w, llrs, llrs_f64, nb, max_iterations, bits, out_len, iterations, posterior, s, may_block)
-         : impl_.f64
-             ? run_group<double>(w, llrs, llrs_f64, nb, max_iterations, bits, out_len, iterations, posterior, s, may_block)
-             : run_group<float>(w, llrs, llrs_f64, nb, max_iterations, bits, out_len, iterations, posterior, s, may_block);
+  return impl_.i8 ? run_group_i8(w, c) : impl_.f64 ? run_group<double>(w, c) : run_group<float>(w, c);
 }
 
 // The handle's streams are non-blocking, so the legacy default stream (handle 0: what a caller that
@@ -876,7 +873,6 @@ int DeviceDecoder::decode_device_plain(const void *llrs, bool llrs_f64, size_t b
                         (impl_.schedule == Schedule::Layered ||
                          (impl_.schedule == Schedule::Flooding && !impl_.i8 && (opt_throttle_ || own_stream) && opt_poll_));
   const bool may_block = own_stream || opt_throttle_;
-  t_flood_pace = lanes == 1;
   auto run_groups = [&](uint32_t only_lane) -> int {  // only_lane: 0 / 1 = that lane's groups, 2 = all of them in turn
     uint32_t gi = 0;
     for (size_t b0 = 0; b0 < batch; b0 += G, gi++) {
@@ -887,8 +883,8 @@ int DeviceDecoder::decode_device_plain(const void *llrs, bool llrs_f64, size_t b
       uint8_t *dst_bits = bits + b0 * out_len;
       int32_t *dst_it = iterations ? iterations + b0 : nullptr;
       void *dst_post = posterior ? static_cast<char *>(posterior) + b0 * n_ * in_elem : nullptr;
-      if (int rc = run_any(*ws_[lane], src, llrs_f64, nb, max_iterations, dst_bits, out_len, dst_it, dst_post,
-                           lane ? stream2_ : s, may_block, threaded))
+      if (int rc = run_any(*ws_[lane], GroupCall{src, llrs_f64, nb, max_iterations, dst_bits, out_len, dst_it, dst_post,
+                                                 lane ? stream2_ : s, may_block, threaded, lanes == 1}))
         return rc;
     }
     return 0;
@@ -1125,7 +1121,6 @@ int DeviceDecoder::decode_host_pooled(const void *llrs, bool llrs_f64, size_t ba
 int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations,
                                      uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior) {
   if (batch == 0) return 0;
-  t_flood_pace = false;  // (this thread stages copies between its enqueues: it does not wait on a flooding group)
   if (out_len > n_) {
     fail("output_len larger than the codeword length");
     return -1;
@@ -1315,8 +1310,9 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
       HIP_TRY(hipStreamWaitEvent(s, p.in_ready[lane], 0));
       // a single small group (the reference-style scalar call) may let the host follow the device's progress; so may
       // a lane with an enqueuing thread of its own
-      const int erc = run_any(w, w.in, llrs_f64, nb, max_iterations, p.d_bits[r], out_len, p.d_iters[r],
-                              posterior ? p.d_post[r] : nullptr, s, n_groups == 1 || threaded, threaded);
+      // (flood_pace false: this thread stages copies between its enqueues, it does not wait on a flooding group)
+      const int erc = run_any(w, GroupCall{w.in, llrs_f64, nb, max_iterations, p.d_bits[r], out_len, p.d_iters[r],
+                                           posterior ? p.d_post[r] : nullptr, s, n_groups == 1 || threaded, threaded, false});
       if (erc) return erc;
       HIP_TRY(hipEventRecord(p.group_done[gi], s));
       return 0;

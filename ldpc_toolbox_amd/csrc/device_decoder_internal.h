@@ -17,6 +17,7 @@
 #include <functional>
 #include <mutex>
 #include <thread>
+#include <type_traits>
 
 #include "kernels.hip.h"
 #include "slice_tasks.h"
@@ -244,19 +245,39 @@ inline Tiling make_tiling(uint32_t G, uint32_t tile, uint32_t slice, uint32_t no
   return t;
 }
 
-// per-call launch choices (the tunables never affect results; `fast` and `corr` carry the implementation's arithmetic)
-struct Knobs {
-  bool rec_long = true;  // some row has more than 8 edges
-  bool fast = false;  // "@fast" implementation: the approximate Tanh / Phi rule variants
-  void *row_scratch = nullptr;  // non-null: the LDS-staged kernels keep their columns there (rows beyond the LDS)
-  // normalized / offset min-sum (Implementation::correction; this one DOES decide results): every min-sum launch of the call
-  // takes its corrected form with c = max(alpha * m - beta, 0) (kernels_common.hip.h, MinsumCorr)
-  bool corr = false;
-  double alpha = 1.0, beta = 0.0;
+// One group's call, from the batch entries through run_any to run_group<T> / run_group_i8.
+struct GroupCall {
+  const void *llrs;  // the group's input rows (device memory), f32 or f64
+  bool llrs_f64;
+  size_t nb;  // codewords of this group
+  uint32_t max_iterations;
+  uint8_t *bits;
+  size_t out_len;
+  int32_t *iterations;
+  void *posterior;
+  hipStream_t stream;
+  bool may_block;   // the entry's call may wait on the device; run_any hands on whether this group's host is paced
+  bool own_thread;  // the calling thread enqueues this lane's groups only
+  bool flood_pace;  // a one-lane call of the device-resident entry: a flooding group's host may follow its progress
+  uint32_t pace_lead = 0;  // resolved by run_any: iterations a paced host runs ahead (0: by schedule)
 };
-inline thread_local Knobs g_knobs;  // set at the top of run_group for the launches of this call
-inline thread_local bool t_flood_pace = false;  // set by decode_device for the groups it starts: a one-lane call on the device-resident entry
-inline thread_local uint32_t t_pace_lead = 0;  // set by run_any for the group it starts: iterations a paced host runs ahead (0: by schedule)
+
+// Run-time values as template arguments, each ladder written once: f gets the value as a std::integral_constant.
+template <int V>
+using int_c = std::integral_constant<int, V>;
+template <typename F>
+auto with_bool(bool b, F &&f) {
+  if (b) return f(std::true_type{});
+  return f(std::false_type{});
+}
+// codewords per lane of the streaming kernels: 4 for f32 only (T = double never instantiates VEC = 4: it lands on 2), 2 or 1
+template <typename T, typename F>
+auto with_vec(uint32_t vec, F &&f) {
+  if constexpr (sizeof(T) == 4)
+    if (vec == 4) return f(int_c<4>{});
+  if (vec >= 2) return f(int_c<2>{});
+  return f(int_c<1>{});
+}
 
 // LDS-staged kernels: largest block whose [arrays][dmax][threads] columns fit the CU's LDS
 inline bool staged_block(uint32_t arrays, uint32_t dmax, size_t elem, uint32_t *threads, size_t *lds) {
@@ -359,5 +380,87 @@ void compact_plan(hipStream_t s, dev::State st, dev::CompactPlan *plan, uint32_t
 void compact_commit(hipStream_t s, dev::State st, const dev::CompactPlan *plan, uint32_t *unsat0, uint32_t *unsat1,
                     uint32_t *n_slots, const uint32_t *fill_cw, uint32_t G);
 }  // namespace grp
+
+// What one group's run has in common under the float and the 8-bit rules (run_group<T>, run_group_i8): the codeword state
+// with its progress word, the launches up to the pre-check on the raw input, the syndrome / latch pair that ends an
+// iteration, and the emit launch.  The schedule loops between them are each rule family's own.
+struct DeviceDecoder::GroupFrame {
+  DeviceDecoder &d;
+  Workspace &w;
+  const GroupCall &c;
+  const hipStream_t s;
+  const uint32_t G, W, n, m, tile;  // tile: codewords per self-contained sub-batch (kernels.hip.h, tile_base)
+  dev::State st;
+  const ProgressPoll poll;
+  // syndrome launch: a wavefront takes 64 packed words of a few checks; enough wavefronts to fill the chip
+  const uint32_t synd_chunks = (W + 63) / 64;
+  const uint32_t synd_rows =
+      std::max<uint32_t>(1, std::min<uint32_t>(64, uint32_t(uint64_t(m) * synd_chunks * 64 / kSyndThreads)));
+  const uint32_t synd_threads = 64 * synd_chunks * ((m + synd_rows - 1) / synd_rows);
+
+  GroupFrame(DeviceDecoder &dec, Workspace &ws, const GroupCall &call, uint32_t tile_)
+      : d(dec), w(ws), c(call), s(call.stream), G(static_cast<uint32_t>(ws.G)), W(G / 64), n(static_cast<uint32_t>(dec.n_)),
+        m(static_cast<uint32_t>(dec.m_)), tile(tile_),
+        st{ws.done, ws.iters, ws.n_active, ws.n_slots, ws.slot_cw, nullptr, 0, 0, nullptr, nullptr, 0},
+        poll{(dec.opt_poll_ && ws.d_flag) ? ws.h_flag : nullptr, ws.epoch = (ws.epoch % 0xFFFFFFu) + 1, call.may_block,
+             call.pace_lead ? call.pace_lead : (dec.impl_.schedule == Schedule::Layered ? 2u : 8u), call.stream} {}
+
+  dev::Graph graph(const uint32_t *edge_aux, const uint32_t *edge_peer) const {
+    return dev::Graph{d.d_row_ptr_, d.d_edge_col_, d.d_col_ptr_, d.d_col_edge_, m, n, static_cast<uint32_t>(d.e_),
+                      nullptr,      nullptr,       nullptr,      0,             edge_aux, edge_peer};
+  }
+  // progress word: the first check-node launch of iteration `it` runs with ticked(it)
+  dev::State ticked(uint32_t it) const {
+    dev::State t = st;
+    t.publish = d.opt_poll_ ? w.d_flag : nullptr;
+    t.epoch = w.epoch;
+    t.tick = it;
+    return t;
+  }
+  void syndrome_of(const uint64_t *hard, uint32_t *unsat) const {
+    if (m == 0) return;
+    grp::syndrome_bits(s, synd_threads, d.d_row_ptr_, d.d_edge_col_, m, hard, unsat, w.n_active, w.n_slots, W, synd_rows);
+  }
+  void latch(uint32_t *unsat, int32_t it) const { grp::latch(s, w.done, w.iters, unsat, w.n_active, it, G); }
+  // the group's first launches: state, ingest (the rule family's kernel for f32 and for f64 input), and the pre-check on
+  // the raw input: iterations = 0 (flooding.rs:57-64)
+  template <typename K32, typename K64, typename C, typename P>
+  int begin(K32 ingest_f32, K64 ingest_f64, C *chan, P *post) const {
+    grp::init_group(s, w.done, w.iters, w.unsat0, w.unsat1, w.n_active, w.n_slots, w.slot_cw, static_cast<uint32_t>(c.nb), G);
+    const dim3 grid((n + 63) / 64, W);
+    const uint32_t block_size = d.pattern_len_ ? n / d.pattern_len_ : 0;
+    auto ingest = [&](auto kernel, auto *src) {
+      kernel<<<grid, 256, 0, s>>>(src, d.input_len_, static_cast<uint32_t>(c.nb), n, G, tile, chan, post, w.rawbits,
+                                  d.d_src_block_, block_size);
+    };
+    if (c.llrs_f64)
+      ingest(ingest_f64, static_cast<const double *>(c.llrs));
+    else
+      ingest(ingest_f32, static_cast<const float *>(c.llrs));
+    if (w.after_ingest) {
+      if (const hipError_t e = hipEventRecord(w.after_ingest, s); e != hipSuccess) {
+        d.fail("hipEventRecord(w.after_ingest, s)", e);
+        return -2;
+      }
+      if (w.ingest_seq) w.ingest_seq->fetch_add(1, std::memory_order_release);
+    }
+    syndrome_of(w.rawbits, w.unsat0);
+    latch(w.unsat0, 0);
+    return 0;
+  }
+  // results to the caller's rows, in the precision of its input (retire_only: a compaction checkpoint's, do_compact its plan)
+  template <typename P>
+  void emit(const P *post, const uint32_t *do_compact, int zero_fill, int retire_only) const {
+    const dim3 grid(std::min<uint32_t>((n + 63) / 64, retire_only ? kRetireBlocks : 4096), W);
+    auto go = [&](auto kernel, auto *out) {
+      kernel<<<grid, 256, 0, s>>>(post, w.rawbits, st, do_compact, n, G, tile, static_cast<uint32_t>(c.out_len), c.bits,
+                                  c.iterations, out, zero_fill, retire_only);
+    };
+    if (c.llrs_f64)
+      go(dev::emit_kernel<P, double>, static_cast<double *>(c.posterior));
+    else
+      go(dev::emit_kernel<P, float>, static_cast<float *>(c.posterior));
+  }
+};
 
 }  // namespace ldpc

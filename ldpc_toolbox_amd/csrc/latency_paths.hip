@@ -165,8 +165,9 @@ namespace {
 // (MC: dev::MinsumCorr<T> with kRuleMinsumCorr -- the kernel then has one more argument -- nothing otherwise)
 template <int RULE, typename T, typename SrcT, typename... MC>
 const void *edge_kernel_s(bool layered) {
-  return layered ? reinterpret_cast<const void *>(dev::latency_edge_kernel<RULE, T, SrcT, true, MC...>)
-                 : reinterpret_cast<const void *>(dev::latency_edge_kernel<RULE, T, SrcT, false, MC...>);
+  return with_bool(layered, [](auto L) {
+    return reinterpret_cast<const void *>(dev::latency_edge_kernel<RULE, T, SrcT, decltype(L)::value, MC...>);
+  });
 }
 template <typename T, typename SrcT>
 const void *edge_kernel_r(Rule rule, bool corrected, bool layered) {

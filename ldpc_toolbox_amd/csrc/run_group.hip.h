@@ -8,77 +8,30 @@ namespace ldpc {
 // ---- one group of codewords ----------------------------------------------------------------
 
 template <typename T>
-int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size_t nb, uint32_t max_iterations,
-                             uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior,
-                             hipStream_t s, bool may_block) {
-  const uint32_t G = static_cast<uint32_t>(w.G);
-  const uint32_t W = G / 64;
-  const uint32_t n = static_cast<uint32_t>(n_), m = static_cast<uint32_t>(m_);
+int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
+  const uint32_t max_iterations = call.max_iterations;
+  const size_t nb = call.nb;
+  // layout tile: codewords per self-contained sub-batch (kernels.hip.h, tile_base)
+  uint32_t tile = opt_tile_ ? opt_tile_ : (sizeof(T) == 4 ? 256 : 128);
+  tile = std::max<uint32_t>(64, tile / 64 * 64);
+  while (w.G % tile != 0) tile -= 64;
+  GroupFrame f(*this, w, call, tile);
+  const uint32_t G = f.G, W = f.W, n = f.n, m = f.m;
+  const hipStream_t s = f.s;
+  const ProgressPoll &poll = f.poll;
+  dev::State &st = f.st;
+  auto ticked = [&](uint32_t it) { return f.ticked(it); };
   T *chan = static_cast<T *>(w.chan), *post = static_cast<T *>(w.post), *msg = static_cast<T *>(w.msg);
   // default: enough waves that each handles ~4 nodes (oversubscription evens out the tail)
   const uint32_t target_waves = opt_waves_ ? opt_waves_ : 256 * 1024;
   // LDS columns per thread of the staged kernels: the Tanh rule works in one (rule_check_node), the others need
   // the inputs beside the outputs
   const uint32_t lds_columns = impl_.rule == Rule::Tanh ? 1u : 2u;
+  const Launch<T> launch{s, max_row_weight_ > 8 || opt_rec_long_, impl_.fast, impl_.correction != Correction::None,
+                         dev::MinsumCorr<T>{static_cast<T>(impl_.alpha()), static_cast<T>(impl_.beta())}};
+  const dev::Graph g = f.graph(d_edge_aux_, d_edge_peer_);
 
-  // layout tile: codewords per self-contained sub-batch (kernels.hip.h, tile_base)
-  uint32_t tile = opt_tile_ ? opt_tile_ : (sizeof(T) == 4 ? 256 : 128);
-  tile = std::max<uint32_t>(64, tile / 64 * 64);
-  while (G % tile != 0) tile -= 64;
-
-  g_knobs.rec_long = max_row_weight_ > 8 || opt_rec_long_;
-  g_knobs.fast = impl_.fast;
-  g_knobs.corr = impl_.correction != Correction::None;
-  g_knobs.alpha = impl_.alpha();
-  g_knobs.beta = impl_.beta();
-  g_knobs.row_scratch = nullptr;
-  dev::Graph g{d_row_ptr_, d_edge_col_, d_col_ptr_, d_col_edge_, m, n, static_cast<uint32_t>(e_),
-               nullptr,    nullptr,     nullptr,    0,           d_edge_aux_, d_edge_peer_};
-  dev::State st{w.done, w.iters, w.n_active, w.n_slots, w.slot_cw, nullptr, 0, 0, nullptr, nullptr, 0};
-  // progress word: the first check-node launch of iteration `it` runs with ticked(it)
-  w.epoch = (w.epoch % 0xFFFFFFu) + 1;
-  auto ticked = [&](uint32_t it) {
-    dev::State t = st;
-    t.publish = opt_poll_ ? w.d_flag : nullptr;
-    t.epoch = w.epoch;
-    t.tick = it;
-    return t;
-  };
-  const ProgressPoll poll{(opt_poll_ && w.d_flag) ? w.h_flag : nullptr, w.epoch, may_block,
-                          t_pace_lead ? t_pace_lead : (impl_.schedule == Schedule::Layered ? 2u : 8u), s};
-
-  grp::init_group(s, w.done, w.iters, w.unsat0, w.unsat1, w.n_active, w.n_slots,
-                                                         w.slot_cw, static_cast<uint32_t>(nb), G);
-  {
-    dim3 grid((n + 63) / 64, W);
-    const uint32_t block_size = pattern_len_ ? n / pattern_len_ : 0;
-    if (llrs_f64)
-      dev::ingest_kernel<double, T><<<grid, 256, 0, s>>>(static_cast<const double *>(llrs), input_len_,
-                                                        static_cast<uint32_t>(nb), n, G, tile, chan, post,
-                                                        w.rawbits, d_src_block_, block_size);
-    else
-      dev::ingest_kernel<float, T><<<grid, 256, 0, s>>>(static_cast<const float *>(llrs), input_len_,
-                                                       static_cast<uint32_t>(nb), n, G, tile, chan, post,
-                                                       w.rawbits, d_src_block_, block_size);
-    if (w.after_ingest) {
-      HIP_TRY(hipEventRecord(w.after_ingest, s));
-      if (w.ingest_seq) w.ingest_seq->fetch_add(1, std::memory_order_release);
-    }
-  }
-  // enough threads to fill the chip: each handles one packed word of a few checks
-  // a wavefront takes 64 packed words of a few checks; enough wavefronts to fill the chip
-  const uint32_t synd_chunks = (W + 63) / 64;
-  const uint32_t synd_rows =
-      std::max<uint32_t>(1, std::min<uint32_t>(64, uint32_t(uint64_t(m) * synd_chunks * 64 / kSyndThreads)));
-  const uint32_t synd_threads = 64 * synd_chunks * ((m + synd_rows - 1) / synd_rows);
-  auto syndrome_of = [&](const uint64_t *hard, uint32_t *unsat) {
-    if (m == 0) return;
-    grp::syndrome_bits(s, synd_threads, d_row_ptr_, d_edge_col_, m, hard,
-                                                                         unsat, w.n_active, w.n_slots, W, synd_rows);
-  };
-  auto latch = [&](uint32_t *unsat, int32_t it) {
-    grp::latch(s, w.done, w.iters, unsat, w.n_active, it, G);
-  };
+  if (int rc = f.begin(dev::ingest_kernel<float, T>, dev::ingest_kernel<double, T>, chan, post)) return rc;
   // (one codeword per lane: the paired-load form of the 16-bit posterior, pack_hard_pair_kernel, is slower here --
   // 210 vs 191 us for 8192 x BG1 Zc=384: 256-byte requests already stream, the exchange only adds work)
   // (16 K waves by default: the launch runs once per layered iteration and its waves are short -- at the 256 K of the other
@@ -89,17 +42,7 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
                                                                       W, pack_t.sched.waves_per_chunk);
   };
 
-  auto emit = [&](int zero_fill, int retire_only) {
-    dim3 grid(std::min<uint32_t>((n + 63) / 64, retire_only ? kRetireBlocks : 4096), W);
-    if (llrs_f64)
-      dev::emit_kernel<T, double><<<grid, 256, 0, s>>>(post, w.rawbits, st, &w.plan->do_compact, n, G, tile,
-                                                      static_cast<uint32_t>(out_len), bits, iterations,
-                                                      static_cast<double *>(posterior), zero_fill, retire_only);
-    else
-      dev::emit_kernel<T, float><<<grid, 256, 0, s>>>(post, w.rawbits, st, &w.plan->do_compact, n, G, tile,
-                                                     static_cast<uint32_t>(out_len), bits, iterations,
-                                                     static_cast<float *>(posterior), zero_fill, retire_only);
-  };
+  auto emit = [&](int zero_fill, int retire_only) { f.emit(post, &w.plan->do_compact, zero_fill, retire_only); };
   // batch compaction checkpoint (kernels.hip.h): everything decided on the device
   const Tiling mv_t = make_tiling(G, tile, 64, n, 256, kMoveWaves);
   uint32_t post_move_rows = 0;  // 0 = all rows; set by the flooding L-free paths below
@@ -136,10 +79,6 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
     return it <= 26 ? (it - first) % every == 0 : it % 4 == 0;
   };
 
-  // pre-check on the raw input: iterations = 0 (flooding.rs:57-64)
-  syndrome_of(w.rawbits, w.unsat0);
-  latch(w.unsat0, 0);
-
   uint32_t *unsat[2] = {w.unsat0, w.unsat1};
   int zero_fill = 0;
 
@@ -153,6 +92,7 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
     Tiling cn_t = make_tiling(G, tile, 64 * vec, m, stream_block, target_waves);
     uint32_t st_threads = 256;
     size_t st_lds = 0;
+    T *cn_scratch = nullptr;  // non-null: the LDS-staged kernel keeps its columns there
     if (!streaming) {
       if (staged_block(lds_columns, max_row_weight_, sizeof(T), &st_threads, &st_lds)) {
         cn_t = make_tiling(G, tile, 64, m, st_threads, target_waves);
@@ -162,7 +102,7 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
         st_lds = 0;
         cn_t = make_tiling(G, tile, 64, m, st_threads, std::min(target_waves, kScratchWaves));
         if (int rc = ensure_row_scratch(w, scratch_bytes_for(cn_t, max_row_weight_, sizeof(T)))) return rc;
-        g_knobs.row_scratch = w.row_scratch;
+        cn_scratch = static_cast<T *>(w.row_scratch);
       }
     }
     // the Tanh rule on graphs with rows of at most 12 edges: rows in registers (cn_reg_kernel: 32-bit byte offsets inside
@@ -223,31 +163,15 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
       const T *m_in = mbuf[(it + 1) & 1];
       const dev::State stp = ticked(it);
       timed_begin(kKernelCheck, s);
-      if (records) {
-        if (first)
-          Launch<T>::template cn_rec<true>(vec, rec_w_, rec_t, s, g, stp, chan, post, rbuf[(it + 1) & 1], rbuf[it & 1], msg,
-                                           unsat_out, rec_run);
-        else
-          Launch<T>::template cn_rec<false>(vec, rec_w_, rec_t, s, g, stp, chan, post, rbuf[(it + 1) & 1], rbuf[it & 1], msg,
-                                            unsat_out, rec_run);
-      } else if (lfree) {
-        if (first)
-          Launch<T>::template cn_lfree<true>(vec, wide_mask, cn_t, s, g, stp, chan, post, m_in, m_out, unsat_out);
-        else
-          Launch<T>::template cn_lfree<false>(vec, wide_mask, cn_t, s, g, stp, chan, post, m_in, m_out, unsat_out);
-      } else if (streaming) {
-        if (first)
-          Launch<T>::template cn_minsum<true>(vec, wide_mask, cn_t, s, g, stp, chan, msg, unsat_out);
-        else
-          Launch<T>::template cn_minsum<false>(vec, wide_mask, cn_t, s, g, stp, post, msg, unsat_out);
-      } else {
-        if (first)
-          Launch<T>::template cn_staged<true>(impl_.rule, cn_reg, d_row_recs_, cn_t, st_lds, s, g, stp, chan, msg, unsat_out,
-                                              max_row_weight_);
-        else
-          Launch<T>::template cn_staged<false>(impl_.rule, cn_reg, d_row_recs_, cn_t, st_lds, s, g, stp, post, msg, unsat_out,
-                                               max_row_weight_);
-      }
+      if (records)
+        launch.cn_rec(first, vec, rec_w_, rec_t, g, stp, chan, post, rbuf[(it + 1) & 1], rbuf[it & 1], msg, unsat_out, rec_run);
+      else if (lfree)
+        launch.cn_lfree(first, vec, wide_mask, cn_t, g, stp, chan, post, m_in, m_out, unsat_out);
+      else if (streaming)
+        launch.cn_minsum(first, vec, wide_mask, cn_t, g, stp, first ? chan : post, msg, unsat_out);
+      else
+        launch.cn_staged(first, impl_.rule, cn_reg, d_row_recs_, cn_t, st_lds, cn_scratch, g, stp, first ? chan : post, msg,
+                         unsat_out, max_row_weight_);
       timed_end(kKernelCheck, s);
       timed_begin(kKernelVar, s);
       // (deferred L-free stores: the first convergences of a slice get their L-free posteriors from the records of the latched
@@ -255,14 +179,14 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
       // almost always found nothing: 4.4 us + a 5.7 us dispatch gap per iteration)
       if (quiet && it > 1 && opt_vn_event_) {
         const dev::VnEvent<T> ev{d_free_var_, d_free_rs_, rbuf[(it - 1) & 1], n_free_};
-        Launch<T>::vn_event(vec, rec_w_, vn_keep_t, s, g_keep, st, chan, m_out, post, unsat_out, unsat[(it + 1) & 1],
-                            static_cast<int32_t>(it) - 1, ev);
+        launch.vn_event(vec, rec_w_, vn_keep_t, g_keep, st, chan, m_out, post, unsat_out, unsat[(it + 1) & 1],
+                        static_cast<int32_t>(it) - 1, ev);
       } else {
-        Launch<T>::vn(lfree, vec, lfree ? vn_keep_t : vn_t, s, lfree ? g_keep : g, st, chan, m_out, post,
-                      first ? nullptr : unsat_out, unsat[(it + 1) & 1], static_cast<int32_t>(it) - 1);
+        launch.vn(lfree, vec, lfree ? vn_keep_t : vn_t, lfree ? g_keep : g, st, chan, m_out, post,
+                  first ? nullptr : unsat_out, unsat[(it + 1) & 1], static_cast<int32_t>(it) - 1);
         if (quiet && it > 1)
-          Launch<T>::vn_free_rec(vec, rec_w_, vn_event_t, s, g_free, st, d_free_rs_, chan, rbuf[(it - 1) & 1], post,
-                                 static_cast<int32_t>(it) - 1);
+          launch.vn_free_rec(vec, rec_w_, vn_event_t, g_free, st, d_free_rs_, chan, rbuf[(it - 1) & 1], post,
+                             static_cast<int32_t>(it) - 1);
       }
       timed_end(kKernelVar, s);
       if (checkpoint_due(it) || tail_checkpoint(it)) {
@@ -274,20 +198,19 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
       }
     }
     if (records && max_iterations > 0) {
-      Launch<T>::vn_free_rec(vec, rec_w_, vn_free_t, s, g_free, st, d_free_rs_, chan, rbuf[max_iterations & 1], post, -1);
+      launch.vn_free_rec(vec, rec_w_, vn_free_t, g_free, st, d_free_rs_, chan, rbuf[max_iterations & 1], post, -1);
     } else if (lfree && max_iterations > 0) {
       // posterior of the L-free variables after the last iteration (no later check-node pass
       // rebuilds it): one variable-node pass over just them; frozen codewords are skipped
       dev::State st_nolatch = st;
-      Launch<T>::vn(true, vec, vn_free_t, s, g_free, st_nolatch, chan, mbuf[max_iterations & 1], post,
-                    nullptr, w.scratch_flags, -1);
+      launch.vn(true, vec, vn_free_t, g_free, st_nolatch, chan, mbuf[max_iterations & 1], post, nullptr, w.scratch_flags, -1);
     }
     if (max_iterations > 0) {
       // syndrome of the last posterior (flooding.rs:69-79 at iteration == max_iterations)
       pack(post);
       uint32_t *u = unsat[(max_iterations + 1) & 1];
-      syndrome_of(w.hardbits, u);
-      latch(u, static_cast<int32_t>(max_iterations));
+      f.syndrome_of(w.hardbits, u);
+      f.latch(u, static_cast<int32_t>(max_iterations));
     } else {
       zero_fill = 1;
     }
@@ -330,9 +253,7 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
           const uint32_t rvec = Launch<T>::hl_rec_vec(vec, reg_dmax);
           const Tiling t = make_tiling(G, tile, 64 * rvec, tnodes, sblock, target_waves);
           timed_begin(kKernelLayer, s);
-          const bool launched =
-              it == 1 ? Launch<T>::template hl_minsum_rec<true>(rvec, reg_dmax, t, s, g, st, d_level_rows_ + r0, cnt, post, msg)
-                      : Launch<T>::template hl_minsum_rec<false>(rvec, reg_dmax, t, s, g, st, d_level_rows_ + r0, cnt, post, msg);
+          const bool launched = launch.hl_minsum_rec(it == 1, rvec, reg_dmax, t, g, st, d_level_rows_ + r0, cnt, post, msg);
           timed_end(kKernelLayer, s);
           if (!launched) {
             fail("internal error: no row-record layered kernel for this level");
@@ -344,9 +265,7 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
           const uint32_t rvec = Launch<T>::hl_reg_vec(vec, reg_dmax);
           const Tiling t = make_tiling(G, tile, 64 * rvec, tnodes, sblock, target_waves);
           timed_begin(kKernelLayer, s);
-          const bool launched =
-              it == 1 ? Launch<T>::template hl_minsum_reg<true>(rvec, reg_dmax, t, s, g, st, d_level_rows_ + r0, cnt, post, msg)
-                      : Launch<T>::template hl_minsum_reg<false>(rvec, reg_dmax, t, s, g, st, d_level_rows_ + r0, cnt, post, msg);
+          const bool launched = launch.hl_minsum_reg(it == 1, rvec, reg_dmax, t, g, st, d_level_rows_ + r0, cnt, post, msg);
           timed_end(kKernelLayer, s);
           if (!launched) {
             fail("internal error: no register-resident layered kernel for this level");
@@ -357,10 +276,7 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
         if (streaming) {
           const Tiling t = make_tiling(G, tile, 64 * vec, tnodes, sblock, target_waves);
           timed_begin(kKernelLayer, s);
-          if (it == 1)
-            Launch<T>::template hl_minsum<true>(vec, t, s, g, st, d_level_rows_ + r0, cnt, post, msg);
-          else
-            Launch<T>::template hl_minsum<false>(vec, t, s, g, st, d_level_rows_ + r0, cnt, post, msg);
+          launch.hl_minsum(it == 1, vec, t, g, st, d_level_rows_ + r0, cnt, post, msg);
           timed_end(kKernelLayer, s);
           continue;
         }
@@ -387,25 +303,19 @@ int DeviceDecoder::run_group(Workspace &w, const void *llrs, bool llrs_f64, size
         // (the register-resident kernels read a level's row records, the two-pass kernel the row list)
         const uint32_t *ltab = !lreg ? d_level_rows_ + r0 : (serial ? d_serial_recs_ : d_level_recs_ + level_rec_ptr_[l]);
         const Tiling t = make_tiling(G, tile, 64, tnodes, lthreads, lfits ? target_waves : std::min(target_waves, kScratchWaves));
-        g_knobs.row_scratch = nullptr;
-        if (!lfits) {
-          if (scratch_bytes_for(t, ldmax, sizeof(T)) > w.row_scratch_bytes) {
-            fail("internal error: row scratch smaller than a level's launch");
-            return -3;
-          }
-          g_knobs.row_scratch = w.row_scratch;
+        if (!lfits && scratch_bytes_for(t, ldmax, sizeof(T)) > w.row_scratch_bytes) {
+          fail("internal error: row scratch smaller than a level's launch");
+          return -3;
         }
         timed_begin(kKernelLayer, s);
-        if (it == 1)
-          Launch<T>::template hl<true>(impl_.rule, lreg, t, llds, s, g, st, ltab, cnt, post, msg, ldmax);
-        else
-          Launch<T>::template hl<false>(impl_.rule, lreg, t, llds, s, g, st, ltab, cnt, post, msg, ldmax);
+        launch.hl(it == 1, impl_.rule, lreg, t, llds, lfits ? nullptr : static_cast<T *>(w.row_scratch), g, st, ltab, cnt, post,
+                  msg, ldmax);
         timed_end(kKernelLayer, s);
       }
       // horizontal_layered.rs:66-78
       pack(post);
-      syndrome_of(w.hardbits, w.unsat0);
-      latch(w.unsat0, static_cast<int32_t>(it));
+      f.syndrome_of(w.hardbits, w.unsat0);
+      f.latch(w.unsat0, static_cast<int32_t>(it));
       if (checkpoint_due(it)) compact(max_iterations - it, msg, false, hl_rec ? m * 3 : static_cast<uint32_t>(e_));
     }
   }

@@ -9,73 +9,28 @@ namespace ldpc {
 
 // ---- one group of codewords, 8-bit quantised arithmetics (kernels_i8.hip.h) ------------------
 
-int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, size_t nb, uint32_t max_iterations,
-                                uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior, hipStream_t s,
-                                bool may_block) {
-  const uint32_t G = static_cast<uint32_t>(w.G);
-  const uint32_t W = G / 64, tile = 256;
-  const uint32_t n = static_cast<uint32_t>(n_), m = static_cast<uint32_t>(m_);
+int DeviceDecoder::run_group_i8(Workspace &w, const GroupCall &call) {
+  const uint32_t max_iterations = call.max_iterations;
+  GroupFrame f(*this, w, call, 256);
+  const uint32_t G = f.G, n = f.n, m = f.m, tile = f.tile;
+  const hipStream_t s = f.s;
+  const dev::State &st = f.st;
   int8_t *chan = static_cast<int8_t *>(w.chan), *msg = static_cast<int8_t *>(w.msg);
   int16_t *post = static_cast<int16_t *>(w.post);
   const uint32_t target_waves = opt_waves_ ? opt_waves_ : 128 * 1024;
-  dev::Graph g{d_row_ptr_, d_edge_col_, d_col_ptr_, d_col_edge_, m, n, static_cast<uint32_t>(e_),
-               nullptr,    nullptr,     nullptr,    0,           nullptr, nullptr};
-  dev::State st{w.done, w.iters, w.n_active, w.n_slots, w.slot_cw, nullptr, 0, 0, nullptr, nullptr, 0};
-  // progress word: the first check-node launch of iteration `it` runs with ticked(it)
-  w.epoch = (w.epoch % 0xFFFFFFu) + 1;
-  auto ticked = [&](uint32_t it) {
-    dev::State t = st;
-    t.publish = opt_poll_ ? w.d_flag : nullptr;
-    t.epoch = w.epoch;
-    t.tick = it;
-    return t;
-  };
-  const ProgressPoll poll{(opt_poll_ && w.d_flag) ? w.h_flag : nullptr, w.epoch, may_block,
-                          t_pace_lead ? t_pace_lead : (impl_.schedule == Schedule::Layered ? 2u : 8u), s};
+  const dev::Graph g = f.graph(nullptr, nullptr);
   const dev::I8Opts o{impl_.rule == Rule::Aminstar, impl_.jones, impl_.hardlimit, impl_.deg1clip};
   // Minsumi8*: check nodes without LDS or scratch (kernels_i8_minsum.hip.h); a = 16 and b = 0 are the plain rule
   const bool minsum = impl_.rule == Rule::Minsum;
   const dev::I8MinsumOpts mo{impl_.hardlimit, impl_.correction == Correction::Normalized ? impl_.correction_int : 16,
                              impl_.correction == Correction::Offset ? impl_.correction_int : 0};
 
-  grp::init_group(s, w.done, w.iters, w.unsat0, w.unsat1, w.n_active, w.n_slots,
-                                                         w.slot_cw, static_cast<uint32_t>(nb), G);
-  {
-    dim3 grid((n + 63) / 64, W);
-    const uint32_t block_size = pattern_len_ ? n / pattern_len_ : 0;
-    if (llrs_f64)
-      dev::ingest_i8_kernel<double><<<grid, 256, 0, s>>>(static_cast<const double *>(llrs), input_len_,
-                                                        static_cast<uint32_t>(nb), n, G, tile, chan, post, w.rawbits,
-                                                        d_src_block_, block_size);
-    else
-      dev::ingest_i8_kernel<float><<<grid, 256, 0, s>>>(static_cast<const float *>(llrs), input_len_,
-                                                       static_cast<uint32_t>(nb), n, G, tile, chan, post, w.rawbits,
-                                                       d_src_block_, block_size);
-    if (w.after_ingest) {
-      HIP_TRY(hipEventRecord(w.after_ingest, s));
-      if (w.ingest_seq) w.ingest_seq->fetch_add(1, std::memory_order_release);
-    }
-  }
-  // a wavefront takes 64 packed words of a few checks; enough wavefronts to fill the chip
-  const uint32_t synd_chunks = (W + 63) / 64;
-  const uint32_t synd_rows =
-      std::max<uint32_t>(1, std::min<uint32_t>(64, uint32_t(uint64_t(m) * synd_chunks * 64 / kSyndThreads)));
-  const uint32_t synd_threads = 64 * synd_chunks * ((m + synd_rows - 1) / synd_rows);
-  auto syndrome_of = [&](const uint64_t *hard, uint32_t *unsat) {
-    if (m == 0) return;
-    grp::syndrome_bits(s, synd_threads, d_row_ptr_, d_edge_col_, m, hard, unsat,
-                                                                         w.n_active, w.n_slots, W, synd_rows);
-  };
-  auto latch = [&](uint32_t *unsat, int32_t it) {
-    grp::latch(s, w.done, w.iters, unsat, w.n_active, it, G);
-  };
+  if (int rc = f.begin(dev::ingest_i8_kernel<float>, dev::ingest_i8_kernel<double>, chan, post)) return rc;
   const Tiling pack_t = make_tiling(G, tile, 128, n, 256, target_waves);
   auto pack = [&]() {
     dev::pack_hard_pair_kernel<int16_t><<<pack_t.blocks, pack_t.threads, 0, s>>>(post, w.hardbits, w.n_active, w.n_slots,
-                                                                                n, tile, W, pack_t.sched.waves_per_chunk);
+                                                                                n, tile, f.W, pack_t.sched.waves_per_chunk);
   };
-  syndrome_of(w.rawbits, w.unsat0);
-  latch(w.unsat0, 0);
 
   uint32_t threads = 256;
   size_t lds = 0;
@@ -109,29 +64,22 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
     set_lds(reinterpret_cast<const void *>(dev::cn_i8_kernel<true>));
     set_lds(reinterpret_cast<const void *>(dev::cn_i8_kernel<false>));
     for (uint32_t it = 1; it <= max_iterations; it++) {
-      if (it > 1 && poll.finished(it)) break;
+      if (it > 1 && f.poll.finished(it)) break;
       const bool first = it == 1;
       uint32_t *unsat_out = unsat[it & 1];
-      const dev::State stp = ticked(it);
+      const dev::State stp = f.ticked(it);
       timed_begin(kKernelCheck, s);
-      if (minsum) {
-        if (first)
-          dev::cn_i8_minsum_kernel<true><<<cn_t.blocks, cn_t.threads, 0, s>>>(g, cn_t.sched, stp, mo, chan, post, msg, unsat_out);
+      with_bool(first, [&](auto FIRST) {
+        constexpr bool F = decltype(FIRST)::value;
+        if (minsum)
+          dev::cn_i8_minsum_kernel<F><<<cn_t.blocks, cn_t.threads, 0, s>>>(g, cn_t.sched, stp, mo, chan, post, msg, unsat_out);
+        else if (!i8_fits)
+          dev::cn_i8_kernel<F, true><<<cn_t.blocks, cn_t.threads, 0, s>>>(g, cn_t.sched, stp, o, chan, post, msg, unsat_out,
+                                                                          max_row_weight_, i8_scratch);
         else
-          dev::cn_i8_minsum_kernel<false><<<cn_t.blocks, cn_t.threads, 0, s>>>(g, cn_t.sched, stp, mo, chan, post, msg, unsat_out);
-      } else if (!i8_fits) {
-        if (first)
-          dev::cn_i8_kernel<true, true><<<cn_t.blocks, cn_t.threads, 0, s>>>(g, cn_t.sched, stp, o, chan, post, msg, unsat_out,
-                                                                             max_row_weight_, i8_scratch);
-        else
-          dev::cn_i8_kernel<false, true><<<cn_t.blocks, cn_t.threads, 0, s>>>(g, cn_t.sched, stp, o, chan, post, msg, unsat_out,
-                                                                              max_row_weight_, i8_scratch);
-      } else if (first)
-        dev::cn_i8_kernel<true><<<cn_t.blocks, cn_t.threads, lds, s>>>(g, cn_t.sched, stp, o, chan, post, msg, unsat_out,
-                                                                       max_row_weight_);
-      else
-        dev::cn_i8_kernel<false><<<cn_t.blocks, cn_t.threads, lds, s>>>(g, cn_t.sched, stp, o, chan, post, msg,
-                                                                        unsat_out, max_row_weight_);
+          dev::cn_i8_kernel<F><<<cn_t.blocks, cn_t.threads, lds, s>>>(g, cn_t.sched, stp, o, chan, post, msg, unsat_out,
+                                                                      max_row_weight_);
+      });
       timed_end(kKernelCheck, s);
       timed_begin(kKernelVar, s);
       dev::vn_i8_kernel<<<vn_t.blocks, vn_t.threads, 0, s>>>(g, vn_t.sched, st, o, chan, msg, post,
@@ -142,8 +90,8 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
     if (max_iterations > 0) {
       pack();
       uint32_t *u = unsat[(max_iterations + 1) & 1];
-      syndrome_of(w.hardbits, u);
-      latch(u, static_cast<int32_t>(max_iterations));
+      f.syndrome_of(w.hardbits, u);
+      f.latch(u, static_cast<int32_t>(max_iterations));
     } else {
       zero_fill = 1;
     }
@@ -155,8 +103,8 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
     const bool serial = n_levels > opt_serial_levels_;
     const uint32_t n_launch = serial ? std::min<uint32_t>(n_levels, 1) : n_levels;
     for (uint32_t it = 1; it <= max_iterations; it++) {
-      if (it > 1 && poll.finished(it)) break;
-      const dev::State stp = ticked(it);
+      if (it > 1 && f.poll.finished(it)) break;
+      const dev::State stp = f.ticked(it);
       for (uint32_t l = 0; l < n_launch; l++) {
         const dev::State &st = l == 0 ? stp : st0;
         const uint32_t r0 = serial ? 0 : level_ptr_[l], cnt = serial ? m : level_ptr_[l + 1] - level_ptr_[l];
@@ -181,76 +129,44 @@ int DeviceDecoder::run_group_i8(Workspace &w, const void *llrs, bool llrs_f64, s
           fail("internal error: row scratch smaller than a level's launch");
           return -3;
         }
-        auto launch = [&](auto k) {
+        // k(..., tail...): hl_i8_reg_kernel ends with dmax, hl_i8_kernel with dmax and its scratch
+        auto launch = [&](auto k, auto... tail) {
           if (llds > 48 * 1024)
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       static_cast<int>(llds));
-          k<<<t.blocks, t.threads, llds, s>>>(g, t.sched, st, o, d_level_rows_ + r0, cnt, post, msg, ldmax);
-        };
-        auto launch_staged = [&](auto k, uint32_t *scratch) {
-          if (llds > 48 * 1024)
-            (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      static_cast<int>(llds));
-          k<<<t.blocks, t.threads, llds, s>>>(g, t.sched, st, o, d_level_rows_ + r0, cnt, post, msg, ldmax, scratch);
+          k<<<t.blocks, t.threads, llds, s>>>(g, t.sched, st, o, d_level_rows_ + r0, cnt, post, msg, tail...);
         };
         auto launch_minsum = [&](auto k) {
           const Tiling mt = make_tiling(G, tile, 256, serial ? 1 : cnt, serial ? 64 : 256, target_waves);
           k<<<mt.blocks, mt.threads, 0, s>>>(g, mt.sched, st, mo, d_level_rows_ + r0, cnt, post, msg);
         };
         timed_begin(kKernelLayer, s);
-        if (minsum) {
-          if (it == 1) {
+        with_bool(it == 1, [&](auto FIRST) {
+          constexpr bool F = decltype(FIRST)::value;
+          if (minsum) {
             if (lreg == 12)
-              launch_minsum(dev::hl_i8_minsum_kernel<12, true>);
+              launch_minsum(dev::hl_i8_minsum_kernel<12, F>);
             else if (lreg == 24)
-              launch_minsum(dev::hl_i8_minsum_kernel<24, true>);
+              launch_minsum(dev::hl_i8_minsum_kernel<24, F>);
             else
-              launch_minsum(dev::hl_i8_minsum_kernel<0, true>);
-          } else {
-            if (lreg == 12)
-              launch_minsum(dev::hl_i8_minsum_kernel<12, false>);
-            else if (lreg == 24)
-              launch_minsum(dev::hl_i8_minsum_kernel<24, false>);
-            else
-              launch_minsum(dev::hl_i8_minsum_kernel<0, false>);
-          }
-        } else if (it == 1) {
-          if (lreg == 12)
-            launch(dev::hl_i8_reg_kernel<12, true>);
+              launch_minsum(dev::hl_i8_minsum_kernel<0, F>);
+          } else if (lreg == 12)
+            launch(dev::hl_i8_reg_kernel<12, F>, ldmax);
           else if (lreg == 24)
-            launch(dev::hl_i8_reg_kernel<24, true>);
+            launch(dev::hl_i8_reg_kernel<24, F>, ldmax);
           else if (!lfits)
-            launch_staged(dev::hl_i8_kernel<true, true>, i8_scratch);
+            launch(dev::hl_i8_kernel<F, true>, ldmax, i8_scratch);
           else
-            launch_staged(dev::hl_i8_kernel<true>, nullptr);
-        } else {
-          if (lreg == 12)
-            launch(dev::hl_i8_reg_kernel<12, false>);
-          else if (lreg == 24)
-            launch(dev::hl_i8_reg_kernel<24, false>);
-          else if (!lfits)
-            launch_staged(dev::hl_i8_kernel<false, true>, i8_scratch);
-          else
-            launch_staged(dev::hl_i8_kernel<false>, nullptr);
-        }
+            launch(dev::hl_i8_kernel<F>, ldmax, nullptr);
+        });
         timed_end(kKernelLayer, s);
       }
       pack();
-      syndrome_of(w.hardbits, w.unsat0);
-      latch(w.unsat0, static_cast<int32_t>(it));
+      f.syndrome_of(w.hardbits, w.unsat0);
+      f.latch(w.unsat0, static_cast<int32_t>(it));
     }
   }
-  {
-    dim3 grid(std::min<uint32_t>((n + 63) / 64, 4096), W);
-    if (llrs_f64)
-      dev::emit_kernel<int16_t, double><<<grid, 256, 0, s>>>(post, w.rawbits, st, nullptr, n, G, tile,
-                                                            static_cast<uint32_t>(out_len), bits, iterations,
-                                                            static_cast<double *>(posterior), zero_fill, 0);
-    else
-      dev::emit_kernel<int16_t, float><<<grid, 256, 0, s>>>(post, w.rawbits, st, nullptr, n, G, tile,
-                                                           static_cast<uint32_t>(out_len), bits, iterations,
-                                                           static_cast<float *>(posterior), zero_fill, 0);
-  }
+  f.emit(post, nullptr, zero_fill, 0);
   HIP_TRY(hipGetLastError());
   return 0;
 }

@@ -7,8 +7,11 @@
 //   * a kernel launch is a no-op -- except that a launch carrying a decoder State with a progress word publishes
 //     (epoch, iteration, codewords running) there as the real kernels do, with "running" scripted by HIP_STUB_DONE_AT
 //     (0 from that iteration on: the host's early-termination paths run);
-//   * HIP_STUB_FAIL=<function>:<n> makes the n-th call of that function return hipErrorUnknown.
+//   * HIP_STUB_FAIL=<function>:<n> makes the n-th call of that function return hipErrorUnknown;
+//   * HIP_STUB_TRACE=<file> appends one line per kernel launch, in the host's enqueue order: the stream's ordinal in
+//     creation order, grid, block, dynamic LDS bytes and the kernel's demangled name (hip_stub_trace_note adds a "# ..." line).
 // Built with the same host-only clang mode as the library objects it is linked with (it needs dev::State).
+#include <cxxabi.h>
 #include <hip/hip_runtime_api.h>
 
 #include <atomic>
@@ -32,7 +35,10 @@
 
 namespace {
 
+std::atomic<unsigned> g_streams{0};
+
 struct Stream {
+  const unsigned ordinal = g_streams++;  // in creation order (HIP_STUB_TRACE)
   std::thread worker;
   std::mutex m;
   std::condition_variable cv, idle;
@@ -116,6 +122,26 @@ struct LaunchConfig {
 thread_local LaunchConfig t_config;
 
 std::atomic<uint64_t> g_launches{0};
+
+// HIP_STUB_TRACE: one line at a time, appended by whichever host thread makes the launch
+void trace_line(const std::string &line) {
+  static const char *path = std::getenv("HIP_STUB_TRACE");
+  if (!path) return;
+  static std::mutex m;
+  std::lock_guard<std::mutex> lock(m);
+  static std::FILE *f = std::fopen(path, "a");
+  if (!f) return;
+  std::fputs(line.c_str(), f);
+  std::fputc('\n', f);
+  std::fflush(f);
+}
+std::string demangled(const std::string &name) {
+  int status = 0;
+  char *d = abi::__cxa_demangle(name.c_str(), nullptr, nullptr, &status);
+  std::string out = (status == 0 && d) ? d : name;
+  std::free(d);
+  return out;
+}
 
 bool fail_now(const char *fn) {
   static const char *spec = std::getenv("HIP_STUB_FAIL");
@@ -297,7 +323,7 @@ void __hipRegisterFunction(void **, const void *host_fun, char *, const char *de
 }
 void __hipRegisterVar(void **, void *, char *, const char *, int, size_t, int, int) {}
 
-hipError_t hipLaunchKernel(const void *fun, dim3, dim3, void **args, size_t, hipStream_t s) {
+hipError_t hipLaunchKernel(const void *fun, dim3 grid, dim3 block, void **args, size_t shmem, hipStream_t s) {
   if (fail_now("hipLaunchKernel")) {
     g_last_error = static_cast<int>(hipErrorUnknown);
     return hipErrorUnknown;
@@ -307,7 +333,15 @@ hipError_t hipLaunchKernel(const void *fun, dim3, dim3, void **args, size_t, hip
   {
     std::lock_guard<std::mutex> lock(g_reg_mutex);
     auto it = kernel_names().find(fun);
-    if (it != kernel_names().end()) at = state_arg(it->second);
+    if (it != kernel_names().end()) {
+      at = state_arg(it->second);
+      if (std::getenv("HIP_STUB_TRACE")) {
+        char geometry[128];
+        std::snprintf(geometry, sizeof(geometry), "%u grid %u %u %u block %u %u %u lds %zu ", as_stream(s)->ordinal, grid.x, grid.y,
+                      grid.z, block.x, block.y, block.z, shmem);
+        trace_line(geometry + demangled(it->second));
+      }
+    }
   }
   if (at < 0) {
     as_stream(s)->push([] {});
@@ -325,5 +359,6 @@ hipError_t hipLaunchKernel(const void *fun, dim3, dim3, void **args, size_t, hip
 }
 
 unsigned long long hip_stub_launches(void) { return g_launches.load(); }
+void hip_stub_trace_note(const char *text) { trace_line(std::string("# ") + text); }
 
 }  // extern "C"

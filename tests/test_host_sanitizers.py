@@ -55,17 +55,27 @@ def test_layered_level_tables_under_asan_ubsan(tmp_path):
     assert "slice tasks driver: ok" in r.stdout
 
 
-def test_host_threads_are_clean_under_tsan(tmp_path):
+_TSAN_BUILD = {}
+
+
+def _tsan_driver(tmp_path_factory):
+    """tests/tsan_driver: the library's host code + tests/hip_stub under ThreadSanitizer, built once for the module"""
+    if "exe" not in _TSAN_BUILD:
+        out = str(tmp_path_factory.mktemp("tsan"))
+        b = subprocess.run([os.path.join(ROOT, "tests", "hip_stub", "build.sh"), out], capture_output=True, text=True, timeout=900)
+        assert b.returncode == 0, b.stdout[-2000:] + b.stderr[-4000:]
+        _TSAN_BUILD["exe"] = os.path.join(out, "tsan_driver")
+    return _TSAN_BUILD["exe"]
+
+
+def test_host_threads_are_clean_under_tsan(tmp_path_factory):
     """SURVEY section 5 "Race detection": the library's real host code (c_api.cpp, device_decoder.hip, simulator.hip
     compiled host-only) under ThreadSanitizer against tests/hip_stub -- streams are worker threads, events are counters,
     kernels publish the progress word.  Scenarios: every group runs all its iterations; the device "finishes" at
     iteration 3 / 1 (the enqueuing threads' early exits and pacing); a HIP call fails somewhere in the middle (the
     error returns of decode_host / decode_device with lane threads alive).  Round 4 found and fixed two unsynchronised
     writes this way (skew_record_ and another member written by both lanes' threads)."""
-    out = str(tmp_path / "tsan")
-    b = subprocess.run([os.path.join(ROOT, "tests", "hip_stub", "build.sh"), out], capture_output=True, text=True, timeout=900)
-    assert b.returncode == 0, b.stdout[-2000:] + b.stderr[-4000:]
-    exe = os.path.join(out, "tsan_driver")
+    exe = _tsan_driver(tmp_path_factory)
     scenarios = [({}, "0"), ({"HIP_STUB_DONE_AT": "3"}, "0"), ({"HIP_STUB_DONE_AT": "1"}, "0")]
     scenarios += [({"HIP_STUB_FAIL": f}, "1") for f in ("hipEventRecord:3", "hipEventRecord:40", "hipStreamWaitEvent:2",
                                                         "hipStreamWaitEvent:25", "hipLaunchKernel:7000", "hipMemcpyAsync:9",
@@ -76,3 +86,46 @@ def test_host_threads_are_clean_under_tsan(tmp_path):
         text = r.stdout + r.stderr
         assert "ThreadSanitizer" not in text, (extra, text[-6000:])
         assert r.returncode == 0 and "tsan driver: ok" in r.stdout, (extra, text[-3000:])
+
+
+def test_launch_trace_keeps_the_arithmetic_and_the_pack_width(tmp_path_factory, tmp_path):
+    """Which kernel a launch names decides the arithmetic (normalized / offset min-sum: the x_kernel<..., MinsumCorr<T>>
+    instantiations) and must respect the pack width of the type (f64: at most two codewords per lane).  `tsan_driver
+    trace` walks every such choice of launch.hip.h, run_group.hip.h and run_group_i8.hip on the CPU -- the stub writes
+    down stream, geometry and kernel name of every launch -- with "poll" 0 and "lane_threads" 0, so that the host's
+    enqueue order depends on the inputs alone."""
+    import re
+    exe = _tsan_driver(tmp_path_factory)
+    trace = tmp_path / "launches.txt"
+    env = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66", HIP_STUB_TRACE=str(trace))
+    r = subprocess.run([exe, "trace"], capture_output=True, text=True, env=env, timeout=600)
+    assert r.returncode == 0 and "trace: ok" in r.stdout and "ThreadSanitizer" not in r.stdout + r.stderr, (r.stdout + r.stderr)[-4000:]
+    rules = dict(re.findall(r"(kRuleMinsum(?:Corr)?) = (\d+)", open(os.path.join(CSRC, "kernels_common.hip.h")).read()))
+    minsum_rules = {rules["kRuleMinsum"], rules["kRuleMinsumCorr"]}
+    sections = []  # (implementation, [kernel names])
+    for line in trace.read_text().splitlines():
+        if line.startswith("# "):
+            sections.append((line.split()[1], []))
+        else:
+            stream, name = re.fullmatch(r"(\d+) grid \d+ \d+ \d+ block \d+ \d+ \d+ lds \d+ (.*)", line).groups()
+            sections[-1][1].append(name)
+    assert all(names for _, names in sections)
+
+    def arithmetic_is_minsum(name):
+        staged = re.search(r"(?:cn_staged|hl_level|hl_level_reg)_kernel<(\d+),", name)
+        return "minsum" in name or (staged is not None and staged.group(1) in minsum_rules)
+
+    corrected = [names for impl, names in sections if re.fullmatch(r"(HL)?(Norm|Offset)Minsumf(32|64)", impl)]
+    plain = [names for impl, names in sections if re.fullmatch(r"(HL)?Minsumf(32|64)", impl)]
+    f64 = [names for impl, names in sections if impl.endswith("f64")]
+    assert len(corrected) >= 2 and len(plain) >= 2 and len(f64) >= 2
+    for names in corrected:
+        hot = [k for k in names if arithmetic_is_minsum(k)]
+        assert hot and all("MinsumCorr<" in k for k in hot), [k for k in hot if "MinsumCorr<" not in k][:3]
+    for names in plain:
+        assert any(arithmetic_is_minsum(k) for k in names)
+        assert not any("MinsumCorr<" in k for k in names), [k for k in names if "MinsumCorr<" in k][:3]
+    for names in f64:
+        assert not any(re.search(r"_kernel<double, 4,", k) for k in names)
+    # (the test's own eyes: the f32 sections do launch four codewords per lane, under the name the f64 check looks for)
+    assert any(re.search(r"_kernel<float, 4,", k) for _, names in sections for k in names)

@@ -6,17 +6,22 @@
 // returns (HIP_STUB_FAIL).  Results are meaningless (no kernel runs); return codes and the absence of TSan reports are
 // what is checked.  The reference's contract for a handle is `Send`, one call at a time (src/decoder.rs:19); two
 // handles driven by two threads must not interfere either.
+// `tsan_driver trace` (with HIP_STUB_TRACE=<file>) instead walks a fixed list of (code, implementation, options) through
+// every launch choice the host makes from run-time values, with the host's enqueue order a function of the inputs alone
+// ("poll" 0, "lane_threads" 0): the stub writes the launches down, test_launch_trace_* reads them.
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <string>
 #include <thread>
+#include <utility>
 #include <vector>
 
 #include "../include/ldpc_toolbox.h"
 
 extern "C" unsigned long long hip_stub_launches(void);
+extern "C" void hip_stub_trace_note(const char *text);
 
 static std::string alist_of(const char *spec) {
   const size_t need = ldpc_toolbox_code_alist(spec, nullptr, 0);
@@ -80,7 +85,133 @@ static int drive(const char *spec, const char *impl, size_t batch, int lanes, in
   return bad;
 }
 
+// ---- trace mode ------------------------------------------------------------------------------------------------------
+
+// a 14 x n matrix with eight long rows of base .. base + 3 * spread edges and six shorter ones, every column in at least one
+// row (as test_rows_beyond_the_lds_limit builds, without the random numbers).  "long-rows": 330..420 edges, beyond the 320
+// the LDS-staged kernels hold; "wide-rows": at most 64, beyond a 32-bit sign mask and a three-word row record
+static std::string synthetic_alist(size_t n, size_t base, size_t spread) {
+  const size_t m = 14;
+  const size_t step[14] = {7, 11, 13, 17, 19, 23, 29, 31, 37, 41, 43, 47, 49, 53};  // coprime to n: a row's columns are distinct
+  std::vector<std::vector<size_t>> col_rows(n);
+  for (size_t r = 0; r < m; r++) {
+    const size_t deg = r < 8 ? base + spread * (r % 4) : 5 + r;
+    for (size_t i = 0; i < deg; i++) col_rows[(r * 101 + i * step[r]) % n].push_back(r);
+  }
+  for (size_t c = 0; c < n; c++)
+    if (col_rows[c].empty()) col_rows[c].push_back(8 + c % 6);
+  std::string a = std::to_string(n) + " 14\n\n\n\n";  // (the reader takes the dimensions and the column lists)
+  for (size_t c = 0; c < n; c++) {
+    for (size_t r : col_rows[c]) a += std::to_string(r + 1) + " ";
+    a += "\n";
+  }
+  return a;
+}
+
+struct TraceCase {
+  const char *spec, *impl;
+  std::vector<std::vector<std::pair<const char *, int>>> option_sets;  // each on top of the defaults
+  int llrs_f64 = -1;  // the caller's LLRs: -1 = in the implementation's precision
+};
+
+// 300 frames in groups of 256 (one full group, one ragged), 3 iterations (a first one and later ones), host and device entry
+static int trace_case(const TraceCase &tc) {
+  const std::string alist = std::strcmp(tc.spec, "long-rows") == 0   ? synthetic_alist(1500, 330, 30)
+                            : std::strcmp(tc.spec, "wide-rows") == 0 ? synthetic_alist(500, 40, 3)
+                                                                     : alist_of(tc.spec);
+  const bool f64 = tc.llrs_f64 < 0 ? std::strstr(tc.impl, "f64") != nullptr : tc.llrs_f64 != 0;
+  int bad = 0;
+  for (const auto &options : tc.option_sets) {
+    void *dec = ldpc_toolbox_decoder_ctor_alist_string(alist.c_str(), tc.impl, "");
+    if (!dec) {
+      std::fprintf(stderr, "%s %s: ctor failed: %s\n", tc.spec, tc.impl, ldpc_toolbox_last_error());
+      return 1;
+    }
+    std::string note = std::string(tc.impl) + " " + tc.spec + (f64 ? " llrs=f64" : " llrs=f32");
+    for (const auto &kv : {std::pair<const char *, int>{"latency", 0}, {"latency_edge", 0}, {"group_size", 256}, {"poll", 0}, {"lane_threads", 0}})
+      ldpc_toolbox_decoder_set(dec, kv.first, kv.second);
+    for (const auto &kv : options) {
+      if (ldpc_toolbox_decoder_set(dec, kv.first, kv.second) != 0) {
+        std::fprintf(stderr, "%s: option %s refused\n", tc.impl, kv.first);
+        bad++;
+      }
+      note += std::string(" ") + kv.first + "=" + std::to_string(kv.second);
+    }
+    hip_stub_trace_note(note.c_str());
+    const size_t n = size_t(get(dec, "n")), k = size_t(get(dec, "k")), batch = 300;
+    std::vector<uint8_t> out(batch * k);
+    std::vector<int32_t> its(batch);
+    int rc_host, rc_device;
+    if (f64) {
+      std::vector<double> llrs(batch * n, 1.0), post(batch * n);
+      rc_host = ldpc_toolbox_decoder_decode_batch_f64(dec, out.data(), k, llrs.data(), n, batch, 3, its.data(), post.data());
+      rc_device = ldpc_toolbox_decoder_decode_batch_f64_device(dec, out.data(), k, llrs.data(), n, batch, 3, its.data(), post.data(), nullptr);
+    } else {
+      std::vector<float> llrs(batch * n, 1.0f), post(batch * n);
+      rc_host = ldpc_toolbox_decoder_decode_batch_f32(dec, out.data(), k, llrs.data(), n, batch, 3, its.data(), post.data());
+      rc_device = ldpc_toolbox_decoder_decode_batch_f32_device(dec, out.data(), k, llrs.data(), n, batch, 3, its.data(), post.data(), nullptr);
+    }
+    if (rc_host != 0 || rc_device != 0) {
+      std::fprintf(stderr, "%s: rc %d / %d (%s)\n", note.c_str(), rc_host, rc_device, ldpc_toolbox_last_error());
+      bad++;
+    }
+    ldpc_toolbox_decoder_dtor(dec);
+  }
+  return bad;
+}
+
+static int trace_main() {
+  std::vector<std::vector<std::pair<const char *, int>>> flooding_minsum;
+  for (int vec : {4, 2, 1})
+    for (int records : {0, 2})
+      for (int lfree : {0, 1}) flooding_minsum.push_back({{"vec", vec}, {"records", records}, {"lfree", lfree}});
+  flooding_minsum.push_back({{"records", 2}, {"rec_long", 1}});
+  flooding_minsum.push_back({{"staged_minsum", 1}});
+  // the layered min-sum forms: row records, register-resident rows, streaming, the two-pass level kernel (x register-resident)
+  const std::vector<std::vector<std::pair<const char *, int>>> layered_minsum = {
+      {}, {{"vec", 2}}, {{"vec", 1}}, {{"hl_records", 0}}, {{"hl_records", 0}, {"vec", 1}}, {{"hl_reg", 0}}, {{"hl_reg", 0}, {"vec", 2}}, {{"hl_reg", 0}, {"vec", 1}}, {{"staged_minsum", 1}},
+      {{"staged_minsum", 1}, {"hl_reg", 0}}, {{"serial_levels", 0}}, {{"serial_levels", 0}, {"hl_reg", 0}}};
+  const std::vector<std::vector<std::pair<const char *, int>>> layered_staged = {
+      {}, {{"hl_reg", 0}}, {{"serial_levels", 0}}, {{"serial_levels", 0}, {"hl_reg", 0}}};
+  const std::vector<TraceCase> cases = {
+      {"ar4ja:1/2:1024", "Minsumf32", flooding_minsum},
+      {"ar4ja:1/2:1024", "Minsumf64", {{{"vec", 4}}, {{"vec", 4}, {"records", 2}}, {{"vec", 4}, {"lfree", 0}}}},
+      {"ar4ja:1/2:1024", "NormMinsumf32", flooding_minsum},
+      {"nr5g:1:8", "HLOffsetMinsumf64", layered_minsum},
+      {"wide-rows", "Minsumf32", {{{"lfree", 0}, {"records", 0}}, {{"records", 0}}, {{"records", 2}}, {{"records", 2}, {"vn_event", 0}}}},
+      {"wide-rows", "OffsetMinsumf64", {{{"lfree", 0}, {"records", 0}}, {{"records", 2}}}},
+      {"ar4ja:1/2:1024", "Tanhf32", {{{"cn_reg", 0}}, {{"cn_reg", 1}}}},
+      {"dvbs2:R3_5short", "Tanhf32", {{}}},
+      {"ar4ja:1/2:1024", "Phif32@fast", {{}}, 1},
+      {"nr5g:1:8", "HLTanhf32@fast", {{}}},
+      {"nr5g:1:8", "HLTanhf32", layered_staged},
+      {"nr5g:1:8", "HLMinsumf32", layered_minsum},
+      {"dvbs2:R1_2short", "HLMinsumf32", {{}, {{"hl_records", 0}}, {{"hl_reg", 0}}}},
+      {"dvbs2:R8_9short", "HLNormMinsumf32", {{}}},
+      {"dvbs2:R8_9short", "Minsumf32", {{{"records", 2}}, {{"records", 2}, {"vn_event", 0}}}},
+      {"long-rows", "Phif32", {{}}},
+      {"long-rows", "HLPhif32", {{}}},
+      {"long-rows", "Minsumf32", {{}, {{"staged_minsum", 1}}}},
+      {"long-rows", "HLOffsetMinsumf32", {{}, {{"staged_minsum", 1}}}},
+      {"long-rows", "Minstarapproxi8", {{}}},
+      {"long-rows", "HLAminstari8", {{}}},
+      {"nr5g:1:8", "Minstarapproxi8", {{}}, 1},
+      {"nr5g:1:8", "HLAminstari8", {{}, {{"hl_reg", 0}}, {{"serial_levels", 0}}}},
+      {"nr5g:1:8", "Minsumi8Norm", {{}}},
+      {"nr5g:1:8", "HLMinsumi8Offset", {{}, {{"hl_reg", 0}}, {{"serial_levels", 0}}}},
+  };
+  int bad = 0;
+  size_t scenarios = 0;
+  for (const auto &tc : cases) {
+    bad += trace_case(tc);
+    scenarios += tc.option_sets.size();
+  }
+  std::printf("trace: %s (%zu scenarios, %llu kernel launches through the stub)\n", bad ? "FAILED" : "ok", scenarios, hip_stub_launches());
+  return bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
+  if (argc > 1 && std::strcmp(argv[1], "trace") == 0) return trace_main();
   const int expect_error = argc > 1 ? std::atoi(argv[1]) : 0;
   int bad = 0;
   bad += drive("nr5g:1:8", "HLMinsumf32", 2048, 2, expect_error);   // layered: lane threads
