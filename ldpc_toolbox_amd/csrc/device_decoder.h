@@ -18,9 +18,11 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <vector>
 
+#include "hip_owned.h"
 #include "implementation.h"
 #include "sparse.h"
 
@@ -134,7 +136,6 @@ class DeviceDecoder {
   int ensure_row_scratch(Workspace &w, size_t bytes);
   // host-pointer entry: pinned staging rings, copy streams, batch-wide device output buffers
   struct HostPipe;
-  HostPipe *pipe_ = nullptr;
   int ensure_pipe(size_t group, size_t out_len, size_t in_elem, bool posterior);
   int stage_in(const char *src, char *dst, size_t bytes);
   int drain_out(char *dst, const char *src, size_t bytes);
@@ -142,11 +143,10 @@ class DeviceDecoder {
   // small-batch (latency) path: lanes across the rows / variables of one codeword, one persistent launch
   // per call (latency.hip.h).  Flooding Minsumf32 only; the other implementations take the batch kernels.
   struct LatencyPath;
-  LatencyPath *lat_ = nullptr;
+  struct SmallBatchCall;  // what both small-batch paths stage alike (latency_paths.hip)
   // the lane-per-edge small-batch path (latency_edge.hip.h): the layered schedule and, for every rule but Minsumf32,
   // the flooding schedule; f32 and f64 arithmetic
   struct EdgeLatencyPath;
-  EdgeLatencyPath *lat_edge_ = nullptr;
   // largest batch that takes it: up to 8 codewords decode one per XCD, larger calls in bundles of up to 8 per XCD that
   // share every phase and barrier; measured against the batched kernels (tools/scalar_probe_layered.py,
   // profiles/r03_latency.txt); the A-Min* rule's serial fold is repeated by every lane of a row: a lower limit
@@ -191,22 +191,10 @@ class DeviceDecoder {
   static constexpr uint32_t kCompactHorizon = 8, kCompactCostLive = 9, kCompactCostSlots = 0, kCompactMinFreedQ = 2;
   std::string error_;
 
-  // graph tables in HBM
-  uint32_t *d_row_ptr_ = nullptr, *d_edge_col_ = nullptr, *d_col_ptr_ = nullptr, *d_col_edge_ = nullptr;
-  // layered schedule: rows grouped into dependency levels (SURVEY.md section 7, hard part 5)
-  uint32_t *d_level_rows_ = nullptr;
-  uint32_t *d_level_recs_ = nullptr;  // row records of the register-resident level kernels (slice_tasks.h, build_level_recs)
-  uint32_t *d_row_recs_ = nullptr;     // flooding: every row's record in row order (cn_reg_kernel)
-  uint32_t *d_serial_recs_ = nullptr;  // the same for the row-serial launch: all rows as one level, one record size
-  // L-free variables (degree <= 2) of the flooding min-sum path: per-edge aux word, the variables
-  // the variable-node kernel still handles ("keep") and the L-free ones ("free"), as compacted CSC
-  uint32_t *d_edge_aux_ = nullptr, *d_keep_var_ = nullptr, *d_keep_ptr_ = nullptr, *d_keep_edge_ = nullptr,
-           *d_free_var_ = nullptr, *d_free_ptr_ = nullptr, *d_free_edge_ = nullptr;
+  // L-free variables (degree <= 2) of the flooding min-sum path (graph_tables.h, LfreeTables)
   uint32_t n_keep_ = 0, n_free_ = 0;
   uint32_t post_rows_keep_ = 0;  // 1 + index of the last variable of degree != 1, 2 (a compaction moves only those posterior rows)
-  // row records of the flooding min-sum path (kernels.hip.h, cn_minsum_rec_kernel): per-edge peer word, the
-  // (row, slot) pairs of the L-free variables' edges, words per record (3, or 4 for rows too long for the packed form)
-  uint32_t *d_edge_peer_ = nullptr, *d_free_rs_ = nullptr, *d_keep_pos_ = nullptr;
+  // row records of the flooding min-sum path (graph_tables.h, RowRecordTables)
   bool opt_rec_long_ = false;  // "rec_long": take the record kernel's long-row variant whatever the graph (A/B)
   bool opt_rec_quiet_ = true;  // "rec_quiet": L-free posteriors are stored only once a slice has a converged codeword
   bool opt_vn_event_ = true;  // "vn_event": the first convergences' L-free posteriors rebuilt inside the variable-node launch (0: a launch of their own)
@@ -216,8 +204,6 @@ class DeviceDecoder {
   uint32_t opt_records_ = 1;
   bool records_wanted() const { return opt_records_ >= 2 || (opt_records_ == 1 && rec_prefers_); }
   uint32_t opt_rec_run_ = 8;
-  static constexpr uint32_t kStreamEvents = 8, kStreamAhead = 4;
-  hipEvent_t stream_events_[kStreamEvents] = {};
   bool opt_compact_ = true;
   // schedule of the compaction checkpoints ("compact_first", "compact_every": 0 = 6 and 2 for flooding, 3 and 1 for the
   // layered schedule)
@@ -236,18 +222,9 @@ class DeviceDecoder {
   std::vector<uint32_t> level_rec_ptr_;  // [n_levels] first word of a level's records in d_level_recs_
   bool lfree_ready_ = false, opt_lfree_ = true;
   std::vector<uint32_t> level_ptr_;
-  // depuncture map: source block of every pattern block, -1 = punctured
-  int32_t *d_src_block_ = nullptr;
-  uint32_t pattern_len_ = 0;
+  uint32_t pattern_len_ = 0;  // blocks of the puncturing pattern (0: none)
 
-  // Two execution lanes (workspace + stream): groups alternate between them, so the idle gaps
-  // between one lane's short launches (layered schedule: one per dependency level) are filled by
-  // the other's, and the host entry's PCIe copies overlap the other lane's decode.
-  Workspace *ws_[2] = {nullptr, nullptr};
-  void *joint_slab_ = nullptr;  // both lanes' workspaces (ensure_lanes)
   size_t joint_stride_ = 0, joint_second_ = 0;  // nominal distance of the lanes; the one the placement probe chose
-  hipStream_t stream_ = nullptr, stream2_ = nullptr;
-  hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr, ev_default_ = nullptr;
   int order_after_default_stream(hipStream_t s);
   uint32_t last_lanes_ = 0;
   size_t last_group_ = 0;
@@ -263,7 +240,6 @@ class DeviceDecoder {
   uint64_t last_pooled_ = 0;
   uint32_t pool_budget_ = 0, pool_budget_max_it_ = 0;  // the budget the last pooled call ended with carries over to the next one at the same limit
   struct StragglerPool;
-  StragglerPool *pool_ = nullptr;
   int ensure_pool(size_t batch, size_t rows, size_t out_len, size_t in_elem, bool posterior, bool own_iterations);
   static uint32_t next_pool_budget(double ok, double sum_its_ok, double stragglers, double straggler_its, double failed_full,
                                    uint32_t max_it);
@@ -282,11 +258,35 @@ class DeviceDecoder {
   bool profiling_ = false;
   struct PendingEvent {
     int kind;
-    hipEvent_t a, b;
+    Event a, b;
   };
-  std::vector<PendingEvent> pending_;
-  std::vector<hipEvent_t> event_pool_;
   KernelStat stats_[kKernelKinds];
+
+  // What the handle owns (hip_owned.h).  Members are destroyed last to first: the streams go after every buffer and
+  // event, and ~DeviceDecoder has made them idle before anything goes.
+  Stream stream_, stream2_;
+  Event ev_fork_, ev_join_, ev_default_;
+  // graph tables in HBM
+  DeviceBuffer d_row_ptr_, d_edge_col_, d_col_ptr_, d_col_edge_;
+  // layered schedule: rows grouped into dependency levels (SURVEY.md section 7, hard part 5)
+  DeviceBuffer d_level_rows_;
+  DeviceBuffer d_level_recs_;   // row records of the register-resident level kernels (slice_tasks.h, build_level_recs)
+  DeviceBuffer d_row_recs_;     // flooding: every row's record in row order (cn_reg_kernel)
+  DeviceBuffer d_serial_recs_;  // the same for the row-serial launch: all rows as one level, one record size
+  DeviceBuffer d_src_block_;    // depuncture map: source block of every pattern block, -1 = punctured
+  DeviceBuffer d_edge_aux_, d_keep_var_, d_keep_ptr_, d_keep_edge_, d_free_var_, d_free_ptr_, d_free_edge_;  // LfreeTables
+  DeviceBuffer d_edge_peer_, d_free_rs_, d_keep_pos_;                                                         // RowRecordTables
+  // Two execution lanes (workspace + stream): groups alternate between them, so the idle gaps
+  // between one lane's short launches (layered schedule: one per dependency level) are filled by
+  // the other's, and the host entry's PCIe copies overlap the other lane's decode.
+  DeviceBuffer joint_slab_;  // both lanes' workspaces (ensure_lanes); a workspace inside it is a view, not an owner
+  std::unique_ptr<Workspace> ws_[2];
+  std::unique_ptr<StragglerPool> pool_;
+  std::unique_ptr<EdgeLatencyPath> lat_edge_;
+  std::unique_ptr<LatencyPath> lat_;
+  std::unique_ptr<HostPipe> pipe_;
+  std::vector<Event> event_pool_;
+  std::vector<PendingEvent> pending_;
 };
 
 }  // namespace ldpc

@@ -55,9 +55,6 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
 
   SparseMatrix::Csr g = h.csr();
   if (g.n_cols == 0) return bail("parity check matrix has no columns");
-  // the row-record kernel fetches a row's first indices as one block: a few entries of slack behind the table
-  constexpr uint32_t kTablePad = 16;
-  g.edge_col.resize(g.edge_col.size() + kTablePad, 0);
   // degenerate rows the reference panics on at decode time are refused here
   for (uint32_t r = 0; r < g.n_rows; r++) {
     const uint32_t d = g.row_ptr[r + 1] - g.row_ptr[r];
@@ -67,7 +64,7 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
       return bail("empty check row: the Aminstar rule is undefined (arithmetic.rs:952)");
   }
 
-  DeviceDecoder *d = new DeviceDecoder();
+  std::unique_ptr<DeviceDecoder> d(new DeviceDecoder());
   d->impl_ = impl;
   d->device_ = device;
   d->n_ = g.n_cols;
@@ -81,162 +78,42 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
   d->opt_vec_ = env_u32("LDPC_TOOLBOX_VEC", 4);
   d->opt_staged_minsum_ = env_u32("LDPC_TOOLBOX_STAGED_MINSUM", 0) != 0;
 
-  auto upload = [&](const std::vector<uint32_t> &v, uint32_t **dst) {
-    const size_t bytes = std::max<size_t>(v.size(), 1) * sizeof(uint32_t);
-    if (hipMalloc(reinterpret_cast<void **>(dst), bytes) != hipSuccess) return false;
-    if (!v.empty() && hipMemcpy(*dst, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice) != hipSuccess)
-      return false;
-    return true;
+  // the tables (graph_tables.h, slice_tasks.h), uploaded in this order
+  auto up = [](const auto &v, DeviceBuffer *dst) {
+    hipError_t e;
+    *dst = upload(v, &e);
+    return e == hipSuccess;
   };
-  bool ok = upload(g.row_ptr, &d->d_row_ptr_) && upload(g.edge_col, &d->d_edge_col_) &&
-            upload(g.col_ptr, &d->d_col_ptr_) && upload(g.col_edge, &d->d_col_edge_);
-
-  if (ok && impl.schedule == Schedule::Flooding && impl.rule == Rule::Minsum && !impl.i8) {
-    // L-free variables: degree 1 or 2 (kernels.hip.h, cn_minsum_lfree_kernel)
-    std::vector<uint32_t> aux(std::max<uint32_t>(g.n_edges, 1), dev::kAuxNone);
-    std::vector<uint32_t> keep_var, keep_ptr{0}, keep_edge, free_var, free_ptr{0}, free_edge;
-    for (uint32_t v = 0; v < g.n_cols; v++) {
-      const uint32_t s0 = g.col_ptr[v], dv = g.col_ptr[v + 1] - s0;
-      const bool is_free = dv == 1 || dv == 2;
-      auto &lv = is_free ? free_var : keep_var;
-      auto &lp = is_free ? free_ptr : keep_ptr;
-      auto &le = is_free ? free_edge : keep_edge;
-      lv.push_back(v);
-      for (uint32_t j = 0; j < dv; j++) le.push_back(g.col_edge[s0 + j]);
-      lp.push_back(static_cast<uint32_t>(le.size()));
-      if (dv == 1) aux[g.col_edge[s0]] = dev::kAuxSingle | dev::kAuxWriter;
-      if (dv == 2) {
-        aux[g.col_edge[s0]] = g.col_edge[s0 + 1] | dev::kAuxWriter;
-        aux[g.col_edge[s0 + 1]] = g.col_edge[s0];
-      }
-    }
-    if (!free_var.empty() && !keep_var.empty() && g.n_edges < dev::kAuxSingle) {
-      d->n_keep_ = static_cast<uint32_t>(keep_var.size());
-      d->n_free_ = static_cast<uint32_t>(free_var.size());
-      d->post_rows_keep_ = keep_var.back() + 1;  // posterior rows up to the last variable the variable-node kernel writes
-      ok = upload(aux, &d->d_edge_aux_) && upload(keep_var, &d->d_keep_var_) && upload(keep_ptr, &d->d_keep_ptr_) &&
-           upload(keep_edge, &d->d_keep_edge_) && upload(free_var, &d->d_free_var_) &&
-           upload(free_ptr, &d->d_free_ptr_) && upload(free_edge, &d->d_free_edge_);
+  g.edge_col.resize(g.edge_col.size() + kTablePad, 0);
+  bool ok = up(g.row_ptr, &d->d_row_ptr_) && up(g.edge_col, &d->d_edge_col_) && up(g.col_ptr, &d->d_col_ptr_) &&
+            up(g.col_edge, &d->d_col_edge_);
+  const bool flooding_minsum = impl.schedule == Schedule::Flooding && impl.rule == Rule::Minsum && !impl.i8;
+  if (ok && flooding_minsum) {
+    const LfreeTables lf = build_lfree_tables(g);
+    if (lf.ready) {
+      d->n_keep_ = lf.n_keep;
+      d->n_free_ = lf.n_free;
+      d->post_rows_keep_ = lf.post_rows_keep;
+      ok = up(lf.aux, &d->d_edge_aux_) && up(lf.keep_var, &d->d_keep_var_) && up(lf.keep_ptr, &d->d_keep_ptr_) &&
+           up(lf.keep_edge, &d->d_keep_edge_) && up(lf.free_var, &d->d_free_var_) && up(lf.free_ptr, &d->d_free_ptr_) &&
+           up(lf.free_edge, &d->d_free_edge_);
       d->lfree_ready_ = ok;
     }
-    // row records (cn_minsum_rec_kernel): where the OTHER message of an L-free variable lives, as (row, slot)
-    const uint32_t rec_bits = impl.f64 ? 64u : 32u, rec_packed = impl.f64 ? 58u : 26u;
-    if (ok && d->lfree_ready_ && g.max_row_weight <= rec_bits && g.n_rows < dev::kPeerSingle) {
-      std::vector<uint32_t> rs(std::max<uint32_t>(g.n_edges, 1));  // edge -> row << 6 | slot
-      for (uint32_t r = 0; r < g.n_rows; r++)
-        for (uint32_t e = g.row_ptr[r]; e < g.row_ptr[r + 1]; e++) rs[e] = (r << 6) | (e - g.row_ptr[r]);
-      // keep edges: where the variable-node kernel reads the message (its compacted list, variable-major)
-      std::vector<uint32_t> peer(std::max<uint32_t>(g.n_edges, 1), dev::kPeerKeep), free_rs(2 * free_var.size(), dev::kAuxNone),
-          keep_pos(keep_edge.size());
-      for (size_t j = 0; j < keep_edge.size(); j++) {
-        peer[keep_edge[j]] = dev::kPeerKeep | static_cast<uint32_t>(j);
-        keep_pos[j] = static_cast<uint32_t>(j);
-      }
-      for (size_t i = 0; i < free_var.size(); i++) {
-        const uint32_t v = free_var[i], s0 = g.col_ptr[v], dv = g.col_ptr[v + 1] - s0;
-        if (dv == 1) {
-          peer[g.col_edge[s0]] = dev::kPeerWriter | (dev::kPeerSingle << 6);
-          free_rs[2 * i] = rs[g.col_edge[s0]];
-        } else {
-          peer[g.col_edge[s0]] = dev::kPeerWriter | rs[g.col_edge[s0 + 1]];
-          peer[g.col_edge[s0 + 1]] = rs[g.col_edge[s0]];
-          free_rs[2 * i] = rs[g.col_edge[s0]];
-          free_rs[2 * i + 1] = rs[g.col_edge[s0 + 1]];
-        }
-      }
-      // the record kernel rebuilds an L-free variable's other message from the peer row's record, which it has at
-      // hand only when the peer is the row before or after (staircase codes; a degree-1 variable has no peer).  Codes
-      // whose degree-2 variables join distant rows (AR4JA: measured 10 % slower with records) keep per-edge messages.
-      size_t far_peers = 0, near_peers = 0;
-      for (size_t i = 0; i < free_var.size(); i++) {
-        const uint32_t v = free_var[i], s0 = g.col_ptr[v];
-        if (g.col_ptr[v + 1] - s0 != 2) continue;
-        const uint32_t ra = rs[g.col_edge[s0]] >> 6, rb = rs[g.col_edge[s0 + 1]] >> 6;
-        ((ra + 1 == rb || rb + 1 == ra) ? near_peers : far_peers) += 1;
-      }
-      d->rec_prefers_ = far_peers * 4 <= near_peers + far_peers;  // at most a quarter of the degree-2 variables join distant rows
-      d->rec_w_ = g.max_row_weight <= rec_packed ? 3u : 4u;
-      peer.resize(peer.size() + kTablePad, dev::kPeerKeep);
-      ok = upload(keep_pos, &d->d_keep_pos_);
-      ok = ok && upload(peer, &d->d_edge_peer_) && upload(free_rs, &d->d_free_rs_);
+    const RowRecordTables rr = d->lfree_ready_ ? build_row_record_tables(g, lf, impl.f64) : RowRecordTables();
+    if (rr.ready) {
+      d->rec_prefers_ = rr.rec_prefers;
+      d->rec_w_ = rr.rec_w;
+      ok = up(rr.keep_pos, &d->d_keep_pos_) && up(rr.peer, &d->d_edge_peer_) && up(rr.free_rs, &d->d_free_rs_);
       d->rec_ready_ = ok;
     }
   }
-
-  if (ok && impl.schedule == Schedule::Flooding && impl.rule == Rule::Minsum && !impl.f64 && !impl.i8 &&
-      g.max_row_weight <= 64 && g.n_rows > 0 && uint64_t(g.max_row_weight) * (g.n_rows + 64) < (1ull << 30) &&
-      uint64_t(g.max_col_weight) * (g.n_cols + 64) < (1ull << 30)) {
-    // small-batch path: rows in the order of their first variable, 64 to a slice, slot-major inside a slice:
-    // edge (position p, slot j) -> id rslice_ptr[p / 64] + j * 64 + p % 64 (messages and `col` share it)
-    auto *lp = new LatencyPath();
-    std::vector<uint32_t> order(g.n_rows), pos_of_row(g.n_rows), edge_row(std::max<uint32_t>(g.n_edges, 1));
-    for (uint32_t r = 0; r < g.n_rows; r++) order[r] = r;
-    auto first_var = [&](uint32_t r) { return g.row_ptr[r] < g.row_ptr[r + 1] ? g.edge_col[g.row_ptr[r]] : 0xFFFFFFFFu; };
-    std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first_var(a) < first_var(b); });
-    const uint32_t n_rs = (g.n_rows + 63) / 64, n_vs = (g.n_cols + 63) / 64;
-    lp->h_rslice_ptr.assign(1, 0);
-    lp->h_rdeg.assign(size_t(n_rs) * 64, 0);
-    for (uint32_t sl = 0; sl < n_rs; sl++) {
-      uint32_t width = 0;
-      for (uint32_t p = sl * 64; p < std::min(g.n_rows, sl * 64 + 64); p++) {
-        const uint32_t r = order[p], dr = g.row_ptr[r + 1] - g.row_ptr[r];
-        pos_of_row[r] = p;
-        lp->h_rdeg[p] = dr;
-        width = std::max(width, dr);
-      }
-      lp->h_rslice_ptr.push_back(lp->h_rslice_ptr.back() + width * 64);
+  if (ok && flooding_minsum && !impl.f64) {
+    SlicedTables st = build_sliced_tables(g);
+    if (st.ready) {
+      d->lat_ = std::make_unique<LatencyPath>();
+      d->lat_->tables = std::move(st);
     }
-    // The variables are renumbered too, in the order of their first appearance when the slots are scanned
-    // slot-major over the row positions: neighbouring lanes (rows) then gather neighbouring words of the
-    // soft values in EVERY slot where the code has structure -- also in DVB-S2's staircase part, whose
-    // natural numbering puts the parity bits of neighbouring positions q words apart (a gather per lane) --
-    // and neighbouring variables read neighbouring messages.  The per-codeword arrays (chan, post, rawhard)
-    // live in this numbering; only ingest and emit translate (perm / inv).
-    lp->h_perm.assign(g.n_cols, 0xFFFFFFFFu);
-    {
-      uint32_t next = 0;
-      for (uint32_t j = 0; j < g.max_row_weight; j++)
-        for (uint32_t p = 0; p < g.n_rows; p++) {
-          const uint32_t r = order[p];
-          if (j < g.row_ptr[r + 1] - g.row_ptr[r]) {
-            const uint32_t v = g.edge_col[g.row_ptr[r] + j];
-            if (lp->h_perm[v] == 0xFFFFFFFFu) lp->h_perm[v] = next++;
-          }
-        }
-      for (uint32_t v = 0; v < g.n_cols; v++)
-        if (lp->h_perm[v] == 0xFFFFFFFFu) lp->h_perm[v] = next++;
-    }
-    lp->h_inv.assign(g.n_cols, 0);
-    for (uint32_t v = 0; v < g.n_cols; v++) lp->h_inv[lp->h_perm[v]] = v;
-    lp->h_col.assign(lp->h_rslice_ptr.back() + 8 * 64, 0);  // + padding: a chunk may read past the last slice
-    auto edge_id = [&](uint32_t r, uint32_t j) { return lp->h_rslice_ptr[pos_of_row[r] / 64] + j * 64 + pos_of_row[r] % 64; };
-    for (uint32_t r = 0; r < g.n_rows; r++)
-      for (uint32_t e = g.row_ptr[r]; e < g.row_ptr[r + 1]; e++) {
-        lp->h_col[edge_id(r, e - g.row_ptr[r])] = lp->h_perm[g.edge_col[e]];
-        edge_row[e] = r;
-      }
-    lp->h_vslice_ptr.assign(1, 0);
-    lp->h_vdeg.assign(size_t(n_vs) * 64, 0);
-    for (uint32_t sl = 0; sl < n_vs; sl++) {
-      uint32_t width = 0;
-      for (uint32_t t = sl * 64; t < std::min(g.n_cols, sl * 64 + 64); t++) {
-        const uint32_t v = lp->h_inv[t];
-        lp->h_vdeg[t] = g.col_ptr[v + 1] - g.col_ptr[v];
-        width = std::max(width, lp->h_vdeg[t]);
-      }
-      lp->h_vslice_ptr.push_back(lp->h_vslice_ptr.back() + width * 64);
-    }
-    lp->h_vedge.assign(lp->h_vslice_ptr.back() + 8 * 64, 0);
-    for (uint32_t t = 0; t < g.n_cols; t++) {
-      const uint32_t v = lp->h_inv[t];
-      for (uint32_t k = g.col_ptr[v]; k < g.col_ptr[v + 1]; k++) {  // cols[v] order: the reference's sum order
-        const uint32_t e = g.col_edge[k], r = edge_row[e];
-        lp->h_vedge[lp->h_vslice_ptr[t / 64] + (k - g.col_ptr[v]) * 64 + t % 64] = edge_id(r, e - g.row_ptr[r]);
-      }
-    }
-    d->lat_ = lp;
   }
-
   if (ok && impl.schedule == Schedule::Flooding && impl.rule == Rule::Tanh && !impl.i8 && d->max_row_weight_ <= kLevelRecShort) {
     // row records of cn_reg_kernel: all rows as one level, in row order
     LevelTables all;
@@ -244,153 +121,53 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
     all.rows.resize(g.n_rows);
     for (uint32_t r = 0; r < g.n_rows; r++) all.rows[r] = r;
     all.maxdeg = {d->max_row_weight_};
-    ok = upload(build_level_recs(all, g.row_ptr, g.edge_col).words, &d->d_row_recs_);
+    ok = up(build_level_recs(all, g.row_ptr, g.edge_col).words, &d->d_row_recs_);
   }
+  LevelTables lt;
   if (ok && impl.schedule == Schedule::Layered) {
-    const LevelTables lt = build_levels(g.row_ptr, g.edge_col, g.n_rows, g.n_cols);
+    lt = build_levels(g.row_ptr, g.edge_col, g.n_rows, g.n_cols);
     d->level_ptr_ = lt.level_ptr;
     d->level_maxdeg_ = lt.maxdeg;
-    ok = upload(lt.rows, &d->d_level_rows_);
-    if (ok) {
-      const LevelRecs lr = build_level_recs(lt, g.row_ptr, g.edge_col);
-      d->level_rec_ptr_ = lr.rec_ptr;
-      ok = upload(lr.words, &d->d_level_recs_);
-      if (ok) {
-        LevelTables all;
-        all.level_ptr = {0u, g.n_rows};
-        all.rows = lt.rows;
-        all.maxdeg = {lt.maxdeg.empty() ? 0u : *std::max_element(lt.maxdeg.begin(), lt.maxdeg.end())};
-        ok = upload(build_level_recs(all, g.row_ptr, g.edge_col).words, &d->d_serial_recs_);
-      }
-    }
+    const LevelRecs lr = build_level_recs(lt, g.row_ptr, g.edge_col);
+    d->level_rec_ptr_ = lr.rec_ptr;
+    LevelTables all;
+    all.level_ptr = {0u, g.n_rows};
+    all.rows = lt.rows;
+    all.maxdeg = {lt.maxdeg.empty() ? 0u : *std::max_element(lt.maxdeg.begin(), lt.maxdeg.end())};
+    ok = up(lt.rows, &d->d_level_rows_) && up(lr.words, &d->d_level_recs_) &&
+         up(build_level_recs(all, g.row_ptr, g.edge_col).words, &d->d_serial_recs_);
   }
-
-  // small-batch path with a lane per edge (latency_edge.hip.h): the rows are packed, whole, into chunks of at most 64
-  // lanes (one wavefront) -- level after level for the layered schedule, all rows in order for flooding, which also
-  // gets the variables' edge lists (cols[v] order) as lane indices.  Flooding Minsumf32 keeps latency.hip.h's kernel.
+  // The lane-per-edge small-batch path (latency_edge.hip.h).  Flooding Minsumf32 keeps latency.hip.h's kernel.
   // (the 8-bit min-sum names take the batched kernels at every batch size: a min-sum row is cheap enough there)
-  if (ok && !impl.fast && !(impl.i8 && impl.rule == Rule::Minsum) && g.max_row_weight <= 64 && g.n_rows > 0 && d->lat_ == nullptr &&
+  if (ok && !impl.fast && !(impl.i8 && impl.rule == Rule::Minsum) && d->lat_ == nullptr &&
       (impl.schedule == Schedule::Flooding || d->level_ptr_.size() <= size_t(opt_serial_levels_default()) + 1)) {
-    auto *lp = new EdgeLatencyPath();
-    lp->layered = impl.schedule == Schedule::Layered;
-    lp->h_level_chunk.assign(1, 0);
-    std::vector<uint32_t> edge_lane(std::max<uint32_t>(g.n_edges, 1), 0);
-    uint32_t fill = 0;  // lanes used in the open chunk
-    auto close = [&]() {
-      if (fill == 0) return;
-      const size_t c0 = lp->h_lane_var.size() - fill;
-      uint32_t dmax = 0;
-      for (size_t k = c0; k < c0 + fill; k++) dmax = std::max(dmax, (lp->h_lane_info[k] >> 8) & 0xFFu);
-      lp->h_lane_var.resize(c0 + 64, dev::kNoLane);
-      lp->h_lane_info.resize(c0 + 64, 0);
-      for (size_t k = c0; k < c0 + 64; k++) lp->h_lane_info[k] |= dmax << 16;
-      fill = 0;
-    };
-    auto add_row = [&](uint32_t r) {
-      const uint32_t e0 = g.row_ptr[r], dr = g.row_ptr[r + 1] - e0;
-      if (dr == 0) return;  // an empty row has no message and an even parity
-      if (fill + dr > 64) close();
-      for (uint32_t i = 0; i < dr; i++) {
-        edge_lane[e0 + i] = static_cast<uint32_t>(lp->h_lane_var.size());
-        lp->h_lane_var.push_back(g.edge_col[e0 + i]);
-        lp->h_lane_info.push_back(i | (dr << 8));
-      }
-      fill += dr;
-    };
-    if (lp->layered) {
-      std::vector<uint32_t> level_rows(g.n_rows);
-      if (hipMemcpy(level_rows.data(), d->d_level_rows_, size_t(g.n_rows) * sizeof(uint32_t), hipMemcpyDeviceToHost) != hipSuccess)
-        ok = false;
-      for (size_t l = 0; ok && l + 1 < d->level_ptr_.size(); l++) {
-        for (uint32_t idx = d->level_ptr_[l]; idx < d->level_ptr_[l + 1]; idx++) add_row(level_rows[idx]);
-        close();
-        lp->h_level_chunk.push_back(static_cast<uint32_t>(lp->h_lane_var.size() / 64));
-      }
-    } else {
-      for (uint32_t r = 0; r < g.n_rows; r++) add_row(r);
-      close();
-      lp->h_level_chunk.push_back(static_cast<uint32_t>(lp->h_lane_var.size() / 64));
-      lp->h_var_ptr.assign(g.col_ptr.begin(), g.col_ptr.end());
-      lp->h_var_lane.resize(std::max<uint32_t>(g.n_edges, 1), 0);
-      for (uint32_t j = 0; j < g.n_edges; j++) lp->h_var_lane[j] = edge_lane[g.col_edge[j]];
+    EdgeLaneTables et = build_edge_lane_tables(g, impl.schedule == Schedule::Layered ? &lt : nullptr);
+    if (et.ready) {
+      d->edge_lanes_ = et.lane_var.size();
+      d->lat_edge_ = std::make_unique<EdgeLatencyPath>();
+      d->lat_edge_->tables = std::move(et);
     }
-    lp->n_chunks = static_cast<uint32_t>(lp->h_lane_var.size() / 64);
-    d->edge_lanes_ = lp->h_lane_var.size();
-    d->lat_edge_ = lp;
   }
-
   if (ok && !puncturing.empty()) {
-    size_t trues = 0;
-    for (uint8_t p : puncturing) trues += p ? 1 : 0;
-    if (trues == 0 || g.n_cols % puncturing.size() != 0) {
-      delete d;
-      return bail("codeword size not divisible by puncturing pattern length");
-    }
-    std::vector<int32_t> src(puncturing.size());
-    int32_t j = 0;
-    for (size_t k = 0; k < puncturing.size(); k++) src[k] = puncturing[k] ? j++ : -1;
+    const DepunctureMap dm = build_depuncture_map(puncturing, g.n_cols);
+    if (!dm.ready) return bail("codeword size not divisible by puncturing pattern length");
     d->pattern_len_ = static_cast<uint32_t>(puncturing.size());
-    d->input_len_ = g.n_cols / puncturing.size() * trues;
-    ok = hipMalloc(reinterpret_cast<void **>(&d->d_src_block_), src.size() * sizeof(int32_t)) == hipSuccess &&
-         hipMemcpy(d->d_src_block_, src.data(), src.size() * sizeof(int32_t), hipMemcpyHostToDevice) == hipSuccess;
+    d->input_len_ = dm.input_len;
+    ok = up(dm.src_block, &d->d_src_block_);
   }
-  if (ok) ok = hipStreamCreateWithFlags(&d->stream_, hipStreamNonBlocking) == hipSuccess;
-  if (ok) ok = hipStreamCreateWithFlags(&d->stream2_, hipStreamNonBlocking) == hipSuccess;
-  if (ok) ok = hipEventCreateWithFlags(&d->ev_fork_, hipEventDisableTiming) == hipSuccess;
-  if (ok) ok = hipEventCreateWithFlags(&d->ev_join_, hipEventDisableTiming) == hipSuccess;
-  if (ok) ok = hipEventCreateWithFlags(&d->ev_default_, hipEventDisableTiming) == hipSuccess;
-  if (!ok) {
-    delete d;
-    return bail("device allocation / upload of the graph tables failed");
-  }
-  d->ws_[0] = new Workspace();
-  d->ws_[1] = new Workspace();
-  return d;
+  ok = ok && d->stream_.create() == hipSuccess && d->stream2_.create() == hipSuccess && d->ev_fork_.create() == hipSuccess &&
+       d->ev_join_.create() == hipSuccess && d->ev_default_.create() == hipSuccess;
+  if (!ok) return bail("device allocation / upload of the graph tables failed");
+  d->ws_[0] = std::make_unique<Workspace>();
+  d->ws_[1] = std::make_unique<Workspace>();
+  return d.release();
 }
 
+// The members free what they own (device_decoder.h: streams last); before that the handle's streams are made idle.
 DeviceDecoder::~DeviceDecoder() {
   (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize(stream_);
   if (stream2_) (void)hipStreamSynchronize(stream2_);
-  for (auto &p : pending_) {
-    (void)hipEventDestroy(p.a);
-    (void)hipEventDestroy(p.b);
-  }
-  for (auto e : event_pool_) (void)hipEventDestroy(e);
-  if (pipe_) {
-    pipe_->release();
-    delete pipe_;
-  }
-  if (lat_) {
-    lat_->release();
-    delete lat_;
-  }
-  if (lat_edge_) {
-    lat_edge_->release();
-    delete lat_edge_;
-  }
-  if (pool_) {
-    pool_->release();
-    delete pool_;
-  }
-  for (Workspace *w : ws_)
-    if (w) {
-      w->release();
-      delete w;
-    }
-  if (joint_slab_) (void)hipFree(joint_slab_);
-  for (void *p : {(void *)d_row_ptr_, (void *)d_edge_col_, (void *)d_col_ptr_, (void *)d_col_edge_,
-                  (void *)d_level_rows_, (void *)d_level_recs_, (void *)d_serial_recs_, (void *)d_row_recs_, (void *)d_src_block_, (void *)d_edge_aux_, (void *)d_keep_var_,
-                  (void *)d_keep_ptr_, (void *)d_keep_edge_, (void *)d_free_var_, (void *)d_free_ptr_,
-                  (void *)d_free_edge_, (void *)d_edge_peer_, (void *)d_free_rs_, (void *)d_keep_pos_})
-    if (p) (void)hipFree(p);
-  for (auto e : stream_events_)
-    if (e) (void)hipEventDestroy(e);
-  if (ev_fork_) (void)hipEventDestroy(ev_fork_);
-  if (ev_join_) (void)hipEventDestroy(ev_join_);
-  if (ev_default_) (void)hipEventDestroy(ev_default_);
-  if (stream_) (void)hipStreamDestroy(stream_);
-  if (stream2_) (void)hipStreamDestroy(stream2_);
 }
 
 // ---- profiling: hipEvents around the bracketed launches, on the launch stream -----------
@@ -463,19 +240,19 @@ void DeviceDecoder::timed_begin(int kind, hipStream_t s) {
   PendingEvent p;
   p.kind = kind;
   auto get = [&]() {
-    hipEvent_t e;
+    Event e;
     if (!event_pool_.empty()) {
-      e = event_pool_.back();
+      e = std::move(event_pool_.back());
       event_pool_.pop_back();
     } else {
-      (void)hipEventCreate(&e);
+      (void)e.create(hipEventDefault);
     }
     return e;
   };
   p.a = get();
   p.b = get();
   (void)hipEventRecord(p.a, s);
-  pending_.push_back(p);
+  pending_.push_back(std::move(p));
 }
 
 void DeviceDecoder::timed_end(int, hipStream_t s) {
@@ -491,8 +268,8 @@ void DeviceDecoder::drain_events() {
       stats_[p.kind].launches++;
       stats_[p.kind].total_ms += ms;
     }
-    event_pool_.push_back(p.a);
-    event_pool_.push_back(p.b);
+    event_pool_.push_back(std::move(p.a));
+    event_pool_.push_back(std::move(p.b));
   }
   pending_.clear();
 }
@@ -559,7 +336,7 @@ int DeviceDecoder::ensure_workspace(Workspace &w, size_t G, void *place, size_t 
   if (!need) {
     if (w.G == G && w.elem == elem && w.chan && w.records == records && (!place || w.slab == place))
       return 0;
-    w.release();
+    w = Workspace();
   }
   const size_t W = G / 64;
   // One slab, carved: the big arrays first, each start 2 MiB-aligned.
@@ -588,7 +365,8 @@ int DeviceDecoder::ensure_workspace(Workspace &w, size_t G, void *place, size_t 
     return 0;
   }
   w.records = records;
-  if (hipHostMalloc(reinterpret_cast<void **>(&w.h_flag), 64, hipHostMallocMapped) == hipSuccess) {
+  if (w.flag.ensure(64, 64, 64, hipHostMallocMapped) == hipSuccess) {
+    w.h_flag = w.flag.get<uint64_t>();
     *w.h_flag = 0;
     if (hipHostGetDevicePointer(reinterpret_cast<void **>(&w.d_flag), w.h_flag, 0) != hipSuccess) w.d_flag = nullptr;
   } else {
@@ -600,7 +378,8 @@ int DeviceDecoder::ensure_workspace(Workspace &w, size_t G, void *place, size_t 
     w.slab = place;
     w.borrowed = true;
   } else {
-    HIP_TRY(hipMalloc(&w.slab, off));
+    HIP_TRY(w.own_slab.ensure(off));
+    w.slab = w.own_slab.get();
   }
   w.slab_bytes = off;
   char *base = static_cast<char *>(w.slab);
@@ -651,11 +430,11 @@ int DeviceDecoder::ensure_lanes(uint32_t lanes, size_t G) {
   auto current = [&](const Workspace &w, const char *at) {
     return w.borrowed && w.slab == at && w.G == G && w.elem == elem && w.records == records;
   };
-  char *base = joint_slab_ ? reinterpret_cast<char *>(round_up(reinterpret_cast<size_t>(joint_slab_), lane_align)) : nullptr;
+  char *base = joint_slab_ ? reinterpret_cast<char *>(round_up(reinterpret_cast<size_t>(joint_slab_.get()), lane_align)) : nullptr;
   if (base && joint_stride_ == stride && current(*ws_[0], base) && current(*ws_[1], base + joint_second_)) return 0;
   release_joint();
-  HIP_TRY(hipMalloc(&joint_slab_, stride + bytes + lane_align));
-  base = reinterpret_cast<char *>(round_up(reinterpret_cast<size_t>(joint_slab_), lane_align));
+  HIP_TRY(joint_slab_.ensure(stride + bytes + lane_align));
+  base = reinterpret_cast<char *>(round_up(reinterpret_cast<size_t>(joint_slab_.get()), lane_align));
   joint_stride_ = stride;
   joint_second_ = stride;
   if (int rc = ensure_workspace(*ws_[0], G, base)) return rc;
@@ -663,10 +442,9 @@ int DeviceDecoder::ensure_lanes(uint32_t lanes, size_t G) {
 }
 
 void DeviceDecoder::release_joint() {
-  for (Workspace *w : ws_)
-    if (w && w->borrowed) w->release();
-  if (joint_slab_) (void)hipFree(joint_slab_);
-  joint_slab_ = nullptr;
+  for (auto &w : ws_)
+    if (w && w->borrowed) *w = Workspace();
+  joint_slab_ = DeviceBuffer();
   joint_stride_ = 0;
   joint_second_ = 0;
 }
@@ -721,26 +499,16 @@ int DeviceDecoder::order_after_default_stream(hipStream_t s) {
 // ---- straggler pooling inside the batch entries (device_decoder.h, "pooling") -------------------------------------------
 
 int DeviceDecoder::ensure_pool(size_t batch, size_t rows, size_t out_len, size_t in_elem, bool posterior, bool own_iterations) {
-  if (!pool_) pool_ = new StragglerPool();
+  if (!pool_) pool_ = std::make_unique<StragglerPool>();
   StragglerPool &p = *pool_;
-  auto grow = [&](void **ptr, size_t *have, size_t need) -> int {
-    if (*have >= need) return 0;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(ptr, std::max<size_t>(need, 256)));
-    *have = need;
-    return 0;
-  };
-  if (int rc = grow(reinterpret_cast<void **>(&p.d_idx), &p.idx_cap, batch * sizeof(uint32_t))) return rc;
-  if (!p.d_stats) HIP_TRY(hipMalloc(reinterpret_cast<void **>(&p.d_stats), 64));
-  if (int rc = grow(&p.d_llrs, &p.llr_bytes, rows * input_len_ * in_elem)) return rc;
-  if (int rc = grow(reinterpret_cast<void **>(&p.d_bits), &p.bits_bytes, rows * std::max<size_t>(out_len, 1))) return rc;
-  if (int rc = grow(reinterpret_cast<void **>(&p.d_its), &p.its_rows, rows * sizeof(int32_t))) return rc;
-  if (posterior)
-    if (int rc = grow(&p.d_post, &p.post_bytes, rows * n_ * in_elem)) return rc;
-  if (own_iterations)
-    if (int rc = grow(reinterpret_cast<void **>(&p.d_its_all), &p.its_all, batch * sizeof(int32_t))) return rc;
+  constexpr size_t kFloor = 256;
+  HIP_TRY(p.d_idx.ensure(batch * sizeof(uint32_t), kFloor));
+  HIP_TRY(p.d_stats.ensure(64));
+  HIP_TRY(p.d_llrs.ensure(rows * input_len_ * in_elem, kFloor));
+  HIP_TRY(p.d_bits.ensure(rows * std::max<size_t>(out_len, 1), kFloor));
+  HIP_TRY(p.d_its.ensure(rows * sizeof(int32_t), kFloor));
+  if (posterior) HIP_TRY(p.d_post.ensure(rows * n_ * in_elem, kFloor));
+  if (own_iterations) HIP_TRY(p.d_its_all.ensure(batch * sizeof(int32_t), kFloor));
   return 0;
 }
 
@@ -777,9 +545,10 @@ int DeviceDecoder::decode_device_pooled(const void *llrs, bool llrs_f64, size_t 
   hipStream_t s = stream ? stream : stream_;
   if (int rc = ensure_pool(batch, chunk, out_len, in_elem, posterior != nullptr, iterations == nullptr)) return rc;
   StragglerPool &p = *pool_;
-  int32_t *its = iterations ? iterations : p.d_its_all;
-  unsigned long long *d_sum = reinterpret_cast<unsigned long long *>(p.d_stats + 4);
-  HIP_TRY(hipMemsetAsync(p.d_stats, 0, 64, s));
+  uint32_t *const d_idx = p.d_idx.get<uint32_t>(), *const d_stats = p.d_stats.get<uint32_t>();
+  int32_t *its = iterations ? iterations : p.d_its_all.get<int32_t>();
+  unsigned long long *d_sum = reinterpret_cast<unsigned long long *>(d_stats + 4);
+  HIP_TRY(hipMemsetAsync(d_stats, 0, 64, s));
   uint32_t budget = (pool_budget_ && pool_budget_max_it_ == max_iterations) ? std::min(pool_budget_, max_iterations) : max_iterations;
   double straggler_its = 0.0;
   uint32_t seen_stragglers = 0;
@@ -790,9 +559,9 @@ int DeviceDecoder::decode_device_pooled(const void *llrs, bool llrs_f64, size_t 
                                      its + b0, posterior ? static_cast<char *>(posterior) + b0 * post_row : nullptr, stream))
       return rc;
     dev::pool_select_kernel<<<static_cast<uint32_t>((nf + 255) / 256), 256, 0, s>>>(
-        its + b0, static_cast<uint32_t>(nf), static_cast<uint32_t>(b0), budget < max_iterations ? 1 : 0, p.d_idx, p.d_stats, d_sum);
+        its + b0, static_cast<uint32_t>(nf), static_cast<uint32_t>(b0), budget < max_iterations ? 1 : 0, d_idx, d_stats, d_sum);
     uint32_t h[6];
-    HIP_TRY(hipMemcpyAsync(h, p.d_stats, sizeof(h), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(h, d_stats, sizeof(h), hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     unsigned long long sum_ok;
     std::memcpy(&sum_ok, &h[4], sizeof(sum_ok));
@@ -808,14 +577,15 @@ int DeviceDecoder::decode_device_pooled(const void *llrs, bool llrs_f64, size_t 
   for (size_t p0 = 0; p0 < seen_stragglers; p0 += chunk) {
     const uint32_t np = static_cast<uint32_t>(std::min<size_t>(chunk, seen_stragglers - p0));
     const uint32_t blocks = (np * 64 + 255) / 256;
-    dev::pool_gather_kernel<<<blocks, 256, 0, s>>>(p.d_idx + p0, np, static_cast<const uint32_t *>(llrs), llr_row / 4,
-                                                   static_cast<uint32_t *>(p.d_llrs));
+    dev::pool_gather_kernel<<<blocks, 256, 0, s>>>(d_idx + p0, np, static_cast<const uint32_t *>(llrs), llr_row / 4,
+                                                   p.d_llrs.get<uint32_t>());
     min_group_ = G;
-    const int rc = decode_device_plain(p.d_llrs, llrs_f64, np, max_iterations, p.d_bits, out_len, p.d_its, posterior ? p.d_post : nullptr, stream);
+    const int rc = decode_device_plain(p.d_llrs.get(), llrs_f64, np, max_iterations, p.d_bits.get<uint8_t>(), out_len, p.d_its.get<int32_t>(),
+                                       posterior ? p.d_post.get() : nullptr, stream);
     min_group_ = keep_min;
     if (rc) return rc;
-    dev::pool_scatter_kernel<<<blocks, 256, 0, s>>>(p.d_idx + p0, np, p.d_bits, static_cast<uint32_t>(out_len), p.d_its,
-                                                    static_cast<const uint32_t *>(p.d_post), posterior ? post_row / 4 : 0, bits,
+    dev::pool_scatter_kernel<<<blocks, 256, 0, s>>>(d_idx + p0, np, p.d_bits.get<uint8_t>(), static_cast<uint32_t>(out_len), p.d_its.get<int32_t>(),
+                                                    p.d_post.get<const uint32_t>(), posterior ? post_row / 4 : 0, bits,
                                                     iterations, static_cast<uint32_t *>(posterior));
   }
   last_pooled_ = seen_stragglers;
@@ -909,24 +679,12 @@ int DeviceDecoder::decode_device_plain(const void *llrs, bool llrs_f64, size_t b
 }
 
 int DeviceDecoder::ensure_row_scratch(Workspace &w, size_t bytes) {
-  if (w.row_scratch_bytes >= bytes) return 0;
-  if (w.row_scratch) (void)hipFree(w.row_scratch);   // (waits for the work that may still use it)
-  w.row_scratch = nullptr;
-  w.row_scratch_bytes = 0;
-  HIP_TRY(hipMalloc(&w.row_scratch, bytes));
-  w.row_scratch_bytes = bytes;
+  HIP_TRY(w.row_scratch.ensure(bytes));  // (freeing the smaller one waits for the work that may still use it)
   return 0;
 }
 
 int DeviceDecoder::ensure_host_staging(Workspace &w, size_t G, size_t in_elem) {
-  const size_t in_bytes = G * input_len_ * in_elem;
-  if (w.in_bytes < in_bytes) {
-    if (w.in) (void)hipFree(w.in);
-    w.in = nullptr;
-    w.in_bytes = 0;
-    HIP_TRY(hipMalloc(&w.in, in_bytes));
-    w.in_bytes = in_bytes;
-  }
+  HIP_TRY(w.in.ensure(G * input_len_ * in_elem));
   return 0;
 }
 
@@ -966,42 +724,25 @@ void par_memcpy(char *dst, const char *src, size_t bytes, unsigned threads) {
 int DeviceDecoder::ensure_pipe(size_t group, size_t out_len, size_t in_elem, bool posterior) {
   if (!pipe_) {
     // built aside and published only when complete: a half-built pipe must never be seen by a later call
-    HostPipe *p = new HostPipe();
+    auto p = std::make_unique<HostPipe>();
     const unsigned hw = std::max(1u, std::thread::hardware_concurrency());
     p->copy_threads = std::min(8u, std::max(1u, hw / 2));
-    bool ok = hipStreamCreateWithFlags(&p->h2d, hipStreamNonBlocking) == hipSuccess &&
-              hipStreamCreateWithFlags(&p->d2h, hipStreamNonBlocking) == hipSuccess;
-    for (int i = 0; ok && i < HostPipe::kSlots; i++)
-      ok = hipEventCreateWithFlags(&p->in_done[i], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&p->out_done[i], hipEventDisableTiming) == hipSuccess;
-    for (int l = 0; ok && l < 2; l++)
-      ok = hipEventCreateWithFlags(&p->in_ready[l], hipEventDisableTiming) == hipSuccess &&
-           hipEventCreateWithFlags(&p->ingested[l], hipEventDisableTiming) == hipSuccess;
+    bool ok = p->h2d.create() == hipSuccess && p->d2h.create() == hipSuccess;
+    for (int i = 0; ok && i < HostPipe::kSlots; i++) ok = p->in_done[i].create() == hipSuccess && p->out_done[i].create() == hipSuccess;
+    for (int l = 0; ok && l < 2; l++) ok = p->in_ready[l].create() == hipSuccess && p->ingested[l].create() == hipSuccess;
     if (!ok) {
-      p->release();
-      delete p;
       fail("host staging: stream / event creation failed");
       return -2;
     }
-    pipe_ = p;
+    pipe_ = std::move(p);
   }
   HostPipe &p = *pipe_;
-  auto grow = [&](void **ptr, size_t *have, size_t want) -> int {
-    if (*have >= want) return 0;
-    if (*ptr) (void)hipFree(*ptr);
-    *ptr = nullptr;
-    *have = 0;
-    HIP_TRY(hipMalloc(ptr, want));
-    *have = want;
-    return 0;
-  };
   // results stay on the device for one group at a time per ring entry (not for the whole batch: a long call
   // with posteriors would not fit), drained while later groups decode
   for (int r = 0; r < HostPipe::kOutRing; r++) {
-    if (int rc = grow(reinterpret_cast<void **>(&p.d_bits[r]), &p.bits_cap[r], std::max<size_t>(group * out_len, 1))) return rc;
-    if (int rc = grow(reinterpret_cast<void **>(&p.d_iters[r]), &p.iters_cap[r], group * sizeof(int32_t))) return rc;
-    if (posterior)
-      if (int rc = grow(&p.d_post[r], &p.post_cap[r], group * n_ * in_elem)) return rc;
+    HIP_TRY(p.d_bits[r].ensure(std::max<size_t>(group * out_len, 1)));
+    HIP_TRY(p.d_iters[r].ensure(group * sizeof(int32_t)));
+    if (posterior) HIP_TRY(p.d_post[r].ensure(group * n_ * in_elem));
   }
   return 0;
 }
@@ -1014,12 +755,12 @@ int DeviceDecoder::stage_in(const char *src, char *dst, size_t bytes) {
     const int slot = p.next_in;
     p.next_in = (p.next_in + 1) % HostPipe::kSlots;
     HIP_TRY(hipEventSynchronize(p.in_done[slot]));  // the DMA that last used this chunk has finished
-    if (HostPipe::pinned(&p.in_slot[slot], &p.in_cap[slot], len)) {
+    if (p.in_slot[slot].ensure(len, HostPipe::kGranule, HostPipe::kChunk) != hipSuccess) {
       fail("host staging: pinned input chunk");
       return -2;
     }
-    par_memcpy(p.in_slot[slot], src + off, len, p.copy_threads);
-    HIP_TRY(hipMemcpyAsync(dst + off, p.in_slot[slot], len, hipMemcpyHostToDevice, p.h2d));
+    par_memcpy(p.in_slot[slot].get<char>(), src + off, len, p.copy_threads);
+    HIP_TRY(hipMemcpyAsync(dst + off, p.in_slot[slot].get(), len, hipMemcpyHostToDevice, p.h2d));
     HIP_TRY(hipEventRecord(p.in_done[slot], p.h2d));
   }
   return 0;
@@ -1033,11 +774,11 @@ int DeviceDecoder::drain_out(char *dst, const char *src, size_t bytes) {
   auto issue = [&](size_t c) -> int {
     const size_t off = c * HostPipe::kChunk, len = std::min(HostPipe::kChunk, bytes - off);
     const int slot = static_cast<int>(c % HostPipe::kSlots);
-    if (HostPipe::pinned(&p.out_slot[slot], &p.out_cap[slot], len)) {
+    if (p.out_slot[slot].ensure(len, HostPipe::kGranule, HostPipe::kChunk) != hipSuccess) {
       fail("host staging: pinned output chunk");
       return -2;
     }
-    HIP_TRY(hipMemcpyAsync(p.out_slot[slot], src + off, len, hipMemcpyDeviceToHost, p.d2h));
+    HIP_TRY(hipMemcpyAsync(p.out_slot[slot].get(), src + off, len, hipMemcpyDeviceToHost, p.d2h));
     HIP_TRY(hipEventRecord(p.out_done[slot], p.d2h));
     return 0;
   };
@@ -1047,7 +788,7 @@ int DeviceDecoder::drain_out(char *dst, const char *src, size_t bytes) {
     const size_t off = c * HostPipe::kChunk, len = std::min(HostPipe::kChunk, bytes - off);
     const int slot = static_cast<int>(c % HostPipe::kSlots);
     HIP_TRY(hipEventSynchronize(p.out_done[slot]));
-    par_memcpy(dst + off, p.out_slot[slot], len, p.copy_threads);
+    par_memcpy(dst + off, p.out_slot[slot].get<char>(), len, p.copy_threads);
     if (c + HostPipe::kSlots < chunks)
       if (int rc = issue(c + HostPipe::kSlots)) return rc;
   }
@@ -1169,9 +910,9 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
   }
   const size_t n_groups = starts.size() - 1;
   while (p.group_done.size() < n_groups) {
-    hipEvent_t e;
-    HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    p.group_done.push_back(e);
+    Event e;
+    HIP_TRY(e.create());
+    p.group_done.push_back(std::move(e));
   }
   hipStream_t streams[2] = {stream_, stream2_};
   const size_t row_in = input_len_ * in_elem;
@@ -1183,11 +924,11 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
     const size_t b0 = starts[gi], nb = starts[gi + 1] - b0, r = gi % R;
     HIP_TRY(hipStreamWaitEvent(p.d2h, p.group_done[gi], 0));
     int drc = 0;
-    if (out_len) drc = drain_out(reinterpret_cast<char *>(bits + b0 * out_len), reinterpret_cast<const char *>(p.d_bits[r]), nb * out_len);
+    if (out_len) drc = drain_out(reinterpret_cast<char *>(bits + b0 * out_len), p.d_bits[r].get<const char>(), nb * out_len);
     if (drc == 0 && iterations)
-      drc = drain_out(reinterpret_cast<char *>(iterations + b0), reinterpret_cast<const char *>(p.d_iters[r]), nb * sizeof(int32_t));
+      drc = drain_out(reinterpret_cast<char *>(iterations + b0), p.d_iters[r].get<const char>(), nb * sizeof(int32_t));
     if (drc == 0 && posterior)
-      drc = drain_out(static_cast<char *>(posterior) + b0 * n_ * in_elem, static_cast<const char *>(p.d_post[r]), nb * n_ * in_elem);
+      drc = drain_out(static_cast<char *>(posterior) + b0 * n_ * in_elem, p.d_post[r].get<const char>(), nb * n_ * in_elem);
     return drc;
   };
   // The layered schedule enqueues dozens of launches per iteration: each lane's launches are enqueued by a thread of its
@@ -1256,7 +997,7 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
       ws_[l]->after_ingest = nullptr;
       ws_[l]->ingest_seq = nullptr;
     }
-    for (hipStream_t st : {p.h2d, streams[0], streams[1], p.d2h}) {
+    for (hipStream_t st : {hipStream_t(p.h2d), streams[0], streams[1], hipStream_t(p.d2h)}) {
       const hipError_t e = hipStreamSynchronize(st);
       if (e != hipSuccess && rc == 0) {
         fail("hipStreamSynchronize", e);
@@ -1296,11 +1037,11 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
       if (threaded) wait_for(lq[lane].ingest_recorded, static_cast<uint32_t>(gi / lanes), lq[lane]);
       if (!hip_ok(hipStreamWaitEvent(p.h2d, p.ingested[lane], 0), "hipStreamWaitEvent")) break;
     }
-    rc = stage_in(static_cast<const char *>(llrs) + b0 * row_in, static_cast<char *>(w.in), nb * row_in);
+    rc = stage_in(static_cast<const char *>(llrs) + b0 * row_in, w.in.get<char>(), nb * row_in);
     if (rc) break;
     if (!hip_ok(hipEventRecord(p.in_ready[lane], p.h2d), "hipEventRecord")) break;
     const size_t r = gi % R;
-    hipEvent_t ingested = p.ingested[lane];
+    const hipEvent_t ingested = p.ingested[lane];
     std::atomic<uint32_t> *ingest_seq = threaded ? &lq[lane].ingest_recorded : nullptr;
     // (the workspace's "record this after the ingest" fields are written by whoever enqueues the lane's launches --
     // the lane's own thread, or this one when there are none -- never by one thread while another reads them)
@@ -1311,8 +1052,8 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
       // a single small group (the reference-style scalar call) may let the host follow the device's progress; so may
       // a lane with an enqueuing thread of its own
       // (flood_pace false: this thread stages copies between its enqueues, it does not wait on a flooding group)
-      const int erc = run_any(w, GroupCall{w.in, llrs_f64, nb, max_iterations, p.d_bits[r], out_len, p.d_iters[r],
-                                           posterior ? p.d_post[r] : nullptr, s, n_groups == 1 || threaded, threaded, false});
+      const int erc = run_any(w, GroupCall{w.in.get(), llrs_f64, nb, max_iterations, p.d_bits[r].get<uint8_t>(), out_len, p.d_iters[r].get<int32_t>(),
+                                           posterior ? p.d_post[r].get() : nullptr, s, n_groups == 1 || threaded, threaded, false});
       if (erc) return erc;
       HIP_TRY(hipEventRecord(p.group_done[gi], s));
       return 0;
@@ -1356,7 +1097,7 @@ int DeviceDecoder::syndrome_device(const uint8_t *bits, size_t batch, uint8_t *s
   if (weight) HIP_TRY(hipMemsetAsync(weight, 0, batch * sizeof(uint32_t), s));
   const uint32_t m = static_cast<uint32_t>(m_);
   dim3 grid(std::max<uint32_t>((m + 255) / 256, 1), static_cast<uint32_t>(batch));
-  dev::syndrome_of_bits_kernel<<<grid, 256, 0, s>>>(d_row_ptr_, d_edge_col_, m, static_cast<uint32_t>(n_),
+  dev::syndrome_of_bits_kernel<<<grid, 256, 0, s>>>(d_row_ptr_.get<uint32_t>(), d_edge_col_.get<uint32_t>(), m, static_cast<uint32_t>(n_),
                                                     static_cast<uint32_t>(batch), bits, syndrome, weight);
   HIP_TRY(hipGetLastError());
   if (own_stream) HIP_TRY(hipStreamSynchronize(s));
@@ -1367,21 +1108,17 @@ int DeviceDecoder::syndrome_host(const uint8_t *bits, size_t batch, uint8_t *syn
   if (batch == 0 || (!syndrome && !weight)) return 0;
   HIP_TRY(hipSetDevice(device_));
   const size_t chunk = 4096;
-  uint8_t *d_bits = nullptr, *d_syn = nullptr;
-  uint32_t *d_w = nullptr;
-  auto release = [&]() {
-    for (void *p : {(void *)d_bits, (void *)d_syn, (void *)d_w})
-      if (p) (void)hipFree(p);
-  };
+  DeviceBuffer bits_buf, syn_buf, w_buf;
   const size_t cap = std::min(batch, chunk);
-  bool ok = hipMalloc(reinterpret_cast<void **>(&d_bits), cap * n_) == hipSuccess;
-  if (ok && syndrome) ok = hipMalloc(reinterpret_cast<void **>(&d_syn), std::max<size_t>(cap * m_, 1)) == hipSuccess;
-  if (ok && weight) ok = hipMalloc(reinterpret_cast<void **>(&d_w), cap * sizeof(uint32_t)) == hipSuccess;
+  bool ok = bits_buf.ensure(cap * n_) == hipSuccess;
+  if (ok && syndrome) ok = syn_buf.ensure(std::max<size_t>(cap * m_, 1)) == hipSuccess;
+  if (ok && weight) ok = w_buf.ensure(cap * sizeof(uint32_t)) == hipSuccess;
   if (!ok) {
-    release();
     fail("syndrome: device staging allocation failed");
     return -2;
   }
+  uint8_t *const d_bits = bits_buf.get<uint8_t>(), *const d_syn = syn_buf.get<uint8_t>();
+  uint32_t *const d_w = w_buf.get<uint32_t>();
   int rc = 0;
   for (size_t b0 = 0; b0 < batch && rc == 0; b0 += chunk) {
     const size_t nb = std::min(chunk, batch - b0);
@@ -1395,7 +1132,6 @@ int DeviceDecoder::syndrome_host(const uint8_t *bits, size_t batch, uint8_t *syn
       rc = -2;
     if (rc == 0 && hipStreamSynchronize(stream_) != hipSuccess) rc = -2;
   }
-  release();
   if (rc == -2 && error_.empty()) fail("syndrome: copy failed");
   return rc;
 }

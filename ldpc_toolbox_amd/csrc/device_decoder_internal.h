@@ -19,6 +19,8 @@
 #include <thread>
 #include <type_traits>
 
+#include "graph_tables.h"
+#include "hip_owned.h"
 #include "kernels.hip.h"
 #include "slice_tasks.h"
 #include "latency.hip.h"
@@ -38,7 +40,8 @@ struct DeviceDecoder::Workspace {
   size_t G = 0;  // codewords per group this workspace is sized for
   size_t elem = 4;
   void *slab = nullptr;  // one allocation; the arrays below are carved from it
-  bool borrowed = false;  // the slab is a part of the decoder's joint allocation for both lanes (ensure_lanes)
+  DeviceBuffer own_slab;  // ... this one, unless
+  bool borrowed = false;  // the slab is a part of the decoder's joint allocation for both lanes (ensure_lanes): a view
   size_t slab_bytes = 0;
   void *chan = nullptr, *post = nullptr, *msg = nullptr, *msg2 = nullptr;
   void *rec[2] = {nullptr, nullptr};  // row records, double-buffered (instead of msg2)
@@ -51,143 +54,67 @@ struct DeviceDecoder::Workspace {
            *slice_state = nullptr;
   int32_t *iters = nullptr;
   // progress word (pinned host memory, mapped into the device): kernels.hip.h, State::publish
+  PinnedBuffer flag;
   uint64_t *h_flag = nullptr, *d_flag = nullptr;
   uint32_t epoch = 0;
   // device-side input staging of decode_host (one group's rows as the caller laid them out)
-  void *in = nullptr;
-  size_t in_bytes = 0;
+  DeviceBuffer in;
   // decode_host: recorded right after the ingest kernel of the group being enqueued (the lane's input buffer is free
   // again), and counted, so that the staging thread knows the record has been made
   hipEvent_t after_ingest = nullptr;
   std::atomic<uint32_t> *ingest_seq = nullptr;
   // check rows too long for the LDS-staged kernels' columns (more than 160 KB per 64 threads): per-wavefront columns in
   // HBM, allocated at the first call that needs them (kernels.hip.h, cn_staged_kernel SCRATCH)
-  void *row_scratch = nullptr;
-  size_t row_scratch_bytes = 0;
-
-  void release() {
-    if (slab && !borrowed) (void)hipFree(slab);
-    if (in) (void)hipFree(in);
-    if (row_scratch) (void)hipFree(row_scratch);
-    if (h_flag) (void)hipHostFree(h_flag);
-    *this = Workspace();
-  }
+  DeviceBuffer row_scratch;
 };
 
 // pinned staging of the host-pointer entry (decode_host, further down)
 struct DeviceDecoder::HostPipe {
   static constexpr size_t kChunk = size_t(32) << 20;
+  static constexpr size_t kGranule = size_t(64) << 10;
   static constexpr int kSlots = 4;
   static constexpr int kOutRing = 4;  // group-sized device output buffers (two per execution lane)
-  // pinned chunks, allocated at first use and only as large as the calls need (a reference-style scalar call
+  Stream h2d, d2h;
+  // pinned chunks (<= kChunk), allocated at first use and only as large as the calls need (a reference-style scalar call
   // pins a few hundred KB, not 8 x 32 MiB)
-  char *in_slot[kSlots] = {}, *out_slot[kSlots] = {};
-  size_t in_cap[kSlots] = {}, out_cap[kSlots] = {};
-  hipEvent_t in_done[kSlots] = {}, out_done[kSlots] = {};
+  PinnedBuffer in_slot[kSlots], out_slot[kSlots];
+  Event in_done[kSlots], out_done[kSlots];
   int next_in = 0;
-  hipStream_t h2d = nullptr, d2h = nullptr;
-  hipEvent_t in_ready[2] = {}, ingested[2] = {};
-  std::vector<hipEvent_t> group_done;
-  uint8_t *d_bits[kOutRing] = {};
-  int32_t *d_iters[kOutRing] = {};
-  void *d_post[kOutRing] = {};
-  size_t bits_cap[kOutRing] = {}, iters_cap[kOutRing] = {}, post_cap[kOutRing] = {};
+  Event in_ready[2], ingested[2];
+  std::vector<Event> group_done;
+  DeviceBuffer d_bits[kOutRing], d_iters[kOutRing], d_post[kOutRing];
   unsigned copy_threads = 1;
+};
 
-  // a pinned chunk of at least `need` bytes (<= kChunk) in *slot
-  static int pinned(char **slot, size_t *cap, size_t need) {
-    if (*cap >= need) return 0;
-    if (*slot) (void)hipHostFree(*slot);
-    *slot = nullptr;
-    *cap = 0;
-    const size_t bytes = std::min(kChunk, (need + (size_t(64) << 10) - 1) >> 16 << 16);
-    if (hipHostMalloc(reinterpret_cast<void **>(slot), bytes, hipHostMallocDefault) != hipSuccess) return -2;
-    *cap = bytes;
-    return 0;
-  }
-  void release() {
-    for (int i = 0; i < kSlots; i++) {
-      if (in_slot[i]) (void)hipHostFree(in_slot[i]);
-      if (out_slot[i]) (void)hipHostFree(out_slot[i]);
-      if (in_done[i]) (void)hipEventDestroy(in_done[i]);
-      if (out_done[i]) (void)hipEventDestroy(out_done[i]);
-    }
-    for (int l = 0; l < 2; l++) {
-      if (in_ready[l]) (void)hipEventDestroy(in_ready[l]);
-      if (ingested[l]) (void)hipEventDestroy(ingested[l]);
-    }
-    for (auto e : group_done) (void)hipEventDestroy(e);
-    if (h2d) (void)hipStreamDestroy(h2d);
-    if (d2h) (void)hipStreamDestroy(d2h);
-    for (int r = 0; r < kOutRing; r++)
-      for (void *p : {(void *)d_bits[r], (void *)d_iters[r], d_post[r]})
-        if (p) (void)hipFree(p);
-  }
+// What the two single-launch small-batch paths stage alike (latency_paths.hip, stage_small_batch): pinned memory the
+// kernel reads and writes itself, sized by the largest call so far -- the caller's input; [error word | bits |
+// iterations | posterior] -- and the size of the persistent launch.
+struct SmallBatchStaging {
+  PinnedBuffer h_in, h_out;
+  uint32_t grid = 0;  // workgroups of the persistent launch (0 = not yet sized from the device's occupancy)
 };
 
 // small-batch path (latency.hip.h): graph tables in the order that path wants, per-XCD codeword state
 struct DeviceDecoder::LatencyPath {
-  // sliced-ELLPACK tables (latency.hip.h), built in create(), uploaded at first use
-  std::vector<uint32_t> h_rslice_ptr, h_rdeg, h_col, h_vslice_ptr, h_vdeg, h_vedge, h_perm, h_inv;
+  SlicedTables tables;  // built in create(), uploaded at first use
   bool uploaded = false;
-  uint32_t *d_rslice_ptr = nullptr, *d_rdeg = nullptr, *d_col = nullptr, *d_vslice_ptr = nullptr, *d_vdeg = nullptr,
-           *d_vedge = nullptr, *d_perm = nullptr, *d_inv = nullptr;
-  dev::LatencyState slots{};  // 8 slots of {chan, post, msg, rawhard} in one allocation
-  dev::LatencySync *d_sync = nullptr;
-  uint32_t grid = 0;  // workgroups of the persistent launch (0 = not yet sized from the device's occupancy)
-  // pinned host memory the kernel reads and writes itself (sized by the largest call so far): the caller's
-  // input; [error word | bits | iterations | posterior]
-  char *h_in = nullptr, *h_out = nullptr;
-  size_t h_in_bytes = 0, h_out_bytes = 0;
-
-  int pinned(char **p, size_t *have, size_t need) {
-    if (*have >= need) return 0;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *have = 0;
-    const size_t bytes = (need + (size_t(1) << 20) - 1) >> 20 << 20;
-    if (hipHostMalloc(reinterpret_cast<void **>(p), bytes, hipHostMallocDefault) != hipSuccess) return -1;
-    *have = bytes;
-    return 0;
-  }
-  void release() {
-    for (void *p : {(void *)d_rslice_ptr, (void *)d_rdeg, (void *)d_col, (void *)d_vslice_ptr, (void *)d_vdeg, (void *)d_vedge,
-                    (void *)d_perm, (void *)d_inv, (void *)slots.base, (void *)d_sync})
-      if (p) (void)hipFree(p);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-  }
+  DeviceBuffer d_rslice_ptr, d_rdeg, d_col, d_vslice_ptr, d_vdeg, d_vedge, d_perm, d_inv;
+  DeviceBuffer slot_mem, sync;
+  dev::LatencyState slots{};  // 8 slots of {chan, post, msg, rawhard} in slot_mem
+  SmallBatchStaging staging;
+  static constexpr size_t kPinnedGranule = size_t(1) << 20;
 };
 
 // small-batch path with the lanes across a codeword's edges (latency_edge.hip.h): the rows packed into wavefront
 // chunks, level after level (layered) or all at once (flooding, plus the variables' edge lists)
 struct DeviceDecoder::EdgeLatencyPath {
-  std::vector<uint32_t> h_level_chunk, h_lane_var, h_lane_info, h_var_ptr, h_var_lane;
-  bool uploaded = false, layered = true;
-  uint32_t *d_level_chunk = nullptr, *d_lane_var = nullptr, *d_lane_info = nullptr, *d_var_ptr = nullptr, *d_var_lane = nullptr;
-  uint32_t n_chunks = 0, grid = 0;
-  dev::EdgeLatState slots{};
-  dev::LatencySync *d_sync = nullptr;
-  char *h_in = nullptr, *h_out = nullptr;  // pinned: the caller's input; [error word | bits | iterations | posterior]
-  size_t h_in_bytes = 0, h_out_bytes = 0;
-
-  static int pinned(char **p, size_t *have, size_t need) {
-    if (*have >= need) return 0;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *have = 0;
-    const size_t bytes = (need + (size_t(1) << 16) - 1) >> 16 << 16;
-    if (hipHostMalloc(reinterpret_cast<void **>(p), bytes, hipHostMallocDefault) != hipSuccess) return -1;
-    *have = bytes;
-    return 0;
-  }
-  void release() {
-    for (void *p : {(void *)d_level_chunk, (void *)d_lane_var, (void *)d_lane_info, (void *)d_var_ptr, (void *)d_var_lane,
-                    (void *)slots.base, (void *)slots.flags, (void *)d_sync})
-      if (p) (void)hipFree(p);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-  }
+  EdgeLaneTables tables;
+  bool uploaded = false;
+  DeviceBuffer d_level_chunk, d_lane_var, d_lane_info, d_var_ptr, d_var_lane;
+  DeviceBuffer slot_mem, flag_mem, sync;
+  dev::EdgeLatState slots{};  // base in slot_mem, flags in flag_mem
+  SmallBatchStaging staging;
+  static constexpr size_t kPinnedGranule = size_t(1) << 16;
 };
 
 #define HIP_TRY(expr)                                  \
@@ -201,17 +128,8 @@ struct DeviceDecoder::EdgeLatencyPath {
 
 // the batch entries' straggler pool (device_decoder.h, "pooling"): device buffers of decode_device_pooled
 struct DeviceDecoder::StragglerPool {
-  uint32_t *d_idx = nullptr, *d_stats = nullptr;  // stats: [converged, failed at the full budget, stragglers] + u64 iterations of the converged
-  size_t idx_cap = 0;
-  void *d_llrs = nullptr, *d_post = nullptr;
-  uint8_t *d_bits = nullptr;
-  int32_t *d_its = nullptr, *d_its_all = nullptr;
-  size_t llr_bytes = 0, post_bytes = 0, bits_bytes = 0, its_rows = 0, its_all = 0;
-  void release() {
-    for (void *p : {(void *)d_idx, (void *)d_stats, d_llrs, d_post, (void *)d_bits, (void *)d_its, (void *)d_its_all})
-      if (p) (void)hipFree(p);
-    *this = StragglerPool();
-  }
+  // stats: [converged, failed at the full budget, stragglers] + u64 iterations of the converged
+  DeviceBuffer d_idx, d_stats, d_llrs, d_post, d_bits, d_its, d_its_all;
 };
 
 // ---- launch helpers ----------------------------------------------------------------------
@@ -390,6 +308,7 @@ struct DeviceDecoder::GroupFrame {
   const GroupCall &c;
   const hipStream_t s;
   const uint32_t G, W, n, m, tile;  // tile: codewords per self-contained sub-batch (kernels.hip.h, tile_base)
+  const uint32_t *const row_ptr = d.d_row_ptr_.get<uint32_t>(), *const edge_col = d.d_edge_col_.get<uint32_t>();
   dev::State st;
   const ProgressPoll poll;
   // syndrome launch: a wavefront takes 64 packed words of a few checks; enough wavefronts to fill the chip
@@ -406,8 +325,8 @@ struct DeviceDecoder::GroupFrame {
              call.pace_lead ? call.pace_lead : (dec.impl_.schedule == Schedule::Layered ? 2u : 8u), call.stream} {}
 
   dev::Graph graph(const uint32_t *edge_aux, const uint32_t *edge_peer) const {
-    return dev::Graph{d.d_row_ptr_, d.d_edge_col_, d.d_col_ptr_, d.d_col_edge_, m, n, static_cast<uint32_t>(d.e_),
-                      nullptr,      nullptr,       nullptr,      0,             edge_aux, edge_peer};
+    return dev::Graph{row_ptr, edge_col, d.d_col_ptr_.get<uint32_t>(), d.d_col_edge_.get<uint32_t>(), m, n, static_cast<uint32_t>(d.e_),
+                      nullptr, nullptr,  nullptr,                      0,                              edge_aux, edge_peer};
   }
   // progress word: the first check-node launch of iteration `it` runs with ticked(it)
   dev::State ticked(uint32_t it) const {
@@ -419,7 +338,7 @@ struct DeviceDecoder::GroupFrame {
   }
   void syndrome_of(const uint64_t *hard, uint32_t *unsat) const {
     if (m == 0) return;
-    grp::syndrome_bits(s, synd_threads, d.d_row_ptr_, d.d_edge_col_, m, hard, unsat, w.n_active, w.n_slots, W, synd_rows);
+    grp::syndrome_bits(s, synd_threads, row_ptr, edge_col, m, hard, unsat, w.n_active, w.n_slots, W, synd_rows);
   }
   void latch(uint32_t *unsat, int32_t it) const { grp::latch(s, w.done, w.iters, unsat, w.n_active, it, G); }
   // the group's first launches: state, ingest (the rule family's kernel for f32 and for f64 input), and the pre-check on
@@ -431,7 +350,7 @@ struct DeviceDecoder::GroupFrame {
     const uint32_t block_size = d.pattern_len_ ? n / d.pattern_len_ : 0;
     auto ingest = [&](auto kernel, auto *src) {
       kernel<<<grid, 256, 0, s>>>(src, d.input_len_, static_cast<uint32_t>(c.nb), n, G, tile, chan, post, w.rawbits,
-                                  d.d_src_block_, block_size);
+                                  d.d_src_block_.get<int32_t>(), block_size);
     };
     if (c.llrs_f64)
       ingest(ingest_f64, static_cast<const double *>(c.llrs));

@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "encoder.h"
+#include "hip_owned.h"
 
 namespace ldpc {
 
@@ -54,28 +55,28 @@ class DeviceEncoder {
  private:
   DeviceEncoder() = default;
   bool fail(const std::string &m, hipError_t e = hipSuccess);
-  int grow(void **ptr, size_t *have, size_t need);
+  int grow(DeviceBuffer &b, size_t need);
   int launch_staircase(const uint8_t *in, uint8_t *cw, size_t batch, hipStream_t s);
   int launch_dense(const uint8_t *in, uint8_t *cw, size_t batch, hipStream_t s);
 
   int device_ = -1;
   size_t k_ = 0, n_ = 0, m_ = 0, out_len_ = 0;
   bool staircase_ = false;
-  // staircase: H0 in CSR form
-  uint32_t *d_h0_ptr_ = nullptr, *d_h0_idx_ = nullptr;
-  // dense: G0 transposed, [words][m rounded up to 64] 64-bit words (a wave reads 64 rows of one word column at once)
-  uint64_t *d_gen_t_ = nullptr;
   size_t words_ = 0, m_pad_ = 0;
-  // puncturing: kept block j of the output is block d_keep_[j] of the codeword
-  uint32_t *d_keep_ = nullptr;
   uint32_t kept_ = 0, block_ = 0;
+  std::string error_;
+  // what the handle owns (hip_owned.h): the stream is declared first and so destroyed last
+  Stream stream_;
+  Event ev_default_;
+  // staircase: H0 in CSR form
+  DeviceBuffer d_h0_ptr_, d_h0_idx_;
+  // dense: G0 transposed, [words][m rounded up to 64] 64-bit words (a wave reads 64 rows of one word column at once)
+  DeviceBuffer d_gen_t_;
+  // puncturing: kept block j of the output is block d_keep_[j] of the codeword
+  DeviceBuffer d_keep_;
   // work buffers, grown on demand: bit-packed messages, row-sum prefixes + slice totals, full codewords before
   // puncturing, and the staging buffers of the host entry
-  void *d_packed_ = nullptr, *d_prefix_ = nullptr, *d_cw_ = nullptr, *d_in_ = nullptr, *d_out_ = nullptr;
-  size_t packed_bytes_ = 0, prefix_bytes_ = 0, cw_bytes_ = 0, in_bytes_ = 0, out_bytes_ = 0;
-  hipStream_t stream_ = nullptr;
-  hipEvent_t ev_default_ = nullptr;
-  std::string error_;
+  DeviceBuffer d_packed_, d_prefix_, d_cw_, d_in_, d_out_;
 };
 
 }  // namespace ldpc

@@ -51,14 +51,14 @@ DeviceEncoder *DeviceEncoder::create(const Encoder &enc, const std::vector<uint8
   d->m_ = m;
   d->out_len_ = n;
   d->staircase_ = enc.staircase();
-  auto upload = [](void **dst, const void *src, size_t bytes) {
-    return hipMalloc(dst, std::max<size_t>(bytes, 256)) == hipSuccess &&
-           (bytes == 0 || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess);
+  auto up = [](const auto &v, DeviceBuffer *dst) {
+    hipError_t e;
+    *dst = upload(v, &e, 256);
+    return e == hipSuccess;
   };
   bool ok = true;
   if (d->staircase_) {
-    ok = upload(reinterpret_cast<void **>(&d->d_h0_ptr_), enc.h0_ptr().data(), enc.h0_ptr().size() * sizeof(uint32_t)) &&
-         upload(reinterpret_cast<void **>(&d->d_h0_idx_), enc.h0_idx().data(), enc.h0_idx().size() * sizeof(uint32_t));
+    ok = up(enc.h0_ptr(), &d->d_h0_ptr_) && up(enc.h0_idx(), &d->d_h0_idx_);
   } else {
     // G0 transposed: [word][row], rows padded with zeros to a multiple of 64
     d->words_ = enc.words();
@@ -67,7 +67,7 @@ DeviceEncoder *DeviceEncoder::create(const Encoder &enc, const std::vector<uint8
     const std::vector<uint64_t> &gen = enc.gen();
     for (size_t r = 0; r < m; r++)
       for (size_t w = 0; w < d->words_; w++) gt[w * d->m_pad_ + r] = gen[r * d->words_ + w];
-    ok = upload(reinterpret_cast<void **>(&d->d_gen_t_), gt.data(), gt.size() * sizeof(uint64_t));
+    ok = up(gt, &d->d_gen_t_);
   }
   if (ok && !pattern.empty()) {
     std::vector<uint32_t> keep;
@@ -76,30 +76,21 @@ DeviceEncoder *DeviceEncoder::create(const Encoder &enc, const std::vector<uint8
     d->block_ = static_cast<uint32_t>(n / pattern.size());
     d->kept_ = static_cast<uint32_t>(keep.size());
     d->out_len_ = size_t(d->block_) * d->kept_;
-    ok = upload(reinterpret_cast<void **>(&d->d_keep_), keep.data(), keep.size() * sizeof(uint32_t));
+    ok = up(keep, &d->d_keep_);
   }
-  if (ok) ok = hipStreamCreateWithFlags(&d->stream_, hipStreamNonBlocking) == hipSuccess;
-  if (ok) ok = hipEventCreateWithFlags(&d->ev_default_, hipEventDisableTiming) == hipSuccess;
+  ok = ok && d->stream_.create() == hipSuccess && d->ev_default_.create() == hipSuccess;
   if (!ok) return bail("device allocation / upload of the encoder tables failed");
   return d.release();
 }
 
+// (the members free what they own, the stream last)
 DeviceEncoder::~DeviceEncoder() {
   (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize(stream_);
-  for (void *p : {(void *)d_h0_ptr_, (void *)d_h0_idx_, (void *)d_gen_t_, (void *)d_keep_, d_packed_, d_prefix_, d_cw_, d_in_, d_out_})
-    if (p) (void)hipFree(p);
-  if (ev_default_) (void)hipEventDestroy(ev_default_);
-  if (stream_) (void)hipStreamDestroy(stream_);
 }
 
-int DeviceEncoder::grow(void **ptr, size_t *have, size_t need) {
-  if (*have >= need) return 0;
-  if (*ptr) (void)hipFree(*ptr);
-  *ptr = nullptr;
-  *have = 0;
-  ENC_TRY(hipMalloc(ptr, std::max<size_t>(need, 256)));
-  *have = need;
+int DeviceEncoder::grow(DeviceBuffer &b, size_t need) {
+  ENC_TRY(b.ensure(need, 256));
   return 0;
 }
 
@@ -140,18 +131,19 @@ int DeviceEncoder::launch_staircase(const uint8_t *in, uint8_t *cw, size_t batch
   const int form = staircase_form(k_);
   const size_t word = form == 1 ? 2 : 4, frames_per_group = 8 * word;
   const size_t pass = std::min(batch, kEncPassFrames), groups = (pass + frames_per_group - 1) / frames_per_group;
-  if (int rc = grow(&d_packed_, &packed_bytes_, groups * kp * word + 16)) return rc;
-  if (int rc = grow(&d_prefix_, &prefix_bytes_, groups * (m_ + 8) * word)) return rc;
+  if (int rc = grow(d_packed_, groups * kp * word + 16)) return rc;
+  if (int rc = grow(d_prefix_, groups * (m_ + 8) * word)) return rc;
+  const uint32_t *const h0_ptr = d_h0_ptr_.get<uint32_t>(), *const h0_idx = d_h0_idx_.get<uint32_t>();
   for (size_t b0 = 0; b0 < batch; b0 += pass) {
     const uint32_t nb = static_cast<uint32_t>(std::min(pass, batch - b0));
     const uint8_t *pin = in + b0 * k_;
     uint8_t *pcw = cw + b0 * n_;
     if (form == 0)
-      enc_staircase_pass<uint32_t, true>(pin, pcw, nb, k, n, kp, d_packed_, d_prefix_, d_h0_ptr_, d_h0_idx_, s);
+      enc_staircase_pass<uint32_t, true>(pin, pcw, nb, k, n, kp, d_packed_.get(), d_prefix_.get(), h0_ptr, h0_idx, s);
     else if (form == 1)
-      enc_staircase_pass<uint16_t, true>(pin, pcw, nb, k, n, kp, d_packed_, d_prefix_, d_h0_ptr_, d_h0_idx_, s);
+      enc_staircase_pass<uint16_t, true>(pin, pcw, nb, k, n, kp, d_packed_.get(), d_prefix_.get(), h0_ptr, h0_idx, s);
     else
-      enc_staircase_pass<uint32_t, false>(pin, pcw, nb, k, n, kp, d_packed_, d_prefix_, d_h0_ptr_, d_h0_idx_, s);
+      enc_staircase_pass<uint32_t, false>(pin, pcw, nb, k, n, kp, d_packed_.get(), d_prefix_.get(), h0_ptr, h0_idx, s);
   }
   return 0;
 }
@@ -161,16 +153,16 @@ int DeviceEncoder::launch_dense(const uint8_t *in, uint8_t *cw, size_t batch, hi
   const uint32_t words = static_cast<uint32_t>(words_), m_pad = static_cast<uint32_t>(m_pad_);
   // passes of at most 2^20 frames (the frame index is a 32-bit grid dimension)
   const size_t pass = std::min<size_t>(batch, size_t(1) << 20), bpad = (pass + 63) / 64 * 64;
-  if (int rc = grow(&d_packed_, &packed_bytes_, std::max<size_t>(words, 1) * bpad * sizeof(uint64_t))) return rc;
+  if (int rc = grow(d_packed_, std::max<size_t>(words, 1) * bpad * sizeof(uint64_t))) return rc;
   for (size_t b0 = 0; b0 < batch; b0 += pass) {
     const uint32_t nb = static_cast<uint32_t>(std::min(pass, batch - b0)), nbpad = (nb + 63) / 64 * 64;
     const uint8_t *pin = in + b0 * k_;
     uint8_t *pcw = cw + b0 * n_;
-    uint64_t *pk = static_cast<uint64_t *>(d_packed_);
+    uint64_t *pk = d_packed_.get<uint64_t>();
     if (words > 0)
       enc::pack_words_kernel<<<dim3(nbpad, (words + 3) / 4), 256, 0, s>>>(pin, pcw, pk, k, n, words, nb, nbpad);
     if (m > 0)
-      enc::dense_parity_kernel<<<dim3(nbpad / 64, m_pad / 64), 256, 0, s>>>(d_gen_t_, pk, pcw, k, n, m, m_pad, words, nb, nbpad);
+      enc::dense_parity_kernel<<<dim3(nbpad / 64, m_pad / 64), 256, 0, s>>>(d_gen_t_.get<uint64_t>(), pk, pcw, k, n, m, m_pad, words, nb, nbpad);
   }
   return 0;
 }
@@ -181,8 +173,8 @@ int DeviceEncoder::encode_device(const uint8_t *input, uint8_t *output, size_t b
   hipStream_t s = stream ? stream : stream_;
   uint8_t *cw = output;
   if (d_keep_) {  // the full codewords go to a buffer of the handle, the kept blocks from there to the output
-    if (int rc = grow(&d_cw_, &cw_bytes_, batch * n_)) return rc;
-    cw = static_cast<uint8_t *>(d_cw_);
+    if (int rc = grow(d_cw_, batch * n_)) return rc;
+    cw = d_cw_.get<uint8_t>();
   }
   if (!stream) {
     // (the handle's stream is non-blocking: ordered explicitly after what the legacy default stream holds now)
@@ -194,7 +186,7 @@ int DeviceEncoder::encode_device(const uint8_t *input, uint8_t *output, size_t b
     const uint64_t total = uint64_t(batch) * out_len_;
     const uint32_t blocks = static_cast<uint32_t>(std::min<uint64_t>((total + 255) / 256, 256 * 32));
     if (total > 0)
-      enc::puncture_kernel<<<blocks, 256, 0, s>>>(cw, output, d_keep_, static_cast<uint32_t>(n_), block_, kept_, total);
+      enc::puncture_kernel<<<blocks, 256, 0, s>>>(cw, output, d_keep_.get<uint32_t>(), static_cast<uint32_t>(n_), block_, kept_, total);
   }
   ENC_TRY(hipGetLastError());
   if (!stream) ENC_TRY(hipStreamSynchronize(s));
@@ -204,12 +196,12 @@ int DeviceEncoder::encode_device(const uint8_t *input, uint8_t *output, size_t b
 int DeviceEncoder::encode_host(const uint8_t *input, uint8_t *output, size_t batch) {
   if (batch == 0) return 0;
   ENC_TRY(hipSetDevice(device_));
-  if (int rc = grow(&d_in_, &in_bytes_, batch * k_)) return rc;
-  if (int rc = grow(&d_out_, &out_bytes_, batch * out_len_)) return rc;
-  if (k_ > 0) ENC_TRY(hipMemcpyAsync(d_in_, input, batch * k_, hipMemcpyHostToDevice, stream_));
-  if (int rc = encode_device(static_cast<const uint8_t *>(d_in_), static_cast<uint8_t *>(d_out_), batch, stream_)) return rc;
+  if (int rc = grow(d_in_, batch * k_)) return rc;
+  if (int rc = grow(d_out_, batch * out_len_)) return rc;
+  if (k_ > 0) ENC_TRY(hipMemcpyAsync(d_in_.get(), input, batch * k_, hipMemcpyHostToDevice, stream_));
+  if (int rc = encode_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), batch, stream_)) return rc;
   // (the only write to the caller's buffer: after an earlier failure nothing has been written)
-  if (out_len_ > 0) ENC_TRY(hipMemcpyAsync(output, d_out_, batch * out_len_, hipMemcpyDeviceToHost, stream_));
+  if (out_len_ > 0) ENC_TRY(hipMemcpyAsync(output, d_out_.get(), batch * out_len_, hipMemcpyDeviceToHost, stream_));
   ENC_TRY(hipStreamSynchronize(stream_));
   return 0;
 }

@@ -1,0 +1,270 @@
+// Host-side graph tables of the decoder, as pure functions of the parity check matrix's CSR form: what
+// DeviceDecoder::create uploads (and the small-batch paths at their first call).  No HIP here: tests/graph_tables_driver.cpp
+// checks these tables on the CPU.  The layered schedule's levels and row records are in slice_tasks.h.
+#pragma once
+#include <algorithm>
+#include <cstdint>
+#include <vector>
+
+#include "slice_tasks.h"
+#include "sparse.h"
+
+namespace ldpc {
+
+namespace dev {
+// edge_aux[e]: kAuxNone, or for an edge whose variable is L-free: the edge id of the variable's other edge (kAuxSingle for
+// degree 1), with kAuxWriter set on the variable's first slot (kernels_common.hip.h, Graph)
+enum : uint32_t { kAuxNone = 0xFFFFFFFFu, kAuxWriter = 0x80000000u, kAuxSingle = 0x7FFFFFFEu, kAuxMask = 0x7FFFFFFFu };
+// edge_peer[e]: see kernels_flooding.hip.h, cn_minsum_rec_kernel
+enum : uint32_t { kPeerKeep = 0x80000000u, kPeerPosMask = 0x7FFFFFFFu, kPeerWriter = 0x40000000u, kPeerRowMask = 0xFFFFFFu,
+                  kPeerSingle = 0xFFFFFFu };
+// lane_var of a padding lane (latency_edge.hip.h)
+enum : uint32_t { kNoLane = 0xFFFFFFFFu };
+}  // namespace dev
+
+// the row-record kernel fetches a row's first indices as one block: a few entries of slack behind edge_col and peer
+constexpr uint32_t kTablePad = 16;
+
+// L-free variables (degree 1 or 2) of the flooding min-sum path (kernels_flooding.hip.h, cn_minsum_lfree_kernel): the
+// per-edge aux word, and the variables the variable-node kernel still handles ("keep") and the L-free ones ("free") as
+// compacted CSC.  ready: the graph has both kinds and its edge ids fit the aux word.
+struct LfreeTables {
+  bool ready = false;
+  std::vector<uint32_t> aux, keep_var, keep_ptr{0}, keep_edge, free_var, free_ptr{0}, free_edge;
+  uint32_t n_keep = 0, n_free = 0;
+  uint32_t post_rows_keep = 0;  // posterior rows up to the last variable the variable-node kernel writes
+};
+inline LfreeTables build_lfree_tables(const SparseMatrix::Csr &g) {
+  LfreeTables t;
+  t.aux.assign(std::max<uint32_t>(g.n_edges, 1), dev::kAuxNone);
+  for (uint32_t v = 0; v < g.n_cols; v++) {
+    const uint32_t s0 = g.col_ptr[v], dv = g.col_ptr[v + 1] - s0;
+    const bool is_free = dv == 1 || dv == 2;
+    auto &lv = is_free ? t.free_var : t.keep_var;
+    auto &lp = is_free ? t.free_ptr : t.keep_ptr;
+    auto &le = is_free ? t.free_edge : t.keep_edge;
+    lv.push_back(v);
+    for (uint32_t j = 0; j < dv; j++) le.push_back(g.col_edge[s0 + j]);
+    lp.push_back(static_cast<uint32_t>(le.size()));
+    if (dv == 1) t.aux[g.col_edge[s0]] = dev::kAuxSingle | dev::kAuxWriter;
+    if (dv == 2) {
+      t.aux[g.col_edge[s0]] = g.col_edge[s0 + 1] | dev::kAuxWriter;
+      t.aux[g.col_edge[s0 + 1]] = g.col_edge[s0];
+    }
+  }
+  if (!t.free_var.empty() && !t.keep_var.empty() && g.n_edges < dev::kAuxSingle) {
+    t.ready = true;
+    t.n_keep = static_cast<uint32_t>(t.keep_var.size());
+    t.n_free = static_cast<uint32_t>(t.free_var.size());
+    t.post_rows_keep = t.keep_var.back() + 1;
+  }
+  return t;
+}
+
+// Row records (cn_minsum_rec_kernel): where the OTHER message of an L-free variable lives, as (row, slot).
+// ready: every row fits a record's sign mask (32 / 64 bits) and the row index fits the peer word.
+struct RowRecordTables {
+  bool ready = false;
+  std::vector<uint32_t> peer, free_rs, keep_pos;
+  uint32_t rec_w = 0;        // words per record: 3, or 4 for rows too long for the packed form
+  bool rec_prefers = false;  // at most a quarter of the degree-2 variables join distant rows
+};
+inline RowRecordTables build_row_record_tables(const SparseMatrix::Csr &g, const LfreeTables &lf, bool f64) {
+  RowRecordTables t;
+  const uint32_t rec_bits = f64 ? 64u : 32u, rec_packed = f64 ? 58u : 26u;
+  if (!lf.ready || g.max_row_weight > rec_bits || g.n_rows >= dev::kPeerSingle) return t;
+  std::vector<uint32_t> rs(std::max<uint32_t>(g.n_edges, 1));  // edge -> row << 6 | slot
+  for (uint32_t r = 0; r < g.n_rows; r++)
+    for (uint32_t e = g.row_ptr[r]; e < g.row_ptr[r + 1]; e++) rs[e] = (r << 6) | (e - g.row_ptr[r]);
+  // keep edges: where the variable-node kernel reads the message (its compacted list, variable-major)
+  t.peer.assign(std::max<uint32_t>(g.n_edges, 1), dev::kPeerKeep);
+  t.free_rs.assign(2 * lf.free_var.size(), dev::kAuxNone);
+  t.keep_pos.resize(lf.keep_edge.size());
+  for (size_t j = 0; j < lf.keep_edge.size(); j++) {
+    t.peer[lf.keep_edge[j]] = dev::kPeerKeep | static_cast<uint32_t>(j);
+    t.keep_pos[j] = static_cast<uint32_t>(j);
+  }
+  // The record kernel rebuilds an L-free variable's other message from the peer row's record, which it has at hand only
+  // when the peer is the row before or after (staircase codes; a degree-1 variable has no peer).  Codes whose degree-2
+  // variables join distant rows (AR4JA: measured 10 % slower with records) keep per-edge messages.
+  size_t far_peers = 0, near_peers = 0;
+  for (size_t i = 0; i < lf.free_var.size(); i++) {
+    const uint32_t v = lf.free_var[i], s0 = g.col_ptr[v], dv = g.col_ptr[v + 1] - s0;
+    const uint32_t ea = g.col_edge[s0];
+    t.free_rs[2 * i] = rs[ea];
+    if (dv == 1) {
+      t.peer[ea] = dev::kPeerWriter | (dev::kPeerSingle << 6);
+      continue;
+    }
+    const uint32_t eb = g.col_edge[s0 + 1];
+    t.peer[ea] = dev::kPeerWriter | rs[eb];
+    t.peer[eb] = rs[ea];
+    t.free_rs[2 * i + 1] = rs[eb];
+    const uint32_t ra = rs[ea] >> 6, rb = rs[eb] >> 6;
+    ((ra + 1 == rb || rb + 1 == ra) ? near_peers : far_peers) += 1;
+  }
+  t.rec_prefers = far_peers * 4 <= near_peers + far_peers;
+  t.rec_w = g.max_row_weight <= rec_packed ? 3u : 4u;
+  t.peer.resize(t.peer.size() + kTablePad, dev::kPeerKeep);
+  t.ready = true;
+  return t;
+}
+
+// Sliced-ELLPACK tables of the small-batch path (latency.hip.h): rows in the order of their first variable, 64 to a slice,
+// slot-major inside a slice: edge (position p, slot j) -> id rslice_ptr[p / 64] + j * 64 + p % 64 (messages and `col`
+// share it).  ready: rows of at most 64 edges, at least one row, and edge ids within 2^30.
+struct SlicedTables {
+  bool ready = false;
+  std::vector<uint32_t> rslice_ptr, rdeg, col, vslice_ptr, vdeg, vedge, perm, inv;
+};
+inline SlicedTables build_sliced_tables(const SparseMatrix::Csr &g) {
+  SlicedTables t;
+  if (g.max_row_weight > 64 || g.n_rows == 0 || uint64_t(g.max_row_weight) * (g.n_rows + 64) >= (1ull << 30) ||
+      uint64_t(g.max_col_weight) * (g.n_cols + 64) >= (1ull << 30))
+    return t;
+  std::vector<uint32_t> order(g.n_rows), pos_of_row(g.n_rows), edge_row(std::max<uint32_t>(g.n_edges, 1));
+  for (uint32_t r = 0; r < g.n_rows; r++) order[r] = r;
+  auto first_var = [&](uint32_t r) { return g.row_ptr[r] < g.row_ptr[r + 1] ? g.edge_col[g.row_ptr[r]] : 0xFFFFFFFFu; };
+  std::stable_sort(order.begin(), order.end(), [&](uint32_t a, uint32_t b) { return first_var(a) < first_var(b); });
+  const uint32_t n_rs = (g.n_rows + 63) / 64, n_vs = (g.n_cols + 63) / 64;
+  t.rslice_ptr.assign(1, 0);
+  t.rdeg.assign(size_t(n_rs) * 64, 0);
+  for (uint32_t sl = 0; sl < n_rs; sl++) {
+    uint32_t width = 0;
+    for (uint32_t p = sl * 64; p < std::min(g.n_rows, sl * 64 + 64); p++) {
+      const uint32_t r = order[p], dr = g.row_ptr[r + 1] - g.row_ptr[r];
+      pos_of_row[r] = p;
+      t.rdeg[p] = dr;
+      width = std::max(width, dr);
+    }
+    t.rslice_ptr.push_back(t.rslice_ptr.back() + width * 64);
+  }
+  // The variables are renumbered too, in the order of their first appearance when the slots are scanned
+  // slot-major over the row positions: neighbouring lanes (rows) then gather neighbouring words of the
+  // soft values in EVERY slot where the code has structure -- also in DVB-S2's staircase part, whose
+  // natural numbering puts the parity bits of neighbouring positions q words apart (a gather per lane) --
+  // and neighbouring variables read neighbouring messages.  The per-codeword arrays (chan, post, rawhard)
+  // live in this numbering; only ingest and emit translate (perm / inv).
+  t.perm.assign(g.n_cols, 0xFFFFFFFFu);
+  uint32_t next = 0;
+  for (uint32_t j = 0; j < g.max_row_weight; j++)
+    for (uint32_t p = 0; p < g.n_rows; p++) {
+      const uint32_t r = order[p];
+      if (j < g.row_ptr[r + 1] - g.row_ptr[r]) {
+        const uint32_t v = g.edge_col[g.row_ptr[r] + j];
+        if (t.perm[v] == 0xFFFFFFFFu) t.perm[v] = next++;
+      }
+    }
+  for (uint32_t v = 0; v < g.n_cols; v++)
+    if (t.perm[v] == 0xFFFFFFFFu) t.perm[v] = next++;
+  t.inv.assign(g.n_cols, 0);
+  for (uint32_t v = 0; v < g.n_cols; v++) t.inv[t.perm[v]] = v;
+  t.col.assign(t.rslice_ptr.back() + 8 * 64, 0);  // + padding: a chunk may read past the last slice
+  auto edge_id = [&](uint32_t r, uint32_t j) { return t.rslice_ptr[pos_of_row[r] / 64] + j * 64 + pos_of_row[r] % 64; };
+  for (uint32_t r = 0; r < g.n_rows; r++)
+    for (uint32_t e = g.row_ptr[r]; e < g.row_ptr[r + 1]; e++) {
+      t.col[edge_id(r, e - g.row_ptr[r])] = t.perm[g.edge_col[e]];
+      edge_row[e] = r;
+    }
+  t.vslice_ptr.assign(1, 0);
+  t.vdeg.assign(size_t(n_vs) * 64, 0);
+  for (uint32_t sl = 0; sl < n_vs; sl++) {
+    uint32_t width = 0;
+    for (uint32_t k = sl * 64; k < std::min(g.n_cols, sl * 64 + 64); k++) {
+      const uint32_t v = t.inv[k];
+      t.vdeg[k] = g.col_ptr[v + 1] - g.col_ptr[v];
+      width = std::max(width, t.vdeg[k]);
+    }
+    t.vslice_ptr.push_back(t.vslice_ptr.back() + width * 64);
+  }
+  t.vedge.assign(t.vslice_ptr.back() + 8 * 64, 0);
+  for (uint32_t k = 0; k < g.n_cols; k++) {
+    const uint32_t v = t.inv[k];
+    for (uint32_t c = g.col_ptr[v]; c < g.col_ptr[v + 1]; c++) {  // cols[v] order: the reference's sum order
+      const uint32_t e = g.col_edge[c], r = edge_row[e];
+      t.vedge[t.vslice_ptr[k / 64] + (c - g.col_ptr[v]) * 64 + k % 64] = edge_id(r, e - g.row_ptr[r]);
+    }
+  }
+  t.ready = true;
+  return t;
+}
+
+// Lane packing of the lane-per-edge small-batch path (latency_edge.hip.h): the rows are packed, whole, into chunks of at
+// most 64 lanes (one wavefront) -- level after level for the layered schedule (levels != nullptr), all rows in order for
+// flooding, which also gets the variables' edge lists (cols[v] order) as lane indices.
+// lane_info: slot | degree << 8 | the chunk's largest degree << 16.  ready: rows of at most 64 edges, at least one row.
+struct EdgeLaneTables {
+  bool ready = false, layered = true;
+  std::vector<uint32_t> level_chunk, lane_var, lane_info, var_ptr, var_lane;
+  uint32_t n_chunks = 0;
+};
+inline EdgeLaneTables build_edge_lane_tables(const SparseMatrix::Csr &g, const LevelTables *levels) {
+  EdgeLaneTables t;
+  if (g.max_row_weight > 64 || g.n_rows == 0) return t;
+  t.layered = levels != nullptr;
+  t.level_chunk.assign(1, 0);
+  std::vector<uint32_t> edge_lane(std::max<uint32_t>(g.n_edges, 1), 0);
+  uint32_t fill = 0;  // lanes used in the open chunk
+  auto close = [&]() {
+    if (fill == 0) return;
+    const size_t c0 = t.lane_var.size() - fill;
+    uint32_t dmax = 0;
+    for (size_t k = c0; k < c0 + fill; k++) dmax = std::max(dmax, (t.lane_info[k] >> 8) & 0xFFu);
+    t.lane_var.resize(c0 + 64, dev::kNoLane);
+    t.lane_info.resize(c0 + 64, 0);
+    for (size_t k = c0; k < c0 + 64; k++) t.lane_info[k] |= dmax << 16;
+    fill = 0;
+  };
+  auto add_row = [&](uint32_t r) {
+    const uint32_t e0 = g.row_ptr[r], dr = g.row_ptr[r + 1] - e0;
+    if (dr == 0) return;  // an empty row has no message and an even parity
+    if (fill + dr > 64) close();
+    for (uint32_t i = 0; i < dr; i++) {
+      edge_lane[e0 + i] = static_cast<uint32_t>(t.lane_var.size());
+      t.lane_var.push_back(g.edge_col[e0 + i]);
+      t.lane_info.push_back(i | (dr << 8));
+    }
+    fill += dr;
+  };
+  auto close_level = [&]() {
+    close();
+    t.level_chunk.push_back(static_cast<uint32_t>(t.lane_var.size() / 64));
+  };
+  if (t.layered) {
+    for (size_t l = 0; l + 1 < levels->level_ptr.size(); l++) {
+      for (uint32_t idx = levels->level_ptr[l]; idx < levels->level_ptr[l + 1]; idx++) add_row(levels->rows[idx]);
+      close_level();
+    }
+  } else {
+    for (uint32_t r = 0; r < g.n_rows; r++) add_row(r);
+    close_level();
+    t.var_ptr.assign(g.col_ptr.begin(), g.col_ptr.end());
+    t.var_lane.resize(std::max<uint32_t>(g.n_edges, 1), 0);
+    for (uint32_t j = 0; j < g.n_edges; j++) t.var_lane[j] = edge_lane[g.col_edge[j]];
+  }
+  t.n_chunks = static_cast<uint32_t>(t.lane_var.size() / 64);
+  t.ready = true;
+  return t;
+}
+
+// Depuncture map of the reference's block pattern (puncturing.rs:27-40): source block of every pattern block, -1 =
+// punctured.  ready: the pattern keeps something and its length divides the codeword length.
+struct DepunctureMap {
+  bool ready = false;
+  std::vector<int32_t> src_block;
+  size_t input_len = 0;  // LLRs per codeword a caller supplies
+};
+inline DepunctureMap build_depuncture_map(const std::vector<uint8_t> &puncturing, size_t n_cols) {
+  DepunctureMap t;
+  size_t trues = 0;
+  for (uint8_t p : puncturing) trues += p ? 1 : 0;
+  if (trues == 0 || n_cols % puncturing.size() != 0) return t;
+  t.src_block.resize(puncturing.size());
+  int32_t j = 0;
+  for (size_t k = 0; k < puncturing.size(); k++) t.src_block[k] = puncturing[k] ? j++ : -1;
+  t.input_len = n_cols / puncturing.size() * trues;
+  t.ready = true;
+  return t;
+}
+
+}  // namespace ldpc

@@ -22,6 +22,7 @@
 
 #include "exact_math.h"
 #include "fast_div.h"
+#include "graph_tables.h"  // constants of the table words: kAux*, kPeer*, kNoLane
 
 // The kernels, by schedule.  Every translation unit of the library includes this header (device_decoder_internal.h); a kernel is
 // compiled where it is launched: the float rules in run_group_f32.hip / run_group_f64.hip, the group kernels in device_decoder.hip.

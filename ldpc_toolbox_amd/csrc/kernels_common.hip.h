@@ -124,7 +124,6 @@ struct Graph {
   // row-record kernels (cn_minsum_rec_kernel): per-edge word, see kPeerKeep
   const uint32_t *edge_peer;
 };
-enum : uint32_t { kAuxNone = 0xFFFFFFFFu, kAuxWriter = 0x80000000u, kAuxSingle = 0x7FFFFFFEu, kAuxMask = 0x7FFFFFFFu };
 struct Sched {
   uint32_t tile;             // codewords per layout tile
   uint32_t nchunks;          // wave-sized codeword slices in the group

@@ -53,7 +53,6 @@ struct EdgeLatTables {
   const int32_t *src_block;     // depuncture map or null
   uint32_t block_size;
 };
-enum : uint32_t { kNoLane = 0xFFFFFFFFu };
 
 struct EdgeLatState {  // 8 XCDs x kEdgeBundle codeword slots carved from one allocation: soft | msg | chan | rawhard
   char *base;

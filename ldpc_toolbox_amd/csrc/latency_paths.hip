@@ -15,127 +15,162 @@ namespace ldpc {
 // the kernel gives up with its error word set and the call is redone by the batched kernels (kLatencyRetry).
 static std::mutex g_latency_mutex;
 
+// What a call of either small-batch path stages, the same way: the size of the persistent launch, the pinned chunks,
+// the error word, and the retreat to the batched kernels.  The paths' tables, state and launches are their own.
+struct DeviceDecoder::SmallBatchCall {
+  DeviceDecoder &d;
+  SmallBatchStaging &st;
+  const bool host_pointers;
+  const size_t batch;
+  // the caller's buffers ...
+  const void *const llrs;
+  uint8_t *const bits;
+  int32_t *const iterations;
+  void *const posterior;
+  const size_t in_bytes, bits_bytes, post_bytes;
+  // ... and what the kernel reads and writes: those (device memory), or the pinned chunks of a host-pointer call
+  const void *d_llrs;
+  uint8_t *d_bits;
+  int32_t *d_iters;
+  void *d_post;
+  uint32_t *o_err = nullptr;
+
+  SmallBatchCall(DeviceDecoder &dec, SmallBatchStaging &staging, const void *llrs_, bool llrs_f64, bool host, size_t batch_,
+                 uint8_t *bits_, size_t out_len, int32_t *iterations_, void *posterior_)
+      : d(dec), st(staging), host_pointers(host), batch(batch_), llrs(llrs_), bits(bits_), iterations(iterations_),
+        posterior(posterior_), in_bytes(batch_ * dec.input_len_ * (llrs_f64 ? 8 : 4)), bits_bytes(batch_ * out_len),
+        post_bytes(batch_ * dec.n_ * (llrs_f64 ? 8 : 4)), d_llrs(llrs_), d_bits(bits_), d_iters(iterations_), d_post(posterior_) {
+    d.last_lanes_ = 1;
+    d.last_group_ = batch;
+  }
+
+  int retreat() {
+    d.opt_latency_ = 0;
+    d.opt_latency_edge_ = 0;
+    return kLatencyRetry;
+  }
+  // One workgroup of 1024 threads per CU, all of them resident together (the kernel's census waits for all of them, and
+  // derives how many share an XCD at run time): the grid is what the device can hold at once of the kernel this handle
+  // launches, for f32 and for f64 input -- 256 on an MI355X in SPX mode, fewer on a partitioned or smaller device --
+  // and never more than 256.  Fewer than 8 cannot be co-resident in any useful number: the handle keeps the batched kernels.
+  int size_grid(const void *kernel_f32, const void *kernel_f64) {
+    if (st.grid != 0) return 0;
+    int cus = 0, per_cu_f = 0, per_cu_d = 0;
+    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device_);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, kernel_f32, 1024, 0);
+    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, kernel_f64, 1024, 0);
+    const int resident = e == hipSuccess ? cus * std::min(per_cu_f, per_cu_d) : 0;
+    if (resident < 8) return retreat();
+    st.grid = static_cast<uint32_t>(std::min(resident, 256));
+    return 0;
+  }
+  // The kernel writes the error word into pinned host memory (system scope), and for host-pointer calls it also
+  // reads the input there (its ingest: coalesced, in source order, over the bus) and writes the outputs there:
+  // a call is memcpy -> one launch -> memcpy with no copy commands (each costs ~10 us of command latency, as
+  // much as ten iterations of the decoder; measured -15..25 us per call, profiles/r02_latency.txt).
+  int stage(size_t granule) {
+    const size_t iters_at = round_up(256 + bits_bytes, 256), post_at = round_up(iters_at + batch * sizeof(int32_t), 256);
+    const size_t out_need = host_pointers ? post_at + (posterior ? post_bytes : 0) : 256;
+    if (st.h_out.ensure(out_need, granule) != hipSuccess || (host_pointers && st.h_in.ensure(in_bytes, granule) != hipSuccess)) {
+      d.fail("pinned host memory for the small-batch path");
+      return -1;
+    }
+    char *const h_out = st.h_out.get<char>();
+    o_err = reinterpret_cast<uint32_t *>(h_out);
+    *o_err = 0;
+    if (host_pointers) {
+      std::memcpy(st.h_in.get(), llrs, in_bytes);
+      d_llrs = st.h_in.get();
+      d_bits = reinterpret_cast<uint8_t *>(h_out + 256);
+      d_iters = reinterpret_cast<int32_t *>(h_out + iters_at);
+      d_post = posterior ? static_cast<void *>(h_out + post_at) : nullptr;
+    }
+    return 0;
+  }
+  // after the launch has been synchronised
+  int finish() {
+    if (*o_err != 0) {
+      // the workgroups did not come together within the bounded spins (another process holds CUs, or the device
+      // is not what the occupancy query promised): do not pay that timeout on every call -- this handle decodes
+      // its small batches with the batched kernels from now on
+      std::fprintf(stderr, "ldpc_toolbox (hip): the single-launch small-batch path could not get its %u workgroups resident; "
+                           "this decoder uses the batched kernels from now on\n", st.grid);
+      return retreat();
+    }
+    if (host_pointers) {
+      if (bits_bytes) std::memcpy(bits, d_bits, bits_bytes);
+      if (iterations) std::memcpy(iterations, d_iters, batch * sizeof(int32_t));
+      if (posterior) std::memcpy(posterior, d_post, post_bytes);
+    }
+    return 0;
+  }
+};
+
 int DeviceDecoder::decode_latency(const void *llrs, bool llrs_f64, bool host_pointers, size_t batch,
                                   uint32_t max_iterations, uint8_t *bits, size_t out_len, int32_t *iterations,
                                   void *posterior, hipStream_t s) {
   std::lock_guard<std::mutex> one_at_a_time(g_latency_mutex);
   LatencyPath &lp = *lat_;
-  const size_t in_elem = llrs_f64 ? 8 : 4;
+  const SlicedTables &tb = lp.tables;
+  SmallBatchCall call(*this, lp.staging, llrs, llrs_f64, host_pointers, batch, bits, out_len, iterations, posterior);
   const uint32_t n = static_cast<uint32_t>(n_), m = static_cast<uint32_t>(m_);
-  last_lanes_ = 1;
-  last_group_ = batch;
   if (!lp.uploaded) {
-    auto up = [&](const std::vector<uint32_t> &v, uint32_t **dst) -> int {
-      HIP_TRY(hipMalloc(reinterpret_cast<void **>(dst), std::max<size_t>(v.size(), 1) * sizeof(uint32_t)));
-      if (!v.empty()) HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      return 0;
-    };
-    if (int rc = up(lp.h_rslice_ptr, &lp.d_rslice_ptr)) return rc;
-    if (int rc = up(lp.h_rdeg, &lp.d_rdeg)) return rc;
-    if (int rc = up(lp.h_col, &lp.d_col)) return rc;
-    if (int rc = up(lp.h_vslice_ptr, &lp.d_vslice_ptr)) return rc;
-    if (int rc = up(lp.h_vdeg, &lp.d_vdeg)) return rc;
-    if (int rc = up(lp.h_vedge, &lp.d_vedge)) return rc;
-    if (int rc = up(lp.h_perm, &lp.d_perm)) return rc;
-    if (int rc = up(lp.h_inv, &lp.d_inv)) return rc;
+    hipError_t e = hipSuccess;
+    for (auto [v, dst] : {std::pair{&tb.rslice_ptr, &lp.d_rslice_ptr}, {&tb.rdeg, &lp.d_rdeg}, {&tb.col, &lp.d_col},
+                          {&tb.vslice_ptr, &lp.d_vslice_ptr}, {&tb.vdeg, &lp.d_vdeg}, {&tb.vedge, &lp.d_vedge},
+                          {&tb.perm, &lp.d_perm}, {&tb.inv, &lp.d_inv}}) {
+      *dst = upload(*v, &e);
+      HIP_TRY(e);
+    }
     // per-XCD codeword state, each array on a 256-byte boundary (msg: one word per edge id)
-    const size_t a_n = round_up((size_t(n) * 2 + 64) * 4, 256), a_m = round_up((size_t(lp.h_rslice_ptr.back()) + 8 * 64) * 4, 256),
+    const size_t a_n = round_up((size_t(n) * 2 + 64) * 4, 256), a_m = round_up((size_t(tb.rslice_ptr.back()) + 8 * 64) * 4, 256),
                  a_h = round_up(n, 256), slot = 2 * a_n + a_m + a_h;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lp.slots.base), 8 * slot));
+    HIP_TRY(lp.slot_mem.ensure(8 * slot));
+    lp.slots.base = lp.slot_mem.get<char>();
     lp.slots.slot_bytes = slot;
     lp.slots.off_post = a_n;
     lp.slots.off_msg = 2 * a_n;
     lp.slots.off_rawhard = 2 * a_n + a_m;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lp.d_sync), sizeof(dev::LatencySync)));
+    HIP_TRY(lp.sync.ensure(sizeof(dev::LatencySync)));
     lp.uploaded = true;
   }
-  const void *d_llrs = llrs;
-  uint8_t *d_bits = bits;
-  int32_t *d_iters = iterations;
-  void *d_post = posterior;
-  const size_t in_bytes = batch * input_len_ * in_elem, bits_bytes = batch * out_len, post_bytes = batch * n_ * in_elem;
-  // The kernel writes the error word into pinned host memory (system scope), and for host-pointer calls it also
-  // reads the input there (its ingest: coalesced, in source order, over the bus) and writes the outputs there:
-  // a call is memcpy -> one launch -> memcpy with no copy commands (each costs ~10 us of command latency, as
-  // much as ten iterations of the decoder; measured -15..25 us per call, profiles/r02_latency.txt).
-  const size_t iters_at = round_up(256 + bits_bytes, 256), post_at = round_up(iters_at + batch * sizeof(int32_t), 256);
-  const size_t out_need = host_pointers ? post_at + (posterior ? post_bytes : 0) : 256;
-  if (lp.pinned(&lp.h_out, &lp.h_out_bytes, out_need) || (host_pointers && lp.pinned(&lp.h_in, &lp.h_in_bytes, in_bytes))) {
-    fail("pinned host memory for the small-batch path");
-    return -1;
-  }
-  uint32_t *const o_err = reinterpret_cast<uint32_t *>(lp.h_out);
-  *o_err = 0;
-  if (host_pointers) {
-    std::memcpy(lp.h_in, llrs, in_bytes);
-    d_llrs = lp.h_in;
-    d_bits = reinterpret_cast<uint8_t *>(lp.h_out + 256);
-    d_iters = reinterpret_cast<int32_t *>(lp.h_out + iters_at);
-    d_post = posterior ? static_cast<void *>(lp.h_out + post_at) : nullptr;
-  }
-  HIP_TRY(hipMemsetAsync(lp.d_sync, 0, sizeof(dev::LatencySync), s));
-  dev::LatencyTables t{n, m, (m + 63) / 64, (n + 63) / 64, lp.d_rslice_ptr, lp.d_rdeg, lp.d_col, lp.d_vslice_ptr, lp.d_vdeg,
-                       lp.d_vedge, lp.d_perm, lp.d_inv, d_src_block_, pattern_len_ ? n / pattern_len_ : 0};
-  // one workgroup of 1024 threads per CU, all of them resident together (the kernel's census waits for all of them,
-  // and derives how many share an XCD at run time): the grid is what the device can hold at once -- 256 on an
-  // MI355X in SPX mode, fewer on a partitioned or smaller device -- and never more than 256
+  if (int rc = call.stage(LatencyPath::kPinnedGranule)) return rc;
+  dev::LatencySync *const d_sync = lp.sync.get<dev::LatencySync>();
+  HIP_TRY(hipMemsetAsync(d_sync, 0, sizeof(dev::LatencySync), s));
+  auto u32 = [](const DeviceBuffer &b) { return b.get<uint32_t>(); };
+  dev::LatencyTables t{n, m, (m + 63) / 64, (n + 63) / 64, u32(lp.d_rslice_ptr), u32(lp.d_rdeg), u32(lp.d_col), u32(lp.d_vslice_ptr),
+                       u32(lp.d_vdeg), u32(lp.d_vedge), u32(lp.d_perm), u32(lp.d_inv), d_src_block_.get<int32_t>(),
+                       pattern_len_ ? n / pattern_len_ : 0};
   // plain / corrected arithmetic: f(auto... c) gets nothing or the kernel's last argument, and names the kernel
   // latency_minsum_kernel<SrcT, decltype(c)...> (a corrected implementation never takes the plain kernel)
   const dev::MinsumCorr<float> mc{static_cast<float>(impl_.alpha()), static_cast<float>(impl_.beta())};
   auto with_corr = [&](auto f) {
     if (impl_.correction != Correction::None)
-      f(mc);
-    else
-      f();
+      return f(mc);
+    return f();
   };
-  if (lp.grid == 0) {
-    int cus = 0, per_cu_f = 0, per_cu_d = 0;
-    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_);
-    // (of the kernel this handle launches)
-    with_corr([&](auto... c) {
-      if (e == hipSuccess)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, dev::latency_minsum_kernel<float, decltype(c)...>, 1024, 0);
-      if (e == hipSuccess)
-        e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, dev::latency_minsum_kernel<double, decltype(c)...>, 1024, 0);
-    });
-    const int resident = e == hipSuccess ? cus * std::min(per_cu_f, per_cu_d) : 0;
-    if (resident < 8) {  // cannot be co-resident in any useful number: this handle keeps the batched kernels
-      opt_latency_ = 0;
-      opt_latency_edge_ = 0;
-      return kLatencyRetry;
-    }
-    lp.grid = static_cast<uint32_t>(std::min(resident, 256));
-  }
-  const uint32_t grid = lp.grid;
+  // (sized by the kernel this handle launches)
+  if (int rc = with_corr([&](auto... c) {
+        return call.size_grid(reinterpret_cast<const void *>(dev::latency_minsum_kernel<float, decltype(c)...>),
+                              reinterpret_cast<const void *>(dev::latency_minsum_kernel<double, decltype(c)...>));
+      }))
+    return rc;
+  const uint32_t grid = lp.staging.grid;
   // one launch, four kernels: the caller's LLR type x plain / corrected arithmetic
   with_corr([&](auto... c) {
     auto go = [&](auto kernel, auto *src, auto *dst) {
-      kernel<<<grid, 1024, 0, s>>>(t, lp.slots, lp.d_sync, src, static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
-                                   max_iterations, d_bits, static_cast<uint32_t>(out_len), d_iters, dst, o_err, c...);
+      kernel<<<grid, 1024, 0, s>>>(t, lp.slots, d_sync, src, static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
+                                   max_iterations, call.d_bits, static_cast<uint32_t>(out_len), call.d_iters, dst, call.o_err, c...);
     };
     if (llrs_f64)
-      go(dev::latency_minsum_kernel<double, decltype(c)...>, static_cast<const double *>(d_llrs), static_cast<double *>(d_post));
+      go(dev::latency_minsum_kernel<double, decltype(c)...>, static_cast<const double *>(call.d_llrs), static_cast<double *>(call.d_post));
     else
-      go(dev::latency_minsum_kernel<float, decltype(c)...>, static_cast<const float *>(d_llrs), static_cast<float *>(d_post));
+      go(dev::latency_minsum_kernel<float, decltype(c)...>, static_cast<const float *>(call.d_llrs), static_cast<float *>(call.d_post));
+    return 0;
   });
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(s));
-  if (*o_err != 0) {
-    // the workgroups did not come together within the bounded spins (another process holds CUs, or the device
-    // is not what the occupancy query promised): do not pay that timeout on every call -- this handle decodes
-    // its small batches with the batched kernels from now on
-    opt_latency_ = 0;
-    opt_latency_edge_ = 0;
-    std::fprintf(stderr, "ldpc_toolbox (hip): the single-launch small-batch path could not get its %u workgroups resident; "
-                         "this decoder uses the batched kernels from now on\n", grid);
-    return kLatencyRetry;
-  }
-  if (host_pointers) {
-    if (bits_bytes) std::memcpy(bits, d_bits, bits_bytes);
-    if (iterations) std::memcpy(iterations, d_iters, batch * sizeof(int32_t));
-    if (posterior) std::memcpy(posterior, d_post, post_bytes);
-  }
-  return 0;
+  return call.finish();
 }
 
 // Largest batch the lane-per-edge path takes: 8 XCDs x the bundle an XCD decodes at once -- as many codewords as keep the
@@ -196,103 +231,62 @@ int DeviceDecoder::decode_latency_edge(const void *llrs, bool llrs_f64, bool hos
                                           void *posterior, hipStream_t s) {
   std::lock_guard<std::mutex> one_at_a_time(g_latency_mutex);
   EdgeLatencyPath &lp = *lat_edge_;
-  const size_t in_elem = llrs_f64 ? 8 : 4, elem = impl_.f64 ? 8 : 4;
+  const EdgeLaneTables &tb = lp.tables;
+  SmallBatchCall call(*this, lp.staging, llrs, llrs_f64, host_pointers, batch, bits, out_len, iterations, posterior);
+  const size_t elem = impl_.f64 ? 8 : 4;
   const bool corrected = impl_.correction != Correction::None;
   const uint32_t n = static_cast<uint32_t>(n_), m = static_cast<uint32_t>(m_);
-  last_lanes_ = 1;
-  last_group_ = batch;
   if (!lp.uploaded) {
-    auto up = [&](const std::vector<uint32_t> &v, uint32_t **dst) -> int {
-      HIP_TRY(hipMalloc(reinterpret_cast<void **>(dst), std::max<size_t>(v.size(), 1) * sizeof(uint32_t)));
-      if (!v.empty()) HIP_TRY(hipMemcpy(*dst, v.data(), v.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-      return 0;
-    };
-    if (int rc = up(lp.h_level_chunk, &lp.d_level_chunk)) return rc;
-    if (int rc = up(lp.h_lane_var, &lp.d_lane_var)) return rc;
-    if (int rc = up(lp.h_lane_info, &lp.d_lane_info)) return rc;
-    if (int rc = up(lp.h_var_ptr, &lp.d_var_ptr)) return rc;
-    if (int rc = up(lp.h_var_lane, &lp.d_var_lane)) return rc;
+    hipError_t e = hipSuccess;
+    for (auto [v, dst] : {std::pair{&tb.level_chunk, &lp.d_level_chunk}, {&tb.lane_var, &lp.d_lane_var}, {&tb.lane_info, &lp.d_lane_info},
+                          {&tb.var_ptr, &lp.d_var_ptr}, {&tb.var_lane, &lp.d_var_lane}}) {
+      *dst = upload(*v, &e);
+      HIP_TRY(e);
+    }
     // per-XCD codeword state, each array on a 256-byte boundary: soft values | messages (one per lane slot) |
     // channel LLRs (flooding) | raw hard decisions
-    const size_t a_q = round_up(size_t(n) * elem + 256, 256), a_r = round_up(size_t(lp.n_chunks) * 64 * elem + 256, 256),
-                 a_c = lp.layered ? 0 : a_q, a_h = round_up(size_t(n) + 256, 256), slot = a_q + a_r + a_c + a_h;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lp.slots.base), size_t(8) * dev::kEdgeBundle * slot));
+    const size_t a_q = round_up(size_t(n) * elem + 256, 256), a_r = round_up(size_t(tb.n_chunks) * 64 * elem + 256, 256),
+                 a_c = tb.layered ? 0 : a_q, a_h = round_up(size_t(n) + 256, 256), slot = a_q + a_r + a_c + a_h;
+    HIP_TRY(lp.slot_mem.ensure(size_t(8) * dev::kEdgeBundle * slot));
+    lp.slots.base = lp.slot_mem.get<char>();
     lp.slots.slot_bytes = slot;
     lp.slots.off_msg = a_q;
     lp.slots.off_chan = a_q + a_r;
     lp.slots.off_rawhard = a_q + a_r + a_c;
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lp.slots.flags), size_t(8) * 2 * dev::kEdgeBundle * sizeof(uint32_t)));
-    HIP_TRY(hipMalloc(reinterpret_cast<void **>(&lp.d_sync), sizeof(dev::LatencySync)));
+    HIP_TRY(lp.flag_mem.ensure(size_t(8) * 2 * dev::kEdgeBundle * sizeof(uint32_t)));
+    lp.slots.flags = lp.flag_mem.get<uint32_t>();
+    HIP_TRY(lp.sync.ensure(sizeof(dev::LatencySync)));
     lp.uploaded = true;
   }
-  if (lp.grid == 0) {
-    // every workgroup of the persistent launch must be resident (see decode_latency)
-    int cus = 0, per_cu_f = 0, per_cu_d = 0;
-    hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device_);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, false, lp.layered), 1024, 0);
-    if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, true, lp.layered), 1024, 0);
-    const int resident = e == hipSuccess ? cus * std::min(per_cu_f, per_cu_d) : 0;
-    if (resident < 8) {
-      opt_latency_ = 0;
-      opt_latency_edge_ = 0;
-      return kLatencyRetry;
-    }
-    lp.grid = static_cast<uint32_t>(std::min<int>(resident, 256));
-  }
-  const void *d_llrs = llrs;
-  uint8_t *d_bits = bits;
-  int32_t *d_iters = iterations;
-  void *d_post = posterior;
-  const size_t in_bytes = batch * input_len_ * in_elem, bits_bytes = batch * out_len, post_bytes = batch * n_ * in_elem;
-  const size_t iters_at = round_up(256 + bits_bytes, 256), post_at = round_up(iters_at + batch * sizeof(int32_t), 256);
-  const size_t out_need = host_pointers ? post_at + (posterior ? post_bytes : 0) : 256;
-  if (EdgeLatencyPath::pinned(&lp.h_out, &lp.h_out_bytes, out_need) ||
-      (host_pointers && EdgeLatencyPath::pinned(&lp.h_in, &lp.h_in_bytes, in_bytes))) {
-    fail("pinned host memory for the small-batch path");
-    return -1;
-  }
-  uint32_t *o_err = reinterpret_cast<uint32_t *>(lp.h_out);
-  *o_err = 0;
-  if (host_pointers) {
-    std::memcpy(lp.h_in, llrs, in_bytes);
-    d_llrs = lp.h_in;
-    d_bits = reinterpret_cast<uint8_t *>(lp.h_out + 256);
-    d_iters = reinterpret_cast<int32_t *>(lp.h_out + iters_at);
-    d_post = posterior ? static_cast<void *>(lp.h_out + post_at) : nullptr;
-  }
-  HIP_TRY(hipMemsetAsync(lp.d_sync, 0, sizeof(dev::LatencySync), s));
+  // every workgroup of the persistent launch must be resident (see decode_latency)
+  if (int rc = call.size_grid(edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, false, tb.layered),
+                              edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, true, tb.layered)))
+    return rc;
+  if (int rc = call.stage(EdgeLatencyPath::kPinnedGranule)) return rc;
+  dev::LatencySync *d_sync = lp.sync.get<dev::LatencySync>();
+  HIP_TRY(hipMemsetAsync(d_sync, 0, sizeof(dev::LatencySync), s));
   // up to 8 codewords: one per XCD; more: every XCD takes a bundle of up to kEdgeBundle that share each phase and barrier
   uint32_t bundle = static_cast<uint32_t>(std::min<size_t>(dev::kEdgeBundle, (batch + 7) / 8));
   if (bundle > 1) HIP_TRY(hipMemsetAsync(lp.slots.flags, 0, size_t(8) * 2 * dev::kEdgeBundle * sizeof(uint32_t), s));
-  dev::EdgeLatTables t{n, m, static_cast<uint32_t>(lp.h_level_chunk.size() - 1), lp.n_chunks, lp.d_level_chunk, lp.d_lane_var,
-                       lp.d_lane_info, lp.d_var_ptr, lp.d_var_lane, d_src_block_, pattern_len_ ? n / pattern_len_ : 0};
+  auto u32 = [](const DeviceBuffer &b) { return b.get<uint32_t>(); };
+  dev::EdgeLatTables t{n, m, static_cast<uint32_t>(tb.level_chunk.size() - 1), tb.n_chunks, u32(lp.d_level_chunk), u32(lp.d_lane_var),
+                       u32(lp.d_lane_info), u32(lp.d_var_ptr), u32(lp.d_var_lane), d_src_block_.get<int32_t>(),
+                       pattern_len_ ? n / pattern_len_ : 0};
   uint32_t in_len = static_cast<uint32_t>(input_len_), nb = static_cast<uint32_t>(batch), ol = static_cast<uint32_t>(out_len);
   dev::I8Opts i8o{impl_.rule == Rule::Aminstar, impl_.jones, impl_.hardlimit, impl_.deg1clip};
   // the corrected kernels' last argument, in the decoder's type (the others take the first 14)
   dev::MinsumCorr<float> mc_f{static_cast<float>(impl_.alpha()), static_cast<float>(impl_.beta())};
   dev::MinsumCorr<double> mc_d{impl_.alpha(), impl_.beta()};
-  void *args[] = {&t, &lp.slots, &lp.d_sync, &d_llrs, &in_len, &nb, &max_iterations, &d_bits, &ol, &d_iters, &d_post, &o_err, &bundle, &i8o,
-                  impl_.f64 ? static_cast<void *>(&mc_d) : static_cast<void *>(&mc_f)};
-  const void *kernel = edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, llrs_f64, lp.layered);
+  void *args[] = {&t, &lp.slots, &d_sync, &call.d_llrs, &in_len, &nb, &max_iterations, &call.d_bits, &ol, &call.d_iters, &call.d_post,
+                  &call.o_err, &bundle, &i8o, impl_.f64 ? static_cast<void *>(&mc_d) : static_cast<void *>(&mc_f)};
+  const void *kernel = edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, llrs_f64, tb.layered);
   if (kernel == nullptr) {
     fail("internal error: no small-batch kernel for this rule");
     return -3;
   }
-  HIP_TRY(hipLaunchKernel(kernel, dim3(lp.grid), dim3(1024), args, 0, s));
+  HIP_TRY(hipLaunchKernel(kernel, dim3(lp.staging.grid), dim3(1024), args, 0, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (*o_err != 0) {
-    opt_latency_ = 0;  // see decode_latency
-    opt_latency_edge_ = 0;
-    std::fprintf(stderr, "ldpc_toolbox (hip): the single-launch small-batch path could not get its %u workgroups resident; "
-                         "this decoder uses the batched kernels from now on\n", lp.grid);
-    return kLatencyRetry;
-  }
-  if (host_pointers) {
-    if (bits_bytes) std::memcpy(bits, d_bits, bits_bytes);
-    if (iterations) std::memcpy(iterations, d_iters, batch * sizeof(int32_t));
-    if (posterior) std::memcpy(posterior, d_post, post_bytes);
-  }
-  return 0;
+  return call.finish();
 }
 
 }  // namespace ldpc

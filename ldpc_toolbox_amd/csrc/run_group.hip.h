@@ -29,7 +29,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
   const uint32_t lds_columns = impl_.rule == Rule::Tanh ? 1u : 2u;
   const Launch<T> launch{s, max_row_weight_ > 8 || opt_rec_long_, impl_.fast, impl_.correction != Correction::None,
                          dev::MinsumCorr<T>{static_cast<T>(impl_.alpha()), static_cast<T>(impl_.beta())}};
-  const dev::Graph g = f.graph(d_edge_aux_, d_edge_peer_);
+  const dev::Graph g = f.graph(d_edge_aux_.get<uint32_t>(), d_edge_peer_.get<uint32_t>());
 
   if (int rc = f.begin(dev::ingest_kernel<float, T>, dev::ingest_kernel<double, T>, chan, post)) return rc;
   // (one codeword per lane: the paired-load form of the 16-bit posterior, pack_hard_pair_kernel, is slower here --
@@ -102,14 +102,14 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
         st_lds = 0;
         cn_t = make_tiling(G, tile, 64, m, st_threads, std::min(target_waves, kScratchWaves));
         if (int rc = ensure_row_scratch(w, scratch_bytes_for(cn_t, max_row_weight_, sizeof(T)))) return rc;
-        cn_scratch = static_cast<T *>(w.row_scratch);
+        cn_scratch = w.row_scratch.get<T>();
       }
     }
     // the Tanh rule on graphs with rows of at most 12 edges: rows in registers (cn_reg_kernel: 32-bit byte offsets inside
     // a tile slice).  Measured (round 4, 0.xxx of the roofline, cn_staged_kernel -> cn_reg_kernel): DVB-S2 1/2 Tanhf32
     // 0.455 -> 0.469, Tanhf64 0.410 -> 0.417, CCSDS AR4JA 1/2 Tanhf32 0.478 -> 0.479; the other rules lose 0-2 % and 5G NR
     // BG1's mixed 3..19-edge rows in one 24-edge bucket 15 %, so they keep cn_staged_kernel.
-    const uint32_t cn_reg = (streaming || !opt_cn_reg_ || d_row_recs_ == nullptr || impl_.rule != Rule::Tanh || impl_.fast ||
+    const uint32_t cn_reg = (streaming || !opt_cn_reg_ || !d_row_recs_ || impl_.rule != Rule::Tanh || impl_.fast ||
                              uint64_t(std::max(e_, n_)) * tile * sizeof(T) >= (1ull << 32))
                                 ? 0u
                                 : (max_row_weight_ <= 10 ? 10u : (max_row_weight_ <= 12 ? 12u : 0u));
@@ -132,13 +132,13 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     dev::Graph g_keep = g, g_free = g;
     Tiling vn_keep_t = vn_t, vn_free_t = vn_t, vn_event_t = vn_t;
     if (lfree) {
-      g_keep.list_var = d_keep_var_;
-      g_keep.list_ptr = d_keep_ptr_;
-      g_keep.list_edge = records ? d_keep_pos_ : d_keep_edge_;  // records: the messages are stored in this list's order
+      g_keep.list_var = d_keep_var_.get<uint32_t>();
+      g_keep.list_ptr = d_keep_ptr_.get<uint32_t>();
+      g_keep.list_edge = records ? d_keep_pos_.get<uint32_t>() : d_keep_edge_.get<uint32_t>();  // records: the messages are stored in this list's order
       g_keep.n_list = n_keep_;
-      g_free.list_var = d_free_var_;
-      g_free.list_ptr = d_free_ptr_;
-      g_free.list_edge = d_free_edge_;
+      g_free.list_var = d_free_var_.get<uint32_t>();
+      g_free.list_ptr = d_free_ptr_.get<uint32_t>();
+      g_free.list_edge = d_free_edge_.get<uint32_t>();
       g_free.n_list = n_free_;
       const uint32_t wv = opt_waves_ ? opt_waves_ : kVnWaves;
       vn_keep_t = make_tiling(G, tile, 64 * vec, n_keep_, stream_block, wv);
@@ -170,7 +170,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       else if (streaming)
         launch.cn_minsum(first, vec, wide_mask, cn_t, g, stp, first ? chan : post, msg, unsat_out);
       else
-        launch.cn_staged(first, impl_.rule, cn_reg, d_row_recs_, cn_t, st_lds, cn_scratch, g, stp, first ? chan : post, msg,
+        launch.cn_staged(first, impl_.rule, cn_reg, d_row_recs_.get<uint32_t>(), cn_t, st_lds, cn_scratch, g, stp, first ? chan : post, msg,
                          unsat_out, max_row_weight_);
       timed_end(kKernelCheck, s);
       timed_begin(kKernelVar, s);
@@ -178,14 +178,14 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       // iteration INSIDE this launch -- rounds 3-4 ran a small vn_free_rec_kernel launch behind it in every iteration, which
       // almost always found nothing: 4.4 us + a 5.7 us dispatch gap per iteration)
       if (quiet && it > 1 && opt_vn_event_) {
-        const dev::VnEvent<T> ev{d_free_var_, d_free_rs_, rbuf[(it - 1) & 1], n_free_};
+        const dev::VnEvent<T> ev{d_free_var_.get<uint32_t>(), d_free_rs_.get<uint32_t>(), rbuf[(it - 1) & 1], n_free_};
         launch.vn_event(vec, rec_w_, vn_keep_t, g_keep, st, chan, m_out, post, unsat_out, unsat[(it + 1) & 1],
                         static_cast<int32_t>(it) - 1, ev);
       } else {
         launch.vn(lfree, vec, lfree ? vn_keep_t : vn_t, lfree ? g_keep : g, st, chan, m_out, post,
                   first ? nullptr : unsat_out, unsat[(it + 1) & 1], static_cast<int32_t>(it) - 1);
         if (quiet && it > 1)
-          launch.vn_free_rec(vec, rec_w_, vn_event_t, g_free, st, d_free_rs_, chan, rbuf[(it - 1) & 1], post,
+          launch.vn_free_rec(vec, rec_w_, vn_event_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[(it - 1) & 1], post,
                              static_cast<int32_t>(it) - 1);
       }
       timed_end(kKernelVar, s);
@@ -198,7 +198,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       }
     }
     if (records && max_iterations > 0) {
-      launch.vn_free_rec(vec, rec_w_, vn_free_t, g_free, st, d_free_rs_, chan, rbuf[max_iterations & 1], post, -1);
+      launch.vn_free_rec(vec, rec_w_, vn_free_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[max_iterations & 1], post, -1);
     } else if (lfree && max_iterations > 0) {
       // posterior of the L-free variables after the last iteration (no later check-node pass
       // rebuilds it): one variable-node pass over just them; frozen codewords are skipped
@@ -253,7 +253,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
           const uint32_t rvec = Launch<T>::hl_rec_vec(vec, reg_dmax);
           const Tiling t = make_tiling(G, tile, 64 * rvec, tnodes, sblock, target_waves);
           timed_begin(kKernelLayer, s);
-          const bool launched = launch.hl_minsum_rec(it == 1, rvec, reg_dmax, t, g, st, d_level_rows_ + r0, cnt, post, msg);
+          const bool launched = launch.hl_minsum_rec(it == 1, rvec, reg_dmax, t, g, st, d_level_rows_.get<uint32_t>() + r0, cnt, post, msg);
           timed_end(kKernelLayer, s);
           if (!launched) {
             fail("internal error: no row-record layered kernel for this level");
@@ -265,7 +265,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
           const uint32_t rvec = Launch<T>::hl_reg_vec(vec, reg_dmax);
           const Tiling t = make_tiling(G, tile, 64 * rvec, tnodes, sblock, target_waves);
           timed_begin(kKernelLayer, s);
-          const bool launched = launch.hl_minsum_reg(it == 1, rvec, reg_dmax, t, g, st, d_level_rows_ + r0, cnt, post, msg);
+          const bool launched = launch.hl_minsum_reg(it == 1, rvec, reg_dmax, t, g, st, d_level_rows_.get<uint32_t>() + r0, cnt, post, msg);
           timed_end(kKernelLayer, s);
           if (!launched) {
             fail("internal error: no register-resident layered kernel for this level");
@@ -276,7 +276,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
         if (streaming) {
           const Tiling t = make_tiling(G, tile, 64 * vec, tnodes, sblock, target_waves);
           timed_begin(kKernelLayer, s);
-          launch.hl_minsum(it == 1, vec, t, g, st, d_level_rows_ + r0, cnt, post, msg);
+          launch.hl_minsum(it == 1, vec, t, g, st, d_level_rows_.get<uint32_t>() + r0, cnt, post, msg);
           timed_end(kKernelLayer, s);
           continue;
         }
@@ -301,14 +301,14 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
         // edge it saves decide whether the Tanh rule's kernel keeps 7 or 8 waves per SIMD)
         const uint32_t lreg = (!opt_hl_reg_ || !fits32) ? 0 : (ldmax <= 10 ? 10 : (ldmax <= 12 ? 12 : (ldmax <= 24 ? 24 : 0)));
         // (the register-resident kernels read a level's row records, the two-pass kernel the row list)
-        const uint32_t *ltab = !lreg ? d_level_rows_ + r0 : (serial ? d_serial_recs_ : d_level_recs_ + level_rec_ptr_[l]);
+        const uint32_t *ltab = !lreg ? d_level_rows_.get<uint32_t>() + r0 : (serial ? d_serial_recs_.get<uint32_t>() : d_level_recs_.get<uint32_t>() + level_rec_ptr_[l]);
         const Tiling t = make_tiling(G, tile, 64, tnodes, lthreads, lfits ? target_waves : std::min(target_waves, kScratchWaves));
-        if (!lfits && scratch_bytes_for(t, ldmax, sizeof(T)) > w.row_scratch_bytes) {
+        if (!lfits && scratch_bytes_for(t, ldmax, sizeof(T)) > w.row_scratch.capacity()) {
           fail("internal error: row scratch smaller than a level's launch");
           return -3;
         }
         timed_begin(kKernelLayer, s);
-        launch.hl(it == 1, impl_.rule, lreg, t, llds, lfits ? nullptr : static_cast<T *>(w.row_scratch), g, st, ltab, cnt, post,
+        launch.hl(it == 1, impl_.rule, lreg, t, llds, lfits ? nullptr : w.row_scratch.get<T>(), g, st, ltab, cnt, post,
                   msg, ldmax);
         timed_end(kKernelLayer, s);
       }

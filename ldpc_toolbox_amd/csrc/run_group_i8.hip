@@ -46,7 +46,7 @@ int DeviceDecoder::run_group_i8(Workspace &w, const GroupCall &call) {
     const size_t waves_bound = size_t(kScratchWaves) + size_t(G / 256) * (kScratchThreads / 64);
     if (int rc = ensure_row_scratch(w, waves_bound * 2 * max_row_weight_ * 64 * 4)) return rc;
   }
-  uint32_t *const i8_scratch = static_cast<uint32_t *>(w.row_scratch);
+  uint32_t *const i8_scratch = w.row_scratch.get<uint32_t>();
   if (!minsum) lds += 32;  // the correction lookup table (kernels_i8.hip.h, i8_table_init)
   auto set_lds = [&](const void *k) {
     if (lds > 48 * 1024)
@@ -57,7 +57,7 @@ int DeviceDecoder::run_group_i8(Workspace &w, const GroupCall &call) {
   if (impl_.schedule == Schedule::Flooding) {
     const Tiling cn_t = make_tiling(G, tile, 256, m, threads, i8_fits ? target_waves : std::min(target_waves, kScratchWaves));
     const Tiling vn_t = make_tiling(G, tile, 256, n, 256, target_waves);
-    if (!i8_fits && scratch_bytes_for(cn_t, max_row_weight_, 4) > w.row_scratch_bytes) {
+    if (!i8_fits && scratch_bytes_for(cn_t, max_row_weight_, 4) > w.row_scratch.capacity()) {
       fail("internal error: row scratch smaller than the check-node launch");
       return -3;
     }
@@ -125,7 +125,7 @@ int DeviceDecoder::run_group_i8(Workspace &w, const GroupCall &call) {
         }
         const uint32_t lreg = !opt_hl_reg_ ? 0 : (ldmax <= 12 ? 12 : (ldmax <= 24 ? 24 : 0));
         const Tiling t = make_tiling(G, tile, 256, serial ? 1 : cnt, lthreads, lfits ? target_waves : std::min(target_waves, kScratchWaves));
-        if (!minsum && !lfits && scratch_bytes_for(t, ldmax, 4) > w.row_scratch_bytes) {
+        if (!minsum && !lfits && scratch_bytes_for(t, ldmax, 4) > w.row_scratch.capacity()) {
           fail("internal error: row scratch smaller than a level's launch");
           return -3;
         }
@@ -134,11 +134,11 @@ int DeviceDecoder::run_group_i8(Workspace &w, const GroupCall &call) {
           if (llds > 48 * 1024)
             (void)hipFuncSetAttribute(reinterpret_cast<const void *>(k), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       static_cast<int>(llds));
-          k<<<t.blocks, t.threads, llds, s>>>(g, t.sched, st, o, d_level_rows_ + r0, cnt, post, msg, tail...);
+          k<<<t.blocks, t.threads, llds, s>>>(g, t.sched, st, o, d_level_rows_.get<uint32_t>() + r0, cnt, post, msg, tail...);
         };
         auto launch_minsum = [&](auto k) {
           const Tiling mt = make_tiling(G, tile, 256, serial ? 1 : cnt, serial ? 64 : 256, target_waves);
-          k<<<mt.blocks, mt.threads, 0, s>>>(g, mt.sched, st, mo, d_level_rows_ + r0, cnt, post, msg);
+          k<<<mt.blocks, mt.threads, 0, s>>>(g, mt.sched, st, mo, d_level_rows_.get<uint32_t>() + r0, cnt, post, msg);
         };
         timed_begin(kKernelLayer, s);
         with_bool(it == 1, [&](auto FIRST) {

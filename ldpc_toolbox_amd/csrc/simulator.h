@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "device_decoder.h"
+#include "hip_owned.h"
 #include "encoder.h"
 
 namespace ldpc {
@@ -70,17 +71,14 @@ class Simulator {
   bool fail(const std::string &m, hipError_t e = hipSuccess);
 
   std::unique_ptr<DeviceDecoder> dec_;
+  Stream stream_;  // (declared before the buffers: destroyed after them)
   size_t k_ = 0, n_ = 0, n_tx_ = 0;
   uint32_t pool_ = 0;
   int device_ = 0;
   int bits_per_symbol_ = 1;
   int64_t interleaving_ = 0;
   std::vector<uint8_t> messages_, tx_bits_;
-  uint8_t *d_messages_ = nullptr, *d_tx_ = nullptr, *d_bits_ = nullptr;
-  float *d_llrs_ = nullptr;
-  int32_t *d_its_ = nullptr;
-  unsigned long long *d_counters_ = nullptr;
-  size_t cap_frames_ = 0, cap_llr_rows_ = 0;
+  DeviceBuffer d_messages_, d_tx_, d_bits_, d_llrs_, d_its_, d_counters_;
   // Straggler pooling: once a run() call has seen how many iterations its frames take, later chunks run a reduced
   // budget and the frames that have not converged by then are pooled and decoded together with the full budget --
   // instead of every chunk dragging its few slow (or failing) frames through launch-bound, nearly empty iterations
@@ -91,15 +89,10 @@ class Simulator {
   bool budget_valid_ = false;  // the reduced budget the last call arrived at, and the point it belongs to
   uint32_t budget_ = 0, budget_max_it_ = 0;
   double budget_ebn0_ = 0.0;
-  float *d_pool_llrs_ = nullptr;
-  uint64_t *d_pool_frames_ = nullptr;
-  uint32_t *d_pool_count_ = nullptr;
-  uint8_t *d_pool_bits_ = nullptr;
-  int32_t *d_pool_its_ = nullptr;
+  DeviceBuffer d_pool_llrs_, d_pool_frames_, d_pool_count_, d_pool_bits_, d_pool_its_;
   size_t pool_cap_ = 0;
   int ensure_pool(size_t capacity);
   int flush_pool(uint32_t count, uint64_t seed, uint32_t max_iterations, uint64_t bch_max_errors, size_t chunk_group);
-  hipStream_t stream_ = nullptr;
   std::string error_;
 };
 

@@ -79,62 +79,38 @@ Simulator *Simulator::create(const std::string &alist, const std::string &implem
     }
   }
   if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice failed");
-  bool ok = hipMalloc(reinterpret_cast<void **>(&s->d_messages_), s->messages_.size()) == hipSuccess &&
-            hipMalloc(reinterpret_cast<void **>(&s->d_tx_), s->tx_bits_.size()) == hipSuccess &&
-            hipMalloc(reinterpret_cast<void **>(&s->d_counters_), 9 * sizeof(unsigned long long)) == hipSuccess &&
-            hipMemcpy(s->d_messages_, s->messages_.data(), s->messages_.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            hipMemcpy(s->d_tx_, s->tx_bits_.data(), s->tx_bits_.size(), hipMemcpyHostToDevice) == hipSuccess &&
-            hipStreamCreateWithFlags(&s->stream_, hipStreamNonBlocking) == hipSuccess;
+  bool ok = s->d_messages_.ensure(s->messages_.size()) == hipSuccess && s->d_tx_.ensure(s->tx_bits_.size()) == hipSuccess &&
+            s->d_counters_.ensure(9 * sizeof(unsigned long long)) == hipSuccess &&
+            hipMemcpy(s->d_messages_.get(), s->messages_.data(), s->messages_.size(), hipMemcpyHostToDevice) == hipSuccess &&
+            hipMemcpy(s->d_tx_.get(), s->tx_bits_.data(), s->tx_bits_.size(), hipMemcpyHostToDevice) == hipSuccess &&
+            s->stream_.create() == hipSuccess;
   if (!ok) return bail("device allocation for the simulator failed");
   return s.release();
 }
 
+// (the members free what they own, the stream last and the decoder after it)
 Simulator::~Simulator() {
   (void)hipSetDevice(device_);
   if (stream_) (void)hipStreamSynchronize(stream_);
-  for (void *p : {(void *)d_messages_, (void *)d_tx_, (void *)d_bits_, (void *)d_llrs_, (void *)d_its_,
-                  (void *)d_counters_, (void *)d_pool_llrs_, (void *)d_pool_frames_, (void *)d_pool_count_,
-                  (void *)d_pool_bits_, (void *)d_pool_its_})
-    if (p) (void)hipFree(p);
-  if (stream_) (void)hipStreamDestroy(stream_);
 }
 
 // device buffers: LLR rows (one group's worth is enough for the streamed chunks), decoded bits and iteration counts
 int Simulator::ensure(size_t frames, size_t llr_rows) {
-  if (llr_rows > cap_llr_rows_) {
-    if (d_llrs_) (void)hipFree(d_llrs_);
-    d_llrs_ = nullptr;
-    cap_llr_rows_ = 0;
-    SIM_TRY(hipMalloc(reinterpret_cast<void **>(&d_llrs_), llr_rows * n_tx_ * sizeof(float)));
-    cap_llr_rows_ = llr_rows;
-  }
-  if (frames <= cap_frames_) return 0;
-  for (void *p : {(void *)d_bits_, (void *)d_its_})
-    if (p) (void)hipFree(p);
-  d_bits_ = nullptr;
-  d_its_ = nullptr;
-  cap_frames_ = 0;
-  SIM_TRY(hipMalloc(reinterpret_cast<void **>(&d_bits_), frames * std::max<size_t>(k_, 1)));
-  SIM_TRY(hipMalloc(reinterpret_cast<void **>(&d_its_), frames * sizeof(int32_t)));
-  cap_frames_ = frames;
+  SIM_TRY(d_llrs_.ensure(llr_rows * n_tx_ * sizeof(float)));
+  SIM_TRY(d_bits_.ensure(frames * std::max<size_t>(k_, 1)));
+  SIM_TRY(d_its_.ensure(frames * sizeof(int32_t)));
   return 0;
 }
 
 int Simulator::ensure_pool(size_t capacity) {
   if (capacity <= pool_cap_) return 0;
-  for (void *p : {(void *)d_pool_llrs_, (void *)d_pool_frames_, (void *)d_pool_count_, (void *)d_pool_bits_, (void *)d_pool_its_})
-    if (p) (void)hipFree(p);
-  d_pool_llrs_ = nullptr;
-  d_pool_frames_ = nullptr;
-  d_pool_count_ = nullptr;
-  d_pool_bits_ = nullptr;
-  d_pool_its_ = nullptr;
   pool_cap_ = 0;
-  SIM_TRY(hipMalloc(reinterpret_cast<void **>(&d_pool_llrs_), capacity * n_tx_ * sizeof(float)));
-  SIM_TRY(hipMalloc(reinterpret_cast<void **>(&d_pool_frames_), capacity * sizeof(uint64_t)));
-  SIM_TRY(hipMalloc(reinterpret_cast<void **>(&d_pool_count_), 64));
-  SIM_TRY(hipMalloc(reinterpret_cast<void **>(&d_pool_bits_), capacity * std::max<size_t>(k_, 1)));
-  SIM_TRY(hipMalloc(reinterpret_cast<void **>(&d_pool_its_), capacity * sizeof(int32_t)));
+  d_pool_count_ = DeviceBuffer();  // (its size is fixed: allocated anew with the others, as it always was)
+  SIM_TRY(d_pool_llrs_.ensure(capacity * n_tx_ * sizeof(float)));
+  SIM_TRY(d_pool_frames_.ensure(capacity * sizeof(uint64_t)));
+  SIM_TRY(d_pool_count_.ensure(64));
+  SIM_TRY(d_pool_bits_.ensure(capacity * std::max<size_t>(k_, 1)));
+  SIM_TRY(d_pool_its_.ensure(capacity * sizeof(int32_t)));
   pool_cap_ = capacity;
   return 0;
 }
@@ -146,16 +122,18 @@ int Simulator::flush_pool(uint32_t count, uint64_t seed, uint32_t max_iterations
   // large for that is decoded in the chunks' group size, so that the decoder keeps the workspace it has -- a group
   // sized by the pool would free and re-allocate gigabytes before and after every flush)
   dec_->set_min_group(chunk_group);
-  const int drc = dec_->decode_device(d_pool_llrs_, false, count, max_iterations, d_pool_bits_, k_, d_pool_its_, nullptr, nullptr);
+  const int drc = dec_->decode_device(d_pool_llrs_.get(), false, count, max_iterations, d_pool_bits_.get<uint8_t>(), k_,
+                                      d_pool_its_.get<int32_t>(), nullptr, nullptr);
   dec_->set_min_group(0);
   if (drc) {
     error_ = dec_->last_error();
     return drc;
   }
   gen::count_errors_kernel<<<(count * 64 + 255) / 256, 256, 0, stream_>>>(
-      d_pool_bits_, static_cast<uint32_t>(k_), d_pool_its_, d_messages_, static_cast<uint32_t>(k_), pool_, seed, 0, count,
-      max_iterations, bch_max_errors, d_counters_, d_pool_frames_, nullptr, 0);
-  SIM_TRY(hipMemsetAsync(d_pool_count_, 0, sizeof(uint32_t), stream_));
+      d_pool_bits_.get<uint8_t>(), static_cast<uint32_t>(k_), d_pool_its_.get<int32_t>(), d_messages_.get<uint8_t>(),
+      static_cast<uint32_t>(k_), pool_, seed, 0, count, max_iterations, bch_max_errors, d_counters_.get<unsigned long long>(),
+      d_pool_frames_.get<uint64_t>(), nullptr, 0);
+  SIM_TRY(hipMemsetAsync(d_pool_count_.get(), 0, sizeof(uint32_t), stream_));
   pooled_frames_ += count;
   return 0;
 }
@@ -198,12 +176,12 @@ void Simulator::noise_params(double ebn0_db, float *sigma, float *scale) const {
 // frames [first_frame, first_frame + frames) -> d_llrs_ (codeword order, ready for the decoder)
 void Simulator::launch_generator(double ebn0_db, uint64_t seed, uint64_t first_frame, uint32_t frames, float *dst) {
   const uint32_t n_tx = static_cast<uint32_t>(n_tx_);
-  if (dst == nullptr) dst = d_llrs_;
+  if (dst == nullptr) dst = d_llrs_.get<float>();
   if (bits_per_symbol_ == 3) {
     const double s = noise_sigma(ebn0_db);
     const uint64_t threads = uint64_t(frames) * (n_tx / 3);
     gen::psk8_llr_kernel<<<static_cast<uint32_t>((threads + 255) / 256), 256, 0, stream_>>>(
-        d_tx_, pool_, n_tx, static_cast<int32_t>(interleaving_), seed, first_frame, frames, s, 1.0 / (s * s), dst);
+        d_tx_.get<uint8_t>(), pool_, n_tx, static_cast<int32_t>(interleaving_), seed, first_frame, frames, s, 1.0 / (s * s), dst);
     return;
   }
   // BPSK: one LLR per bit, so interleaving followed by deinterleaving changes nothing but which
@@ -212,7 +190,7 @@ void Simulator::launch_generator(double ebn0_db, uint64_t seed, uint64_t first_f
   noise_params(ebn0_db, &sigma, &scale);
   const uint64_t threads = uint64_t(frames) * ((n_tx + 1) / 2);
   gen::awgn_llr_kernel<<<static_cast<uint32_t>((threads + 255) / 256), 256, 0, stream_>>>(
-      d_tx_, pool_, n_tx, seed, first_frame, frames, sigma, scale, dst);
+      d_tx_.get<uint8_t>(), pool_, n_tx, seed, first_frame, frames, sigma, scale, dst);
 }
 
 int Simulator::run(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations,
@@ -231,14 +209,14 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
   // a chunk is one group of the decoder -- 4096 frames, more for small graphs
   const size_t chunk = std::min<size_t>(frames, std::max<size_t>(dec_->preferred_group(frames), 4096));
   if (int rc = ensure(chunk, chunk)) return rc;
-  SIM_TRY(hipMemsetAsync(d_counters_, 0, 9 * sizeof(unsigned long long), stream_));
+  SIM_TRY(hipMemsetAsync(d_counters_.get(), 0, 9 * sizeof(unsigned long long), stream_));
   // straggler pooling (simulator.h): from the second chunk on, when the frames seen so far converge well within the budget
   const bool track = pooling_ && max_iterations >= 24;
   const bool can_pool = track && (frames > chunk || (budget_valid_ && budget_ebn0_ == ebn0_db && budget_max_it_ == max_iterations));
   pooled_frames_ = 0;
   if (can_pool) {
     if (int rc = ensure_pool(2 * chunk)) return rc;
-    SIM_TRY(hipMemsetAsync(d_pool_count_, 0, sizeof(uint32_t), stream_));
+    SIM_TRY(hipMemsetAsync(d_pool_count_.get(), 0, sizeof(uint32_t), stream_));
   }
   // (a sweep calls run() again and again at one Eb/N0: the budget the previous call arrived at carries over)
   const bool same_point = can_pool && budget_valid_ && budget_ebn0_ == ebn0_db && budget_max_it_ == max_iterations;
@@ -265,25 +243,27 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
   for (size_t f0 = 0; f0 < frames; f0 += chunk) {
     const uint32_t nf = static_cast<uint32_t>(std::min(chunk, frames - f0));
     launch_generator(ebn0_db, seed, first_frame + f0, nf);
-    if (int rc = dec_->decode_device(d_llrs_, false, nf, budget, d_bits_, k_, d_its_, nullptr, stream_)) {
+    if (int rc = dec_->decode_device(d_llrs_.get(), false, nf, budget, d_bits_.get<uint8_t>(), k_, d_its_.get<int32_t>(), nullptr, stream_)) {
       error_ = dec_->last_error();
       return rc;
     }
     const bool reduced = budget < max_iterations;
     if (reduced)
       gen::straggler_collect_kernel<<<(nf * 64 + 255) / 256, 256, 0, stream_>>>(
-          d_its_, nf, first_frame + f0, d_llrs_, static_cast<uint32_t>(n_tx_), d_pool_llrs_, d_pool_frames_, d_pool_count_,
+          d_its_.get<int32_t>(), nf, first_frame + f0, d_llrs_.get<float>(), static_cast<uint32_t>(n_tx_), d_pool_llrs_.get<float>(),
+          d_pool_frames_.get<uint64_t>(), d_pool_count_.get<uint32_t>(),
           static_cast<uint32_t>(pool_cap_));
     gen::count_errors_kernel<<<(nf * 64 + 255) / 256, 256, 0, stream_>>>(
-        d_bits_, static_cast<uint32_t>(k_), d_its_, d_messages_, static_cast<uint32_t>(k_), pool_, seed,
-        first_frame + f0, nf, max_iterations, bch_max_errors, d_counters_, nullptr, nullptr, reduced ? 1 : 0);
+        d_bits_.get<uint8_t>(), static_cast<uint32_t>(k_), d_its_.get<int32_t>(), d_messages_.get<uint8_t>(), static_cast<uint32_t>(k_),
+        pool_, seed, first_frame + f0, nf, max_iterations, bch_max_errors, d_counters_.get<unsigned long long>(), nullptr, nullptr,
+        reduced ? 1 : 0);
     if (can_pool) {
       // what the frames of this call have needed so far decides the next chunk's budget (a call that cannot pool -- a
       // single chunk at a new point -- reads the counters once, at the end: no synchronisation between its launches)
       unsigned long long c[9];
       uint32_t pooled = 0;
-      SIM_TRY(hipMemcpyAsync(c, d_counters_, sizeof(c), hipMemcpyDeviceToHost, stream_));
-      SIM_TRY(hipMemcpyAsync(&pooled, d_pool_count_, sizeof(pooled), hipMemcpyDeviceToHost, stream_));
+      SIM_TRY(hipMemcpyAsync(c, d_counters_.get(), sizeof(c), hipMemcpyDeviceToHost, stream_));
+      SIM_TRY(hipMemcpyAsync(&pooled, d_pool_count_.get(), sizeof(pooled), hipMemcpyDeviceToHost, stream_));
       SIM_TRY(hipStreamSynchronize(stream_));
       if (pooled > pool_cap_) {
         fail("straggler pool overflow");
@@ -305,7 +285,7 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
   }
   if (can_pool) {
     uint32_t pooled = 0;
-    SIM_TRY(hipMemcpyAsync(&pooled, d_pool_count_, sizeof(pooled), hipMemcpyDeviceToHost, stream_));
+    SIM_TRY(hipMemcpyAsync(&pooled, d_pool_count_.get(), sizeof(pooled), hipMemcpyDeviceToHost, stream_));
     SIM_TRY(hipStreamSynchronize(stream_));
     if (pooled > pool_cap_) {
       fail("straggler pool overflow");
@@ -315,7 +295,7 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
       if (int rc = flush_pool(pooled, seed, max_iterations, bch_max_errors, chunk_group)) return rc;
   }
   unsigned long long host[9];
-  SIM_TRY(hipMemcpyAsync(host, d_counters_, sizeof(host), hipMemcpyDeviceToHost, stream_));
+  SIM_TRY(hipMemcpyAsync(host, d_counters_.get(), sizeof(host), hipMemcpyDeviceToHost, stream_));
   SIM_TRY(hipStreamSynchronize(stream_));
   SIM_TRY(hipGetLastError());
   if (track && !can_pool) {  // every frame of this call ran the full budget: what they needed is the next call's estimate
@@ -342,7 +322,7 @@ int Simulator::generate(double ebn0_db, uint64_t seed, uint64_t first_frame, siz
   } else {
     if (int rc = ensure(0, frames)) return rc;
     launch_generator(ebn0_db, seed, first_frame, static_cast<uint32_t>(frames));
-    SIM_TRY(hipMemcpyAsync(llrs, d_llrs_, frames * n_tx_ * sizeof(float), hipMemcpyDefault, stream_));
+    SIM_TRY(hipMemcpyAsync(llrs, d_llrs_.get(), frames * n_tx_ * sizeof(float), hipMemcpyDefault, stream_));
   }
   SIM_TRY(hipStreamSynchronize(stream_));
   SIM_TRY(hipGetLastError());

@@ -7,9 +7,13 @@
 //   * a kernel launch is a no-op -- except that a launch carrying a decoder State with a progress word publishes
 //     (epoch, iteration, codewords running) there as the real kernels do, with "running" scripted by HIP_STUB_DONE_AT
 //     (0 from that iteration on: the host's early-termination paths run);
-//   * HIP_STUB_FAIL=<function>:<n> makes the n-th call of that function return hipErrorUnknown;
+//   * HIP_STUB_FAIL=<function>:<n> makes the n-th call of that function return hipErrorUnknown (the functions with a
+//     STUB_FAIL line below);
 //   * HIP_STUB_TRACE=<file> appends one line per kernel launch, in the host's enqueue order: the stream's ordinal in
-//     creation order, grid, block, dynamic LDS bytes and the kernel's demangled name (hip_stub_trace_note adds a "# ..." line).
+//     creation order, grid, block, dynamic LDS bytes and the kernel's demangled name (hip_stub_trace_note adds a "# ..."
+//     line) -- and "malloc <bytes>" per hipMalloc, "hostmalloc <bytes>" per hipHostMalloc, "h2d <bytes> <FNV-1a of the
+//     bytes, 64 bits>" per synchronous host-to-device hipMemcpy: what the library allocates and the tables it uploads;
+//   * hip_stub_live counts what has been created and not yet given back: device and pinned allocations, events, streams.
 // Built with the same host-only clang mode as the library objects it is linked with (it needs dev::State).
 #include <cxxabi.h>
 #include <hip/hip_runtime_api.h>
@@ -122,6 +126,9 @@ struct LaunchConfig {
 thread_local LaunchConfig t_config;
 
 std::atomic<uint64_t> g_launches{0};
+// live device allocations, pinned allocations, events and streams (the stub's own default stream is not counted)
+std::atomic<long long> g_live[4];
+enum { kLiveDevice = 0, kLivePinned = 1, kLiveEvents = 2, kLiveStreams = 3 };
 
 // HIP_STUB_TRACE: one line at a time, appended by whichever host thread makes the launch
 void trace_line(const std::string &line) {
@@ -191,20 +198,28 @@ std::atomic<int> g_last_error{0};  // a failed kernel launch is reported by the 
 hipError_t hipGetLastError(void) { return static_cast<hipError_t>(g_last_error.exchange(0)); }
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "injected by the HIP stub"; }
 
+static hipError_t allocate(void **p, size_t bytes, const char *what, int live) {
+  if (std::getenv("HIP_STUB_TRACE")) trace_line(std::string(what) + " " + std::to_string(bytes));
+  *p = std::calloc(std::max<size_t>(bytes, 1), 1);
+  if (!*p) return hipErrorOutOfMemory;
+  g_live[live]++;
+  return hipSuccess;
+}
 hipError_t hipMalloc(void **p, size_t bytes) {
   STUB_FAIL("hipMalloc");
-  *p = std::calloc(std::max<size_t>(bytes, 1), 1);
-  return *p ? hipSuccess : hipErrorOutOfMemory;
+  return allocate(p, bytes, "malloc", kLiveDevice);
 }
 hipError_t hipFree(void *p) {
+  if (p) g_live[kLiveDevice]--;
   std::free(p);
   return hipSuccess;
 }
 hipError_t hipHostMalloc(void **p, size_t bytes, unsigned int) {
-  *p = std::calloc(std::max<size_t>(bytes, 1), 1);
-  return *p ? hipSuccess : hipErrorOutOfMemory;
+  STUB_FAIL("hipHostMalloc");
+  return allocate(p, bytes, "hostmalloc", kLivePinned);
 }
 hipError_t hipHostFree(void *p) {
+  if (p) g_live[kLivePinned]--;
   std::free(p);
   return hipSuccess;
 }
@@ -220,10 +235,13 @@ hipError_t hipHostGetDevicePointer(void **dev, void *host, unsigned int) {
 }
 
 hipError_t hipStreamCreateWithFlags(hipStream_t *s, unsigned int) {
+  STUB_FAIL("hipStreamCreateWithFlags");
   *s = reinterpret_cast<hipStream_t>(new Stream());
+  g_live[kLiveStreams]++;
   return hipSuccess;
 }
 hipError_t hipStreamDestroy(hipStream_t s) {
+  g_live[kLiveStreams]--;
   delete reinterpret_cast<Stream *>(s);
   return hipSuccess;
 }
@@ -235,11 +253,14 @@ hipError_t hipStreamSynchronize(hipStream_t s) {
 hipError_t hipStreamQuery(hipStream_t s) { return as_stream(s)->busy() ? hipErrorNotReady : hipSuccess; }
 
 hipError_t hipEventCreateWithFlags(hipEvent_t *e, unsigned int) {
+  STUB_FAIL("hipEventCreateWithFlags");
   *e = reinterpret_cast<hipEvent_t>(new Event());
+  g_live[kLiveEvents]++;
   return hipSuccess;
 }
 hipError_t hipEventCreate(hipEvent_t *e) { return hipEventCreateWithFlags(e, 0); }
 hipError_t hipEventDestroy(hipEvent_t e) {
+  g_live[kLiveEvents]--;
   delete reinterpret_cast<Event *>(e);
   return hipSuccess;
 }
@@ -290,8 +311,16 @@ hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKin
   as_stream(s)->push([=] { std::memcpy(dst, src, bytes); });
   return hipSuccess;
 }
-hipError_t hipMemcpy(void *dst, const void *src, size_t bytes, hipMemcpyKind) {
+hipError_t hipMemcpy(void *dst, const void *src, size_t bytes, hipMemcpyKind kind) {
+  STUB_FAIL("hipMemcpy");
   default_stream()->sync();
+  if (kind == hipMemcpyHostToDevice && std::getenv("HIP_STUB_TRACE")) {
+    uint64_t h = 0xcbf29ce484222325ull;  // FNV-1a
+    for (size_t i = 0; i < bytes; i++) h = (h ^ static_cast<const unsigned char *>(src)[i]) * 0x100000001b3ull;
+    char line[64];
+    std::snprintf(line, sizeof(line), "h2d %zu %016llx", bytes, static_cast<unsigned long long>(h));
+    trace_line(line);
+  }
   std::memcpy(dst, src, bytes);
   return hipSuccess;
 }
@@ -359,6 +388,9 @@ hipError_t hipLaunchKernel(const void *fun, dim3 grid, dim3 block, void **args, 
 }
 
 unsigned long long hip_stub_launches(void) { return g_launches.load(); }
+void hip_stub_live(long long counts[4]) {
+  for (int i = 0; i < 4; i++) counts[i] = g_live[i].load();
+}
 void hip_stub_trace_note(const char *text) { trace_line(std::string("# ") + text); }
 
 }  // extern "C"

@@ -8,7 +8,10 @@
 // handles driven by two threads must not interfere either.
 // `tsan_driver trace` (with HIP_STUB_TRACE=<file>) instead walks a fixed list of (code, implementation, options) through
 // every launch choice the host makes from run-time values, with the host's enqueue order a function of the inputs alone
-// ("poll" 0, "lane_threads" 0): the stub writes the launches down, test_launch_trace_* reads them.
+// ("poll" 0, "lane_threads" 0): the stub writes the launches down, test_launch_trace_* reads them.  The same file lists
+// every allocation and every uploaded table (size and hash), so two builds of the library can be compared line by line.
+// Both modes end with the stub's count of live device allocations, pinned allocations, events and streams: all zero once
+// the last handle is gone, also after an injected failure.
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
@@ -22,6 +25,14 @@
 
 extern "C" unsigned long long hip_stub_launches(void);
 extern "C" void hip_stub_trace_note(const char *text);
+extern "C" void hip_stub_live(long long counts[4]);
+
+static int leaked() {
+  long long c[4];
+  hip_stub_live(c);
+  std::printf("live after the last handle: device %lld pinned %lld events %lld streams %lld\n", c[0], c[1], c[2], c[3]);
+  return (c[0] || c[1] || c[2] || c[3]) ? 1 : 0;
+}
 
 static std::string alist_of(const char *spec) {
   const size_t need = ldpc_toolbox_code_alist(spec, nullptr, 0);
@@ -85,6 +96,33 @@ static int drive(const char *spec, const char *impl, size_t batch, int lanes, in
   return bad;
 }
 
+// The single-launch small-batch paths (four frames; under the stub their kernels do nothing and the error word stays zero):
+// each call twice, so that a first call that failed while it uploaded its tables is followed by one that uploads them again.
+static int drive_small_batch(const char *spec, const char *impl, int expect_error) {
+  const std::string alist = alist_of(spec);
+  void *dec = ldpc_toolbox_decoder_ctor_alist_string(alist.c_str(), impl, "");
+  if (!dec) {
+    std::fprintf(stderr, "ctor failed: %s\n", ldpc_toolbox_last_error());
+    return 1;
+  }
+  const size_t n = size_t(get(dec, "n")), k = size_t(get(dec, "k")), batch = 4;
+  std::vector<float> llrs(batch * n, 1.0f), post(batch * n);
+  std::vector<uint8_t> out(batch * k);
+  std::vector<int32_t> its(batch);
+  int bad = 0;
+  for (int call = 0; call < 4; call++) {
+    const int rc = call < 2 ? ldpc_toolbox_decoder_decode_batch_f32(dec, out.data(), k, llrs.data(), n, batch, 12, its.data(), post.data())
+                            : ldpc_toolbox_decoder_decode_batch_f32_device(dec, out.data(), k, llrs.data(), n, batch, 12, its.data(), post.data(), nullptr);
+    if (rc < -1) g_errors++;
+    if (rc == -1 || rc > 0 || (rc != 0 && !expect_error)) {
+      std::fprintf(stderr, "%s %s small batch, call %d: rc %d (%s)\n", spec, impl, call, rc, ldpc_toolbox_last_error());
+      bad++;
+    }
+  }
+  ldpc_toolbox_decoder_dtor(dec);
+  return bad;
+}
+
 // ---- trace mode ------------------------------------------------------------------------------------------------------
 
 // a 14 x n matrix with eight long rows of base .. base + 3 * spread edges and six shorter ones, every column in at least one
@@ -112,9 +150,12 @@ struct TraceCase {
   const char *spec, *impl;
   std::vector<std::vector<std::pair<const char *, int>>> option_sets;  // each on top of the defaults
   int llrs_f64 = -1;  // the caller's LLRs: -1 = in the implementation's precision
+  size_t small_batch = 0;  // not 0: a call of this many frames with the single-launch small-batch paths left on
 };
 
 // 300 frames in groups of 256 (one full group, one ragged), 3 iterations (a first one and later ones), host and device entry
+// (small_batch: that many frames through latency.hip.h / latency_edge.hip.h -- under the stub their kernels do nothing and
+// the error word stays zero, so the calls stage, launch once and copy back)
 static int trace_case(const TraceCase &tc) {
   const std::string alist = std::strcmp(tc.spec, "long-rows") == 0   ? synthetic_alist(1500, 330, 30)
                             : std::strcmp(tc.spec, "wide-rows") == 0 ? synthetic_alist(500, 40, 3)
@@ -129,7 +170,8 @@ static int trace_case(const TraceCase &tc) {
     }
     std::string note = std::string(tc.impl) + " " + tc.spec + (f64 ? " llrs=f64" : " llrs=f32");
     for (const auto &kv : {std::pair<const char *, int>{"latency", 0}, {"latency_edge", 0}, {"group_size", 256}, {"poll", 0}, {"lane_threads", 0}})
-      ldpc_toolbox_decoder_set(dec, kv.first, kv.second);
+      if (!tc.small_batch || std::strncmp(kv.first, "latency", 7) != 0) ldpc_toolbox_decoder_set(dec, kv.first, kv.second);
+    if (tc.small_batch) note += " small-batch";
     for (const auto &kv : options) {
       if (ldpc_toolbox_decoder_set(dec, kv.first, kv.second) != 0) {
         std::fprintf(stderr, "%s: option %s refused\n", tc.impl, kv.first);
@@ -138,7 +180,7 @@ static int trace_case(const TraceCase &tc) {
       note += std::string(" ") + kv.first + "=" + std::to_string(kv.second);
     }
     hip_stub_trace_note(note.c_str());
-    const size_t n = size_t(get(dec, "n")), k = size_t(get(dec, "k")), batch = 300;
+    const size_t n = size_t(get(dec, "n")), k = size_t(get(dec, "k")), batch = tc.small_batch ? tc.small_batch : 300;
     std::vector<uint8_t> out(batch * k);
     std::vector<int32_t> its(batch);
     int rc_host, rc_device;
@@ -199,6 +241,10 @@ static int trace_main() {
       {"nr5g:1:8", "HLAminstari8", {{}, {{"hl_reg", 0}}, {{"serial_levels", 0}}}},
       {"nr5g:1:8", "Minsumi8Norm", {{}}},
       {"nr5g:1:8", "HLMinsumi8Offset", {{}, {{"hl_reg", 0}}, {{"serial_levels", 0}}}},
+      // the small-batch paths: LatencyPath (flooding Minsumf32), EdgeLatencyPath layered and flooding
+      {"dvbs2:R1_2short", "Minsumf32", {{}}, -1, 4},
+      {"nr5g:1:8", "HLTanhf32", {{}}, -1, 4},
+      {"ar4ja:1/2:1024", "Tanhf32", {{}}, -1, 4},
   };
   int bad = 0;
   size_t scenarios = 0;
@@ -206,6 +252,7 @@ static int trace_main() {
     bad += trace_case(tc);
     scenarios += tc.option_sets.size();
   }
+  bad += leaked();
   std::printf("trace: %s (%zu scenarios, %llu kernel launches through the stub)\n", bad ? "FAILED" : "ok", scenarios, hip_stub_launches());
   return bad ? 1 : 0;
 }
@@ -225,10 +272,13 @@ int main(int argc, char **argv) {
   a.join();
   b.join();
   bad += rc_a + rc_b;
+  bad += drive_small_batch("dvbs2:R1_2short", "Minsumf32", expect_error);  // latency.hip.h
+  bad += drive_small_batch("nr5g:1:8", "HLTanhf32", expect_error);         // latency_edge.hip.h
   if (expect_error && g_errors.load() == 0) {
     std::fprintf(stderr, "the injected failure never surfaced\n");
     bad++;
   }
+  bad += leaked();
   std::printf("tsan driver: %s (%llu kernel launches through the stub)\n", bad ? "FAILED" : "ok", hip_stub_launches());
   return bad ? 1 : 0;
 }
