@@ -282,6 +282,53 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value);
  * returns 0, or -1 (unknown key / unusable value, message via ldpc_toolbox_last_error). */
 int32_t ldpc_toolbox_sim_set(void *sim, const char *key, int64_t value);
 
+/* ===================================================================================
+ * PART 4 -- batched soft demapper on the GPU (reference: trait Demodulator, src/simulation/modulation.rs:109-281,
+ * and the LLR deinterleaver, src/simulation/interleaving.rs:65-86; one frame per call there)
+ * =================================================================================== */
+
+/* A demodulator handle turns [batch][symbols_len] received symbols into [batch][llrs_len] channel LLRs in codeword
+ * order (deinterleaved): exactly the `llrs` of ldpc_toolbox_decoder_decode_batch_f32_device / _f64_device, so the two
+ * calls chain on one stream without a host round trip.  A positive LLR means bit 0.
+ *
+ * modulation: "BPSK" (real symbols, llr = -2 / sigma^2 * x), "QPSK" or "8PSK" (the DVB-S2 mappings; symbols are
+ * (re, im) pairs).  The _table constructor takes any constellation of m = bits_per_symbol (1..5) bits: 2^m (re, im)
+ * doubles, point p_V at index V = sum_j b_j << (m-1-j) (b0, the first bit of the symbol, most significant).
+ * With scale = 1 / sigma^2:   d_V = (re * scale) * p_V.re + (im * scale) * p_V.im   [ - (0.5 * scale) * |p_V|^2
+ * when energy_term != 0: needed for points of unequal energy ],
+ *   llr_j = F({d_V : bit j of V = 0}) - F({d_V : bit j of V = 1}),  F a left fold over ascending V with the step
+ *   max*(a, b) = max(a, b) + log1p(exp(-|a - b|))  (exact; with "8PSK" the reference's Psk8Demodulator bit for bit), or
+ *   max(a, b) with a NaN operand ignored, -0 < +0  (max_log != 0: IEEE 754-2019 maximumNumber).
+ * The constructors need no GPU (`device` is used by the first run; -1 = LDPC_TOOLBOX_DEVICE, default 0).  NULL for an
+ * unknown name, bits_per_symbol outside 1..5, or a point that is not finite (message via ldpc_toolbox_last_error). */
+void *ldpc_toolbox_demod_ctor(const char *modulation, int32_t device);
+void *ldpc_toolbox_demod_ctor_table(const double *points_re_im, uint32_t bits_per_symbol, int32_t energy_term,
+                                    int32_t device);
+void ldpc_toolbox_demod_dtor(void *demod);
+/* symbols [batch][symbols_len] -- (re, im) pairs, reals for "BPSK" -- to llrs [batch][llrs_len], host pointers, staged
+ * through device buffers of the handle.  _f64: all arithmetic in double.  _f32: exact = symbols widened to double, the
+ * double arithmetic, each LLR rounded once; max_log = the same formulas in float throughout.
+ * interleaving: signed columns of the DVB-S2 bit interleaver as in ldpc_toolbox_sim_set (0 = none, negative = rows read
+ * backwards); the LLR of interleaved position i = m * symbol + j is written to its codeword position.
+ * llrs_len must be bits_per_symbol * symbols_len and a multiple of |interleaving|, noise_sigma finite and > 0: else
+ * LDPC_TOOLBOX_ERR_ARGUMENT, before the GPU is touched and with nothing written.  Without a GPU: LDPC_TOOLBOX_ERR_DEVICE
+ * (there is no CPU path).  batch == 0 returns 0.  One call at a time per handle.  returns 0 or an LDPC_TOOLBOX_ERR_* code. */
+int32_t ldpc_toolbox_demod_run_f32(void *demod, float *llrs, size_t llrs_len, const float *symbols, size_t symbols_len,
+                                   size_t batch, double noise_sigma, int32_t interleaving, int32_t max_log);
+int32_t ldpc_toolbox_demod_run_f64(void *demod, double *llrs, size_t llrs_len, const double *symbols, size_t symbols_len,
+                                   size_t batch, double noise_sigma, int32_t interleaving, int32_t max_log);
+/* The same on device pointers.  hip_stream as in the decode entries: a stream = enqueue and return; NULL = the handle's
+ * own stream, ordered after what the legacy default stream holds at the call, synchronised on return. */
+int32_t ldpc_toolbox_demod_run_f32_device(void *demod, float *llrs, size_t llrs_len, const float *symbols,
+                                          size_t symbols_len, size_t batch, double noise_sigma, int32_t interleaving,
+                                          int32_t max_log, void *hip_stream);
+int32_t ldpc_toolbox_demod_run_f64_device(void *demod, double *llrs, size_t llrs_len, const double *symbols,
+                                          size_t symbols_len, size_t batch, double noise_sigma, int32_t interleaving,
+                                          int32_t max_log, void *hip_stream);
+/* key: "bits_per_symbol", "points", "energy_term", "device" (-1 until the first run made the device state).
+ * returns 0, or -1 for an unknown key. */
+int32_t ldpc_toolbox_demod_get(void *demod, const char *key, int64_t *value);
+
 /* Standard-code generator (what the reference's `dvbs2` / `5g` / `ccsds` / `ccsds-c2` CLI
  * sub-commands print, src/cli/dvbs2.rs:91, src/cli/nr5g.rs:46, src/cli/ccsds.rs:70): writes the
  * padded alist text of `spec` ("dvbs2:R1_2", "nr5g:1:384", "ar4ja:1/2:1024", "c2") into

@@ -45,6 +45,14 @@ SYMBOLS = [
     "ldpc_toolbox_sim_pool",
     "ldpc_toolbox_sim_get",
     "ldpc_toolbox_sim_set",
+    "ldpc_toolbox_demod_ctor",
+    "ldpc_toolbox_demod_ctor_table",
+    "ldpc_toolbox_demod_dtor",
+    "ldpc_toolbox_demod_run_f32",
+    "ldpc_toolbox_demod_run_f64",
+    "ldpc_toolbox_demod_run_f32_device",
+    "ldpc_toolbox_demod_run_f64_device",
+    "ldpc_toolbox_demod_get",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
     "ldpc_toolbox_device_count",
@@ -180,6 +188,21 @@ def lib():
     L.ldpc_toolbox_sim_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
     L.ldpc_toolbox_sim_set.restype = i32
     L.ldpc_toolbox_sim_set.argtypes = [vp, cp, C.c_int64]
+    L.ldpc_toolbox_demod_ctor.restype = vp
+    L.ldpc_toolbox_demod_ctor.argtypes = [cp, i32]
+    L.ldpc_toolbox_demod_ctor_table.restype = vp
+    L.ldpc_toolbox_demod_ctor_table.argtypes = [vp, u32, i32, i32]
+    L.ldpc_toolbox_demod_dtor.restype = None
+    L.ldpc_toolbox_demod_dtor.argtypes = [vp]
+    for name in ("f32", "f64"):
+        f = getattr(L, "ldpc_toolbox_demod_run_" + name)
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, C.c_double, i32, i32]
+        f = getattr(L, "ldpc_toolbox_demod_run_" + name + "_device")
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, C.c_double, i32, i32, vp]
+    L.ldpc_toolbox_demod_get.restype = i32
+    L.ldpc_toolbox_demod_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
     L.ldpc_toolbox_code_alist.restype = sz
     L.ldpc_toolbox_code_alist.argtypes = [cp, vp, sz]
     L.ldpc_toolbox_alist_normalize.restype = sz

@@ -14,6 +14,7 @@
 #include <vector>
 
 #include "codes.h"
+#include "demodulator.h"
 #include "device_decoder.h"
 #include "device_encoder.h"
 #include "encoder.h"
@@ -51,6 +52,13 @@ struct EncoderHandle {
   std::vector<uint8_t> scratch;
   // the batched entries' device state: made by the ..._on_device constructor, or at the first batched call
   std::unique_ptr<ldpc::DeviceEncoder> dev;
+};
+
+struct DemodHandle {
+  ldpc::Constellation c;
+  int device = 0;
+  // the device state: made at the first run
+  std::unique_ptr<ldpc::DeviceDemodulator> dev;
 };
 
 // a device index: decimal digits only (no sign, no trailing characters)
@@ -186,6 +194,50 @@ int32_t encode_batch(void *encoder, uint8_t *output, size_t output_len, const ui
   if (!h->dev && !make_device_encoder(h, default_device())) return LDPC_TOOLBOX_ERR_DEVICE;
   const int rc = on_device ? h->dev->encode_device(input, output, batch, static_cast<hipStream_t>(stream))
                            : h->dev->encode_host(input, output, batch);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+void *make_demod(const ldpc::Constellation &c, int32_t device) {
+  auto h = std::make_unique<DemodHandle>();
+  h->c = c;
+  h->device = device < 0 ? default_device() : device;
+  return h.release();
+}
+
+int32_t demod_run(void *demod, void *llrs, size_t llrs_len, const void *symbols, size_t symbols_len, size_t batch, bool f64,
+                  double sigma, int32_t interleaving, int32_t max_log, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<DemodHandle *>(demod);
+  if (!h) {
+    set_error("null demodulator handle");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (const char *why = ldpc::demod_argument_error(h->c, llrs_len, symbols_len, sigma, interleaving)) {
+    set_error(why);
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (batch == 0 || llrs_len == 0) return 0;
+  if (!symbols || !llrs) {
+    set_error("null symbol or LLR buffer");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (!h->dev) {
+    if (h->device < 0) {
+      set_error("LDPC_TOOLBOX_DEVICE is not a decimal GPU index");
+      return LDPC_TOOLBOX_ERR_DEVICE;
+    }
+    std::string err;
+    h->dev.reset(ldpc::DeviceDemodulator::create(h->c, h->device, &err));
+    if (!h->dev) {
+      set_error(err);
+      return LDPC_TOOLBOX_ERR_DEVICE;
+    }
+  }
+  const int rc = on_device ? h->dev->run_device(symbols, llrs, f64, symbols_len, llrs_len, batch, sigma, interleaving,
+                                                max_log != 0, static_cast<hipStream_t>(stream))
+                           : h->dev->run_host(symbols, llrs, f64, symbols_len, llrs_len, batch, sigma, interleaving, max_log != 0);
   if (rc == 0) return 0;
   set_error(h->dev->last_error());
   return LDPC_TOOLBOX_ERR_DEVICE;
@@ -639,6 +691,71 @@ int32_t ldpc_toolbox_sim_set(void *sim, const char *key, int64_t value) {
     return ok ? 0 : -1;
   }
   return s->decoder()->set_option(k, value) ? 0 : -1;
+}
+
+// ---- PART 4: batched soft demapper -----------------------------------------------------------------
+
+void *ldpc_toolbox_demod_ctor(const char *modulation, int32_t device) {
+  g_last_error.clear();
+  ldpc::Constellation c;
+  if (!modulation || !ldpc::named_constellation(modulation, &c)) {
+    set_error("unknown modulation (expected BPSK, QPSK or 8PSK; other constellations through ldpc_toolbox_demod_ctor_table)");
+    return nullptr;
+  }
+  return make_demod(c, device);
+}
+
+void *ldpc_toolbox_demod_ctor_table(const double *points_re_im, uint32_t bits_per_symbol, int32_t energy_term,
+                                    int32_t device) {
+  g_last_error.clear();
+  ldpc::Constellation c;
+  std::string err;
+  if (!ldpc::table_constellation(points_re_im, bits_per_symbol, energy_term != 0, &c, &err)) {
+    set_error(err);
+    return nullptr;
+  }
+  return make_demod(c, device);
+}
+
+void ldpc_toolbox_demod_dtor(void *demod) { delete static_cast<DemodHandle *>(demod); }
+
+int32_t ldpc_toolbox_demod_run_f32(void *demod, float *llrs, size_t llrs_len, const float *symbols, size_t symbols_len,
+                                   size_t batch, double noise_sigma, int32_t interleaving, int32_t max_log) {
+  return demod_run(demod, llrs, llrs_len, symbols, symbols_len, batch, false, noise_sigma, interleaving, max_log, false, nullptr);
+}
+
+int32_t ldpc_toolbox_demod_run_f64(void *demod, double *llrs, size_t llrs_len, const double *symbols, size_t symbols_len,
+                                   size_t batch, double noise_sigma, int32_t interleaving, int32_t max_log) {
+  return demod_run(demod, llrs, llrs_len, symbols, symbols_len, batch, true, noise_sigma, interleaving, max_log, false, nullptr);
+}
+
+int32_t ldpc_toolbox_demod_run_f32_device(void *demod, float *llrs, size_t llrs_len, const float *symbols,
+                                          size_t symbols_len, size_t batch, double noise_sigma, int32_t interleaving,
+                                          int32_t max_log, void *hip_stream) {
+  return demod_run(demod, llrs, llrs_len, symbols, symbols_len, batch, false, noise_sigma, interleaving, max_log, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_demod_run_f64_device(void *demod, double *llrs, size_t llrs_len, const double *symbols,
+                                          size_t symbols_len, size_t batch, double noise_sigma, int32_t interleaving,
+                                          int32_t max_log, void *hip_stream) {
+  return demod_run(demod, llrs, llrs_len, symbols, symbols_len, batch, true, noise_sigma, interleaving, max_log, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_demod_get(void *demod, const char *key, int64_t *value) {
+  auto *h = static_cast<DemodHandle *>(demod);
+  if (!h || !key || !value) return -1;
+  const std::string k = key;
+  if (k == "bits_per_symbol")
+    *value = h->c.bits;
+  else if (k == "points")
+    *value = h->c.points();
+  else if (k == "energy_term")
+    *value = h->c.energy ? 1 : 0;
+  else if (k == "device")
+    *value = h->dev ? h->dev->device() : -1;
+  else
+    return -1;
+  return 0;
 }
 
 size_t ldpc_toolbox_code_alist(const char *spec, char *buffer, size_t buffer_len) {

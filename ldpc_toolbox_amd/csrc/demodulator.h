@@ -1,0 +1,143 @@
+// Batched soft demapper on the GPU, for the ldpc_toolbox_demod_* entries of the C ABI: received symbols
+// [batch][symbols_len] -> channel LLRs [batch][llrs_len] in codeword order (deinterleaved), the layout the decoder's
+// decode_batch*_device entries take.  A positive LLR means bit 0 (the reference's convention).
+//
+//   * BPSK (modulation.rs:123-141): real symbols, llr = scale * x with scale = -2 / sigma^2.
+//   * table constellations of m = 1..5 bits, M = 2^m points: point p_V at index V = sum_j b_j << (m-1-j) (b0 the most
+//     significant bit), complex symbols.  With scale = 1 / sigma^2 and sr = re * scale, si = im * scale:
+//       d_V   = sr * p_V.re + si * p_V.im   [ - (0.5 * scale) * e_V  with e_V = |p_V|^2, when the table has an energy term ]
+//       llr_j = F({d_V : bit j of V = 0}) - F({d_V : bit j of V = 1}),  F a left fold over ascending V
+//     with the fold step maxstar (exact: modulation.rs:286-288) or, for max-log, the maximum that ignores a NaN operand
+//     and orders -0 < +0 (IEEE 754-2019 maximumNumber: what v_max_f32 / v_max_f64 compute).  The 8PSK table and the exact
+//     step give Psk8Demodulator::demodulate_symbol (modulation.rs:228-264) bit for bit.
+//   * the LLR of interleaved position i = m * sym + j goes to gen::deinterleaved_position(i, llrs_len, interleaving).
+//
+// f64 entries: all of it in f64.  f32 entries: exact = symbols widened, the f64 arithmetic, one rounding per LLR;
+// max-log = the same formulas in f32, scale and 0.5 * scale * e_V rounded to f32 once.
+// The kernels are in kernels_demod.hip.h; the host side (demodulator.hip.h) is part of the simulator's translation unit.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cmath>
+#include <cstdint>
+#include <string>
+
+#include "hip_owned.h"
+
+namespace ldpc {
+
+constexpr uint32_t kDemodMaxBits = 5, kDemodMaxPoints = 32;
+
+// what a demodulator handle is made from: pure host data
+struct Constellation {
+  uint32_t bits = 0;    // m
+  bool bpsk = false;    // real symbols, no table
+  bool energy = false;  // d_V carries the energy term
+  double re[kDemodMaxPoints] = {}, im[kDemodMaxPoints] = {}, e[kDemodMaxPoints] = {};
+  uint32_t points() const { return 1u << bits; }
+};
+
+// "BPSK" | "QPSK" | "8PSK" (the DVB-S2 mappings); false for any other name
+inline bool named_constellation(const std::string &name, Constellation *c) {
+  const double a = 0.70710678118654757;  // (0.5f64).sqrt()
+  *c = Constellation();
+  if (name == "BPSK") {
+    c->bits = 1;
+    c->bpsk = true;
+    return true;
+  }
+  if (name == "QPSK") {  // 00 at pi/4, 10 at 3 pi/4
+    c->bits = 2;
+    for (uint32_t v = 0; v < 4; v++) {
+      c->re[v] = (v & 2u) ? -a : a;
+      c->im[v] = (v & 1u) ? -a : a;
+    }
+    return true;
+  }
+  if (name == "8PSK") {  // modulation.rs:168-179, indexed by V = b0 b1 b2
+    const double p[8][2] = {{a, a}, {1.0, 0.0}, {-1.0, 0.0}, {-a, -a}, {0.0, 1.0}, {a, -a}, {-a, a}, {0.0, -1.0}};
+    c->bits = 3;
+    for (uint32_t v = 0; v < 8; v++) {
+      c->re[v] = p[v][0];
+      c->im[v] = p[v][1];
+    }
+    return true;
+  }
+  return false;
+}
+
+// 2^bits (re, im) pairs; false (and *err) for bits outside 1..5 or a point that is not finite
+inline bool table_constellation(const double *points_re_im, uint32_t bits, bool energy, Constellation *c, std::string *err) {
+  *c = Constellation();
+  if (bits < 1 || bits > kDemodMaxBits) {
+    *err = "bits_per_symbol must be 1..5";
+    return false;
+  }
+  if (!points_re_im) {
+    *err = "null constellation table";
+    return false;
+  }
+  c->bits = bits;
+  c->energy = energy;
+  for (uint32_t v = 0; v < c->points(); v++) {
+    const double re = points_re_im[2 * v], im = points_re_im[2 * v + 1];
+    if (!std::isfinite(re) || !std::isfinite(im)) {
+      *err = "constellation point is not finite";
+      return false;
+    }
+    c->re[v] = re;
+    c->im[v] = im;
+    c->e[v] = re * re + im * im;
+  }
+  return true;
+}
+
+// What a run call must satisfy before the GPU is touched (nullptr), or why it does not.
+inline const char *demod_argument_error(const Constellation &c, size_t llrs_len, size_t symbols_len, double sigma,
+                                        int32_t interleaving) {
+  if (llrs_len % c.bits != 0 || llrs_len / c.bits != symbols_len) return "llrs_len is not bits_per_symbol * symbols_len";
+  if (llrs_len > 0x7fffffffu) return "frame length out of range for the demodulator";
+  if (!(std::isfinite(sigma) && sigma > 0.0)) return "noise_sigma must be finite and greater than 0";
+  const uint64_t columns = static_cast<uint64_t>(interleaving < 0 ? -static_cast<int64_t>(interleaving) : interleaving);
+  if (columns != 0 && llrs_len % columns != 0) return "interleaving does not divide llrs_len";
+  return nullptr;
+}
+
+class DeviceDemodulator {
+ public:
+  // nullptr (and *err) when there is no usable GPU: there is no CPU path here.
+  static DeviceDemodulator *create(const Constellation &c, int device, std::string *err);
+  ~DeviceDemodulator();
+  DeviceDemodulator(const DeviceDemodulator &) = delete;
+  DeviceDemodulator &operator=(const DeviceDemodulator &) = delete;
+
+  int device() const { return device_; }
+  const std::string &last_error() const { return error_; }
+
+  // symbols [batch][symbols_len] (re, im) pairs -- reals for BPSK -- and llrs [batch][llrs_len], float or double (f64),
+  // the arguments already checked (demod_argument_error).  0, or -2 on a HIP failure.
+  // Device pointers; stream: launch stream (nullptr = the handle's own stream, ordered after everything queued on the
+  // legacy default stream at the time of the call, and synchronised on return).
+  int run_device(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
+                 int32_t interleaving, bool max_log, hipStream_t stream);
+  // Host pointers: staged through device buffers of the handle, synchronous.
+  int run_host(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
+               int32_t interleaving, bool max_log);
+
+ private:
+  DeviceDemodulator() = default;
+  bool fail(const std::string &m, hipError_t e = hipSuccess);
+  template <typename IO>
+  void launch(const IO *symbols, IO *llrs, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
+              int32_t interleaving, bool max_log, hipStream_t s);
+
+  Constellation c_;
+  int device_ = -1;
+  std::string error_;
+  // what the handle owns (hip_owned.h): the stream is declared first and so destroyed last
+  Stream stream_;
+  Event ev_default_;
+  DeviceBuffer d_in_, d_out_;  // the staging buffers of the host entry
+};
+
+}  // namespace ldpc

@@ -1,0 +1,148 @@
+// Host side of the batched soft demapper (demodulator.h): per-call tables and launches.
+// Included by simulator.hip -- the demodulator shares the simulator's translation unit, as the batched encoder does.
+#pragma once
+#include <algorithm>
+#include <cstdio>
+#include <memory>
+
+#include "demodulator.h"
+#include "kernels_demod.hip.h"
+
+namespace ldpc {
+
+bool DeviceDemodulator::fail(const std::string &m, hipError_t e) {
+  error_ = m;
+  if (e != hipSuccess) error_ += std::string(": ") + hipGetErrorString(e);
+  std::fprintf(stderr, "ldpc_toolbox (hip): demodulator: %s\n", error_.c_str());
+  return false;
+}
+
+#define DEMOD_TRY(expr)               \
+  do {                                \
+    hipError_t _e = (expr);           \
+    if (_e != hipSuccess) {           \
+      fail(#expr, _e);                \
+      return -2;                      \
+    }                                 \
+  } while (0)
+
+DeviceDemodulator *DeviceDemodulator::create(const Constellation &c, int device, std::string *err) {
+  auto bail = [&](const std::string &m) -> DeviceDemodulator * {
+    if (err) *err = m;
+    return nullptr;
+  };
+  int count = 0;
+  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
+    return bail("no HIP device available: the demodulator has no CPU path");
+  if (device < 0 || device >= count) return bail("HIP device index out of range");
+  if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice failed");
+  std::unique_ptr<DeviceDemodulator> d(new DeviceDemodulator());
+  d->c_ = c;
+  d->device_ = device;
+  if (d->stream_.create() != hipSuccess || d->ev_default_.create() != hipSuccess)
+    return bail("creating the demodulator's stream failed");
+  return d.release();
+}
+
+// (the members free what they own, the stream last)
+DeviceDemodulator::~DeviceDemodulator() {
+  (void)hipSetDevice(device_);
+  if (stream_) (void)hipStreamSynchronize(stream_);
+}
+
+namespace {
+// one pass of a table constellation: frames * symbols_len threads
+template <int M, typename IO, typename A, bool MAXLOG>
+void demod_table_pass(const IO *symbols, IO *llrs, uint32_t symbols_len, uint32_t llrs_len, uint64_t total, double scale,
+                      int32_t interleaving, const Constellation &c, hipStream_t s) {
+  demod::Table<A> t;
+  const double half_scale = 0.5 * scale;
+  for (uint32_t v = 0; v < 32; v++) {
+    t.re[v] = static_cast<A>(c.re[v]);
+    t.im[v] = static_cast<A>(c.im[v]);
+    t.c[v] = static_cast<A>(half_scale * c.e[v]);
+  }
+  const uint32_t blocks = static_cast<uint32_t>((total + demod::kThreads - 1) / demod::kThreads);
+  demod::table_kernel<M, IO, A, MAXLOG><<<blocks, demod::kThreads, 0, s>>>(symbols, llrs, symbols_len, llrs_len, total,
+                                                                          static_cast<A>(scale), interleaving, c.energy ? 1 : 0, t);
+}
+
+template <typename IO, typename A, bool MAXLOG>
+void demod_table_pass_m(uint32_t bits, const IO *symbols, IO *llrs, uint32_t symbols_len, uint32_t llrs_len, uint64_t total,
+                        double scale, int32_t interleaving, const Constellation &c, hipStream_t s) {
+  switch (bits) {
+    case 1: return demod_table_pass<1, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
+    case 2: return demod_table_pass<2, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
+    case 3: return demod_table_pass<3, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
+    case 4: return demod_table_pass<4, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
+    default: return demod_table_pass<5, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
+  }
+}
+}  // namespace
+
+template <typename IO>
+void DeviceDemodulator::launch(const IO *symbols, IO *llrs, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
+                               int32_t interleaving, bool max_log, hipStream_t s) {
+  // passes of whole frames whose thread count fits a 31-bit grid (symbols_len <= llrs_len < 2^31: at least 255 frames each)
+  const size_t pass = std::max<size_t>((uint64_t(0x7fffffffu) * demod::kThreads) / symbols_len, 1);
+  const size_t per_symbol = c_.bpsk ? 1 : 2;
+  const uint32_t sl = static_cast<uint32_t>(symbols_len), ll = static_cast<uint32_t>(llrs_len);
+  for (size_t b0 = 0; b0 < batch; b0 += pass) {
+    const uint64_t total = uint64_t(std::min(pass, batch - b0)) * symbols_len;
+    const IO *sym = symbols + b0 * symbols_len * per_symbol;
+    IO *out = llrs + b0 * llrs_len;
+    if (c_.bpsk) {
+      const double scale = -2.0 / (sigma * sigma);
+      const uint32_t blocks = static_cast<uint32_t>((total + demod::kThreads - 1) / demod::kThreads);
+      demod::bpsk_kernel<IO><<<blocks, demod::kThreads, 0, s>>>(sym, out, ll, total, static_cast<IO>(scale), interleaving);
+      continue;
+    }
+    const double scale = 1.0 / (sigma * sigma);
+    if (!max_log)
+      demod_table_pass_m<IO, double, false>(c_.bits, sym, out, sl, ll, total, scale, interleaving, c_, s);
+    else
+      demod_table_pass_m<IO, IO, true>(c_.bits, sym, out, sl, ll, total, scale, interleaving, c_, s);
+  }
+}
+
+int DeviceDemodulator::run_device(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch,
+                                  double sigma, int32_t interleaving, bool max_log, hipStream_t stream) {
+  if (batch == 0 || llrs_len == 0) return 0;
+  DEMOD_TRY(hipSetDevice(device_));
+  hipStream_t s = stream ? stream : stream_;
+  if (!stream) {
+    // (the handle's stream is non-blocking: ordered explicitly after what the legacy default stream holds now)
+    DEMOD_TRY(hipEventRecord(ev_default_, nullptr));
+    DEMOD_TRY(hipStreamWaitEvent(s, ev_default_, 0));
+  }
+  if (f64)
+    launch(static_cast<const double *>(symbols), static_cast<double *>(llrs), symbols_len, llrs_len, batch, sigma, interleaving,
+           max_log, s);
+  else
+    launch(static_cast<const float *>(symbols), static_cast<float *>(llrs), symbols_len, llrs_len, batch, sigma, interleaving,
+           max_log, s);
+  DEMOD_TRY(hipGetLastError());
+  if (!stream) DEMOD_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int DeviceDemodulator::run_host(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch,
+                                double sigma, int32_t interleaving, bool max_log) {
+  if (batch == 0 || llrs_len == 0) return 0;
+  DEMOD_TRY(hipSetDevice(device_));
+  const size_t elem = f64 ? 8 : 4;
+  const size_t in_bytes = batch * symbols_len * (c_.bpsk ? 1 : 2) * elem, out_bytes = batch * llrs_len * elem;
+  DEMOD_TRY(d_in_.ensure(in_bytes, 256));
+  DEMOD_TRY(d_out_.ensure(out_bytes, 256));
+  DEMOD_TRY(hipMemcpyAsync(d_in_.get(), symbols, in_bytes, hipMemcpyHostToDevice, stream_));
+  if (int rc = run_device(d_in_.get(), d_out_.get(), f64, symbols_len, llrs_len, batch, sigma, interleaving, max_log, stream_))
+    return rc;
+  // (the only write to the caller's buffer: after an earlier failure nothing has been written)
+  DEMOD_TRY(hipMemcpyAsync(llrs, d_out_.get(), out_bytes, hipMemcpyDeviceToHost, stream_));
+  DEMOD_TRY(hipStreamSynchronize(stream_));
+  return 0;
+}
+
+#undef DEMOD_TRY
+
+}  // namespace ldpc

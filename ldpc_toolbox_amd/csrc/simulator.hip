@@ -6,6 +6,7 @@
 #include <cstdlib>
 #include <random>
 
+#include "demodulator.hip.h"      // so does the batched soft demapper
 #include "device_encoder.hip.h"  // the batched GPU encoder lives in this translation unit
 #include "frame_gen.hip.h"
 #include "implementation.h"
