@@ -198,7 +198,10 @@ int32_t ldpc_toolbox_decoder_syndrome_device(void *decoder, const uint8_t *bits,
  * "last_lanes" / "last_group" (execution lanes and codewords per group of the last decode call),
  * "preferred_group" (codewords per group of a large call: "group_size" if set, else 4096, more for small graphs),
  * "row_records" (words per check-row record when flooding min-sum keeps a row's messages as
- * {min1, min2, flip bits, argmin}; 0 = per-edge messages), "minsum_correction" (0: none, 1: normalized min-sum,
+ * {min1, min2, flip bits, argmin}; 0 = per-edge messages), "record_flag_bits" (read-only: bits of the word that holds a
+ * record's flip bits and argmin in memory -- 16 where every row has at most 12 edges, then kept in an array of its own
+ * beside the two magnitudes, else 32 or 64, the decoder's own word; 0 without records.  "row_records" stays the record
+ * family, 3 or 4, whatever the width), "minsum_correction" (0: none, 1: normalized min-sum,
  * 2: offset min-sum), "minsum_correction_int" (the 8-bit min-sum names: the integer the kernels use, 16 * alpha or
  * 8 * beta; 0 for every other name).  returns 0 or -1 (unknown key). */
 int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value);

@@ -62,6 +62,7 @@ class DeviceDecoder {
   // words per check-row record when the flooding min-sum path keeps row records (kernels.hip.h,
   // cn_minsum_rec_kernel), 0 when it keeps per-edge messages
   uint32_t row_records() const { return (rec_ready_ && records_wanted() && opt_lfree_ && !opt_staged_minsum_) ? rec_w_ : 0; }
+  uint32_t record_flag_bits() const { return row_records() ? rec_flag_bits_ : 0; }
 
   // codewords per group (rounded up to the wave tile).  0 = automatic.
   void set_group_size(size_t g) { group_pref_ = g; }
@@ -199,6 +200,7 @@ class DeviceDecoder {
   bool opt_rec_quiet_ = true;  // "rec_quiet": L-free posteriors are stored only once a slice has a converged codeword
   bool opt_vn_event_ = true;  // "vn_event": the first convergences' L-free posteriors rebuilt inside the variable-node launch (0: a launch of their own)
   uint32_t rec_w_ = 0;
+  uint32_t rec_flag_bits_ = 0;  // 16: the records' flags are half-words in an array of their own (graph_tables.h)
   bool rec_ready_ = false, rec_prefers_ = false;
   // "records": 0 = never, 1 = where the graph suits them (rec_prefers_: the default), 2 = wherever they are possible
   uint32_t opt_records_ = 1;

@@ -103,6 +103,7 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
     if (rr.ready) {
       d->rec_prefers_ = rr.rec_prefers;
       d->rec_w_ = rr.rec_w;
+      d->rec_flag_bits_ = rr.flag_bits;
       ok = up(rr.keep_pos, &d->d_keep_pos_) && up(rr.peer, &d->d_edge_peer_) && up(rr.free_rs, &d->d_free_rs_);
       d->rec_ready_ = ok;
     }
@@ -351,8 +352,12 @@ int DeviceDecoder::ensure_workspace(Workspace &w, size_t G, void *place, size_t 
   };
   const size_t o_msg = carve(std::max<size_t>(e_, 1) * G * elem);
   const size_t o_msg2 = (lfree_ready_ && !records) ? carve(std::max<size_t>(e_, 1) * G * elem) : 0;
-  const size_t rec_bytes = records ? std::max<size_t>(m_, 1) * rec_w_ * G * elem : 0;
+  // (16-bit flags: two rows of magnitudes per record, and the flags as half-words in an array of their own)
+  const bool flags16 = records && rec_flag_bits_ == 16;
+  const size_t rec_bytes = records ? std::max<size_t>(m_, 1) * (flags16 ? 2 : rec_w_) * G * elem : 0;
   const size_t o_rec0 = records ? carve(rec_bytes) : 0, o_rec1 = records ? carve(rec_bytes) : 0;
+  const size_t flag_bytes = flags16 ? std::max<size_t>(m_, 1) * G * sizeof(uint16_t) : 0;
+  const size_t o_flag0 = flags16 ? carve(flag_bytes) : 0, o_flag1 = flags16 ? carve(flag_bytes) : 0;
   const size_t o_post = carve(n_ * G * elem);
   const size_t o_chan = carve(n_ * G * elem);
   const size_t o_perm = carve(4 * G * sizeof(uint32_t) + 1024);
@@ -387,6 +392,8 @@ int DeviceDecoder::ensure_workspace(Workspace &w, size_t G, void *place, size_t 
   w.msg2 = (lfree_ready_ && !records) ? base + o_msg2 : nullptr;
   w.rec[0] = records ? base + o_rec0 : nullptr;
   w.rec[1] = records ? base + o_rec1 : nullptr;
+  w.rec_flags[0] = flags16 ? reinterpret_cast<uint16_t *>(base + o_flag0) : nullptr;
+  w.rec_flags[1] = flags16 ? reinterpret_cast<uint16_t *>(base + o_flag1) : nullptr;
   w.post = base + o_post;
   w.chan = base + o_chan;
   w.perm = reinterpret_cast<uint32_t *>(base + o_perm);

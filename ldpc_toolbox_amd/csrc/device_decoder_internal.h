@@ -45,6 +45,7 @@ struct DeviceDecoder::Workspace {
   size_t slab_bytes = 0;
   void *chan = nullptr, *post = nullptr, *msg = nullptr, *msg2 = nullptr;
   void *rec[2] = {nullptr, nullptr};  // row records, double-buffered (instead of msg2)
+  uint16_t *rec_flags[2] = {nullptr, nullptr};  // their 16-bit flags (rec then holds the magnitudes alone), or null
   bool records = false;
   uint64_t *rawbits = nullptr, *hardbits = nullptr;
   // compaction: perm = the movers' slots, slot_tmp = the holes they fill, fill_cw = codeword landing in a slot

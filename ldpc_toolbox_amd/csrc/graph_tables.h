@@ -67,8 +67,22 @@ struct RowRecordTables {
   bool ready = false;
   std::vector<uint32_t> peer, free_rs, keep_pos;
   uint32_t rec_w = 0;        // words per record: 3, or 4 for rows too long for the packed form
+  uint32_t flag_bits = 0;    // width of a record's flags word in memory: 16, 32 or 64 (record_flag_bits)
   bool rec_prefers = false;  // at most a quarter of the degree-2 variables join distant rows
 };
+// Width of the word that holds a row record's flip bits and argmin, from the longest row: 16 where the flip bits and the
+// argmin (ceil(log2(weight)) bits, one for a single edge) fit a half-word -- rows of at most 12 edges --, else the decoder's
+// own word: packed with the argmin up to 26 (f32) / 58 (f64) edges, the argmin in a fourth word beyond.  0: no record form.
+inline uint32_t record_arg_bits(uint32_t max_row_weight) {
+  uint32_t bits = 1;
+  while ((1u << bits) < max_row_weight) bits++;
+  return bits;
+}
+inline uint32_t record_flag_bits(uint32_t max_row_weight, bool f64) {
+  const uint32_t word = f64 ? 64u : 32u;
+  if (max_row_weight == 0 || max_row_weight > word) return 0;
+  return max_row_weight + record_arg_bits(max_row_weight) <= 16 ? 16u : word;
+}
 inline RowRecordTables build_row_record_tables(const SparseMatrix::Csr &g, const LfreeTables &lf, bool f64) {
   RowRecordTables t;
   const uint32_t rec_bits = f64 ? 64u : 32u, rec_packed = f64 ? 58u : 26u;
@@ -105,6 +119,7 @@ inline RowRecordTables build_row_record_tables(const SparseMatrix::Csr &g, const
   }
   t.rec_prefers = far_peers * 4 <= near_peers + far_peers;
   t.rec_w = g.max_row_weight <= rec_packed ? 3u : 4u;
+  t.flag_bits = record_flag_bits(g.max_row_weight, f64);
   t.peer.resize(t.peer.size() + kTablePad, dev::kPeerKeep);
   t.ready = true;
   return t;

@@ -24,8 +24,12 @@ namespace dev {
 //     kernel still walks (degree >= 3): 5 of 7 words for DVB-S2 1/2.
 // Records are double-buffered (a row reads its neighbours' previous records while they write their new ones);
 // the per-edge messages no longer are (nobody but vn_kernel reads them).  Per row of DVB-S2 1/2 the launch
-// moves 3 + 5 + 1 + 3 + 5 + 1 = 18 words where cn_minsum_lfree_kernel moves 22-24.
+// moves 3 + 5 + 1 + 3 + 5 + 1 = 18 words where cn_minsum_lfree_kernel moves 22-24 -- 17 with 16-bit flags, below.
 //   rec_in / rec_out  [M * RECW][tile]  words of T's size: row c occupies rows c*RECW .. c*RECW + RECW-1
+//   with 16-bit flags (F16; rows of at most 12 edges, graph_tables.h record_flag_bits) a pair of arrays, RecPair:
+//     mag    [M * 2][tile]  of T: min1 and min2 of row c in rows 2c and 2c + 1
+//     flags  [M][tile]      of uint16_t: flip bits 0..11, argmin in bits 12..15
+//   a record is then 2.5 words of f32 (2.25 of f64) in each direction
 // ---------------------------------------------------------------------------------------
 template <typename T>
 struct RecWord {
@@ -84,9 +88,89 @@ __device__ __forceinline__ void buf_store(const RowBuf &b, uint32_t lane_off, ui
   }
 }
 
-template <typename T, int VEC, int RECW>
+// 16-bit flags (flooding records of rows of at most 12 edges: graph_tables.h, record_flag_bits): the flags leave the
+// record's rows for an array of their own, [M][tile] of uint16_t beside the magnitudes' [2M][tile] of T (rows 2c, 2c+1),
+// both tiled like every other array.  A lane's VEC half-words are one b64 / b32 / b16 buffer access.
+constexpr int kArgShift16 = 12;  // flip bits at 0..11, argmin at 12..15
+template <int VEC, bool NT>
+__device__ __forceinline__ Pack<uint16_t, VEC> flags_load(const RowBuf &b, uint32_t lane_off, uint32_t row_off) {
+  static_assert(VEC == 1 || VEC == 2 || VEC == 4, "pack size");
+  if constexpr (VEC == 1)
+    return __builtin_bit_cast(Pack<uint16_t, VEC>, __builtin_amdgcn_raw_buffer_load_b16(b.r, lane_off, row_off, NT ? 2 : 0));
+  else if constexpr (VEC == 2)
+    return __builtin_bit_cast(Pack<uint16_t, VEC>, __builtin_amdgcn_raw_buffer_load_b32(b.r, lane_off, row_off, NT ? 2 : 0));
+  else
+    return __builtin_bit_cast(Pack<uint16_t, VEC>, __builtin_amdgcn_raw_buffer_load_b64(b.r, lane_off, row_off, NT ? 2 : 0));
+}
+template <int VEC, bool NT>
+__device__ __forceinline__ void flags_store(const RowBuf &b, uint32_t lane_off, uint32_t row_off, const Pack<uint16_t, VEC> &x) {
+  typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+  if constexpr (VEC == 1)
+    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
+  else if constexpr (VEC == 2)
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
+  else
+    __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, x), b.r, lane_off, row_off, NT ? 2 : 0);
+}
+
+// Where a launch finds the records: one array of T (flags in the record's own rows), or with 16-bit flags the magnitudes
+// and the flags array.  Ref: the kernel argument; Buf: the wavefront's slice behind buffer descriptors.
+template <typename T, bool F16>
+struct RecRef {
+  typedef const T *__restrict__ in;
+  typedef T *__restrict__ out;
+};
+template <typename T>
+struct RecPair {
+  T *mag;
+  uint16_t *flags;
+};
+template <typename T>
+struct RecRef<T, true> {
+  typedef RecPair<const T> in;
+  typedef RecPair<T> out;
+};
+template <bool F16>
+struct RecBuf {
+  RowBuf b;
+};
+template <>
+struct RecBuf<true> {
+  RowBuf b, f;
+};
+// the slice of codewords b0.. of the records of n_rows rows (row_bytes: tile * sizeof(T))
+template <typename T, int RECW>
+__device__ __forceinline__ RecBuf<false> rec_buf(const T *rec, uint32_t b0, uint32_t n_rows, const Sched &sc, uint32_t row_bytes) {
+  return RecBuf<false>{row_buf(rec + tile_base(b0, n_rows * RECW, sc),
+                               uint64_t(n_rows) * RECW * row_bytes - in_tile_of(b0, sc) * uint32_t(sizeof(T)))};
+}
+template <typename T, int RECW, typename TT>
+__device__ __forceinline__ RecBuf<true> rec_buf(const RecPair<TT> &rec, uint32_t b0, uint32_t n_rows, const Sched &sc,
+                                                uint32_t row_bytes) {
+  static_assert(RECW == 3, "16-bit flags: the three-word family");
+  const uint32_t in_tile = in_tile_of(b0, sc);
+  return RecBuf<true>{row_buf(rec.mag + tile_base(b0, n_rows * 2, sc), uint64_t(n_rows) * 2 * row_bytes - in_tile * uint32_t(sizeof(T))),
+                      row_buf(rec.flags + tile_base(b0, n_rows, sc), (uint64_t(n_rows) * sc.tile - in_tile) * sizeof(uint16_t))};
+}
+
+// FW, the type of the stored flags word: the decoder's own word (this form: the flags are the record's third row, and a
+// fourth for RECW == 4) or uint16_t (the specialisation below)
+template <typename T, int VEC, int RECW, typename FW = typename RecWord<T>::type>
 struct RowRec {
+  static_assert(std::is_same_v<FW, typename RecWord<T>::type>, "flags word: RecWord<T>::type or uint16_t");
   typedef typename RecWord<T>::type W;
+  // the flags word of a new record (RECW == 3): flip bits below the argmin
+  static __device__ __forceinline__ W pack_flags(W fl, uint32_t arg) {
+    return (fl & ((W(1) << RecWord<T>::kArgShift) - 1)) | (W(arg) << RecWord<T>::kArgShift);
+  }
+  static constexpr uint32_t kRows = RECW;  // rows of T per record: row c's record is at row_off = c * kRows * row_bytes
+  __device__ __forceinline__ void load(const RecBuf<false> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) {
+    load(b.b, lane_off, row_off, row_bytes);
+  }
+  template <bool NT>
+  __device__ __forceinline__ void store(const RecBuf<false> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) const {
+    store<NT>(b.b, lane_off, row_off, row_bytes);
+  }
   Pack<T, VEC> min1, min2;
   Pack<W, VEC> flip, arg;  // RECW == 3: `flip` is the whole third word, `arg` unused
   // row_off: byte offset of the record's first row in the wavefront's slice; row_bytes: bytes between rows
@@ -112,6 +196,37 @@ struct RowRec {
     return __builtin_bit_cast(T, __builtin_bit_cast(W, mag) | sign);
   }
 };
+// the three-word family with its flags as 16-bit words in an array of their own: every row still has flags of its own,
+// `value` returns what the wide form returns
+template <typename T, int VEC>
+struct RowRec<T, VEC, 3, uint16_t> {
+  typedef typename RecWord<T>::type W;
+  static __device__ __forceinline__ uint16_t pack_flags(W fl, uint32_t arg) {
+    return uint16_t((uint32_t(fl) & ((1u << kArgShift16) - 1)) | (arg << kArgShift16));
+  }
+  static constexpr uint32_t kRows = 2;
+  Pack<T, VEC> min1, min2;
+  Pack<uint16_t, VEC> flip;
+  // lane_off, row_off: byte offsets in the magnitudes (row c: c * 2 * tile * sizeof(T)).  The flags of the same codewords
+  // and row sit at lane_off * 2 / sizeof(T) and c * tile * 2 = row_off / sizeof(T) in theirs.
+  __device__ __forceinline__ void load(const RecBuf<true> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) {
+    min1 = buf_load<T, VEC, false>(b.b, lane_off, row_off);
+    min2 = buf_load<T, VEC, false>(b.b, lane_off, row_off + row_bytes);
+    flip = flags_load<VEC, false>(b.f, lane_off / uint32_t(sizeof(T) / sizeof(uint16_t)), row_off / uint32_t(sizeof(T)));
+  }
+  template <bool NT>
+  __device__ __forceinline__ void store(const RecBuf<true> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) const {
+    buf_store<T, VEC, NT>(b.b, lane_off, row_off, min1);
+    buf_store<T, VEC, NT>(b.b, lane_off, row_off + row_bytes, min2);
+    flags_store<VEC, NT>(b.f, lane_off / uint32_t(sizeof(T) / sizeof(uint16_t)), row_off / uint32_t(sizeof(T)), flip);
+  }
+  __device__ __forceinline__ T value(uint32_t slot, int k) const {
+    const uint32_t f = flip.v[k];
+    const T mag = ((f >> kArgShift16) == slot) ? min2.v[k] : min1.v[k];
+    const W sign = W(f >> slot) << (8 * sizeof(W) - 1);  // widened before the shift that makes the sign bit
+    return __builtin_bit_cast(T, __builtin_bit_cast(W, mag) | sign);
+  }
+};
 
 
 // Posterior of the L-free variables from the row records: L = chan + (m_a + m_b), the messages read out of the
@@ -121,10 +236,12 @@ struct RowRec {
 //   event_iteration >= 0: after the variable-node pass that latched the FIRST converged codewords of a slice
 //                        (State::slice_state == 1) at that iteration count: for exactly those codewords, whose
 //                        L-free posteriors the check-node kernel had not been storing.
-template <typename T, int VEC, int RECW>
+// F16: the records' flags are 16-bit words in an array of their own (RecRef / RowRec above).
+template <typename T, int VEC, int RECW, bool F16 = false>
 __global__ __launch_bounds__(256) void vn_free_rec_kernel(Graph g, Sched sc, State st, const uint32_t *__restrict__ free_rs_,
-                                                          const T *__restrict__ chan, const T *__restrict__ rec,
+                                                          const T *__restrict__ chan, typename RecRef<T, F16>::in rec,
                                                           T *__restrict__ post, int32_t event_iteration) {
+  typedef RowRec<T, VEC, RECW, std::conditional_t<F16, uint16_t, typename RecWord<T>::type>> Rec;
   if (event_iteration < 0 && *st.n_active == 0) return;
   const TablePtr free_var = table_ptr(g.list_var), free_rs = table_ptr(free_rs_);
   const uint32_t lane = threadIdx.x & 63u, tile = sc.tile;
@@ -140,8 +257,7 @@ __global__ __launch_bounds__(256) void vn_free_rec_kernel(Graph g, Sched sc, Sta
   chan += tile_base(b0, g.n_cols, sc) + lane * VEC;
   post += tile_base(b0, g.n_cols, sc) + lane * VEC;
   const uint32_t row_bytes = tile * uint32_t(sizeof(T)), lane_off = lane * uint32_t(VEC * sizeof(T));
-  const RowBuf b_rec = row_buf(rec + tile_base(b0, g.n_rows * RECW, sc),
-                               uint64_t(g.n_rows) * RECW * row_bytes - in_tile_of(b0, sc) * uint32_t(sizeof(T)));
+  const RecBuf<F16> b_rec = rec_buf<T, RECW>(rec, b0, g.n_rows, sc, row_bytes);
   bool live[VEC];  // the codewords this pass writes
   bool any_live = false;
 #pragma unroll
@@ -153,9 +269,9 @@ __global__ __launch_bounds__(256) void vn_free_rec_kernel(Graph g, Sched sc, Sta
   for (uint32_t i = i0; i < g.n_list; i += sc.waves_per_chunk) {
     const uint32_t v = free_var[i], a = free_rs[2 * i], b = free_rs[2 * i + 1];
     const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(v) * G);
-    RowRec<T, VEC, RECW> ra, rb;
-    if (a != kAuxNone) ra.load(b_rec, lane_off, (a >> 6) * RECW * row_bytes, row_bytes);
-    if (b != kAuxNone) rb.load(b_rec, lane_off, (b >> 6) * RECW * row_bytes, row_bytes);
+    Rec ra, rb;
+    if (a != kAuxNone) ra.load(b_rec, lane_off, (a >> 6) * Rec::kRows * row_bytes, row_bytes);
+    if (b != kAuxNone) rb.load(b_rec, lane_off, (b >> 6) * Rec::kRows * row_bytes, row_bytes);
 #pragma unroll
     for (int k = 0; k < VEC; k++) {
       T sum = -T(0.0);  // arithmetic.rs:146: the slot-ordered sum, from Rust's float Sum identity
@@ -188,11 +304,20 @@ struct VnEvent {
   const T *rec;                        // records of the iteration being latched
   uint32_t n_free;
 };
-template <typename T, int VEC, int U, bool NT, bool LIST, int EVW = 0>
+template <typename T>
+struct VnEvent16 {  // the same with 16-bit flags (EVF16)
+  const uint32_t *free_var, *free_rs;
+  RecPair<const T> rec;
+  uint32_t n_free;
+};
+__device__ __forceinline__ bool has_records(const void *rec) { return rec != nullptr; }
+template <typename T>
+__device__ __forceinline__ bool has_records(const RecPair<T> &rec) { return rec.mag != nullptr; }
+template <typename T, int VEC, int U, bool NT, bool LIST, int EVW = 0, bool EVF16 = false>
 __global__ __launch_bounds__(256) void vn_kernel(
     Graph g, Sched sc, State st, const T *__restrict__ chan, const T *__restrict__ msg,
     T *__restrict__ post, const uint32_t *__restrict__ unsat_in, uint32_t *__restrict__ unsat_clear,
-    int32_t latch_iteration, VnEvent<T> ev = VnEvent<T>{nullptr, nullptr, nullptr, 0}) {
+    int32_t latch_iteration, std::conditional_t<EVF16, VnEvent16<T>, VnEvent<T>> ev = {}) {
   uint32_t *__restrict__ n_active = st.n_active;
   // A finished group's launches return at once.  With EVW the count can also reach zero INSIDE this launch -- the
   // bookkeeping waves below subtract the codewords they latch -- and a wave that starts after the last subtraction must
@@ -214,7 +339,7 @@ __global__ __launch_bounds__(256) void vn_kernel(
   const uint32_t b0 = chunk * (64 * VEC);
   if (b0 >= *st.n_slots) return;
   if constexpr (EVW != 0) {
-    if (idle && (ev.rec == nullptr || unsat_in == nullptr || st.slice_state == nullptr || st.slice_state[chunk] == 2u)) return;
+    if (idle && (!has_records(ev.rec) || unsat_in == nullptr || st.slice_state == nullptr || st.slice_state[chunk] == 2u)) return;
   }
   const size_t off = size_t(b0) + lane * VEC;
   const size_t G = tile;
@@ -256,7 +381,7 @@ __global__ __launch_bounds__(256) void vn_kernel(
     // flag the last check-node pass left, the slot's codeword) and from `iters`, which is -1 before the launch and
     // latch_iteration once the bookkeeping wave has been here: both mean "this launch" (an earlier convergence carries its
     // own, smaller count; an empty slot has no codeword).
-    if (ev.rec != nullptr && unsat_in != nullptr && st.slice_state != nullptr && st.slice_state[chunk] != 2u) {
+    if (has_records(ev.rec) && unsat_in != nullptr && st.slice_state != nullptr && st.slice_state[chunk] != 2u) {
       bool fresh[VEC];
       bool any_fresh = false;
 #pragma unroll
@@ -268,14 +393,14 @@ __global__ __launch_bounds__(256) void vn_kernel(
       if (__builtin_amdgcn_ballot_w64(any_fresh) != 0) {
         const TablePtr free_var = table_ptr(ev.free_var), free_rs = table_ptr(ev.free_rs);
         const uint32_t row_bytes = tile * uint32_t(sizeof(T)), lane_off = lane * uint32_t(VEC * sizeof(T));
-        const RowBuf b_rec = row_buf(ev.rec + tile_base(b0, g.n_rows * EVW, sc),
-                                     uint64_t(g.n_rows) * EVW * row_bytes - in_tile_of(b0, sc) * uint32_t(sizeof(T)));
+        const RecBuf<EVF16> b_rec = rec_buf<T, EVW>(ev.rec, b0, g.n_rows, sc, row_bytes);
         for (uint32_t i = v_first; i < ev.n_free; i += waves_per_chunk) {
           const uint32_t fv = free_var[i], a = free_rs[2 * i], b = free_rs[2 * i + 1];
           const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(fv) * G);
-          RowRec<T, VEC, EVW> ra, rb;
-          if (a != kAuxNone) ra.load(b_rec, lane_off, (a >> 6) * EVW * row_bytes, row_bytes);
-          if (b != kAuxNone) rb.load(b_rec, lane_off, (b >> 6) * EVW * row_bytes, row_bytes);
+          typedef RowRec<T, VEC, EVW, std::conditional_t<EVF16, uint16_t, typename RecWord<T>::type>> Rec;
+          Rec ra, rb;
+          if (a != kAuxNone) ra.load(b_rec, lane_off, (a >> 6) * Rec::kRows * row_bytes, row_bytes);
+          if (b != kAuxNone) rb.load(b_rec, lane_off, (b >> 6) * Rec::kRows * row_bytes, row_bytes);
 #pragma unroll
           for (int k = 0; k < VEC; k++) {
             T sum = -T(0.0);  // arithmetic.rs:146: the slot-ordered sum, from Rust's float Sum identity
@@ -691,10 +816,12 @@ __global__ __launch_bounds__(256) void cn_minsum_lfree_kernel(
 // state -- whatever the record arrays hold from the slot's previous codeword.
 // LONG: some row has more than U edges (further rounds of U loads; compiled out otherwise: the extra code costs the
 // short-row case 2 % in registers and scheduling).
-template <typename T, int VEC, int RECW, int U, bool FIRST, bool NT, bool STREAM = false, bool LONG = true, typename... MC>
+// F16: the records' flags are 16-bit words in an array of their own (RecRef / RowRec above): rows of at most 12 edges.
+template <typename T, int VEC, int RECW, bool F16, int U, bool FIRST, bool NT, bool STREAM = false, bool LONG = true, typename... MC>
 __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
-    Graph g, Sched sc, State st, const T *__restrict__ chan, T *__restrict__ post, const T *__restrict__ rec_in,
-    T *__restrict__ rec_out, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t run, MC... mc) {
+    Graph g, Sched sc, State st, const T *__restrict__ chan, T *__restrict__ post, typename RecRef<T, F16>::in rec_in,
+    typename RecRef<T, F16>::out rec_out, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t run, MC... mc) {
+  typedef RowRec<T, VEC, RECW, std::conditional_t<F16, uint16_t, typename RecWord<T>::type>> Rec;
   constexpr bool CORR = sizeof...(MC) != 0;  // normalized / offset min-sum
   static_assert(is_corr_pack<T, MC...>, "mc: nothing, or one MinsumCorr<T>");
   typedef typename RecWord<T>::type W;
@@ -740,9 +867,18 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
   const RowBuf b_chan = row_buf(chan + tile_base(b0, g.n_cols, sc), uint64_t(g.n_cols) * row_bytes - in_tile);
   const RowBuf b_post = row_buf(post + tile_base(b0, g.n_cols, sc), uint64_t(g.n_cols) * row_bytes - in_tile);
   const RowBuf b_msg = row_buf(msg + tile_base(b0, g.n_edges, sc), uint64_t(g.n_edges) * row_bytes - in_tile);
-  const RowBuf b_rin = row_buf(rec_in + tile_base(b0, g.n_rows * RECW, sc), uint64_t(g.n_rows) * RECW * row_bytes - in_tile);
-  const RowBuf b_rout = row_buf(rec_out + tile_base(b0, g.n_rows * RECW, sc), uint64_t(g.n_rows) * RECW * row_bytes - in_tile);
-  const uint32_t rec_bytes = RECW * row_bytes;
+  // (the one-array form spells out what rec_buf<T, RECW>(const T *, ...) does, with the in_tile above: through rec_buf the
+  // compiler schedules the 40 instantiations that existed before the 16-bit form differently, and they are to stay
+  // instruction-identical, tools/kernel_digest.py)
+  RecBuf<F16> b_rin, b_rout;
+  if constexpr (F16) {
+    b_rin = rec_buf<T, RECW>(rec_in, b0, g.n_rows, sc, row_bytes);
+    b_rout = rec_buf<T, RECW>(rec_out, b0, g.n_rows, sc, row_bytes);
+  } else {
+    b_rin.b = row_buf(rec_in + tile_base(b0, g.n_rows * RECW, sc), uint64_t(g.n_rows) * RECW * row_bytes - in_tile);
+    b_rout.b = row_buf(rec_out + tile_base(b0, g.n_rows * RECW, sc), uint64_t(g.n_rows) * RECW * row_bytes - in_tile);
+  }
+  const uint32_t rec_bytes = Rec::kRows * row_bytes;
   uint64_t odd_m[VEC];  // lane masks (SGPR pairs): codeword k of the lane has seen an odd row
 #pragma unroll
   for (int k = 0; k < VEC; k++) odd_m[k] = 0;
@@ -754,7 +890,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     // own = record of the current row, nxt = record of the row the walk reaches next (this row's peer now, `own`
     // one step later); carry = the message the PREVIOUS row of the walk sent to the variable it shares with this
     // one (it had that value in hand as its own message: the previous row's record need not be kept)
-    RowRec<T, VEC, RECW> recA, recB;
+    Rec recA, recB;
     T carry[VEC];
 #pragma unroll
     for (int k = 0; k < VEC; k++) carry[k] = T(0.0);
@@ -772,7 +908,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     }
     if (!FIRST) recA.load(b_rin, lane_off, c * rec_bytes, row_bytes);
 
-    auto row_step = [&](RowRec<T, VEC, RECW> &own, RowRec<T, VEC, RECW> &nxt) {
+    auto row_step = [&](Rec &own, Rec &nxt) {
       const uint32_t d = e1 - e0, cn = c + dir, cp = c - dir;
       if (!FIRST && cn < n_rows) nxt.load(b_rin, lane_off, cn * rec_bytes, row_bytes);
       Pack<T, VEC> lv[U];
@@ -824,7 +960,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
 #pragma unroll
             for (int k = 0; k < VEC; k++) m_other[k] = carry[k];
           } else {
-            RowRec<T, VEC, RECW> far;  // not a neighbour inside the run: fetch the peer's record
+            Rec far;  // not a neighbour inside the run: fetch the peer's record
             far.load(b_rin, lane_off, prow * rec_bytes, row_bytes);
 #pragma unroll
             for (int k = 0; k < VEC; k++) m_other[k] = far.value(pslot, k);
@@ -893,7 +1029,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
       for (int k = 0; k < VEC; k++) carry[k] = next_carry[k];
       if (d != 0) {
         // the new record: flip[slot] = (parity of all signs) ^ (x_slot < 0)
-        RowRec<T, VEC, RECW> out;
+        Rec out;
 #pragma unroll
         for (int k = 0; k < VEC; k++) {
           const uint32_t tot = (sizeof(W) == 8 ? __popcll(sgn[k]) : __popc(uint32_t(sgn[k]))) & 1u;
@@ -911,7 +1047,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
             out.flip.v[k] = fl;
             out.arg.v[k] = W(arg[k]);
           } else {
-            out.flip.v[k] = (fl & ((W(1) << RecWord<T>::kArgShift) - 1)) | (W(arg[k]) << RecWord<T>::kArgShift);
+            out.flip.v[k] = Rec::pack_flags(fl, arg[k]);
           }
         }
         // (Round 4 kept this store behind an always-true `run != 0`: with it unconditional two variants returned results that

@@ -87,28 +87,57 @@ struct Launch {
       });
     });
   }
-  // row records (cn_minsum_rec_kernel): VEC x words per record (3 or 4) x FIRST x long rows
+  // the record form of a flooding launch: f(RECW, F16) -- three words with the flags in the record's own rows or as 16-bit
+  // words in an array of their own (Records::flags), or four words
+  struct Records {
+    T *mag;           // the records ([M * recw][tile]); with 16-bit flags the magnitudes alone ([2M][tile])
+    uint16_t *flags;  // [M][tile], or null: the flags are the record's third word
+    uint32_t recw;
+  };
+  template <typename F>
+  static void with_rec_form(const Records &r, F &&f) {
+    if (r.recw == 3 && r.flags != nullptr) return f(int_c<3>{}, std::true_type{});
+    if (r.recw == 3) return f(int_c<3>{}, std::false_type{});
+    f(int_c<4>{}, std::false_type{});
+  }
+  template <bool F16>
+  static auto rec_in(const Records &r) {
+    if constexpr (F16)
+      return dev::RecPair<const T>{r.mag, r.flags};
+    else
+      return static_cast<const T *>(r.mag);
+  }
+  template <bool F16>
+  static auto rec_out(const Records &r) {
+    if constexpr (F16)
+      return dev::RecPair<T>{r.mag, r.flags};
+    else
+      return r.mag;
+  }
+  // row records (cn_minsum_rec_kernel): VEC x record form x FIRST x long rows
   // (rows of at most 8 edges -- DVB-S2 up to rate 1/2, most 5G NR rows are longer -- take the variant without the
   // further-rounds code)
   // (eight loads in flight per lane; the four-load variant of earlier rounds, a tuning knob nothing selected, is gone)
-  void cn_rec(bool first, uint32_t vec, uint32_t recw, const Tiling &t, const dev::Graph &g, const dev::State &st,
-              const T *chan, T *post, const T *rec_in, T *rec_out, T *msg, uint32_t *unsat, uint32_t run) const {
+  void cn_rec(bool first, uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan, T *post,
+              const Records &in, const Records &out, T *msg, uint32_t *unsat, uint32_t run) const {
     minsum(vec, first, [&](auto V, auto FIRST, auto... mc) {
-      with_bool(recw == 3, [&](auto three) {
+      with_rec_form(in, [&](auto W, auto F16) {
         with_bool(rec_long, [&](auto long_rows) {
-          dev::cn_minsum_rec_kernel<T, decltype(V)::value, decltype(three)::value ? 3 : 4, 8, decltype(FIRST)::value, true,
-                                    false, decltype(long_rows)::value, decltype(mc)...>
-              <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_in, rec_out, msg, unsat, run, mc...);
+          dev::cn_minsum_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, 8, decltype(FIRST)::value,
+                                    true, false, decltype(long_rows)::value, decltype(mc)...>
+              <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_in<decltype(F16)::value>(in),
+                                              rec_out<decltype(F16)::value>(out), msg, unsat, run, mc...);
         });
       });
     });
   }
-  void vn_free_rec(uint32_t vec, uint32_t recw, const Tiling &t, const dev::Graph &g, const dev::State &st,
-                   const uint32_t *free_rs, const T *chan, const T *rec, T *post, int32_t event_iteration) const {
+  void vn_free_rec(uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const uint32_t *free_rs,
+                   const T *chan, const Records &rec, T *post, int32_t event_iteration) const {
     with_vec<T>(vec, [&](auto V) {
-      with_bool(recw == 3, [&](auto three) {
-        dev::vn_free_rec_kernel<T, decltype(V)::value, decltype(three)::value ? 3 : 4>
-            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, free_rs, chan, rec, post, event_iteration);
+      with_rec_form(rec, [&](auto W, auto F16) {
+        dev::vn_free_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value>
+            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, free_rs, chan, rec_in<decltype(F16)::value>(rec), post,
+                                            event_iteration);
       });
     });
   }
@@ -151,12 +180,15 @@ struct Launch {
     });
   }
   // the list variant that also rebuilds the L-free posteriors of a slice's first convergences (kernels_flooding.hip.h, EVW)
-  void vn_event(uint32_t vec, uint32_t recw, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan,
-                const T *msg, T *post, const uint32_t *unsat_in, uint32_t *unsat_clear, int32_t latch_it,
-                const dev::VnEvent<T> &ev) const {
+  // (free_var, free_rs, n_free: the L-free variables; rec: the records of the iteration being latched)
+  void vn_event(uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan, const T *msg, T *post,
+                const uint32_t *unsat_in, uint32_t *unsat_clear, int32_t latch_it, const uint32_t *free_var,
+                const uint32_t *free_rs, const Records &rec, uint32_t n_free) const {
     with_vec<T>(vec, [&](auto V) {
-      with_bool(recw == 3, [&](auto three) {
-        dev::vn_kernel<T, decltype(V)::value, 8, true, true, decltype(three)::value ? 3 : 4>
+      with_rec_form(rec, [&](auto W, auto F16) {
+        const std::conditional_t<decltype(F16)::value, dev::VnEvent16<T>, dev::VnEvent<T>> ev{
+            free_var, free_rs, rec_in<decltype(F16)::value>(rec), n_free};
+        dev::vn_kernel<T, decltype(V)::value, 8, true, true, decltype(W)::value, decltype(F16)::value>
             <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, msg, post, unsat_in, unsat_clear, latch_it, ev);
       });
     });

@@ -46,7 +46,9 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
   // batch compaction checkpoint (kernels.hip.h): everything decided on the device
   const Tiling mv_t = make_tiling(G, tile, 64, n, 256, kMoveWaves);
   uint32_t post_move_rows = 0;  // 0 = all rows; set by the flooding L-free paths below
-  auto compact = [&](uint32_t remaining, T *msg_cur, bool with_chan, uint32_t msg_rows) {
+  // (flags, flag_rows: the 16-bit flags of flooding row records, which travel with their magnitudes in msg_cur)
+  auto compact = [&](uint32_t remaining, T *msg_cur, bool with_chan, uint32_t msg_rows, uint16_t *flags = nullptr,
+                     uint32_t flag_rows = 0) {
     grp::compact_plan(s, ticked(max_iterations - remaining), w.plan, w.perm, w.slot_tmp, w.fill_cw, remaining,
         dev::CompactRule{kCompactHorizon, kCompactCostLive, kCompactCostSlots, kCompactMinFreedQ});
     emit(0, 1);
@@ -65,6 +67,11 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     if (msg_rows) add(msg_cur, msg_rows, msg_rows);
     dev::compact_move_kernel<T><<<mv_t.blocks, mv_t.threads, 0, s>>>(w.plan, w.perm, w.slot_tmp, ml, tile,
                                                                      mv_t.sched.nchunks, mv_t.sched.waves_per_chunk);
+    if (flags) {
+      const dev::MoveList<uint16_t> fl{{flags}, {flag_rows}, {flag_rows}, 1};
+      dev::compact_move_kernel<uint16_t><<<mv_t.blocks, mv_t.threads, 0, s>>>(w.plan, w.perm, w.slot_tmp, fl, tile,
+                                                                            mv_t.sched.nchunks, mv_t.sched.waves_per_chunk);
+    }
     grp::compact_commit(s, st, w.plan, w.unsat0, w.unsat1, w.n_slots, w.fill_cw, G);
   };
   auto checkpoint_due = [&](uint32_t it) {
@@ -120,7 +127,10 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
                          uint64_t(std::max<size_t>(std::max(e_, n_), m_ * rec_w_)) * tile * sizeof(T) < (1ull << 32);
     const bool lfree = streaming && lfree_ready_ && opt_lfree_ && (w.msg2 != nullptr || records);
     T *mbuf[2] = {msg, (lfree && !records) ? static_cast<T *>(w.msg2) : msg};
-    T *rbuf[2] = {static_cast<T *>(w.rec[0]), static_cast<T *>(w.rec[1])};
+    // (16-bit flags, rows of at most 12 edges: w.rec_flags holds them, w.rec the magnitudes alone)
+    const typename Launch<T>::Records rbuf[2] = {{static_cast<T *>(w.rec[0]), w.rec_flags[0], rec_w_},
+                                                 {static_cast<T *>(w.rec[1]), w.rec_flags[1], rec_w_}};
+    const uint32_t rec_rows = w.rec_flags[0] ? 2 * m : m * rec_w_;  // rows of T a compaction moves
     if (lfree && post_rows_keep_ > 0 && post_rows_keep_ <= n) post_move_rows = post_rows_keep_;
     const bool quiet = records && opt_rec_quiet_;
     if (quiet) {
@@ -164,7 +174,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       const dev::State stp = ticked(it);
       timed_begin(kKernelCheck, s);
       if (records)
-        launch.cn_rec(first, vec, rec_w_, rec_t, g, stp, chan, post, rbuf[(it + 1) & 1], rbuf[it & 1], msg, unsat_out, rec_run);
+        launch.cn_rec(first, vec, rec_t, g, stp, chan, post, rbuf[(it + 1) & 1], rbuf[it & 1], msg, unsat_out, rec_run);
       else if (lfree)
         launch.cn_lfree(first, vec, wide_mask, cn_t, g, stp, chan, post, m_in, m_out, unsat_out);
       else if (streaming)
@@ -178,27 +188,27 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       // iteration INSIDE this launch -- rounds 3-4 ran a small vn_free_rec_kernel launch behind it in every iteration, which
       // almost always found nothing: 4.4 us + a 5.7 us dispatch gap per iteration)
       if (quiet && it > 1 && opt_vn_event_) {
-        const dev::VnEvent<T> ev{d_free_var_.get<uint32_t>(), d_free_rs_.get<uint32_t>(), rbuf[(it - 1) & 1], n_free_};
-        launch.vn_event(vec, rec_w_, vn_keep_t, g_keep, st, chan, m_out, post, unsat_out, unsat[(it + 1) & 1],
-                        static_cast<int32_t>(it) - 1, ev);
+        launch.vn_event(vec, vn_keep_t, g_keep, st, chan, m_out, post, unsat_out, unsat[(it + 1) & 1],
+                        static_cast<int32_t>(it) - 1, d_free_var_.get<uint32_t>(), d_free_rs_.get<uint32_t>(), rbuf[(it - 1) & 1],
+                        n_free_);
       } else {
         launch.vn(lfree, vec, lfree ? vn_keep_t : vn_t, lfree ? g_keep : g, st, chan, m_out, post,
                   first ? nullptr : unsat_out, unsat[(it + 1) & 1], static_cast<int32_t>(it) - 1);
         if (quiet && it > 1)
-          launch.vn_free_rec(vec, rec_w_, vn_event_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[(it - 1) & 1], post,
+          launch.vn_free_rec(vec, vn_event_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[(it - 1) & 1], post,
                              static_cast<int32_t>(it) - 1);
       }
       timed_end(kKernelVar, s);
       if (checkpoint_due(it) || tail_checkpoint(it)) {
         // what the next iteration reads: the records of this one (the per-edge messages have been consumed)
         if (records)
-          compact(max_iterations - it, rbuf[it & 1], true, m * rec_w_);
+          compact(max_iterations - it, rbuf[it & 1].mag, true, rec_rows, rbuf[it & 1].flags, m);
         else
           compact(max_iterations - it, m_out, true, static_cast<uint32_t>(e_));
       }
     }
     if (records && max_iterations > 0) {
-      launch.vn_free_rec(vec, rec_w_, vn_free_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[max_iterations & 1], post, -1);
+      launch.vn_free_rec(vec, vn_free_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[max_iterations & 1], post, -1);
     } else if (lfree && max_iterations > 0) {
       // posterior of the L-free variables after the last iteration (no later check-node pass
       // rebuilds it): one variable-node pass over just them; frozen codewords are skipped

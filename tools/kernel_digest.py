@@ -2,8 +2,21 @@
 """Per-kernel digest of a built library's gfx950 code: {demangled kernel name: sha1 of its disassembly without addresses}.
 Used to check that a refactoring of the host code / a split into translation units left every kernel's instructions as
 they were:  tools/kernel_digest.py old.so new.so  -> kernels only in one, kernels whose code differs.
-A third argument PATTERN=REPLACEMENT (a regular expression and its substitution) renames the first library's kernels before the
-comparison, for a change that renames kernels on purpose.  It is split at its first '=': PATTERN itself cannot contain one."""
+Further arguments PATTERN=REPLACEMENT (a regular expression and its substitution, applied in order) rename the first library's
+kernels before the comparison, for a change that renames kernels on purpose.  Each is split at its first '=': PATTERN itself
+cannot contain one.
+--no-params (anywhere on the command line) compares the kernels by their names without the parameter lists: a parameter whose
+type becomes a dependent name (a typedef of a traits template) demangles differently though it is the same type.  Overloads
+that differ in their parameters alone then count as one name with several bodies, compared as a multiset.
+
+Example, the change that gave the flooding record kernels a `bool F16` (16-bit flags) -- fourth template argument of
+cn_minsum_rec_kernel, last of vn_free_rec_kernel and of vn_kernel (profiles/record_flags.txt has the output):
+  tools/kernel_digest.py parent.so new.so --no-params \
+      '(cn_minsum_rec_kernel<\w+, \d+, \d+), =\\1, false, ' \
+      '(vn_free_rec_kernel<\w+, \d+, \d+)>=\\1, false>' \
+      '(vn_kernel<[^>]*)>=\\1, false>'
+lists the kernels only in the second library (the F16 = true instantiations) and exits 1 if there are any, or if a body of the
+first is missing or differs."""
 import hashlib
 import os
 import re
@@ -55,10 +68,27 @@ def digests(path):
     return out
 
 
+def without_params(name):
+    """`void ns::kernel<...>(A, B)` -> `void ns::kernel<...>`"""
+    if not name.endswith(")"):
+        return name
+    depth = 0
+    for i in range(len(name) - 1, -1, -1):
+        depth += {")": 1, "(": -1}.get(name[i], 0)
+        if depth == 0:
+            return name[:i]
+    return name
+
+
 if __name__ == "__main__":
+    no_params = "--no-params" in sys.argv
+    sys.argv = [x for x in sys.argv if x != "--no-params"]
     a, b = digests(sys.argv[1]), digests(sys.argv[2])
-    if len(sys.argv) > 3:
-        pattern, replacement = sys.argv[3].split("=", 1)
+    if no_params:
+        a, b = ({k2: sum((v for k, v in d.items() if without_params(k) == k2), []) for k2 in {without_params(k) for k in d}}
+                for d in (a, b))
+    for rename in sys.argv[3:]:
+        pattern, replacement = rename.split("=", 1)
         renamed = {}
         for k, v in a.items():
             renamed.setdefault(re.sub(pattern, replacement, k), []).extend(v)
