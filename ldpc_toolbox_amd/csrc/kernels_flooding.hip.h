@@ -879,6 +879,13 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     b_rout.b = row_buf(rec_out + tile_base(b0, g.n_rows * RECW, sc), uint64_t(g.n_rows) * RECW * row_bytes - in_tile);
   }
   const uint32_t rec_bytes = Rec::kRows * row_bytes;
+  // What a row hands to the next row of its walk, for the variable the two share (below): a pack per lane, private to the
+  // lane -- written and read by the same thread in program order, so no barrier -- and double-buffered by the parity of the
+  // step (`ph`): a long row may write its own hand-off in an early round and read the previous row's in a later one.
+  // In LDS and not in registers: held in registers across the step, the two packs cost the steady-state f32 pack-of-4
+  // kernel 8 VGPRs (96 -> 104) and with them the fifth wave per SIMD.  16 KiB per workgroup at most.
+  __shared__ Pack<T, VEC> carry_chan[2][256], carry_msg[2][256];
+  static_assert(sizeof(Pack<T, VEC>) * 256 * 4 <= 16384, "the hand-off arrays: 16 KiB per workgroup at most");
   uint64_t odd_m[VEC];  // lane masks (SGPR pairs): codeword k of the lane has seen an odd row
 #pragma unroll
   for (int k = 0; k < VEC; k++) odd_m[k] = 0;
@@ -888,13 +895,16 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     const uint32_t dir = (r & 1u) ? 0xFFFFFFFFu : 1u;  // +1 / -1 (row numbers wrap: an invalid row is >= n_rows)
     uint32_t c = (r & 1u) ? hi - 1 : lo;
     // own = record of the current row, nxt = record of the row the walk reaches next (this row's peer now, `own`
-    // one step later); carry = the message the PREVIOUS row of the walk sent to the variable it shares with this
-    // one (it had that value in hand as its own message: the previous row's record need not be kept)
+    // one step later); carry_msg = the message the PREVIOUS row of the walk sent to the variable it shares with this
+    // one (it had that value in hand as its own message: the previous row's record need not be kept); carry_chan = that
+    // variable's channel row as the previous row loaded it: this row does not fetch it again (the second fetch, a whole
+    // row step later, found it in no cache).  Both start empty with every run, in either direction.
     Rec recA, recB;
-    T carry[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; k++) carry[k] = T(0.0);
-    uint32_t carry_slot = kAuxNone;  // slot of the previous row whose old message `carry` holds
+    uint32_t carry_slot = kAuxNone;  // slot of the previous row whose old message carry_msg holds
+    // the variable whose channel row carry_chan holds (wave-uniform).  Matched by variable, not by slot: two degree-2
+    // variables may join the same pair of rows; one is carried, the other loads.  Never a degree-1 variable or one whose
+    // peer is a far row: only an edge with `prow == cn` hands anything on.
+    uint32_t carry_var = kAuxNone;
     uint32_t e0 = row_ptr[c], e1 = row_ptr[c + 1], ne0 = 0, ne1 = 0;
     if (c + dir < n_rows) {
       ne0 = row_ptr[c + dir];
@@ -908,13 +918,13 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     }
     if (!FIRST) recA.load(b_rin, lane_off, c * rec_bytes, row_bytes);
 
-    auto row_step = [&](Rec &own, Rec &nxt) {
+    auto row_step = [&](Rec &own, Rec &nxt, uint32_t ph) {
       const uint32_t d = e1 - e0, cn = c + dir, cp = c - dir;
       if (!FIRST && cn < n_rows) nxt.load(b_rin, lane_off, cn * rec_bytes, row_bytes);
       Pack<T, VEC> lv[U];
 #pragma unroll
       for (int u = 0; u < U; u++)
-        if (uint32_t(u) < d)
+        if (uint32_t(u) < d && cols[u] != carry_var)  // (wave-uniform; the carried row: `edge` takes it from carry_chan)
           lv[u] = buf_load<T, VEC, false>((peers[u] & kPeerKeep) ? b_post : b_chan, lane_off,
                                           cols[u] * row_bytes);
       // the next row's indices and the range of the row after it: scalar loads that complete while this row's
@@ -942,12 +952,13 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
         par_m[k] = 0;
       }
       uint32_t next_carry_slot = kAuxNone;
-      T next_carry[VEC];
-#pragma unroll
-      for (int k = 0; k < VEC; k++) next_carry[k] = T(0.0);  // (read below whether or not an edge has set it)
-      // one edge: slot, variable, peer word, the loaded soft value (posterior, or channel LLR for an L-free variable)
-      auto edge = [&](uint32_t slot, uint32_t var, uint32_t peer, const Pack<T, VEC> &lvu) {
+      uint32_t next_carry_var = kAuxNone;
+      // one edge: slot, variable, peer word, the loaded soft value (posterior, or channel LLR for an L-free variable);
+      // `have`: `loaded` is valid also for the carried variable (the later rounds of a long row)
+      auto edge = [&](uint32_t slot, uint32_t var, uint32_t peer, const Pack<T, VEC> loaded, bool have) {
         const bool lfree = !(peer & kPeerKeep);
+        Pack<T, VEC> lvu = loaded;
+        if (!have && var == carry_var) lvu = carry_chan[ph ^ 1u][threadIdx.x];
         const uint32_t prow = (peer >> 6) & kPeerRowMask, pslot = peer & 63u;
         const bool single = prow == kPeerSingle;
         // the variable's other message (wave-uniform choice of where it comes from)
@@ -958,7 +969,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
             for (int k = 0; k < VEC; k++) m_other[k] = nxt.value(pslot, k);
           } else if (prow == cp && pslot == carry_slot) {
 #pragma unroll
-            for (int k = 0; k < VEC; k++) m_other[k] = carry[k];
+            for (int k = 0; k < VEC; k++) m_other[k] = carry_msg[ph ^ 1u][threadIdx.x].v[k];
           } else {
             Rec far;  // not a neighbour inside the run: fetch the peer's record
             far.load(b_rin, lane_off, prow * rec_bytes, row_bytes);
@@ -970,7 +981,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
             for (int k = 0; k < VEC; k++) m_other[k] = fresh[k] ? T(0.0) : m_other[k];
           }
         }
-        Pack<T, VEC> lnew;
+        Pack<T, VEC> lnew, sent;
 #pragma unroll
         for (int k = 0; k < VEC; k++) {
           T l = lvu.v[k];
@@ -981,7 +992,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
             if (lfree) l = l + (single ? m_own : (m_own + m_other[k]));  // chan + (m_a + m_b)
           }
           lnew.v[k] = l;
-          if (lfree && !FIRST && prow == cn) next_carry[k] = m_own;
+          sent.v[k] = m_own;
           const T x = FIRST ? l : (l - m_own);
           const T a = m_abs(x);
           if (x < T(0.0)) sgn[k] |= W(1) << slot;
@@ -994,7 +1005,14 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
             min2[k] = a;
           }
         }
-        if (lfree && !FIRST && prow == cn) next_carry_slot = slot;
+        if (lfree && !FIRST && prow == cn) {
+          next_carry_slot = slot;
+          carry_msg[ph][threadIdx.x] = sent;
+        }
+        if (lfree && !single && prow == cn) {  // the next row of the walk reads the same channel row
+          next_carry_var = var;
+          carry_chan[ph][threadIdx.x] = lvu;
+        }
         if (lfree && write_post && (peer & kPeerWriter)) {
           if (all_live) {
             buf_store<T, VEC, false>(b_post, lane_off, var * row_bytes, lnew);
@@ -1007,7 +1025,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
       };
 #pragma unroll
       for (int u = 0; u < U; u++)
-        if (uint32_t(u) < d) edge(u, cols[u], peers[u], lv[u]);
+        if (uint32_t(u) < d) edge(u, cols[u], peers[u], lv[u], false);
       if constexpr (LONG)
       for (uint32_t i0 = U; i0 < d; i0 += U) {  // rows longer than U: further rounds of U loads in flight
         uint32_t cv[U], pv[U];
@@ -1019,14 +1037,18 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
         }
 #pragma unroll
         for (int u = 0; u < U; u++)
-          if (i0 + u < d) lw[u] = buf_load<T, VEC, false>((pv[u] & kPeerKeep) ? b_post : b_chan, lane_off, cv[u] * row_bytes);
+          if (i0 + u < d) {
+            if (cv[u] == carry_var)
+              lw[u] = carry_chan[ph ^ 1u][threadIdx.x];
+            else
+              lw[u] = buf_load<T, VEC, false>((pv[u] & kPeerKeep) ? b_post : b_chan, lane_off, cv[u] * row_bytes);
+          }
 #pragma unroll
         for (int u = 0; u < U; u++)
-          if (i0 + u < d) edge(i0 + u, cv[u], pv[u], lw[u]);
+          if (i0 + u < d) edge(i0 + u, cv[u], pv[u], lw[u], true);
       }
       carry_slot = next_carry_slot;
-#pragma unroll
-      for (int k = 0; k < VEC; k++) carry[k] = next_carry[k];
+      carry_var = next_carry_var;
       if (d != 0) {
         // the new record: flip[slot] = (parity of all signs) ^ (x_slot < 0)
         Rec out;
@@ -1082,8 +1104,8 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     };
     // two rows per round: the records alternate between recA and recB, no register copies
     for (uint32_t i = lo; i < hi; i += 2) {
-      row_step(recA, recB);
-      if (i + 1 < hi) row_step(recB, recA);
+      row_step(recA, recB, 0);
+      if (i + 1 < hi) row_step(recB, recA, 1);
     }
   }
   if (!FIRST) {
