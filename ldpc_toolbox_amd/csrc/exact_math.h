@@ -12,8 +12,10 @@
 //   log1pf, expm1f, tanhf   the Sun fdlibm float routines
 // Every constant was checked against the libm binary; the f32 functions are compared with the
 // host libm exhaustively over all 2^32 arguments (tools/check_exact_math.cpp), the f64 ones on
-// 2e9 sampled arguments each (tools/check_exact_math64.cpp); tests/test_exact_math.py re-checks a
-// sample in the CPU suite.
+// 2e9 sampled arguments each (tools/check_exact_math64.cpp) and, as DEVICE code, on every double within
+// 4096 ulps of each class boundary plus 2^26 random arguments each, against glibc and against the host
+// build (tools/check_exact_math64_device.hip on the cases of tests/exact_math64_cases.h);
+// tests/test_exact_math.py re-checks a sample and the class boundaries in the CPU suite.
 // Works as host code (for that test) and as HIP device code; needs -ffp-contract=off.
 //
 // Provenance and licences of the algorithms re-implemented here (no source text was copied; the

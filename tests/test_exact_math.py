@@ -104,3 +104,77 @@ def test_device_functions_equal_glibc_on_every_float():
     r = subprocess.run([exe], capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, r.stdout + r.stderr
     assert r.stdout.count("2^32 arguments: 0 mismatches") == 11 and "mismatches   e.g." not in r.stdout, r.stdout
+
+
+# ---- the f64 functions on the argument set of tests/exact_math64_cases.h ------------------------------------------------
+
+SRC64_CASES = r"""
+#include <stdio.h>
+#include <algorithm>
+#include <atomic>
+#include <thread>
+#include "%s/tests/exact_math64_cases.h"
+int main() {
+  const std::vector<double> edge = em64::edges();
+  if (edge.size() != em64::kEdges) return 2;
+  const unsigned nthreads = std::min(std::max(1u, std::thread::hardware_concurrency()), 16u);
+  for (int f = 0; f < em64::kCount; f++) {
+    std::atomic<unsigned long long> bad{0}, n{0};
+    std::vector<std::thread> th;
+    for (unsigned t = 0; t < nthreads; t++)
+      th.emplace_back([&, t] {
+        unsigned long long lb = 0, ln = 0;
+        for (uint64_t i = t; i < em64::kBoundaryCount; i += nthreads, ln++) {
+          const double x = em64::boundary_arg(edge.data(), i);
+          lb += !em64::same(em64::mine(f, x), em64::glibc(f, x));
+        }
+        bad += lb;
+        n += ln;
+      });
+    for (auto &x : th) x.join();
+    printf("%%s\t%%llu\t%%llu\n", em64::name(f), n.load(), bad.load());
+  }
+  return 0;
+}
+"""
+
+
+def test_exact_math_f64_class_boundaries_match_host_libm(tmp_path):
+    """the HOST build of exact_math.h against glibc on set (a) of exact_math64_cases.h -- every double within 4096 ulps of
+    each of the 2731 class boundaries, both signs -- for exp, log, log1p, expm1, tanh, the fused phi and the three
+    compositions the f64 kernels form (a few seconds)"""
+    src = tmp_path / "t64cases.cpp"
+    src.write_text(SRC64_CASES % ROOT)
+    exe = tmp_path / "t64cases"
+    subprocess.run(["g++", "-O2", "-std=c++17", "-mfma", "-ffp-contract=off", "-pthread", str(src), "-o", str(exe), "-lm"],
+                   check=True)
+    lines = subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines()
+    rows = [line.split("\t") for line in lines]
+    assert [r[0] for r in rows] == ["exp", "log", "log1p", "expm1", "tanh", "phi", "log1p(exp(-|x|))", "0.5*log1p(2x/(1-x))",
+                                    "tanh(clamp(x,-18,18))"]
+    for fn, n, bad in rows:
+        assert int(n) == 2731 * 2 * 8193 == 44_750_166, (fn, n)
+        assert int(bad) == 0, f"{fn}: {bad} of {n} results differ from the host libm"
+
+
+CHECK64_FLAGS = ["-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math", "--offload-arch=gfx950", "-pthread"]
+
+
+@pytest.mark.gpu
+def test_device_f64_functions_equal_glibc_and_the_host_build():
+    """tools/check_exact_math64_device.hip: the DEVICE build of the nine f64 functions of exact_math64_cases.h on its whole
+    argument set (44 750 166 boundary neighbours + 2^26 random arguments each), against this box's glibc and against the
+    host build of the header.  The device kernels take well under a second; the host comparison a few seconds
+    (profiles/exact_math64_device.txt)."""
+    exe = os.path.join(ROOT, "tools", "mb", "check_device64")
+    src = os.path.join(ROOT, "tools", "check_exact_math64_device.hip")
+    deps = [src, os.path.join(ROOT, "tests", "exact_math64_cases.h"), os.path.join(ROOT, "ldpc_toolbox_amd", "csrc", "exact_math.h")]
+    if not os.path.exists(exe) or os.path.getmtime(exe) < max(map(os.path.getmtime, deps)):
+        os.makedirs(os.path.dirname(exe), exist_ok=True)
+        subprocess.run(["/opt/rocm/bin/hipcc"] + CHECK64_FLAGS + [src, "-o", exe], check=True)
+    r = subprocess.run(["timeout", "-k", "10", "300", exe], capture_output=True, text=True)
+    print(r.stdout)
+    assert r.returncode == 0, r.stdout + r.stderr
+    clean = [line for line in r.stdout.splitlines()
+             if "111859030 arguments: 0 mismatches vs glibc, 0 mismatches vs the host build" in line]
+    assert len(clean) == 9 and "first at" not in r.stdout, r.stdout
