@@ -266,7 +266,9 @@ int32_t ldpc_toolbox_sim_generate(void *sim, double ebn0_db, uint64_t seed, uint
                                   size_t frames, float *llrs, uint32_t *pool_index);
 /* The pool: messages [pool][k] and transmitted (punctured) codewords [pool][n_tx]; either may be NULL. */
 int32_t ldpc_toolbox_sim_pool(void *sim, uint8_t *messages, uint8_t *tx_bits);
-/* "k", "n", "n_tx", "pool", "modulation", "interleaving"; "preferred_batch" (frames per run call that fill one
+/* "k", "n", "n_tx", "pool", "modulation" (bits per symbol of what generates the frames: of the constellation while one
+ * is set), "interleaving", "constellation" (read-only, 0/1: ldpc_toolbox_sim_set_constellation is in force), "max_log"
+ * (read-only, 0/1: its fold step); "preferred_batch" (frames per run call that fill one
  * group of the decoder: 4096, more for small graphs); of the last run call: "pooled_frames" (frames that went
  * through the straggler pool, below); "streamed_frames" and "stream_iterations" are accepted and read 0.
  * returns 0 or -1. */
@@ -284,10 +286,26 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value);
  * Any other key is forwarded to the simulator's decoder (see ldpc_toolbox_decoder_set).
  * returns 0, or -1 (unknown key / unusable value, message via ldpc_toolbox_last_error). */
 int32_t ldpc_toolbox_sim_set(void *sim, const char *key, int64_t value);
+/* Any constellation of PART 4 as the simulator's modulation.  demod: a handle of ldpc_toolbox_demod_ctor[_table]; its
+ * constellation is copied, the handle may be destroyed afterwards.  NULL returns to what the "modulation" key selects
+ * (which ldpc_toolbox_sim_set keeps recording while a constellation is in force).  A "BPSK" handle selects the BPSK
+ * generator of "modulation" = 1.  Any other: n_tx must be a multiple of bits_per_symbol, and the table's mean energy
+ * sum_V |p_V|^2 / 2^m must lie within 1e-6 of 1 -- noise_sigma stays sqrt(0.5 / (rate * m * EbN0))
+ * (src/simulation/ber.rs:299-302), which presumes unit symbol energy; a table of another energy is refused rather than
+ * simulated on a shifted Eb/N0 axis.  max_log != 0: the demapper's max-log fold step instead of max*.
+ * DEFINED RESULT: for either fold step the LLRs of frame f are what ldpc_toolbox_mod_run_f64 (the frame's pooled
+ * codeword, the simulator's "interleaving"), then ldpc_toolbox_awgn_run_f64 (the run's seed, frame f, noise_sigma),
+ * then ldpc_toolbox_demod_run_f64 (the same noise_sigma, interleaving and max_log; the handle's energy term) give, each
+ * value rounded once to float.  With the "8PSK" handle and max_log = 0 that is bit for bit what "modulation" = 3
+ * produces.  One fused kernel computes it, one thread per symbol; the symbols are never stored.
+ * Resets the straggler-pooling budget, as "modulation" does.  returns 0, or -1 with a message and nothing changed. */
+int32_t ldpc_toolbox_sim_set_constellation(void *sim, void *demod, int32_t max_log);
 
 /* ===================================================================================
- * PART 4 -- batched soft demapper on the GPU (reference: trait Demodulator, src/simulation/modulation.rs:109-281,
- * and the LLR deinterleaver, src/simulation/interleaving.rs:65-86; one frame per call there)
+ * PART 4 -- batched soft demapper, modulator and AWGN channel on the GPU (reference: trait Demodulator,
+ * src/simulation/modulation.rs:109-281, and the LLR deinterleaver, src/simulation/interleaving.rs:65-86; trait Modulator,
+ * modulation.rs:40-62 with the bit interleaver, interleaving.rs:40-58; AwgnChannel::add_noise, src/simulation/channel.rs:60-81;
+ * one frame per call there)
  * =================================================================================== */
 
 /* A demodulator handle turns [batch][symbols_len] received symbols into [batch][llrs_len] channel LLRs in codeword
@@ -328,6 +346,43 @@ int32_t ldpc_toolbox_demod_run_f32_device(void *demod, float *llrs, size_t llrs_
 int32_t ldpc_toolbox_demod_run_f64_device(void *demod, double *llrs, size_t llrs_len, const double *symbols,
                                           size_t symbols_len, size_t batch, double noise_sigma, int32_t interleaving,
                                           int32_t max_log, void *hip_stream);
+/* The handle is a constellation: it maps as well as demaps.  bits [batch][bits_len], one byte per bit with the encoder's
+ * convention (a byte equal to 1 is a one, anything else a zero) -> symbols [batch][symbols_len], (re, im) pairs.
+ * Interleaved position i = m * symbol + j carries the bit of codeword position
+ * deinterleaved_position(i) = c * rows + r, with columns = |interleaving|, rows = bits_len / columns, r = i / columns,
+ * c' = i % columns, c = interleaving < 0 ? columns - 1 - c' : c'  (i itself for interleaving == 0): the bit interleaver of
+ * src/simulation/interleaving.rs:40-58, the inverse of what ldpc_toolbox_demod_run_* undoes.  V = sum_j b_j << (m-1-j),
+ * and the symbol is (p_V.re, p_V.im): the handle's doubles for _f64, each rounded once to float for _f32.  A "BPSK"
+ * handle writes reals: +1 for a one, -1 for a zero (modulation.rs:87-95).
+ * A null handle, bits_len != bits_per_symbol * symbols_len, bits_len > 0x7fffffff or |interleaving| not dividing bits_len:
+ * LDPC_TOOLBOX_ERR_ARGUMENT before the GPU is touched, nothing written.  Without a GPU LDPC_TOOLBOX_ERR_DEVICE; batch == 0
+ * returns 0.  Host pointers (staged through the handle's buffers) or, _device, device pointers and a hipStream_t as in
+ * ldpc_toolbox_demod_run_*_device.  returns 0 or an LDPC_TOOLBOX_ERR_* code. */
+int32_t ldpc_toolbox_mod_run_f32(void *demod, float *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                 size_t batch, int32_t interleaving);
+int32_t ldpc_toolbox_mod_run_f64(void *demod, double *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                 size_t batch, int32_t interleaving);
+int32_t ldpc_toolbox_mod_run_f32_device(void *demod, float *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                        size_t batch, int32_t interleaving, void *hip_stream);
+int32_t ldpc_toolbox_mod_run_f64_device(void *demod, double *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                        size_t batch, int32_t interleaving, void *hip_stream);
+/* AWGN in place on symbols [batch][symbols_len] (src/simulation/channel.rs:60-81); row r is frame first_frame + r.  The
+ * noise is the simulator's: Philox4x32-10 with key (seed low word, seed high word) and counter (attempt, pair, frame low
+ * word, frame high word), and the polar method in float over the block's two candidate points (v = (w >> 8) * 2^-23 - 1;
+ * the first with 0 < s = v1^2 + v2^2 < 1 gives f = sqrt(-2 * logf(s) / s), z0 = v1 * f, z1 = v2 * f; else the next attempt).
+ * Complex handles: symbol s uses pair s, re += sigma * z0, im += sigma * z1.  "BPSK" handle (real symbols): position j
+ * uses pair j / 2, z0 for even j, z1 for odd j -- the simulator's BPSK keying.  _f64: x + sigma * (double)z.
+ * _f32: x + (float)sigma * z.  Each product and each sum is rounded once.
+ * noise_sigma must be finite and >= 0 (channel.rs:52-53) and symbols_len <= 0x7fffffff, else LDPC_TOOLBOX_ERR_ARGUMENT with
+ * nothing written.  Other behaviour as ldpc_toolbox_mod_run_*. */
+int32_t ldpc_toolbox_awgn_run_f32(void *demod, float *symbols, size_t symbols_len, size_t batch, double noise_sigma,
+                                  uint64_t seed, uint64_t first_frame);
+int32_t ldpc_toolbox_awgn_run_f64(void *demod, double *symbols, size_t symbols_len, size_t batch, double noise_sigma,
+                                  uint64_t seed, uint64_t first_frame);
+int32_t ldpc_toolbox_awgn_run_f32_device(void *demod, float *symbols, size_t symbols_len, size_t batch, double noise_sigma,
+                                         uint64_t seed, uint64_t first_frame, void *hip_stream);
+int32_t ldpc_toolbox_awgn_run_f64_device(void *demod, double *symbols, size_t symbols_len, size_t batch, double noise_sigma,
+                                         uint64_t seed, uint64_t first_frame, void *hip_stream);
 /* key: "bits_per_symbol", "points", "energy_term", "device" (-1 until the first run made the device state).
  * returns 0, or -1 for an unknown key. */
 int32_t ldpc_toolbox_demod_get(void *demod, const char *key, int64_t *value);

@@ -45,6 +45,7 @@ SYMBOLS = [
     "ldpc_toolbox_sim_pool",
     "ldpc_toolbox_sim_get",
     "ldpc_toolbox_sim_set",
+    "ldpc_toolbox_sim_set_constellation",
     "ldpc_toolbox_demod_ctor",
     "ldpc_toolbox_demod_ctor_table",
     "ldpc_toolbox_demod_dtor",
@@ -52,6 +53,14 @@ SYMBOLS = [
     "ldpc_toolbox_demod_run_f64",
     "ldpc_toolbox_demod_run_f32_device",
     "ldpc_toolbox_demod_run_f64_device",
+    "ldpc_toolbox_mod_run_f32",
+    "ldpc_toolbox_mod_run_f64",
+    "ldpc_toolbox_mod_run_f32_device",
+    "ldpc_toolbox_mod_run_f64_device",
+    "ldpc_toolbox_awgn_run_f32",
+    "ldpc_toolbox_awgn_run_f64",
+    "ldpc_toolbox_awgn_run_f32_device",
+    "ldpc_toolbox_awgn_run_f64_device",
     "ldpc_toolbox_demod_get",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
@@ -188,6 +197,8 @@ def lib():
     L.ldpc_toolbox_sim_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
     L.ldpc_toolbox_sim_set.restype = i32
     L.ldpc_toolbox_sim_set.argtypes = [vp, cp, C.c_int64]
+    L.ldpc_toolbox_sim_set_constellation.restype = i32
+    L.ldpc_toolbox_sim_set_constellation.argtypes = [vp, vp, i32]
     L.ldpc_toolbox_demod_ctor.restype = vp
     L.ldpc_toolbox_demod_ctor.argtypes = [cp, i32]
     L.ldpc_toolbox_demod_ctor_table.restype = vp
@@ -201,6 +212,18 @@ def lib():
         f = getattr(L, "ldpc_toolbox_demod_run_" + name + "_device")
         f.restype = i32
         f.argtypes = [vp, vp, sz, vp, sz, sz, C.c_double, i32, i32, vp]
+        f = getattr(L, "ldpc_toolbox_mod_run_" + name)
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, i32]
+        f = getattr(L, "ldpc_toolbox_mod_run_" + name + "_device")
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, i32, vp]
+        f = getattr(L, "ldpc_toolbox_awgn_run_" + name)
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, sz, C.c_double, u64, u64]
+        f = getattr(L, "ldpc_toolbox_awgn_run_" + name + "_device")
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, sz, C.c_double, u64, u64, vp]
     L.ldpc_toolbox_demod_get.restype = i32
     L.ldpc_toolbox_demod_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
     L.ldpc_toolbox_code_alist.restype = sz

@@ -122,6 +122,32 @@ def sweep(sim: Simulator, ebn0s_db, max_iterations=100, max_frame_errors=100, mi
     return results
 
 
+def read_constellation(path):
+    """--constellation FILE: 2^m lines `re im` (m = 1..5), line V the point of the symbol whose bits, first bit most
+    significant, spell V.  -> (points scaled to unit mean energy, whether their energies differ)"""
+    rows = [line.split() for line in open(path) if line.strip() and not line.lstrip().startswith("#")]
+    if any(len(r) != 2 for r in rows):
+        raise ValueError(f"{path}: every line must be `re im`")
+    pts = np.array([complex(float(r[0]), float(r[1])) for r in rows], dtype=np.complex128)
+    if pts.size not in (2, 4, 8, 16, 32):
+        raise ValueError(f"{path}: {pts.size} points; 2, 4, 8, 16 or 32 are needed")
+    energy = pts.real * pts.real + pts.imag * pts.imag
+    mean = float(energy.mean())
+    if not (np.isfinite(mean) and mean > 0.0):
+        raise ValueError(f"{path}: the points have no finite positive mean energy")
+    pts = pts / np.sqrt(mean)
+    return pts, bool(np.ptp(energy) > 1e-9 * mean)
+
+
+def make_modulation(a, device):
+    """what `Simulator(modulation=...)` takes for the driver's --modulation / --constellation options"""
+    if getattr(a, "constellation", None):
+        from .demodulator import Demodulator
+        pts, energy_term = read_constellation(a.constellation)
+        return Demodulator(pts, energy_term=energy_term, device=device)
+    return a.modulation
+
+
 def format_details(a, sim, world: int) -> str:
     """src/cli/ber.rs:161-211 write_details: the parameter block the reference writes to the terminal
     and at the top of its result files ("Number of worker threads" reads "Number of GPUs" here)"""
@@ -134,8 +160,14 @@ def format_details(a, sim, world: int) -> str:
         lines.append(f" - Maximum run time per Eb/N0: {format_duration(a.max_time)}")
     if a.max_frames is not None:
         lines.append(f" - Maximum number of frames per Eb/N0: {a.max_frames}")     # this build's addition
-    lines += [f" - Number of GPUs: {world}", "Channel:", f" - Modulation: {a.modulation}", "LDPC code:",
-              f" - alist: {a.alist if a.alist else a.code}"]
+    lines += [f" - Number of GPUs: {world}", "Channel:"]
+    if getattr(a, "constellation", None):                                             # this build's additions
+        lines += [f" - Modulation: constellation {a.constellation}", f" - Bits per symbol: {sim.get('modulation')}"]
+    else:
+        lines.append(f" - Modulation: {a.modulation}")
+    if getattr(a, "max_log", False):
+        lines.append(" - Demodulator: max-log")
+    lines += ["LDPC code:", f" - alist: {a.alist if a.alist else a.code}"]
     if a.puncturing:
         lines.append(f" - Puncturing pattern: {a.puncturing}")
     if a.interleaving:
@@ -154,7 +186,12 @@ def main(argv=None):
     ap.add_argument("--alist", help="alist file (instead of --code)")
     ap.add_argument("--decoder", default="Phif64", help="decoder implementation (cli/ber.rs:49 default Phif64)")
     ap.add_argument("--puncturing", default="")
-    ap.add_argument("--modulation", default="BPSK", choices=["BPSK", "8PSK"], help="cli/ber.rs:52-53")
+    ap.add_argument("--modulation", default="BPSK", choices=["BPSK", "QPSK", "8PSK"], help="cli/ber.rs:52-53; QPSK: this build's")
+    ap.add_argument("--constellation", metavar="FILE",
+                    help="instead of --modulation: 2^m lines `re im` (m = 1..5), line V = the point of the bits of V, first "
+                         "bit most significant; scaled to unit mean energy, demapped with the energy term when the points' "
+                         "energies differ")
+    ap.add_argument("--max-log", action="store_true", help="max-log demapper (with QPSK or --constellation)")
     ap.add_argument("--interleaving", type=int, default=0,
                     help="interleaver columns, negative = read rows backwards (cli/ber.rs:55-59)")
     ap.add_argument("--codes", help='several codes as ONE job (sweep_scheduler.py): comma-separated specs, "dvbs2:normal" = the 11 '
@@ -232,7 +269,7 @@ def main(argv=None):
         return res
     alist = open(a.alist).read() if a.alist else _capi.code_alist(a.code)
     sim = Simulator(alist, a.decoder, a.puncturing, device=local, pool_size=a.pool_size, pool_seed=a.seed + 1,
-                    modulation=a.modulation, interleaving=a.interleaving)
+                    modulation=make_modulation(a, local), interleaving=a.interleaving, max_log=a.max_log)
     out = open(a.output_file, "w") if (a.output_file and rank == 0) else None
     out_ldpc = open(a.output_file_ldpc, "w") if (a.output_file_ldpc and a.bch_max_errors > 0 and rank == 0) else None
     details = format_details(a, sim, world)

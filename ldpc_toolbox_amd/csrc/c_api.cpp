@@ -243,6 +243,74 @@ int32_t demod_run(void *demod, void *llrs, size_t llrs_len, const void *symbols,
   return LDPC_TOOLBOX_ERR_DEVICE;
 }
 
+// the handle's device state, made at the first call that needs it: 0 or LDPC_TOOLBOX_ERR_DEVICE
+int32_t demod_device_state(DemodHandle *h) {
+  if (h->dev) return 0;
+  if (h->device < 0) {
+    set_error("LDPC_TOOLBOX_DEVICE is not a decimal GPU index");
+    return LDPC_TOOLBOX_ERR_DEVICE;
+  }
+  std::string err;
+  h->dev.reset(ldpc::DeviceDemodulator::create(h->c, h->device, &err));
+  if (!h->dev) {
+    set_error(err);
+    return LDPC_TOOLBOX_ERR_DEVICE;
+  }
+  return 0;
+}
+
+int32_t mod_run(void *demod, void *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len, size_t batch, bool f64,
+                int32_t interleaving, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<DemodHandle *>(demod);
+  if (!h) {
+    set_error("null demodulator handle");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (const char *why = ldpc::mod_argument_error(h->c, bits_len, symbols_len, interleaving)) {
+    set_error(why);
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (batch == 0 || bits_len == 0) return 0;
+  if (!symbols || !bits) {
+    set_error("null bit or symbol buffer");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (int32_t rc = demod_device_state(h)) return rc;
+  const int rc = on_device ? h->dev->mod_device(bits, symbols, f64, bits_len, symbols_len, batch, interleaving,
+                                                static_cast<hipStream_t>(stream))
+                           : h->dev->mod_host(bits, symbols, f64, bits_len, symbols_len, batch, interleaving);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+int32_t awgn_run(void *demod, void *symbols, size_t symbols_len, size_t batch, bool f64, double sigma, uint64_t seed,
+                 uint64_t first_frame, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<DemodHandle *>(demod);
+  if (!h) {
+    set_error("null demodulator handle");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (const char *why = ldpc::awgn_argument_error(symbols_len, sigma)) {
+    set_error(why);
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (batch == 0 || symbols_len == 0) return 0;
+  if (!symbols) {
+    set_error("null symbol buffer");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (int32_t rc = demod_device_state(h)) return rc;
+  const int rc = on_device ? h->dev->awgn_device(symbols, f64, symbols_len, batch, sigma, seed, first_frame,
+                                                 static_cast<hipStream_t>(stream))
+                           : h->dev->awgn_host(symbols, f64, symbols_len, batch, sigma, seed, first_frame);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
 template <typename F>
 int32_t decode_scalar(void *decoder, uint8_t *output, size_t output_len, const F *llrs, size_t llrs_len,
                       uint32_t max_iterations) {
@@ -662,6 +730,10 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value) {
     *value = s->modulation();
   else if (k == "interleaving")
     *value = s->interleaving();
+  else if (k == "constellation")  // 1 while ldpc_toolbox_sim_set_constellation is in force
+    *value = s->has_constellation() ? 1 : 0;
+  else if (k == "max_log")
+    *value = s->max_log() ? 1 : 0;
   else if (k == "streamed_frames" || k == "stream_iterations")  // (continuous batching: profiles/r03_continuous_batching.txt)
     *value = 0;
   else if (k == "pooled_frames")  // frames of the last run() call that went through the straggler pool
@@ -693,6 +765,19 @@ int32_t ldpc_toolbox_sim_set(void *sim, const char *key, int64_t value) {
     return ok ? 0 : -1;
   }
   return s->decoder()->set_option(k, value) ? 0 : -1;
+}
+
+int32_t ldpc_toolbox_sim_set_constellation(void *sim, void *demod, int32_t max_log) {
+  g_last_error.clear();
+  auto *s = static_cast<ldpc::Simulator *>(sim);
+  if (!s) {
+    set_error("null argument");
+    return -1;
+  }
+  auto *h = static_cast<DemodHandle *>(demod);
+  if (s->set_constellation(h ? &h->c : nullptr, max_log != 0)) return 0;
+  set_error(s->last_error());
+  return -1;
 }
 
 // ---- PART 4: batched soft demapper -----------------------------------------------------------------
@@ -741,6 +826,46 @@ int32_t ldpc_toolbox_demod_run_f64_device(void *demod, double *llrs, size_t llrs
                                           size_t symbols_len, size_t batch, double noise_sigma, int32_t interleaving,
                                           int32_t max_log, void *hip_stream) {
   return demod_run(demod, llrs, llrs_len, symbols, symbols_len, batch, true, noise_sigma, interleaving, max_log, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_mod_run_f32(void *demod, float *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                 size_t batch, int32_t interleaving) {
+  return mod_run(demod, symbols, symbols_len, bits, bits_len, batch, false, interleaving, false, nullptr);
+}
+
+int32_t ldpc_toolbox_mod_run_f64(void *demod, double *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                 size_t batch, int32_t interleaving) {
+  return mod_run(demod, symbols, symbols_len, bits, bits_len, batch, true, interleaving, false, nullptr);
+}
+
+int32_t ldpc_toolbox_mod_run_f32_device(void *demod, float *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                        size_t batch, int32_t interleaving, void *hip_stream) {
+  return mod_run(demod, symbols, symbols_len, bits, bits_len, batch, false, interleaving, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_mod_run_f64_device(void *demod, double *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                        size_t batch, int32_t interleaving, void *hip_stream) {
+  return mod_run(demod, symbols, symbols_len, bits, bits_len, batch, true, interleaving, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_awgn_run_f32(void *demod, float *symbols, size_t symbols_len, size_t batch, double noise_sigma,
+                                  uint64_t seed, uint64_t first_frame) {
+  return awgn_run(demod, symbols, symbols_len, batch, false, noise_sigma, seed, first_frame, false, nullptr);
+}
+
+int32_t ldpc_toolbox_awgn_run_f64(void *demod, double *symbols, size_t symbols_len, size_t batch, double noise_sigma,
+                                  uint64_t seed, uint64_t first_frame) {
+  return awgn_run(demod, symbols, symbols_len, batch, true, noise_sigma, seed, first_frame, false, nullptr);
+}
+
+int32_t ldpc_toolbox_awgn_run_f32_device(void *demod, float *symbols, size_t symbols_len, size_t batch, double noise_sigma,
+                                         uint64_t seed, uint64_t first_frame, void *hip_stream) {
+  return awgn_run(demod, symbols, symbols_len, batch, false, noise_sigma, seed, first_frame, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_awgn_run_f64_device(void *demod, double *symbols, size_t symbols_len, size_t batch, double noise_sigma,
+                                         uint64_t seed, uint64_t first_frame, void *hip_stream) {
+  return awgn_run(demod, symbols, symbols_len, batch, true, noise_sigma, seed, first_frame, true, hip_stream);
 }
 
 int32_t ldpc_toolbox_demod_get(void *demod, const char *key, int64_t *value) {

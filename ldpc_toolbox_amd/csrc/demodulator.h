@@ -15,6 +15,16 @@
 // f64 entries: all of it in f64.  f32 entries: exact = symbols widened, the f64 arithmetic, one rounding per LLR;
 // max-log = the same formulas in f32, scale and 0.5 * scale * e_V rounded to f32 once.
 // The kernels are in kernels_demod.hip.h; the host side (demodulator.hip.h) is part of the simulator's translation unit.
+//
+// The same handle is the transmit side (reference: trait Modulator, modulation.rs:40-62, and AwgnChannel::add_noise,
+// channel.rs:60-81); the kernels are in kernels_channel.hip.h.
+//   * modulator: bits [batch][bits_len] (a byte equal to 1 is a one, anything else a zero) -> symbols [batch][symbols_len].
+//     Interleaved position i = m * sym + j carries codeword position gen::deinterleaved_position(i, bits_len, interleaving)
+//     (the interleaver of interleaving.rs:40-58, which the demapper undoes); V = sum_j b_j << (m-1-j); the symbol is
+//     (p_V.re, p_V.im) -- the handle's doubles, or each rounded once to float.  BPSK: reals, +1 for a one, -1 for a zero.
+//   * AWGN, in place, row r = frame first_frame + r: symbol s gets (z0, z1) = gen::normal_pair(seed, frame, s),
+//     re += sigma * z0, im += sigma * z1; BPSK position j uses pair j / 2, z0 for even j and z1 for odd j (the keying of
+//     gen::awgn_llr_kernel).  f64: x + sigma * (double)z.  f32: x + (float)sigma * z.  Each product and sum rounded once.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -103,6 +113,41 @@ inline const char *demod_argument_error(const Constellation &c, size_t llrs_len,
   return nullptr;
 }
 
+// The same for a modulator call: bits [batch][bits_len] -> symbols [batch][symbols_len].
+inline const char *mod_argument_error(const Constellation &c, size_t bits_len, size_t symbols_len, int32_t interleaving) {
+  if (bits_len % c.bits != 0 || bits_len / c.bits != symbols_len) return "bits_len is not bits_per_symbol * symbols_len";
+  if (bits_len > 0x7fffffffu) return "frame length out of range for the modulator";
+  const uint64_t columns = static_cast<uint64_t>(interleaving < 0 ? -static_cast<int64_t>(interleaving) : interleaving);
+  if (columns != 0 && bits_len % columns != 0) return "interleaving does not divide bits_len";
+  return nullptr;
+}
+
+// ... and for an AWGN call on [batch][symbols_len] symbols (channel.rs:52-53: sigma >= 0; a noise pair is a 32-bit index)
+inline const char *awgn_argument_error(size_t symbols_len, double sigma) {
+  if (symbols_len > 0x7fffffffu) return "frame length out of range for the channel";
+  if (!(std::isfinite(sigma) && sigma >= 0.0)) return "noise_sigma must be finite and not negative";
+  return nullptr;
+}
+
+// mean symbol energy of a table: sum_V |p_V|^2 / 2^m (BPSK: 1)
+inline double mean_energy(const Constellation &c) {
+  if (c.bpsk) return 1.0;
+  double sum = 0.0;
+  for (uint32_t v = 0; v < c.points(); v++) sum += c.re[v] * c.re[v] + c.im[v] * c.im[v];
+  return sum / static_cast<double>(c.points());
+}
+
+// What the simulator asks of a constellation for frames of n_tx bits (nullptr), or why it refuses it: whole symbols, and
+// unit mean energy -- noise_sigma = sqrt(0.5 / (rate * m * EbN0)) (ber.rs:299-302) presumes it.
+inline const char *sim_constellation_error(const Constellation &c, size_t n_tx) {
+  if (c.bpsk) return nullptr;
+  if (c.bits < 1 || c.bits > kDemodMaxBits) return "bits_per_symbol must be 1..5";
+  if (n_tx % c.bits != 0) return "the transmitted length is not a multiple of bits_per_symbol";
+  const double e = mean_energy(c);
+  if (!(e >= 1.0 - 1e-6 && e <= 1.0 + 1e-6)) return "the constellation's mean energy is not 1 (the Eb/N0 axis presumes unit symbol energy)";
+  return nullptr;
+}
+
 class DeviceDemodulator {
  public:
   // nullptr (and *err) when there is no usable GPU: there is no CPU path here.
@@ -123,6 +168,16 @@ class DeviceDemodulator {
   // Host pointers: staged through device buffers of the handle, synchronous.
   int run_host(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
                int32_t interleaving, bool max_log);
+  // Modulator: bits [batch][bits_len] -> symbols, the arguments already checked (mod_argument_error); pointers and
+  // stream as in run_device / run_host.
+  int mod_device(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch,
+                 int32_t interleaving, hipStream_t stream);
+  int mod_host(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch,
+               int32_t interleaving);
+  // AWGN in place on symbols [batch][symbols_len] (awgn_argument_error)
+  int awgn_device(void *symbols, bool f64, size_t symbols_len, size_t batch, double sigma, uint64_t seed, uint64_t first_frame,
+                  hipStream_t stream);
+  int awgn_host(void *symbols, bool f64, size_t symbols_len, size_t batch, double sigma, uint64_t seed, uint64_t first_frame);
 
  private:
   DeviceDemodulator() = default;
@@ -130,6 +185,9 @@ class DeviceDemodulator {
   template <typename IO>
   void launch(const IO *symbols, IO *llrs, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
               int32_t interleaving, bool max_log, hipStream_t s);
+  // the launch stream of a device entry (ordered after the legacy default stream when it is the handle's own): -2 on failure
+  int begin(hipStream_t stream, hipStream_t *s);
+  int end(hipStream_t stream, hipStream_t s);
 
   Constellation c_;
   int device_ = -1;

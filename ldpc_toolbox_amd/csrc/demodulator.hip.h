@@ -6,6 +6,7 @@
 #include <memory>
 
 #include "demodulator.h"
+#include "kernels_channel.hip.h"
 #include "kernels_demod.hip.h"
 
 namespace ldpc {
@@ -105,25 +106,35 @@ void DeviceDemodulator::launch(const IO *symbols, IO *llrs, size_t symbols_len, 
   }
 }
 
-int DeviceDemodulator::run_device(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch,
-                                  double sigma, int32_t interleaving, bool max_log, hipStream_t stream) {
-  if (batch == 0 || llrs_len == 0) return 0;
+int DeviceDemodulator::begin(hipStream_t stream, hipStream_t *s) {
   DEMOD_TRY(hipSetDevice(device_));
-  hipStream_t s = stream ? stream : stream_;
+  *s = stream ? stream : static_cast<hipStream_t>(stream_);
   if (!stream) {
     // (the handle's stream is non-blocking: ordered explicitly after what the legacy default stream holds now)
     DEMOD_TRY(hipEventRecord(ev_default_, nullptr));
-    DEMOD_TRY(hipStreamWaitEvent(s, ev_default_, 0));
+    DEMOD_TRY(hipStreamWaitEvent(*s, ev_default_, 0));
   }
+  return 0;
+}
+
+int DeviceDemodulator::end(hipStream_t stream, hipStream_t s) {
+  DEMOD_TRY(hipGetLastError());
+  if (!stream) DEMOD_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+int DeviceDemodulator::run_device(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch,
+                                  double sigma, int32_t interleaving, bool max_log, hipStream_t stream) {
+  if (batch == 0 || llrs_len == 0) return 0;
+  hipStream_t s;
+  if (int rc = begin(stream, &s)) return rc;
   if (f64)
     launch(static_cast<const double *>(symbols), static_cast<double *>(llrs), symbols_len, llrs_len, batch, sigma, interleaving,
            max_log, s);
   else
     launch(static_cast<const float *>(symbols), static_cast<float *>(llrs), symbols_len, llrs_len, batch, sigma, interleaving,
            max_log, s);
-  DEMOD_TRY(hipGetLastError());
-  if (!stream) DEMOD_TRY(hipStreamSynchronize(s));
-  return 0;
+  return end(stream, s);
 }
 
 int DeviceDemodulator::run_host(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch,
@@ -139,6 +150,106 @@ int DeviceDemodulator::run_host(const void *symbols, void *llrs, bool f64, size_
     return rc;
   // (the only write to the caller's buffer: after an earlier failure nothing has been written)
   DEMOD_TRY(hipMemcpyAsync(llrs, d_out_.get(), out_bytes, hipMemcpyDeviceToHost, stream_));
+  DEMOD_TRY(hipStreamSynchronize(stream_));
+  return 0;
+}
+
+// ---- the transmit side: modulator and AWGN channel (kernels_channel.hip.h) ------------------------------------------
+
+namespace {
+// passes of whole frames whose thread count fits a 31-bit grid: fn(first frame of the pass, its frames)
+template <typename F>
+void channel_passes(size_t batch, size_t threads_per_frame, F fn) {
+  const size_t pass = std::max<size_t>((uint64_t(0x7fffffffu) * chan::kThreads) / threads_per_frame, 1);
+  for (size_t b0 = 0; b0 < batch; b0 += pass) fn(b0, std::min(pass, batch - b0));
+}
+
+inline uint32_t channel_blocks(uint64_t total) { return static_cast<uint32_t>((total + chan::kThreads - 1) / chan::kThreads); }
+
+template <typename T>
+void mod_launch(const Constellation &c, const uint8_t *bits, T *symbols, size_t bits_len, size_t symbols_len, size_t batch,
+                int32_t interleaving, hipStream_t s) {
+  const uint32_t bl = static_cast<uint32_t>(bits_len), sl = static_cast<uint32_t>(symbols_len);
+  chan::Points<T> t;
+  for (uint32_t v = 0; v < 32; v++) {  // (each coordinate rounded once to the symbols' type)
+    t.re[v] = static_cast<T>(c.re[v]);
+    t.im[v] = static_cast<T>(c.im[v]);
+  }
+  channel_passes(batch, symbols_len, [&](size_t b0, size_t frames) {
+    const uint64_t total = uint64_t(frames) * symbols_len;
+    if (c.bpsk)
+      chan::bpsk_mod_kernel<T><<<channel_blocks(total), chan::kThreads, 0, s>>>(bits + b0 * bits_len, symbols + b0 * symbols_len,
+                                                                               bl, total, interleaving);
+    else
+      chan::mod_kernel<T><<<channel_blocks(total), chan::kThreads, 0, s>>>(bits + b0 * bits_len, symbols + 2 * b0 * symbols_len,
+                                                                          c.bits, sl, bl, total, interleaving, t);
+  });
+}
+
+template <typename T>
+void awgn_launch(const Constellation &c, T *symbols, size_t symbols_len, size_t batch, double sigma, uint64_t seed,
+                 uint64_t first_frame, hipStream_t s) {
+  const uint32_t sl = static_cast<uint32_t>(symbols_len), pairs = static_cast<uint32_t>((symbols_len + 1) / 2);
+  const size_t per_frame = c.bpsk ? pairs : symbols_len;
+  channel_passes(batch, per_frame, [&](size_t b0, size_t frames) {
+    const uint64_t total = uint64_t(frames) * per_frame;
+    if (c.bpsk)
+      chan::awgn_real_kernel<T><<<channel_blocks(total), chan::kThreads, 0, s>>>(symbols + b0 * symbols_len, sl, pairs, total,
+                                                                                static_cast<T>(sigma), seed, first_frame + b0);
+    else
+      chan::awgn_kernel<T><<<channel_blocks(total), chan::kThreads, 0, s>>>(symbols + 2 * b0 * symbols_len, sl, total,
+                                                                           static_cast<T>(sigma), seed, first_frame + b0);
+  });
+}
+}  // namespace
+
+int DeviceDemodulator::mod_device(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch,
+                                  int32_t interleaving, hipStream_t stream) {
+  if (batch == 0 || bits_len == 0) return 0;
+  hipStream_t s;
+  if (int rc = begin(stream, &s)) return rc;
+  if (f64)
+    mod_launch(c_, bits, static_cast<double *>(symbols), bits_len, symbols_len, batch, interleaving, s);
+  else
+    mod_launch(c_, bits, static_cast<float *>(symbols), bits_len, symbols_len, batch, interleaving, s);
+  return end(stream, s);
+}
+
+int DeviceDemodulator::mod_host(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch,
+                                int32_t interleaving) {
+  if (batch == 0 || bits_len == 0) return 0;
+  DEMOD_TRY(hipSetDevice(device_));
+  const size_t in_bytes = batch * bits_len, out_bytes = batch * symbols_len * (c_.bpsk ? 1 : 2) * (f64 ? 8 : 4);
+  DEMOD_TRY(d_in_.ensure(in_bytes, 256));
+  DEMOD_TRY(d_out_.ensure(out_bytes, 256));
+  DEMOD_TRY(hipMemcpyAsync(d_in_.get(), bits, in_bytes, hipMemcpyHostToDevice, stream_));
+  if (int rc = mod_device(d_in_.get<uint8_t>(), d_out_.get(), f64, bits_len, symbols_len, batch, interleaving, stream_)) return rc;
+  DEMOD_TRY(hipMemcpyAsync(symbols, d_out_.get(), out_bytes, hipMemcpyDeviceToHost, stream_));
+  DEMOD_TRY(hipStreamSynchronize(stream_));
+  return 0;
+}
+
+int DeviceDemodulator::awgn_device(void *symbols, bool f64, size_t symbols_len, size_t batch, double sigma, uint64_t seed,
+                                   uint64_t first_frame, hipStream_t stream) {
+  if (batch == 0 || symbols_len == 0) return 0;
+  hipStream_t s;
+  if (int rc = begin(stream, &s)) return rc;
+  if (f64)
+    awgn_launch(c_, static_cast<double *>(symbols), symbols_len, batch, sigma, seed, first_frame, s);
+  else
+    awgn_launch(c_, static_cast<float *>(symbols), symbols_len, batch, sigma, seed, first_frame, s);
+  return end(stream, s);
+}
+
+int DeviceDemodulator::awgn_host(void *symbols, bool f64, size_t symbols_len, size_t batch, double sigma, uint64_t seed,
+                                 uint64_t first_frame) {
+  if (batch == 0 || symbols_len == 0) return 0;
+  DEMOD_TRY(hipSetDevice(device_));
+  const size_t bytes = batch * symbols_len * (c_.bpsk ? 1 : 2) * (f64 ? 8 : 4);
+  DEMOD_TRY(d_in_.ensure(bytes, 256));
+  DEMOD_TRY(hipMemcpyAsync(d_in_.get(), symbols, bytes, hipMemcpyHostToDevice, stream_));
+  if (int rc = awgn_device(d_in_.get(), f64, symbols_len, batch, sigma, seed, first_frame, stream_)) return rc;
+  DEMOD_TRY(hipMemcpyAsync(symbols, d_in_.get(), bytes, hipMemcpyDeviceToHost, stream_));
   DEMOD_TRY(hipStreamSynchronize(stream_));
   return 0;
 }

@@ -10,6 +10,7 @@
 #include <string>
 #include <vector>
 
+#include "demodulator.h"
 #include "device_decoder.h"
 #include "hip_owned.h"
 #include "encoder.h"
@@ -35,7 +36,15 @@ class Simulator {
   // (ber.rs:250-252; needs n_tx % columns == 0).  Both return false on an unusable value.
   bool set_modulation(int bits_per_symbol);
   bool set_interleaving(int64_t columns);
-  int modulation() const { return bits_per_symbol_; }
+  // A constellation (a copy of the one a demodulator handle holds) in place of what set_modulation selects; nullptr
+  // returns to that.  BPSK: the BPSK generator.  A table: n_tx must be a multiple of its bits and its mean energy 1 within
+  // 1e-6 (sim_constellation_error), else false with nothing changed.  max_log: the demapper's fold step.
+  // The frames are then defined by composition: the LLRs are what the modulator, the AWGN channel (the run's seed, frame
+  // numbers and sigma) and the f64 demapper of this constellation give on the pooled codewords, each rounded once to float.
+  bool set_constellation(const Constellation *c, bool max_log);
+  bool has_constellation() const { return use_constellation_; }
+  bool max_log() const { return use_constellation_ && max_log_; }
+  int modulation() const { return use_constellation_ ? static_cast<int>(constellation_.bits) : bits_per_symbol_; }
   int64_t interleaving() const { return interleaving_; }
   DeviceDecoder *decoder() { return dec_.get(); }
   // straggler pooling (run_bch): 0 = every chunk runs the full iteration budget
@@ -68,6 +77,7 @@ class Simulator {
   void noise_params(double ebn0_db, float *sigma, float *scale) const;
   double noise_sigma(double ebn0_db) const;
   void launch_generator(double ebn0_db, uint64_t seed, uint64_t first_frame, uint32_t frames, float *dst = nullptr);
+  void launch_table_generator(double sigma, uint64_t seed, uint64_t first_frame, uint32_t frames, float *dst);
   bool fail(const std::string &m, hipError_t e = hipSuccess);
 
   std::unique_ptr<DeviceDecoder> dec_;
@@ -76,6 +86,8 @@ class Simulator {
   uint32_t pool_ = 0;
   int device_ = 0;
   int bits_per_symbol_ = 1;
+  bool use_constellation_ = false, max_log_ = false;
+  Constellation constellation_;
   int64_t interleaving_ = 0;
   std::vector<uint8_t> messages_, tx_bits_;
   DeviceBuffer d_messages_, d_tx_, d_bits_, d_llrs_, d_its_, d_counters_;

@@ -150,6 +150,20 @@ bool Simulator::set_modulation(int bits_per_symbol) {
   return false;
 }
 
+bool Simulator::set_constellation(const Constellation *c, bool max_log) {
+  if (c != nullptr) {
+    if (const char *why = sim_constellation_error(*c, n_tx_)) {
+      fail(why);
+      return false;
+    }
+    constellation_ = *c;
+  }
+  use_constellation_ = c != nullptr;
+  max_log_ = c != nullptr && max_log;
+  budget_valid_ = false;  // (as in set_modulation)
+  return true;
+}
+
 bool Simulator::set_interleaving(int64_t columns) {
   const uint64_t c = columns < 0 ? uint64_t(-columns) : uint64_t(columns);
   if (c > 0x7FFFFFFFull || (c != 0 && n_tx_ % c != 0)) {
@@ -164,7 +178,7 @@ bool Simulator::set_interleaving(int64_t columns) {
 // ber.rs:299-302: EsN0 = rate * bits_per_symbol * EbN0, sigma = sqrt(0.5 / EsN0)
 double Simulator::noise_sigma(double ebn0_db) const {
   const double ebn0 = std::pow(10.0, 0.1 * ebn0_db);
-  return std::sqrt(0.5 / (rate() * static_cast<double>(bits_per_symbol_) * ebn0));
+  return std::sqrt(0.5 / (rate() * static_cast<double>(modulation()) * ebn0));
 }
 
 // BPSK: the f32 values the generator uses are the roundings of these doubles
@@ -174,11 +188,54 @@ void Simulator::noise_params(double ebn0_db, float *sigma, float *scale) const {
   *scale = static_cast<float>(-2.0 / (s * s));
 }
 
+namespace {
+template <int M>
+void table_generator_pass(bool max_log, uint32_t blocks, hipStream_t s, const uint8_t *tx, uint32_t pool, uint32_t n_tx,
+                          int32_t interleaving, uint64_t seed, uint64_t first_frame, uint64_t total, double sigma, double scale,
+                          int32_t energy, const demod::Table<double> &t, float *dst) {
+  if (max_log)
+    chan::table_llr_kernel<M, true><<<blocks, chan::kThreads, 0, s>>>(tx, pool, n_tx, interleaving, seed, first_frame, total, sigma,
+                                                                     scale, energy, t, dst);
+  else
+    chan::table_llr_kernel<M, false><<<blocks, chan::kThreads, 0, s>>>(tx, pool, n_tx, interleaving, seed, first_frame, total, sigma,
+                                                                      scale, energy, t, dst);
+}
+}  // namespace
+
+// the fused generator of a table constellation (kernels_channel.hip.h): scale and the energy terms as the demapper's
+// host side makes them (demodulator.hip.h, demod_table_pass)
+void Simulator::launch_table_generator(double sigma, uint64_t seed, uint64_t first_frame, uint32_t frames, float *dst) {
+  const Constellation &c = constellation_;
+  const uint32_t n_tx = static_cast<uint32_t>(n_tx_);
+  const double scale = 1.0 / (sigma * sigma), half_scale = 0.5 * scale;
+  demod::Table<double> t;
+  for (uint32_t v = 0; v < 32; v++) {
+    t.re[v] = c.re[v];
+    t.im[v] = c.im[v];
+    t.c[v] = half_scale * c.e[v];
+  }
+  const uint64_t total = uint64_t(frames) * (n_tx / c.bits);
+  const uint32_t blocks = static_cast<uint32_t>((total + chan::kThreads - 1) / chan::kThreads);
+  const uint8_t *tx = d_tx_.get<uint8_t>();
+  const int32_t il = static_cast<int32_t>(interleaving_), energy = c.energy ? 1 : 0;
+  switch (c.bits) {
+    case 1: return table_generator_pass<1>(max_log_, blocks, stream_, tx, pool_, n_tx, il, seed, first_frame, total, sigma, scale, energy, t, dst);
+    case 2: return table_generator_pass<2>(max_log_, blocks, stream_, tx, pool_, n_tx, il, seed, first_frame, total, sigma, scale, energy, t, dst);
+    case 3: return table_generator_pass<3>(max_log_, blocks, stream_, tx, pool_, n_tx, il, seed, first_frame, total, sigma, scale, energy, t, dst);
+    case 4: return table_generator_pass<4>(max_log_, blocks, stream_, tx, pool_, n_tx, il, seed, first_frame, total, sigma, scale, energy, t, dst);
+    default: return table_generator_pass<5>(max_log_, blocks, stream_, tx, pool_, n_tx, il, seed, first_frame, total, sigma, scale, energy, t, dst);
+  }
+}
+
 // frames [first_frame, first_frame + frames) -> d_llrs_ (codeword order, ready for the decoder)
 void Simulator::launch_generator(double ebn0_db, uint64_t seed, uint64_t first_frame, uint32_t frames, float *dst) {
   const uint32_t n_tx = static_cast<uint32_t>(n_tx_);
   if (dst == nullptr) dst = d_llrs_.get<float>();
-  if (bits_per_symbol_ == 3) {
+  if (use_constellation_ && !constellation_.bpsk) {
+    launch_table_generator(noise_sigma(ebn0_db), seed, first_frame, frames, dst);
+    return;
+  }
+  if (!use_constellation_ && bits_per_symbol_ == 3) {
     const double s = noise_sigma(ebn0_db);
     const uint64_t threads = uint64_t(frames) * (n_tx / 3);
     gen::psk8_llr_kernel<<<static_cast<uint32_t>((threads + 255) / 256), 256, 0, stream_>>>(

@@ -317,12 +317,26 @@ class Simulator:
     generated, decoded and scored on the device; only six counters come back."""
 
     def __init__(self, alist: str, implementation: str, puncturing: str = "", device: int = 0, pool_size: int = 64,
-                 pool_seed: int = 1, modulation: str = "BPSK", interleaving: int = 0):
-        """modulation: "BPSK" or "8PSK" (factory.rs:53-73); interleaving: columns of the DVB-S2 bit
+                 pool_seed: int = 1, modulation="BPSK", interleaving: int = 0, max_log: bool = False):
+        """modulation: "BPSK" or "8PSK" (factory.rs:53-73), "QPSK", or a `Demodulator` -- any constellation of up to 32
+        points with unit mean energy (its table is copied; the instance may be closed afterwards).  max_log: the max-log
+        demapper instead of the exact one ("QPSK" or a `Demodulator` only).  interleaving: columns of the DVB-S2 bit
         interleaver, negative = rows read backwards, 0 = none (ber.rs:250-252)."""
-        bits_per_symbol = {"BPSK": 1, "8PSK": 3}.get(modulation)
-        if bits_per_symbol is None:
-            raise ValueError(f"invalid modulation {modulation}")
+        constellation = owned = None
+        if isinstance(modulation, str):
+            bits_per_symbol = {"BPSK": 1, "8PSK": 3, "QPSK": 1}.get(modulation)
+            if bits_per_symbol is None:
+                raise ValueError(f"invalid modulation {modulation}")
+            if max_log and modulation != "QPSK":
+                raise ValueError('max_log needs a constellation: "QPSK" or a Demodulator instance')
+            if modulation == "QPSK":
+                from .demodulator import Demodulator
+                constellation = owned = Demodulator("QPSK", device=device)
+        elif hasattr(modulation, "_h") and hasattr(modulation, "bits_per_symbol"):
+            constellation, bits_per_symbol = modulation, 1
+            modulation = f"constellation:{constellation.points}"
+        else:
+            raise ValueError(f"invalid modulation {modulation!r}")
         h = _capi.lib().ldpc_toolbox_sim_ctor(alist.encode(), implementation.encode(), puncturing.encode(),
                                               int(device), int(pool_size), int(pool_seed))
         if not h:
@@ -330,12 +344,30 @@ class Simulator:
         self._h = h
         self.k, self.n, self.n_tx, self.pool = (self.get(x) for x in ("k", "n", "n_tx", "pool"))
         self.rate = self.k / self.n_tx
-        self.modulation, self.interleaving = modulation, int(interleaving)
-        for key, value in (("modulation", bits_per_symbol), ("interleaving", int(interleaving))):
-            if _capi.lib().ldpc_toolbox_sim_set(self._h, key.encode(), value) != 0:
-                msg = _capi.last_error() or f"cannot set {key}"
-                self.close()
-                raise ValueError(msg)
+        self.modulation, self.interleaving, self.max_log = modulation, int(interleaving), bool(max_log)
+        try:
+            for key, value in (("modulation", bits_per_symbol), ("interleaving", int(interleaving))):
+                if _capi.lib().ldpc_toolbox_sim_set(self._h, key.encode(), value) != 0:
+                    msg = _capi.last_error() or f"cannot set {key}"
+                    self.close()
+                    raise ValueError(msg)
+            if constellation is not None:
+                try:
+                    self.set_constellation(constellation, max_log)
+                except ValueError:
+                    self.close()
+                    raise
+        finally:
+            if owned is not None:
+                owned.close()
+        self.bits_per_symbol = self.get("modulation")
+
+    def set_constellation(self, demodulator, max_log=False):
+        """`demodulator`: a `Demodulator` whose constellation generates the frames from now on, or None for what the
+        "modulation" key selects.  ValueError (nothing changed) when the simulator refuses it."""
+        h = None if demodulator is None else demodulator._h
+        if _capi.lib().ldpc_toolbox_sim_set_constellation(self._h, h, int(bool(max_log))) != 0:
+            raise ValueError(_capi.last_error() or "cannot set the constellation")
 
     def get(self, key):
         v = C.c_int64(0)

@@ -1,5 +1,6 @@
 """Batched soft demapper on the GPU (include/ldpc_toolbox.h, PART 4): received symbols -> channel LLRs in codeword
-order, the layout `LdpcDecoder.decode_batch_device` takes.  There is no CPU fallback."""
+order, the layout `LdpcDecoder.decode_batch_device` takes -- and, on the same constellation handle, the transmit side:
+the modulator (bits -> symbols) and the AWGN channel.  There is no CPU fallback."""
 import ctypes as C
 
 import numpy as np
@@ -85,6 +86,69 @@ class Demodulator:
                 int(interleaving), int(bool(max_log)), stream or None)
         if rc != 0:
             self._raise("demodulate_device", rc)
+
+    def modulate(self, bits, interleaving=0, f64=True):
+        """bits [batch][bits_len] uint8 host array (a byte equal to 1 is a one) -> symbols [batch][bits_len / m]
+        complex128 / complex64 (float64 / float32 reals for BPSK), the bits interleaved first (`interleaving`: signed
+        columns, the interleaver `demodulate` undoes)."""
+        bits = np.ascontiguousarray(bits, dtype=np.uint8)
+        if bits.ndim != 2:
+            raise ValueError("bits must be [batch][bits_len]")
+        B, n = bits.shape
+        m = self.bits_per_symbol
+        S = n // m
+        if self.real_symbols:
+            out = np.zeros((B, S), dtype=np.float64 if f64 else np.float32)
+        else:
+            out = np.zeros((B, S), dtype=np.complex128 if f64 else np.complex64)
+        L = _capi.lib()
+        fn = L.ldpc_toolbox_mod_run_f64 if f64 else L.ldpc_toolbox_mod_run_f32
+        rc = fn(self._h, out.ctypes.data, S, bits.ctypes.data, n, B, int(interleaving))
+        if rc != 0:
+            self._raise("modulate", rc)
+        return out
+
+    def modulate_device(self, bits_ptr: int, sym_ptr: int, f64: bool, batch: int, bits_len: int, interleaving=0,
+                        stream: int = 0, symbols_len=None):
+        """Raw device pointers: bits [batch][bits_len] uint8 -> symbols [batch][bits_len / m]; stream as in
+        `demodulate_device`.  symbols_len: given only to state a length other than bits_len / m (it is refused)."""
+        L = _capi.lib()
+        fn = L.ldpc_toolbox_mod_run_f64_device if f64 else L.ldpc_toolbox_mod_run_f32_device
+        S = bits_len // self.bits_per_symbol if symbols_len is None else symbols_len
+        rc = fn(self._h, sym_ptr, S, bits_ptr, bits_len, batch, int(interleaving), stream or None)
+        if rc != 0:
+            self._raise("modulate_device", rc)
+
+    def add_noise(self, symbols, sigma, seed, first_frame=0):
+        """symbols [batch][symbols_len] (dtype rules of `demodulate`) -> a new array: row r with the noise of frame
+        first_frame + r (the simulator's Philox4x32-10 + polar method, keyed by seed, frame and symbol)."""
+        symbols = np.asarray(symbols)
+        if symbols.ndim != 2:
+            raise ValueError("symbols must be [batch][symbols_len]")
+        if self.real_symbols:
+            if np.iscomplexobj(symbols):
+                raise ValueError("BPSK symbols are real")
+            real = np.float32 if symbols.dtype == np.float32 else np.float64
+            out = np.array(symbols, dtype=real, order="C")
+        else:
+            real = np.float32 if symbols.dtype in (np.complex64, np.float32) else np.float64
+            out = np.array(symbols, dtype=np.complex64 if real == np.float32 else np.complex128, order="C")
+        B, S = out.shape
+        L = _capi.lib()
+        fn = L.ldpc_toolbox_awgn_run_f32 if real == np.float32 else L.ldpc_toolbox_awgn_run_f64
+        rc = fn(self._h, out.ctypes.data, S, B, float(sigma), int(seed), int(first_frame))
+        if rc != 0:
+            self._raise("add_noise", rc)
+        return out
+
+    def add_noise_device(self, sym_ptr: int, f64: bool, batch: int, symbols_len: int, sigma, seed, first_frame=0,
+                         stream: int = 0):
+        """Raw device pointer: symbols [batch][symbols_len], noise added in place; stream as in `demodulate_device`."""
+        L = _capi.lib()
+        fn = L.ldpc_toolbox_awgn_run_f64_device if f64 else L.ldpc_toolbox_awgn_run_f32_device
+        rc = fn(self._h, sym_ptr, symbols_len, batch, float(sigma), int(seed), int(first_frame), stream or None)
+        if rc != 0:
+            self._raise("add_noise_device", rc)
 
     def close(self):
         if getattr(self, "_h", None):

@@ -367,7 +367,7 @@ def main_multi(a, rank, local, world, device, distributed):
     import os
 
     from . import _capi
-    from .ber import ebn0_grid, format_details, statistics_from_counters
+    from .ber import ebn0_grid, format_details, make_modulation, statistics_from_counters
     from .decoder import Simulator
     from .simulation import format_header, format_progress
     codes = expand_codes(a.codes)
@@ -377,7 +377,8 @@ def main_multi(a, rank, local, world, device, distributed):
 
     def make_sim(code):
         return Simulator(_capi.code_alist(code), a.decoder, a.puncturing, device=local, pool_size=a.pool_size,
-                         pool_seed=a.seed + 1, modulation=a.modulation, interleaving=a.interleaving)
+                         pool_seed=a.seed + 1, modulation=make_modulation(a, local), interleaving=a.interleaving,
+                         max_log=getattr(a, "max_log", False))
 
     job = SweepJob(codes, make_sim, rank, world, device, a.max_iter, a.frame_errors, a.max_frames, a.min_time, a.max_time,
                    a.seed, a.bch_max_errors, queue=a.queue, defer_groups=a.defer_groups,
