@@ -16,6 +16,7 @@
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
+#include <atomic>
 #include <cstddef>
 #include <cstdint>
 #include <memory>
@@ -63,6 +64,8 @@ class DeviceDecoder {
   // cn_minsum_rec_kernel), 0 when it keeps per-edge messages
   uint32_t row_records() const { return (rec_ready_ && records_wanted() && opt_lfree_ && !opt_staged_minsum_) ? rec_w_ : 0; }
   uint32_t record_flag_bits() const { return row_records() ? rec_flag_bits_ : 0; }
+  // whether the last decode call's variable-node launches read the row records ("vn_records")
+  uint32_t last_vn_records() const { return last_vn_records_.load(std::memory_order_relaxed) ? 1 : 0; }
 
   // codewords per group (rounded up to the wave tile).  0 = automatic.
   void set_group_size(size_t g) { group_pref_ = g; }
@@ -72,12 +75,13 @@ class DeviceDecoder {
   void set_min_group(size_t g) { min_group_ = g; }
   // codewords per group a call of `batch` codewords is cut into (the set value, else a default that grows for small graphs)
   size_t preferred_group(size_t batch) const { return pick_group(batch); }
-  // The 26 options of set_option (round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
+  // The 27 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
   // percent are constants now, see kStreamBlock ... below).  Results never depend on any of them; each selects between
   // forms that tests/ compare bit for bit.  returns false for an unknown key.
   //   which kernels run   "lfree" (0: plain flooding min-sum kernels), "records" (0 / 1 / 2: per-edge messages / row records
   //                       where the graph suits them / wherever possible), "rec_quiet" (0: L-free posteriors stored every
-  //                       iteration), "vn_event" (0: the first convergences' rebuild as a launch of its own), "rec_long"
+  //                       iteration), "vn_event" (0: the first convergences' rebuild as a launch of its own), "vn_records" (0 / 1:
+  //                       the variable nodes summed from per-edge messages / from the row records, 16-bit flags only), "rec_long"
   //                       (1: the record kernel's long-row variant whatever the graph), "staged_minsum" (1: Minsum through
   //                       the generic LDS-staged kernel), "cn_reg" / "hl_reg" / "hl_records" (0: the LDS-staged / two-pass /
   //                       per-edge forms instead of register-resident rows and layered row records), "serial_levels"
@@ -199,6 +203,12 @@ class DeviceDecoder {
   bool opt_rec_long_ = false;  // "rec_long": take the record kernel's long-row variant whatever the graph (A/B)
   bool opt_rec_quiet_ = true;  // "rec_quiet": L-free posteriors are stored only once a slice has a converged codeword
   bool opt_vn_event_ = true;  // "vn_event": the first convergences' L-free posteriors rebuilt inside the variable-node launch (0: a launch of their own)
+  // "vn_records": the variable-node launch reads this iteration's row records instead of per-edge messages, which the
+  // check-node launch then does not store (run_group.hip.h; 16-bit flags only)
+  // (default: on for plain Minsumf32 on DVB-S2 normal frames at rate 1/2, the one configuration measured to pay by the
+  // project's bar, profiles/vn_records.txt; off for every other code, rule and precision)
+  bool opt_vn_records_ = false;
+  std::atomic<bool> last_vn_records_{false};  // (written by every group's run_group: with "lane_threads" from two host threads)
   uint32_t rec_w_ = 0;
   uint32_t rec_flag_bits_ = 0;  // 16: the records' flags are half-words in an array of their own (graph_tables.h)
   bool rec_ready_ = false, rec_prefers_ = false;
@@ -278,6 +288,7 @@ class DeviceDecoder {
   DeviceBuffer d_src_block_;    // depuncture map: source block of every pattern block, -1 = punctured
   DeviceBuffer d_edge_aux_, d_keep_var_, d_keep_ptr_, d_keep_edge_, d_free_var_, d_free_ptr_, d_free_edge_;  // LfreeTables
   DeviceBuffer d_edge_peer_, d_free_rs_, d_keep_pos_;                                                         // RowRecordTables
+  DeviceBuffer d_keep_rs_;                                                                                    // KeepRsTable
   // Two execution lanes (workspace + stream): groups alternate between them, so the idle gaps
   // between one lane's short launches (layered schedule: one per dependency level) are filled by
   // the other's, and the host entry's PCIe copies overlap the other lane's decode.

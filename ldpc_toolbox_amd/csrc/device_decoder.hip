@@ -1,9 +1,29 @@
 // Host orchestration of the batched HIP decoder: graph upload, workspace in HBM,
 // the per-group launch sequence of both schedules.  See device_decoder.h / DESIGN.md.
 #define LDPC_GROUP_KERNELS_TU 1  // this translation unit compiles the non-template group kernels
+#include "codes.h"
 #include "device_decoder_internal.h"
 
 namespace ldpc {
+
+// The one graph on which the "vn_records" form is the default (device_decoder.h, opt_vn_records_): DVB-S2 normal frames at
+// rate 1/2 -- the same rows with the same columns, in whatever order a row lists them.
+static bool is_dvbs2_half_rate_normal(const SparseMatrix::Csr &g) {
+  if (g.n_cols != 64800 || g.n_rows != 32400) return false;
+  SparseMatrix ref;
+  if (!codes::dvbs2("R1_2", &ref)) return false;
+  const SparseMatrix::Csr r = ref.csr();
+  if (r.n_edges != g.n_edges || r.row_ptr != g.row_ptr) return false;
+  std::vector<uint32_t> a, b;
+  for (uint32_t row = 0; row < g.n_rows; row++) {
+    a.assign(g.edge_col.begin() + g.row_ptr[row], g.edge_col.begin() + g.row_ptr[row + 1]);
+    b.assign(r.edge_col.begin() + r.row_ptr[row], r.edge_col.begin() + r.row_ptr[row + 1]);
+    std::sort(a.begin(), a.end());
+    std::sort(b.begin(), b.end());
+    if (a != b) return false;
+  }
+  return true;
+}
 
 bool DeviceDecoder::fail(const std::string &msg, hipError_t e) {
   static std::mutex m;  // (the execution lanes' enqueuing threads may both fail)
@@ -106,6 +126,11 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
       d->rec_flag_bits_ = rr.flag_bits;
       ok = up(rr.keep_pos, &d->d_keep_pos_) && up(rr.peer, &d->d_edge_peer_) && up(rr.free_rs, &d->d_free_rs_);
       d->rec_ready_ = ok;
+      const KeepRsTable kr = (ok && rr.flag_bits == 16) ? build_keep_rs(g, lf) : KeepRsTable();
+      if (kr.ready) ok = up(kr.rs, &d->d_keep_rs_);
+      // the default: on for the one configuration measured to pay by the project's bar (profiles/vn_records.txt), plain
+      // Minsumf32 on DVB-S2 normal frames at rate 1/2; everything else takes it with the key
+      d->opt_vn_records_ = kr.ready && ok && !impl.f64 && impl.correction == Correction::None && is_dvbs2_half_rate_normal(g);
     }
   }
   if (ok && flooding_minsum && !impl.f64) {
@@ -194,6 +219,8 @@ bool DeviceDecoder::set_option(const std::string &key, int64_t value) {
     opt_rec_quiet_ = v != 0;
   else if (key == "vn_event")
     opt_vn_event_ = v != 0;
+  else if (key == "vn_records")
+    opt_vn_records_ = v != 0;
   else if (key == "rec_long")
     opt_rec_long_ = v != 0;
   else if (key == "compact")

@@ -125,6 +125,27 @@ inline RowRecordTables build_row_record_tables(const SparseMatrix::Csr &g, const
   return t;
 }
 
+// The variable-node kernel's record source (kernels_flooding.hip.h, from_records::vn_kernel): for every edge of the kept list, in
+// the list's own order (keep_var / keep_ptr, cols[v] order inside a variable), row << 6 | slot of the edge inside its row --
+// free_rs's word, with free_rs's limits: a slot below 64 and a row index below kPeerSingle, else not ready.  Padded by
+// kTablePad words (the kernel fetches a variable's first indices as one block).
+struct KeepRsTable {
+  bool ready = false;
+  std::vector<uint32_t> rs;
+};
+inline KeepRsTable build_keep_rs(const SparseMatrix::Csr &g, const LfreeTables &lf) {
+  KeepRsTable t;
+  if (!lf.ready || g.max_row_weight > 64 || g.n_rows >= dev::kPeerSingle) return t;
+  std::vector<uint32_t> rs(std::max<uint32_t>(g.n_edges, 1));  // edge -> row << 6 | slot
+  for (uint32_t r = 0; r < g.n_rows; r++)
+    for (uint32_t e = g.row_ptr[r]; e < g.row_ptr[r + 1]; e++) rs[e] = (r << 6) | (e - g.row_ptr[r]);
+  t.rs.reserve(lf.keep_edge.size() + kTablePad);
+  for (uint32_t e : lf.keep_edge) t.rs.push_back(rs[e]);
+  t.rs.resize(t.rs.size() + kTablePad, 0);
+  t.ready = true;
+  return t;
+}
+
 // Sliced-ELLPACK tables of the small-batch path (latency.hip.h): rows in the order of their first variable, 64 to a slice,
 // slot-major inside a slice: edge (position p, slot j) -> id rslice_ptr[p / 64] + j * 64 + p % 64 (messages and `col`
 // share it).  ready: rows of at most 64 edges, at least one row, and edge ids within 2^30.

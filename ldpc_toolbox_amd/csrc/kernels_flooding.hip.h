@@ -313,6 +313,8 @@ struct VnEvent16 {  // the same with 16-bit flags (EVF16)
 __device__ __forceinline__ bool has_records(const void *rec) { return rec != nullptr; }
 template <typename T>
 __device__ __forceinline__ bool has_records(const RecPair<T> &rec) { return rec.mag != nullptr; }
+// (from_records::vn_kernel below repeats this kernel's prologue -- the idle test, the bookkeeping wave, the EVW block, the
+// slice_state latch -- line for line: a change to any of them is made in both)
 template <typename T, int VEC, int U, bool NT, bool LIST, int EVW = 0, bool EVF16 = false>
 __global__ __launch_bounds__(256) void vn_kernel(
     Graph g, Sched sc, State st, const T *__restrict__ chan, const T *__restrict__ msg,
@@ -492,6 +494,191 @@ __global__ __launch_bounds__(256) void vn_kernel(
     for (int u = 0; u < U; u++) ed[u] = ned[u];
   }
 }
+
+// ---------------------------------------------------------------------------------------
+// Flooding, variable nodes from ROW RECORDS: vn_kernel's list variant with the per-edge message array taken out of the
+// iteration.  The message on a kept edge is already in the record its row wrote in the same iteration --
+// Rec::value(slot, k) is the very pack cn_minsum_rec_kernel's `send` stores -- so this kernel gathers, per edge, the record
+// of the edge's row (keep_rs: row << 6 | slot per edge of the kept list, graph_tables.h build_keep_rs) and the check-node
+// launch stores no per-edge messages at all (its SEND = false form).  Same sum, same order: cols[v] order from -0.0, then
+// post = chan + sum.  The 16-bit-flags record form only (rows of at most 12 edges); a record is 2.5 words of f32 where a
+// message was one, but a row's record is wanted by every kept edge of the row and is fetched from HBM once per tile.
+//   rec     the records the check-node launch of THIS iteration wrote
+//   EV      the EVW block of vn_kernel (the L-free posteriors of a slice's first convergences, from ev.rec: the records of
+//           the iteration being latched, the other buffer), word for word; the bookkeeping wave likewise
+//   U       records in flight per lane; a variable of more edges takes further rounds
+//   NTCH    the channel rows (read by no other kernel in this form) through nontemporal loads
+// Everything up to the main loop -- the idle test, the bookkeeping wave, the event block with its `fresh` rule, the
+// slice_state latch -- is vn_kernel's, line for line; the reasons are written there, once.  (Kept as a second copy and not as
+// shared helpers so that every existing instantiation of vn_kernel stays instruction-identical by construction.)
+// The kernel is from_records::vn_kernel: it IS the iteration's variable-node launch, and whoever accounts for the launches
+// of an iteration by kernel name (bench.py's counter passes sum "vn_kernel") finds it under that name.
+// ---------------------------------------------------------------------------------------
+namespace from_records {
+template <typename T, int VEC, int U, bool NTCH, bool EV>
+__global__ __launch_bounds__(256) void vn_kernel(
+    Graph g, Sched sc, State st, const T *__restrict__ chan, RecPair<const T> rec, const uint32_t *__restrict__ keep_rs_,
+    T *__restrict__ post, const uint32_t *__restrict__ unsat_in, uint32_t *__restrict__ unsat_clear,
+    int32_t latch_iteration, VnEvent16<T> ev = {}) {
+  typedef RowRec<T, VEC, 3, uint16_t> Rec;
+  uint32_t *__restrict__ n_active = st.n_active;
+  const bool idle = *n_active == 0;  // (see vn_kernel: with EV a wave may still owe its share of the rebuild)
+  if (!EV && idle) return;
+  const TablePtr col_ptr = table_ptr(g.list_ptr), keep_rs = table_ptr(keep_rs_);
+  uint32_t *__restrict__ done = st.done;
+  int32_t *__restrict__ iters = st.iters;
+  const uint32_t n_cols = g.n_list;
+  const uint32_t waves_per_chunk = sc.waves_per_chunk, tile = sc.tile;
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t wave = uniform((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  uint32_t chunk, v_first;
+  wave_slot(sc, wave, &chunk, &v_first);
+  if (chunk >= sc.nchunks) return;
+  const uint32_t b0 = chunk * (64 * VEC);
+  if (b0 >= *st.n_slots) return;
+  if constexpr (EV) {
+    if (idle && (!has_records(ev.rec) || unsat_in == nullptr || st.slice_state == nullptr || st.slice_state[chunk] == 2u)) return;
+  }
+  const size_t off = size_t(b0) + lane * VEC;
+  const size_t G = tile;
+  chan += tile_base(b0, g.n_cols, sc) + lane * VEC;
+  post += tile_base(b0, g.n_cols, sc) + lane * VEC;
+  const uint32_t row_bytes = tile * uint32_t(sizeof(T)), lane_off = lane * uint32_t(VEC * sizeof(T));
+  bool skip[VEC];
+  bool any_live = false, any_new = false;
+#pragma unroll
+  for (int k = 0; k < VEC; k++) {
+    const bool was_done = done[off + k] != 0;
+    const bool converged = !was_done && unsat_in != nullptr && unsat_in[off + k] == 0;
+    int32_t own_iterations = latch_iteration;
+    bool expired = false;
+    if (st.it0 != nullptr) {
+      own_iterations = latch_iteration - static_cast<int32_t>(st.it0[off + k]);
+      expired = !was_done && !converged && own_iterations >= static_cast<int32_t>(st.max_it);
+    }
+    skip[k] = was_done || converged || expired;
+    any_live = any_live || !skip[k];
+    if (v_first == 0 && !idle) {  // the slice's bookkeeping wave
+      if (converged || expired) {
+        done[off + k] = 1u;
+        iters[off + k] = converged ? own_iterations : -1;
+        atomicSub(n_active, 1u);
+        any_new = true;
+      }
+      unsat_clear[off + k] = 0u;
+    }
+  }
+  if constexpr (EV) {
+    if (has_records(ev.rec) && unsat_in != nullptr && st.slice_state != nullptr && st.slice_state[chunk] != 2u) {
+      bool fresh[VEC];
+      bool any_fresh = false;
+#pragma unroll
+      for (int k = 0; k < VEC; k++) {
+        const int32_t was = iters[off + k];
+        fresh[k] = unsat_in[off + k] == 0 && st.slot_cw[off + k] != kNoCodeword && (was < 0 || was == latch_iteration);
+        any_fresh = any_fresh || fresh[k];
+      }
+      if (__builtin_amdgcn_ballot_w64(any_fresh) != 0) {
+        const TablePtr free_var = table_ptr(ev.free_var), free_rs = table_ptr(ev.free_rs);
+        const RecBuf<true> b_ev = rec_buf<T, 3>(ev.rec, b0, g.n_rows, sc, row_bytes);
+        for (uint32_t i = v_first; i < ev.n_free; i += waves_per_chunk) {
+          const uint32_t fv = free_var[i], a = free_rs[2 * i], b = free_rs[2 * i + 1];
+          const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(fv) * G);
+          Rec ra, rb;
+          if (a != kAuxNone) ra.load(b_ev, lane_off, (a >> 6) * Rec::kRows * row_bytes, row_bytes);
+          if (b != kAuxNone) rb.load(b_ev, lane_off, (b >> 6) * Rec::kRows * row_bytes, row_bytes);
+#pragma unroll
+          for (int k = 0; k < VEC; k++) {
+            T sum = -T(0.0);  // arithmetic.rs:146: the slot-ordered sum, from Rust's float Sum identity
+            if (a != kAuxNone) sum = sum + ra.value(a & 63u, k);
+            if (b != kAuxNone) sum = sum + rb.value(b & 63u, k);
+            if (fresh[k]) post[size_t(fv) * G + k] = ch.v[k] + sum;
+          }
+        }
+      }
+    }
+  }
+  if (idle) return;
+  if (v_first == 0 && st.slice_state != nullptr && __builtin_amdgcn_ballot_w64(any_new) != 0 && lane == 0 &&
+      st.slice_state[chunk] == 0)
+    st.slice_state[chunk] = 1;  // the first convergences of this slice: see State::slice_state
+  if (__builtin_amdgcn_ballot_w64(any_live) == 0) return;
+  bool all = true;
+#pragma unroll
+  for (int k = 0; k < VEC; k++) all = all && !skip[k];
+
+  const RecBuf<true> b_rec = rec_buf<T, 3>(rec, b0, g.n_rows, sc, row_bytes);
+  const uint32_t rec_bytes = Rec::kRows * row_bytes;
+  // (keep_rs is padded by kTablePad words: the block fetch of a variable's first U indices stays in bounds)
+  uint32_t v = v_first, s0 = 0, s1 = 0, rs[U], var = v_first;
+  if (v < n_cols) {
+    s0 = col_ptr[v];
+    s1 = col_ptr[v + 1];
+    var = table_ptr(g.list_var)[v];
+  }
+#pragma unroll
+  for (int u = 0; u < U; u++) rs[u] = keep_rs[s0 + u];
+
+  while (v < n_cols) {
+    T sum[VEC];
+#pragma unroll
+    for (int k = 0; k < VEC; k++) sum[k] = -T(0.0);
+    const Pack<T, VEC> ch = load_msg<T, VEC, NTCH>(chan + size_t(var) * G);
+    const uint32_t vn = v + waves_per_chunk;
+    uint32_t ns0 = 0, ns1 = 0, nvar = vn;
+    if (vn < n_cols) {
+      ns0 = col_ptr[vn];
+      ns1 = col_ptr[vn + 1];
+      nvar = table_ptr(g.list_var)[vn];
+    }
+    uint32_t nrs[U];
+    for (uint32_t j0 = s0; j0 < s1; j0 += U) {
+      Rec rv[U];
+      uint32_t w[U];
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        w[u] = 0;
+        if (j0 + u < s1) {  // wave-uniform
+          w[u] = (j0 == s0) ? rs[u] : keep_rs[j0 + u];
+          rv[u].load(b_rec, lane_off, (w[u] >> 6) * rec_bytes, row_bytes);
+        }
+      }
+      if (j0 == s0) {
+#pragma unroll
+        for (int u = 0; u < U; u++) nrs[u] = keep_rs[ns0 + u];
+      }
+#pragma unroll
+      for (int u = 0; u < U; u++) {
+        if (j0 + u < s1) {
+#pragma unroll
+          for (int k = 0; k < VEC; k++) sum[k] = sum[k] + rv[u].value(w[u] & 63u, k);
+        }
+      }
+    }
+    if (s0 == s1) {
+#pragma unroll
+      for (int u = 0; u < U; u++) nrs[u] = keep_rs[ns0 + u];
+    }
+    Pack<T, VEC> o;
+#pragma unroll
+    for (int k = 0; k < VEC; k++) o.v[k] = ch.v[k] + sum[k];
+    T *dst = post + size_t(var) * G;
+    if (all) {
+      store_pack<T, VEC>(dst, o);
+    } else {
+#pragma unroll
+      for (int k = 0; k < VEC; k++)
+        if (!skip[k]) dst[k] = o.v[k];
+    }
+    v = vn;
+    var = nvar;
+    s0 = ns0;
+    s1 = ns1;
+#pragma unroll
+    for (int u = 0; u < U; u++) rs[u] = nrs[u];
+  }
+}
+}  // namespace from_records
 // ---------------------------------------------------------------------------------------
 // The check-node kernels min-sum can take: cn_minsum (streaming), cn_minsum_lfree, cn_minsum_rec (row records), cn_staged
 // (LDS-staged, every rule).  Each ends in `typename... MC` / `MC... mc` (kernels_common.hip.h, MinsumCorr): with the pack
@@ -817,7 +1004,10 @@ __global__ __launch_bounds__(256) void cn_minsum_lfree_kernel(
 // LONG: some row has more than U edges (further rounds of U loads; compiled out otherwise: the extra code costs the
 // short-row case 2 % in registers and scheduling).
 // F16: the records' flags are 16-bit words in an array of their own (RecRef / RowRec above): rows of at most 12 edges.
-template <typename T, int VEC, int RECW, bool F16, int U, bool FIRST, bool NT, bool STREAM = false, bool LONG = true, typename... MC>
+// SEND = false: no per-edge messages are stored -- the variable-node launch rebuilds them from the records this launch
+// writes (from_records::vn_kernel); the record already holds the corrected pair, so the normalized / offset forms need nothing more.
+template <typename T, int VEC, int RECW, bool F16, int U, bool FIRST, bool NT, bool STREAM = false, bool LONG = true, bool SEND = true,
+          typename... MC>
 __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     Graph g, Sched sc, State st, const T *__restrict__ chan, T *__restrict__ post, typename RecRef<T, F16>::in rec_in,
     typename RecRef<T, F16>::out rec_out, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t run, MC... mc) {
@@ -1085,11 +1275,13 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
           for (int k = 0; k < VEC; k++) o.v[k] = out.value(slot, k);
           buf_store<T, VEC, NT>(b_msg, lane_off, (peer & kPeerPosMask) * row_bytes, o);
         };
+        if constexpr (SEND) {
 #pragma unroll
-        for (int u = 0; u < U; u++)
-          if (uint32_t(u) < d) send(u, peers[u]);
-        if constexpr (LONG)
-          for (uint32_t i = U; i < d; i++) send(i, edge_peer[e0 + i]);
+          for (int u = 0; u < U; u++)
+            if (uint32_t(u) < d) send(u, peers[u]);
+          if constexpr (LONG)
+            for (uint32_t i = U; i < d; i++) send(i, edge_peer[e0 + i]);
+        }
       }
       c = cn;
       e0 = ne0;

@@ -42,6 +42,7 @@ struct DeviceDecoder::SmallBatchCall {
         post_bytes(batch_ * dec.n_ * (llrs_f64 ? 8 : 4)), d_llrs(llrs_), d_bits(bits_), d_iters(iterations_), d_post(posterior_) {
     d.last_lanes_ = 1;
     d.last_group_ = batch;
+    d.last_vn_records_.store(false, std::memory_order_relaxed);
   }
 
   int retreat() {

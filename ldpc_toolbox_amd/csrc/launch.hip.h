@@ -118,15 +118,22 @@ struct Launch {
   // (rows of at most 8 edges -- DVB-S2 up to rate 1/2, most 5G NR rows are longer -- take the variant without the
   // further-rounds code)
   // (eight loads in flight per lane; the four-load variant of earlier rounds, a tuning knob nothing selected, is gone)
+  // (send = false: no per-edge messages, for a variable-node launch that reads the records -- vn_rec below; 16-bit flags only)
   void cn_rec(bool first, uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan, T *post,
-              const Records &in, const Records &out, T *msg, uint32_t *unsat, uint32_t run) const {
+              const Records &in, const Records &out, T *msg, uint32_t *unsat, uint32_t run, bool send = true) const {
     minsum(vec, first, [&](auto V, auto FIRST, auto... mc) {
       with_rec_form(in, [&](auto W, auto F16) {
         with_bool(rec_long, [&](auto long_rows) {
-          dev::cn_minsum_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, 8, decltype(FIRST)::value,
-                                    true, false, decltype(long_rows)::value, decltype(mc)...>
-              <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_in<decltype(F16)::value>(in),
-                                              rec_out<decltype(F16)::value>(out), msg, unsat, run, mc...);
+          auto go_rec = [&](auto SEND) {
+            dev::cn_minsum_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, 8, decltype(FIRST)::value,
+                                      true, false, decltype(long_rows)::value, decltype(SEND)::value, decltype(mc)...>
+                <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_in<decltype(F16)::value>(in),
+                                                rec_out<decltype(F16)::value>(out), msg, unsat, run, mc...);
+          };
+          if constexpr (decltype(F16)::value) {
+            if (!send) return go_rec(std::false_type{});
+          }
+          go_rec(std::true_type{});
         });
       });
     });
@@ -190,6 +197,24 @@ struct Launch {
             free_var, free_rs, rec_in<decltype(F16)::value>(rec), n_free};
         dev::vn_kernel<T, decltype(V)::value, 8, true, true, decltype(W)::value, decltype(F16)::value>
             <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, msg, post, unsat_in, unsat_clear, latch_it, ev);
+      });
+    });
+  }
+
+  // the list variant that sums the kept variables from the records of this iteration (from_records::vn_kernel; 16-bit flags).  ev_rec
+  // null: no event block (the first iteration, or "vn_event" / "rec_quiet" off).
+  // (eight records in flight and nontemporal channel loads: the headline gains 0.65 % over four in flight -- 98 against 57
+  // VGPRs, 4 against 8 waves per SIMD -- and 0.35 % over cached channel loads, profiles/vn_records.txt section 1)
+  void vn_rec(uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan,
+              const Records &rec, const uint32_t *keep_rs, T *post, const uint32_t *unsat_in, uint32_t *unsat_clear,
+              int32_t latch_it, const uint32_t *free_var, const uint32_t *free_rs, const Records *ev_rec, uint32_t n_free) const {
+    with_vec<T>(vec, [&](auto V) {
+      with_bool(ev_rec != nullptr, [&](auto EV) {
+        dev::VnEvent16<T> ev{};
+        if (ev_rec) ev = dev::VnEvent16<T>{free_var, free_rs, rec_in<true>(*ev_rec), n_free};
+        dev::from_records::vn_kernel<T, decltype(V)::value, 8, true, decltype(EV)::value>
+            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, rec_in<true>(rec), keep_rs, post, unsat_in, unsat_clear,
+                                            latch_it, ev);
       });
     });
   }

@@ -132,6 +132,10 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
                                                  {static_cast<T *>(w.rec[1]), w.rec_flags[1], rec_w_}};
     const uint32_t rec_rows = w.rec_flags[0] ? 2 * m : m * rec_w_;  // rows of T a compaction moves
     if (lfree && post_rows_keep_ > 0 && post_rows_keep_ <= n) post_move_rows = post_rows_keep_;
+    // "vn_records": the variable-node launch sums the kept variables from this iteration's records and the check-node launch
+    // stores no per-edge messages (from_records::vn_kernel); with 16-bit flags only
+    const bool vn_records = records && w.rec_flags[0] != nullptr && d_keep_rs_ && opt_vn_records_;
+    last_vn_records_.store(vn_records, std::memory_order_relaxed);
     const bool quiet = records && opt_rec_quiet_;
     if (quiet) {
       st.slice_state = w.slice_state;
@@ -174,7 +178,8 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       const dev::State stp = ticked(it);
       timed_begin(kKernelCheck, s);
       if (records)
-        launch.cn_rec(first, vec, rec_t, g, stp, chan, post, rbuf[(it + 1) & 1], rbuf[it & 1], msg, unsat_out, rec_run);
+        launch.cn_rec(first, vec, rec_t, g, stp, chan, post, rbuf[(it + 1) & 1], rbuf[it & 1], msg, unsat_out, rec_run,
+                      !vn_records);
       else if (lfree)
         launch.cn_lfree(first, vec, wide_mask, cn_t, g, stp, chan, post, m_in, m_out, unsat_out);
       else if (streaming)
@@ -187,7 +192,15 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       // (deferred L-free stores: the first convergences of a slice get their L-free posteriors from the records of the latched
       // iteration INSIDE this launch -- rounds 3-4 ran a small vn_free_rec_kernel launch behind it in every iteration, which
       // almost always found nothing: 4.4 us + a 5.7 us dispatch gap per iteration)
-      if (quiet && it > 1 && opt_vn_event_) {
+      if (vn_records) {
+        const bool event = quiet && it > 1 && opt_vn_event_;
+        launch.vn_rec(vec, vn_keep_t, g_keep, st, chan, rbuf[it & 1], d_keep_rs_.get<uint32_t>(), post,
+                      first ? nullptr : unsat_out, unsat[(it + 1) & 1], static_cast<int32_t>(it) - 1, d_free_var_.get<uint32_t>(),
+                      d_free_rs_.get<uint32_t>(), event ? &rbuf[(it - 1) & 1] : nullptr, n_free_);
+        if (quiet && it > 1 && !event)
+          launch.vn_free_rec(vec, vn_event_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[(it - 1) & 1], post,
+                             static_cast<int32_t>(it) - 1);
+      } else if (quiet && it > 1 && opt_vn_event_) {
         launch.vn_event(vec, vn_keep_t, g_keep, st, chan, m_out, post, unsat_out, unsat[(it + 1) & 1],
                         static_cast<int32_t>(it) - 1, d_free_var_.get<uint32_t>(), d_free_rs_.get<uint32_t>(), rbuf[(it - 1) & 1],
                         n_free_);
