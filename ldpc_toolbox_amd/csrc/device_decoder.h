@@ -66,6 +66,10 @@ class DeviceDecoder {
   uint32_t record_flag_bits() const { return row_records() ? rec_flag_bits_ : 0; }
   // whether the last decode call's variable-node launches read the row records ("vn_records")
   uint32_t last_vn_records() const { return last_vn_records_.load(std::memory_order_relaxed) ? 1 : 0; }
+  // "flags8" as set, and the bytes of a record's flags word in the last decode call: 1 (the byte form), 2, 4 or 8; 0: the call
+  // kept no flooding row records
+  uint32_t flags8() const { return opt_flags8_ ? 1 : 0; }
+  uint32_t last_record_flag_bytes() const { return last_record_flag_bytes_.load(std::memory_order_relaxed); }
 
   // codewords per group (rounded up to the wave tile).  0 = automatic.
   void set_group_size(size_t g) { group_pref_ = g; }
@@ -75,13 +79,14 @@ class DeviceDecoder {
   void set_min_group(size_t g) { min_group_ = g; }
   // codewords per group a call of `batch` codewords is cut into (the set value, else a default that grows for small graphs)
   size_t preferred_group(size_t batch) const { return pick_group(batch); }
-  // The 27 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
+  // The 28 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
   // percent are constants now, see kStreamBlock ... below).  Results never depend on any of them; each selects between
   // forms that tests/ compare bit for bit.  returns false for an unknown key.
   //   which kernels run   "lfree" (0: plain flooding min-sum kernels), "records" (0 / 1 / 2: per-edge messages / row records
   //                       where the graph suits them / wherever possible), "rec_quiet" (0: L-free posteriors stored every
   //                       iteration), "vn_event" (0: the first convergences' rebuild as a launch of its own), "vn_records" (0 / 1:
-  //                       the variable nodes summed from per-edge messages / from the row records, 16-bit flags only), "rec_long"
+  //                       the variable nodes summed from per-edge messages / from the row records, 16-bit flags only), "flags8" (0 / 1: the
+  //                       16-bit flags of rows of at most 7 edges stored as half-words / as bytes), "rec_long"
   //                       (1: the record kernel's long-row variant whatever the graph), "staged_minsum" (1: Minsum through
   //                       the generic LDS-staged kernel), "cn_reg" / "hl_reg" / "hl_records" (0: the LDS-staged / two-pass /
   //                       per-edge forms instead of register-resident rows and layered row records), "serial_levels"
@@ -208,6 +213,13 @@ class DeviceDecoder {
   // (default: on for plain Minsumf32 on DVB-S2 normal frames at rate 1/2, the one configuration measured to pay by the
   // project's bar, profiles/vn_records.txt; off for every other code, rule and precision)
   bool opt_vn_records_ = false;
+  // "flags8": where record_flag_bytes (graph_tables.h) says 1 -- 16-bit flags, rows of at most 7 edges -- the flags are stored
+  // as bytes and two argmin bits in the magnitudes' sign bits (record_flags8.h), in the first half of the same arrays: the
+  // key may change between calls.  (default: on where "vn_records" is -- plain Minsumf32 on DVB-S2 normal frames at rate 1/2,
+  // the one configuration timed: +2.9 .. +3.5 % codewords/s, profiles/record_flags8.txt; off for every other code, rule
+  // and precision, where the key selects it)
+  bool opt_flags8_ = false;
+  std::atomic<uint32_t> last_record_flag_bytes_{0};
   std::atomic<bool> last_vn_records_{false};  // (written by every group's run_group: with "lane_threads" from two host threads)
   uint32_t rec_w_ = 0;
   uint32_t rec_flag_bits_ = 0;  // 16: the records' flags are half-words in an array of their own (graph_tables.h)

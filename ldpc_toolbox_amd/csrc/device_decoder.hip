@@ -131,6 +131,9 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
       // the default: on for the one configuration measured to pay by the project's bar (profiles/vn_records.txt), plain
       // Minsumf32 on DVB-S2 normal frames at rate 1/2; everything else takes it with the key
       d->opt_vn_records_ = kr.ready && ok && !impl.f64 && impl.correction == Correction::None && is_dvbs2_half_rate_normal(g);
+      // "flags8", the byte form of those records' flags: the same rule and the same one configuration
+      // (profiles/record_flags8.txt); everything else with rows of at most 7 edges takes it with the key
+      d->opt_flags8_ = d->opt_vn_records_;
     }
   }
   if (ok && flooding_minsum && !impl.f64) {
@@ -221,6 +224,8 @@ bool DeviceDecoder::set_option(const std::string &key, int64_t value) {
     opt_vn_event_ = v != 0;
   else if (key == "vn_records")
     opt_vn_records_ = v != 0;
+  else if (key == "flags8")
+    opt_flags8_ = v != 0;
   else if (key == "rec_long")
     opt_rec_long_ = v != 0;
   else if (key == "compact")

@@ -6,6 +6,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "record_flags8.h"
 #include "slice_tasks.h"
 #include "sparse.h"
 
@@ -82,6 +83,15 @@ inline uint32_t record_flag_bits(uint32_t max_row_weight, bool f64) {
   const uint32_t word = f64 ? 64u : 32u;
   if (max_row_weight == 0 || max_row_weight > word) return 0;
   return max_row_weight + record_arg_bits(max_row_weight) <= 16 ? 16u : word;
+}
+// Bytes of that word in memory when the byte form is chosen ("flags8", device_decoder.h): 1 where the flags are a half-word
+// and the flip bits and the argmin take at most 10 bits -- rows of at most 7 edges: 8 bits in a byte of their own, 2 in the
+// sign bits of the stored magnitudes (record_flags8.h) --, else the width record_flag_bits names.  record_flag_bits keeps
+// naming the FAMILY (16 for such rows): the byte form is a way of storing the half-word family's records.
+inline uint32_t record_flag_bytes(uint32_t max_row_weight, bool f64) {
+  const uint32_t bits = record_flag_bits(max_row_weight, f64);
+  if (bits == 16 && max_row_weight + record_arg_bits(max_row_weight) <= 10) return 1;
+  return bits / 8;
 }
 inline RowRecordTables build_row_record_tables(const SparseMatrix::Csr &g, const LfreeTables &lf, bool f64) {
   RowRecordTables t;

@@ -30,6 +30,8 @@ namespace dev {
 //     mag    [M * 2][tile]  of T: min1 and min2 of row c in rows 2c and 2c + 1
 //     flags  [M][tile]      of uint16_t: flip bits 0..11, argmin in bits 12..15
 //   a record is then 2.5 words of f32 (2.25 of f64) in each direction
+//   with byte flags (F8; rows of at most 7 edges, graph_tables.h record_flag_bytes) the same pair with flags [M][tile] of
+//   uint8_t and two argmin bits in the magnitudes' sign bits (record_flags8.h): 2.25 words of f32 (2.125 of f64)
 // ---------------------------------------------------------------------------------------
 template <typename T>
 struct RecWord {
@@ -113,10 +115,35 @@ __device__ __forceinline__ void flags_store(const RowBuf &b, uint32_t lane_off, 
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, x), b.r, lane_off, row_off, NT ? 2 : 0);
 }
 
+// Byte flags (rows of at most 7 edges: graph_tables.h, record_flag_bytes; the format: record_flags8.h): the same array with
+// one byte per row and codeword.  A lane's VEC bytes are one b32 / b16 / b8 buffer access.
+static_assert(kArgShift16 == kRecArgShift16, "record_flags8.h encodes the register form of the 16-bit flags");
+template <int VEC, bool NT>
+__device__ __forceinline__ Pack<uint8_t, VEC> flags8_load(const RowBuf &b, uint32_t lane_off, uint32_t row_off) {
+  static_assert(VEC == 1 || VEC == 2 || VEC == 4, "pack size");
+  if constexpr (VEC == 1)
+    return __builtin_bit_cast(Pack<uint8_t, VEC>, __builtin_amdgcn_raw_buffer_load_b8(b.r, lane_off, row_off, NT ? 2 : 0));
+  else if constexpr (VEC == 2)
+    return __builtin_bit_cast(Pack<uint8_t, VEC>, __builtin_amdgcn_raw_buffer_load_b16(b.r, lane_off, row_off, NT ? 2 : 0));
+  else
+    return __builtin_bit_cast(Pack<uint8_t, VEC>, __builtin_amdgcn_raw_buffer_load_b32(b.r, lane_off, row_off, NT ? 2 : 0));
+}
+template <int VEC, bool NT>
+__device__ __forceinline__ void flags8_store(const RowBuf &b, uint32_t lane_off, uint32_t row_off, const Pack<uint8_t, VEC> &x) {
+  if constexpr (VEC == 1)
+    __builtin_amdgcn_raw_buffer_store_b8(__builtin_bit_cast(uint8_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
+  else if constexpr (VEC == 2)
+    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
+  else
+    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
+}
+
 // Where a launch finds the records: one array of T (flags in the record's own rows), or with 16-bit flags the magnitudes
 // and the flags array.  Ref: the kernel argument; Buf: the wavefront's slice behind buffer descriptors.
-template <typename T, bool F16>
+// F8 (with F16: the byte form stores the 16-bit family's records): RecPair8, the flags as bytes.
+template <typename T, bool F16, bool F8 = false>
 struct RecRef {
+  static_assert(!F8, "byte flags: a form of the 16-bit family");
   typedef const T *__restrict__ in;
   typedef T *__restrict__ out;
 };
@@ -126,10 +153,23 @@ struct RecPair {
   uint16_t *flags;
 };
 template <typename T>
-struct RecRef<T, true> {
+struct RecPair8 {
+  T *mag;
+  uint8_t *flags;
+};
+template <typename T>
+struct RecRef<T, true, false> {
   typedef RecPair<const T> in;
   typedef RecPair<T> out;
 };
+template <typename T>
+struct RecRef<T, true, true> {
+  typedef RecPair8<const T> in;
+  typedef RecPair8<T> out;
+};
+// the type of a record's stored flags word: the decoder's own word, uint16_t (F16) or uint8_t (F16 and F8)
+template <typename T, bool F16, bool F8 = false>
+using RecFlagWord = std::conditional_t<F16, std::conditional_t<F8, uint8_t, uint16_t>, typename RecWord<T>::type>;
 template <bool F16>
 struct RecBuf {
   RowBuf b;
@@ -153,16 +193,26 @@ __device__ __forceinline__ RecBuf<true> rec_buf(const RecPair<TT> &rec, uint32_t
                       row_buf(rec.flags + tile_base(b0, n_rows, sc), (uint64_t(n_rows) * sc.tile - in_tile) * sizeof(uint16_t))};
 }
 
+template <typename T, int RECW, typename TT>
+__device__ __forceinline__ RecBuf<true> rec_buf(const RecPair8<TT> &rec, uint32_t b0, uint32_t n_rows, const Sched &sc,
+                                                uint32_t row_bytes) {
+  static_assert(RECW == 3, "byte flags: the three-word family");
+  const uint32_t in_tile = in_tile_of(b0, sc);
+  return RecBuf<true>{row_buf(rec.mag + tile_base(b0, n_rows * 2, sc), uint64_t(n_rows) * 2 * row_bytes - in_tile * uint32_t(sizeof(T))),
+                      row_buf(rec.flags + tile_base(b0, n_rows, sc), uint64_t(n_rows) * sc.tile - in_tile)};
+}
+
 // FW, the type of the stored flags word: the decoder's own word (this form: the flags are the record's third row, and a
-// fourth for RECW == 4) or uint16_t (the specialisation below)
+// fourth for RECW == 4) or uint16_t / uint8_t (the specialisations below)
 template <typename T, int VEC, int RECW, typename FW = typename RecWord<T>::type>
 struct RowRec {
-  static_assert(std::is_same_v<FW, typename RecWord<T>::type>, "flags word: RecWord<T>::type or uint16_t");
+  static_assert(std::is_same_v<FW, typename RecWord<T>::type>, "flags word: RecWord<T>::type, uint16_t or uint8_t");
   typedef typename RecWord<T>::type W;
   // the flags word of a new record (RECW == 3): flip bits below the argmin
   static __device__ __forceinline__ W pack_flags(W fl, uint32_t arg) {
     return (fl & ((W(1) << RecWord<T>::kArgShift) - 1)) | (W(arg) << RecWord<T>::kArgShift);
   }
+  typedef RowRec New;  // a record built in registers
   static constexpr uint32_t kRows = RECW;  // rows of T per record: row c's record is at row_off = c * kRows * row_bytes
   __device__ __forceinline__ void load(const RecBuf<false> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) {
     load(b.b, lane_off, row_off, row_bytes);
@@ -204,6 +254,7 @@ struct RowRec<T, VEC, 3, uint16_t> {
   static __device__ __forceinline__ uint16_t pack_flags(W fl, uint32_t arg) {
     return uint16_t((uint32_t(fl) & ((1u << kArgShift16) - 1)) | (arg << kArgShift16));
   }
+  typedef RowRec New;
   static constexpr uint32_t kRows = 2;
   Pack<T, VEC> min1, min2;
   Pack<uint16_t, VEC> flip;
@@ -227,6 +278,53 @@ struct RowRec<T, VEC, 3, uint16_t> {
     return __builtin_bit_cast(T, __builtin_bit_cast(W, mag) | sign);
   }
 };
+// The same records with their flags as bytes (record_flags8.h).  New: a record built in registers (the 16-bit form's
+// members), encoded at `store`.  The record itself holds what `load` read, as it is in memory, and `value` decodes it into
+// the 16-bit form's registers on the spot.  Decoded once at `load` instead, the unpacked flags cost the steady-state f32
+// pack-of-4 check-node kernel 10 VGPRs (96 -> 106) and with them its fifth wave per SIMD; held as stored, the flags of four
+// codewords are ONE register and it stays at 96 -- at the price of a decode per value taken: 4804 vector instructions in that
+// kernel against the 16-bit twin's 2903, which costs it 25 us of 812 (profiles/record_flags8.txt, sections 3 to 5).
+template <typename T, int VEC>
+struct RowRec8New : RowRec<T, VEC, 3, uint16_t> {
+  typedef typename RecWord<T>::type W;
+  template <bool NT>
+  __device__ __forceinline__ void store(const RecBuf<true> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) const {
+    Pack<T, VEC> m1, m2;
+    Pack<uint8_t, VEC> fl;
+#pragma unroll
+    for (int k = 0; k < VEC; k++) {
+      const RecFlags8Stored<W> r = record_flags8_encode<W>(__builtin_bit_cast(W, this->min1.v[k]),
+                                                           __builtin_bit_cast(W, this->min2.v[k]), this->flip.v[k]);
+      m1.v[k] = __builtin_bit_cast(T, r.min1);
+      m2.v[k] = __builtin_bit_cast(T, r.min2);
+      fl.v[k] = r.byte;
+    }
+    buf_store<T, VEC, NT>(b.b, lane_off, row_off, m1);
+    buf_store<T, VEC, NT>(b.b, lane_off, row_off + row_bytes, m2);
+    flags8_store<VEC, NT>(b.f, lane_off / uint32_t(sizeof(T)), row_off / uint32_t(2 * sizeof(T)), fl);
+  }
+};
+template <typename T, int VEC>
+struct RowRec<T, VEC, 3, uint8_t> {
+  typedef typename RecWord<T>::type W;
+  typedef RowRec8New<T, VEC> New;
+  static __device__ __forceinline__ uint16_t pack_flags(W fl, uint32_t arg) { return New::pack_flags(fl, arg); }
+  static constexpr uint32_t kRows = 2;
+  Pack<T, VEC> min1, min2;   // as stored: argmin bits 1 and 2 in the sign bits
+  Pack<uint8_t, VEC> fl;
+  __device__ __forceinline__ void load(const RecBuf<true> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) {
+    min1 = buf_load<T, VEC, false>(b.b, lane_off, row_off);
+    min2 = buf_load<T, VEC, false>(b.b, lane_off, row_off + row_bytes);
+    fl = flags8_load<VEC, false>(b.f, lane_off / uint32_t(sizeof(T)), row_off / uint32_t(2 * sizeof(T)));
+  }
+  __device__ __forceinline__ T value(uint32_t slot, int k) const {
+    const RecFlags8Loaded<W> r = record_flags8_decode<W>(__builtin_bit_cast(W, min1.v[k]), __builtin_bit_cast(W, min2.v[k]), fl.v[k]);
+    const uint32_t f = r.flags;
+    const W mag = ((f >> kArgShift16) == slot) ? r.min2 : r.min1;
+    const W sign = W(f >> slot) << (8 * sizeof(W) - 1);
+    return __builtin_bit_cast(T, mag | sign);
+  }
+};
 
 
 // Posterior of the L-free variables from the row records: L = chan + (m_a + m_b), the messages read out of the
@@ -236,12 +334,12 @@ struct RowRec<T, VEC, 3, uint16_t> {
 //   event_iteration >= 0: after the variable-node pass that latched the FIRST converged codewords of a slice
 //                        (State::slice_state == 1) at that iteration count: for exactly those codewords, whose
 //                        L-free posteriors the check-node kernel had not been storing.
-// F16: the records' flags are 16-bit words in an array of their own (RecRef / RowRec above).
-template <typename T, int VEC, int RECW, bool F16 = false>
+// F16: the records' flags are 16-bit words in an array of their own (RecRef / RowRec above); F8: bytes.
+template <typename T, int VEC, int RECW, bool F16 = false, bool F8 = false>
 __global__ __launch_bounds__(256) void vn_free_rec_kernel(Graph g, Sched sc, State st, const uint32_t *__restrict__ free_rs_,
-                                                          const T *__restrict__ chan, typename RecRef<T, F16>::in rec,
+                                                          const T *__restrict__ chan, typename RecRef<T, F16, F8>::in rec,
                                                           T *__restrict__ post, int32_t event_iteration) {
-  typedef RowRec<T, VEC, RECW, std::conditional_t<F16, uint16_t, typename RecWord<T>::type>> Rec;
+  typedef RowRec<T, VEC, RECW, RecFlagWord<T, F16, F8>> Rec;
   if (event_iteration < 0 && *st.n_active == 0) return;
   const TablePtr free_var = table_ptr(g.list_var), free_rs = table_ptr(free_rs_);
   const uint32_t lane = threadIdx.x & 63u, tile = sc.tile;
@@ -310,16 +408,26 @@ struct VnEvent16 {  // the same with 16-bit flags (EVF16)
   RecPair<const T> rec;
   uint32_t n_free;
 };
+template <typename T>
+struct VnEvent8 {  // ... stored with byte flags (EVF16 and EVF8)
+  const uint32_t *free_var, *free_rs;
+  RecPair8<const T> rec;
+  uint32_t n_free;
+};
+template <typename T, bool EVF16, bool EVF8 = false>
+using VnEventOf = std::conditional_t<EVF16, std::conditional_t<EVF8, VnEvent8<T>, VnEvent16<T>>, VnEvent<T>>;
 __device__ __forceinline__ bool has_records(const void *rec) { return rec != nullptr; }
 template <typename T>
 __device__ __forceinline__ bool has_records(const RecPair<T> &rec) { return rec.mag != nullptr; }
+template <typename T>
+__device__ __forceinline__ bool has_records(const RecPair8<T> &rec) { return rec.mag != nullptr; }
 // (from_records::vn_kernel below repeats this kernel's prologue -- the idle test, the bookkeeping wave, the EVW block, the
 // slice_state latch -- line for line: a change to any of them is made in both)
-template <typename T, int VEC, int U, bool NT, bool LIST, int EVW = 0, bool EVF16 = false>
+template <typename T, int VEC, int U, bool NT, bool LIST, int EVW = 0, bool EVF16 = false, bool EVF8 = false>
 __global__ __launch_bounds__(256) void vn_kernel(
     Graph g, Sched sc, State st, const T *__restrict__ chan, const T *__restrict__ msg,
     T *__restrict__ post, const uint32_t *__restrict__ unsat_in, uint32_t *__restrict__ unsat_clear,
-    int32_t latch_iteration, std::conditional_t<EVF16, VnEvent16<T>, VnEvent<T>> ev = {}) {
+    int32_t latch_iteration, VnEventOf<T, EVF16, EVF8> ev = {}) {
   uint32_t *__restrict__ n_active = st.n_active;
   // A finished group's launches return at once.  With EVW the count can also reach zero INSIDE this launch -- the
   // bookkeeping waves below subtract the codewords they latch -- and a wave that starts after the last subtraction must
@@ -399,7 +507,7 @@ __global__ __launch_bounds__(256) void vn_kernel(
         for (uint32_t i = v_first; i < ev.n_free; i += waves_per_chunk) {
           const uint32_t fv = free_var[i], a = free_rs[2 * i], b = free_rs[2 * i + 1];
           const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(fv) * G);
-          typedef RowRec<T, VEC, EVW, std::conditional_t<EVF16, uint16_t, typename RecWord<T>::type>> Rec;
+          typedef RowRec<T, VEC, EVW, RecFlagWord<T, EVF16, EVF8>> Rec;
           Rec ra, rb;
           if (a != kAuxNone) ra.load(b_rec, lane_off, (a >> 6) * Rec::kRows * row_bytes, row_bytes);
           if (b != kAuxNone) rb.load(b_rec, lane_off, (b >> 6) * Rec::kRows * row_bytes, row_bytes);
@@ -508,6 +616,7 @@ __global__ __launch_bounds__(256) void vn_kernel(
 //           the iteration being latched, the other buffer), word for word; the bookkeeping wave likewise
 //   U       records in flight per lane; a variable of more edges takes further rounds
 //   NTCH    the channel rows (read by no other kernel in this form) through nontemporal loads
+//   F8      the records' flags are stored as bytes (rows of at most 7 edges), rec and ev.rec alike
 // Everything up to the main loop -- the idle test, the bookkeeping wave, the event block with its `fresh` rule, the
 // slice_state latch -- is vn_kernel's, line for line; the reasons are written there, once.  (Kept as a second copy and not as
 // shared helpers so that every existing instantiation of vn_kernel stays instruction-identical by construction.)
@@ -515,12 +624,12 @@ __global__ __launch_bounds__(256) void vn_kernel(
 // of an iteration by kernel name (bench.py's counter passes sum "vn_kernel") finds it under that name.
 // ---------------------------------------------------------------------------------------
 namespace from_records {
-template <typename T, int VEC, int U, bool NTCH, bool EV>
+template <typename T, int VEC, int U, bool NTCH, bool EV, bool F8 = false>
 __global__ __launch_bounds__(256) void vn_kernel(
-    Graph g, Sched sc, State st, const T *__restrict__ chan, RecPair<const T> rec, const uint32_t *__restrict__ keep_rs_,
-    T *__restrict__ post, const uint32_t *__restrict__ unsat_in, uint32_t *__restrict__ unsat_clear,
-    int32_t latch_iteration, VnEvent16<T> ev = {}) {
-  typedef RowRec<T, VEC, 3, uint16_t> Rec;
+    Graph g, Sched sc, State st, const T *__restrict__ chan, typename RecRef<T, true, F8>::in rec,
+    const uint32_t *__restrict__ keep_rs_, T *__restrict__ post, const uint32_t *__restrict__ unsat_in,
+    uint32_t *__restrict__ unsat_clear, int32_t latch_iteration, VnEventOf<T, true, F8> ev = {}) {
+  typedef RowRec<T, VEC, 3, RecFlagWord<T, true, F8>> Rec;
   uint32_t *__restrict__ n_active = st.n_active;
   const bool idle = *n_active == 0;  // (see vn_kernel: with EV a wave may still owe its share of the rebuild)
   if (!EV && idle) return;
@@ -1006,12 +1115,14 @@ __global__ __launch_bounds__(256) void cn_minsum_lfree_kernel(
 // F16: the records' flags are 16-bit words in an array of their own (RecRef / RowRec above): rows of at most 12 edges.
 // SEND = false: no per-edge messages are stored -- the variable-node launch rebuilds them from the records this launch
 // writes (from_records::vn_kernel); the record already holds the corrected pair, so the normalized / offset forms need nothing more.
+// F8: the 16-bit family's records stored with byte flags (rows of at most 7 edges: record_flags8.h); short rows only.
 template <typename T, int VEC, int RECW, bool F16, int U, bool FIRST, bool NT, bool STREAM = false, bool LONG = true, bool SEND = true,
-          typename... MC>
+          bool F8 = false, typename... MC>
 __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
-    Graph g, Sched sc, State st, const T *__restrict__ chan, T *__restrict__ post, typename RecRef<T, F16>::in rec_in,
-    typename RecRef<T, F16>::out rec_out, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t run, MC... mc) {
-  typedef RowRec<T, VEC, RECW, std::conditional_t<F16, uint16_t, typename RecWord<T>::type>> Rec;
+    Graph g, Sched sc, State st, const T *__restrict__ chan, T *__restrict__ post, typename RecRef<T, F16, F8>::in rec_in,
+    typename RecRef<T, F16, F8>::out rec_out, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t run, MC... mc) {
+  static_assert(!F8 || (F16 && !LONG), "byte flags: rows of at most 7 edges");
+  typedef RowRec<T, VEC, RECW, RecFlagWord<T, F16, F8>> Rec;
   constexpr bool CORR = sizeof...(MC) != 0;  // normalized / offset min-sum
   static_assert(is_corr_pack<T, MC...>, "mc: nothing, or one MinsumCorr<T>");
   typedef typename RecWord<T>::type W;
@@ -1241,7 +1352,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
       carry_var = next_carry_var;
       if (d != 0) {
         // the new record: flip[slot] = (parity of all signs) ^ (x_slot < 0)
-        Rec out;
+        typename Rec::New out;
 #pragma unroll
         for (int k = 0; k < VEC; k++) {
           const uint32_t tot = (sizeof(W) == 8 ? __popcll(sgn[k]) : __popc(uint32_t(sgn[k]))) & 1u;

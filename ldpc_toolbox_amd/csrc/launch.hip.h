@@ -87,29 +87,36 @@ struct Launch {
       });
     });
   }
-  // the record form of a flooding launch: f(RECW, F16) -- three words with the flags in the record's own rows or as 16-bit
-  // words in an array of their own (Records::flags), or four words
+  // the record form of a flooding launch: f(RECW, F16, F8) -- three words with the flags in the record's own rows, or as
+  // 16-bit words in an array of their own (Records::flags), or that array as bytes (Records::flags8: rows of at most 7
+  // edges, "flags8"), or four words
   struct Records {
     T *mag;           // the records ([M * recw][tile]); with 16-bit flags the magnitudes alone ([2M][tile])
     uint16_t *flags;  // [M][tile], or null: the flags are the record's third word
     uint32_t recw;
+    bool flags8 = false;  // the byte form: `flags` holds [M][tile] bytes (the array keeps its 16-bit size)
   };
   template <typename F>
   static void with_rec_form(const Records &r, F &&f) {
-    if (r.recw == 3 && r.flags != nullptr) return f(int_c<3>{}, std::true_type{});
-    if (r.recw == 3) return f(int_c<3>{}, std::false_type{});
-    f(int_c<4>{}, std::false_type{});
+    if (r.recw == 3 && r.flags != nullptr && r.flags8) return f(int_c<3>{}, std::true_type{}, std::true_type{});
+    if (r.recw == 3 && r.flags != nullptr) return f(int_c<3>{}, std::true_type{}, std::false_type{});
+    if (r.recw == 3) return f(int_c<3>{}, std::false_type{}, std::false_type{});
+    f(int_c<4>{}, std::false_type{}, std::false_type{});
   }
-  template <bool F16>
+  template <bool F16, bool F8 = false>
   static auto rec_in(const Records &r) {
-    if constexpr (F16)
+    if constexpr (F16 && F8)
+      return dev::RecPair8<const T>{r.mag, reinterpret_cast<uint8_t *>(r.flags)};
+    else if constexpr (F16)
       return dev::RecPair<const T>{r.mag, r.flags};
     else
       return static_cast<const T *>(r.mag);
   }
-  template <bool F16>
+  template <bool F16, bool F8 = false>
   static auto rec_out(const Records &r) {
-    if constexpr (F16)
+    if constexpr (F16 && F8)
+      return dev::RecPair8<T>{r.mag, reinterpret_cast<uint8_t *>(r.flags)};
+    else if constexpr (F16)
       return dev::RecPair<T>{r.mag, r.flags};
     else
       return r.mag;
@@ -122,13 +129,16 @@ struct Launch {
   void cn_rec(bool first, uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan, T *post,
               const Records &in, const Records &out, T *msg, uint32_t *unsat, uint32_t run, bool send = true) const {
     minsum(vec, first, [&](auto V, auto FIRST, auto... mc) {
-      with_rec_form(in, [&](auto W, auto F16) {
+      with_rec_form(in, [&](auto W, auto F16, auto F8) {
         with_bool(rec_long, [&](auto long_rows) {
+          // (byte flags: rows of at most 7 edges, so only the short-row variant has them; run_group never sets Records::flags8
+          // beside rec_long -- every launch of a call must agree on the form)
+          constexpr bool kF8 = decltype(F8)::value && !decltype(long_rows)::value;
           auto go_rec = [&](auto SEND) {
             dev::cn_minsum_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, 8, decltype(FIRST)::value,
-                                      true, false, decltype(long_rows)::value, decltype(SEND)::value, decltype(mc)...>
-                <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_in<decltype(F16)::value>(in),
-                                                rec_out<decltype(F16)::value>(out), msg, unsat, run, mc...);
+                                      true, false, decltype(long_rows)::value, decltype(SEND)::value, kF8, decltype(mc)...>
+                <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_in<decltype(F16)::value, kF8>(in),
+                                                rec_out<decltype(F16)::value, kF8>(out), msg, unsat, run, mc...);
           };
           if constexpr (decltype(F16)::value) {
             if (!send) return go_rec(std::false_type{});
@@ -141,10 +151,10 @@ struct Launch {
   void vn_free_rec(uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const uint32_t *free_rs,
                    const T *chan, const Records &rec, T *post, int32_t event_iteration) const {
     with_vec<T>(vec, [&](auto V) {
-      with_rec_form(rec, [&](auto W, auto F16) {
-        dev::vn_free_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value>
-            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, free_rs, chan, rec_in<decltype(F16)::value>(rec), post,
-                                            event_iteration);
+      with_rec_form(rec, [&](auto W, auto F16, auto F8) {
+        dev::vn_free_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, decltype(F8)::value>
+            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, free_rs, chan, rec_in<decltype(F16)::value, decltype(F8)::value>(rec),
+                                            post, event_iteration);
       });
     });
   }
@@ -192,16 +202,17 @@ struct Launch {
                 const uint32_t *unsat_in, uint32_t *unsat_clear, int32_t latch_it, const uint32_t *free_var,
                 const uint32_t *free_rs, const Records &rec, uint32_t n_free) const {
     with_vec<T>(vec, [&](auto V) {
-      with_rec_form(rec, [&](auto W, auto F16) {
-        const std::conditional_t<decltype(F16)::value, dev::VnEvent16<T>, dev::VnEvent<T>> ev{
-            free_var, free_rs, rec_in<decltype(F16)::value>(rec), n_free};
-        dev::vn_kernel<T, decltype(V)::value, 8, true, true, decltype(W)::value, decltype(F16)::value>
+      with_rec_form(rec, [&](auto W, auto F16, auto F8) {
+        const dev::VnEventOf<T, decltype(F16)::value, decltype(F8)::value> ev{
+            free_var, free_rs, rec_in<decltype(F16)::value, decltype(F8)::value>(rec), n_free};
+        dev::vn_kernel<T, decltype(V)::value, 8, true, true, decltype(W)::value, decltype(F16)::value, decltype(F8)::value>
             <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, msg, post, unsat_in, unsat_clear, latch_it, ev);
       });
     });
   }
 
-  // the list variant that sums the kept variables from the records of this iteration (from_records::vn_kernel; 16-bit flags).  ev_rec
+  // the list variant that sums the kept variables from the records of this iteration (from_records::vn_kernel; 16-bit flags, or
+  // the same records with byte flags).  ev_rec
   // null: no event block (the first iteration, or "vn_event" / "rec_quiet" off).
   // (eight records in flight and nontemporal channel loads: the headline gains 0.65 % over four in flight -- 98 against 57
   // VGPRs, 4 against 8 waves per SIMD -- and 0.35 % over cached channel loads, profiles/vn_records.txt section 1)
@@ -210,11 +221,14 @@ struct Launch {
               int32_t latch_it, const uint32_t *free_var, const uint32_t *free_rs, const Records *ev_rec, uint32_t n_free) const {
     with_vec<T>(vec, [&](auto V) {
       with_bool(ev_rec != nullptr, [&](auto EV) {
-        dev::VnEvent16<T> ev{};
-        if (ev_rec) ev = dev::VnEvent16<T>{free_var, free_rs, rec_in<true>(*ev_rec), n_free};
-        dev::from_records::vn_kernel<T, decltype(V)::value, 8, true, decltype(EV)::value>
-            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, rec_in<true>(rec), keep_rs, post, unsat_in, unsat_clear,
-                                            latch_it, ev);
+        with_bool(rec.flags8, [&](auto F8) {
+          constexpr bool kF8 = decltype(F8)::value;
+          dev::VnEventOf<T, true, kF8> ev{};
+          if (ev_rec) ev = dev::VnEventOf<T, true, kF8>{free_var, free_rs, rec_in<true, kF8>(*ev_rec), n_free};
+          dev::from_records::vn_kernel<T, decltype(V)::value, 8, true, decltype(EV)::value, kF8>
+              <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, rec_in<true, kF8>(rec), keep_rs, post, unsat_in, unsat_clear,
+                                              latch_it, ev);
+        });
       });
     });
   }

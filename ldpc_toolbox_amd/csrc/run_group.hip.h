@@ -46,9 +46,10 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
   // batch compaction checkpoint (kernels.hip.h): everything decided on the device
   const Tiling mv_t = make_tiling(G, tile, 64, n, 256, kMoveWaves);
   uint32_t post_move_rows = 0;  // 0 = all rows; set by the flooding L-free paths below
-  // (flags, flag_rows: the 16-bit flags of flooding row records, which travel with their magnitudes in msg_cur)
+  // (flags, flag_rows: the 16-bit flags of flooding row records, which travel with their magnitudes in msg_cur; flags8: the
+  // same array holds bytes)
   auto compact = [&](uint32_t remaining, T *msg_cur, bool with_chan, uint32_t msg_rows, uint16_t *flags = nullptr,
-                     uint32_t flag_rows = 0) {
+                     uint32_t flag_rows = 0, bool flags8 = false) {
     grp::compact_plan(s, ticked(max_iterations - remaining), w.plan, w.perm, w.slot_tmp, w.fill_cw, remaining,
         dev::CompactRule{kCompactHorizon, kCompactCostLive, kCompactCostSlots, kCompactMinFreedQ});
     emit(0, 1);
@@ -67,7 +68,11 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     if (msg_rows) add(msg_cur, msg_rows, msg_rows);
     dev::compact_move_kernel<T><<<mv_t.blocks, mv_t.threads, 0, s>>>(w.plan, w.perm, w.slot_tmp, ml, tile,
                                                                      mv_t.sched.nchunks, mv_t.sched.waves_per_chunk);
-    if (flags) {
+    if (flags && flags8) {
+      const dev::MoveList<uint8_t> fl{{reinterpret_cast<uint8_t *>(flags)}, {flag_rows}, {flag_rows}, 1};
+      dev::compact_move_kernel<uint8_t><<<mv_t.blocks, mv_t.threads, 0, s>>>(w.plan, w.perm, w.slot_tmp, fl, tile,
+                                                                           mv_t.sched.nchunks, mv_t.sched.waves_per_chunk);
+    } else if (flags) {
       const dev::MoveList<uint16_t> fl{{flags}, {flag_rows}, {flag_rows}, 1};
       dev::compact_move_kernel<uint16_t><<<mv_t.blocks, mv_t.threads, 0, s>>>(w.plan, w.perm, w.slot_tmp, fl, tile,
                                                                             mv_t.sched.nchunks, mv_t.sched.waves_per_chunk);
@@ -88,6 +93,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
 
   uint32_t *unsat[2] = {w.unsat0, w.unsat1};
   int zero_fill = 0;
+  last_record_flag_bytes_.store(0, std::memory_order_relaxed);  // (the flooding record path says what it ran)
 
   if (impl_.schedule == Schedule::Flooding) {
     // the streaming min-sum kernels keep a row's signs in a 64-bit mask: longer rows take the
@@ -128,8 +134,14 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     const bool lfree = streaming && lfree_ready_ && opt_lfree_ && (w.msg2 != nullptr || records);
     T *mbuf[2] = {msg, (lfree && !records) ? static_cast<T *>(w.msg2) : msg};
     // (16-bit flags, rows of at most 12 edges: w.rec_flags holds them, w.rec the magnitudes alone)
-    const typename Launch<T>::Records rbuf[2] = {{static_cast<T *>(w.rec[0]), w.rec_flags[0], rec_w_},
-                                                 {static_cast<T *>(w.rec[1]), w.rec_flags[1], rec_w_}};
+    // "flags8": rows of at most 7 edges store those flags as bytes, in the first half of the same arrays (record_flags8.h); one
+    // decision for every launch of the call -- the long-row variant of the record kernel ("rec_long") has no byte form
+    const bool flags8 = records && w.rec_flags[0] != nullptr && opt_flags8_ && !launch.rec_long &&
+                        record_flag_bytes(max_row_weight_, sizeof(T) == 8) == 1;
+    if (records) last_record_flag_bytes_.store((flags8 ? 1u : (w.rec_flags[0] ? 2u : uint32_t(sizeof(T)))),
+                                  std::memory_order_relaxed);
+    const typename Launch<T>::Records rbuf[2] = {{static_cast<T *>(w.rec[0]), w.rec_flags[0], rec_w_, flags8},
+                                                 {static_cast<T *>(w.rec[1]), w.rec_flags[1], rec_w_, flags8}};
     const uint32_t rec_rows = w.rec_flags[0] ? 2 * m : m * rec_w_;  // rows of T a compaction moves
     if (lfree && post_rows_keep_ > 0 && post_rows_keep_ <= n) post_move_rows = post_rows_keep_;
     // "vn_records": the variable-node launch sums the kept variables from this iteration's records and the check-node launch
@@ -215,7 +227,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       if (checkpoint_due(it) || tail_checkpoint(it)) {
         // what the next iteration reads: the records of this one (the per-edge messages have been consumed)
         if (records)
-          compact(max_iterations - it, rbuf[it & 1].mag, true, rec_rows, rbuf[it & 1].flags, m);
+          compact(max_iterations - it, rbuf[it & 1].mag, true, rec_rows, rbuf[it & 1].flags, m, flags8);
         else
           compact(max_iterations - it, m_out, true, static_cast<uint32_t>(e_));
       }
