@@ -23,7 +23,8 @@ enum : uint32_t { kPeerKeep = 0x80000000u, kPeerPosMask = 0x7FFFFFFFu, kPeerWrit
 enum : uint32_t { kNoLane = 0xFFFFFFFFu };
 }  // namespace dev
 
-// the row-record kernel fetches a row's first indices as one block: a few entries of slack behind edge_col and peer
+// the row-record kernel fetches a row's first indices as one block of U entries -- 8, or 7 in the byte form of the flags
+// (launch.hip.h, cn_rec) -- whatever the row's length: this much slack behind edge_col and peer keeps any U up to 16 in bounds
 constexpr uint32_t kTablePad = 16;
 
 // L-free variables (degree 1 or 2) of the flooding min-sum path (kernels_flooding.hip.h, cn_minsum_lfree_kernel): the

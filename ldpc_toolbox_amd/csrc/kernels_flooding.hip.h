@@ -279,11 +279,12 @@ struct RowRec<T, VEC, 3, uint16_t> {
   }
 };
 // The same records with their flags as bytes (record_flags8.h).  New: a record built in registers (the 16-bit form's
-// members), encoded at `store`.  The record itself holds what `load` read, as it is in memory, and `value` decodes it into
-// the 16-bit form's registers on the spot.  Decoded once at `load` instead, the unpacked flags cost the steady-state f32
-// pack-of-4 check-node kernel 10 VGPRs (96 -> 106) and with them its fifth wave per SIMD; held as stored, the flags of four
-// codewords are ONE register and it stays at 96 -- at the price of a decode per value taken: 4804 vector instructions in that
-// kernel against the 16-bit twin's 2903, which costs it 25 us of 812 (profiles/record_flags8.txt, sections 3 to 5).
+// members), encoded at `store`.  A loaded record has two forms.  RowRec<T, VEC, 3, uint8_t>, the form of the variable-node
+// kernels (from_records::vn_kernel, vn_free_rec_kernel, vn_kernel's event block), holds what `load` read, as it is in memory,
+// and `value` decodes it into the 16-bit form's registers on the spot: they take one value, or two, of each record they
+// load.  RowRec8Once below is the check-node kernel's, which takes up to eight values of a record and decodes it once.
+// (Until profiles/cn_flags8_decode.txt the check-node kernel used the first form too: 4804 vector instructions against the
+// 16-bit twin's 2903, and 25 us of 812 lost to them -- profiles/record_flags8.txt, sections 3 to 5.)
 template <typename T, int VEC>
 struct RowRec8New : RowRec<T, VEC, 3, uint16_t> {
   typedef typename RecWord<T>::type W;
@@ -323,6 +324,41 @@ struct RowRec<T, VEC, 3, uint8_t> {
     const W mag = ((f >> kArgShift16) == slot) ? r.min2 : r.min1;
     const W sign = W(f >> slot) << (8 * sizeof(W) - 1);
     return __builtin_bit_cast(T, mag | sign);
+  }
+};
+// The byte form as the check-node kernel holds it (cn_minsum_rec_kernel with F8): the magnitudes and the lane's VEC flag
+// bytes as stored, in one register, and beside them ONE register of argmins, byte k the argmin of codeword k, put together
+// once at `load`.  A value is then record_flags8_value's select between the two stored words and one bit-field insert of the
+// shifted flip bit over the stored sign bit -- compare, select, shift, insert: what the 16-bit form spends -- in the ten
+// registers per record (f32 pack of 4) that form holds, and nothing is masked at `load`.
+template <typename T, int VEC>
+struct RowRec8Once {
+  typedef typename RecWord<T>::type W;
+  typedef RowRec8New<T, VEC> New;
+  static constexpr uint32_t kRows = 2;
+  Pack<T, VEC> min1, min2;  // as stored: argmin bits 1 and 2 in the sign bits
+  uint32_t fl, arg;         // byte k: codeword k's stored flags byte; its argmin
+  __device__ __forceinline__ void load(const RecBuf<true> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) {
+    min1 = buf_load<T, VEC, false>(b.b, lane_off, row_off);
+    min2 = buf_load<T, VEC, false>(b.b, lane_off, row_off + row_bytes);
+    const Pack<uint8_t, VEC> bytes = flags8_load<VEC, false>(b.f, lane_off / uint32_t(sizeof(T)), row_off / uint32_t(2 * sizeof(T)));
+    fl = 0;
+#pragma unroll
+    for (int k = 0; k < VEC; k++) fl |= uint32_t(bytes.v[k]) << (8 * k);
+    // bit 0 of all VEC argmins with one shift and one mask, then bits 1 and 2 from each codeword's sign bits
+    uint32_t a = (fl >> 7) & 0x01010101u;
+#pragma unroll
+    for (int k = 0; k < VEC; k++)
+      a |= record_flags8_arg<W>(__builtin_bit_cast(W, min1.v[k]), __builtin_bit_cast(W, min2.v[k]), uint8_t(0)) << (8 * k);
+    // (both words opaque to the compiler: it would otherwise take them apart again and keep a byte and an argmin per codeword
+    // in registers of their own, which is the register count this form exists to avoid)
+    asm("" : "+v"(fl));
+    asm("" : "+v"(a));
+    arg = a;
+  }
+  __device__ __forceinline__ T value(uint32_t slot, int k) const {
+    return __builtin_bit_cast(T, record_flags8_value<W>(__builtin_bit_cast(W, min1.v[k]), __builtin_bit_cast(W, min2.v[k]),
+                                                        uint8_t(fl >> (8 * k)), (arg >> (8 * k)) & 0xFFu, slot));
   }
 };
 
@@ -1115,14 +1151,20 @@ __global__ __launch_bounds__(256) void cn_minsum_lfree_kernel(
 // F16: the records' flags are 16-bit words in an array of their own (RecRef / RowRec above): rows of at most 12 edges.
 // SEND = false: no per-edge messages are stored -- the variable-node launch rebuilds them from the records this launch
 // writes (from_records::vn_kernel); the record already holds the corrected pair, so the normalized / offset forms need nothing more.
-// F8: the 16-bit family's records stored with byte flags (rows of at most 7 edges: record_flags8.h); short rows only.
+// F8: the 16-bit family's records stored with byte flags (rows of at most 7 edges: record_flags8.h); short rows only, and
+// U = 7: a row is one round of seven loads (the tables' padding, graph_tables.h kTablePad, covers any U up to 16).  The byte
+// form also holds the signs and the running argmin of a row in ONE register per codeword (`sa`), folds the minima with
+// selects instead of branches, and keeps a loaded record's argmins in one register (RowRec8Once): 91 VGPRs and 2929 vector
+// instructions in the steady-state f32 pack-of-4 kernel, where decoding per value had 96 and 4804
+// (profiles/cn_flags8_decode.txt).
 template <typename T, int VEC, int RECW, bool F16, int U, bool FIRST, bool NT, bool STREAM = false, bool LONG = true, bool SEND = true,
           bool F8 = false, typename... MC>
 __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     Graph g, Sched sc, State st, const T *__restrict__ chan, T *__restrict__ post, typename RecRef<T, F16, F8>::in rec_in,
     typename RecRef<T, F16, F8>::out rec_out, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t run, MC... mc) {
   static_assert(!F8 || (F16 && !LONG), "byte flags: rows of at most 7 edges");
-  typedef RowRec<T, VEC, RECW, RecFlagWord<T, F16, F8>> Rec;
+  static_assert(!F8 || U == int(kRecFlags8MaxRow), "byte flags: a row is one round of 7 loads");
+  typedef std::conditional_t<F8, RowRec8Once<T, VEC>, RowRec<T, VEC, RECW, RecFlagWord<T, F16, F8>>> Rec;
   constexpr bool CORR = sizeof...(MC) != 0;  // normalized / offset min-sum
   static_assert(is_corr_pack<T, MC...>, "mc: nothing, or one MinsumCorr<T>");
   typedef typename RecWord<T>::type W;
@@ -1243,6 +1285,9 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
       T min1[VEC], min2[VEC];
       uint32_t arg[VEC];
       W sgn[VEC];
+      // F8: both in one register, the 16-bit flags word as it grows -- the signs of at most 7 edges below the running argmin
+      uint32_t sa[VEC];
+      constexpr uint32_t kSgnMask8 = (1u << kRecFlags8MaxRow) - 1;
       uint64_t par_m[VEC];
 #pragma unroll
       for (int k = 0; k < VEC; k++) {
@@ -1250,6 +1295,7 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
         min2[k] = Limits<T>::inf();
         arg[k] = 0;
         sgn[k] = 0;
+        sa[k] = 0;
         par_m[k] = 0;
       }
       uint32_t next_carry_slot = kAuxNone;
@@ -1296,9 +1342,19 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
           sent.v[k] = m_own;
           const T x = FIRST ? l : (l - m_own);
           const T a = m_abs(x);
-          if (x < T(0.0)) sgn[k] |= W(1) << slot;
+          if constexpr (F8) {
+            if (x < T(0.0)) sa[k] |= 1u << slot;
+          } else {
+            if (x < T(0.0)) sgn[k] |= W(1) << slot;
+          }
           par_m[k] ^= __builtin_amdgcn_ballot_w64(l <= T(0.0));
-          if (a < min1[k]) {
+          if constexpr (F8) {
+            // the same fold as selects: no branch, no change of the exec mask per edge and codeword
+            const bool lt1 = a < min1[k], lt2 = a < min2[k];
+            min2[k] = lt1 ? min1[k] : (lt2 ? a : min2[k]);
+            min1[k] = lt1 ? a : min1[k];
+            sa[k] = lt1 ? ((sa[k] & kSgnMask8) | (slot << kArgShift16)) : sa[k];
+          } else if (a < min1[k]) {
             min2[k] = min1[k];
             min1[k] = a;
             arg[k] = slot;
@@ -1353,11 +1409,26 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
       if (d != 0) {
         // the new record: flip[slot] = (parity of all signs) ^ (x_slot < 0)
         typename Rec::New out;
+        if constexpr (CORR && F8) {
+          // The byte form corrects each magnitude on its own, fenced from its neighbours: left to itself the compiler pairs the
+          // eight corrections into packed f32 math, whose operands want aligned register pairs and copies of alpha and beta
+          // in vector registers -- 99 VGPRs in the f32 pack-of-4 kernel without per-edge messages, where this has 91.
+#pragma unroll
+          for (int k = 0; k < VEC; k++) {
+            asm("" : "+v"(min1[k]));
+            asm("" : "+v"(min2[k]));
+            min1[k] = minsum_corrected(min1[k], mc...);
+            min2[k] = minsum_corrected(min2[k], mc...);
+            asm("" : "+v"(min1[k]));
+            asm("" : "+v"(min2[k]));
+          }
+        }
 #pragma unroll
         for (int k = 0; k < VEC; k++) {
-          const uint32_t tot = (sizeof(W) == 8 ? __popcll(sgn[k]) : __popc(uint32_t(sgn[k]))) & 1u;
+          const uint32_t tot =
+              F8 ? __popc(sa[k] & kSgnMask8) & 1u : (sizeof(W) == 8 ? __popcll(sgn[k]) : __popc(uint32_t(sgn[k]))) & 1u;
           odd_m[k] |= par_m[k];
-          if constexpr (CORR) {
+          if constexpr (CORR && !F8) {
             // the record holds the corrected pair, so every reader of the record (value()) sees corrected messages
             out.min1.v[k] = minsum_corrected(min1[k], mc...);
             out.min2.v[k] = minsum_corrected(min2[k], mc...);
@@ -1366,7 +1437,9 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
             out.min2.v[k] = min2[k];
           }
           const W fl = tot ? ~sgn[k] : sgn[k];
-          if constexpr (RECW == 4) {
+          if constexpr (F8) {
+            out.flip.v[k] = uint16_t(tot ? sa[k] ^ kSgnMask8 : sa[k]);  // (pack_flags: the word is packed already)
+          } else if constexpr (RECW == 4) {
             out.flip.v[k] = fl;
             out.arg.v[k] = W(arg[k]);
           } else {

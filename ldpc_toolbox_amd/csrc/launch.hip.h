@@ -134,8 +134,10 @@ struct Launch {
           // (byte flags: rows of at most 7 edges, so only the short-row variant has them; run_group never sets Records::flags8
           // beside rec_long -- every launch of a call must agree on the form)
           constexpr bool kF8 = decltype(F8)::value && !decltype(long_rows)::value;
+          // (and so the byte form has seven loads in flight per lane, a whole row, where every other form has eight)
+          constexpr int kU = kF8 ? int(kRecFlags8MaxRow) : 8;
           auto go_rec = [&](auto SEND) {
-            dev::cn_minsum_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, 8, decltype(FIRST)::value,
+            dev::cn_minsum_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, kU, decltype(FIRST)::value,
                                       true, false, decltype(long_rows)::value, decltype(SEND)::value, kF8, decltype(mc)...>
                 <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_in<decltype(F16)::value, kF8>(in),
                                                 rec_out<decltype(F16)::value, kF8>(out), msg, unsat, run, mc...);

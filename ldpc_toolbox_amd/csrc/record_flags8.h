@@ -1,6 +1,8 @@
 // The byte form of a flooding row record's flags (rows of at most 7 edges: graph_tables.h, record_flag_bytes), as the pair
-// of functions that turns the record's registers into what memory holds and back.  Host and device compile the same code:
-// the kernels' RowRec<T, VEC, 3, uint8_t> (kernels_flooding.hip.h) and tests/record_flags8_driver.cpp on the CPU.
+// of functions that turns the record's registers into what memory holds and back, and the value a reader takes from the
+// stored words directly (record_flags8_value, at the end).  Host and device compile the same code: the kernels' RowRec<T,
+// VEC, 3, uint8_t> and RowRec8Once (kernels_flooding.hip.h), tests/record_flags8_driver.cpp and
+// tests/record_flags8_value_driver.cpp on the CPU.
 //
 // In registers a record is the 16-bit form's: two magnitudes with clear sign bits and a half-word, flip bits 0..11 and the
 // argmin in bits 12..15.  With at most 7 edges that is 7 flip bits and 3 argmin bits, and the stored magnitudes never use
@@ -49,6 +51,33 @@ REC8_FN RecFlags8Loaded<W> record_flags8_decode(W min1, W min2, uint8_t byte) {
   const uint32_t b = byte;
   const uint32_t arg = (b >> 7) | (uint32_t(min1 >> kSign) << 1) | (uint32_t(min2 >> kSign) << 2);
   return RecFlags8Loaded<W>{W(min1 & mag), W(min2 & mag), uint16_t((b & 0x7Fu) | (arg << kRecArgShift16))};
+}
+
+// The message a stored record sends on `slot`, taken from the stored words themselves -- what the 16-bit form's `value`
+// returns for record_flags8_decode's output, without building that output: the argmin once per record and codeword
+// (record_flags8_arg), then per slot one select between the stored words, whose sign bits the flip bit replaces.
+// (x with its sign bit replaced by s's.  Spelt as the floating-point copysign, a pure bit operation on every target: the
+// GPU then has one bit-field insert, and knows that only s's top bit is read -- the flip bit need only be SHIFTED there)
+REC8_FN uint32_t record_flags8_with_sign_of(uint32_t x, uint32_t s) {
+  return __builtin_bit_cast(uint32_t, __builtin_copysignf(__builtin_bit_cast(float, x), __builtin_bit_cast(float, s)));
+}
+REC8_FN uint64_t record_flags8_with_sign_of(uint64_t x, uint64_t s) {
+  return __builtin_bit_cast(uint64_t, __builtin_copysign(__builtin_bit_cast(double, x), __builtin_bit_cast(double, s)));
+}
+template <typename W>
+REC8_FN uint32_t record_flags8_arg(W min1, W min2, uint8_t byte) {
+  constexpr int kSign = 8 * sizeof(W) - 1;
+  return (uint32_t(byte) >> 7) | (uint32_t(min1 >> kSign) << 1) | (uint32_t(min2 >> kSign) << 2);
+}
+template <typename W>
+REC8_FN W record_flags8_value(W min1, W min2, uint8_t byte, uint32_t arg, uint32_t slot) {
+  constexpr int kSign = 8 * sizeof(W) - 1;
+  const W sel = (arg == slot) ? min2 : min1;
+  return record_flags8_with_sign_of(sel, W(W(uint32_t(byte) >> slot) << kSign));
+}
+template <typename W>
+REC8_FN W record_flags8_value(W min1, W min2, uint8_t byte, uint32_t slot) {
+  return record_flags8_value<W>(min1, min2, byte, record_flags8_arg<W>(min1, min2, byte), slot);
 }
 
 }  // namespace ldpc
