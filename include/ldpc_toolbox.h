@@ -390,6 +390,67 @@ int32_t ldpc_toolbox_awgn_run_f64_device(void *demod, double *symbols, size_t sy
  * returns 0, or -1 for an unknown key. */
 int32_t ldpc_toolbox_demod_get(void *demod, const char *key, int64_t *value);
 
+/* ===================================================================================
+ * PART 5 -- batched BCH outer code on the GPU: the DVB-S2 outer code (EN 302 307-1 5.3.1) and any narrow-sense binary
+ * BCH code over GF(2^4)..GF(2^16).  The reference has no BCH code; its simulation counts "a frame with at most
+ * bch_max_errors bit errors" as corrected (src/simulation/ber.rs:328-337).
+ * =================================================================================== */
+
+/* spec: "dvbs2:NAME" with the names of ldpc_toolbox_code_alist ("R1_2", "R8_9short", ...): (n, k, t) of the standard,
+ * GF(2^16) with P = 1 + x^2 + x^3 + x^5 + x^16 for normal frames, GF(2^14) with P = 1 + x + x^3 + x^5 + x^14 for short
+ * ones -- or "bch:M:P:T:N": GF(2^M) built from the primitive polynomial P (hex, bit i = coefficient of x^i, alpha = x),
+ * T errors corrected, shortened length N.  g(x) = lcm of the minimal polynomials of alpha^1, alpha^3, ..., alpha^(2T-1),
+ * derived from P; parity = deg g, k = n - parity.
+ * NULL (message via ldpc_toolbox_last_error) for an unknown name, M outside 4..16, a P of another degree or not primitive,
+ * T < 1, 2T >= 2^M - 1, T > 12, N > 2^M - 1 or N - deg g < 1.
+ * n is the LDPC code's k, so the handles chain -- except for "dvbs2:R3_4short": the library's LDPC code of that name
+ * follows the reference's m() and has k = 1080, the BCH handle follows the standard (n = 11880); the length checks of
+ * the entries refuse that chain by themselves.
+ * The constructor needs no GPU (`device` is used by the first batched call; -1 = LDPC_TOOLBOX_DEVICE, default 0). */
+void *ldpc_toolbox_bch_ctor(const char *spec, int32_t device);
+void ldpc_toolbox_bch_dtor(void *bch);
+/* key: "n", "k", "t", "m", "parity", "primitive" (P), "pass_frames" (frames per pass of a batched call),
+ * "stage_frames" (frames a host entry stages on the device at a time), "device" (-1
+ * until the first batched call made the device state).  returns 0, or -1 for an unknown key. */
+int32_t ldpc_toolbox_bch_get(void *bch, const char *key, int64_t *value);
+/* g_0 .. g_parity, one byte each, when len >= parity + 1; returns parity + 1. */
+size_t ldpc_toolbox_bch_generator(void *bch, uint8_t *coefficients, size_t len);
+/* Bytes hold one bit each; on input a byte equal to 1 is a one and anything else a zero (the encoder's convention),
+ * outputs are 0 or 1.  Byte i of a row of length n is the coefficient of x^(n-1-i): the first message bit is the highest
+ * power.  input [batch][k] -> output [batch][n], c(x) = x^parity m(x) + (x^parity m(x) mod g(x)): the first k bytes are
+ * the normalised message, the last `parity` the remainder -- exactly the `input` of
+ * ldpc_toolbox_encoder_encode_batch_device.
+ * input_len != k, output_len != n or a null handle: LDPC_TOOLBOX_ERR_ARGUMENT before the GPU is touched, nothing written.
+ * Without a GPU LDPC_TOOLBOX_ERR_DEVICE (there is no CPU path).  batch == 0 returns 0; batch is otherwise unlimited.
+ * Input and output do not overlap.  One call at a time per handle.  Host pointers (staged through the handle's buffers)
+ * or, _device, device pointers and a hipStream_t: a stream = enqueue and return; NULL = the handle's own stream, ordered
+ * after what the legacy default stream holds at the call, synchronised on return. */
+int32_t ldpc_toolbox_bch_encode_batch(void *bch, uint8_t *output, size_t output_len, const uint8_t *input, size_t input_len,
+                                      size_t batch);
+int32_t ldpc_toolbox_bch_encode_batch_device(void *bch, uint8_t *output, size_t output_len, const uint8_t *input,
+                                             size_t input_len, size_t batch, void *hip_stream);
+/* Bounded-distance decoder.  input [batch][n] (the LDPC decode entries' `output` with output_len = k_ldpc) -> output
+ * [batch][output_len], output_len = k (the message) or n (the whole word); errors [batch] may be NULL.
+ * If a codeword c within Hamming distance t of the input exists (it is unique), the output is c (its first output_len
+ * bytes) and errors = the distance, corrected parity bits included.  Otherwise the output is the normalised input
+ * unchanged and errors = -1.  Other behaviour as ldpc_toolbox_bch_encode_batch. */
+int32_t ldpc_toolbox_bch_decode_batch(void *bch, uint8_t *output, size_t output_len, const uint8_t *input, size_t input_len,
+                                      size_t batch, int32_t *errors);
+int32_t ldpc_toolbox_bch_decode_batch_device(void *bch, uint8_t *output, size_t output_len, const uint8_t *input,
+                                             size_t input_len, size_t batch, int32_t *errors, void *hip_stream);
+/* The simulator's option to run the real code instead of the genie of ldpc_toolbox_sim_run_bch.  The code is copied
+ * (the handle may be destroyed afterwards); returns -1 with a message and changes nothing unless the code's n equals the
+ * simulator's k -- which also refuses "dvbs2:R3_4short" on the library's LDPC code of that name.  NULL returns to the
+ * genie.  Resets the straggler-pooling budget, as "modulation" does.  "bch" of ldpc_toolbox_sim_get is 1 while a code is set.
+ * With a code set, ldpc_toolbox_sim_run_bch requires bch_max_errors == t (else LDPC_TOOLBOX_ERR_ARGUMENT); counters 0..5
+ * are what they are without it, and counters 6..8 come from the real decoder.  Per frame: e = the XOR of the frame's k
+ * hard decisions with its pooled message; the bounded-distance decoder runs on e -- by linearity that is the outcome for
+ * EVERY transmitted BCH codeword, so the pool's messages are not BCH codewords and need not be; residual = the weight of
+ * the first k_bch bits of the decoder's output; [6] += residual, [7] += (residual > 0), [8] += the frame's iterations
+ * when residual == 0.  This differs from the genie where it should: a miscorrection adds errors, parity bits are not
+ * payload, and a frame whose more-than-t errors all lie in the parity is correct.  The counters do not depend on "pooling". */
+int32_t ldpc_toolbox_sim_set_bch(void *sim, void *bch);
+
 /* Standard-code generator (what the reference's `dvbs2` / `5g` / `ccsds` / `ccsds-c2` CLI
  * sub-commands print, src/cli/dvbs2.rs:91, src/cli/nr5g.rs:46, src/cli/ccsds.rs:70): writes the
  * padded alist text of `spec` ("dvbs2:R1_2", "nr5g:1:384", "ar4ja:1/2:1024", "c2") into

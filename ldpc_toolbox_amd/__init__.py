@@ -4,10 +4,11 @@ this package is the Python mirror of the reference's interface for that path."""
 from . import _capi
 from .decoder import (ALL_IMPLEMENTATIONS, CORRECTED_MINSUM_IMPLEMENTATIONS, FAST_IMPLEMENTATIONS, DecoderImplementation, DecoderOutput, DecoderUnavailable, Encoder,
                       I8_IMPLEMENTATIONS, IMPLEMENTATIONS, MINSUM_I8_IMPLEMENTATIONS, LdpcDecoder, Simulator)
+from .bch import BchCode
 from .demodulator import Demodulator
 from .sparse import SparseMatrix
 
 code_alist = _capi.code_alist
 
-__all__ = ["ALL_IMPLEMENTATIONS", "CORRECTED_MINSUM_IMPLEMENTATIONS", "FAST_IMPLEMENTATIONS", "I8_IMPLEMENTATIONS", "DecoderImplementation", "DecoderOutput", "DecoderUnavailable", "Demodulator", "Encoder",
+__all__ = ["ALL_IMPLEMENTATIONS", "BchCode", "CORRECTED_MINSUM_IMPLEMENTATIONS", "FAST_IMPLEMENTATIONS", "I8_IMPLEMENTATIONS", "DecoderImplementation", "DecoderOutput", "DecoderUnavailable", "Demodulator", "Encoder",
            "IMPLEMENTATIONS", "MINSUM_I8_IMPLEMENTATIONS", "LdpcDecoder", "Simulator", "SparseMatrix", "code_alist"]

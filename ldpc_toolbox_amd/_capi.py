@@ -62,6 +62,15 @@ SYMBOLS = [
     "ldpc_toolbox_awgn_run_f32_device",
     "ldpc_toolbox_awgn_run_f64_device",
     "ldpc_toolbox_demod_get",
+    "ldpc_toolbox_bch_ctor",
+    "ldpc_toolbox_bch_dtor",
+    "ldpc_toolbox_bch_get",
+    "ldpc_toolbox_bch_generator",
+    "ldpc_toolbox_bch_encode_batch",
+    "ldpc_toolbox_bch_encode_batch_device",
+    "ldpc_toolbox_bch_decode_batch",
+    "ldpc_toolbox_bch_decode_batch_device",
+    "ldpc_toolbox_sim_set_bch",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
     "ldpc_toolbox_device_count",
@@ -226,6 +235,24 @@ def lib():
         f.argtypes = [vp, vp, sz, sz, C.c_double, u64, u64, vp]
     L.ldpc_toolbox_demod_get.restype = i32
     L.ldpc_toolbox_demod_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
+    L.ldpc_toolbox_bch_ctor.restype = vp
+    L.ldpc_toolbox_bch_ctor.argtypes = [cp, i32]
+    L.ldpc_toolbox_bch_dtor.restype = None
+    L.ldpc_toolbox_bch_dtor.argtypes = [vp]
+    L.ldpc_toolbox_bch_get.restype = i32
+    L.ldpc_toolbox_bch_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
+    L.ldpc_toolbox_bch_generator.restype = sz
+    L.ldpc_toolbox_bch_generator.argtypes = [vp, vp, sz]
+    L.ldpc_toolbox_bch_encode_batch.restype = i32
+    L.ldpc_toolbox_bch_encode_batch.argtypes = [vp, vp, sz, vp, sz, sz]
+    L.ldpc_toolbox_bch_encode_batch_device.restype = i32
+    L.ldpc_toolbox_bch_encode_batch_device.argtypes = [vp, vp, sz, vp, sz, sz, vp]
+    L.ldpc_toolbox_bch_decode_batch.restype = i32
+    L.ldpc_toolbox_bch_decode_batch.argtypes = [vp, vp, sz, vp, sz, sz, vp]
+    L.ldpc_toolbox_bch_decode_batch_device.restype = i32
+    L.ldpc_toolbox_bch_decode_batch_device.argtypes = [vp, vp, sz, vp, sz, sz, vp, vp]
+    L.ldpc_toolbox_sim_set_bch.restype = i32
+    L.ldpc_toolbox_sim_set_bch.argtypes = [vp, vp]
     L.ldpc_toolbox_code_alist.restype = sz
     L.ldpc_toolbox_code_alist.argtypes = [cp, vp, sz]
     L.ldpc_toolbox_alist_normalize.restype = sz

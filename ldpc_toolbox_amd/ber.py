@@ -227,6 +227,9 @@ def main(argv=None):
     ap.add_argument("--output-file")
     ap.add_argument("--bch-max-errors", type=int, default=0,
                     help="outer BCH code: frames with at most this many bit errors count as corrected (cli/ber.rs:83)")
+    ap.add_argument("--bch-code", metavar="SPEC",
+                    help='the real outer code instead of that count: "dvbs2:NAME" or "bch:M:P:T:N" (its n must be the LDPC '
+                         "code's k); sets --bch-max-errors to its t")
     ap.add_argument("--output-file-ldpc", help="LDPC-only results when --bch-max-errors is used (cli/ber.rs:102-105)")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal of the multi-GPU sweep on a one-GPU box: every rank uses GPU 0 and the counters are "
@@ -236,6 +239,8 @@ def main(argv=None):
         ap.error("--min-ebn0, --max-ebn0 and --step-ebn0 are required (except with --codes ... --grid waterfall)")
     if not a.codes and not a.code and not a.alist:
         ap.error("one of --code, --alist, --codes is required")
+    if a.codes and a.bch_code:
+        ap.error("--bch-code names one code: it cannot be combined with --codes")
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -270,6 +275,17 @@ def main(argv=None):
     alist = open(a.alist).read() if a.alist else _capi.code_alist(a.code)
     sim = Simulator(alist, a.decoder, a.puncturing, device=local, pool_size=a.pool_size, pool_seed=a.seed + 1,
                     modulation=make_modulation(a, local), interleaving=a.interleaving, max_log=a.max_log)
+    if a.bch_code:
+        from .bch import BchCode
+        code = BchCode(a.bch_code, device=local)
+        if a.bch_max_errors not in (0, code.t):
+            ap.error(f"--bch-max-errors {a.bch_max_errors} contradicts --bch-code {a.bch_code} (t = {code.t})")
+        a.bch_max_errors = code.t
+        try:
+            sim.set_bch(code)
+        except ValueError as e:
+            ap.error(f"--bch-code {a.bch_code}: {e}")
+        code.close()
     out = open(a.output_file, "w") if (a.output_file and rank == 0) else None
     out_ldpc = open(a.output_file_ldpc, "w") if (a.output_file_ldpc and a.bch_max_errors > 0 and rank == 0) else None
     details = format_details(a, sim, world)

@@ -3,6 +3,7 @@
 // /root/reference/src/c_api/encoder.rs; every entry point below cites what it replaces.
 #include "../../include/ldpc_toolbox.h"
 
+#include <algorithm>
 #include <cerrno>
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +16,7 @@
 
 #include "codes.h"
 #include "demodulator.h"
+#include "device_bch.h"
 #include "device_decoder.h"
 #include "device_encoder.h"
 #include "encoder.h"
@@ -59,6 +61,13 @@ struct DemodHandle {
   int device = 0;
   // the device state: made at the first run
   std::unique_ptr<ldpc::DeviceDemodulator> dev;
+};
+
+struct BchHandle {
+  ldpc::bch::Code code;
+  int device = 0;
+  // the device state: made at the first batched call
+  std::unique_ptr<ldpc::DeviceBch> dev;
 };
 
 // a device index: decimal digits only (no sign, no trailing characters)
@@ -306,6 +315,47 @@ int32_t awgn_run(void *demod, void *symbols, size_t symbols_len, size_t batch, b
   const int rc = on_device ? h->dev->awgn_device(symbols, f64, symbols_len, batch, sigma, seed, first_frame,
                                                  static_cast<hipStream_t>(stream))
                            : h->dev->awgn_host(symbols, f64, symbols_len, batch, sigma, seed, first_frame);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+int32_t bch_run(void *bch, bool decode, uint8_t *output, size_t output_len, const uint8_t *input, size_t input_len, size_t batch,
+                int32_t *errors, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<BchHandle *>(bch);
+  if (!h) {
+    set_error("null BCH handle");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (const char *why = ldpc::bch::bch_argument_error(h->code, decode, output_len, input_len)) {
+    set_error(why);
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (batch == 0) return 0;
+  if (!input || !output) {
+    set_error("null input or output buffer");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (!h->dev) {
+    if (h->device < 0) {
+      set_error("LDPC_TOOLBOX_DEVICE is not a decimal GPU index");
+      return LDPC_TOOLBOX_ERR_DEVICE;
+    }
+    std::string err;
+    h->dev.reset(ldpc::DeviceBch::create(h->code, h->device, &err));
+    if (!h->dev) {
+      set_error(err);
+      return LDPC_TOOLBOX_ERR_DEVICE;
+    }
+  }
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int rc;
+  if (decode)
+    rc = on_device ? h->dev->decode_device(input, output, output_len, batch, errors, s)
+                   : h->dev->decode_host(input, output, output_len, batch, errors);
+  else
+    rc = on_device ? h->dev->encode_device(input, output, batch, s) : h->dev->encode_host(input, output, batch);
   if (rc == 0) return 0;
   set_error(h->dev->last_error());
   return LDPC_TOOLBOX_ERR_DEVICE;
@@ -740,6 +790,8 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value) {
     *value = s->has_constellation() ? 1 : 0;
   else if (k == "max_log")
     *value = s->max_log() ? 1 : 0;
+  else if (k == "bch")  // 1 while ldpc_toolbox_sim_set_bch is in force
+    *value = s->has_bch() ? 1 : 0;
   else if (k == "streamed_frames" || k == "stream_iterations")  // (continuous batching: profiles/r03_continuous_batching.txt)
     *value = 0;
   else if (k == "pooled_frames")  // frames of the last run() call that went through the straggler pool
@@ -782,6 +834,19 @@ int32_t ldpc_toolbox_sim_set_constellation(void *sim, void *demod, int32_t max_l
   }
   auto *h = static_cast<DemodHandle *>(demod);
   if (s->set_constellation(h ? &h->c : nullptr, max_log != 0)) return 0;
+  set_error(s->last_error());
+  return -1;
+}
+
+int32_t ldpc_toolbox_sim_set_bch(void *sim, void *bch) {
+  g_last_error.clear();
+  auto *s = static_cast<ldpc::Simulator *>(sim);
+  if (!s) {
+    set_error("null argument");
+    return -1;
+  }
+  auto *h = static_cast<BchHandle *>(bch);
+  if (s->set_bch(h ? &h->code : nullptr)) return 0;
   set_error(s->last_error());
   return -1;
 }
@@ -889,6 +954,81 @@ int32_t ldpc_toolbox_demod_get(void *demod, const char *key, int64_t *value) {
   else
     return -1;
   return 0;
+}
+
+// ---- PART 5: batched BCH outer code ----------------------------------------------------------------
+
+void *ldpc_toolbox_bch_ctor(const char *spec, int32_t device) {
+  g_last_error.clear();
+  if (!spec) {
+    set_error("null BCH spec");
+    return nullptr;
+  }
+  auto h = std::make_unique<BchHandle>();
+  std::string err;
+  if (!ldpc::bch::parse_spec(spec, &h->code, &err)) {
+    set_error(err);
+    return nullptr;
+  }
+  h->device = device < 0 ? default_device() : device;
+  return h.release();
+}
+
+void ldpc_toolbox_bch_dtor(void *bch) { delete static_cast<BchHandle *>(bch); }
+
+int32_t ldpc_toolbox_bch_get(void *bch, const char *key, int64_t *value) {
+  auto *h = static_cast<BchHandle *>(bch);
+  if (!h || !key || !value) return -1;
+  const std::string k = key;
+  if (k == "n")
+    *value = h->code.n;
+  else if (k == "k")
+    *value = h->code.k;
+  else if (k == "t")
+    *value = h->code.t;
+  else if (k == "m")
+    *value = h->code.m;
+  else if (k == "parity")
+    *value = h->code.parity;
+  else if (k == "primitive")
+    *value = h->code.poly;
+  else if (k == "pass_frames")  // frames per pass of a batched call
+    *value = static_cast<int64_t>(ldpc::kBchPassFrames);
+  else if (k == "stage_frames")  // frames a host entry stages on the device at a time
+    *value = static_cast<int64_t>(std::max<size_t>(std::min(ldpc::kBchStageFrames, ldpc::kBchStageBytes / h->code.n), 1));
+  else if (k == "device")
+    *value = h->dev ? h->dev->device() : -1;
+  else
+    return -1;
+  return 0;
+}
+
+size_t ldpc_toolbox_bch_generator(void *bch, uint8_t *coefficients, size_t len) {
+  auto *h = static_cast<BchHandle *>(bch);
+  if (!h) return 0;
+  const std::vector<uint8_t> &g = h->code.g;
+  if (coefficients && len >= g.size()) std::memcpy(coefficients, g.data(), g.size());
+  return g.size();
+}
+
+int32_t ldpc_toolbox_bch_encode_batch(void *bch, uint8_t *output, size_t output_len, const uint8_t *input, size_t input_len,
+                                      size_t batch) {
+  return bch_run(bch, false, output, output_len, input, input_len, batch, nullptr, false, nullptr);
+}
+
+int32_t ldpc_toolbox_bch_encode_batch_device(void *bch, uint8_t *output, size_t output_len, const uint8_t *input,
+                                             size_t input_len, size_t batch, void *hip_stream) {
+  return bch_run(bch, false, output, output_len, input, input_len, batch, nullptr, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_bch_decode_batch(void *bch, uint8_t *output, size_t output_len, const uint8_t *input, size_t input_len,
+                                      size_t batch, int32_t *errors) {
+  return bch_run(bch, true, output, output_len, input, input_len, batch, errors, false, nullptr);
+}
+
+int32_t ldpc_toolbox_bch_decode_batch_device(void *bch, uint8_t *output, size_t output_len, const uint8_t *input,
+                                             size_t input_len, size_t batch, int32_t *errors, void *hip_stream) {
+  return bch_run(bch, true, output, output_len, input, input_len, batch, errors, true, hip_stream);
 }
 
 size_t ldpc_toolbox_code_alist(const char *spec, char *buffer, size_t buffer_len) {

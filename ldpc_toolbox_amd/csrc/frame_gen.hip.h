@@ -248,6 +248,47 @@ __global__ __launch_bounds__(256) void count_errors_kernel(const uint8_t *__rest
   }
 }
 
+// With a real outer code (Simulator::set_bch).  pattern[f][i] = decoded[f][i] ^ the frame's pooled message[i], i < k:
+// what the BCH decoder runs on.  One wave per frame, the frames as in count_errors_kernel.
+__global__ __launch_bounds__(256) void bch_pattern_kernel(const uint8_t *__restrict__ decoded, const uint8_t *__restrict__ messages,
+                                                          uint32_t k, uint32_t pool, uint64_t seed, uint64_t first_frame,
+                                                          uint32_t frames, uint8_t *__restrict__ pattern,
+                                                          const uint64_t *__restrict__ frame_ids) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t f = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (f >= frames) return;
+  const uint8_t *msg = messages + size_t(pool_index(seed, frame_ids ? frame_ids[f] : first_frame + f, pool)) * k;
+  const uint8_t *dec = decoded + size_t(f) * k;
+  uint8_t *e = pattern + size_t(f) * k;
+  for (uint32_t i = lane; i < k; i += 64) e[i] = (dec[i] != msg[i]) ? 1 : 0;
+}
+
+// counters [6] [7] [8] from the BCH decoder's output on those patterns, corrected [frames][k_bch]: the residual errors
+// of a frame are the ones left in it.  skip_failed as in count_errors_kernel.
+__global__ __launch_bounds__(256) void count_bch_kernel(const uint8_t *__restrict__ corrected, uint32_t k_bch,
+                                                        const int32_t *__restrict__ iterations, uint32_t frames,
+                                                        uint32_t max_iterations, unsigned long long *__restrict__ counters,
+                                                        int skip_failed) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t f = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (f >= frames) return;
+  if (skip_failed && iterations[f] < 0) return;
+  const uint8_t *row = corrected + size_t(f) * k_bch;
+  uint32_t residual = 0;
+  for (uint32_t i = lane; i < k_bch; i += 64) residual += row[i];
+  for (int off = 32; off > 0; off >>= 1) residual += __shfl_down(residual, off, 64);
+  if (lane == 0) {
+    const int32_t it = iterations[f];
+    const uint32_t its = it >= 0 ? static_cast<uint32_t>(it) : max_iterations;
+    if (residual) {
+      atomicAdd(&counters[6], static_cast<unsigned long long>(residual));
+      atomicAdd(&counters[7], 1ull);
+    } else {
+      atomicAdd(&counters[8], static_cast<unsigned long long>(its));
+    }
+  }
+}
+
 // Straggler pooling (Simulator::run_bch): the frames of a chunk that have not converged within the chunk's iteration
 // budget are set aside -- their LLR rows and frame numbers appended to a pool -- and decoded later, many at a time, with
 // the full budget.  One wavefront per frame.

@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "demodulator.h"
+#include "device_bch.h"
 #include "device_decoder.h"
 #include "hip_owned.h"
 #include "encoder.h"
@@ -46,6 +47,10 @@ class Simulator {
   bool max_log() const { return use_constellation_ && max_log_; }
   int modulation() const { return use_constellation_ ? static_cast<int>(constellation_.bits) : bits_per_symbol_; }
   int64_t interleaving() const { return interleaving_; }
+  // An outer BCH code (a copy of the one a BCH handle holds) in place of the genie of run_bch; nullptr returns to the
+  // genie.  false with nothing changed unless the code's n is this simulator's k.
+  bool set_bch(const bch::Code *c);
+  bool has_bch() const { return bch_ != nullptr; }
   DeviceDecoder *decoder() { return dec_.get(); }
   // straggler pooling (run_bch): 0 = every chunk runs the full iteration budget
   void set_pooling(bool on) {
@@ -65,6 +70,13 @@ class Simulator {
   // The same with the outer-BCH accounting of ber.rs:328-337: counters[9] = the six above, then
   // BCH bit errors, BCH frame errors (frames with more than bch_max_errors bit errors) and the
   // iterations of the frames the BCH code corrects.
+  // With a code set (set_bch) bch_max_errors must be its t (else -4, 0 included), and counters 6..8 come from the real
+  // decoder; run() does not see the code.
+  // Per frame, e = the frame's k hard decisions XOR its pooled message; the bounded-distance decoder runs on e -- by
+  // linearity the outcome for EVERY transmitted BCH codeword, so the pool's messages need not be codewords --
+  // residual = the weight of the first k_bch bits of its output; [6] += residual, [7] += residual > 0, [8] += the
+  // frame's iterations when residual == 0.  A miscorrection adds errors, parity bits are not payload, and a frame
+  // whose errors all lie in the parity is correct.
   int run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations,
               uint64_t bch_max_errors, uint64_t counters[9]);
   // The same frames' LLRs (host [frames][n_tx]) and pooled-codeword indices, for tests.
@@ -104,7 +116,15 @@ class Simulator {
   DeviceBuffer d_pool_llrs_, d_pool_frames_, d_pool_count_, d_pool_bits_, d_pool_its_;
   size_t pool_cap_ = 0;
   int ensure_pool(size_t capacity);
-  int flush_pool(uint32_t count, uint64_t seed, uint32_t max_iterations, uint64_t bch_max_errors, size_t chunk_group);
+  int flush_pool(uint32_t count, uint64_t seed, uint32_t max_iterations, uint64_t bch_max_errors, bool real_bch, size_t chunk_group);
+  int run_frames(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations,
+                 uint64_t bch_max_errors, bool real_bch, uint64_t counters[9]);
+  // the outer code of set_bch: the error patterns of a chunk (or of the pool) and what the decoder makes of them
+  std::unique_ptr<DeviceBch> bch_;
+  bch::Code bch_code_;
+  DeviceBuffer d_bch_in_, d_bch_out_;
+  int count_bch(const uint8_t *bits, const int32_t *its, uint64_t seed, uint64_t first_frame, uint32_t frames,
+                uint32_t max_iterations, const uint64_t *frame_ids, int skip_failed);
   std::string error_;
 };
 

@@ -7,6 +7,7 @@
 #include <random>
 
 #include "demodulator.hip.h"      // so does the batched soft demapper
+#include "device_bch.hip.h"       // and the batched BCH code
 #include "device_encoder.hip.h"  // the batched GPU encoder lives in this translation unit
 #include "frame_gen.hip.h"
 #include "implementation.h"
@@ -117,7 +118,7 @@ int Simulator::ensure_pool(size_t capacity) {
 }
 
 // the pooled stragglers, with the full iteration budget (the stream is idle: the caller has just read the count)
-int Simulator::flush_pool(uint32_t count, uint64_t seed, uint32_t max_iterations, uint64_t bch_max_errors,
+int Simulator::flush_pool(uint32_t count, uint64_t seed, uint32_t max_iterations, uint64_t bch_max_errors, bool real_bch,
                           size_t chunk_group) {
   // (a call on the decoder's own stream: a handful of stragglers takes the single-launch small-batch path; a pool too
   // large for that is decoded in the chunks' group size, so that the decoder keeps the workspace it has -- a group
@@ -132,8 +133,12 @@ int Simulator::flush_pool(uint32_t count, uint64_t seed, uint32_t max_iterations
   }
   gen::count_errors_kernel<<<(count * 64 + 255) / 256, 256, 0, stream_>>>(
       d_pool_bits_.get<uint8_t>(), static_cast<uint32_t>(k_), d_pool_its_.get<int32_t>(), d_messages_.get<uint8_t>(),
-      static_cast<uint32_t>(k_), pool_, seed, 0, count, max_iterations, bch_max_errors, d_counters_.get<unsigned long long>(),
-      d_pool_frames_.get<uint64_t>(), nullptr, 0);
+      static_cast<uint32_t>(k_), pool_, seed, 0, count, max_iterations, real_bch ? 0 : bch_max_errors,
+      d_counters_.get<unsigned long long>(), d_pool_frames_.get<uint64_t>(), nullptr, 0);
+  if (real_bch)
+    if (int rc = count_bch(d_pool_bits_.get<uint8_t>(), d_pool_its_.get<int32_t>(), seed, 0, count, max_iterations,
+                           d_pool_frames_.get<uint64_t>(), 0))
+      return rc;
   SIM_TRY(hipMemsetAsync(d_pool_count_.get(), 0, sizeof(uint32_t), stream_));
   pooled_frames_ += count;
   return 0;
@@ -162,6 +167,49 @@ bool Simulator::set_constellation(const Constellation *c, bool max_log) {
   max_log_ = c != nullptr && max_log;
   budget_valid_ = false;  // (as in set_modulation)
   return true;
+}
+
+bool Simulator::set_bch(const bch::Code *c) {
+  if (c != nullptr) {
+    if (c->n != k_) {
+      fail("the BCH code's n is not the LDPC code's k");
+      return false;
+    }
+    std::string e;
+    std::unique_ptr<DeviceBch> d(DeviceBch::create(*c, device_, &e));
+    if (!d) {
+      fail(e);
+      return false;
+    }
+    bch_ = std::move(d);
+    bch_code_ = *c;
+  } else {
+    bch_.reset();
+    d_bch_in_ = DeviceBuffer();
+    d_bch_out_ = DeviceBuffer();
+  }
+  budget_valid_ = false;  // (as in set_modulation)
+  return true;
+}
+
+// counters 6..8 of `frames` decoded frames (bits [frames][k]) from the real outer decoder, on the simulator's stream
+int Simulator::count_bch(const uint8_t *bits, const int32_t *its, uint64_t seed, uint64_t first_frame, uint32_t frames,
+                         uint32_t max_iterations, const uint64_t *frame_ids, int skip_failed) {
+  const uint32_t k = static_cast<uint32_t>(k_);
+  // (run_frames has sized both for a chunk and for a full pool; a count beyond them is refused, never written)
+  if (d_bch_in_.capacity() < size_t(frames) * k_ || d_bch_out_.capacity() < size_t(frames) * bch_code_.k) {
+    fail("the BCH buffers are smaller than the frames to count");
+    return -3;
+  }
+  gen::bch_pattern_kernel<<<(frames * 64 + 255) / 256, 256, 0, stream_>>>(bits, d_messages_.get<uint8_t>(), k, pool_, seed, first_frame,
+                                                                         frames, d_bch_in_.get<uint8_t>(), frame_ids);
+  if (bch_->decode_device(d_bch_in_.get<uint8_t>(), d_bch_out_.get<uint8_t>(), bch_code_.k, frames, nullptr, stream_)) {
+    error_ = bch_->last_error();
+    return -2;
+  }
+  gen::count_bch_kernel<<<(frames * 64 + 255) / 256, 256, 0, stream_>>>(d_bch_out_.get<uint8_t>(), bch_code_.k, its, frames, max_iterations,
+                                                                       d_counters_.get<unsigned long long>(), skip_failed);
+  return 0;
 }
 
 bool Simulator::set_interleaving(int64_t columns) {
@@ -254,13 +302,24 @@ void Simulator::launch_generator(double ebn0_db, uint64_t seed, uint64_t first_f
 int Simulator::run(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations,
                    uint64_t counters[6]) {
   uint64_t all[9];
-  const int rc = run_bch(ebn0_db, seed, first_frame, frames, max_iterations, 0, all);
+  const int rc = run_frames(ebn0_db, seed, first_frame, frames, max_iterations, 0, false, all);
   for (int i = 0; i < 6; i++) counters[i] = all[i];
   return rc;
 }
 
 int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations,
                        uint64_t bch_max_errors, uint64_t counters[9]) {
+  if (bch_ && bch_max_errors != bch_code_.t) {
+    for (int i = 0; i < 9; i++) counters[i] = 0;
+    fail("bch_max_errors is not the t of the BCH code in force");
+    return -4;
+  }
+  return run_frames(ebn0_db, seed, first_frame, frames, max_iterations, bch_max_errors, bch_ != nullptr, counters);
+}
+
+// real_bch: counters 6..8 from the decoder of set_bch; else from the genie when bch_max_errors > 0
+int Simulator::run_frames(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations,
+                          uint64_t bch_max_errors, bool real_bch, uint64_t counters[9]) {
   for (int i = 0; i < 9; i++) counters[i] = 0;
   if (frames == 0) return 0;
   SIM_TRY(hipSetDevice(device_));
@@ -275,6 +334,11 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
   if (can_pool) {
     if (int rc = ensure_pool(2 * chunk)) return rc;
     SIM_TRY(hipMemsetAsync(d_pool_count_.get(), 0, sizeof(uint32_t), stream_));
+  }
+  if (real_bch) {  // the patterns of a chunk, or of a full pool -- whose capacity an earlier call with larger chunks may have left
+    const size_t rows = can_pool ? std::max(pool_cap_, chunk) : chunk;
+    SIM_TRY(d_bch_in_.ensure(rows * k_));
+    SIM_TRY(d_bch_out_.ensure(rows * bch_code_.k));
   }
   // (a sweep calls run() again and again at one Eb/N0: the budget the previous call arrived at carries over)
   const bool same_point = can_pool && budget_valid_ && budget_ebn0_ == ebn0_db && budget_max_it_ == max_iterations;
@@ -313,8 +377,12 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
           static_cast<uint32_t>(pool_cap_));
     gen::count_errors_kernel<<<(nf * 64 + 255) / 256, 256, 0, stream_>>>(
         d_bits_.get<uint8_t>(), static_cast<uint32_t>(k_), d_its_.get<int32_t>(), d_messages_.get<uint8_t>(), static_cast<uint32_t>(k_),
-        pool_, seed, first_frame + f0, nf, max_iterations, bch_max_errors, d_counters_.get<unsigned long long>(), nullptr, nullptr,
-        reduced ? 1 : 0);
+        pool_, seed, first_frame + f0, nf, max_iterations, real_bch ? 0 : bch_max_errors, d_counters_.get<unsigned long long>(),
+        nullptr, nullptr, reduced ? 1 : 0);
+    if (real_bch)
+      if (int rc = count_bch(d_bits_.get<uint8_t>(), d_its_.get<int32_t>(), seed, first_frame + f0, nf, max_iterations, nullptr,
+                             reduced ? 1 : 0))
+        return rc;
     if (can_pool) {
       // what the frames of this call have needed so far decides the next chunk's budget (a call that cannot pool -- a
       // single chunk at a new point -- reads the counters once, at the end: no synchronisation between its launches)
@@ -331,7 +399,7 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
       budget = next;
       next_call_budget = next;
       if (f0 + chunk < frames && pooled + chunk > pool_cap_) {
-        if (int rc = flush_pool(pooled, seed, max_iterations, bch_max_errors, chunk_group)) return rc;
+        if (int rc = flush_pool(pooled, seed, max_iterations, bch_max_errors, real_bch, chunk_group)) return rc;
       }
     }
   }
@@ -350,7 +418,7 @@ int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size
       return -3;
     }
     if (pooled)
-      if (int rc = flush_pool(pooled, seed, max_iterations, bch_max_errors, chunk_group)) return rc;
+      if (int rc = flush_pool(pooled, seed, max_iterations, bch_max_errors, real_bch, chunk_group)) return rc;
   }
   unsigned long long host[9];
   SIM_TRY(hipMemcpyAsync(host, d_counters_.get(), sizeof(host), hipMemcpyDeviceToHost, stream_));

@@ -369,6 +369,14 @@ class Simulator:
         if _capi.lib().ldpc_toolbox_sim_set_constellation(self._h, h, int(bool(max_log))) != 0:
             raise ValueError(_capi.last_error() or "cannot set the constellation")
 
+    def set_bch(self, code):
+        """`code`: a `BchCode` whose bounded-distance decoder gives the outer-BCH counters of `run(..., bch_max_errors=t)`
+        from now on, or None for the genie ("at most bch_max_errors bit errors count as corrected").  ValueError (nothing
+        changed) unless the code's n is this simulator's k."""
+        h = None if code is None else code._h
+        if _capi.lib().ldpc_toolbox_sim_set_bch(self._h, h) != 0:
+            raise ValueError(_capi.last_error() or "cannot set the BCH code")
+
     def get(self, key):
         v = C.c_int64(0)
         if _capi.lib().ldpc_toolbox_sim_get(self._h, key.encode(), C.byref(v)) != 0:
@@ -391,6 +399,8 @@ class Simulator:
         else:
             rc = _capi.lib().ldpc_toolbox_sim_run(self._h, float(ebn0_db), int(seed), int(first_frame), int(frames),
                                                   int(max_iterations), out.ctypes.data)
+        if rc == -4:
+            raise ValueError(f"sim_run refused ({rc}): {_capi.last_error()}")
         if rc != 0:
             raise RuntimeError(f"sim_run failed ({rc}): {_capi.last_error()}")
         return out.astype(np.int64)
