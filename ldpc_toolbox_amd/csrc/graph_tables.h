@@ -136,7 +136,7 @@ inline RowRecordTables build_row_record_tables(const SparseMatrix::Csr &g, const
   return t;
 }
 
-// The variable-node kernel's record source (kernels_flooding.hip.h, from_records::vn_kernel): for every edge of the kept list, in
+// The variable-node kernel's record source (kernels_flooding.hip.h, vn_kernel's record form): for every edge of the kept list, in
 // the list's own order (keep_var / keep_ptr, cols[v] order inside a variable), row << 6 | slot of the edge inside its row --
 // free_rs's word, with free_rs's limits: a slot below 64 and a row index below kPeerSingle, else not ready.  Padded by
 // kTablePad words (the kernel fetches a variable's first indices as one block).

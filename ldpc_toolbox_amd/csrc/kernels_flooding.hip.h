@@ -92,80 +92,57 @@ __device__ __forceinline__ void buf_store(const RowBuf &b, uint32_t lane_off, ui
 
 // 16-bit flags (flooding records of rows of at most 12 edges: graph_tables.h, record_flag_bits): the flags leave the
 // record's rows for an array of their own, [M][tile] of uint16_t beside the magnitudes' [2M][tile] of T (rows 2c, 2c+1),
-// both tiled like every other array.  A lane's VEC half-words are one b64 / b32 / b16 buffer access.
+// both tiled like every other array.  Byte flags (rows of at most 7 edges: graph_tables.h, record_flag_bytes; the format:
+// record_flags8.h): the same array with one byte per row and codeword.  A lane's VEC flag words of type FW are one buffer
+// access of sizeof(FW) * VEC bytes: b64 / b32 / b16 / b8.
 constexpr int kArgShift16 = 12;  // flip bits at 0..11, argmin at 12..15
-template <int VEC, bool NT>
-__device__ __forceinline__ Pack<uint16_t, VEC> flags_load(const RowBuf &b, uint32_t lane_off, uint32_t row_off) {
-  static_assert(VEC == 1 || VEC == 2 || VEC == 4, "pack size");
-  if constexpr (VEC == 1)
-    return __builtin_bit_cast(Pack<uint16_t, VEC>, __builtin_amdgcn_raw_buffer_load_b16(b.r, lane_off, row_off, NT ? 2 : 0));
-  else if constexpr (VEC == 2)
-    return __builtin_bit_cast(Pack<uint16_t, VEC>, __builtin_amdgcn_raw_buffer_load_b32(b.r, lane_off, row_off, NT ? 2 : 0));
+static_assert(kArgShift16 == kRecArgShift16, "record_flags8.h encodes the register form of the 16-bit flags");
+template <typename FW, int VEC, bool NT>
+__device__ __forceinline__ Pack<FW, VEC> flags_load(const RowBuf &b, uint32_t lane_off, uint32_t row_off) {
+  constexpr int kBytes = sizeof(FW) * VEC;
+  static_assert(kBytes == 1 || kBytes == 2 || kBytes == 4 || kBytes == 8, "pack size");
+  if constexpr (kBytes == 1)
+    return __builtin_bit_cast(Pack<FW, VEC>, __builtin_amdgcn_raw_buffer_load_b8(b.r, lane_off, row_off, NT ? 2 : 0));
+  else if constexpr (kBytes == 2)
+    return __builtin_bit_cast(Pack<FW, VEC>, __builtin_amdgcn_raw_buffer_load_b16(b.r, lane_off, row_off, NT ? 2 : 0));
+  else if constexpr (kBytes == 4)
+    return __builtin_bit_cast(Pack<FW, VEC>, __builtin_amdgcn_raw_buffer_load_b32(b.r, lane_off, row_off, NT ? 2 : 0));
   else
-    return __builtin_bit_cast(Pack<uint16_t, VEC>, __builtin_amdgcn_raw_buffer_load_b64(b.r, lane_off, row_off, NT ? 2 : 0));
+    return __builtin_bit_cast(Pack<FW, VEC>, __builtin_amdgcn_raw_buffer_load_b64(b.r, lane_off, row_off, NT ? 2 : 0));
 }
-template <int VEC, bool NT>
-__device__ __forceinline__ void flags_store(const RowBuf &b, uint32_t lane_off, uint32_t row_off, const Pack<uint16_t, VEC> &x) {
+template <typename FW, int VEC, bool NT>
+__device__ __forceinline__ void flags_store(const RowBuf &b, uint32_t lane_off, uint32_t row_off, const Pack<FW, VEC> &x) {
+  constexpr int kBytes = sizeof(FW) * VEC;
   typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-  if constexpr (VEC == 1)
+  if constexpr (kBytes == 1)
+    __builtin_amdgcn_raw_buffer_store_b8(__builtin_bit_cast(uint8_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
+  else if constexpr (kBytes == 2)
     __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
-  else if constexpr (VEC == 2)
+  else if constexpr (kBytes == 4)
     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
   else
     __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2, x), b.r, lane_off, row_off, NT ? 2 : 0);
 }
 
-// Byte flags (rows of at most 7 edges: graph_tables.h, record_flag_bytes; the format: record_flags8.h): the same array with
-// one byte per row and codeword.  A lane's VEC bytes are one b32 / b16 / b8 buffer access.
-static_assert(kArgShift16 == kRecArgShift16, "record_flags8.h encodes the register form of the 16-bit flags");
-template <int VEC, bool NT>
-__device__ __forceinline__ Pack<uint8_t, VEC> flags8_load(const RowBuf &b, uint32_t lane_off, uint32_t row_off) {
-  static_assert(VEC == 1 || VEC == 2 || VEC == 4, "pack size");
-  if constexpr (VEC == 1)
-    return __builtin_bit_cast(Pack<uint8_t, VEC>, __builtin_amdgcn_raw_buffer_load_b8(b.r, lane_off, row_off, NT ? 2 : 0));
-  else if constexpr (VEC == 2)
-    return __builtin_bit_cast(Pack<uint8_t, VEC>, __builtin_amdgcn_raw_buffer_load_b16(b.r, lane_off, row_off, NT ? 2 : 0));
-  else
-    return __builtin_bit_cast(Pack<uint8_t, VEC>, __builtin_amdgcn_raw_buffer_load_b32(b.r, lane_off, row_off, NT ? 2 : 0));
-}
-template <int VEC, bool NT>
-__device__ __forceinline__ void flags8_store(const RowBuf &b, uint32_t lane_off, uint32_t row_off, const Pack<uint8_t, VEC> &x) {
-  if constexpr (VEC == 1)
-    __builtin_amdgcn_raw_buffer_store_b8(__builtin_bit_cast(uint8_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
-  else if constexpr (VEC == 2)
-    __builtin_amdgcn_raw_buffer_store_b16(__builtin_bit_cast(uint16_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
-  else
-    __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(uint32_t, x), b.r, lane_off, row_off, NT ? 2 : 0);
-}
-
 // Where a launch finds the records: one array of T (flags in the record's own rows), or with 16-bit flags the magnitudes
-// and the flags array.  Ref: the kernel argument; Buf: the wavefront's slice behind buffer descriptors.
-// F8 (with F16: the byte form stores the 16-bit family's records): RecPair8, the flags as bytes.
+// and the flags array, RecPair.  Ref: the kernel argument; Buf: the wavefront's slice behind buffer descriptors.
+// F8 (with F16: the byte form stores the 16-bit family's records): the same pair, the flags as bytes.
 template <typename T, bool F16, bool F8 = false>
 struct RecRef {
   static_assert(!F8, "byte flags: a form of the 16-bit family");
   typedef const T *__restrict__ in;
   typedef T *__restrict__ out;
 };
-template <typename T>
+template <typename T, typename FW>
 struct RecPair {
+  static_assert(std::is_same_v<FW, uint16_t> || std::is_same_v<FW, uint8_t>, "flags word: uint16_t or uint8_t");
   T *mag;
-  uint16_t *flags;
+  FW *flags;
 };
-template <typename T>
-struct RecPair8 {
-  T *mag;
-  uint8_t *flags;
-};
-template <typename T>
-struct RecRef<T, true, false> {
-  typedef RecPair<const T> in;
-  typedef RecPair<T> out;
-};
-template <typename T>
-struct RecRef<T, true, true> {
-  typedef RecPair8<const T> in;
-  typedef RecPair8<T> out;
+template <typename T, bool F8>
+struct RecRef<T, true, F8> {
+  typedef RecPair<const T, std::conditional_t<F8, uint8_t, uint16_t>> in;
+  typedef RecPair<T, std::conditional_t<F8, uint8_t, uint16_t>> out;
 };
 // the type of a record's stored flags word: the decoder's own word, uint16_t (F16) or uint8_t (F16 and F8)
 template <typename T, bool F16, bool F8 = false>
@@ -184,22 +161,13 @@ __device__ __forceinline__ RecBuf<false> rec_buf(const T *rec, uint32_t b0, uint
   return RecBuf<false>{row_buf(rec + tile_base(b0, n_rows * RECW, sc),
                                uint64_t(n_rows) * RECW * row_bytes - in_tile_of(b0, sc) * uint32_t(sizeof(T)))};
 }
-template <typename T, int RECW, typename TT>
-__device__ __forceinline__ RecBuf<true> rec_buf(const RecPair<TT> &rec, uint32_t b0, uint32_t n_rows, const Sched &sc,
+template <typename T, int RECW, typename TT, typename FW>
+__device__ __forceinline__ RecBuf<true> rec_buf(const RecPair<TT, FW> &rec, uint32_t b0, uint32_t n_rows, const Sched &sc,
                                                 uint32_t row_bytes) {
-  static_assert(RECW == 3, "16-bit flags: the three-word family");
+  static_assert(RECW == 3, "16-bit and byte flags: the three-word family");
   const uint32_t in_tile = in_tile_of(b0, sc);
   return RecBuf<true>{row_buf(rec.mag + tile_base(b0, n_rows * 2, sc), uint64_t(n_rows) * 2 * row_bytes - in_tile * uint32_t(sizeof(T))),
-                      row_buf(rec.flags + tile_base(b0, n_rows, sc), (uint64_t(n_rows) * sc.tile - in_tile) * sizeof(uint16_t))};
-}
-
-template <typename T, int RECW, typename TT>
-__device__ __forceinline__ RecBuf<true> rec_buf(const RecPair8<TT> &rec, uint32_t b0, uint32_t n_rows, const Sched &sc,
-                                                uint32_t row_bytes) {
-  static_assert(RECW == 3, "byte flags: the three-word family");
-  const uint32_t in_tile = in_tile_of(b0, sc);
-  return RecBuf<true>{row_buf(rec.mag + tile_base(b0, n_rows * 2, sc), uint64_t(n_rows) * 2 * row_bytes - in_tile * uint32_t(sizeof(T))),
-                      row_buf(rec.flags + tile_base(b0, n_rows, sc), uint64_t(n_rows) * sc.tile - in_tile)};
+                      row_buf(rec.flags + tile_base(b0, n_rows, sc), (uint64_t(n_rows) * sc.tile - in_tile) * sizeof(FW))};
 }
 
 // FW, the type of the stored flags word: the decoder's own word (this form: the flags are the record's third row, and a
@@ -263,13 +231,13 @@ struct RowRec<T, VEC, 3, uint16_t> {
   __device__ __forceinline__ void load(const RecBuf<true> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) {
     min1 = buf_load<T, VEC, false>(b.b, lane_off, row_off);
     min2 = buf_load<T, VEC, false>(b.b, lane_off, row_off + row_bytes);
-    flip = flags_load<VEC, false>(b.f, lane_off / uint32_t(sizeof(T) / sizeof(uint16_t)), row_off / uint32_t(sizeof(T)));
+    flip = flags_load<uint16_t, VEC, false>(b.f, lane_off / uint32_t(sizeof(T) / sizeof(uint16_t)), row_off / uint32_t(sizeof(T)));
   }
   template <bool NT>
   __device__ __forceinline__ void store(const RecBuf<true> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) const {
     buf_store<T, VEC, NT>(b.b, lane_off, row_off, min1);
     buf_store<T, VEC, NT>(b.b, lane_off, row_off + row_bytes, min2);
-    flags_store<VEC, NT>(b.f, lane_off / uint32_t(sizeof(T) / sizeof(uint16_t)), row_off / uint32_t(sizeof(T)), flip);
+    flags_store<uint16_t, VEC, NT>(b.f, lane_off / uint32_t(sizeof(T) / sizeof(uint16_t)), row_off / uint32_t(sizeof(T)), flip);
   }
   __device__ __forceinline__ T value(uint32_t slot, int k) const {
     const uint32_t f = flip.v[k];
@@ -280,7 +248,7 @@ struct RowRec<T, VEC, 3, uint16_t> {
 };
 // The same records with their flags as bytes (record_flags8.h).  New: a record built in registers (the 16-bit form's
 // members), encoded at `store`.  A loaded record has two forms.  RowRec<T, VEC, 3, uint8_t>, the form of the variable-node
-// kernels (from_records::vn_kernel, vn_free_rec_kernel, vn_kernel's event block), holds what `load` read, as it is in memory,
+// kernels (vn_kernel: its record form and its event block; vn_free_rec_kernel), holds what `load` read, as it is in memory,
 // and `value` decodes it into the 16-bit form's registers on the spot: they take one value, or two, of each record they
 // load.  RowRec8Once below is the check-node kernel's, which takes up to eight values of a record and decodes it once.
 // (Until profiles/cn_flags8_decode.txt the check-node kernel used the first form too: 4804 vector instructions against the
@@ -302,7 +270,7 @@ struct RowRec8New : RowRec<T, VEC, 3, uint16_t> {
     }
     buf_store<T, VEC, NT>(b.b, lane_off, row_off, m1);
     buf_store<T, VEC, NT>(b.b, lane_off, row_off + row_bytes, m2);
-    flags8_store<VEC, NT>(b.f, lane_off / uint32_t(sizeof(T)), row_off / uint32_t(2 * sizeof(T)), fl);
+    flags_store<uint8_t, VEC, NT>(b.f, lane_off / uint32_t(sizeof(T)), row_off / uint32_t(2 * sizeof(T)), fl);
   }
 };
 template <typename T, int VEC>
@@ -316,7 +284,7 @@ struct RowRec<T, VEC, 3, uint8_t> {
   __device__ __forceinline__ void load(const RecBuf<true> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) {
     min1 = buf_load<T, VEC, false>(b.b, lane_off, row_off);
     min2 = buf_load<T, VEC, false>(b.b, lane_off, row_off + row_bytes);
-    fl = flags8_load<VEC, false>(b.f, lane_off / uint32_t(sizeof(T)), row_off / uint32_t(2 * sizeof(T)));
+    fl = flags_load<uint8_t, VEC, false>(b.f, lane_off / uint32_t(sizeof(T)), row_off / uint32_t(2 * sizeof(T)));
   }
   __device__ __forceinline__ T value(uint32_t slot, int k) const {
     const RecFlags8Loaded<W> r = record_flags8_decode<W>(__builtin_bit_cast(W, min1.v[k]), __builtin_bit_cast(W, min2.v[k]), fl.v[k]);
@@ -341,7 +309,7 @@ struct RowRec8Once {
   __device__ __forceinline__ void load(const RecBuf<true> &b, uint32_t lane_off, uint32_t row_off, uint32_t row_bytes) {
     min1 = buf_load<T, VEC, false>(b.b, lane_off, row_off);
     min2 = buf_load<T, VEC, false>(b.b, lane_off, row_off + row_bytes);
-    const Pack<uint8_t, VEC> bytes = flags8_load<VEC, false>(b.f, lane_off / uint32_t(sizeof(T)), row_off / uint32_t(2 * sizeof(T)));
+    const Pack<uint8_t, VEC> bytes = flags_load<uint8_t, VEC, false>(b.f, lane_off / uint32_t(sizeof(T)), row_off / uint32_t(2 * sizeof(T)));
     fl = 0;
 #pragma unroll
     for (int k = 0; k < VEC; k++) fl |= uint32_t(bytes.v[k]) << (8 * k);
@@ -400,6 +368,7 @@ __global__ __launch_bounds__(256) void vn_free_rec_kernel(Graph g, Sched sc, Sta
     any_live = any_live || live[k];
   }
   if (__builtin_amdgcn_ballot_w64(any_live) == 0) return;
+  // (the L-free rebuild loop: vn_kernel's event block has the other copy)
   for (uint32_t i = i0; i < g.n_list; i += sc.waves_per_chunk) {
     const uint32_t v = free_var[i], a = free_rs[2 * i], b = free_rs[2 * i + 1];
     const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(v) * G);
@@ -432,38 +401,55 @@ __global__ __launch_bounds__(256) void vn_free_rec_kernel(Graph g, Sched sc, Sta
 // waves instead of a small grid of its own: one launch and one dispatch gap fewer per iteration (4.4 + 5.7 us of 2050), and
 // the one pass that does find work runs at the full grid's width.  Which codewords are "newly converged" must not depend on
 // what the bookkeeping wave of the slice has already written in this same launch: see `fresh` below.
-template <typename T>
+template <typename RecIn>
 struct VnEvent {
   const uint32_t *free_var, *free_rs;  // the L-free variables and, per variable, its two (row << 6 | slot) words
-  const T *rec;                        // records of the iteration being latched
+  RecIn rec;                           // records of the iteration being latched
   uint32_t n_free;
 };
-template <typename T>
-struct VnEvent16 {  // the same with 16-bit flags (EVF16)
-  const uint32_t *free_var, *free_rs;
-  RecPair<const T> rec;
-  uint32_t n_free;
-};
-template <typename T>
-struct VnEvent8 {  // ... stored with byte flags (EVF16 and EVF8)
-  const uint32_t *free_var, *free_rs;
-  RecPair8<const T> rec;
-  uint32_t n_free;
-};
+// (EVF16, EVF8: those records' flags are 16-bit words in an array of their own; stored as bytes)
 template <typename T, bool EVF16, bool EVF8 = false>
-using VnEventOf = std::conditional_t<EVF16, std::conditional_t<EVF8, VnEvent8<T>, VnEvent16<T>>, VnEvent<T>>;
+using VnEventOf = VnEvent<typename RecRef<T, EVF16, EVF8>::in>;
 __device__ __forceinline__ bool has_records(const void *rec) { return rec != nullptr; }
-template <typename T>
-__device__ __forceinline__ bool has_records(const RecPair<T> &rec) { return rec.mag != nullptr; }
-template <typename T>
-__device__ __forceinline__ bool has_records(const RecPair8<T> &rec) { return rec.mag != nullptr; }
-// (from_records::vn_kernel below repeats this kernel's prologue -- the idle test, the bookkeeping wave, the EVW block, the
-// slice_state latch -- line for line: a change to any of them is made in both)
-template <typename T, int VEC, int U, bool NT, bool LIST, int EVW = 0, bool EVF16 = false, bool EVF8 = false>
+template <typename T, typename FW>
+__device__ __forceinline__ bool has_records(const RecPair<T, FW> &rec) { return rec.mag != nullptr; }
+// What the kernel sums, SRC... src: one kernel argument or two, where they have always been.  The per-edge messages the
+// check-node launch stored -- `const T *__restrict__ msg`, [E][tile], gathered through col_edge ...
+template <typename... SRC>
+struct VnSource;
+template <typename M>
+struct VnSource<M> {
+  M msg;
+};
+// ... or, REC, the ROW RECORDS the check-node launch of THIS iteration wrote -- `RecRef<T, true, EVF8>::in rec, const uint32_t
+// *__restrict__ keep_rs`: the list variant with the per-edge message array taken out of the iteration.  The message on a kept
+// edge is already in the record its row wrote in the same iteration -- Rec::value(slot, k) is the very pack
+// cn_minsum_rec_kernel's `send` stores -- so the kernel gathers, per edge, the record of the edge's row (keep_rs: row << 6 |
+// slot per edge of the kept list, graph_tables.h build_keep_rs) and the check-node launch stores no per-edge messages at all
+// (its SEND = false form).  Same sum, same order.  The 16-bit-flags record form only (rows of at most 12 edges; EVF8: stored
+// with byte flags, rows of at most 7 edges, rec and ev.rec alike); a record is 2.5 words of f32 where a message was one, but a
+// row's record is wanted by every kept edge of the row and is fetched from HBM once per tile.
+template <typename R, typename K>
+struct VnSource<R, K> {
+  R rec;
+  K keep_rs;
+};
+// (Arguments of their own and not one struct: a pointer inside a struct is not `noalias` to the compiler, and a struct's
+// members are loaded apart from the arguments beside them -- either gives every instantiation other instructions,
+// profiles/vn_kernel_merge.txt.)
+//   U     messages / records in flight per lane; a variable of more edges takes further rounds
+//   NT    nontemporal loads of what no other kernel reads: the messages; REC: the channel rows
+//   LIST  only the variables of Graph::list_* (REC: always)
+// Both forms are this one kernel, and in both it IS the iteration's variable-node launch: whoever accounts for the launches
+// of an iteration by kernel name (bench.py's counter passes sum "vn_kernel") finds it.
+template <typename T, int VEC, int U, bool NT, bool LIST, int EVW = 0, bool EVF16 = false, bool EVF8 = false, typename... SRC>
 __global__ __launch_bounds__(256) void vn_kernel(
-    Graph g, Sched sc, State st, const T *__restrict__ chan, const T *__restrict__ msg,
+    Graph g, Sched sc, State st, const T *__restrict__ chan, SRC... src,
     T *__restrict__ post, const uint32_t *__restrict__ unsat_in, uint32_t *__restrict__ unsat_clear,
     int32_t latch_iteration, VnEventOf<T, EVF16, EVF8> ev = {}) {
+  constexpr bool REC = sizeof...(SRC) == 2;
+  const VnSource<const SRC &...> from{src...};  // (a view: references)
+  static_assert(!REC || (LIST && EVF16 && (EVW == 0 || EVW == 3)), "from records: the kept list, the 16-bit family's records");
   uint32_t *__restrict__ n_active = st.n_active;
   // A finished group's launches return at once.  With EVW the count can also reach zero INSIDE this launch -- the
   // bookkeeping waves below subtract the codewords they latch -- and a wave that starts after the last subtraction must
@@ -472,7 +458,11 @@ __global__ __launch_bounds__(256) void vn_kernel(
   const bool idle = *n_active == 0;
   if (EVW == 0 && idle) return;
   const TablePtr col_ptr = table_ptr(LIST ? g.list_ptr : g.col_ptr);
-  const TablePtr col_edge = table_ptr(LIST ? g.list_edge : g.col_edge);
+  // (col_edge and msg here, row_bytes and lane_off below: what only one form's main loop needs belongs in that form's branch.
+  // These four stay where each form has always computed them -- moved, every instantiation comes out with the same
+  // instructions in another order and other registers, and they are to stay identical: tools/kernel_digest.py.)
+  TablePtr col_edge = nullptr;
+  if constexpr (!REC) col_edge = table_ptr(LIST ? g.list_edge : g.col_edge);
   uint32_t *__restrict__ done = st.done;
   int32_t *__restrict__ iters = st.iters;
   const uint32_t n_cols = LIST ? g.n_list : g.n_cols;  // items to process
@@ -491,7 +481,13 @@ __global__ __launch_bounds__(256) void vn_kernel(
   const size_t G = tile;
   chan += tile_base(b0, g.n_cols, sc) + lane * VEC;
   post += tile_base(b0, g.n_cols, sc) + lane * VEC;
-  msg += tile_base(b0, g.n_edges, sc) + lane * VEC;
+  const T *__restrict__ msg = nullptr;
+  if constexpr (!REC) msg = from.msg + tile_base(b0, g.n_edges, sc) + lane * VEC;
+  uint32_t row_bytes = 0, lane_off = 0;
+  if constexpr (REC) {
+    row_bytes = tile * uint32_t(sizeof(T));
+    lane_off = lane * uint32_t(VEC * sizeof(T));
+  }
   bool skip[VEC];
   bool any_live = false, any_new = false;
 #pragma unroll
@@ -538,8 +534,12 @@ __global__ __launch_bounds__(256) void vn_kernel(
       }
       if (__builtin_amdgcn_ballot_w64(any_fresh) != 0) {
         const TablePtr free_var = table_ptr(ev.free_var), free_rs = table_ptr(ev.free_rs);
-        const uint32_t row_bytes = tile * uint32_t(sizeof(T)), lane_off = lane * uint32_t(VEC * sizeof(T));
+        if constexpr (!REC) {
+          row_bytes = tile * uint32_t(sizeof(T));
+          lane_off = lane * uint32_t(VEC * sizeof(T));
+        }
         const RecBuf<EVF16> b_rec = rec_buf<T, EVW>(ev.rec, b0, g.n_rows, sc, row_bytes);
+        // (the L-free rebuild loop: vn_free_rec_kernel has the other copy)
         for (uint32_t i = v_first; i < ev.n_free; i += waves_per_chunk) {
           const uint32_t fv = free_var[i], a = free_rs[2 * i], b = free_rs[2 * i + 1];
           const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(fv) * G);
@@ -567,263 +567,152 @@ __global__ __launch_bounds__(256) void vn_kernel(
 #pragma unroll
   for (int k = 0; k < VEC; k++) all = all && !skip[k];
 
-  const uint32_t last_slot = g.n_edges ? g.n_edges - 1 : 0;
-  uint32_t v = v_first, s0 = 0, s1 = 0, ed[U], var = v_first;
-  if (v < n_cols) {
-    s0 = col_ptr[v];
-    s1 = col_ptr[v + 1];
-    if (LIST) var = table_ptr(g.list_var)[v];
-  }
+  if constexpr (!REC) {  // the sum of the per-edge messages
+    const uint32_t last_slot = g.n_edges ? g.n_edges - 1 : 0;
+    uint32_t v = v_first, s0 = 0, s1 = 0, ed[U], var = v_first;
+    if (v < n_cols) {
+      s0 = col_ptr[v];
+      s1 = col_ptr[v + 1];
+      if (LIST) var = table_ptr(g.list_var)[v];
+    }
 #pragma unroll
-  for (int u = 0; u < U; u++) ed[u] = col_edge[min(s0 + u, last_slot)];
+    for (int u = 0; u < U; u++) ed[u] = col_edge[min(s0 + u, last_slot)];
 
-  while (v < n_cols) {
-    T sum[VEC];
+    while (v < n_cols) {
+      T sum[VEC];
 #pragma unroll
-    for (int k = 0; k < VEC; k++) sum[k] = -T(0.0);
-    // (a nontemporal load here -- nobody else reads these channel rows in the list variant -- takes 7 us off this kernel
-    // and puts 14 us on the check-node kernel that follows: profiles/r04_vn_kernel.txt)
-    const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(var) * G);
-    const uint32_t vn = v + waves_per_chunk;
-    uint32_t ns0 = 0, ns1 = 0, nvar = vn;
-    if (vn < n_cols) {
-      ns0 = col_ptr[vn];
-      ns1 = col_ptr[vn + 1];
-      if (LIST) nvar = table_ptr(g.list_var)[vn];
-    }
-    uint32_t ned[U];
-    for (uint32_t j0 = s0; j0 < s1; j0 += U) {
-      Pack<T, VEC> mv[U];
+      for (int k = 0; k < VEC; k++) sum[k] = -T(0.0);
+      // (a nontemporal load here -- nobody else reads these channel rows in the list variant -- takes 7 us off this kernel
+      // and puts 14 us on the check-node kernel that follows: profiles/r04_vn_kernel.txt)
+      const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(var) * G);
+      const uint32_t vn = v + waves_per_chunk;
+      uint32_t ns0 = 0, ns1 = 0, nvar = vn;
+      if (vn < n_cols) {
+        ns0 = col_ptr[vn];
+        ns1 = col_ptr[vn + 1];
+        if (LIST) nvar = table_ptr(g.list_var)[vn];
+      }
+      uint32_t ned[U];
+      for (uint32_t j0 = s0; j0 < s1; j0 += U) {
+        Pack<T, VEC> mv[U];
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        if (j0 + u < s1) {  // wave-uniform
-          const uint32_t e = (j0 == s0) ? ed[u] : col_edge[j0 + u];
-          mv[u] = load_msg<T, VEC, NT>(msg + size_t(e) * G);
+        for (int u = 0; u < U; u++) {
+          if (j0 + u < s1) {  // wave-uniform
+            const uint32_t e = (j0 == s0) ? ed[u] : col_edge[j0 + u];
+            mv[u] = load_msg<T, VEC, NT>(msg + size_t(e) * G);
+          }
         }
-      }
-      if (j0 == s0) {
+        if (j0 == s0) {
 #pragma unroll
-        for (int u = 0; u < U; u++) ned[u] = col_edge[min(ns0 + u, last_slot)];
-      }
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        if (j0 + u < s1) {
-#pragma unroll
-          for (int k = 0; k < VEC; k++) sum[k] = sum[k] + mv[u].v[k];
+          for (int u = 0; u < U; u++) ned[u] = col_edge[min(ns0 + u, last_slot)];
         }
-      }
-    }
-    if (s0 == s1) {
 #pragma unroll
-      for (int u = 0; u < U; u++) ned[u] = col_edge[min(ns0 + u, last_slot)];
-    }
-    Pack<T, VEC> o;
+        for (int u = 0; u < U; u++) {
+          if (j0 + u < s1) {
 #pragma unroll
-    for (int k = 0; k < VEC; k++) o.v[k] = ch.v[k] + sum[k];
-    T *dst = post + size_t(var) * G;
-    if (all) {
-      store_pack<T, VEC>(dst, o);
-    } else {
-      // (reading the frozen codewords' values back and storing whole packs instead was measured in round 5: no gain at
-      // +2 dB, 0.5 % on the fixed-work pass for the extra branch -- profiles/r05_p2_timeline.txt)
-#pragma unroll
-      for (int k = 0; k < VEC; k++)
-        if (!skip[k]) dst[k] = o.v[k];
-    }
-    v = vn;
-    var = nvar;
-    s0 = ns0;
-    s1 = ns1;
-#pragma unroll
-    for (int u = 0; u < U; u++) ed[u] = ned[u];
-  }
-}
-
-// ---------------------------------------------------------------------------------------
-// Flooding, variable nodes from ROW RECORDS: vn_kernel's list variant with the per-edge message array taken out of the
-// iteration.  The message on a kept edge is already in the record its row wrote in the same iteration --
-// Rec::value(slot, k) is the very pack cn_minsum_rec_kernel's `send` stores -- so this kernel gathers, per edge, the record
-// of the edge's row (keep_rs: row << 6 | slot per edge of the kept list, graph_tables.h build_keep_rs) and the check-node
-// launch stores no per-edge messages at all (its SEND = false form).  Same sum, same order: cols[v] order from -0.0, then
-// post = chan + sum.  The 16-bit-flags record form only (rows of at most 12 edges); a record is 2.5 words of f32 where a
-// message was one, but a row's record is wanted by every kept edge of the row and is fetched from HBM once per tile.
-//   rec     the records the check-node launch of THIS iteration wrote
-//   EV      the EVW block of vn_kernel (the L-free posteriors of a slice's first convergences, from ev.rec: the records of
-//           the iteration being latched, the other buffer), word for word; the bookkeeping wave likewise
-//   U       records in flight per lane; a variable of more edges takes further rounds
-//   NTCH    the channel rows (read by no other kernel in this form) through nontemporal loads
-//   F8      the records' flags are stored as bytes (rows of at most 7 edges), rec and ev.rec alike
-// Everything up to the main loop -- the idle test, the bookkeeping wave, the event block with its `fresh` rule, the
-// slice_state latch -- is vn_kernel's, line for line; the reasons are written there, once.  (Kept as a second copy and not as
-// shared helpers so that every existing instantiation of vn_kernel stays instruction-identical by construction.)
-// The kernel is from_records::vn_kernel: it IS the iteration's variable-node launch, and whoever accounts for the launches
-// of an iteration by kernel name (bench.py's counter passes sum "vn_kernel") finds it under that name.
-// ---------------------------------------------------------------------------------------
-namespace from_records {
-template <typename T, int VEC, int U, bool NTCH, bool EV, bool F8 = false>
-__global__ __launch_bounds__(256) void vn_kernel(
-    Graph g, Sched sc, State st, const T *__restrict__ chan, typename RecRef<T, true, F8>::in rec,
-    const uint32_t *__restrict__ keep_rs_, T *__restrict__ post, const uint32_t *__restrict__ unsat_in,
-    uint32_t *__restrict__ unsat_clear, int32_t latch_iteration, VnEventOf<T, true, F8> ev = {}) {
-  typedef RowRec<T, VEC, 3, RecFlagWord<T, true, F8>> Rec;
-  uint32_t *__restrict__ n_active = st.n_active;
-  const bool idle = *n_active == 0;  // (see vn_kernel: with EV a wave may still owe its share of the rebuild)
-  if (!EV && idle) return;
-  const TablePtr col_ptr = table_ptr(g.list_ptr), keep_rs = table_ptr(keep_rs_);
-  uint32_t *__restrict__ done = st.done;
-  int32_t *__restrict__ iters = st.iters;
-  const uint32_t n_cols = g.n_list;
-  const uint32_t waves_per_chunk = sc.waves_per_chunk, tile = sc.tile;
-  const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = uniform((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
-  uint32_t chunk, v_first;
-  wave_slot(sc, wave, &chunk, &v_first);
-  if (chunk >= sc.nchunks) return;
-  const uint32_t b0 = chunk * (64 * VEC);
-  if (b0 >= *st.n_slots) return;
-  if constexpr (EV) {
-    if (idle && (!has_records(ev.rec) || unsat_in == nullptr || st.slice_state == nullptr || st.slice_state[chunk] == 2u)) return;
-  }
-  const size_t off = size_t(b0) + lane * VEC;
-  const size_t G = tile;
-  chan += tile_base(b0, g.n_cols, sc) + lane * VEC;
-  post += tile_base(b0, g.n_cols, sc) + lane * VEC;
-  const uint32_t row_bytes = tile * uint32_t(sizeof(T)), lane_off = lane * uint32_t(VEC * sizeof(T));
-  bool skip[VEC];
-  bool any_live = false, any_new = false;
-#pragma unroll
-  for (int k = 0; k < VEC; k++) {
-    const bool was_done = done[off + k] != 0;
-    const bool converged = !was_done && unsat_in != nullptr && unsat_in[off + k] == 0;
-    int32_t own_iterations = latch_iteration;
-    bool expired = false;
-    if (st.it0 != nullptr) {
-      own_iterations = latch_iteration - static_cast<int32_t>(st.it0[off + k]);
-      expired = !was_done && !converged && own_iterations >= static_cast<int32_t>(st.max_it);
-    }
-    skip[k] = was_done || converged || expired;
-    any_live = any_live || !skip[k];
-    if (v_first == 0 && !idle) {  // the slice's bookkeeping wave
-      if (converged || expired) {
-        done[off + k] = 1u;
-        iters[off + k] = converged ? own_iterations : -1;
-        atomicSub(n_active, 1u);
-        any_new = true;
-      }
-      unsat_clear[off + k] = 0u;
-    }
-  }
-  if constexpr (EV) {
-    if (has_records(ev.rec) && unsat_in != nullptr && st.slice_state != nullptr && st.slice_state[chunk] != 2u) {
-      bool fresh[VEC];
-      bool any_fresh = false;
-#pragma unroll
-      for (int k = 0; k < VEC; k++) {
-        const int32_t was = iters[off + k];
-        fresh[k] = unsat_in[off + k] == 0 && st.slot_cw[off + k] != kNoCodeword && (was < 0 || was == latch_iteration);
-        any_fresh = any_fresh || fresh[k];
-      }
-      if (__builtin_amdgcn_ballot_w64(any_fresh) != 0) {
-        const TablePtr free_var = table_ptr(ev.free_var), free_rs = table_ptr(ev.free_rs);
-        const RecBuf<true> b_ev = rec_buf<T, 3>(ev.rec, b0, g.n_rows, sc, row_bytes);
-        for (uint32_t i = v_first; i < ev.n_free; i += waves_per_chunk) {
-          const uint32_t fv = free_var[i], a = free_rs[2 * i], b = free_rs[2 * i + 1];
-          const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(fv) * G);
-          Rec ra, rb;
-          if (a != kAuxNone) ra.load(b_ev, lane_off, (a >> 6) * Rec::kRows * row_bytes, row_bytes);
-          if (b != kAuxNone) rb.load(b_ev, lane_off, (b >> 6) * Rec::kRows * row_bytes, row_bytes);
-#pragma unroll
-          for (int k = 0; k < VEC; k++) {
-            T sum = -T(0.0);  // arithmetic.rs:146: the slot-ordered sum, from Rust's float Sum identity
-            if (a != kAuxNone) sum = sum + ra.value(a & 63u, k);
-            if (b != kAuxNone) sum = sum + rb.value(b & 63u, k);
-            if (fresh[k]) post[size_t(fv) * G + k] = ch.v[k] + sum;
+            for (int k = 0; k < VEC; k++) sum[k] = sum[k] + mv[u].v[k];
           }
         }
       }
+      if (s0 == s1) {
+#pragma unroll
+        for (int u = 0; u < U; u++) ned[u] = col_edge[min(ns0 + u, last_slot)];
+      }
+      Pack<T, VEC> o;
+#pragma unroll
+      for (int k = 0; k < VEC; k++) o.v[k] = ch.v[k] + sum[k];
+      T *dst = post + size_t(var) * G;
+      if (all) {
+        store_pack<T, VEC>(dst, o);
+      } else {
+        // (reading the frozen codewords' values back and storing whole packs instead was measured in round 5: no gain at
+        // +2 dB, 0.5 % on the fixed-work pass for the extra branch -- profiles/r05_p2_timeline.txt)
+#pragma unroll
+        for (int k = 0; k < VEC; k++)
+          if (!skip[k]) dst[k] = o.v[k];
+      }
+      v = vn;
+      var = nvar;
+      s0 = ns0;
+      s1 = ns1;
+#pragma unroll
+      for (int u = 0; u < U; u++) ed[u] = ned[u];
     }
-  }
-  if (idle) return;
-  if (v_first == 0 && st.slice_state != nullptr && __builtin_amdgcn_ballot_w64(any_new) != 0 && lane == 0 &&
-      st.slice_state[chunk] == 0)
-    st.slice_state[chunk] = 1;  // the first convergences of this slice: see State::slice_state
-  if (__builtin_amdgcn_ballot_w64(any_live) == 0) return;
-  bool all = true;
-#pragma unroll
-  for (int k = 0; k < VEC; k++) all = all && !skip[k];
-
-  const RecBuf<true> b_rec = rec_buf<T, 3>(rec, b0, g.n_rows, sc, row_bytes);
-  const uint32_t rec_bytes = Rec::kRows * row_bytes;
-  // (keep_rs is padded by kTablePad words: the block fetch of a variable's first U indices stays in bounds)
-  uint32_t v = v_first, s0 = 0, s1 = 0, rs[U], var = v_first;
-  if (v < n_cols) {
-    s0 = col_ptr[v];
-    s1 = col_ptr[v + 1];
-    var = table_ptr(g.list_var)[v];
-  }
-#pragma unroll
-  for (int u = 0; u < U; u++) rs[u] = keep_rs[s0 + u];
-
-  while (v < n_cols) {
-    T sum[VEC];
-#pragma unroll
-    for (int k = 0; k < VEC; k++) sum[k] = -T(0.0);
-    const Pack<T, VEC> ch = load_msg<T, VEC, NTCH>(chan + size_t(var) * G);
-    const uint32_t vn = v + waves_per_chunk;
-    uint32_t ns0 = 0, ns1 = 0, nvar = vn;
-    if (vn < n_cols) {
-      ns0 = col_ptr[vn];
-      ns1 = col_ptr[vn + 1];
-      nvar = table_ptr(g.list_var)[vn];
+  } else {  // the same sum, each message taken out of its row's record
+    typedef RowRec<T, VEC, 3, RecFlagWord<T, true, EVF8>> Rec;
+    const TablePtr keep_rs = table_ptr(from.keep_rs);
+    const RecBuf<true> b_rec = rec_buf<T, 3>(from.rec, b0, g.n_rows, sc, row_bytes);
+    const uint32_t rec_bytes = Rec::kRows * row_bytes;
+    // (keep_rs is padded by kTablePad words: the block fetch of a variable's first U indices stays in bounds)
+    uint32_t v = v_first, s0 = 0, s1 = 0, rs[U], var = v_first;
+    if (v < n_cols) {
+      s0 = col_ptr[v];
+      s1 = col_ptr[v + 1];
+      var = table_ptr(g.list_var)[v];
     }
-    uint32_t nrs[U];
-    for (uint32_t j0 = s0; j0 < s1; j0 += U) {
-      Rec rv[U];
-      uint32_t w[U];
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        w[u] = 0;
-        if (j0 + u < s1) {  // wave-uniform
-          w[u] = (j0 == s0) ? rs[u] : keep_rs[j0 + u];
-          rv[u].load(b_rec, lane_off, (w[u] >> 6) * rec_bytes, row_bytes);
+    for (int u = 0; u < U; u++) rs[u] = keep_rs[s0 + u];
+
+    while (v < n_cols) {
+      T sum[VEC];
+#pragma unroll
+      for (int k = 0; k < VEC; k++) sum[k] = -T(0.0);
+      const Pack<T, VEC> ch = load_msg<T, VEC, NT>(chan + size_t(var) * G);
+      const uint32_t vn = v + waves_per_chunk;
+      uint32_t ns0 = 0, ns1 = 0, nvar = vn;
+      if (vn < n_cols) {
+        ns0 = col_ptr[vn];
+        ns1 = col_ptr[vn + 1];
+        nvar = table_ptr(g.list_var)[vn];
+      }
+      uint32_t nrs[U];
+      for (uint32_t j0 = s0; j0 < s1; j0 += U) {
+        Rec rv[U];
+        uint32_t w[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          w[u] = 0;
+          if (j0 + u < s1) {  // wave-uniform
+            w[u] = (j0 == s0) ? rs[u] : keep_rs[j0 + u];
+            rv[u].load(b_rec, lane_off, (w[u] >> 6) * rec_bytes, row_bytes);
+          }
+        }
+        if (j0 == s0) {
+#pragma unroll
+          for (int u = 0; u < U; u++) nrs[u] = keep_rs[ns0 + u];
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+          if (j0 + u < s1) {
+#pragma unroll
+            for (int k = 0; k < VEC; k++) sum[k] = sum[k] + rv[u].value(w[u] & 63u, k);
+          }
         }
       }
-      if (j0 == s0) {
+      if (s0 == s1) {
 #pragma unroll
         for (int u = 0; u < U; u++) nrs[u] = keep_rs[ns0 + u];
       }
+      Pack<T, VEC> o;
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        if (j0 + u < s1) {
+      for (int k = 0; k < VEC; k++) o.v[k] = ch.v[k] + sum[k];
+      T *dst = post + size_t(var) * G;
+      if (all) {
+        store_pack<T, VEC>(dst, o);
+      } else {
 #pragma unroll
-          for (int k = 0; k < VEC; k++) sum[k] = sum[k] + rv[u].value(w[u] & 63u, k);
-        }
+        for (int k = 0; k < VEC; k++)
+          if (!skip[k]) dst[k] = o.v[k];
       }
+      v = vn;
+      var = nvar;
+      s0 = ns0;
+      s1 = ns1;
+#pragma unroll
+      for (int u = 0; u < U; u++) rs[u] = nrs[u];
     }
-    if (s0 == s1) {
-#pragma unroll
-      for (int u = 0; u < U; u++) nrs[u] = keep_rs[ns0 + u];
-    }
-    Pack<T, VEC> o;
-#pragma unroll
-    for (int k = 0; k < VEC; k++) o.v[k] = ch.v[k] + sum[k];
-    T *dst = post + size_t(var) * G;
-    if (all) {
-      store_pack<T, VEC>(dst, o);
-    } else {
-#pragma unroll
-      for (int k = 0; k < VEC; k++)
-        if (!skip[k]) dst[k] = o.v[k];
-    }
-    v = vn;
-    var = nvar;
-    s0 = ns0;
-    s1 = ns1;
-#pragma unroll
-    for (int u = 0; u < U; u++) rs[u] = nrs[u];
   }
 }
-}  // namespace from_records
 // ---------------------------------------------------------------------------------------
 // The check-node kernels min-sum can take: cn_minsum (streaming), cn_minsum_lfree, cn_minsum_rec (row records), cn_staged
 // (LDS-staged, every rule).  Each ends in `typename... MC` / `MC... mc` (kernels_common.hip.h, MinsumCorr): with the pack
@@ -1150,7 +1039,7 @@ __global__ __launch_bounds__(256) void cn_minsum_lfree_kernel(
 // short-row case 2 % in registers and scheduling).
 // F16: the records' flags are 16-bit words in an array of their own (RecRef / RowRec above): rows of at most 12 edges.
 // SEND = false: no per-edge messages are stored -- the variable-node launch rebuilds them from the records this launch
-// writes (from_records::vn_kernel); the record already holds the corrected pair, so the normalized / offset forms need nothing more.
+// writes (vn_kernel's record form); the record already holds the corrected pair, so the normalized / offset forms need nothing more.
 // F8: the 16-bit family's records stored with byte flags (rows of at most 7 edges: record_flags8.h); short rows only, and
 // U = 7: a row is one round of seven loads (the tables' padding, graph_tables.h kTablePad, covers any U up to 16).  The byte
 // form also holds the signs and the running argmin of a row in ONE register per codeword (`sa`), folds the minima with

@@ -91,10 +91,10 @@ struct Launch {
   // 16-bit words in an array of their own (Records::flags), or that array as bytes (Records::flags8: rows of at most 7
   // edges, "flags8"), or four words
   struct Records {
-    T *mag;           // the records ([M * recw][tile]); with 16-bit flags the magnitudes alone ([2M][tile])
-    uint16_t *flags;  // [M][tile], or null: the flags are the record's third word
+    T *mag;       // the records ([M * recw][tile]); with 16-bit flags the magnitudes alone ([2M][tile])
+    void *flags;  // [M][tile] of uint16_t, or null: the flags are the record's third word
     uint32_t recw;
-    bool flags8 = false;  // the byte form: `flags` holds [M][tile] bytes (the array keeps its 16-bit size)
+    bool flags8 = false;  // the byte form: `flags` holds [M][tile] of uint8_t (the array keeps its 16-bit size)
   };
   template <typename F>
   static void with_rec_form(const Records &r, F &&f) {
@@ -103,23 +103,15 @@ struct Launch {
     if (r.recw == 3) return f(int_c<3>{}, std::false_type{}, std::false_type{});
     f(int_c<4>{}, std::false_type{}, std::false_type{});
   }
-  template <bool F16, bool F8 = false>
-  static auto rec_in(const Records &r) {
-    if constexpr (F16 && F8)
-      return dev::RecPair8<const T>{r.mag, reinterpret_cast<uint8_t *>(r.flags)};
-    else if constexpr (F16)
-      return dev::RecPair<const T>{r.mag, r.flags};
+  // the records as a kernel argument (dev::RecRef): for a launch that reads them (CONST) or writes them
+  template <bool CONST, bool F16, bool F8 = false>
+  static auto rec_ref(const Records &r) {
+    using TT = std::conditional_t<CONST, const T, T>;
+    using FW = dev::RecFlagWord<T, F16, F8>;
+    if constexpr (F16)
+      return dev::RecPair<TT, FW>{r.mag, static_cast<FW *>(r.flags)};
     else
-      return static_cast<const T *>(r.mag);
-  }
-  template <bool F16, bool F8 = false>
-  static auto rec_out(const Records &r) {
-    if constexpr (F16 && F8)
-      return dev::RecPair8<T>{r.mag, reinterpret_cast<uint8_t *>(r.flags)};
-    else if constexpr (F16)
-      return dev::RecPair<T>{r.mag, r.flags};
-    else
-      return r.mag;
+      return static_cast<TT *>(r.mag);
   }
   // row records (cn_minsum_rec_kernel): VEC x record form x FIRST x long rows
   // (rows of at most 8 edges -- DVB-S2 up to rate 1/2, most 5G NR rows are longer -- take the variant without the
@@ -139,8 +131,8 @@ struct Launch {
           auto go_rec = [&](auto SEND) {
             dev::cn_minsum_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, kU, decltype(FIRST)::value,
                                       true, false, decltype(long_rows)::value, decltype(SEND)::value, kF8, decltype(mc)...>
-                <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_in<decltype(F16)::value, kF8>(in),
-                                                rec_out<decltype(F16)::value, kF8>(out), msg, unsat, run, mc...);
+                <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_ref<true, decltype(F16)::value, kF8>(in),
+                                                rec_ref<false, decltype(F16)::value, kF8>(out), msg, unsat, run, mc...);
           };
           if constexpr (decltype(F16)::value) {
             if (!send) return go_rec(std::false_type{});
@@ -155,7 +147,7 @@ struct Launch {
     with_vec<T>(vec, [&](auto V) {
       with_rec_form(rec, [&](auto W, auto F16, auto F8) {
         dev::vn_free_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, decltype(F8)::value>
-            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, free_rs, chan, rec_in<decltype(F16)::value, decltype(F8)::value>(rec),
+            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, free_rs, chan, rec_ref<true, decltype(F16)::value, decltype(F8)::value>(rec),
                                             post, event_iteration);
       });
     });
@@ -187,14 +179,29 @@ struct Launch {
     });
   }
 
-  // variable nodes (list = true: only the variables of Graph::list_*)
-  // (eight loads in flight; the messages are read once: nontemporal -- 732 -> 680 us on DVB-S2 1/2 in round 2)
+  // variable nodes: every form is a launch of dev::vn_kernel, written here once.  src...: what it sums, the kernel's SRC
+  // arguments (the per-edge messages, or the records and keep_rs).  EVW, EVF16, EVF8: the record form of ev_rec, the event
+  // block's records (null, or EVW == 0: no event block)
+  // (eight loads in flight)
+  template <int VEC, bool NT, bool LIST, int EVW, bool EVF16, bool EVF8, typename... SRC>
+  void vn_go(const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan, T *post, const uint32_t *unsat_in,
+             uint32_t *unsat_clear, int32_t latch_it, const uint32_t *free_var, const uint32_t *free_rs, const Records *ev_rec,
+             uint32_t n_free, SRC... src) const {
+    dev::VnEventOf<T, EVF16, EVF8> ev{};
+    if (ev_rec) ev = dev::VnEventOf<T, EVF16, EVF8>{free_var, free_rs, rec_ref<true, EVF16, EVF8>(*ev_rec), n_free};
+    dev::vn_kernel<T, VEC, 8, NT, LIST, EVW, EVF16, EVF8, SRC...>
+        <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, src..., post, unsat_in, unsat_clear, latch_it, ev);
+  }
+  typedef const T *__restrict__ MsgIn;  // (SRC as the kernels have always declared these arguments)
+  typedef const uint32_t *__restrict__ TableIn;
+  // from the per-edge messages (list = true: only the variables of Graph::list_*)
+  // (the messages are read once: nontemporal -- 732 -> 680 us on DVB-S2 1/2 in round 2)
   void vn(bool list, uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan, const T *msg,
           T *post, const uint32_t *unsat_in, uint32_t *unsat_clear, int32_t latch_it) const {
     with_vec<T>(vec, [&](auto V) {
       with_bool(list, [&](auto LIST) {
-        dev::vn_kernel<T, decltype(V)::value, 8, true, decltype(LIST)::value>
-            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, msg, post, unsat_in, unsat_clear, latch_it);
+        vn_go<decltype(V)::value, true, decltype(LIST)::value, 0, false, false, MsgIn>(
+            t, g, st, chan, post, unsat_in, unsat_clear, latch_it, nullptr, nullptr, nullptr, 0, msg);
       });
     });
   }
@@ -205,17 +212,15 @@ struct Launch {
                 const uint32_t *free_rs, const Records &rec, uint32_t n_free) const {
     with_vec<T>(vec, [&](auto V) {
       with_rec_form(rec, [&](auto W, auto F16, auto F8) {
-        const dev::VnEventOf<T, decltype(F16)::value, decltype(F8)::value> ev{
-            free_var, free_rs, rec_in<decltype(F16)::value, decltype(F8)::value>(rec), n_free};
-        dev::vn_kernel<T, decltype(V)::value, 8, true, true, decltype(W)::value, decltype(F16)::value, decltype(F8)::value>
-            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, msg, post, unsat_in, unsat_clear, latch_it, ev);
+        vn_go<decltype(V)::value, true, true, decltype(W)::value, decltype(F16)::value, decltype(F8)::value, MsgIn>(
+            t, g, st, chan, post, unsat_in, unsat_clear, latch_it, free_var, free_rs, &rec, n_free, msg);
       });
     });
   }
 
-  // the list variant that sums the kept variables from the records of this iteration (from_records::vn_kernel; 16-bit flags, or
-  // the same records with byte flags).  ev_rec
-  // null: no event block (the first iteration, or "vn_event" / "rec_quiet" off).
+  // the list variant that sums the kept variables from the records of this iteration (kernels_flooding.hip.h, REC; 16-bit
+  // flags, or the same records with byte flags).  ev_rec null: no event block (the first iteration, or "vn_event" /
+  // "rec_quiet" off).
   // (eight records in flight and nontemporal channel loads: the headline gains 0.65 % over four in flight -- 98 against 57
   // VGPRs, 4 against 8 waves per SIMD -- and 0.35 % over cached channel loads, profiles/vn_records.txt section 1)
   void vn_rec(uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan,
@@ -225,11 +230,10 @@ struct Launch {
       with_bool(ev_rec != nullptr, [&](auto EV) {
         with_bool(rec.flags8, [&](auto F8) {
           constexpr bool kF8 = decltype(F8)::value;
-          dev::VnEventOf<T, true, kF8> ev{};
-          if (ev_rec) ev = dev::VnEventOf<T, true, kF8>{free_var, free_rs, rec_in<true, kF8>(*ev_rec), n_free};
-          dev::from_records::vn_kernel<T, decltype(V)::value, 8, true, decltype(EV)::value, kF8>
-              <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, rec_in<true, kF8>(rec), keep_rs, post, unsat_in, unsat_clear,
-                                              latch_it, ev);
+          using RecIn = typename dev::RecRef<T, true, kF8>::in;
+          vn_go<decltype(V)::value, true, true, decltype(EV)::value ? 3 : 0, true, kF8, RecIn, TableIn>(
+              t, g, st, chan, post, unsat_in, unsat_clear, latch_it, free_var, free_rs, ev_rec, n_free,
+              rec_ref<true, true, kF8>(rec), keep_rs);
         });
       });
     });

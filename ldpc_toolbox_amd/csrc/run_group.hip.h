@@ -145,7 +145,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     const uint32_t rec_rows = w.rec_flags[0] ? 2 * m : m * rec_w_;  // rows of T a compaction moves
     if (lfree && post_rows_keep_ > 0 && post_rows_keep_ <= n) post_move_rows = post_rows_keep_;
     // "vn_records": the variable-node launch sums the kept variables from this iteration's records and the check-node launch
-    // stores no per-edge messages (from_records::vn_kernel); with 16-bit flags only
+    // stores no per-edge messages (vn_kernel's record form); with 16-bit flags only
     const bool vn_records = records && w.rec_flags[0] != nullptr && d_keep_rs_ && opt_vn_records_;
     last_vn_records_.store(vn_records, std::memory_order_relaxed);
     const bool quiet = records && opt_rec_quiet_;
@@ -227,7 +227,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       if (checkpoint_due(it) || tail_checkpoint(it)) {
         // what the next iteration reads: the records of this one (the per-edge messages have been consumed)
         if (records)
-          compact(max_iterations - it, rbuf[it & 1].mag, true, rec_rows, rbuf[it & 1].flags, m, flags8);
+          compact(max_iterations - it, rbuf[it & 1].mag, true, rec_rows, w.rec_flags[it & 1], m, flags8);
         else
           compact(max_iterations - it, m_out, true, static_cast<uint32_t>(e_));
       }

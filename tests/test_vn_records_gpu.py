@@ -1,4 +1,4 @@
-"""Flooding min-sum with the variable nodes summed from the ROW RECORDS ("vn_records" = 1: from_records::vn_kernel gathers, per kept
+"""Flooding min-sum with the variable nodes summed from the ROW RECORDS ("vn_records" = 1: vn_kernel's record form gathers, per kept
 edge, the record of the edge's row, and the check-node launch stores no per-edge messages) against the message form
 ("vn_records" = 0) and the CPU reference: hard decisions, iteration counts and posterior LLRs with np.array_equal -- no
 tolerance -- and "last_vn_records" says which form ran.
