@@ -451,6 +451,75 @@ int32_t ldpc_toolbox_bch_decode_batch_device(void *bch, uint8_t *output, size_t 
  * payload, and a frame whose more-than-t errors all lie in the parity is correct.  The counters do not depend on "pooling". */
 int32_t ldpc_toolbox_sim_set_bch(void *sim, void *bch);
 
+/* ===================================================================================
+ * PART 6 -- batched 5G NR rate matching and rate recovery on the GPU (3GPP TS 38.212 5.4.2: bit selection from the
+ * circular buffer and the bit interleaver; on receive, soft combining of repeats and retransmissions).  The reference
+ * has no rate matcher: its block puncturing pattern can only leave out the first 2 Zc columns.
+ * =================================================================================== */
+
+/* The handle is a code block configuration (BG, Zc, F, Ncb); a transmission (E, rv, Qm) is given per call, because HARQ
+ * changes rv between calls on one soft buffer.
+ *   n = 68 Zc (BG 1) or 52 Zc (BG 2), the columns of "nr5g:BG:ZC";  K = 22 Zc or 10 Zc;  N = n - 2 Zc.
+ *   Column c of the codeword is buffer bit d = c - 2 Zc; the columns c < 2 Zc are never transmitted.
+ *   Fillers: the F columns K-F .. K-1 (buffer bits K-2Zc-F .. K-2Zc-1) are NULL; 0 <= F <= K - 2 Zc.
+ *   Ncb: 1 <= Ncb <= N (default N: no limited-buffer rate matching).  L = the number of non-NULL bits among buffer bits
+ *   0 .. Ncb-1; L >= 1.
+ *   k0 = floor(a Ncb / N) Zc with a = 0, 17, 33, 56 (BG 1) or 0, 13, 25, 43 (BG 2) for rv 0..3.
+ *   Bit selection:  k = j = 0; while k < E: d = (k0 + j) mod Ncb; if d is not NULL: e[k++] = d; j++.
+ *   Interleaver:    f[i + q Qm] = e[i (E / Qm) + q] for i < Qm, q < E / Qm.  Qm in 1..8 divides E; E <= 0x7fffffff.
+ *   f is the transmitted order: the `output` of match and the `rx` of recover.
+ * spec: "nr5g:BG:ZC[:F[:NCB]]", decimal.  NULL (message via ldpc_toolbox_last_error) for another spelling, a BG other than
+ * 1 or 2, a Zc that is none of the 51 lifting sizes, or F, Ncb, L outside the ranges above.
+ * The constructor needs no GPU (`device` is used by the first batched call; -1 = LDPC_TOOLBOX_DEVICE, default 0). */
+void *ldpc_toolbox_nr_rm_ctor(const char *spec, int32_t device);
+void ldpc_toolbox_nr_rm_dtor(void *rm);
+/* key: "n", "k" (K), "zc", "base_graph", "fillers", "n_cb", "buffer_len" (L), "k0_0" .. "k0_3", "device" (-1 until the
+ * first batched call made the device state).  returns 0, or -1 for an unknown key. */
+int32_t ldpc_toolbox_nr_rm_get(void *rm, const char *key, int64_t *value);
+/* codewords [batch][n] -- exactly the output of ldpc_toolbox_encoder_encode_batch_device; a byte equal to 1 is a one,
+ * anything else a zero -- to output [batch][e], bytes 0 or 1 in transmitted order.
+ * A null handle, n other than the code's, rv > 3, qm outside 1..8, e == 0, e > 0x7fffffff or qm not dividing e:
+ * LDPC_TOOLBOX_ERR_ARGUMENT before the GPU is touched, nothing written.  Without a GPU LDPC_TOOLBOX_ERR_DEVICE (there is
+ * no CPU path).  batch == 0 returns 0; batch is otherwise unlimited.  Input and output do not overlap.  One call at a
+ * time per handle.  Host pointers (staged through the handle's buffers) or, _device, device pointers and a hipStream_t:
+ * a stream = enqueue and return; NULL = the handle's own stream, ordered after what the legacy default stream holds at
+ * the call, synchronised on return. */
+int32_t ldpc_toolbox_nr_rm_match(void *rm, uint8_t *output, size_t e, const uint8_t *codewords, size_t n, size_t batch,
+                                 uint32_t rv, uint32_t qm);
+int32_t ldpc_toolbox_nr_rm_match_device(void *rm, uint8_t *output, size_t e, const uint8_t *codewords, size_t n, size_t batch,
+                                        uint32_t rv, uint32_t qm, void *hip_stream);
+/* rx [batch][e], received values in transmitted order (the demapper's LLRs), to llrs [batch][n] -- exactly the `llrs` of
+ * ldpc_toolbox_decoder_decode_batch_f32_device / _f64_device on a decoder built with puncturing "".  Per frame and
+ * column c: let p_0 < p_1 < ... < p_(R-1) be the selection indices k (before interleaving) that carry c, and t_i the
+ * received value at the interleaved position of p_i; S = t_0 + t_1 + ... + t_(R-1), added left to right in the element
+ * type, each sum rounded once.  The output is
+ *   a filler column:  filler_llr rounded once to the type, whatever `combine` is;
+ *   R = 0:            +0.0, or the old value when combine != 0;
+ *   otherwise:        S, or old + S when combine != 0.
+ * No atomics and no reassociation: the result is a pure function of the inputs, bit for bit.  combine != 0 is HARQ soft
+ * combining: call once per transmission on one buffer, the first with combine = 0.
+ * filler_llr must be positive (+inf is allowed; a NaN is not): else, and for what ldpc_toolbox_nr_rm_match refuses,
+ * LDPC_TOOLBOX_ERR_ARGUMENT with nothing written.  rx and llrs do not overlap.  Other behaviour as ldpc_toolbox_nr_rm_match. */
+int32_t ldpc_toolbox_nr_rm_recover_f32(void *rm, float *llrs, size_t n, const float *rx, size_t e, size_t batch, uint32_t rv,
+                                       uint32_t qm, double filler_llr, int32_t combine);
+int32_t ldpc_toolbox_nr_rm_recover_f64(void *rm, double *llrs, size_t n, const double *rx, size_t e, size_t batch, uint32_t rv,
+                                       uint32_t qm, double filler_llr, int32_t combine);
+int32_t ldpc_toolbox_nr_rm_recover_f32_device(void *rm, float *llrs, size_t n, const float *rx, size_t e, size_t batch,
+                                              uint32_t rv, uint32_t qm, double filler_llr, int32_t combine, void *hip_stream);
+int32_t ldpc_toolbox_nr_rm_recover_f64_device(void *rm, double *llrs, size_t n, const double *rx, size_t e, size_t batch,
+                                              uint32_t rv, uint32_t qm, double filler_llr, int32_t combine, void *hip_stream);
+/* The simulator's option to rate-match what it transmits.  The configuration is copied (the handle may be destroyed
+ * afterwards); rm == NULL returns to none.  returns -1 with a message and changes nothing unless the simulator was built
+ * with puncturing "", its n equals the handle's n, the handle's F is 0 (the pool's messages are random in all k
+ * positions), (e, rv, qm) is a transmission as above, and e is a multiple of the modulation's bits per symbol and of
+ * |interleaving|.  While a rate matcher is set: "n_tx" is e and the rate k / e; the pool's transmitted rows
+ * (ldpc_toolbox_sim_pool) are the rate-matched pooled codewords, [pool][e]; the LLRs of frame f are what the generator
+ * produces for that transmitted row with the same keys, and ldpc_toolbox_sim_generate returns these [frames][e] values;
+ * they are recovered with combine = 0 into the [frames][n] rows the decoder and the straggler pool see.  The counters do
+ * not depend on "pooling".  "rate_match" of ldpc_toolbox_sim_get is 1 while one is set.  Setting or clearing resets the
+ * straggler-pooling budget, as "modulation" does. */
+int32_t ldpc_toolbox_sim_set_rate_match(void *sim, void *rm, size_t e, uint32_t rv, uint32_t qm);
+
 /* Standard-code generator (what the reference's `dvbs2` / `5g` / `ccsds` / `ccsds-c2` CLI
  * sub-commands print, src/cli/dvbs2.rs:91, src/cli/nr5g.rs:46, src/cli/ccsds.rs:70): writes the
  * padded alist text of `spec` ("dvbs2:R1_2", "nr5g:1:384", "ar4ja:1/2:1024", "c2") into

@@ -6,9 +6,10 @@ from .decoder import (ALL_IMPLEMENTATIONS, CORRECTED_MINSUM_IMPLEMENTATIONS, FAS
                       I8_IMPLEMENTATIONS, IMPLEMENTATIONS, MINSUM_I8_IMPLEMENTATIONS, LdpcDecoder, Simulator)
 from .bch import BchCode
 from .demodulator import Demodulator
+from .nr_rate_match import NrRateMatcher
 from .sparse import SparseMatrix
 
 code_alist = _capi.code_alist
 
 __all__ = ["ALL_IMPLEMENTATIONS", "BchCode", "CORRECTED_MINSUM_IMPLEMENTATIONS", "FAST_IMPLEMENTATIONS", "I8_IMPLEMENTATIONS", "DecoderImplementation", "DecoderOutput", "DecoderUnavailable", "Demodulator", "Encoder",
-           "IMPLEMENTATIONS", "MINSUM_I8_IMPLEMENTATIONS", "LdpcDecoder", "Simulator", "SparseMatrix", "code_alist"]
+           "IMPLEMENTATIONS", "MINSUM_I8_IMPLEMENTATIONS", "LdpcDecoder", "NrRateMatcher", "Simulator", "SparseMatrix", "code_alist"]

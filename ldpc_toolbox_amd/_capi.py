@@ -71,6 +71,16 @@ SYMBOLS = [
     "ldpc_toolbox_bch_decode_batch",
     "ldpc_toolbox_bch_decode_batch_device",
     "ldpc_toolbox_sim_set_bch",
+    "ldpc_toolbox_nr_rm_ctor",
+    "ldpc_toolbox_nr_rm_dtor",
+    "ldpc_toolbox_nr_rm_get",
+    "ldpc_toolbox_nr_rm_match",
+    "ldpc_toolbox_nr_rm_match_device",
+    "ldpc_toolbox_nr_rm_recover_f32",
+    "ldpc_toolbox_nr_rm_recover_f64",
+    "ldpc_toolbox_nr_rm_recover_f32_device",
+    "ldpc_toolbox_nr_rm_recover_f64_device",
+    "ldpc_toolbox_sim_set_rate_match",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
     "ldpc_toolbox_device_count",
@@ -253,6 +263,25 @@ def lib():
     L.ldpc_toolbox_bch_decode_batch_device.argtypes = [vp, vp, sz, vp, sz, sz, vp, vp]
     L.ldpc_toolbox_sim_set_bch.restype = i32
     L.ldpc_toolbox_sim_set_bch.argtypes = [vp, vp]
+    L.ldpc_toolbox_nr_rm_ctor.restype = vp
+    L.ldpc_toolbox_nr_rm_ctor.argtypes = [cp, i32]
+    L.ldpc_toolbox_nr_rm_dtor.restype = None
+    L.ldpc_toolbox_nr_rm_dtor.argtypes = [vp]
+    L.ldpc_toolbox_nr_rm_get.restype = i32
+    L.ldpc_toolbox_nr_rm_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
+    L.ldpc_toolbox_nr_rm_match.restype = i32
+    L.ldpc_toolbox_nr_rm_match.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32]
+    L.ldpc_toolbox_nr_rm_match_device.restype = i32
+    L.ldpc_toolbox_nr_rm_match_device.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32, vp]
+    for name in ("f32", "f64"):
+        f = getattr(L, "ldpc_toolbox_nr_rm_recover_" + name)
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32, C.c_double, i32]
+        f = getattr(L, "ldpc_toolbox_nr_rm_recover_" + name + "_device")
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32, C.c_double, i32, vp]
+    L.ldpc_toolbox_sim_set_rate_match.restype = i32
+    L.ldpc_toolbox_sim_set_rate_match.argtypes = [vp, vp, sz, u32, u32]
     L.ldpc_toolbox_code_alist.restype = sz
     L.ldpc_toolbox_code_alist.argtypes = [cp, vp, sz]
     L.ldpc_toolbox_alist_normalize.restype = sz

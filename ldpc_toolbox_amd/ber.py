@@ -172,6 +172,8 @@ def format_details(a, sim, world: int) -> str:
         lines.append(f" - Puncturing pattern: {a.puncturing}")
     if a.interleaving:
         lines.append(f" - Interleaving columns: {a.interleaving}")
+    if getattr(a, "nr_rate_match", None):                                             # this build's addition
+        lines.append(f" - NR rate matching (E[:RV[:QM]]): {a.nr_rate_match}")
     lines += [f" - Information bits (k): {sim.k}", f" - Codeword size (N_cw): {sim.n}", f" - Frame size (N): {sim.n_tx}",
               f" - Code rate: {sim.rate:.3f}", "LDPC decoder:", f" - Implementation: {a.decoder}",
               f" - Maximum iterations: {a.max_iter}"]
@@ -230,6 +232,10 @@ def main(argv=None):
     ap.add_argument("--bch-code", metavar="SPEC",
                     help='the real outer code instead of that count: "dvbs2:NAME" or "bch:M:P:T:N" (its n must be the LDPC '
                          "code's k); sets --bch-max-errors to its t")
+    ap.add_argument("--nr-rate-match", metavar="E[:RV[:QM]]",
+                    help="with --code nr5g:BG:ZC: 5G NR rate matching (TS 38.212 5.4.2) of every frame to E transmitted bits "
+                         "with redundancy version RV (default 0) and Qm (default 1) interleaver rows, no filler bits, Ncb = N; "
+                         "the code rate becomes k/E")
     ap.add_argument("--output-file-ldpc", help="LDPC-only results when --bch-max-errors is used (cli/ber.rs:102-105)")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal of the multi-GPU sweep on a one-GPU box: every rank uses GPU 0 and the counters are "
@@ -241,6 +247,16 @@ def main(argv=None):
         ap.error("one of --code, --alist, --codes is required")
     if a.codes and a.bch_code:
         ap.error("--bch-code names one code: it cannot be combined with --codes")
+    rate_match = None
+    if a.nr_rate_match:
+        if a.codes or not (a.code or "").startswith("nr5g:") or a.puncturing:
+            ap.error("--nr-rate-match needs --code nr5g:BG:ZC and no --puncturing")
+        try:
+            rate_match = [int(x) for x in a.nr_rate_match.split(":")]
+        except ValueError:
+            rate_match = []
+        if not 1 <= len(rate_match) <= 3:
+            ap.error("--nr-rate-match takes E[:RV[:QM]]")
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -286,6 +302,14 @@ def main(argv=None):
         except ValueError as e:
             ap.error(f"--bch-code {a.bch_code}: {e}")
         code.close()
+    if rate_match:
+        from .nr_rate_match import NrRateMatcher
+        try:
+            rm = NrRateMatcher(a.code, device=local)
+            sim.set_rate_match(rm, *rate_match)
+        except ValueError as e:
+            ap.error(f"--nr-rate-match {a.nr_rate_match}: {e}")
+        rm.close()
     out = open(a.output_file, "w") if (a.output_file and rank == 0) else None
     out_ldpc = open(a.output_file_ldpc, "w") if (a.output_file_ldpc and a.bch_max_errors > 0 and rank == 0) else None
     details = format_details(a, sim, world)

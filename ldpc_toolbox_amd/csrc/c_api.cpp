@@ -19,6 +19,7 @@
 #include "device_bch.h"
 #include "device_decoder.h"
 #include "device_encoder.h"
+#include "device_nr_rm.h"
 #include "encoder.h"
 #include "implementation.h"
 #include "simulator.h"
@@ -68,6 +69,13 @@ struct BchHandle {
   int device = 0;
   // the device state: made at the first batched call
   std::unique_ptr<ldpc::DeviceBch> dev;
+};
+
+struct NrRmHandle {
+  ldpc::nrrm::Config c;
+  int device = 0;
+  // the device state: made at the first batched call
+  std::unique_ptr<ldpc::DeviceNrRm> dev;
 };
 
 // a device index: decimal digits only (no sign, no trailing characters)
@@ -356,6 +364,105 @@ int32_t bch_run(void *bch, bool decode, uint8_t *output, size_t output_len, cons
                    : h->dev->decode_host(input, output, output_len, batch, errors);
   else
     rc = on_device ? h->dev->encode_device(input, output, batch, s) : h->dev->encode_host(input, output, batch);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+// "nr5g:BG:ZC[:F[:NCB]]": decimal fields, nothing else
+bool parse_nr_rm_spec(const char *spec, ldpc::nrrm::Config *c, std::string *err) {
+  std::vector<std::string> parts;
+  for (std::string rest = spec;;) {
+    const size_t at = rest.find(':');
+    parts.push_back(rest.substr(0, at));
+    if (at == std::string::npos) break;
+    rest = rest.substr(at + 1);
+  }
+  int64_t v[4] = {0, 0, 0, -1};
+  bool ok = parts.size() >= 3 && parts.size() <= 5 && parts[0] == "nr5g";
+  for (size_t i = 1; ok && i < parts.size(); i++) {
+    const std::string &t = parts[i];
+    ok = !t.empty() && t.size() <= 9 && t.find_first_not_of("0123456789") == std::string::npos;
+    if (ok) v[i - 1] = std::strtoll(t.c_str(), nullptr, 10);
+  }
+  if (!ok) {
+    *err = "invalid rate matcher spec (expected nr5g:BG:ZC[:F[:NCB]])";
+    return false;
+  }
+  if (ldpc::codes::nr5g_set_index(static_cast<unsigned>(v[1])) < 0) {
+    *err = "lifting size is none of the 51 of TS 38.212 Table 5.3.2-1";
+    return false;
+  }
+  if (const char *why = ldpc::nrrm::make_config(v[0], v[1], v[2], v[3], c)) {
+    *err = why;
+    return false;
+  }
+  return true;
+}
+
+// 0 with the handle's device state made, or LDPC_TOOLBOX_ERR_DEVICE
+int32_t nr_rm_device_state(NrRmHandle *h) {
+  if (h->dev) return 0;
+  if (h->device < 0) {
+    set_error("LDPC_TOOLBOX_DEVICE is not a decimal GPU index");
+    return LDPC_TOOLBOX_ERR_DEVICE;
+  }
+  std::string err;
+  h->dev.reset(ldpc::DeviceNrRm::create(h->c, h->device, &err));
+  if (!h->dev) {
+    set_error(err);
+    return LDPC_TOOLBOX_ERR_DEVICE;
+  }
+  return 0;
+}
+
+int32_t nr_rm_match(void *rm, uint8_t *output, size_t e, const uint8_t *codewords, size_t n, size_t batch, uint32_t rv, uint32_t qm,
+                    bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrRmHandle *>(rm);
+  if (!h) {
+    set_error("null rate matcher handle");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (const char *why = ldpc::nrrm::match_argument_error(h->c, n, e, rv, qm)) {
+    set_error(why);
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (batch == 0) return 0;
+  if (!codewords || !output) {
+    set_error("null input or output buffer");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (int32_t rc = nr_rm_device_state(h)) return rc;
+  const uint32_t e32 = static_cast<uint32_t>(e);
+  const int rc = on_device ? h->dev->match_device(codewords, output, batch, e32, rv, qm, static_cast<hipStream_t>(stream))
+                           : h->dev->match_host(codewords, output, batch, e32, rv, qm);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+int32_t nr_rm_recover(void *rm, void *llrs, size_t n, const void *rx, size_t e, size_t batch, uint32_t rv, uint32_t qm, bool f64,
+                      double filler_llr, int32_t combine, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrRmHandle *>(rm);
+  if (!h) {
+    set_error("null rate matcher handle");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (const char *why = ldpc::nrrm::recover_argument_error(h->c, n, e, rv, qm, filler_llr)) {
+    set_error(why);
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (batch == 0) return 0;
+  if (!rx || !llrs) {
+    set_error("null input or output buffer");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (int32_t rc = nr_rm_device_state(h)) return rc;
+  const uint32_t e32 = static_cast<uint32_t>(e);
+  const int rc = on_device ? h->dev->recover_device(rx, llrs, f64, batch, e32, rv, qm, filler_llr, combine != 0, static_cast<hipStream_t>(stream))
+                           : h->dev->recover_host(rx, llrs, f64, batch, e32, rv, qm, filler_llr, combine != 0);
   if (rc == 0) return 0;
   set_error(h->dev->last_error());
   return LDPC_TOOLBOX_ERR_DEVICE;
@@ -792,6 +899,8 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value) {
     *value = s->max_log() ? 1 : 0;
   else if (k == "bch")  // 1 while ldpc_toolbox_sim_set_bch is in force
     *value = s->has_bch() ? 1 : 0;
+  else if (k == "rate_match")  // 1 while ldpc_toolbox_sim_set_rate_match is in force
+    *value = s->has_rate_match() ? 1 : 0;
   else if (k == "streamed_frames" || k == "stream_iterations")  // (continuous batching: profiles/r03_continuous_batching.txt)
     *value = 0;
   else if (k == "pooled_frames")  // frames of the last run() call that went through the straggler pool
@@ -1029,6 +1138,96 @@ int32_t ldpc_toolbox_bch_decode_batch(void *bch, uint8_t *output, size_t output_
 int32_t ldpc_toolbox_bch_decode_batch_device(void *bch, uint8_t *output, size_t output_len, const uint8_t *input,
                                              size_t input_len, size_t batch, int32_t *errors, void *hip_stream) {
   return bch_run(bch, true, output, output_len, input, input_len, batch, errors, true, hip_stream);
+}
+
+// ---- PART 6: batched 5G NR rate matching and rate recovery -----------------------------------------
+
+void *ldpc_toolbox_nr_rm_ctor(const char *spec, int32_t device) {
+  g_last_error.clear();
+  if (!spec) {
+    set_error("null rate matcher spec");
+    return nullptr;
+  }
+  auto h = std::make_unique<NrRmHandle>();
+  std::string err;
+  if (!parse_nr_rm_spec(spec, &h->c, &err)) {
+    set_error(err);
+    return nullptr;
+  }
+  h->device = device < 0 ? default_device() : device;
+  return h.release();
+}
+
+void ldpc_toolbox_nr_rm_dtor(void *rm) { delete static_cast<NrRmHandle *>(rm); }
+
+int32_t ldpc_toolbox_nr_rm_get(void *rm, const char *key, int64_t *value) {
+  auto *h = static_cast<NrRmHandle *>(rm);
+  if (!h || !key || !value) return -1;
+  const std::string k = key;
+  if (k == "n")
+    *value = h->c.n;
+  else if (k == "k")
+    *value = h->c.k;
+  else if (k == "zc")
+    *value = h->c.zc;
+  else if (k == "base_graph")
+    *value = h->c.bg;
+  else if (k == "fillers")
+    *value = h->c.fillers;
+  else if (k == "n_cb")
+    *value = h->c.ncb;
+  else if (k == "buffer_len")  // L: the non-NULL bits of the circular buffer
+    *value = h->c.l;
+  else if (k.size() == 4 && k.compare(0, 3, "k0_") == 0 && k[3] >= '0' && k[3] <= '3')
+    *value = ldpc::nrrm::k0_of(h->c, static_cast<uint32_t>(k[3] - '0'));
+  else if (k == "device")
+    *value = h->dev ? h->dev->device() : -1;
+  else
+    return -1;
+  return 0;
+}
+
+int32_t ldpc_toolbox_nr_rm_match(void *rm, uint8_t *output, size_t e, const uint8_t *codewords, size_t n, size_t batch, uint32_t rv,
+                                 uint32_t qm) {
+  return nr_rm_match(rm, output, e, codewords, n, batch, rv, qm, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_rm_match_device(void *rm, uint8_t *output, size_t e, const uint8_t *codewords, size_t n, size_t batch,
+                                        uint32_t rv, uint32_t qm, void *hip_stream) {
+  return nr_rm_match(rm, output, e, codewords, n, batch, rv, qm, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_rm_recover_f32(void *rm, float *llrs, size_t n, const float *rx, size_t e, size_t batch, uint32_t rv,
+                                       uint32_t qm, double filler_llr, int32_t combine) {
+  return nr_rm_recover(rm, llrs, n, rx, e, batch, rv, qm, false, filler_llr, combine, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_rm_recover_f64(void *rm, double *llrs, size_t n, const double *rx, size_t e, size_t batch, uint32_t rv,
+                                       uint32_t qm, double filler_llr, int32_t combine) {
+  return nr_rm_recover(rm, llrs, n, rx, e, batch, rv, qm, true, filler_llr, combine, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_rm_recover_f32_device(void *rm, float *llrs, size_t n, const float *rx, size_t e, size_t batch, uint32_t rv,
+                                              uint32_t qm, double filler_llr, int32_t combine, void *hip_stream) {
+  return nr_rm_recover(rm, llrs, n, rx, e, batch, rv, qm, false, filler_llr, combine, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_rm_recover_f64_device(void *rm, double *llrs, size_t n, const double *rx, size_t e, size_t batch, uint32_t rv,
+                                              uint32_t qm, double filler_llr, int32_t combine, void *hip_stream) {
+  return nr_rm_recover(rm, llrs, n, rx, e, batch, rv, qm, true, filler_llr, combine, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_sim_set_rate_match(void *sim, void *rm, size_t e, uint32_t rv, uint32_t qm) {
+  g_last_error.clear();
+  auto *s = static_cast<ldpc::Simulator *>(sim);
+  if (!s) {
+    set_error("null argument");
+    return -1;
+  }
+  auto *h = static_cast<NrRmHandle *>(rm);
+  if (s->set_rate_match(h ? &h->c : nullptr, e, rv, qm)) return 0;
+  set_error(s->last_error());
+  return -1;
 }
 
 size_t ldpc_toolbox_code_alist(const char *spec, char *buffer, size_t buffer_len) {

@@ -15,6 +15,8 @@ const Dvbs2Entry *find_dvbs2(const std::string &name) {
   return nullptr;
 }
 
+}  // namespace
+
 // set index iLS of a lifting size (TS 38.212 Table 5.3.2-1): Zc = a * 2^j with
 // a in {2,3,5,7,9,11,13,15}.
 int nr5g_set_index(unsigned zc) {
@@ -25,8 +27,6 @@ int nr5g_set_index(unsigned zc) {
       if (zc == (a[s] << j)) return s;
   return -1;
 }
-
-}  // namespace
 
 std::vector<std::string> dvbs2_names() {
   std::vector<std::string> v;

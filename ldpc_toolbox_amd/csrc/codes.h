@@ -23,6 +23,8 @@ std::vector<std::string> dvbs2_names();
 
 // 5G NR: base_graph in {1,2}; lifting size one of the 51 values of TS 38.212 Table 5.3.2-1.
 bool nr5g(int base_graph, unsigned lifting_size, SparseMatrix *h);
+// set index iLS (0..7) of a lifting size, -1 when it is none of the 51
+int nr5g_set_index(unsigned lifting_size);
 
 // CCSDS AR4JA: rate in {"1/2","2/3","4/5"}, k in {1024, 4096, 16384}.
 bool ar4ja(const std::string &rate, unsigned k, SparseMatrix *h);

@@ -13,6 +13,7 @@
 #include "demodulator.h"
 #include "device_bch.h"
 #include "device_decoder.h"
+#include "device_nr_rm.h"
 #include "hip_owned.h"
 #include "encoder.h"
 
@@ -51,6 +52,14 @@ class Simulator {
   // genie.  false with nothing changed unless the code's n is this simulator's k.
   bool set_bch(const bch::Code *c);
   bool has_bch() const { return bch_ != nullptr; }
+  // 5G NR rate matching (nr_rate_match.h) between the pooled codewords and the channel; nullptr returns to none.
+  // false with nothing changed unless the simulator was built with puncturing "", the configuration's n is this
+  // simulator's n, it has no filler bits (the pool's messages are random in all k positions), (e, rv, qm) is a
+  // transmission and e is a multiple of the modulation's bits per symbol and of |interleaving|.
+  // While set, n_tx is e: the pool's transmitted rows are the rate-matched codewords, the generator's LLRs [frames][e]
+  // are what it gives for those rows, and the decoder sees them recovered (combine = 0) to [frames][n].
+  bool set_rate_match(const nrrm::Config *c, uint64_t e, uint32_t rv, uint32_t qm);
+  bool has_rate_match() const { return rate_match_; }
   DeviceDecoder *decoder() { return dec_.get(); }
   // straggler pooling (run_bch): 0 = every chunk runs the full iteration budget
   void set_pooling(bool on) {
@@ -123,6 +132,12 @@ class Simulator {
   std::unique_ptr<DeviceBch> bch_;
   bch::Code bch_code_;
   DeviceBuffer d_bch_in_, d_bch_out_;
+  // the rate matcher of set_rate_match: its plan, the generator's rows [chunk][n_tx] before recovery, and the pooled
+  // codewords (what tx_bits_ holds while none is set)
+  bool rate_match_ = false, punctured_ = false;
+  nrrm::Plan rm_plan_{};
+  DeviceBuffer d_rx_;
+  std::vector<uint8_t> codewords_;
   int count_bch(const uint8_t *bits, const int32_t *its, uint64_t seed, uint64_t first_frame, uint32_t frames,
                 uint32_t max_iterations, const uint64_t *frame_ids, int skip_failed);
   std::string error_;

@@ -9,6 +9,7 @@
 #include "demodulator.hip.h"      // so does the batched soft demapper
 #include "device_bch.hip.h"       // and the batched BCH code
 #include "device_encoder.hip.h"  // the batched GPU encoder lives in this translation unit
+#include "device_nr_rm.hip.h"     // and the batched NR rate matcher
 #include "frame_gen.hip.h"
 #include "implementation.h"
 #include "sparse.h"
@@ -57,6 +58,7 @@ Simulator *Simulator::create(const std::string &alist, const std::string &implem
   s->n_ = h.num_cols();
   s->k_ = h.num_cols() - h.num_rows();
   s->n_tx_ = s->dec_->input_len();
+  s->punctured_ = !pattern.empty();
   s->pool_ = std::max<uint32_t>(pool, 1);
   // the pool: random messages, systematic encode, puncture (puncturing.rs:47-75)
   std::mt19937_64 rng(pool_seed);
@@ -98,7 +100,8 @@ Simulator::~Simulator() {
 
 // device buffers: LLR rows (one group's worth is enough for the streamed chunks), decoded bits and iteration counts
 int Simulator::ensure(size_t frames, size_t llr_rows) {
-  SIM_TRY(d_llrs_.ensure(llr_rows * n_tx_ * sizeof(float)));
+  SIM_TRY(d_llrs_.ensure(llr_rows * dec_->input_len() * sizeof(float)));
+  if (rate_match_) SIM_TRY(d_rx_.ensure(llr_rows * n_tx_ * sizeof(float)));
   SIM_TRY(d_bits_.ensure(frames * std::max<size_t>(k_, 1)));
   SIM_TRY(d_its_.ensure(frames * sizeof(int32_t)));
   return 0;
@@ -108,7 +111,7 @@ int Simulator::ensure_pool(size_t capacity) {
   if (capacity <= pool_cap_) return 0;
   pool_cap_ = 0;
   d_pool_count_ = DeviceBuffer();  // (its size is fixed: allocated anew with the others, as it always was)
-  SIM_TRY(d_pool_llrs_.ensure(capacity * n_tx_ * sizeof(float)));
+  SIM_TRY(d_pool_llrs_.ensure(capacity * dec_->input_len() * sizeof(float)));
   SIM_TRY(d_pool_frames_.ensure(capacity * sizeof(uint64_t)));
   SIM_TRY(d_pool_count_.ensure(64));
   SIM_TRY(d_pool_bits_.ensure(capacity * std::max<size_t>(k_, 1)));
@@ -187,6 +190,49 @@ bool Simulator::set_bch(const bch::Code *c) {
     bch_.reset();
     d_bch_in_ = DeviceBuffer();
     d_bch_out_ = DeviceBuffer();
+  }
+  budget_valid_ = false;  // (as in set_modulation)
+  return true;
+}
+
+bool Simulator::set_rate_match(const nrrm::Config *c, uint64_t e, uint32_t rv, uint32_t qm) {
+  auto refuse = [&](const char *why) {
+    fail(why);
+    return false;
+  };
+  if (c == nullptr && !rate_match_) return true;
+  const std::vector<uint8_t> &cws = rate_match_ ? codewords_ : tx_bits_;
+  std::vector<uint8_t> tx;
+  nrrm::Plan plan{};
+  if (c != nullptr) {
+    if (punctured_) return refuse("rate matching needs a simulator built with puncturing \"\"");
+    if (c->n != n_) return refuse("the rate matcher's n is not the LDPC code's n");
+    if (c->fillers != 0) return refuse("the simulator takes no filler bits: its pooled messages are random in all k positions");
+    if (const char *why = nrrm::transmission_error(e, rv, qm)) return refuse(why);
+    if (e % static_cast<uint64_t>(modulation()) != 0) return refuse("E must be a multiple of the modulation's bits per symbol");
+    const uint64_t il = interleaving_ < 0 ? uint64_t(-interleaving_) : uint64_t(interleaving_);
+    if (il != 0 && e % il != 0) return refuse("E must be a multiple of the interleaver columns");
+    plan = nrrm::make_plan(*c, static_cast<uint32_t>(e), rv, qm);
+    // the pool's transmitted rows: the rate-matched pooled codewords
+    tx.resize(size_t(pool_) * e);
+    for (uint32_t p = 0; p < pool_; p++)
+      for (uint32_t pos = 0; pos < plan.e; pos++) tx[size_t(p) * e + pos] = cws[size_t(p) * n_ + nrrm::column_of_position(plan, pos)];
+  } else {
+    tx = cws;
+  }
+  if (hipSetDevice(device_) != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) return refuse("the simulator's stream failed");
+  DeviceBuffer d_tx;
+  if (d_tx.ensure(tx.size()) != hipSuccess || hipMemcpy(d_tx.get(), tx.data(), tx.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return refuse("device allocation for the rate-matched pool failed");
+  if (c != nullptr && !rate_match_) codewords_ = tx_bits_;
+  d_tx_ = std::move(d_tx);
+  tx_bits_ = std::move(tx);
+  rate_match_ = c != nullptr;
+  rm_plan_ = plan;
+  n_tx_ = rate_match_ ? plan.e : n_;
+  if (!rate_match_) {
+    codewords_.clear();
+    d_rx_ = DeviceBuffer();
   }
   budget_valid_ = false;  // (as in set_modulation)
   return true;
@@ -275,10 +321,11 @@ void Simulator::launch_table_generator(double sigma, uint64_t seed, uint64_t fir
   }
 }
 
-// frames [first_frame, first_frame + frames) -> d_llrs_ (codeword order, ready for the decoder)
+// frames [first_frame, first_frame + frames) -> d_llrs_ (codeword order, ready for the decoder), or with a rate matcher
+// -> d_rx_ (transmitted order, to be recovered)
 void Simulator::launch_generator(double ebn0_db, uint64_t seed, uint64_t first_frame, uint32_t frames, float *dst) {
   const uint32_t n_tx = static_cast<uint32_t>(n_tx_);
-  if (dst == nullptr) dst = d_llrs_.get<float>();
+  if (dst == nullptr) dst = rate_match_ ? d_rx_.get<float>() : d_llrs_.get<float>();
   if (use_constellation_ && !constellation_.bpsk) {
     launch_table_generator(noise_sigma(ebn0_db), seed, first_frame, frames, dst);
     return;
@@ -365,6 +412,7 @@ int Simulator::run_frames(double ebn0_db, uint64_t seed, uint64_t first_frame, s
   for (size_t f0 = 0; f0 < frames; f0 += chunk) {
     const uint32_t nf = static_cast<uint32_t>(std::min(chunk, frames - f0));
     launch_generator(ebn0_db, seed, first_frame + f0, nf);
+    if (rate_match_) nr_rm_launch_recover<float>(rm_plan_, d_rx_.get<float>(), d_llrs_.get<float>(), nf, 0.0f, false, stream_);
     if (int rc = dec_->decode_device(d_llrs_.get(), false, nf, budget, d_bits_.get<uint8_t>(), k_, d_its_.get<int32_t>(), nullptr, stream_)) {
       error_ = dec_->last_error();
       return rc;
@@ -372,7 +420,7 @@ int Simulator::run_frames(double ebn0_db, uint64_t seed, uint64_t first_frame, s
     const bool reduced = budget < max_iterations;
     if (reduced)
       gen::straggler_collect_kernel<<<(nf * 64 + 255) / 256, 256, 0, stream_>>>(
-          d_its_.get<int32_t>(), nf, first_frame + f0, d_llrs_.get<float>(), static_cast<uint32_t>(n_tx_), d_pool_llrs_.get<float>(),
+          d_its_.get<int32_t>(), nf, first_frame + f0, d_llrs_.get<float>(), static_cast<uint32_t>(dec_->input_len()), d_pool_llrs_.get<float>(),
           d_pool_frames_.get<uint64_t>(), d_pool_count_.get<uint32_t>(),
           static_cast<uint32_t>(pool_cap_));
     gen::count_errors_kernel<<<(nf * 64 + 255) / 256, 256, 0, stream_>>>(
@@ -448,7 +496,7 @@ int Simulator::generate(double ebn0_db, uint64_t seed, uint64_t first_frame, siz
   } else {
     if (int rc = ensure(0, frames)) return rc;
     launch_generator(ebn0_db, seed, first_frame, static_cast<uint32_t>(frames));
-    SIM_TRY(hipMemcpyAsync(llrs, d_llrs_.get(), frames * n_tx_ * sizeof(float), hipMemcpyDefault, stream_));
+    SIM_TRY(hipMemcpyAsync(llrs, rate_match_ ? d_rx_.get() : d_llrs_.get(), frames * n_tx_ * sizeof(float), hipMemcpyDefault, stream_));
   }
   SIM_TRY(hipStreamSynchronize(stream_));
   SIM_TRY(hipGetLastError());

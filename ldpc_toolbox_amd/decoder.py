@@ -377,6 +377,16 @@ class Simulator:
         if _capi.lib().ldpc_toolbox_sim_set_bch(self._h, h) != 0:
             raise ValueError(_capi.last_error() or "cannot set the BCH code")
 
+    def set_rate_match(self, rm, e: int = 0, rv: int = 0, qm: int = 1):
+        """`rm`: an `NrRateMatcher` (no filler bits, the simulator's n) whose transmission (e, rv, qm) the frames go
+        through from now on -- n_tx becomes e and the rate k / e -- or None for none.  ValueError (nothing changed) when the
+        simulator refuses it."""
+        h = None if rm is None else rm._h
+        if _capi.lib().ldpc_toolbox_sim_set_rate_match(self._h, h, int(e), int(rv), int(qm)) != 0:
+            raise ValueError(_capi.last_error() or "cannot set the rate matcher")
+        self.n_tx = self.get("n_tx")
+        self.rate = self.k / self.n_tx
+
     def get(self, key):
         v = C.c_int64(0)
         if _capi.lib().ldpc_toolbox_sim_get(self._h, key.encode(), C.byref(v)) != 0:
