@@ -70,6 +70,11 @@ class DeviceDecoder {
   // kept no flooding row records
   uint32_t flags8() const { return opt_flags8_ ? 1 : 0; }
   uint32_t last_record_flag_bytes() const { return last_record_flag_bytes_.load(std::memory_order_relaxed); }
+  // whether the last decode call's variable-node launches walked the kept list in bundles ("vn_bundles"), and the record
+  // fetches the bundles spare when every coincident request of a workgroup is served once, in thousandths of the list's
+  // fetches, at that call's bundle width (graph_tables.h, count_vn_bundle_fetches); 0 when off
+  uint32_t last_vn_bundles() const { return last_vn_bundles_.load(std::memory_order_relaxed) ? 1 : 0; }
+  uint32_t vn_bundle_saved_permille() const { return last_vn_bundle_saved_.load(std::memory_order_relaxed); }
 
   // codewords per group (rounded up to the wave tile).  0 = automatic.
   void set_group_size(size_t g) { group_pref_ = g; }
@@ -79,13 +84,14 @@ class DeviceDecoder {
   void set_min_group(size_t g) { min_group_ = g; }
   // codewords per group a call of `batch` codewords is cut into (the set value, else a default that grows for small graphs)
   size_t preferred_group(size_t batch) const { return pick_group(batch); }
-  // The 28 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
+  // The 29 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
   // percent are constants now, see kStreamBlock ... below).  Results never depend on any of them; each selects between
   // forms that tests/ compare bit for bit.  returns false for an unknown key.
   //   which kernels run   "lfree" (0: plain flooding min-sum kernels), "records" (0 / 1 / 2: per-edge messages / row records
   //                       where the graph suits them / wherever possible), "rec_quiet" (0: L-free posteriors stored every
   //                       iteration), "vn_event" (0: the first convergences' rebuild as a launch of its own), "vn_records" (0 / 1:
-  //                       the variable nodes summed from per-edge messages / from the row records, 16-bit flags only), "flags8" (0 / 1: the
+  //                       the variable nodes summed from per-edge messages / from the row records, 16-bit flags only), "vn_bundles" (0 / 1: that
+  //                       form's kept list in variable order / in bundles of the variables a workgroup sums together), "flags8" (0 / 1: the
   //                       16-bit flags of rows of at most 7 edges stored as half-words / as bytes), "rec_long"
   //                       (1: the record kernel's long-row variant whatever the graph), "staged_minsum" (1: Minsum through
   //                       the generic LDS-staged kernel), "cn_reg" / "hl_reg" / "hl_records" (0: the LDS-staged / two-pass /
@@ -219,6 +225,18 @@ class DeviceDecoder {
   // the one configuration timed: +2.9 .. +3.5 % codewords/s, profiles/record_flags8.txt; off for every other code, rule
   // and precision, where the key selects it)
   bool opt_flags8_ = false;
+  // "vn_bundles": the record form of the variable-node launch walks the kept list in the order of build_vn_bundles
+  // (graph_tables.h): the list entries the waves of a workgroup sum in the same step share rows, so a row's record crosses
+  // the path from the Infinity Cache once for them.  The tables are built for kVnBundleW entries per bundle -- a workgroup's
+  // waves when a slice is a whole tile -- and a launch with more slices per tile finds its narrower bundles inside them.
+  // Another order of independent sums: results do not depend on it.  (default: on where "vn_records" is -- plain Minsumf32 on
+  // DVB-S2 normal frames at rate 1/2, the one configuration timed: +5.0 % codewords/s, profiles/vn_bundles.txt; off for every
+  // other code, rule and precision, where the key selects it)
+  bool opt_vn_bundles_ = false;
+  static constexpr uint32_t kVnBundleW = kStreamBlock / 64;
+  uint32_t vn_bundle_saved_[kVnBundleW + 1] = {};  // [w]: thousandths of the record fetches spared at bundle width w
+  std::atomic<bool> last_vn_bundles_{false};
+  std::atomic<uint32_t> last_vn_bundle_saved_{0};
   std::atomic<uint32_t> last_record_flag_bytes_{0};
   std::atomic<bool> last_vn_records_{false};  // (written by every group's run_group: with "lane_threads" from two host threads)
   uint32_t rec_w_ = 0;
@@ -300,7 +318,9 @@ class DeviceDecoder {
   DeviceBuffer d_src_block_;    // depuncture map: source block of every pattern block, -1 = punctured
   DeviceBuffer d_edge_aux_, d_keep_var_, d_keep_ptr_, d_keep_edge_, d_free_var_, d_free_ptr_, d_free_edge_;  // LfreeTables
   DeviceBuffer d_edge_peer_, d_free_rs_, d_keep_pos_;                                                         // RowRecordTables
-  DeviceBuffer d_keep_rs_;                                                                                    // KeepRsTable
+  // KeepRsTable, and behind it in the same allocation the VnBundleTables: keep_rs, list_var, list_ptr at these word offsets
+  DeviceBuffer d_keep_rs_;
+  uint32_t bundle_rs_at_ = 0, bundle_var_at_ = 0, bundle_ptr_at_ = 0;  // (bundle_rs_at_ 0: no bundled tables)
   // Two execution lanes (workspace + stream): groups alternate between them, so the idle gaps
   // between one lane's short launches (layered schedule: one per dependency level) are filled by
   // the other's, and the host entry's PCIe copies overlap the other lane's decode.

@@ -127,13 +127,34 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
       ok = up(rr.keep_pos, &d->d_keep_pos_) && up(rr.peer, &d->d_edge_peer_) && up(rr.free_rs, &d->d_free_rs_);
       d->rec_ready_ = ok;
       const KeepRsTable kr = (ok && rr.flag_bits == 16) ? build_keep_rs(g, lf) : KeepRsTable();
-      if (kr.ready) ok = up(kr.rs, &d->d_keep_rs_);
+      if (kr.ready) {
+        // "vn_bundles": the same list in bundles behind keep_rs, in one upload, and what each bundle width a launch can have
+        // is worth
+        const VnBundleTables vb = build_vn_bundles(lf.n_keep, lf.keep_ptr, lf.keep_var, kr.rs, kVnBundleW);
+        std::vector<uint32_t> words = kr.rs;
+        auto append = [&](const std::vector<uint32_t> &v) {
+          const uint32_t at = static_cast<uint32_t>(words.size());
+          words.insert(words.end(), v.begin(), v.end());
+          return at;
+        };
+        d->bundle_rs_at_ = append(vb.keep_rs);
+        d->bundle_var_at_ = append(vb.list_var);
+        d->bundle_ptr_at_ = append(vb.list_ptr);
+        ok = up(words, &d->d_keep_rs_);
+        for (uint32_t w = 2; w <= kVnBundleW; w++) {
+          uint64_t fetches = 0, distinct = 0;
+          count_vn_bundle_fetches(lf.n_keep, vb.list_ptr, vb.keep_rs, w, &fetches, &distinct);
+          d->vn_bundle_saved_[w] = fetches ? static_cast<uint32_t>((fetches - distinct) * 1000 / fetches) : 0;
+        }
+      }
       // the default: on for the one configuration measured to pay by the project's bar (profiles/vn_records.txt), plain
       // Minsumf32 on DVB-S2 normal frames at rate 1/2; everything else takes it with the key
       d->opt_vn_records_ = kr.ready && ok && !impl.f64 && impl.correction == Correction::None && is_dvbs2_half_rate_normal(g);
       // "flags8", the byte form of those records' flags: the same rule and the same one configuration
       // (profiles/record_flags8.txt); everything else with rows of at most 7 edges takes it with the key
       d->opt_flags8_ = d->opt_vn_records_;
+      // "vn_bundles", the kept list in bundles: the same one configuration (profiles/vn_bundles.txt)
+      d->opt_vn_bundles_ = d->opt_vn_records_ && d->bundle_rs_at_ != 0;
     }
   }
   if (ok && flooding_minsum && !impl.f64) {
@@ -226,6 +247,8 @@ bool DeviceDecoder::set_option(const std::string &key, int64_t value) {
     opt_vn_records_ = v != 0;
   else if (key == "flags8")
     opt_flags8_ = v != 0;
+  else if (key == "vn_bundles")
+    opt_vn_bundles_ = v != 0;
   else if (key == "rec_long")
     opt_rec_long_ = v != 0;
   else if (key == "compact")

@@ -157,6 +157,120 @@ inline KeepRsTable build_keep_rs(const SparseMatrix::Csr &g, const LfreeTables &
   return t;
 }
 
+// The kept list in BUNDLES ("vn_bundles", run_group.hip.h): the same entries in another order.  In vn_kernel the waves of a
+// workgroup that work on the same codewords sum, at every step of their loops, W consecutive list entries that start at a
+// multiple of W (W = waves per workgroup / slices per tile, make_tiling); a row's record that two of them want at that step
+// is fetched from beyond the L2 once.  Every entry is a sum of its own, so the order of the list is free: variables that
+// share rows are put into the same aligned bundle of W entries.
+//   * Greedy: the seed of a bundle is the first entry not yet placed; the bundle grows by the unplaced entry of the seed's
+//     degree that shares the most rows with the entries already in it (ties: the earliest in the list); where none shares a
+//     row, by the next unplaced entry of that degree, and where that degree has run out, by the next unplaced entry of any.
+//     Equal degrees inside a bundle: the waves of a workgroup issue the same number of loads per step.
+//   * An entry keeps its variable, its edges and their cols[v] order: the sums do not change.
+//   * Deterministic; W <= 1 returns the list as it is.
+// fetches / distinct: record fetches of one pass over the list (its edges), and the distinct rows per bundle, summed -- what
+// is left of them when every coincident request inside a bundle is served once (count_vn_bundle_fetches: the same count of
+// any list, for any W).
+struct VnBundleTables {
+  std::vector<uint32_t> list_var, list_ptr{0}, keep_rs;  // keep_rs padded by kTablePad words, as build_keep_rs pads it
+  uint64_t fetches = 0, distinct = 0;
+};
+inline void count_vn_bundle_fetches(uint32_t n_keep, const std::vector<uint32_t> &list_ptr, const std::vector<uint32_t> &keep_rs,
+                                    uint32_t W, uint64_t *fetches, uint64_t *distinct) {
+  *fetches = 0;
+  *distinct = 0;
+  std::vector<uint32_t> rows;
+  for (uint32_t i0 = 0; i0 < n_keep; i0 += std::max<uint32_t>(W, 1)) {
+    const uint32_t i1 = std::min<uint64_t>(n_keep, uint64_t(i0) + std::max<uint32_t>(W, 1));
+    rows.clear();
+    for (uint32_t j = list_ptr[i0]; j < list_ptr[i1]; j++) rows.push_back(keep_rs[j] >> 6);
+    *fetches += rows.size();
+    std::sort(rows.begin(), rows.end());
+    *distinct += static_cast<uint64_t>(std::unique(rows.begin(), rows.end()) - rows.begin());
+  }
+}
+inline VnBundleTables build_vn_bundles(uint32_t n_keep, const std::vector<uint32_t> &keep_ptr, const std::vector<uint32_t> &keep_var,
+                                       const std::vector<uint32_t> &keep_rs, uint32_t W) {
+  VnBundleTables t;
+  std::vector<uint32_t> order;  // new position -> old position
+  order.reserve(n_keep);
+  if (W <= 1) {
+    for (uint32_t i = 0; i < n_keep; i++) order.push_back(i);
+  } else {
+    auto degree = [&](uint32_t i) { return keep_ptr[i + 1] - keep_ptr[i]; };
+    // row -> the entries on it (CSR over the rows the list touches), entries in list order
+    uint32_t n_rows = 0;
+    for (uint32_t j = 0; j < keep_ptr[n_keep]; j++) n_rows = std::max(n_rows, (keep_rs[j] >> 6) + 1);
+    std::vector<uint32_t> row_ptr(size_t(n_rows) + 1, 0), row_entry(keep_ptr[n_keep]);
+    for (uint32_t j = 0; j < keep_ptr[n_keep]; j++) row_ptr[(keep_rs[j] >> 6) + 1]++;
+    for (uint32_t r = 0; r < n_rows; r++) row_ptr[r + 1] += row_ptr[r];
+    {
+      std::vector<uint32_t> fill(row_ptr.begin(), row_ptr.end() - 1);
+      for (uint32_t i = 0; i < n_keep; i++)
+        for (uint32_t j = keep_ptr[i]; j < keep_ptr[i + 1]; j++) row_entry[fill[keep_rs[j] >> 6]++] = i;
+    }
+    std::vector<uint8_t> placed(n_keep, 0), row_in(n_rows, 0);
+    std::vector<uint32_t> shared(n_keep, 0), touched, bundle_rows;
+    uint32_t max_deg = 0;
+    for (uint32_t i = 0; i < n_keep; i++) max_deg = std::max(max_deg, degree(i));
+    std::vector<uint32_t> next_of(size_t(max_deg) + 1, 0);  // per degree: no unplaced entry of it lies before this position
+    uint32_t next_any = 0;
+    auto place = [&](uint32_t i) {
+      placed[i] = 1;
+      order.push_back(i);
+      // the rows the bundle gains: every unplaced entry on them shares one more row with the bundle
+      for (uint32_t j = keep_ptr[i]; j < keep_ptr[i + 1]; j++) {
+        const uint32_t r = keep_rs[j] >> 6;
+        if (row_in[r]) continue;
+        row_in[r] = 1;
+        bundle_rows.push_back(r);
+        for (uint32_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
+          const uint32_t c = row_entry[k];
+          if (placed[c]) continue;
+          if (shared[c]++ == 0) touched.push_back(c);
+        }
+      }
+    };
+    while (order.size() < n_keep) {
+      while (placed[next_any]) next_any++;
+      const uint32_t seed = next_any, d = degree(seed);
+      place(seed);
+      for (uint32_t k = 1; k < W && order.size() < n_keep; k++) {
+        uint32_t best = 0xFFFFFFFFu, best_shared = 0;
+        for (uint32_t c : touched)
+          if (!placed[c] && degree(c) == d && (shared[c] > best_shared || (shared[c] == best_shared && c < best))) {
+            best = c;
+            best_shared = shared[c];
+          }
+        if (best == 0xFFFFFFFFu) {
+          uint32_t &nd = next_of[d];
+          while (nd < n_keep && (placed[nd] || degree(nd) != d)) nd++;
+          best = nd;
+        }
+        if (best >= n_keep) {
+          while (placed[next_any]) next_any++;
+          best = next_any;
+        }
+        place(best);
+      }
+      for (uint32_t c : touched) shared[c] = 0;
+      for (uint32_t r : bundle_rows) row_in[r] = 0;
+      touched.clear();
+      bundle_rows.clear();
+    }
+  }
+  t.list_var.reserve(n_keep);
+  t.keep_rs.reserve(size_t(keep_ptr[n_keep]) + kTablePad);
+  for (uint32_t i : order) {
+    t.list_var.push_back(keep_var[i]);
+    t.keep_rs.insert(t.keep_rs.end(), keep_rs.begin() + keep_ptr[i], keep_rs.begin() + keep_ptr[i + 1]);
+    t.list_ptr.push_back(static_cast<uint32_t>(t.keep_rs.size()));
+  }
+  count_vn_bundle_fetches(n_keep, t.list_ptr, t.keep_rs, W, &t.fetches, &t.distinct);
+  t.keep_rs.resize(t.keep_rs.size() + kTablePad, 0);
+  return t;
+}
+
 // Sliced-ELLPACK tables of the small-batch path (latency.hip.h): rows in the order of their first variable, 64 to a slice,
 // slot-major inside a slice: edge (position p, slot j) -> id rslice_ptr[p / 64] + j * 64 + p % 64 (messages and `col`
 // share it).  ready: rows of at most 64 edges, at least one row, and edge ids within 2^30.

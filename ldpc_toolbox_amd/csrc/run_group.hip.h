@@ -148,6 +148,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     // stores no per-edge messages (vn_kernel's record form); with 16-bit flags only
     const bool vn_records = records && w.rec_flags[0] != nullptr && d_keep_rs_ && opt_vn_records_;
     last_vn_records_.store(vn_records, std::memory_order_relaxed);
+    bool vn_bundles = false;  // (decided below, where the kept list's tiling is known)
     const bool quiet = records && opt_rec_quiet_;
     if (quiet) {
       st.slice_state = w.slice_state;
@@ -172,6 +173,20 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       vn_free_t = make_tiling(G, tile, 64 * vec, n_free_, stream_block, wv);
       vn_event_t = make_tiling(G, tile, 64 * vec, n_free_, stream_block, 16 * 1024);
     }
+    // "vn_bundles": the record form walks the kept list in bundles (graph_tables.h, build_vn_bundles).  The message form and the
+    // event block keep g_keep; post_rows_keep_ is about variable numbers, not list positions.
+    dev::Graph g_bundle = g_keep;
+    uint32_t bundle_saved = 0;
+    if (vn_records && opt_vn_bundles_ && bundle_rs_at_ != 0) {
+      vn_bundles = true;
+      g_bundle.list_var = d_keep_rs_.get<uint32_t>() + bundle_var_at_;
+      g_bundle.list_ptr = d_keep_rs_.get<uint32_t>() + bundle_ptr_at_;
+      // the waves of a workgroup that see the same codewords: they sum an aligned run of this many list entries per step
+      const uint32_t bundle_w = std::max<uint32_t>(1, (stream_block / 64) / vn_keep_t.sched.slices_per_tile);
+      bundle_saved = vn_bundle_saved_[std::min(bundle_w, kVnBundleW)];
+    }
+    last_vn_bundles_.store(vn_bundles, std::memory_order_relaxed);
+    last_vn_bundle_saved_.store(bundle_saved, std::memory_order_relaxed);
     // a paced host (run_any) sees the group's running count: once the first codewords have converged, every iteration
     // ends with a checkpoint (the device still decides whether re-packing pays)
     const bool adaptive = opt_compact_ && poll.flag != nullptr && poll.throttle && !opt_compact_every_;
@@ -206,7 +221,8 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       // almost always found nothing: 4.4 us + a 5.7 us dispatch gap per iteration)
       if (vn_records) {
         const bool event = quiet && it > 1 && opt_vn_event_;
-        launch.vn_rec(vec, vn_keep_t, g_keep, st, chan, rbuf[it & 1], d_keep_rs_.get<uint32_t>(), post,
+        launch.vn_rec(vec, vn_keep_t, vn_bundles ? g_bundle : g_keep, st, chan, rbuf[it & 1],
+                      d_keep_rs_.get<uint32_t>() + (vn_bundles ? bundle_rs_at_ : 0u), post,
                       first ? nullptr : unsat_out, unsat[(it + 1) & 1], static_cast<int32_t>(it) - 1, d_free_var_.get<uint32_t>(),
                       d_free_rs_.get<uint32_t>(), event ? &rbuf[(it - 1) & 1] : nullptr, n_free_);
         if (quiet && it > 1 && !event)
