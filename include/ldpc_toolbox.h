@@ -204,7 +204,9 @@ int32_t ldpc_toolbox_decoder_syndrome_device(void *decoder, const uint8_t *bits,
  * family, 3 or 4, whatever the width), "last_vn_records" (1: the last decode call's variable-node launches read the row
  * records, the "vn_records" form; 0: per-edge messages), "last_vn_bundles" (1: those launches walked the kept variables in
  * bundles, the "vn_bundles" order), "vn_bundle_saved_permille" (what that order spares in the last decode call: thousandths
- * of the variable-node launch's record fetches that coincide inside a workgroup's step; 0 when off), "flags8" (the tunable
+ * of the variable-node launch's record fetches that coincide inside a workgroup's step; 0 when off), "last_vn_chains" (1:
+ * they walked that order in chains, "vn_chains": a record two consecutive entries of a wave share stays in its registers),
+ * "vn_chain_saved_permille" (thousandths of the record fetches the chained walk does not issue; 0 when off), "flags8" (the tunable
  * below, as set), "last_record_flag_bytes"
  * (bytes of a record's flags word in memory in the last decode call: 1 with "flags8" on rows of at most 7 edges, else 2, 4
  * or 8 = "record_flag_bits" / 8; 0: that call kept no flooding row records), "minsum_correction" (0: none, 1: normalized min-sum,
@@ -212,8 +214,8 @@ int32_t ldpc_toolbox_decoder_syndrome_device(void *decoder, const uint8_t *bits,
  * 8 * beta; 0 for every other name).  returns 0 or -1 (unknown key). */
 int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value);
 /* Tunables: "group_size" (codewords decoded together; 0 = automatic), "profiling" (0/1:
- * bracket the check/variable/layer launches with hipEvents), and 29 launch / execution choices -- "waves", "vec", "tile",
- * "lfree", "records", "rec_run", "rec_quiet", "rec_long", "vn_event", "vn_records", "vn_bundles", "flags8", "staged_minsum", "cn_reg", "hl_reg", "hl_records",
+ * bracket the check/variable/layer launches with hipEvents), and 31 launch / execution choices -- "waves", "vec", "tile",
+ * "lfree", "records", "rec_run", "rec_quiet", "rec_long", "vn_event", "vn_records", "vn_bundles", "vn_chains", "vn_chain_len", "flags8", "staged_minsum", "cn_reg", "hl_reg", "hl_records",
  * "serial_levels", "latency", "latency_edge", "compact", "compact_first", "compact_every", "lanes", "lane_threads",
  * "lane_pace", "lead", "poll", "throttle", "pooling" (ldpc_toolbox_amd/csrc/device_decoder.h says what each selects; results never
  * depend on them: each chooses between forms the test suite compares bit for bit).  "throttle" (0/1, default 0):

@@ -777,6 +777,10 @@ int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value)
     *value = d.last_vn_bundles();
   else if (k == "vn_bundle_saved_permille")
     *value = d.vn_bundle_saved_permille();
+  else if (k == "last_vn_chains")
+    *value = d.last_vn_chains();
+  else if (k == "vn_chain_saved_permille")
+    *value = d.vn_chain_saved_permille();
   else if (k == "flags8")
     *value = d.flags8();
   else if (k == "last_record_flag_bytes")

@@ -75,6 +75,11 @@ class DeviceDecoder {
   // fetches, at that call's bundle width (graph_tables.h, count_vn_bundle_fetches); 0 when off
   uint32_t last_vn_bundles() const { return last_vn_bundles_.load(std::memory_order_relaxed) ? 1 : 0; }
   uint32_t vn_bundle_saved_permille() const { return last_vn_bundle_saved_.load(std::memory_order_relaxed); }
+  // whether they walked it in chains ("vn_chains": the bundled walk with a record carried from entry to entry), and the
+  // loads of records the chains spare, carried ones and coincident ones, in thousandths of the list's fetches
+  // (graph_tables.h, count_vn_chain_fetches); 0 when off
+  uint32_t last_vn_chains() const { return last_vn_chains_.load(std::memory_order_relaxed) ? 1 : 0; }
+  uint32_t vn_chain_saved_permille() const { return last_vn_chain_saved_.load(std::memory_order_relaxed); }
 
   // codewords per group (rounded up to the wave tile).  0 = automatic.
   void set_group_size(size_t g) { group_pref_ = g; }
@@ -84,14 +89,16 @@ class DeviceDecoder {
   void set_min_group(size_t g) { min_group_ = g; }
   // codewords per group a call of `batch` codewords is cut into (the set value, else a default that grows for small graphs)
   size_t preferred_group(size_t batch) const { return pick_group(batch); }
-  // The 29 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
+  // The 31 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
   // percent are constants now, see kStreamBlock ... below).  Results never depend on any of them; each selects between
   // forms that tests/ compare bit for bit.  returns false for an unknown key.
   //   which kernels run   "lfree" (0: plain flooding min-sum kernels), "records" (0 / 1 / 2: per-edge messages / row records
   //                       where the graph suits them / wherever possible), "rec_quiet" (0: L-free posteriors stored every
   //                       iteration), "vn_event" (0: the first convergences' rebuild as a launch of its own), "vn_records" (0 / 1:
   //                       the variable nodes summed from per-edge messages / from the row records, 16-bit flags only), "vn_bundles" (0 / 1: that
-  //                       form's kept list in variable order / in bundles of the variables a workgroup sums together), "flags8" (0 / 1: the
+  //                       form's kept list in variable order / in bundles of the variables a workgroup sums together), "vn_chains" (0 / 1: the
+  //                       bundled list walked entry by entry / in chains whose shared record stays in registers; "vn_chain_len":
+  //                       4, 8 or 16 entries per chain), "flags8" (0 / 1: the
   //                       16-bit flags of rows of at most 7 edges stored as half-words / as bytes), "rec_long"
   //                       (1: the record kernel's long-row variant whatever the graph), "staged_minsum" (1: Minsum through
   //                       the generic LDS-staged kernel), "cn_reg" / "hl_reg" / "hl_records" (0: the LDS-staged / two-pass /
@@ -237,6 +244,23 @@ class DeviceDecoder {
   uint32_t vn_bundle_saved_[kVnBundleW + 1] = {};  // [w]: thousandths of the record fetches spared at bundle width w
   std::atomic<bool> last_vn_bundles_{false};
   std::atomic<uint32_t> last_vn_bundle_saved_{0};
+  // "vn_chains": with "vn_bundles", the launch walks the kept list in the order of build_vn_chains (graph_tables.h): a wave
+  // sums kVnChainLens[...] = "vn_chain_len" entries one after the other, and where two of them share a row the second takes
+  // the row's record from the wave's registers.  Another order of independent sums: results do not depend on it.
+  // (default: on where "vn_bundles" is -- plain Minsumf32 on DVB-S2 normal frames at rate 1/2, the one configuration timed,
+  // with chains of 8: profiles/vn_chains.txt; off for every other code, rule and precision, where the key selects it)
+  // (The tables of all three lengths are built and uploaded at create, for every graph that gets bundled tables: the keys may
+  // change between calls and a call allocates nothing -- the chained lists lie behind the bundled ones in d_keep_rs_.  On
+  // DVB-S2 1/2, the largest built-in graph: 27 ms of create and 0.9 MB per length.)
+  bool opt_vn_chains_ = false;
+  uint32_t opt_vn_chain_len_ = 8;
+  static constexpr uint32_t kVnChainLens[3] = {4, 8, 16};
+  struct VnChainAt {
+    uint32_t rs_at = 0, var_at = 0, ptr_at = 0, n_blocks = 0;  // word offsets in d_keep_rs_ (rs_at 0: no such tables)
+    uint32_t saved = 0, saved_alone = 0;  // thousandths of the fetches spared: with kVnBundleW step-mates; by the carries alone
+  } vn_chain_at_[3];
+  std::atomic<bool> last_vn_chains_{false};
+  std::atomic<uint32_t> last_vn_chain_saved_{0};
   std::atomic<uint32_t> last_record_flag_bytes_{0};
   std::atomic<bool> last_vn_records_{false};  // (written by every group's run_group: with "lane_threads" from two host threads)
   uint32_t rec_w_ = 0;
@@ -319,6 +343,7 @@ class DeviceDecoder {
   DeviceBuffer d_edge_aux_, d_keep_var_, d_keep_ptr_, d_keep_edge_, d_free_var_, d_free_ptr_, d_free_edge_;  // LfreeTables
   DeviceBuffer d_edge_peer_, d_free_rs_, d_keep_pos_;                                                         // RowRecordTables
   // KeepRsTable, and behind it in the same allocation the VnBundleTables: keep_rs, list_var, list_ptr at these word offsets
+  // (and behind those the VnChainTables of every chain length: vn_chain_at_)
   DeviceBuffer d_keep_rs_;
   uint32_t bundle_rs_at_ = 0, bundle_var_at_ = 0, bundle_ptr_at_ = 0;  // (bundle_rs_at_ 0: no bundled tables)
   // Two execution lanes (workspace + stream): groups alternate between them, so the idle gaps

@@ -140,6 +140,17 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
         d->bundle_rs_at_ = append(vb.keep_rs);
         d->bundle_var_at_ = append(vb.list_var);
         d->bundle_ptr_at_ = append(vb.list_ptr);
+        // "vn_chains": the same list in chains of every length a launch can ask for, behind the bundles
+        for (uint32_t c = 0; c < 3; c++) {
+          const VnChainTables vc = build_vn_chains(lf.n_keep, lf.keep_ptr, lf.keep_var, kr.rs, kVnBundleW, kVnChainLens[c]);
+          VnChainAt &at = d->vn_chain_at_[c];
+          at.rs_at = append(vc.keep_rs);
+          at.var_at = append(vc.list_var);
+          at.ptr_at = append(vc.list_ptr);
+          at.n_blocks = vc.n_blocks;
+          at.saved = vc.fetches ? static_cast<uint32_t>((vc.fetches - vc.issued) * 1000 / vc.fetches) : 0;
+          at.saved_alone = vc.fetches ? static_cast<uint32_t>(vc.carried * 1000 / vc.fetches) : 0;
+        }
         ok = up(words, &d->d_keep_rs_);
         for (uint32_t w = 2; w <= kVnBundleW; w++) {
           uint64_t fetches = 0, distinct = 0;
@@ -155,6 +166,8 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
       d->opt_flags8_ = d->opt_vn_records_;
       // "vn_bundles", the kept list in bundles: the same one configuration (profiles/vn_bundles.txt)
       d->opt_vn_bundles_ = d->opt_vn_records_ && d->bundle_rs_at_ != 0;
+      // "vn_chains", the bundled list walked in chains: the same one configuration (profiles/vn_chains.txt)
+      d->opt_vn_chains_ = d->opt_vn_bundles_ && d->vn_chain_at_[0].rs_at != 0;
     }
   }
   if (ok && flooding_minsum && !impl.f64) {
@@ -249,6 +262,12 @@ bool DeviceDecoder::set_option(const std::string &key, int64_t value) {
     opt_flags8_ = v != 0;
   else if (key == "vn_bundles")
     opt_vn_bundles_ = v != 0;
+  else if (key == "vn_chains")
+    opt_vn_chains_ = v != 0;
+  else if (key == "vn_chain_len") {
+    if (v != kVnChainLens[0] && v != kVnChainLens[1] && v != kVnChainLens[2]) return false;
+    opt_vn_chain_len_ = v;
+  }
   else if (key == "rec_long")
     opt_rec_long_ = v != 0;
   else if (key == "compact")

@@ -271,6 +271,187 @@ inline VnBundleTables build_vn_bundles(uint32_t n_keep, const std::vector<uint32
   return t;
 }
 
+// The kept list in CHAINS ("vn_chains", run_group.hip.h): the same entries in blocks of W * L.  Block position (t, w), step
+// t < L and wave w < W, is list index block * W * L + t * W + w; a wave walks t = 0 .. L - 1 of its w, and where two
+// consecutive entries of that walk share a row, the second takes the row's record from the wave's registers (the CARRY)
+// and not from memory: a variable of a chain costs one fetch less, whatever the other waves do and whenever they do it.
+// A tree of n variables shares at most n - 1 rows (girth >= 6), so a chain is as good as any cluster of its size.
+//   * The order is a walk over the graph "two entries share a row": a path starts at the unplaced entry with the fewest
+//     unplaced neighbours and steps to the unplaced neighbour with the fewest unplaced neighbours (ties: the earliest in
+//     the list), until there is none.  The paths, one behind the other, are cut into runs of L: run number block * W + w
+//     is wave w's walk of that block.  (The last block holds the R < W * L entries left: wave w walks its t * W + w < R.)
+//   * keep_rs carries the two decisions in the bits its limits leave free (a row index is below kPeerSingle = 2^24):
+//     kChainFrom on an edge whose record is the carry, kChainLeave on the edge whose record the entry leaves in the carry
+//     for the wave's next entry.  Both on one edge: three entries in a row on the same check row, the carry stays.  Only an
+//     entry's first kChainEdges edges take part: the kernel has them in flight together, so the carry is read before it is
+//     replaced.  Never kChainFrom at t = 0, at most one kChainFrom and one kChainLeave per entry.
+//   * An entry keeps its variable, its edges and their cols[v] order: the sums do not change.
+//   * Deterministic; L <= 1 is build_vn_bundles(..., W): the same list, no flags.
+// fetches: the list's edges; carried: the edges marked kChainFrom; issued: the loads a pass really issues -- per step the
+// distinct rows among the W step-mates, each having dropped its carried row (count_vn_chain_fetches: of any such list).
+enum : uint32_t { kChainFrom = 0x80000000u, kChainLeave = 0x40000000u, kChainRsMask = 0x3FFFFFFFu, kChainEdges = 8 };
+struct VnChainTables {
+  std::vector<uint32_t> list_var, list_ptr{0}, keep_rs;  // keep_rs padded by kTablePad words
+  uint32_t n_blocks = 0;
+  uint64_t fetches = 0, carried = 0, issued = 0;
+};
+inline void count_vn_chain_fetches(uint32_t n_keep, const std::vector<uint32_t> &list_ptr, const std::vector<uint32_t> &keep_rs,
+                                   uint32_t W, uint32_t L, uint64_t *fetches, uint64_t *carried, uint64_t *issued) {
+  *fetches = *carried = *issued = 0;
+  W = std::max<uint32_t>(W, 1);
+  (void)L;  // (a step's mates are W consecutive entries from a multiple of W, in a whole block and in the last one)
+  std::vector<uint32_t> rows;
+  for (uint32_t i0 = 0; i0 < n_keep; i0 += W) {
+    const uint32_t i1 = std::min<uint64_t>(n_keep, uint64_t(i0) + W);
+    rows.clear();
+    for (uint32_t j = list_ptr[i0]; j < list_ptr[i1]; j++) {
+      if (keep_rs[j] & kChainFrom)
+        *carried += 1;
+      else
+        rows.push_back((keep_rs[j] & kChainRsMask) >> 6);
+    }
+    *fetches += list_ptr[i1] - list_ptr[i0];
+    std::sort(rows.begin(), rows.end());
+    *issued += static_cast<uint64_t>(std::unique(rows.begin(), rows.end()) - rows.begin());
+  }
+}
+inline VnChainTables build_vn_chains(uint32_t n_keep, const std::vector<uint32_t> &keep_ptr, const std::vector<uint32_t> &keep_var,
+                                     const std::vector<uint32_t> &keep_rs, uint32_t W, uint32_t L) {
+  VnChainTables t;
+  W = std::max<uint32_t>(W, 1);
+  if (L <= 1) {
+    VnBundleTables b = build_vn_bundles(n_keep, keep_ptr, keep_var, keep_rs, W);
+    t.list_var = std::move(b.list_var);
+    t.list_ptr = std::move(b.list_ptr);
+    t.keep_rs = std::move(b.keep_rs);
+    t.n_blocks = (n_keep + W - 1) / W;
+    t.fetches = b.fetches;
+    t.issued = b.distinct;
+    return t;
+  }
+  const uint32_t kNone = 0xFFFFFFFFu;
+  auto chain_deg = [&](uint32_t i) { return std::min<uint32_t>(keep_ptr[i + 1] - keep_ptr[i], kChainEdges); };
+  // row -> the entries that have it among their first kChainEdges edges, in list order
+  uint32_t n_rows = 0;
+  for (uint32_t j = 0; j < keep_ptr[n_keep]; j++) n_rows = std::max(n_rows, (keep_rs[j] >> 6) + 1);
+  std::vector<uint32_t> row_ptr(size_t(n_rows) + 1, 0);
+  for (uint32_t i = 0; i < n_keep; i++)
+    for (uint32_t p = 0; p < chain_deg(i); p++) row_ptr[(keep_rs[keep_ptr[i] + p] >> 6) + 1]++;
+  for (uint32_t r = 0; r < n_rows; r++) row_ptr[r + 1] += row_ptr[r];
+  std::vector<uint32_t> row_entry(row_ptr[n_rows]);
+  {
+    std::vector<uint32_t> fill(row_ptr.begin(), row_ptr.end() - 1);
+    for (uint32_t i = 0; i < n_keep; i++)
+      for (uint32_t p = 0; p < chain_deg(i); p++) row_entry[fill[keep_rs[keep_ptr[i] + p] >> 6]++] = i;
+  }
+  // unplaced neighbours of every entry (with multiplicity where two entries share more than one row), and the unplaced
+  // entries ordered by that count, then by list position
+  std::vector<uint32_t> free_nb(n_keep, 0);
+  for (uint32_t i = 0; i < n_keep; i++)
+    for (uint32_t p = 0; p < chain_deg(i); p++) {
+      const uint32_t r = keep_rs[keep_ptr[i] + p] >> 6;
+      free_nb[i] += row_ptr[r + 1] - row_ptr[r] - 1;
+    }
+  auto key = [&](uint32_t i) { return (uint64_t(free_nb[i]) << 32) | i; };
+  std::vector<uint64_t> heap;  // min-heap with lazy deletion: an element counts while it matches key() of an unplaced entry
+  heap.reserve(size_t(n_keep) * 2);
+  for (uint32_t i = 0; i < n_keep; i++) heap.push_back(key(i));
+  auto later = [](uint64_t a, uint64_t b) { return a > b; };
+  std::make_heap(heap.begin(), heap.end(), later);
+  std::vector<uint8_t> placed(n_keep, 0);
+  std::vector<uint32_t> seq, link;  // the walk; link[k]: the row seq[k] shares with seq[k - 1] as its chain link, or kNone
+  seq.reserve(n_keep);
+  link.reserve(n_keep);
+  auto place = [&](uint32_t i, uint32_t via) {
+    placed[i] = 1;
+    seq.push_back(i);
+    link.push_back(via);
+    for (uint32_t p = 0; p < chain_deg(i); p++) {
+      const uint32_t r = keep_rs[keep_ptr[i] + p] >> 6;
+      for (uint32_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
+        const uint32_t c = row_entry[k];
+        if (placed[c]) continue;
+        free_nb[c]--;
+        heap.push_back(key(c));
+        std::push_heap(heap.begin(), heap.end(), later);
+      }
+    }
+  };
+  while (seq.size() < n_keep) {
+    uint32_t cur = kNone;
+    while (cur == kNone) {
+      const uint64_t top = heap.front();
+      std::pop_heap(heap.begin(), heap.end(), later);
+      heap.pop_back();
+      const uint32_t i = static_cast<uint32_t>(top);
+      if (!placed[i] && key(i) == top) cur = i;
+    }
+    place(cur, kNone);
+    for (;;) {
+      uint32_t best = kNone, best_row = kNone;
+      for (uint32_t p = 0; p < chain_deg(cur); p++) {
+        const uint32_t r = keep_rs[keep_ptr[cur] + p] >> 6;
+        for (uint32_t k = row_ptr[r]; k < row_ptr[r + 1]; k++) {
+          const uint32_t c = row_entry[k];
+          if (placed[c]) continue;
+          if (best == kNone || key(c) < key(best)) {
+            best = c;
+            best_row = r;
+          }
+        }
+      }
+      if (best == kNone) break;
+      place(best, best_row);
+      cur = best;
+    }
+  }
+  // the runs: run s = block * W + w takes the next len(s) entries of the walk
+  const uint32_t per_block = W * L;
+  t.n_blocks = (n_keep + per_block - 1) / per_block;
+  std::vector<uint32_t> order(n_keep, 0), from_row(n_keep, kNone), leave_row(n_keep, kNone);  // by new position
+  uint32_t k = 0;
+  for (uint32_t blk = 0; blk < t.n_blocks; blk++) {
+    const uint32_t base = blk * per_block, room = std::min(per_block, n_keep - base);
+    for (uint32_t w = 0; w < W && w < room; w++) {
+      const uint32_t len = (room - w + W - 1) / W;  // t with t * W + w < room
+      for (uint32_t s = 0; s < len; s++, k++) {
+        const uint32_t at = base + s * W + w;
+        order[at] = seq[k];
+        if (s > 0 && link[k] != kNone) {
+          from_row[at] = link[k];
+          leave_row[at - W] = link[k];
+        }
+      }
+    }
+  }
+  t.list_var.reserve(n_keep);
+  t.keep_rs.reserve(size_t(keep_ptr[n_keep]) + kTablePad);
+  for (uint32_t at = 0; at < n_keep; at++) {
+    const uint32_t i = order[at];
+    t.list_var.push_back(keep_var[i]);
+    bool from_set = false, leave_set = false;
+    for (uint32_t j = keep_ptr[i]; j < keep_ptr[i + 1]; j++) {
+      uint32_t word = keep_rs[j];
+      const uint32_t row = word >> 6;
+      if (j - keep_ptr[i] < kChainEdges) {
+        if (!from_set && row == from_row[at]) {
+          word |= kChainFrom;
+          from_set = true;
+        }
+        if (!leave_set && row == leave_row[at]) {
+          word |= kChainLeave;
+          leave_set = true;
+        }
+      }
+      t.keep_rs.push_back(word);
+    }
+    t.list_ptr.push_back(static_cast<uint32_t>(t.keep_rs.size()));
+  }
+  count_vn_chain_fetches(n_keep, t.list_ptr, t.keep_rs, W, L, &t.fetches, &t.carried, &t.issued);
+  t.keep_rs.resize(t.keep_rs.size() + kTablePad, 0);
+  return t;
+}
+
 // Sliced-ELLPACK tables of the small-batch path (latency.hip.h): rows in the order of their first variable, 64 to a slice,
 // slot-major inside a slice: edge (position p, slot j) -> id rslice_ptr[p / 64] + j * 64 + p % 64 (messages and `col`
 // share it).  ready: rows of at most 64 edges, at least one row, and edge ids within 2^30.

@@ -434,6 +434,69 @@ struct VnSource<R, K> {
   R rec;
   K keep_rs;
 };
+// ... or, CHAIN, those two and a third argument, `VnChain chain`: the kept list in CHAINS (graph_tables.h, build_vn_chains).
+// The list comes in blocks of width * len entries, block position (t, w) at index (block * len + t) * width + w.  The waves of
+// a slice form groups of `mates`: group g takes the blocks g, g + n_groups, ...; its wave m walks, in every block, the runs
+// w = m, m + mates, ... one after the other, each from t = 0 to len - 1.  Along a run the wave keeps ONE record in registers
+// (the carry, as memory holds it): an edge marked kChainFrom fetches no record of its own and takes its value from the carry,
+// at its own position of the sum; the record of the edge marked kChainLeave is copied into the carry once it has arrived.
+// Both marks are wave-uniform, and the tables never mark kChainFrom at t = 0: a run starts with whatever the carry holds and
+// never reads it.
+struct VnChain {
+  uint32_t len, width, mates, n_blocks, n_groups;
+};
+template <typename R, typename K, typename C>
+struct VnSource<R, K, C> {
+  R rec;
+  K keep_rs;
+  C chain;
+};
+// The carry: a record of the 16-bit family as memory holds it, its VEC flag words packed into one or two registers (the
+// compiler would keep a register per codeword) -- nine registers for an f32 pack of 4 with byte flags.
+template <typename Rec, typename T, int VEC, typename FW>
+struct VnCarry {
+  static_assert(VEC * sizeof(FW) <= 8, "the flag words of a lane fit two registers");
+  Pack<T, VEC> min1, min2;
+  uint32_t fl[2];
+  static __device__ __forceinline__ Pack<FW, VEC> &flags_of(RowRec<T, VEC, 3, uint16_t> &r) { return r.flip; }
+  static __device__ __forceinline__ Pack<FW, VEC> &flags_of(RowRec<T, VEC, 3, uint8_t> &r) { return r.fl; }
+  __device__ __forceinline__ void keep(Rec r) {
+    min1 = r.min1;
+    min2 = r.min2;
+    uint64_t bits = 0;
+#pragma unroll
+    for (int k = 0; k < VEC; k++) bits |= uint64_t(flags_of(r).v[k]) << (8 * sizeof(FW) * k);
+    fl[0] = uint32_t(bits);
+    fl[1] = uint32_t(bits >> 32);
+    asm("" : "+v"(fl[0]));
+    if constexpr (VEC * sizeof(FW) > 4) asm("" : "+v"(fl[1]));
+  }
+  __device__ __forceinline__ T value(uint32_t slot, int k) const {
+    Rec r;
+    r.min1 = min1;
+    r.min2 = min2;
+    const uint64_t bits = uint64_t(fl[0]) | (uint64_t(fl[1]) << 32);
+    flags_of(r).v[k] = FW(bits >> (8 * sizeof(FW) * k));
+    return r.value(slot, k);
+  }
+};
+struct VnChainWalk {
+  uint32_t blk, w, t, mate;
+  // the list index of the position, moved on to the next one that lies in the list; n_list: the walk is over
+  __device__ __forceinline__ uint32_t settle(const VnChain &c, uint32_t n_list) {
+    while (blk < c.n_blocks) {
+      const uint32_t i = (blk * c.len + t) * c.width + w;
+      if (t < c.len && i < n_list) return i;
+      t = 0;
+      w += c.mates;
+      if (w >= c.width) {
+        w = mate;
+        blk += c.n_groups;
+      }
+    }
+    return n_list;
+  }
+};
 // (Arguments of their own and not one struct: a pointer inside a struct is not `noalias` to the compiler, and a struct's
 // members are loaded apart from the arguments beside them -- either gives every instantiation other instructions,
 // profiles/vn_kernel_merge.txt.)
@@ -447,7 +510,7 @@ __global__ __launch_bounds__(256) void vn_kernel(
     Graph g, Sched sc, State st, const T *__restrict__ chan, SRC... src,
     T *__restrict__ post, const uint32_t *__restrict__ unsat_in, uint32_t *__restrict__ unsat_clear,
     int32_t latch_iteration, VnEventOf<T, EVF16, EVF8> ev = {}) {
-  constexpr bool REC = sizeof...(SRC) == 2;
+  constexpr bool REC = sizeof...(SRC) >= 2, CHAIN = sizeof...(SRC) == 3;
   const VnSource<const SRC &...> from{src...};  // (a view: references)
   static_assert(!REC || (LIST && EVF16 && (EVW == 0 || EVW == 3)), "from records: the kept list, the 16-bit family's records");
   uint32_t *__restrict__ n_active = st.n_active;
@@ -645,6 +708,13 @@ __global__ __launch_bounds__(256) void vn_kernel(
     const uint32_t rec_bytes = Rec::kRows * row_bytes;
     // (keep_rs is padded by kTablePad words: the block fetch of a variable's first U indices stays in bounds)
     uint32_t v = v_first, s0 = 0, s1 = 0, rs[U], var = v_first;
+    [[maybe_unused]] VnChainWalk walk{};
+    [[maybe_unused]] VnCarry<Rec, T, VEC, RecFlagWord<T, true, EVF8>> carry = {};
+    if constexpr (CHAIN) {
+      static_assert(U >= int(kChainEdges), "the marked edges of an entry are in flight together");
+      walk = VnChainWalk{v_first / from.chain.mates, v_first % from.chain.mates, 0u, v_first % from.chain.mates};
+      v = uniform(walk.settle(from.chain, n_cols));
+    }
     if (v < n_cols) {
       s0 = col_ptr[v];
       s1 = col_ptr[v + 1];
@@ -658,7 +728,11 @@ __global__ __launch_bounds__(256) void vn_kernel(
 #pragma unroll
       for (int k = 0; k < VEC; k++) sum[k] = -T(0.0);
       const Pack<T, VEC> ch = load_msg<T, VEC, NT>(chan + size_t(var) * G);
-      const uint32_t vn = v + waves_per_chunk;
+      uint32_t vn = v + waves_per_chunk;
+      if constexpr (CHAIN) {
+        walk.t++;
+        vn = uniform(walk.settle(from.chain, n_cols));
+      }
       uint32_t ns0 = 0, ns1 = 0, nvar = vn;
       if (vn < n_cols) {
         ns0 = col_ptr[vn];
@@ -674,7 +748,20 @@ __global__ __launch_bounds__(256) void vn_kernel(
           w[u] = 0;
           if (j0 + u < s1) {  // wave-uniform
             w[u] = (j0 == s0) ? rs[u] : keep_rs[j0 + u];
-            rv[u].load(b_rec, lane_off, (w[u] >> 6) * rec_bytes, row_bytes);
+            if constexpr (CHAIN) {
+              // (no branch around a load: the compiler then waits for each record where it is loaded.  The edge that takes
+              // the carry asks for its neighbour's record again instead, which the wave is fetching anyway, and drops what
+              // arrives; what that second request costs beyond the CU is in profiles/vn_chains.txt, section 6.
+              // Two properties of build_vn_chains' tables are relied on: a marked entry has a neighbour edge -- the kept
+              // list holds variables of degree 3 and more only (graph_tables.h, build_lfree_tables: degree 1 and 2 are
+              // L-free), so rs[1] is an edge of the same entry at u == 0 -- and the marks lie on an entry's first
+              // kChainEdges edges, the round j0 == s0.)
+              uint32_t row = w[u];
+              if (w[u] & kChainFrom) row = u == 0 ? ((j0 == s0) ? rs[1] : keep_rs[j0 + 1]) : w[u - 1];
+              rv[u].load(b_rec, lane_off, ((row & kChainRsMask) >> 6) * rec_bytes, row_bytes);
+            } else {
+              rv[u].load(b_rec, lane_off, (w[u] >> 6) * rec_bytes, row_bytes);
+            }
           }
         }
         if (j0 == s0) {
@@ -684,9 +771,22 @@ __global__ __launch_bounds__(256) void vn_kernel(
 #pragma unroll
         for (int u = 0; u < U; u++) {
           if (j0 + u < s1) {
+            if constexpr (CHAIN) {
+              if (w[u] & kChainFrom) {  // wave-uniform; nothing but arithmetic behind this branch
+#pragma unroll
+                for (int k = 0; k < VEC; k++) sum[k] = sum[k] + carry.value(w[u] & 63u, k);
+                continue;
+              }
+            }
 #pragma unroll
             for (int k = 0; k < VEC; k++) sum[k] = sum[k] + rv[u].value(w[u] & 63u, k);
           }
+        }
+        if constexpr (CHAIN) {
+          // (behind the sums: the carry has been read; an edge with both marks leaves the carry as it is)
+#pragma unroll
+          for (int u = 0; u < U; u++)
+            if (j0 + u < s1 && (w[u] & (kChainFrom | kChainLeave)) == kChainLeave) carry.keep(rv[u]);
         }
       }
       if (s0 == s1) {

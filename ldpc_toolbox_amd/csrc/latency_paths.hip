@@ -45,6 +45,8 @@ struct DeviceDecoder::SmallBatchCall {
     d.last_vn_records_.store(false, std::memory_order_relaxed);
     d.last_vn_bundles_.store(false, std::memory_order_relaxed);
     d.last_vn_bundle_saved_.store(0, std::memory_order_relaxed);
+    d.last_vn_chains_.store(false, std::memory_order_relaxed);
+    d.last_vn_chain_saved_.store(0, std::memory_order_relaxed);
     d.last_record_flag_bytes_.store(0, std::memory_order_relaxed);
   }
 

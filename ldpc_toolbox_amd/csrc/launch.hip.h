@@ -223,20 +223,41 @@ struct Launch {
   // "rec_quiet" off).
   // (eight records in flight and nontemporal channel loads: the headline gains 0.65 % over four in flight -- 98 against 57
   // VGPRs, 4 against 8 waves per SIMD -- and 0.35 % over cached channel loads, profiles/vn_records.txt section 1)
+  // chain non-null: g's list and keep_rs are the chained ones (graph_tables.h, build_vn_chains) and t is chain_tiling's
   void vn_rec(uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan,
               const Records &rec, const uint32_t *keep_rs, T *post, const uint32_t *unsat_in, uint32_t *unsat_clear,
-              int32_t latch_it, const uint32_t *free_var, const uint32_t *free_rs, const Records *ev_rec, uint32_t n_free) const {
+              int32_t latch_it, const uint32_t *free_var, const uint32_t *free_rs, const Records *ev_rec, uint32_t n_free,
+              const dev::VnChain *chain = nullptr) const {
     with_vec<T>(vec, [&](auto V) {
       with_bool(ev_rec != nullptr, [&](auto EV) {
         with_bool(rec.flags8, [&](auto F8) {
           constexpr bool kF8 = decltype(F8)::value;
           using RecIn = typename dev::RecRef<T, true, kF8>::in;
+          if (chain)
+            return vn_go<decltype(V)::value, true, true, decltype(EV)::value ? 3 : 0, true, kF8, RecIn, TableIn, dev::VnChain>(
+                t, g, st, chan, post, unsat_in, unsat_clear, latch_it, free_var, free_rs, ev_rec, n_free,
+                rec_ref<true, true, kF8>(rec), keep_rs, *chain);
           vn_go<decltype(V)::value, true, true, decltype(EV)::value ? 3 : 0, true, kF8, RecIn, TableIn>(
               t, g, st, chan, post, unsat_in, unsat_clear, latch_it, free_var, free_rs, ev_rec, n_free,
               rec_ref<true, true, kF8>(rec), keep_rs);
         });
       });
     });
+  }
+  // The chained launch's waves follow from the blocks: a slice's waves come in groups of `mates` -- the waves of a workgroup
+  // that see the same codewords, where the slice's waves divide into such groups, else 1 -- and a group walks whole blocks,
+  // so no more groups than blocks.  Fills chain->mates and chain->n_groups (len, width, n_blocks: the tables').
+  static Tiling chain_tiling(uint32_t G, uint32_t tile, uint32_t slice, uint32_t threads, uint32_t target_waves,
+                             dev::VnChain *chain) {
+    const uint32_t wpb = threads / 64, spt = std::max<uint32_t>(1, tile / slice);
+    uint32_t mates = (spt <= wpb && wpb % spt == 0) ? wpb / spt : 1;
+    mates = std::min(mates, chain->width);
+    if (chain->width % mates != 0) mates = 1;
+    Tiling t = make_tiling(G, tile, slice, std::max<uint32_t>(chain->n_blocks, 1) * mates, threads, target_waves);
+    if (t.sched.waves_per_chunk % mates != 0) mates = 1;
+    chain->mates = mates;
+    chain->n_groups = t.sched.waves_per_chunk / mates;
+    return t;
   }
 
   // layered

@@ -176,7 +176,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     // "vn_bundles": the record form walks the kept list in bundles (graph_tables.h, build_vn_bundles).  The message form and the
     // event block keep g_keep; post_rows_keep_ is about variable numbers, not list positions.
     dev::Graph g_bundle = g_keep;
-    uint32_t bundle_saved = 0;
+    uint32_t bundle_saved = 0, chain_rs_at = 0;
     if (vn_records && opt_vn_bundles_ && bundle_rs_at_ != 0) {
       vn_bundles = true;
       g_bundle.list_var = d_keep_rs_.get<uint32_t>() + bundle_var_at_;
@@ -187,6 +187,29 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     }
     last_vn_bundles_.store(vn_bundles, std::memory_order_relaxed);
     last_vn_bundle_saved_.store(bundle_saved, std::memory_order_relaxed);
+    // "vn_chains": the bundled walk in chains (graph_tables.h, build_vn_chains): the chained list and its keep_rs, and a launch
+    // whose waves follow from the list's blocks
+    dev::VnChain chain{};
+    Tiling vn_chain_t = vn_keep_t;
+    uint32_t chain_saved = 0;
+    bool vn_chains = false;
+    if (vn_bundles && opt_vn_chains_) {
+      const VnChainAt &at = vn_chain_at_[opt_vn_chain_len_ == kVnChainLens[0] ? 0 : (opt_vn_chain_len_ == kVnChainLens[1] ? 1 : 2)];
+      if (at.rs_at != 0) {
+        vn_chains = true;
+        chain.len = opt_vn_chain_len_;
+        chain.width = kVnBundleW;
+        chain.n_blocks = at.n_blocks;
+        vn_chain_t = Launch<T>::chain_tiling(G, tile, 64 * vec, stream_block, opt_waves_ ? opt_waves_ : kVnWaves, &chain);
+        vn_chain_t.sched.reverse = 1u;
+        g_bundle.list_var = d_keep_rs_.get<uint32_t>() + at.var_at;
+        g_bundle.list_ptr = d_keep_rs_.get<uint32_t>() + at.ptr_at;
+        chain_rs_at = at.rs_at;
+        chain_saved = chain.mates == kVnBundleW ? at.saved : at.saved_alone;
+      }
+    }
+    last_vn_chains_.store(vn_chains, std::memory_order_relaxed);
+    last_vn_chain_saved_.store(chain_saved, std::memory_order_relaxed);
     // a paced host (run_any) sees the group's running count: once the first codewords have converged, every iteration
     // ends with a checkpoint (the device still decides whether re-packing pays)
     const bool adaptive = opt_compact_ && poll.flag != nullptr && poll.throttle && !opt_compact_every_;
@@ -221,10 +244,10 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       // almost always found nothing: 4.4 us + a 5.7 us dispatch gap per iteration)
       if (vn_records) {
         const bool event = quiet && it > 1 && opt_vn_event_;
-        launch.vn_rec(vec, vn_keep_t, vn_bundles ? g_bundle : g_keep, st, chan, rbuf[it & 1],
-                      d_keep_rs_.get<uint32_t>() + (vn_bundles ? bundle_rs_at_ : 0u), post,
+        launch.vn_rec(vec, vn_chains ? vn_chain_t : vn_keep_t, vn_bundles ? g_bundle : g_keep, st, chan, rbuf[it & 1],
+                      d_keep_rs_.get<uint32_t>() + (vn_chains ? chain_rs_at : (vn_bundles ? bundle_rs_at_ : 0u)), post,
                       first ? nullptr : unsat_out, unsat[(it + 1) & 1], static_cast<int32_t>(it) - 1, d_free_var_.get<uint32_t>(),
-                      d_free_rs_.get<uint32_t>(), event ? &rbuf[(it - 1) & 1] : nullptr, n_free_);
+                      d_free_rs_.get<uint32_t>(), event ? &rbuf[(it - 1) & 1] : nullptr, n_free_, vn_chains ? &chain : nullptr);
         if (quiet && it > 1 && !event)
           launch.vn_free_rec(vec, vn_event_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[(it - 1) & 1], post,
                              static_cast<int32_t>(it) - 1);
