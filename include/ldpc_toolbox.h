@@ -209,13 +209,20 @@ int32_t ldpc_toolbox_decoder_syndrome_device(void *decoder, const uint8_t *bits,
  * "vn_chain_saved_permille" (thousandths of the record fetches the chained walk does not issue; 0 when off), "flags8" (the tunable
  * below, as set), "last_record_flag_bytes"
  * (bytes of a record's flags word in memory in the last decode call: 1 with "flags8" on rows of at most 7 edges, else 2, 4
- * or 8 = "record_flag_bits" / 8; 0: that call kept no flooding row records), "minsum_correction" (0: none, 1: normalized min-sum,
+ * or 8 = "record_flag_bits" / 8; 0: that call kept no flooding row records), "call_edges" (the tunable below, as set),
+ * "last_call_edges" (read-only bit mask: which of that tunable's shortcuts the last decode call took -- 1: the ingest launch
+ * stored the input once, with no copy in the posterior array; 2: the last hard-decision pack covered the rows the
+ * variable-node launch writes and the closing launch packed the other variables' decisions without storing their
+ * posteriors; 4: the final output launch read the packed decisions instead of posterior rows; 8: a re-packing checkpoint was
+ * enqueued as two launches behind its plan instead of four; 1, 2 and 4 only on the flooding row-record path of a call that
+ * asks for no posterior), "minsum_correction" (0: none, 1: normalized min-sum,
  * 2: offset min-sum), "minsum_correction_int" (the 8-bit min-sum names: the integer the kernels use, 16 * alpha or
  * 8 * beta; 0 for every other name).  returns 0 or -1 (unknown key). */
 int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value);
 /* Tunables: "group_size" (codewords decoded together; 0 = automatic), "profiling" (0/1:
- * bracket the check/variable/layer launches with hipEvents), and 31 launch / execution choices -- "waves", "vec", "tile",
- * "lfree", "records", "rec_run", "rec_quiet", "rec_long", "vn_event", "vn_records", "vn_bundles", "vn_chains", "vn_chain_len", "flags8", "staged_minsum", "cn_reg", "hl_reg", "hl_records",
+ * bracket the check/variable/layer launches with hipEvents), and 32 launch / execution choices -- "waves", "vec", "tile",
+ * "lfree", "records", "rec_run", "rec_quiet", "rec_long", "call_edges" (0/1, default 1: the launches around a call's iterations trimmed to what
+ * its result needs, see "last_call_edges" above; 0: as they were), "vn_event", "vn_records", "vn_bundles", "vn_chains", "vn_chain_len", "flags8", "staged_minsum", "cn_reg", "hl_reg", "hl_records",
  * "serial_levels", "latency", "latency_edge", "compact", "compact_first", "compact_every", "lanes", "lane_threads",
  * "lane_pace", "lead", "poll", "throttle", "pooling" (ldpc_toolbox_amd/csrc/device_decoder.h says what each selects; results never
  * depend on them: each chooses between forms the test suite compares bit for bit).  "throttle" (0/1, default 0):

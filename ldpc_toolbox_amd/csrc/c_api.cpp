@@ -785,6 +785,10 @@ int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value)
     *value = d.flags8();
   else if (k == "last_record_flag_bytes")
     *value = d.last_record_flag_bytes();
+  else if (k == "call_edges")
+    *value = d.call_edges();
+  else if (k == "last_call_edges")
+    *value = d.last_call_edges();
   else if (k == "minsum_correction")
     *value = static_cast<int64_t>(d.implementation().correction);
   else if (k == "minsum_correction_int")  // the 8-bit min-sum names: a = 16 alpha or b = 8 beta, 0 for every other name

@@ -80,6 +80,13 @@ class DeviceDecoder {
   // (graph_tables.h, count_vn_chain_fetches); 0 when off
   uint32_t last_vn_chains() const { return last_vn_chains_.load(std::memory_order_relaxed) ? 1 : 0; }
   uint32_t vn_chain_saved_permille() const { return last_vn_chain_saved_.load(std::memory_order_relaxed); }
+  // "call_edges" as set, and which of its shortcuts the groups of the last decode call took (kCallEdge* below, OR-ed)
+  uint32_t call_edges() const { return opt_call_edges_ ? 1 : 0; }
+  uint32_t last_call_edges() const { return last_call_edges_.load(std::memory_order_relaxed); }
+  static constexpr uint32_t kCallEdgeIngest = 1;      // the ingest launch stored no copy of the input in the posterior array
+  static constexpr uint32_t kCallEdgeClose = 2;       // the last pack covered the kept rows only; the closing launch packed the L-free ones
+  static constexpr uint32_t kCallEdgeEmit = 4;        // the final emit launch was given the packed decisions
+  static constexpr uint32_t kCallEdgeCheckpoint = 8;  // a checkpoint ran as two launches behind its plan (set when one was enqueued)
 
   // codewords per group (rounded up to the wave tile).  0 = automatic.
   void set_group_size(size_t g) { group_pref_ = g; }
@@ -89,7 +96,7 @@ class DeviceDecoder {
   void set_min_group(size_t g) { min_group_ = g; }
   // codewords per group a call of `batch` codewords is cut into (the set value, else a default that grows for small graphs)
   size_t preferred_group(size_t batch) const { return pick_group(batch); }
-  // The 31 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
+  // The 32 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
   // percent are constants now, see kStreamBlock ... below).  Results never depend on any of them; each selects between
   // forms that tests/ compare bit for bit.  returns false for an unknown key.
   //   which kernels run   "lfree" (0: plain flooding min-sum kernels), "records" (0 / 1 / 2: per-edge messages / row records
@@ -100,7 +107,8 @@ class DeviceDecoder {
   //                       bundled list walked entry by entry / in chains whose shared record stays in registers; "vn_chain_len":
   //                       4, 8 or 16 entries per chain), "flags8" (0 / 1: the
   //                       16-bit flags of rows of at most 7 edges stored as half-words / as bytes), "rec_long"
-  //                       (1: the record kernel's long-row variant whatever the graph), "staged_minsum" (1: Minsum through
+  //                       (1: the record kernel's long-row variant whatever the graph), "call_edges" (0: the launches around a
+  //                       call's iterations as they were: opt_call_edges_ below), "staged_minsum" (1: Minsum through
   //                       the generic LDS-staged kernel), "cn_reg" / "hl_reg" / "hl_records" (0: the LDS-staged / two-pass /
   //                       per-edge forms instead of register-resident rows and layered row records), "serial_levels"
   //                       (layered: more dependency levels than this -> row-serial mode), "latency" / "latency_edge"
@@ -209,6 +217,8 @@ class DeviceDecoder {
   static constexpr uint32_t kVnWaves = 128 * 1024;   // wavefronts of a variable-node launch
   static constexpr uint32_t kPackWaves = 16 * 1024;  // ... of the hard-decision packing launch (256 K: -0.7 % on config 3)
   static constexpr uint32_t kSyndThreads = 512 * 1024, kMoveWaves = 64 * 1024, kRetireBlocks = 256;
+  // workgroups of a "call_edges" checkpoint launch's two roles: they walk the blocks / waves of the launches they stand for
+  static constexpr uint32_t kEdgeRetireBlocks = 1024, kEdgeMoveBlocks = 2048;
   // decision rule of the compaction checkpoints (kernels_group.hip.h, CompactRule): waiting until half of the slots are
   // free beats re-packing at a quarter, the cost constants hardly matter (round 2's sweep over Eb/N0)
   static constexpr uint32_t kCompactHorizon = 8, kCompactCostLive = 9, kCompactCostSlots = 0, kCompactMinFreedQ = 2;
@@ -261,6 +271,15 @@ class DeviceDecoder {
   } vn_chain_at_[3];
   std::atomic<bool> last_vn_chains_{false};
   std::atomic<uint32_t> last_vn_chain_saved_{0};
+  // "call_edges": what a call does around its iterations, trimmed to what its result needs (profiles/call_edges.txt).  On the
+  // flooding record path of a call that asks for no posterior: the ingest launch stores the input once, not twice (the first
+  // check-node launch reads `chan` in the posterior's place); the last pack covers the rows the variable-node launch writes and
+  // the closing launch packs the L-free variables' decisions without storing their posteriors (vn_free_hard_kernel); the
+  // final emit launch reads those packed words, not posterior rows.  And wherever a compaction checkpoint is due, it is two
+  // launches behind its plan, not four (kernels_group.hip.h, compact_retire_move_kernel).  0: every launch as before.
+  // Results do not depend on it.
+  bool opt_call_edges_ = true;
+  std::atomic<uint32_t> last_call_edges_{0};  // (OR-ed by every group's run_group, cleared by the decode entries)
   std::atomic<uint32_t> last_record_flag_bytes_{0};
   std::atomic<bool> last_vn_records_{false};  // (written by every group's run_group: with "lane_threads" from two host threads)
   uint32_t rec_w_ = 0;

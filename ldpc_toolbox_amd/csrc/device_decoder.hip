@@ -270,6 +270,8 @@ bool DeviceDecoder::set_option(const std::string &key, int64_t value) {
   }
   else if (key == "rec_long")
     opt_rec_long_ = v != 0;
+  else if (key == "call_edges")
+    opt_call_edges_ = v != 0;
   else if (key == "compact")
     opt_compact_ = v != 0;
   else if (key == "staged_minsum")
@@ -476,6 +478,7 @@ int DeviceDecoder::ensure_workspace(Workspace &w, size_t G, void *place, size_t 
   w.fill_cw = w.perm + 3 * G;
   w.n_slots = w.perm + 4 * G;
   w.plan = reinterpret_cast<dev::CompactPlan *>(w.perm + 4 * G + 16);
+  w.hard_ok = w.perm + 4 * G + 32;
   w.rawbits = reinterpret_cast<uint64_t *>(base + o_raw);
   w.hardbits = reinterpret_cast<uint64_t *>(base + o_hard);
   uint32_t *flags = reinterpret_cast<uint32_t *>(base + o_flags);
@@ -613,6 +616,7 @@ size_t DeviceDecoder::pool_chunk(size_t batch) const { return pick_group(batch) 
 int DeviceDecoder::decode_device(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits,
                                  size_t out_len, int32_t *iterations, void *posterior, hipStream_t stream) {
   last_pooled_ = 0;
+  last_call_edges_.store(0, std::memory_order_relaxed);
   // (a call on the CALLER's stream only enqueues -- unless "throttle" lets it wait: pooling needs every chunk's counts back)
   if (opt_pooling_ && max_iterations >= 24 && batch >= 2 * pool_chunk(batch) && (stream == nullptr || opt_throttle_) && out_len <= n_)
     return decode_device_pooled(llrs, llrs_f64, batch, max_iterations, bits, out_len, iterations, posterior, stream);
@@ -879,6 +883,7 @@ int DeviceDecoder::drain_out(char *dst, const char *src, size_t bytes) {
 int DeviceDecoder::decode_host(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits,
                                size_t out_len, int32_t *iterations, void *posterior) {
   last_pooled_ = 0;
+  last_call_edges_.store(0, std::memory_order_relaxed);
   if (opt_pooling_ && max_iterations >= 24 && batch >= 2 * 4 * pool_chunk(batch) && out_len <= n_)
     return decode_host_pooled(llrs, llrs_f64, batch, max_iterations, bits, out_len, iterations, posterior);
   return decode_host_plain(llrs, llrs_f64, batch, max_iterations, bits, out_len, iterations, posterior);

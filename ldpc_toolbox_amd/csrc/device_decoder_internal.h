@@ -51,6 +51,7 @@ struct DeviceDecoder::Workspace {
   // compaction: perm = the movers' slots, slot_tmp = the holes they fill, fill_cw = codeword landing in a slot
   uint32_t *perm = nullptr, *slot_cw = nullptr, *slot_tmp = nullptr, *fill_cw = nullptr, *n_slots = nullptr;
   dev::CompactPlan *plan = nullptr;
+  uint32_t *hard_ok = nullptr;  // "call_edges": whether the last pack of the group wrote hardbits (pack_hard_kernel, `ran`)
   uint32_t *done = nullptr, *unsat0 = nullptr, *unsat1 = nullptr, *n_active = nullptr, *scratch_flags = nullptr,
            *slice_state = nullptr;
   int32_t *iters = nullptr;
@@ -369,12 +370,18 @@ struct DeviceDecoder::GroupFrame {
     return 0;
   }
   // results to the caller's rows, in the precision of its input (retire_only: a compaction checkpoint's, do_compact its plan)
+  // hard, hard_ok ("call_edges"): the last posterior's packed decisions, by slot, and the word that says whether they are
+  // valid -- a launch that writes no posterior takes the decisions from them (kernels_group.hip.h, emit_kernel): a block then
+  // covers 256 variables of its 64 slots per step, not 64
   template <typename P>
-  void emit(const P *post, const uint32_t *do_compact, int zero_fill, int retire_only) const {
-    const dim3 grid(std::min<uint32_t>((n + 63) / 64, retire_only ? kRetireBlocks : 4096), W);
+  void emit(const P *post, const uint32_t *do_compact, int zero_fill, int retire_only, const uint64_t *hard = nullptr,
+            const uint32_t *hard_ok = nullptr) const {
+    const bool from_hard = hard != nullptr && c.posterior == nullptr && !zero_fill && !retire_only;
+    const uint32_t blocks_x = from_hard ? (std::min<uint32_t>(n, static_cast<uint32_t>(c.out_len)) + 3) / 4 / 64 + 1 : (n + 63) / 64;
+    const dim3 grid(std::min<uint32_t>(blocks_x, retire_only ? kRetireBlocks : 4096), W);
     auto go = [&](auto kernel, auto *out) {
       kernel<<<grid, 256, 0, s>>>(post, w.rawbits, st, do_compact, n, G, tile, static_cast<uint32_t>(c.out_len), c.bits,
-                                  c.iterations, out, zero_fill, retire_only);
+                                  c.iterations, out, zero_fill, retire_only, from_hard ? hard : nullptr, hard_ok);
     };
     if (c.llrs_f64)
       go(dev::emit_kernel<P, double>, static_cast<double *>(c.posterior));

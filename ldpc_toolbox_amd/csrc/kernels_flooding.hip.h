@@ -385,6 +385,81 @@ __global__ __launch_bounds__(256) void vn_free_rec_kernel(Graph g, Sched sc, Sta
   }
 }
 
+// The closing launch of a call that asked for no posterior ("call_edges"): vn_free_rec_kernel's event_iteration < 0 form with
+// the hard decisions L <= 0 (arithmetic.rs:198-200) as its only output -- L = chan + (m_a + m_b) is formed as above and
+// ballotted straight into pack_hard_kernel's words, bits[v][W]; no posterior row is stored.  The words of a frozen codeword
+// come from its stored row (its L-free rows were stored when it converged): a wave whose codewords are all live reads no
+// posterior, one whose codewords are all frozen no records.  Runs behind the pack of the rows the variable-node launch writes
+// and covers every L-free variable, wherever its row lies.
+// A lane holds the VEC codewords b0 + VEC * lane + k; packed word j of the slice holds b0 + 64 j + i in bit i, which is
+// element i % VEC of lane (64 j + i) / VEC: each lane picks its bit out of the VEC ballots and the wave ballots again.
+template <typename T, int VEC, int RECW, bool F16 = false, bool F8 = false>
+__global__ __launch_bounds__(256) void vn_free_hard_kernel(Graph g, Sched sc, State st, const uint32_t *__restrict__ free_rs_,
+                                                           const T *__restrict__ chan, typename RecRef<T, F16, F8>::in rec,
+                                                           const T *__restrict__ post, uint64_t *__restrict__ bits, uint32_t W) {
+  typedef RowRec<T, VEC, RECW, RecFlagWord<T, F16, F8>> Rec;
+  if (*st.n_active == 0) return;
+  const TablePtr free_var = table_ptr(g.list_var), free_rs = table_ptr(free_rs_);
+  const uint32_t lane = threadIdx.x & 63u, tile = sc.tile;
+  const uint32_t wave = uniform((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+  uint32_t chunk, i0;
+  wave_slot(sc, wave, &chunk, &i0);
+  if (chunk >= sc.nchunks) return;
+  const uint32_t b0 = chunk * (64 * VEC);
+  if (b0 >= *st.n_slots) return;
+  const size_t off = size_t(b0) + lane * VEC;
+  const size_t G = tile;
+  chan += tile_base(b0, g.n_cols, sc) + lane * VEC;
+  post += tile_base(b0, g.n_cols, sc) + lane * VEC;
+  bits += chunk * VEC;
+  const uint32_t row_bytes = tile * uint32_t(sizeof(T)), lane_off = lane * uint32_t(VEC * sizeof(T));
+  const RecBuf<F16> b_rec = rec_buf<T, RECW>(rec, b0, g.n_rows, sc, row_bytes);
+  bool live[VEC];
+  bool any_live = false, all_live = true;
+#pragma unroll
+  for (int k = 0; k < VEC; k++) {
+    live[k] = st.done[off + k] == 0;
+    any_live = any_live || live[k];
+    all_live = all_live && live[k];
+  }
+  any_live = __builtin_amdgcn_ballot_w64(any_live) != 0;   // wave-uniform, both
+  all_live = __builtin_amdgcn_ballot_w64(!all_live) == 0;
+  const uint32_t mine = lane % VEC, at = lane / VEC;
+  for (uint32_t i = i0; i < g.n_list; i += sc.waves_per_chunk) {
+    const uint32_t v = free_var[i], a = free_rs[2 * i], b = free_rs[2 * i + 1];
+    Pack<T, VEC> x;
+    if (any_live) {
+      const Pack<T, VEC> ch = load_pack<T, VEC>(chan + size_t(v) * G);
+      Rec ra, rb;
+      if (a != kAuxNone) ra.load(b_rec, lane_off, (a >> 6) * Rec::kRows * row_bytes, row_bytes);
+      if (b != kAuxNone) rb.load(b_rec, lane_off, (b >> 6) * Rec::kRows * row_bytes, row_bytes);
+#pragma unroll
+      for (int k = 0; k < VEC; k++) {
+        T sum = -T(0.0);  // arithmetic.rs:146: the slot-ordered sum, from Rust's float Sum identity
+        if (a != kAuxNone) sum = sum + ra.value(a & 63u, k);
+        if (b != kAuxNone) sum = sum + rb.value(b & 63u, k);
+        x.v[k] = ch.v[k] + sum;
+      }
+    }
+    if (!all_live) {
+      const Pack<T, VEC> old = load_pack<T, VEC>(post + size_t(v) * G);
+#pragma unroll
+      for (int k = 0; k < VEC; k++) x.v[k] = (any_live && live[k]) ? x.v[k] : old.v[k];
+    }
+    uint64_t picked = 0;  // the ballot of this lane's element of every lane
+#pragma unroll
+    for (int k = 0; k < VEC; k++) {
+      const uint64_t bal = __builtin_amdgcn_ballot_w64(x.v[k] <= T(0.0));
+      picked = (mine == uint32_t(k)) ? bal : picked;
+    }
+#pragma unroll
+    for (int j = 0; j < VEC; j++) {
+      const uint64_t word = __builtin_amdgcn_ballot_w64(((picked >> (uint32_t(j) * (64 / VEC) + at)) & 1ull) != 0);
+      if (lane == 0) bits[size_t(v) * W + j] = word;
+    }
+  }
+}
+
 
 // ---------------------------------------------------------------------------------------
 // Flooding, variable nodes (all float rules share arithmetic.rs:140-156):

@@ -44,10 +44,15 @@ __global__ void latch_kernel(uint32_t *done, int32_t *iters, uint32_t *unsat, ui
 
 // hard decisions (x <= 0, arithmetic.rs:198-200) of [N][G] soft values, bit-packed
 // 64 codewords per word with a wave ballot: bits[v][w], W = G / 64 words per variable
+// n_pack: the leading rows that are packed (<= n_cols: a caller that fills the other rows' words itself, "call_edges").
+// ran (may be null): set to whether the launch packed anything (a finished group's launch returns at once, and `bits` is then
+// what an earlier launch left)
 template <typename T>
 __global__ void pack_hard_kernel(const T *__restrict__ soft, uint64_t *__restrict__ bits,
                                  const uint32_t *__restrict__ n_active, const uint32_t *__restrict__ n_slots,
-                                 uint32_t n_cols, uint32_t tile, uint32_t W, uint32_t waves_per_word) {
+                                 uint32_t n_cols, uint32_t tile, uint32_t W, uint32_t waves_per_word, uint32_t n_pack,
+                                 uint32_t *__restrict__ ran) {
+  if (ran != nullptr && blockIdx.x == 0 && threadIdx.x == 0) *ran = *n_active != 0 ? 1u : 0u;
   if (*n_active == 0) return;
   const uint32_t lane = threadIdx.x & 63u;
   const uint32_t wave = uniform((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
@@ -56,17 +61,17 @@ __global__ void pack_hard_kernel(const T *__restrict__ soft, uint64_t *__restric
   soft += tile_base(w * 64, n_cols, tile) + lane;
   // eight rows in flight per wave: one 256-byte row at a time left the kernel latency-bound
   constexpr int U = 8;
-  for (uint32_t v0 = wave % waves_per_word; v0 < n_cols; v0 += U * waves_per_word) {
+  for (uint32_t v0 = wave % waves_per_word; v0 < n_pack; v0 += U * waves_per_word) {
     T x[U];
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const uint32_t v = v0 + u * waves_per_word;
-      if (v < n_cols) x[u] = soft[size_t(v) * tile];  // wave-uniform guard
+      if (v < n_pack) x[u] = soft[size_t(v) * tile];  // wave-uniform guard
     }
 #pragma unroll
     for (int u = 0; u < U; u++) {
       const uint32_t v = v0 + u * waves_per_word;
-      if (v < n_cols) {
+      if (v < n_pack) {
         const uint64_t b = __builtin_amdgcn_ballot_w64(x[u] <= T(0.0));
         if (lane == 0) bits[size_t(v) * W + w] = b;
       }
@@ -185,6 +190,8 @@ __global__ __launch_bounds__(256) void syndrome_bits_kernel(const uint32_t *__re
 // 0.0 LLRs), quantises to the arithmetic type (`x as f32`, arithmetic.rs:194-196), writes
 // chan and post (= L_0), and packs the hard decisions of the RAW input for the pre-check
 // (flooding.rs:57).  Lanes beyond the batch are padded with +1.0.
+// post null ("call_edges"): no copy in `post` -- for a schedule that reads `chan` in its first launch and rewrites every
+// posterior row before anything reads it (the flooding record path of a call without a posterior, run_group.hip.h).
 template <typename SrcT, typename T>
 __global__ __launch_bounds__(256) void ingest_kernel(const SrcT *__restrict__ src, size_t src_stride,
                                                      uint32_t nb, uint32_t n, uint32_t G, uint32_t tile,
@@ -217,7 +224,7 @@ __global__ __launch_bounds__(256) void ingest_kernel(const SrcT *__restrict__ sr
       const SrcT val = lds[tx][r];
       const T q = static_cast<T>(val);
       chan[base + size_t(v) * tile] = q;
-      post[base + size_t(v) * tile] = q;
+      if (post != nullptr) post[base + size_t(v) * tile] = q;  // (the same for every thread of the launch)
       const uint64_t bal = __builtin_amdgcn_ballot_w64(val <= SrcT(0.0));
       if (tx == 0) rawbits[size_t(v) * W + blockIdx.y] = bal;
     }
@@ -231,6 +238,20 @@ __global__ __launch_bounds__(256) void ingest_kernel(const SrcT *__restrict__ sr
 // hard decisions of the raw input (flooding.rs:59-63).  zero_fill: the reference's
 // max_iterations = 0 failure of the flooding decoder reports its never-written output_llrs
 // (flooding.rs:27-28, 82-85).
+// hard, hard_ok ("call_edges"; both null otherwise): the packed decisions of the last posterior, hard[v][W] with bit s & 63 of
+// word s >> 6 the decision of SLOT s (pack_hard_kernel's layout; rawbits is indexed by codeword), valid if *hard_ok != 0.  A
+// launch that writes no posterior then takes the decisions from them and reads no posterior row: a lane forms four output
+// bytes and stores them as one dword where the address allows (the groups of four are laid out per row of `bits`, from its
+// address: up to three single bytes at either end).  The pre-check's frames still report rawbits.
+// (emit_rows: block (bx, by) of an (nbx, W) grid of the launch, from the posterior rows; lds: the workgroup's 64 x 65 tile.
+// Every return and every barrier is taken by the whole workgroup.)
+template <typename T, typename OutT>
+__device__ __forceinline__ void emit_rows(T (*lds)[65], uint32_t bx, uint32_t nbx, uint32_t by, const T *__restrict__ post,
+                                          const uint64_t *__restrict__ rawbits, const State &st, uint32_t n, uint32_t G,
+                                          uint32_t tile, uint32_t out_len, uint8_t *__restrict__ bits,
+                                          int32_t *__restrict__ iterations, OutT *__restrict__ posterior, int zero_fill,
+                                          int retire_only);
+
 template <typename T, typename OutT>
 __global__ __launch_bounds__(256) void emit_kernel(const T *__restrict__ post,
                                                    const uint64_t *__restrict__ rawbits, State st,
@@ -238,21 +259,83 @@ __global__ __launch_bounds__(256) void emit_kernel(const T *__restrict__ post,
                                                    uint32_t G, uint32_t tile, uint32_t out_len,
                                                    uint8_t *__restrict__ bits, int32_t *__restrict__ iterations,
                                                    OutT *__restrict__ posterior, int zero_fill,
-                                                   int retire_only) {
+                                                   int retire_only, const uint64_t *__restrict__ hard = nullptr,
+                                                   const uint32_t *__restrict__ hard_ok = nullptr) {
   __shared__ T lds[64][65];
-  const uint32_t tx = threadIdx.x & 63u, ty = threadIdx.x >> 6;
-  const uint32_t b0 = blockIdx.y * 64;
-  if (b0 >= *st.n_slots) return;
   if (retire_only && *do_compact == 0) return;
+  const uint32_t W = G / 64;
+  if (hard != nullptr && posterior == nullptr && !zero_fill && !retire_only && (hard_ok == nullptr || *hard_ok != 0)) {
+    const uint32_t tx = threadIdx.x & 63u, ty = threadIdx.x >> 6;
+    const uint32_t b0 = blockIdx.y * 64;
+    if (b0 >= *st.n_slots) return;
+    // words[t]: the 64 slots' decisions of variable 4 * g0 - 3 + t, for the 64 groups of four from group g0 on: group g of a
+    // row whose address is `a` bytes past a dword boundary holds variables 4 g - a .. 4 g - a + 3
+    __shared__ uint64_t words[260];
+    const uint32_t n_bits = min(n, out_len);
+    const uint32_t n_groups = (n_bits + 3) / 4 + 1;
+    for (uint32_t g0 = blockIdx.x * 64; g0 < n_groups; g0 += gridDim.x * 64) {
+      __syncthreads();
+      for (uint32_t t = threadIdx.x; t < 260; t += 256) {
+        const int32_t v = int32_t(4 * g0 + t) - 3;
+        words[t] = (v >= 0 && uint32_t(v) < n_bits) ? hard[size_t(v) * W + blockIdx.y] : 0ull;
+      }
+      __syncthreads();
+      for (uint32_t r = ty; r < 64; r += 4) {
+        const uint32_t slot = b0 + r;
+        const uint32_t cw = st.slot_cw[slot];
+        if (cw == kNoCodeword) continue;  // wave-uniform
+        const int32_t it = st.iters[slot];
+        uint8_t *row = bits + size_t(cw) * out_len;
+        const uint32_t a = uint32_t(reinterpret_cast<uintptr_t>(row)) & 3u;
+        const int32_t vs = int32_t(4 * (g0 + tx)) - int32_t(a);
+        uint32_t four = 0;
+        if (it == 0 && rawbits != nullptr) {  // wave-uniform
+#pragma unroll
+          for (int j = 0; j < 4; j++) {
+            const int32_t v = vs + j;
+            if (v >= 0 && uint32_t(v) < n_bits)
+              four |= uint32_t((rawbits[size_t(v) * W + (cw >> 6)] >> (cw & 63u)) & 1u) << (8 * j);
+          }
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; j++) four |= uint32_t((words[4 * tx + 3 - a + j] >> r) & 1u) << (8 * j);
+        }
+        if (vs >= 0 && uint32_t(vs) + 4 <= n_bits) {
+          *reinterpret_cast<uint32_t *>(row + vs) = four;
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; j++) {
+            const int32_t v = vs + j;
+            if (v >= 0 && uint32_t(v) < n_bits) row[v] = uint8_t(four >> (8 * j));
+          }
+        }
+        if (iterations && g0 == 0 && tx == 0) iterations[cw] = it;
+      }
+    }
+    return;
+  }
+  emit_rows<T, OutT>(lds, blockIdx.x, gridDim.x, blockIdx.y, post, rawbits, st, n, G, tile, out_len, bits, iterations, posterior,
+                     zero_fill, retire_only);
+}
+
+template <typename T, typename OutT>
+__device__ __forceinline__ void emit_rows(T (*lds)[65], uint32_t bx, uint32_t nbx, uint32_t by, const T *__restrict__ post,
+                                          const uint64_t *__restrict__ rawbits, const State &st, uint32_t n, uint32_t G,
+                                          uint32_t tile, uint32_t out_len, uint8_t *__restrict__ bits,
+                                          int32_t *__restrict__ iterations, OutT *__restrict__ posterior, int zero_fill,
+                                          int retire_only) {
+  const uint32_t tx = threadIdx.x & 63u, ty = threadIdx.x >> 6;
+  const uint32_t b0 = by * 64;
+  if (b0 >= *st.n_slots) return;
   if (retire_only) {  // nothing to retire among this block's 64 slots (wave-uniform: every wave looks at the same 64)
     const uint32_t slot = b0 + tx;
     if (__builtin_amdgcn_ballot_w64(st.done[slot] != 0 && st.slot_cw[slot] != kNoCodeword) == 0) return;
   }
-  const size_t base = tile_base(b0, n, tile) + tx;
   const uint32_t W = G / 64;
+  const size_t base = tile_base(b0, n, tile) + tx;
   // only the rows somebody asked for: the first out_len hard decisions, all n soft values if a posterior is wanted
   const uint32_t n_emit = posterior ? n : min(n, out_len);
-  for (uint32_t v0 = blockIdx.x * 64; v0 < max(n_emit, 1u); v0 += gridDim.x * 64) {
+  for (uint32_t v0 = bx * 64; v0 < max(n_emit, 1u); v0 += nbx * 64) {
   __syncthreads();
   for (uint32_t r = ty; r < 64; r += 4) {
     const uint32_t v = v0 + r;
@@ -441,15 +524,25 @@ struct MoveList {
 
 // arr[row][holes[i]] = arr[row][movers[i]]: a wavefront takes 64 pairs and every waves_per_chunk-th row,
 // eight rows in flight
+// (move_rows: what wave `wave` of such a launch does)
+template <typename T>
+__device__ __forceinline__ void move_rows(const CompactPlan *plan, const uint32_t *__restrict__ movers,
+                                          const uint32_t *__restrict__ holes, const MoveList<T> &ml, uint32_t tile,
+                                          uint32_t nchunks, uint32_t waves_per_chunk, uint32_t wave);
 template <typename T>
 __global__ __launch_bounds__(256) void compact_move_kernel(const CompactPlan *plan,
                                                            const uint32_t *__restrict__ movers,
                                                            const uint32_t *__restrict__ holes, MoveList<T> ml,
                                                            uint32_t tile, uint32_t nchunks, uint32_t waves_per_chunk) {
   if (plan->do_compact == 0) return;
+  move_rows<T>(plan, movers, holes, ml, tile, nchunks, waves_per_chunk, uniform((blockIdx.x * blockDim.x + threadIdx.x) >> 6));
+}
+template <typename T>
+__device__ __forceinline__ void move_rows(const CompactPlan *plan, const uint32_t *__restrict__ movers,
+                                          const uint32_t *__restrict__ holes, const MoveList<T> &ml, uint32_t tile,
+                                          uint32_t nchunks, uint32_t waves_per_chunk, uint32_t wave) {
   constexpr int U = 8;
   const uint32_t lane = threadIdx.x & 63u;
-  const uint32_t wave = uniform((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
   const uint32_t chunk = wave / waves_per_chunk;
   if (chunk >= nchunks || chunk * 64 >= plan->n_move) return;
   const uint32_t i = chunk * 64 + lane;
@@ -477,11 +570,9 @@ __global__ __launch_bounds__(256) void compact_move_kernel(const CompactPlan *pl
   }
 }
 
-#ifdef LDPC_GROUP_KERNELS_TU  // not a template: compiled in ONE translation unit (device_decoder.hip), launched through grp:: (device_decoder_internal.h)
-__global__ void compact_commit_kernel(State st, const CompactPlan *plan, uint32_t *unsat0, uint32_t *unsat1,
-                                      uint32_t *n_slots_w, const uint32_t *__restrict__ fill_cw, uint32_t G) {
-  if (plan->do_compact == 0) return;
-  const uint32_t b = blockIdx.x * blockDim.x + threadIdx.x;
+// (commit_slot: slot b of a decided compaction)
+__device__ __forceinline__ void commit_slot(const State &st, const CompactPlan *plan, uint32_t *unsat0, uint32_t *unsat1,
+                                            uint32_t *n_slots_w, const uint32_t *__restrict__ fill_cw, uint32_t G, uint32_t b) {
   if (b >= G) return;
   // codewords change slices: from here on every slice stores its L-free posteriors (State::slice_state)
   if (st.slice_state != nullptr && b < G / 64) st.slice_state[b] = 2;
@@ -498,7 +589,64 @@ __global__ void compact_commit_kernel(State st, const CompactPlan *plan, uint32_
   unsat1[b] = 0;
   if (b == 0) *n_slots_w = plan->new_slots;
 }
+#ifdef LDPC_GROUP_KERNELS_TU  // not a template: compiled in ONE translation unit (device_decoder.hip), launched through grp:: (device_decoder_internal.h)
+__global__ void compact_commit_kernel(State st, const CompactPlan *plan, uint32_t *unsat0, uint32_t *unsat1,
+                                      uint32_t *n_slots_w, const uint32_t *__restrict__ fill_cw, uint32_t G) {
+  if (plan->do_compact == 0) return;
+  commit_slot(st, plan, unsat0, unsat1, n_slots_w, fill_cw, G, blockIdx.x * blockDim.x + threadIdx.x);
+}
 #endif  // LDPC_GROUP_KERNELS_TU
+
+// A checkpoint in two launches behind the plan ("call_edges") instead of four -- one decision per launch instead of one per
+// kernel: an undecided compaction, the usual case, costs two empty launches.  What orders the four is the posterior: the
+// retire-emit reads the finished slots' rows, the mover fills the holes among them, and the commit rewrites the state the
+// retire-emit reads.  So
+//   compact_retire_move_kernel   the retire-emit, and the movers of every array but the posterior (`ml` without it; `fl`: the
+//                                records' flags, count 0 where there are none)
+//   compact_post_commit_kernel   the posterior's mover and the commit
+// each with a role per block range and grid-stride loops over the blocks / waves of the launches they stand for, and no block
+// waits for another.
+template <typename T, typename OutT, typename FW>
+__global__ __launch_bounds__(256) void compact_retire_move_kernel(
+    const CompactPlan *plan, const T *__restrict__ post, const uint64_t *__restrict__ rawbits, State st, uint32_t n, uint32_t G,
+    uint32_t tile, uint32_t out_len, uint8_t *__restrict__ bits, int32_t *__restrict__ iterations, OutT *__restrict__ posterior,
+    uint32_t emit_blocks, uint32_t emit_nbx, const uint32_t *__restrict__ movers, const uint32_t *__restrict__ holes,
+    MoveList<T> ml, MoveList<FW> fl, uint32_t nchunks, uint32_t waves_per_chunk) {
+  __shared__ T lds[64][65];
+  if (plan->do_compact == 0) return;
+  if (blockIdx.x < emit_blocks) {
+    const uint32_t W = G / 64;
+    for (uint32_t b = blockIdx.x; b < emit_nbx * W; b += emit_blocks)
+      emit_rows<T, OutT>(lds, b % emit_nbx, emit_nbx, b / emit_nbx, post, rawbits, st, n, G, tile, out_len, bits, iterations,
+                         posterior, 0, 1);
+    return;
+  }
+  const uint32_t n_waves = (gridDim.x - emit_blocks) * (blockDim.x >> 6);
+  const uint32_t wave0 = uniform(((blockIdx.x - emit_blocks) * blockDim.x + threadIdx.x) >> 6);
+  const uint32_t todo = min(nchunks, (plan->n_move + 63u) / 64u) * waves_per_chunk;
+  for (uint32_t wave = wave0; wave < todo; wave += n_waves) {
+    move_rows<T>(plan, movers, holes, ml, tile, nchunks, waves_per_chunk, wave);
+    if (fl.count != 0) move_rows<FW>(plan, movers, holes, fl, tile, nchunks, waves_per_chunk, wave);
+  }
+}
+template <typename T>
+__global__ __launch_bounds__(256) void compact_post_commit_kernel(State st, const CompactPlan *plan, uint32_t *unsat0,
+                                                                  uint32_t *unsat1, uint32_t *n_slots_w,
+                                                                  const uint32_t *__restrict__ fill_cw, uint32_t G,
+                                                                  uint32_t commit_blocks, const uint32_t *__restrict__ movers,
+                                                                  const uint32_t *__restrict__ holes, MoveList<T> ml,
+                                                                  uint32_t tile, uint32_t nchunks, uint32_t waves_per_chunk) {
+  if (plan->do_compact == 0) return;
+  if (blockIdx.x < commit_blocks) {
+    commit_slot(st, plan, unsat0, unsat1, n_slots_w, fill_cw, G, blockIdx.x * blockDim.x + threadIdx.x);
+    return;
+  }
+  const uint32_t n_waves = (gridDim.x - commit_blocks) * (blockDim.x >> 6);
+  const uint32_t wave0 = uniform(((blockIdx.x - commit_blocks) * blockDim.x + threadIdx.x) >> 6);
+  const uint32_t todo = min(nchunks, (plan->n_move + 63u) / 64u) * waves_per_chunk;
+  for (uint32_t wave = wave0; wave < todo; wave += n_waves)
+    move_rows<T>(plan, movers, holes, ml, tile, nchunks, waves_per_chunk, wave);
+}
 
 #ifdef LDPC_GROUP_KERNELS_TU  // straggler pooling of the batch entries (DeviceDecoder::decode_device_pooled): three small kernels
 // Iteration counts of a chunk -> the call's statistics and the indices of the chunk's stragglers.

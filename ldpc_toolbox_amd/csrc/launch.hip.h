@@ -152,6 +152,17 @@ struct Launch {
       });
     });
   }
+  // the closing launch of a call without a posterior ("call_edges"): the L-free variables' decisions into the packed words
+  void vn_free_hard(uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const uint32_t *free_rs,
+                    const T *chan, const Records &rec, const T *post, uint64_t *bits, uint32_t W) const {
+    with_vec<T>(vec, [&](auto V) {
+      with_rec_form(rec, [&](auto RW, auto F16, auto F8) {
+        dev::vn_free_hard_kernel<T, decltype(V)::value, decltype(RW)::value, decltype(F16)::value, decltype(F8)::value>
+            <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, free_rs, chan, rec_ref<true, decltype(F16)::value, decltype(F8)::value>(rec),
+                                            post, bits, W);
+      });
+    });
+  }
 
   // flooding, LDS-staged rules.  reg_dmax: 0 = cn_staged_kernel; 10 / 12 = cn_reg_kernel (rows of at most that many edges
   // in registers; recs: their records).  row_scratch non-null: cn_staged_kernel keeps its columns there (rows beyond the LDS)

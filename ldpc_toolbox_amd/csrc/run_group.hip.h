@@ -31,18 +31,39 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
                          dev::MinsumCorr<T>{static_cast<T>(impl_.alpha()), static_cast<T>(impl_.beta())}};
   const dev::Graph g = f.graph(d_edge_aux_.get<uint32_t>(), d_edge_peer_.get<uint32_t>());
 
-  if (int rc = f.begin(dev::ingest_kernel<float, T>, dev::ingest_kernel<double, T>, chan, post)) return rc;
+  // Whether the call takes the flooding record path, decided before its first launch: "call_edges" trims the launches around
+  // that path's iterations when no posterior was asked for (device_decoder.h, opt_call_edges_).
+  // (the streaming min-sum kernels keep a row's signs in a 64-bit mask: longer rows take the LDS-staged kernel; the record
+  // kernel's buffer addressing carries 32-bit byte offsets inside a tile slice)
+  const bool fl_streaming = impl_.schedule == Schedule::Flooding && impl_.rule == Rule::Minsum && !opt_staged_minsum_ &&
+                            max_row_weight_ <= 64;
+  const bool fl_records = fl_streaming && w.records && w.rec[0] != nullptr &&
+                          uint64_t(std::max<size_t>(std::max(e_, n_), m_ * rec_w_)) * tile * sizeof(T) < (1ull << 32);
+  const bool edges = opt_call_edges_, edges_no_post = edges && fl_records && call.posterior == nullptr;
+  uint32_t edges_ran = 0;
+  // (1) nothing reads the posterior array before it is rewritten: the first check-node launch reads the kept variables' rows,
+  // which equal the channel's, and stores none; the first variable-node launch writes every kept row of every running
+  // codeword; the L-free rows are stored before they are read (State::slice_state); a frame that passes the pre-check is
+  // emitted from rawbits.  So the ingest launch stores the input once, and the first check-node launch reads `chan` twice.
+  const bool ingest_no_post = edges_no_post;
+  if (ingest_no_post) edges_ran |= kCallEdgeIngest;
+  if (int rc = f.begin(dev::ingest_kernel<float, T>, dev::ingest_kernel<double, T>, chan, ingest_no_post ? static_cast<T *>(nullptr) : post))
+    return rc;
   // (one codeword per lane: the paired-load form of the 16-bit posterior, pack_hard_pair_kernel, is slower here --
   // 210 vs 191 us for 8192 x BG1 Zc=384: 256-byte requests already stream, the exchange only adds work)
   // (16 K waves by default: the launch runs once per layered iteration and its waves are short -- at the 256 K of the other
   // launches a wave packs six rows and is gone; 5G NR BG1 Zc=384 HLTanhf32 +0.7 % over three alternating pairs, round 5)
   const Tiling pack_t = make_tiling(G, tile, 64, n, 256, std::min<uint32_t>(target_waves, kPackWaves));
-  auto pack = [&](const T *soft) {
+  // (rows: the leading rows packed; ran: where the launch says whether it packed -- "call_edges", pack_hard_kernel)
+  auto pack = [&](const T *soft, uint32_t rows, uint32_t *ran) {
     dev::pack_hard_kernel<T><<<pack_t.blocks, pack_t.threads, 0, s>>>(soft, w.hardbits, w.n_active, w.n_slots, n, tile,
-                                                                      W, pack_t.sched.waves_per_chunk);
+                                                                      W, pack_t.sched.waves_per_chunk, rows, ran);
   };
 
-  auto emit = [&](int zero_fill, int retire_only) { f.emit(post, &w.plan->do_compact, zero_fill, retire_only); };
+  const uint64_t *emit_hard = nullptr;  // set where the last pack's words serve the final emit launch ("call_edges")
+  auto emit = [&](int zero_fill, int retire_only) {
+    f.emit(post, &w.plan->do_compact, zero_fill, retire_only, retire_only ? nullptr : emit_hard, w.hard_ok);
+  };
   // batch compaction checkpoint (kernels.hip.h): everything decided on the device
   const Tiling mv_t = make_tiling(G, tile, 64, n, 256, kMoveWaves);
   uint32_t post_move_rows = 0;  // 0 = all rows; set by the flooding L-free paths below
@@ -52,6 +73,46 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
                      uint32_t flag_rows = 0, bool flags8 = false) {
     grp::compact_plan(s, ticked(max_iterations - remaining), w.plan, w.perm, w.slot_tmp, w.fill_cw, remaining,
         dev::CompactRule{kCompactHorizon, kCompactCostLive, kCompactCostSlots, kCompactMinFreedQ});
+    if (edges) {
+      // "call_edges": two launches behind the plan (kernels_group.hip.h, compact_retire_move_kernel): the retire-emit with the
+      // movers of everything but the posterior, then the posterior's mover with the commit
+      edges_ran |= kCallEdgeCheckpoint;
+      dev::MoveList<T> rest{}, pm{};
+      auto add_to = [](dev::MoveList<T> &l, T *arr, uint32_t rows, uint32_t moved) {
+        l.arr[l.count] = arr;
+        l.rows[l.count] = rows;
+        l.moved[l.count++] = moved;
+      };
+      if (with_chan) add_to(rest, chan, n, n);
+      if (msg_rows) add_to(rest, msg_cur, msg_rows, msg_rows);
+      add_to(pm, post, n, post_move_rows ? post_move_rows : n);
+      const uint32_t emit_nbx = std::min<uint32_t>((n + 63) / 64, kRetireBlocks);
+      const uint32_t emit_blocks = std::min<uint32_t>(emit_nbx * W, kEdgeRetireBlocks);
+      const uint32_t commit_blocks = (G + 255) / 256;
+      auto retire_move = [&](auto fw, auto *out) {
+        using FW = decltype(fw);
+        dev::MoveList<FW> fl{};
+        if (flags) fl = dev::MoveList<FW>{{reinterpret_cast<FW *>(flags)}, {flag_rows}, {flag_rows}, 1};
+        using OutT = std::remove_pointer_t<decltype(out)>;
+        dev::compact_retire_move_kernel<T, OutT, FW><<<emit_blocks + kEdgeMoveBlocks, 256, 0, s>>>(
+            w.plan, post, w.rawbits, st, n, G, tile, static_cast<uint32_t>(call.out_len), call.bits, call.iterations, out,
+            emit_blocks, emit_nbx, w.perm, w.slot_tmp, rest, fl, mv_t.sched.nchunks, mv_t.sched.waves_per_chunk);
+      };
+      auto with_out = [&](auto fw) {
+        if (call.llrs_f64)
+          retire_move(fw, static_cast<double *>(call.posterior));
+        else
+          retire_move(fw, static_cast<float *>(call.posterior));
+      };
+      if (flags && flags8)
+        with_out(uint8_t{});
+      else
+        with_out(uint16_t{});
+      dev::compact_post_commit_kernel<T><<<commit_blocks + kEdgeMoveBlocks, 256, 0, s>>>(
+          st, w.plan, w.unsat0, w.unsat1, w.n_slots, w.fill_cw, G, commit_blocks, w.perm, w.slot_tmp, pm, tile,
+          mv_t.sched.nchunks, mv_t.sched.waves_per_chunk);
+      return;
+    }
     emit(0, 1);
     dev::MoveList<T> ml{};
     auto add = [&](T *arr, uint32_t rows, uint32_t moved) {
@@ -96,9 +157,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
   last_record_flag_bytes_.store(0, std::memory_order_relaxed);  // (the flooding record path says what it ran)
 
   if (impl_.schedule == Schedule::Flooding) {
-    // the streaming min-sum kernels keep a row's signs in a 64-bit mask: longer rows take the
-    // LDS-staged kernel
-    const bool streaming = impl_.rule == Rule::Minsum && !opt_staged_minsum_ && max_row_weight_ <= 64;
+    const bool streaming = fl_streaming;  // (decided above)
     const uint32_t vec = pick_vec_for(tile, sizeof(T) == 4 ? 4 : 2, opt_vec_);
     const uint32_t stream_block = kStreamBlock;
     const Tiling vn_t = make_tiling(G, tile, 64 * vec, n, stream_block, opt_waves_ ? opt_waves_ : kVnWaves);
@@ -129,8 +188,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     const bool wide_mask = max_row_weight_ > 32;
     // row records instead of per-edge messages on the check-node side (kernels.hip.h, cn_minsum_rec_kernel)
     // (its buffer addressing carries 32-bit byte offsets inside a tile slice)
-    const bool records = streaming && w.records && w.rec[0] != nullptr &&
-                         uint64_t(std::max<size_t>(std::max(e_, n_), m_ * rec_w_)) * tile * sizeof(T) < (1ull << 32);
+    const bool records = fl_records;  // (decided above)
     const bool lfree = streaming && lfree_ready_ && opt_lfree_ && (w.msg2 != nullptr || records);
     T *mbuf[2] = {msg, (lfree && !records) ? static_cast<T *>(w.msg2) : msg};
     // (16-bit flags, rows of at most 12 edges: w.rec_flags holds them, w.rec the magnitudes alone)
@@ -228,8 +286,9 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       const dev::State stp = ticked(it);
       timed_begin(kKernelCheck, s);
       if (records)
-        launch.cn_rec(first, vec, rec_t, g, stp, chan, post, rbuf[(it + 1) & 1], rbuf[it & 1], msg, unsat_out, rec_run,
-                      !vn_records);
+        // (first && ingest_no_post: the kept variables' rows from `chan`; the FIRST form stores no posterior)
+        launch.cn_rec(first, vec, rec_t, g, stp, chan, (first && ingest_no_post) ? chan : post, rbuf[(it + 1) & 1], rbuf[it & 1],
+                      msg, unsat_out, rec_run, !vn_records);
       else if (lfree)
         launch.cn_lfree(first, vec, wide_mask, cn_t, g, stp, chan, post, m_in, m_out, unsat_out);
       else if (streaming)
@@ -271,7 +330,17 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
           compact(max_iterations - it, m_out, true, static_cast<uint32_t>(e_));
       }
     }
-    if (records && max_iterations > 0) {
+    // (2) the end of a call without a posterior: only the sign of the L-free variables' last posteriors is needed -- for the
+    // last syndrome and for the caller -- so the pack covers the rows the variable-node launch writes, the closing launch
+    // ballots the L-free variables' decisions into the packed words without storing a row (it runs BEHIND the pack: an L-free
+    // variable may lie among the packed rows), and the final emit launch reads the packed words
+    const bool close_hard = edges_no_post && records && lfree && max_iterations > 0;
+    if (close_hard) {
+      edges_ran |= kCallEdgeClose | kCallEdgeEmit;
+      pack(post, post_move_rows ? post_move_rows : n, w.hard_ok);
+      launch.vn_free_hard(vec, vn_free_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[max_iterations & 1], post, w.hardbits, W);
+      emit_hard = w.hardbits;
+    } else if (records && max_iterations > 0) {
       launch.vn_free_rec(vec, vn_free_t, g_free, st, d_free_rs_.get<uint32_t>(), chan, rbuf[max_iterations & 1], post, -1);
     } else if (lfree && max_iterations > 0) {
       // posterior of the L-free variables after the last iteration (no later check-node pass
@@ -281,7 +350,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     }
     if (max_iterations > 0) {
       // syndrome of the last posterior (flooding.rs:69-79 at iteration == max_iterations)
-      pack(post);
+      if (!close_hard) pack(post, n, nullptr);
       uint32_t *u = unsat[(max_iterations + 1) & 1];
       f.syndrome_of(w.hardbits, u);
       f.latch(u, static_cast<int32_t>(max_iterations));
@@ -387,7 +456,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
         timed_end(kKernelLayer, s);
       }
       // horizontal_layered.rs:66-78
-      pack(post);
+      pack(post, n, nullptr);
       f.syndrome_of(w.hardbits, w.unsat0);
       f.latch(w.unsat0, static_cast<int32_t>(it));
       if (checkpoint_due(it)) compact(max_iterations - it, msg, false, hl_rec ? m * 3 : static_cast<uint32_t>(e_));
@@ -395,6 +464,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
   }
 
   emit(zero_fill, 0);
+  last_call_edges_.fetch_or(edges_ran, std::memory_order_relaxed);
   HIP_TRY(hipGetLastError());
   return 0;
 }
