@@ -532,6 +532,77 @@ int32_t ldpc_toolbox_nr_rm_recover_f64_device(void *rm, double *llrs, size_t n, 
  * straggler-pooling budget, as "modulation" does. */
 int32_t ldpc_toolbox_sim_set_rate_match(void *sim, void *rm, size_t e, uint32_t rv, uint32_t qm);
 
+/* ===================================================================================
+ * PART 7 -- batched 5G NR transport block processing on the GPU (3GPP TS 38.212 5.1, 6.2.1, 7.2.1: CRC attachment;
+ * 5.2.2: code block segmentation with CRC24B and filler bits; 5.5 with the E_r of 5.4.2.1: code block concatenation).
+ * It takes payload bits to the batched encoder's input and the decoder's hard decisions back to a payload with the
+ * CRC verdicts, and it produces the F of PART 6.  The reference has none of it.
+ * =================================================================================== */
+
+/* The handle is (BG, A): base graph and payload size in bits, 1 <= A <= 1277992.  Everything else follows TS 38.212:
+ *   L_tb = 24 (gCRC24A) if A > 3824, else 16 (gCRC16);  B = A + L_tb;  Kcb = 8448 (BG 1) or 3840 (BG 2).
+ *   B <= Kcb: C = 1, L_cb = 0, B' = B.  Otherwise L_cb = 24 (gCRC24B), C = ceil(B / (Kcb - 24)), B' = B + 24 C.
+ *   K' = B' / C.  Kb = 22 (BG 1); BG 2: 10 if B > 640, 9 if B > 560, 8 if B > 192, else 6.
+ *   Zc = the smallest of the 51 lifting sizes with Kb Zc >= K';  K = 22 Zc or 10 Zc;  F = K - K';  n = 68 Zc or 52 Zc.
+ * The code blocks are codewords of "nr5g:BG:ZC" and are rate-matched by a PART 6 handle "nr5g:BG:ZC:F".
+ * spec: "nr5g-tb:BG:A", decimal.  NULL (message via ldpc_toolbox_last_error) for another spelling, a BG other than 1 or
+ * 2, an A outside the range, and a pair for which C does not divide B': the transport block sizes of TS 38.214 never
+ * produce one, and the standard has no padding rule for it.
+ * The constructor needs no GPU (`device` is used by the first batched call; -1 = LDPC_TOOLBOX_DEVICE, default 0). */
+void *ldpc_toolbox_nr_tb_ctor(const char *spec, int32_t device);
+void ldpc_toolbox_nr_tb_dtor(void *tb);
+/* key: "a", "base_graph", "tb_crc" (L_tb), "b", "c", "cb_crc" (L_cb), "k_prime", "k_b", "zc", "k", "fillers" (F), "n",
+ * "device" (-1 until the first batched call made the device state).  returns 0, or -1 for an unknown key. */
+int32_t ldpc_toolbox_nr_tb_get(void *tb, const char *key, int64_t *value);
+/* TS 38.212 7.2.2: the base graph for payload size a and target code rate `rate`: 2 if a <= 292, or a <= 3824 and
+ * rate <= 0.67, or rate <= 0.25; otherwise 1. */
+int32_t ldpc_toolbox_nr_base_graph(uint64_t a, double rate);
+/* TS 38.212 5.4.2.1, host only: the rate matching output lengths E_r of G coded bits, q = N_L Qm.  The first
+ * *c_lo = C - (G/q mod C) blocks get *e_lo = q floor(G / (q C)), the others *e_hi = q ceil(G / (q C)); they sum to G.
+ * A null argument, q == 0, G == 0, G > 0x7fffffff, q not dividing G or G / q < C: LDPC_TOOLBOX_ERR_ARGUMENT. */
+int32_t ldpc_toolbox_nr_tb_block_lengths(void *tb, uint64_t g, uint64_t q, uint64_t *e_lo, uint64_t *e_hi, uint64_t *c_lo);
+/* Conventions of every batched entry below.  Bytes hold one bit each; on input a byte equal to 1 is a one and anything
+ * else a zero, outputs are 0 or 1.  Code block rows are block-major: row r * batch + b is block r of transport block b,
+ * so the blocks that share one E are one contiguous batch for the rate matcher.
+ * A null handle or buffer, or a length that is not the handle's: LDPC_TOOLBOX_ERR_ARGUMENT before the GPU is touched,
+ * nothing written.  Without a GPU LDPC_TOOLBOX_ERR_DEVICE (there is no CPU path).  batch == 0 returns 0; batch is
+ * otherwise unlimited.  Input and output do not overlap.  One call at a time per handle.  Host pointers (staged through
+ * the handle's buffers) or, _device, device pointers and a hipStream_t: a stream = enqueue and return; NULL = the
+ * handle's own stream, ordered after what the legacy default stream holds at the call, synchronised on return.
+ *
+ * Segmentation: payload [batch][a], a = A, to rows [C * batch][k], k = K -- exactly the `input` of
+ * ldpc_toolbox_encoder_encode_batch_device on "nr5g:BG:ZC".  Bytes 0 .. K'-L_cb-1 of block r are bits r (K'-L_cb) .. of
+ * the normalised payload followed by its L_tb CRC bits; then, when C > 1, the 24 CRC24B bits over those bytes; then F
+ * zeros.  Parity bit p_0 is the coefficient of the highest power (5.1). */
+int32_t ldpc_toolbox_nr_tb_segment(void *tb, uint8_t *rows, size_t k, const uint8_t *payload, size_t a, size_t batch);
+int32_t ldpc_toolbox_nr_tb_segment_device(void *tb, uint8_t *rows, size_t k, const uint8_t *payload, size_t a, size_t batch,
+                                          void *hip_stream);
+/* The inverse with the verdicts: rows [C * batch][k] (the decode entries' `output` with output_len = K) to payload
+ * [batch][a], tb_ok [batch] and cb_ok [batch][C] (may be NULL), bytes 0 or 1.
+ *   cb_ok[b][r] = 1 exactly when the CRC24B remainder of the first K' bits of block r is zero;
+ *   tb_ok[b]    = 1 exactly when the CRC remainder of the reassembled B bits is zero;  with C = 1, cb_ok[b][0] = tb_ok[b].
+ * The filler columns are not read.  The payload is written whatever the flags say.
+ * An all-zero block passes every CRC: all three are plain polynomial remainders without an initial value, and the
+ * standard relies on scrambling to keep an all-zero transport block from occurring.  A receiver that may see all-zero
+ * hard decisions (an erased slot) has to test for them itself. */
+int32_t ldpc_toolbox_nr_tb_desegment(void *tb, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok, const uint8_t *rows, size_t k,
+                                     size_t batch);
+int32_t ldpc_toolbox_nr_tb_desegment_device(void *tb, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok, const uint8_t *rows,
+                                            size_t k, size_t batch, void *hip_stream);
+/* Code block concatenation (5.5).  With (e_lo, e_hi, c_lo) of the block lengths entry for (g, q): `packed` is c_lo * batch
+ * rows of e_lo bytes directly followed by (C - c_lo) * batch rows of e_hi bytes, both block-major -- what two
+ * ldpc_toolbox_nr_rm_match_device calls leave, the second writing behind the first -- and output is [batch][g] with block
+ * 0 first, bytes normalised.  (g, q) refused by the block lengths entry: LDPC_TOOLBOX_ERR_ARGUMENT. */
+int32_t ldpc_toolbox_nr_tb_concatenate(void *tb, uint8_t *output, size_t g, const uint8_t *packed, size_t q, size_t batch);
+int32_t ldpc_toolbox_nr_tb_concatenate_device(void *tb, uint8_t *output, size_t g, const uint8_t *packed, size_t q, size_t batch,
+                                              void *hip_stream);
+/* The inverse on received values: rx [batch][g] to `packed` in the layout above, the `rx` of two recover calls.  Values
+ * are copied bit for bit. */
+int32_t ldpc_toolbox_nr_tb_split_f32(void *tb, float *packed, const float *rx, size_t g, size_t q, size_t batch);
+int32_t ldpc_toolbox_nr_tb_split_f64(void *tb, double *packed, const double *rx, size_t g, size_t q, size_t batch);
+int32_t ldpc_toolbox_nr_tb_split_f32_device(void *tb, float *packed, const float *rx, size_t g, size_t q, size_t batch, void *hip_stream);
+int32_t ldpc_toolbox_nr_tb_split_f64_device(void *tb, double *packed, const double *rx, size_t g, size_t q, size_t batch, void *hip_stream);
+
 /* Standard-code generator (what the reference's `dvbs2` / `5g` / `ccsds` / `ccsds-c2` CLI
  * sub-commands print, src/cli/dvbs2.rs:91, src/cli/nr5g.rs:46, src/cli/ccsds.rs:70): writes the
  * padded alist text of `spec` ("dvbs2:R1_2", "nr5g:1:384", "ar4ja:1/2:1024", "c2") into

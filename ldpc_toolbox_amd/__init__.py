@@ -7,9 +7,10 @@ from .decoder import (ALL_IMPLEMENTATIONS, CORRECTED_MINSUM_IMPLEMENTATIONS, FAS
 from .bch import BchCode
 from .demodulator import Demodulator
 from .nr_rate_match import NrRateMatcher
+from .nr_transport_block import NrTransportBlock, nr_base_graph
 from .sparse import SparseMatrix
 
 code_alist = _capi.code_alist
 
 __all__ = ["ALL_IMPLEMENTATIONS", "BchCode", "CORRECTED_MINSUM_IMPLEMENTATIONS", "FAST_IMPLEMENTATIONS", "I8_IMPLEMENTATIONS", "DecoderImplementation", "DecoderOutput", "DecoderUnavailable", "Demodulator", "Encoder",
-           "IMPLEMENTATIONS", "MINSUM_I8_IMPLEMENTATIONS", "LdpcDecoder", "NrRateMatcher", "Simulator", "SparseMatrix", "code_alist"]
+           "IMPLEMENTATIONS", "MINSUM_I8_IMPLEMENTATIONS", "LdpcDecoder", "NrRateMatcher", "NrTransportBlock", "Simulator", "SparseMatrix", "code_alist", "nr_base_graph"]

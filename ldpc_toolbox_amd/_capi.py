@@ -81,6 +81,21 @@ SYMBOLS = [
     "ldpc_toolbox_nr_rm_recover_f32_device",
     "ldpc_toolbox_nr_rm_recover_f64_device",
     "ldpc_toolbox_sim_set_rate_match",
+    "ldpc_toolbox_nr_tb_ctor",
+    "ldpc_toolbox_nr_tb_dtor",
+    "ldpc_toolbox_nr_tb_get",
+    "ldpc_toolbox_nr_base_graph",
+    "ldpc_toolbox_nr_tb_block_lengths",
+    "ldpc_toolbox_nr_tb_segment",
+    "ldpc_toolbox_nr_tb_segment_device",
+    "ldpc_toolbox_nr_tb_desegment",
+    "ldpc_toolbox_nr_tb_desegment_device",
+    "ldpc_toolbox_nr_tb_concatenate",
+    "ldpc_toolbox_nr_tb_concatenate_device",
+    "ldpc_toolbox_nr_tb_split_f32",
+    "ldpc_toolbox_nr_tb_split_f64",
+    "ldpc_toolbox_nr_tb_split_f32_device",
+    "ldpc_toolbox_nr_tb_split_f64_device",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
     "ldpc_toolbox_device_count",
@@ -282,6 +297,31 @@ def lib():
         f.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32, C.c_double, i32, vp]
     L.ldpc_toolbox_sim_set_rate_match.restype = i32
     L.ldpc_toolbox_sim_set_rate_match.argtypes = [vp, vp, sz, u32, u32]
+    L.ldpc_toolbox_nr_tb_ctor.restype = vp
+    L.ldpc_toolbox_nr_tb_ctor.argtypes = [cp, i32]
+    L.ldpc_toolbox_nr_tb_dtor.restype = None
+    L.ldpc_toolbox_nr_tb_dtor.argtypes = [vp]
+    L.ldpc_toolbox_nr_tb_get.restype = i32
+    L.ldpc_toolbox_nr_tb_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
+    L.ldpc_toolbox_nr_base_graph.restype = i32
+    L.ldpc_toolbox_nr_base_graph.argtypes = [C.c_uint64, C.c_double]
+    L.ldpc_toolbox_nr_tb_block_lengths.restype = i32
+    L.ldpc_toolbox_nr_tb_block_lengths.argtypes = [vp, C.c_uint64, C.c_uint64] + [C.POINTER(C.c_uint64)] * 3
+    L.ldpc_toolbox_nr_tb_segment.restype = i32
+    L.ldpc_toolbox_nr_tb_segment.argtypes = [vp, vp, sz, vp, sz, sz]
+    L.ldpc_toolbox_nr_tb_segment_device.restype = i32
+    L.ldpc_toolbox_nr_tb_segment_device.argtypes = [vp, vp, sz, vp, sz, sz, vp]
+    L.ldpc_toolbox_nr_tb_desegment.restype = i32
+    L.ldpc_toolbox_nr_tb_desegment.argtypes = [vp, vp, sz, vp, vp, vp, sz, sz]
+    L.ldpc_toolbox_nr_tb_desegment_device.restype = i32
+    L.ldpc_toolbox_nr_tb_desegment_device.argtypes = [vp, vp, sz, vp, vp, vp, sz, sz, vp]
+    for name in ("concatenate", "split_f32", "split_f64"):
+        f = getattr(L, "ldpc_toolbox_nr_tb_" + name)
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz] if name == "concatenate" else [vp, vp, vp, sz, sz, sz]
+        fd = getattr(L, "ldpc_toolbox_nr_tb_" + name + "_device")
+        fd.restype = i32
+        fd.argtypes = f.argtypes + [vp]
     L.ldpc_toolbox_code_alist.restype = sz
     L.ldpc_toolbox_code_alist.argtypes = [cp, vp, sz]
     L.ldpc_toolbox_alist_normalize.restype = sz

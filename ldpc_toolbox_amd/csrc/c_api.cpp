@@ -20,6 +20,7 @@
 #include "device_decoder.h"
 #include "device_encoder.h"
 #include "device_nr_rm.h"
+#include "device_nr_tb.h"
 #include "encoder.h"
 #include "implementation.h"
 #include "simulator.h"
@@ -76,6 +77,13 @@ struct NrRmHandle {
   int device = 0;
   // the device state: made at the first batched call
   std::unique_ptr<ldpc::DeviceNrRm> dev;
+};
+
+struct NrTbHandle {
+  ldpc::nrtb::Config c;
+  int device = 0;
+  // the device state: made at the first batched call
+  std::unique_ptr<ldpc::DeviceNrTb> dev;
 };
 
 // a device index: decimal digits only (no sign, no trailing characters)
@@ -466,6 +474,104 @@ int32_t nr_rm_recover(void *rm, void *llrs, size_t n, const void *rx, size_t e, 
   if (rc == 0) return 0;
   set_error(h->dev->last_error());
   return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+// "nr5g-tb:BG:A": decimal fields, nothing else
+bool parse_nr_tb_spec(const char *spec, ldpc::nrtb::Config *c, std::string *err) {
+  const std::string text = spec;
+  const std::string digits = "0123456789";
+  const size_t first = text.find(':'), second = first == std::string::npos ? first : text.find(':', first + 1);
+  bool ok = second != std::string::npos && text.compare(0, first, "nr5g-tb") == 0;
+  int64_t v[2] = {0, 0};
+  if (ok) {
+    const std::string t[2] = {text.substr(first + 1, second - first - 1), text.substr(second + 1)};
+    for (int i = 0; ok && i < 2; i++) {
+      ok = !t[i].empty() && t[i].size() <= 9 && t[i].find_first_not_of(digits) == std::string::npos;
+      if (ok) v[i] = std::strtoll(t[i].c_str(), nullptr, 10);
+    }
+  }
+  if (!ok) {
+    *err = "invalid transport block spec (expected nr5g-tb:BG:A)";
+    return false;
+  }
+  if (const char *why = ldpc::nrtb::make_config(v[0], v[1], c)) {
+    *err = why;
+    return false;
+  }
+  return true;
+}
+
+// 0 with the handle's device state made, or LDPC_TOOLBOX_ERR_DEVICE
+int32_t nr_tb_device_state(NrTbHandle *h) {
+  if (h->dev) return 0;
+  if (h->device < 0) {
+    set_error("LDPC_TOOLBOX_DEVICE is not a decimal GPU index");
+    return LDPC_TOOLBOX_ERR_DEVICE;
+  }
+  std::string err;
+  h->dev.reset(ldpc::DeviceNrTb::create(h->c, h->device, &err));
+  if (!h->dev) {
+    set_error(err);
+    return LDPC_TOOLBOX_ERR_DEVICE;
+  }
+  return 0;
+}
+
+int32_t nr_tb_argument_error(const char *why) {
+  set_error(why);
+  return LDPC_TOOLBOX_ERR_ARGUMENT;
+}
+
+int32_t nr_tb_result(NrTbHandle *h, int rc) {
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+int32_t nr_tb_segment(void *tb, uint8_t *rows, size_t k, const uint8_t *payload, size_t a, size_t batch, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrTbHandle *>(tb);
+  if (!h) return nr_tb_argument_error("null transport block handle");
+  if (const char *why = ldpc::nrtb::row_lengths_error(h->c, a, k)) return nr_tb_argument_error(why);
+  if (batch == 0) return 0;
+  if (!payload || !rows) return nr_tb_argument_error("null input or output buffer");
+  if (int32_t rc = nr_tb_device_state(h)) return rc;
+  return nr_tb_result(h, on_device ? h->dev->segment_device(payload, rows, batch, static_cast<hipStream_t>(stream))
+                                   : h->dev->segment_host(payload, rows, batch));
+}
+
+int32_t nr_tb_desegment(void *tb, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok, const uint8_t *rows, size_t k, size_t batch,
+                        bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrTbHandle *>(tb);
+  if (!h) return nr_tb_argument_error("null transport block handle");
+  if (const char *why = ldpc::nrtb::row_lengths_error(h->c, a, k)) return nr_tb_argument_error(why);
+  if (batch == 0) return 0;
+  if (!payload || !rows || !tb_ok) return nr_tb_argument_error("null input or output buffer");
+  if (int32_t rc = nr_tb_device_state(h)) return rc;
+  return nr_tb_result(h, on_device ? h->dev->desegment_device(rows, payload, tb_ok, cb_ok, batch, static_cast<hipStream_t>(stream))
+                                   : h->dev->desegment_host(rows, payload, tb_ok, cb_ok, batch));
+}
+
+// concatenate (bytes, packed -> [batch][G]) and split (floats or doubles, [batch][G] -> packed)
+int32_t nr_tb_repack(void *tb, void *output, const void *input, size_t g, size_t q, size_t batch, bool split, bool f64, bool on_device,
+                     void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrTbHandle *>(tb);
+  if (!h) return nr_tb_argument_error("null transport block handle");
+  ldpc::nrtb::Lengths l;
+  if (const char *why = ldpc::nrtb::make_lengths(h->c, g, q, &l)) return nr_tb_argument_error(why);
+  if (batch == 0) return 0;
+  if (!input || !output) return nr_tb_argument_error("null input or output buffer");
+  if (int32_t rc = nr_tb_device_state(h)) return rc;
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  int rc;
+  if (split)
+    rc = on_device ? h->dev->split_device(input, output, f64, l, batch, s) : h->dev->split_host(input, output, f64, l, batch);
+  else
+    rc = on_device ? h->dev->concatenate_device(static_cast<const uint8_t *>(input), static_cast<uint8_t *>(output), l, batch, s)
+                   : h->dev->concatenate_host(static_cast<const uint8_t *>(input), static_cast<uint8_t *>(output), l, batch);
+  return nr_tb_result(h, rc);
 }
 
 template <typename F>
@@ -1240,6 +1346,116 @@ int32_t ldpc_toolbox_sim_set_rate_match(void *sim, void *rm, size_t e, uint32_t 
   if (s->set_rate_match(h ? &h->c : nullptr, e, rv, qm)) return 0;
   set_error(s->last_error());
   return -1;
+}
+
+// ---- PART 7: batched 5G NR transport block CRC, segmentation and concatenation -----------------------
+
+void *ldpc_toolbox_nr_tb_ctor(const char *spec, int32_t device) {
+  g_last_error.clear();
+  if (!spec) {
+    set_error("null transport block spec");
+    return nullptr;
+  }
+  auto h = std::make_unique<NrTbHandle>();
+  std::string err;
+  if (!parse_nr_tb_spec(spec, &h->c, &err)) {
+    set_error(err);
+    return nullptr;
+  }
+  h->device = device < 0 ? default_device() : device;
+  return h.release();
+}
+
+void ldpc_toolbox_nr_tb_dtor(void *tb) { delete static_cast<NrTbHandle *>(tb); }
+
+int32_t ldpc_toolbox_nr_tb_get(void *tb, const char *key, int64_t *value) {
+  auto *h = static_cast<NrTbHandle *>(tb);
+  if (!h || !key || !value) return -1;
+  const std::string k = key;
+  const ldpc::nrtb::Config &c = h->c;
+  if (k == "a")
+    *value = c.a;
+  else if (k == "base_graph")
+    *value = c.bg;
+  else if (k == "tb_crc")
+    *value = c.l_tb;
+  else if (k == "b")
+    *value = c.b;
+  else if (k == "c")
+    *value = c.c;
+  else if (k == "cb_crc")
+    *value = c.l_cb;
+  else if (k == "k_prime")
+    *value = c.k_prime;
+  else if (k == "k_b")
+    *value = c.kb;
+  else if (k == "zc")
+    *value = c.zc;
+  else if (k == "k")
+    *value = c.k;
+  else if (k == "fillers")
+    *value = c.fillers;
+  else if (k == "n")
+    *value = c.n;
+  else if (k == "device")
+    *value = h->dev ? h->dev->device() : -1;
+  else
+    return -1;
+  return 0;
+}
+
+int32_t ldpc_toolbox_nr_base_graph(uint64_t a, double rate) { return ldpc::nrtb::base_graph(a, rate); }
+
+int32_t ldpc_toolbox_nr_tb_block_lengths(void *tb, uint64_t g, uint64_t q, uint64_t *e_lo, uint64_t *e_hi, uint64_t *c_lo) {
+  g_last_error.clear();
+  auto *h = static_cast<NrTbHandle *>(tb);
+  if (!h || !e_lo || !e_hi || !c_lo) return nr_tb_argument_error("null argument");
+  if (const char *why = ldpc::nrtb::block_lengths(h->c, g, q, e_lo, e_hi, c_lo)) return nr_tb_argument_error(why);
+  return 0;
+}
+
+int32_t ldpc_toolbox_nr_tb_segment(void *tb, uint8_t *rows, size_t k, const uint8_t *payload, size_t a, size_t batch) {
+  return nr_tb_segment(tb, rows, k, payload, a, batch, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_tb_segment_device(void *tb, uint8_t *rows, size_t k, const uint8_t *payload, size_t a, size_t batch,
+                                          void *hip_stream) {
+  return nr_tb_segment(tb, rows, k, payload, a, batch, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_tb_desegment(void *tb, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok, const uint8_t *rows, size_t k,
+                                     size_t batch) {
+  return nr_tb_desegment(tb, payload, a, tb_ok, cb_ok, rows, k, batch, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_tb_desegment_device(void *tb, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok, const uint8_t *rows,
+                                            size_t k, size_t batch, void *hip_stream) {
+  return nr_tb_desegment(tb, payload, a, tb_ok, cb_ok, rows, k, batch, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_tb_concatenate(void *tb, uint8_t *output, size_t g, const uint8_t *packed, size_t q, size_t batch) {
+  return nr_tb_repack(tb, output, packed, g, q, batch, false, false, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_tb_concatenate_device(void *tb, uint8_t *output, size_t g, const uint8_t *packed, size_t q, size_t batch,
+                                              void *hip_stream) {
+  return nr_tb_repack(tb, output, packed, g, q, batch, false, false, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_tb_split_f32(void *tb, float *packed, const float *rx, size_t g, size_t q, size_t batch) {
+  return nr_tb_repack(tb, packed, rx, g, q, batch, true, false, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_tb_split_f64(void *tb, double *packed, const double *rx, size_t g, size_t q, size_t batch) {
+  return nr_tb_repack(tb, packed, rx, g, q, batch, true, true, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_tb_split_f32_device(void *tb, float *packed, const float *rx, size_t g, size_t q, size_t batch, void *hip_stream) {
+  return nr_tb_repack(tb, packed, rx, g, q, batch, true, false, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_tb_split_f64_device(void *tb, double *packed, const double *rx, size_t g, size_t q, size_t batch, void *hip_stream) {
+  return nr_tb_repack(tb, packed, rx, g, q, batch, true, true, true, hip_stream);
 }
 
 size_t ldpc_toolbox_code_alist(const char *spec, char *buffer, size_t buffer_len) {

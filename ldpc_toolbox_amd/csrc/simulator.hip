@@ -10,6 +10,7 @@
 #include "device_bch.hip.h"       // and the batched BCH code
 #include "device_encoder.hip.h"  // the batched GPU encoder lives in this translation unit
 #include "device_nr_rm.hip.h"     // and the batched NR rate matcher
+#include "device_nr_tb.hip.h"     // and the NR transport block CRCs, segmentation and concatenation
 #include "frame_gen.hip.h"
 #include "implementation.h"
 #include "sparse.h"
