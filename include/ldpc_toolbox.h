@@ -207,7 +207,10 @@ int32_t ldpc_toolbox_decoder_syndrome_device(void *decoder, const uint8_t *bits,
  * of the variable-node launch's record fetches that coincide inside a workgroup's step; 0 when off), "last_vn_chains" (1:
  * they walked that order in chains, "vn_chains": a record two consecutive entries of a wave share stays in its registers),
  * "vn_chain_saved_permille" (thousandths of the record fetches the chained walk does not issue; 0 when off), "flags8" (the tunable
- * below, as set), "last_record_flag_bytes"
+ * below, as set), "cn_row_shape" (the tunable below, as set), "last_cn_row_shape" (1: the last decode call's check-node
+ * launches behind the first iteration took the row-shape form -- a straight-line row step in the runs of the walk whose rows
+ * all have the graph's dominant shape), "cn_row_shape_runs" / "cn_row_shape_rows" (the runs of the walk that conformed at that
+ * call's "rec_run", and the check rows in them; 0 when the form did not run), "last_record_flag_bytes"
  * (bytes of a record's flags word in memory in the last decode call: 1 with "flags8" on rows of at most 7 edges, else 2, 4
  * or 8 = "record_flag_bits" / 8; 0: that call kept no flooding row records), "call_edges" (the tunable below, as set),
  * "last_call_edges" (read-only bit mask: which of that tunable's shortcuts the last decode call took -- 1: the ingest launch
@@ -220,9 +223,9 @@ int32_t ldpc_toolbox_decoder_syndrome_device(void *decoder, const uint8_t *bits,
  * 8 * beta; 0 for every other name).  returns 0 or -1 (unknown key). */
 int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value);
 /* Tunables: "group_size" (codewords decoded together; 0 = automatic), "profiling" (0/1:
- * bracket the check/variable/layer launches with hipEvents), and 32 launch / execution choices -- "waves", "vec", "tile",
+ * bracket the check/variable/layer launches with hipEvents), and 33 launch / execution choices -- "waves", "vec", "tile",
  * "lfree", "records", "rec_run", "rec_quiet", "rec_long", "call_edges" (0/1, default 1: the launches around a call's iterations trimmed to what
- * its result needs, see "last_call_edges" above; 0: as they were), "vn_event", "vn_records", "vn_bundles", "vn_chains", "vn_chain_len", "flags8", "staged_minsum", "cn_reg", "hl_reg", "hl_records",
+ * its result needs, see "last_call_edges" above; 0: as they were), "vn_event", "vn_records", "vn_bundles", "vn_chains", "vn_chain_len", "flags8", "cn_row_shape", "staged_minsum", "cn_reg", "hl_reg", "hl_records",
  * "serial_levels", "latency", "latency_edge", "compact", "compact_first", "compact_every", "lanes", "lane_threads",
  * "lane_pace", "lead", "poll", "throttle", "pooling" (ldpc_toolbox_amd/csrc/device_decoder.h says what each selects; results never
  * depend on them: each chooses between forms the test suite compares bit for bit).  "throttle" (0/1, default 0):

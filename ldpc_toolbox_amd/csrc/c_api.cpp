@@ -889,6 +889,14 @@ int32_t ldpc_toolbox_decoder_get(void *decoder, const char *key, int64_t *value)
     *value = d.vn_chain_saved_permille();
   else if (k == "flags8")
     *value = d.flags8();
+  else if (k == "cn_row_shape")
+    *value = d.cn_row_shape();
+  else if (k == "last_cn_row_shape")
+    *value = d.last_cn_row_shape();
+  else if (k == "cn_row_shape_runs")
+    *value = d.cn_row_shape_runs();
+  else if (k == "cn_row_shape_rows")
+    *value = d.cn_row_shape_rows();
   else if (k == "last_record_flag_bytes")
     *value = d.last_record_flag_bytes();
   else if (k == "call_edges")

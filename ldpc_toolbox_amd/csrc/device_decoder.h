@@ -80,6 +80,13 @@ class DeviceDecoder {
   // (graph_tables.h, count_vn_chain_fetches); 0 when off
   uint32_t last_vn_chains() const { return last_vn_chains_.load(std::memory_order_relaxed) ? 1 : 0; }
   uint32_t vn_chain_saved_permille() const { return last_vn_chain_saved_.load(std::memory_order_relaxed); }
+  // "cn_row_shape" as set; whether the last decode call's check-node launches behind the first iteration took the row-shape
+  // form; and the runs of the walk that conformed at that call's run length, and the rows in them (graph_tables.h,
+  // count_row_shape_runs); 0 when the form did not run
+  uint32_t cn_row_shape() const { return opt_cn_row_shape_ ? 1 : 0; }
+  uint32_t last_cn_row_shape() const { return last_cn_row_shape_.load(std::memory_order_relaxed) ? 1 : 0; }
+  uint32_t cn_row_shape_runs() const { return last_cn_row_shape() ? last_cn_shape_runs_.load(std::memory_order_relaxed) : 0; }
+  uint32_t cn_row_shape_rows() const { return last_cn_row_shape() ? last_cn_shape_rows_.load(std::memory_order_relaxed) : 0; }
   // "call_edges" as set, and which of its shortcuts the groups of the last decode call took (kCallEdge* below, OR-ed)
   uint32_t call_edges() const { return opt_call_edges_ ? 1 : 0; }
   uint32_t last_call_edges() const { return last_call_edges_.load(std::memory_order_relaxed); }
@@ -96,7 +103,7 @@ class DeviceDecoder {
   void set_min_group(size_t g) { min_group_ = g; }
   // codewords per group a call of `batch` codewords is cut into (the set value, else a default that grows for small graphs)
   size_t preferred_group(size_t batch) const { return pick_group(batch); }
-  // The 32 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
+  // The 33 options of set_option (26 in round 6; there were 54: the tuning knobs whose alternatives had all been measured within a
   // percent are constants now, see kStreamBlock ... below).  Results never depend on any of them; each selects between
   // forms that tests/ compare bit for bit.  returns false for an unknown key.
   //   which kernels run   "lfree" (0: plain flooding min-sum kernels), "records" (0 / 1 / 2: per-edge messages / row records
@@ -106,7 +113,9 @@ class DeviceDecoder {
   //                       form's kept list in variable order / in bundles of the variables a workgroup sums together), "vn_chains" (0 / 1: the
   //                       bundled list walked entry by entry / in chains whose shared record stays in registers; "vn_chain_len":
   //                       4, 8 or 16 entries per chain), "flags8" (0 / 1: the
-  //                       16-bit flags of rows of at most 7 edges stored as half-words / as bytes), "rec_long"
+  //                       16-bit flags of rows of at most 7 edges stored as half-words / as bytes), "cn_row_shape" (0 / 1: with
+  //                       "vn_records" and "flags8" in f32, the generic row step in every run of the check-node walk / a
+  //                       straight-line one in the runs whose rows all have the graph's dominant shape), "rec_long"
   //                       (1: the record kernel's long-row variant whatever the graph), "call_edges" (0: the launches around a
   //                       call's iterations as they were: opt_call_edges_ below), "staged_minsum" (1: Minsum through
   //                       the generic LDS-staged kernel), "cn_reg" / "hl_reg" / "hl_records" (0: the LDS-staged / two-pass /
@@ -271,6 +280,18 @@ class DeviceDecoder {
   } vn_chain_at_[3];
   std::atomic<bool> last_vn_chains_{false};
   std::atomic<uint32_t> last_vn_chain_saved_{0};
+  // "cn_row_shape": with "vn_records" and "flags8" in f32, the check-node launches behind the first iteration take the record
+  // kernel's row-shape form (kernels_flooding.hip.h, SHAPE): runs of the walk whose rows all have the graph's dominant shape
+  // (graph_tables.h, build_row_shapes) run a straight-line row step, every other run the generic one, in the same launch.  The
+  // same operations in the same order: results do not depend on it.  A call whose run length ("rec_run") leaves no
+  // conforming run launches the generic form.  (default: on where "flags8" is -- plain Minsumf32 on DVB-S2 normal frames at
+  // rate 1/2, the one configuration timed: +2.1 % codewords/s, profiles/cn_row_shape.txt; off for every other code, rule and
+  // precision, where the key selects it: f32 only)
+  bool opt_cn_row_shape_ = false;
+  std::vector<uint32_t> row_shape_span_;  // RowShapeTables::span, as uploaded behind the peer words (empty: no such tables)
+  uint32_t row_shape_kind_ = 0;           // RowShapeTables::kind: the order of the two parity slots the counts are about
+  std::atomic<bool> last_cn_row_shape_{false};
+  std::atomic<uint32_t> last_cn_shape_runs_{0}, last_cn_shape_rows_{0};
   // "call_edges": what a call does around its iterations, trimmed to what its result needs (profiles/call_edges.txt).  On the
   // flooding record path of a call that asks for no posterior: the ingest launch stores the input once, not twice (the first
   // check-node launch reads `chan` in the posterior's place); the last pack covers the rows the variable-node launch writes and

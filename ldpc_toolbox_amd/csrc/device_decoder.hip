@@ -124,7 +124,17 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
       d->rec_prefers_ = rr.rec_prefers;
       d->rec_w_ = rr.rec_w;
       d->rec_flag_bits_ = rr.flag_bits;
-      ok = up(rr.keep_pos, &d->d_keep_pos_) && up(rr.peer, &d->d_edge_peer_) && up(rr.free_rs, &d->d_free_rs_);
+      // "cn_row_shape": the rows' shape counts behind the peer words, at n_edges + kTablePad (graph_tables.h, build_row_shapes)
+      std::vector<uint32_t> peer_words = rr.peer;
+      if (peer_words.size() == size_t(g.n_edges) + kTablePad) {
+        const RowShapeTables shapes = build_row_shapes(g, rr, false);  // (kind and span: no signatures, no histogram)
+        if (shapes.kind != kRowShapeNone) {
+          d->row_shape_kind_ = shapes.kind;
+          d->row_shape_span_ = shapes.span;
+          peer_words.insert(peer_words.end(), d->row_shape_span_.begin(), d->row_shape_span_.end());
+        }
+      }
+      ok = up(rr.keep_pos, &d->d_keep_pos_) && up(peer_words, &d->d_edge_peer_) && up(rr.free_rs, &d->d_free_rs_);
       d->rec_ready_ = ok;
       const KeepRsTable kr = (ok && rr.flag_bits == 16) ? build_keep_rs(g, lf) : KeepRsTable();
       if (kr.ready) {
@@ -168,6 +178,9 @@ DeviceDecoder *DeviceDecoder::create(const SparseMatrix &h, const Implementation
       d->opt_vn_bundles_ = d->opt_vn_records_ && d->bundle_rs_at_ != 0;
       // "vn_chains", the bundled list walked in chains: the same one configuration (profiles/vn_chains.txt)
       d->opt_vn_chains_ = d->opt_vn_bundles_ && d->vn_chain_at_[0].rs_at != 0;
+      // "cn_row_shape", the straight-line row step of the check-node launch: the same one configuration
+      // (profiles/cn_row_shape.txt)
+      d->opt_cn_row_shape_ = d->opt_flags8_ && !d->row_shape_span_.empty();
     }
   }
   if (ok && flooding_minsum && !impl.f64) {
@@ -260,6 +273,8 @@ bool DeviceDecoder::set_option(const std::string &key, int64_t value) {
     opt_vn_records_ = v != 0;
   else if (key == "flags8")
     opt_flags8_ = v != 0;
+  else if (key == "cn_row_shape")
+    opt_cn_row_shape_ = v != 0;
   else if (key == "vn_bundles")
     opt_vn_bundles_ = v != 0;
   else if (key == "vn_chains")

@@ -4,6 +4,8 @@
 #pragma once
 #include <algorithm>
 #include <cstdint>
+#include <string>
+#include <utility>
 #include <vector>
 
 #include "record_flags8.h"
@@ -134,6 +136,120 @@ inline RowRecordTables build_row_record_tables(const SparseMatrix::Csr &g, const
   t.peer.resize(t.peer.size() + kTablePad, dev::kPeerKeep);
   t.ready = true;
   return t;
+}
+
+// ROW SHAPES ("cn_row_shape", cn_minsum_rec_kernel's SHAPE form): what the record kernel otherwise learns per row and slot
+// from the peer words, as a signature per row, and which runs of the kernel's walk have a shape the kernel has
+// straight-line code for.
+//   * signature of a row: "<k>:" and a letter per remaining slot, k the number of kept slots at the front (peer word with
+//     kPeerKeep).  P: L-free, the other edge in the row before (row order, c - 1); N: in the row after; S: single, degree 1;
+//     F: far, any other row; T: twin, a second degree-2 variable on a pair of rows an earlier slot of this row already joins;
+//     K: a kept slot behind an L-free one.
+//   * a row FITS the straight-line step of kind "PN" (kRowShapePN) when its signature is kRowShapeKept kept slots, then P,
+//     then N, AND the two peers sit where the step takes them from without a look: P's other edge in the N slot of row
+//     c - 1, N's in the P slot of row c + 1, the variable's first edge (kPeerWriter) the N one.  Kind "NP" (kRowShapeNP): the
+//     same with the two L-free slots the other way round.  The tables are made for ONE kind per graph, the one more rows
+//     fit (ties: PN).  dvbs2:R1_2 read from its alist, as every decoder's graph is (rows sorted by column), is PN: 32 398 of
+//     its 32 400 rows have the signature "5:PN" and 32 397 of them fit (row 1 sits behind the first row, "5:N", one edge
+//     short), the last row is "5:PS"; the built-in tables as codes.cpp lists them, the parity bit shared with the next row
+//     first, are NP: 32 398 rows "5:NP", all fitting.  At a run of 8 both leave the first and the last run to the generic step
+//     (tests/cn_row_shape_driver.cpp prints both histograms).  A row with the signature may still not fit: behind a
+//     shorter row, or one with a second degree-2 variable, the peer's slot is another.
+constexpr uint32_t kRowShapeKept = 5;
+enum : uint32_t { kRowShapeNone = 0, kRowShapePN = 1, kRowShapeNP = 2 };
+struct RowShapeTables {
+  // these two only `with_signatures` (the test driver, a printout): a decoder uses `kind` and `span`
+  std::vector<std::string> signature;                           // per row
+  std::vector<std::pair<std::string, uint32_t>> histogram;      // signature -> rows, most frequent first (ties: by name)
+  uint32_t kind = kRowShapeNone;                                // the kind `fits` and `span` are about (none: no row fits either)
+  std::vector<uint8_t> fits;                                    // per row
+  std::vector<uint32_t> span;                                   // per row, see above
+  uint32_t fitting_rows = 0;
+};
+inline RowShapeTables build_row_shapes(const SparseMatrix::Csr &g, const RowRecordTables &rr, bool with_signatures = true) {
+  RowShapeTables t;
+  if (!rr.ready) return t;
+  const uint32_t M = g.n_rows;
+  if (with_signatures) t.signature.resize(M);
+  t.span.assign(M, 0);
+  std::vector<uint8_t> fits_pn(M, 0), fits_np(M, 0);
+  uint32_t n_pn = 0, n_np = 0;
+  std::vector<uint32_t> seen;  // peer rows of the L-free slots so far
+  std::string s;               // the row's signature (one buffer for all rows)
+  for (uint32_t c = 0; c < M; c++) {
+    const uint32_t e0 = g.row_ptr[c], d = g.row_ptr[c + 1] - e0;
+    uint32_t k = 0;
+    while (k < d && (rr.peer[e0 + k] & dev::kPeerKeep)) k++;
+    s = std::to_string(k);
+    s.push_back(':');
+    seen.clear();
+    for (uint32_t u = k; u < d; u++) {
+      const uint32_t p = rr.peer[e0 + u], prow = (p >> 6) & dev::kPeerRowMask;
+      char ch;
+      if (p & dev::kPeerKeep)
+        ch = 'K';
+      else if (prow == dev::kPeerSingle)
+        ch = 'S';
+      else if (std::find(seen.begin(), seen.end(), prow) != seen.end())
+        ch = 'T';
+      else if (prow + 1 == c)
+        ch = 'P';
+      else if (prow == c + 1)
+        ch = 'N';
+      else
+        ch = 'F';
+      if (!(p & dev::kPeerKeep) && prow != dev::kPeerSingle) seen.push_back(prow);
+      s.push_back(ch);
+    }
+    if (k == kRowShapeKept && d == kRowShapeKept + 2) {
+      const bool pn = s.compare(s.size() - 2, 2, "PN") == 0, np = s.compare(s.size() - 2, 2, "NP") == 0;
+      if (pn || np) {
+        const uint32_t p_slot = pn ? kRowShapeKept : kRowShapeKept + 1, n_slot = pn ? kRowShapeKept + 1 : kRowShapeKept;
+        const uint32_t pp = rr.peer[e0 + p_slot], pn_word = rr.peer[e0 + n_slot];
+        const bool fit = (pp & 63u) == n_slot && (pn_word & 63u) == p_slot && !(pp & dev::kPeerWriter) && (pn_word & dev::kPeerWriter);
+        (pn ? fits_pn : fits_np)[c] = fit;
+        (pn ? n_pn : n_np) += fit;
+      }
+    }
+    if (with_signatures) t.signature[c] = s;
+  }
+  t.kind = (n_pn == 0 && n_np == 0) ? kRowShapeNone : (n_pn >= n_np ? kRowShapePN : kRowShapeNP);
+  t.fits = t.kind == kRowShapeNP ? std::move(fits_np) : std::move(fits_pn);
+  t.fitting_rows = t.kind == kRowShapeNP ? n_np : n_pn;
+  for (uint32_t c = M; c-- > 0;)
+    if (t.fits[c]) t.span[c] = std::min<uint32_t>(0xFFFFu, 1 + (c + 1 < M ? (t.span[c + 1] & 0xFFFFu) : 0u));
+  for (uint32_t c = 0; c < M; c++)
+    if (t.fits[c]) t.span[c] |= std::min<uint32_t>(0xFFFFu, 1 + (c > 0 ? (t.span[c - 1] >> 16) : 0u)) << 16;
+  if (!with_signatures) return t;
+  std::vector<std::string> sorted = t.signature;
+  std::sort(sorted.begin(), sorted.end());
+  for (size_t i = 0; i < sorted.size();) {
+    size_t j = i;
+    while (j < sorted.size() && sorted[j] == sorted[i]) j++;
+    t.histogram.emplace_back(sorted[i], static_cast<uint32_t>(j - i));
+    i = j;
+  }
+  std::stable_sort(t.histogram.begin(), t.histogram.end(), [](const auto &a, const auto &b) { return a.second > b.second; });
+  return t;
+}
+// the kernel's test: run r of `run` rows (rows r * run .. , the last run shorter; even runs walk upwards from their first row,
+// odd ones downwards from their last) is all fitting rows
+inline bool row_shape_run_conforms(const std::vector<uint32_t> &span, uint32_t n_rows, uint32_t run, uint32_t r) {
+  const uint64_t lo = uint64_t(r) * run;
+  if (run == 0 || lo >= n_rows) return false;
+  const uint32_t hi = static_cast<uint32_t>(std::min<uint64_t>(lo + run, n_rows)), len = hi - static_cast<uint32_t>(lo);
+  const uint32_t w = span[(r & 1u) ? hi - 1 : static_cast<uint32_t>(lo)];
+  return ((r & 1u) ? w >> 16 : w & 0xFFFFu) >= len;
+}
+// runs of the walk that conform at this run length, and the rows in them
+inline void count_row_shape_runs(const std::vector<uint32_t> &span, uint32_t n_rows, uint32_t run, uint32_t *runs, uint32_t *rows) {
+  *runs = *rows = 0;
+  if (run == 0 || span.size() < n_rows) return;
+  for (uint32_t r = 0; uint64_t(r) * run < n_rows; r++)
+    if (row_shape_run_conforms(span, n_rows, run, r)) {
+      *runs += 1;
+      *rows += static_cast<uint32_t>(std::min<uint64_t>(uint64_t(r) * run + run, n_rows) - uint64_t(r) * run);
+    }
 }
 
 // The variable-node kernel's record source (kernels_flooding.hip.h, vn_kernel's record form): for every edge of the kept list, in

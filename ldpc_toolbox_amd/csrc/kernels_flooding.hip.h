@@ -1221,13 +1221,31 @@ __global__ __launch_bounds__(256) void cn_minsum_lfree_kernel(
 // selects instead of branches, and keeps a loaded record's argmins in one register (RowRec8Once): 91 VGPRs and 2929 vector
 // instructions in the steady-state f32 pack-of-4 kernel, where decoding per value had 96 and 4804
 // (profiles/cn_flags8_decode.txt).
+// SHAPE = kCnShapePN / kCnShapeNP ("cn_row_shape"; the byte form without per-edge messages, not the first iteration): a run
+// of the walk whose rows all have the graph's dominant shape -- graph_tables.h, build_row_shapes: kRowShapeKept kept slots,
+// then the variable shared with the row before and the one shared with the row after (PN: DVB-S2 1/2 from its alist), or those
+// two the other way round (NP), the peers' slots and the writer where that shape puts them -- takes a row step that knows all this:
+// straight-line code per walk direction, no peer words, no `carry_var` / `carry_slot` compares, no far path and no tests of
+// the row's length.  The other message of the slot shared with the row ahead comes from `nxt`; the variable shared with the
+// row behind arrives through the LDS hand-off as its new posterior, which that row formed a step ago from the same three
+// values.  Only the run's first row, whose neighbour behind belongs to another run, has that neighbour's record fetched (as
+// the generic step does) and the shared channel row loaded.  Whether a run conforms is one word of the peer table (the
+// row-shape counts behind the peer words), loaded beside the run's first row_ptr word; every other run -- the graph's first
+// and last rows, anything odd -- takes the generic step below, in the same launch.  The same operations on the same values
+// in the same slot order: results do not change, NaNs and infinities included (tests/test_cn_row_shape_gpu.py).
+// profiles/cn_row_shape.txt.
+enum : int { kCnShapeNone = 0, kCnShapePN = 1, kCnShapeNP = 2 };
+static_assert(kCnShapePN == int(kRowShapePN) && kCnShapeNP == int(kRowShapeNP), "the kinds of graph_tables.h, build_row_shapes");
 template <typename T, int VEC, int RECW, bool F16, int U, bool FIRST, bool NT, bool STREAM = false, bool LONG = true, bool SEND = true,
-          bool F8 = false, typename... MC>
+          bool F8 = false, int SHAPE = kCnShapeNone, typename... MC>
 __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     Graph g, Sched sc, State st, const T *__restrict__ chan, T *__restrict__ post, typename RecRef<T, F16, F8>::in rec_in,
     typename RecRef<T, F16, F8>::out rec_out, T *__restrict__ msg, uint32_t *__restrict__ unsat_out, uint32_t run, MC... mc) {
   static_assert(!F8 || (F16 && !LONG), "byte flags: rows of at most 7 edges");
   static_assert(!F8 || U == int(kRecFlags8MaxRow), "byte flags: a row is one round of 7 loads");
+  static_assert(SHAPE == kCnShapeNone || ((SHAPE == kCnShapePN || SHAPE == kCnShapeNP) && F8 && !SEND && !FIRST && !STREAM),
+                "row shapes: the byte form without per-edge messages, behind the first iteration");
+  static_assert(kRowShapeKept + 2 <= kRecFlags8MaxRow, "the dominant shape is a row of the byte form");
   typedef std::conditional_t<F8, RowRec8Once<T, VEC>, RowRec<T, VEC, RECW, RecFlagWord<T, F16, F8>>> Rec;
   constexpr bool CORR = sizeof...(MC) != 0;  // normalized / offset min-sum
   static_assert(is_corr_pack<T, MC...>, "mc: nothing, or one MinsumCorr<T>");
@@ -1301,6 +1319,152 @@ __global__ __launch_bounds__(256) void cn_minsum_rec_kernel(
     const uint32_t lo = r * run, hi = min(lo + run, n_rows);
     const uint32_t dir = (r & 1u) ? 0xFFFFFFFFu : 1u;  // +1 / -1 (row numbers wrap: an invalid row is >= n_rows)
     uint32_t c = (r & 1u) ? hi - 1 : lo;
+    if constexpr (SHAPE != kCnShapeNone) {
+      // the fitting rows from c on in the walk's direction (graph_tables.h, row_shape_run_conforms)
+      const uint32_t span = edge_peer[g.n_edges + kTablePad + c];
+      if (((r & 1u) ? span >> 16 : span & 0xFFFFu) >= hi - lo) {
+        // UP: the walk's direction.  AHEAD / BEHIND: the slots shared with the next / the previous row of the walk
+        auto shape_run = [&](auto UP) {
+          constexpr bool kUp = decltype(UP)::value;
+          constexpr uint32_t K = kRowShapeKept, D = K + 2;
+          constexpr uint32_t NEXT = SHAPE == kCnShapePN ? K + 1 : K, PREV = SHAPE == kCnShapePN ? K : K + 1;  // in row order
+          constexpr uint32_t AHEAD = kUp ? NEXT : PREV, BEHIND = kUp ? PREV : NEXT;
+          constexpr uint32_t kSgnMask8 = (1u << kRecFlags8MaxRow) - 1;
+          uint32_t cc = c, e0 = row_ptr[cc], cols[D];
+#pragma unroll
+          for (uint32_t u = 0; u < D; u++) cols[u] = edge_col[e0 + u];
+          Rec recA, recB;
+          {
+            // The hand-off the run's first row finds: the row behind it belongs to another run, so that row's record is fetched
+            // (the generic step's far fetch) and the shared channel row loaded, and the shared variable's new posterior goes
+            // where a row of this run would have left it.  (Both neighbours of a fitting row exist.)  The neighbour's record
+            // as memory holds it, asked for before the first row's own: the three answers come back together, where a
+            // record decoded at its load (RowRec8Once) is waited for before the next request goes out.
+            const uint32_t far_off = (kUp ? cc - 1 : cc + 1) * rec_bytes;
+            const Pack<T, VEC> far_min1 = buf_load<T, VEC, false>(b_rin.b, lane_off, far_off);
+            const Pack<T, VEC> far_min2 = buf_load<T, VEC, false>(b_rin.b, lane_off, far_off + row_bytes);
+            const Pack<uint8_t, VEC> far_fl =
+                flags_load<uint8_t, VEC, false>(b_rin.f, lane_off / uint32_t(sizeof(T)), far_off / uint32_t(2 * sizeof(T)));
+            const Pack<T, VEC> chan_behind = buf_load<T, VEC, false>(b_chan, lane_off, cols[BEHIND] * row_bytes);
+            recA.load(b_rin, lane_off, cc * rec_bytes, row_bytes);
+            Pack<T, VEC> l_behind;
+#pragma unroll
+            for (int k = 0; k < VEC; k++) {
+              const T m_far = __builtin_bit_cast(T, record_flags8_value<W>(__builtin_bit_cast(W, far_min1.v[k]),
+                                                                              __builtin_bit_cast(W, far_min2.v[k]), far_fl.v[k], AHEAD));
+              l_behind.v[k] = chan_behind.v[k] + (recA.value(BEHIND, k) + m_far);
+            }
+            carry_chan[1][threadIdx.x] = l_behind;
+          }
+          auto step = [&](Rec &own, Rec &nxt, uint32_t ph) {
+            const uint32_t cn = kUp ? cc + 1 : cc - 1;
+            nxt.load(b_rin, lane_off, cn * rec_bytes, row_bytes);
+            Pack<T, VEC> lv[D];
+#pragma unroll
+            for (uint32_t u = 0; u < K; u++) lv[u] = buf_load<T, VEC, false>(b_post, lane_off, cols[u] * row_bytes);
+            lv[AHEAD] = buf_load<T, VEC, false>(b_chan, lane_off, cols[AHEAD] * row_bytes);
+            // The variable shared with the row behind: its new posterior L = chan + (m_a + m_b) as that row formed it a step ago,
+            // from the same channel row and the same two messages -- there with this row's message second, and neither
+            // message is ever a NaN, so the sum is the same bits either way.  A message is a stored minimum of magnitudes
+            // (RowRec::value; the fold ignores NaNs) or, with the corrected rules, minsum_corrected of one, whose closing
+            // select `c > 0 ? c : 0` turns a NaN (alpha = 0 on an infinite minimum) into 0: true for every alpha and beta
+            lv[BEHIND] = carry_chan[ph ^ 1u][threadIdx.x];
+            // the next row's columns.  Every row of the run has D edges; the row beyond the run's last one may be shorter (its
+            // columns are read and not used: upwards the tables' padding covers them, downwards the offset stops at 0)
+            const uint32_t ne0 = kUp ? e0 + D : e0 - min(e0, D);
+            const TablePtr next_col = edge_col + ne0;  // (one address, D constant offsets)
+            uint32_t ncols[D];
+#pragma unroll
+            for (uint32_t u = 0; u < D; u++) ncols[u] = next_col[u];
+            T min1[VEC], min2[VEC];
+            uint32_t sa[VEC];
+            uint64_t par_m[VEC];
+#pragma unroll
+            for (int k = 0; k < VEC; k++) {
+              min1[k] = Limits<T>::inf();
+              min2[k] = Limits<T>::inf();
+              sa[k] = 0;
+              par_m[k] = 0;
+            }
+            Pack<T, VEC> lnew;  // the new posterior of the variable this row stores: the one shared with the next row in row order
+#pragma unroll
+            for (uint32_t u = 0; u < D; u++) {
+              // A slot is a basic block of its own, behind a branch that is always taken and that the compiler cannot see
+              // through.  As one block, the compiler fills the wait for the loads with everything the D slots can do ahead of
+              // time and holds the results: 120 VGPRs and four waves per SIMD, or scratch under a bound of 96; in blocks: 94
+              // (96 with the corrected rules).  The build checks it: `make` ends in tools/kernel_resources.py --gate.
+              uint32_t always = 1;
+              asm volatile("" : "+s"(always));
+              if (always)
+#pragma unroll
+              for (int k = 0; k < VEC; k++) {
+                T l = lv[u].v[k];
+                const T m_own = own.value(u, k);
+                if (u == AHEAD) {
+                  l = l + (m_own + nxt.value(BEHIND, k));  // chan + (m_a + m_b)
+                  lv[u].v[k] = l;
+                }
+                if (u == NEXT) lnew.v[k] = l;
+                const T x = l - m_own;
+                const T a = m_abs(x);
+                if (x < T(0.0)) sa[k] |= 1u << u;
+                par_m[k] ^= __builtin_amdgcn_ballot_w64(l <= T(0.0));
+                const bool lt1 = a < min1[k], lt2 = a < min2[k];
+                min2[k] = lt1 ? min1[k] : (lt2 ? a : min2[k]);
+                min1[k] = lt1 ? a : min1[k];
+                sa[k] = lt1 ? ((sa[k] & kSgnMask8) | (u << kArgShift16)) : sa[k];
+              }
+              if (u == AHEAD) carry_chan[ph][threadIdx.x] = lv[u];
+            }
+            if (write_post) {
+              if (all_live) {
+                buf_store<T, VEC, false>(b_post, lane_off, cols[NEXT] * row_bytes, lnew);
+              } else {
+#pragma unroll
+                for (int k = 0; k < VEC; k++)
+                  // (codeword k's word through the scalar offset: no lane offset per codeword held in registers)
+                  if (live[k]) row_store<T, false>(b_post, lane_off, cols[NEXT] * row_bytes + k * uint32_t(sizeof(T)), lnew.v[k]);
+              }
+            }
+            typename Rec::New out;
+            if constexpr (CORR) {
+              // (each magnitude on its own, fenced: see the generic step)
+#pragma unroll
+              for (int k = 0; k < VEC; k++) {
+                asm("" : "+v"(min1[k]));
+                asm("" : "+v"(min2[k]));
+                min1[k] = minsum_corrected(min1[k], mc...);
+                min2[k] = minsum_corrected(min2[k], mc...);
+                asm("" : "+v"(min1[k]));
+                asm("" : "+v"(min2[k]));
+              }
+            }
+#pragma unroll
+            for (int k = 0; k < VEC; k++) {
+              const uint32_t tot = __popc(sa[k] & kSgnMask8) & 1u;
+              odd_m[k] |= par_m[k];
+              out.min1.v[k] = min1[k];
+              out.min2.v[k] = min2[k];
+              out.flip.v[k] = uint16_t(tot ? sa[k] ^ kSgnMask8 : sa[k]);
+            }
+            out.template store<NT>(b_rout, lane_off, cc * rec_bytes, row_bytes);
+            cc = cn;
+            e0 = ne0;
+#pragma unroll
+            for (uint32_t u = 0; u < D; u++) cols[u] = ncols[u];
+          };
+          for (uint32_t i = lo; i < hi; i += 2) {
+            step(recA, recB, 0);
+            if (i + 1 < hi) step(recB, recA, 1);
+          }
+        };
+        if (r & 1u)
+          shape_run(std::false_type{});
+        else
+          shape_run(std::true_type{});
+        continue;
+      }
+    }
     // own = record of the current row, nxt = record of the row the walk reaches next (this row's peer now, `own`
     // one step later); carry_msg = the message the PREVIOUS row of the walk sent to the variable it shares with this
     // one (it had that value in hand as its own message: the previous row's record need not be kept); carry_chan = that

@@ -47,6 +47,9 @@ struct DeviceDecoder::SmallBatchCall {
     d.last_vn_bundle_saved_.store(0, std::memory_order_relaxed);
     d.last_vn_chains_.store(false, std::memory_order_relaxed);
     d.last_vn_chain_saved_.store(0, std::memory_order_relaxed);
+    d.last_cn_row_shape_.store(false, std::memory_order_relaxed);
+    d.last_cn_shape_runs_.store(0, std::memory_order_relaxed);
+    d.last_cn_shape_rows_.store(0, std::memory_order_relaxed);
     d.last_record_flag_bytes_.store(0, std::memory_order_relaxed);
   }
 

@@ -118,8 +118,12 @@ struct Launch {
   // further-rounds code)
   // (eight loads in flight per lane; the four-load variant of earlier rounds, a tuning knob nothing selected, is gone)
   // (send = false: no per-edge messages, for a variable-node launch that reads the records -- vn_rec below; 16-bit flags only)
+  // (shape: the row-shape form of that kind, "cn_row_shape" -- f32, byte flags, send = false, not the first iteration; the
+  // peer table then carries the row-shape counts of that kind, graph_tables.h build_row_shapes.  The caller asks for it only
+  // where all of that holds: any other combination is launched in its generic form)
   void cn_rec(bool first, uint32_t vec, const Tiling &t, const dev::Graph &g, const dev::State &st, const T *chan, T *post,
-              const Records &in, const Records &out, T *msg, uint32_t *unsat, uint32_t run, bool send = true) const {
+              const Records &in, const Records &out, T *msg, uint32_t *unsat, uint32_t run, bool send = true,
+              uint32_t shape = kRowShapeNone) const {
     minsum(vec, first, [&](auto V, auto FIRST, auto... mc) {
       with_rec_form(in, [&](auto W, auto F16, auto F8) {
         with_bool(rec_long, [&](auto long_rows) {
@@ -128,16 +132,21 @@ struct Launch {
           constexpr bool kF8 = decltype(F8)::value && !decltype(long_rows)::value;
           // (and so the byte form has seven loads in flight per lane, a whole row, where every other form has eight)
           constexpr int kU = kF8 ? int(kRecFlags8MaxRow) : 8;
-          auto go_rec = [&](auto SEND) {
+          auto go_rec = [&](auto SEND, auto SHAPE) {
             dev::cn_minsum_rec_kernel<T, decltype(V)::value, decltype(W)::value, decltype(F16)::value, kU, decltype(FIRST)::value,
-                                      true, false, decltype(long_rows)::value, decltype(SEND)::value, kF8, decltype(mc)...>
+                                      true, false, decltype(long_rows)::value, decltype(SEND)::value, kF8, decltype(SHAPE)::value,
+                                      decltype(mc)...>
                 <<<t.blocks, t.threads, 0, s>>>(g, t.sched, st, chan, post, rec_ref<true, decltype(F16)::value, kF8>(in),
                                                 rec_ref<false, decltype(F16)::value, kF8>(out), msg, unsat, run, mc...);
           };
           if constexpr (decltype(F16)::value) {
-            if (!send) return go_rec(std::false_type{});
+            if constexpr (kF8 && !decltype(FIRST)::value && sizeof(T) == 4) {
+              if (!send && shape == kRowShapePN) return go_rec(std::false_type{}, int_c<dev::kCnShapePN>{});
+              if (!send && shape == kRowShapeNP) return go_rec(std::false_type{}, int_c<dev::kCnShapeNP>{});
+            }
+            if (!send) return go_rec(std::false_type{}, int_c<dev::kCnShapeNone>{});
           }
-          go_rec(std::true_type{});
+          go_rec(std::true_type{}, int_c<dev::kCnShapeNone>{});
         });
       });
     });

@@ -155,6 +155,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
   uint32_t *unsat[2] = {w.unsat0, w.unsat1};
   int zero_fill = 0;
   last_record_flag_bytes_.store(0, std::memory_order_relaxed);  // (the flooding record path says what it ran)
+  last_cn_row_shape_.store(false, std::memory_order_relaxed);
 
   if (impl_.schedule == Schedule::Flooding) {
     const bool streaming = fl_streaming;  // (decided above)
@@ -214,6 +215,15 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
     }
     const uint32_t rec_run = std::max<uint32_t>(1, std::min<uint32_t>(opt_rec_run_, m));
     const Tiling rec_t = make_tiling(G, tile, 64 * vec, (m + rec_run - 1) / rec_run, stream_block, target_waves);
+    // "cn_row_shape": the record kernel's row-shape form behind the first iteration (launch.hip.h, cn_rec), where the form
+    // exists -- f32, byte flags, no per-edge messages -- and some run of this call's walk conforms
+    uint32_t shape_runs = 0, shape_rows = 0;
+    if (vn_records && flags8 && opt_cn_row_shape_ && sizeof(T) == 4 && row_shape_span_.size() == m)
+      count_row_shape_runs(row_shape_span_, m, rec_run, &shape_runs, &shape_rows);
+    const bool cn_shape = shape_runs != 0 && max_iterations > 1;
+    last_cn_row_shape_.store(cn_shape, std::memory_order_relaxed);
+    last_cn_shape_runs_.store(cn_shape ? shape_runs : 0, std::memory_order_relaxed);
+    last_cn_shape_rows_.store(cn_shape ? shape_rows : 0, std::memory_order_relaxed);
     dev::Graph g_keep = g, g_free = g;
     Tiling vn_keep_t = vn_t, vn_free_t = vn_t, vn_event_t = vn_t;
     if (lfree) {
@@ -288,7 +298,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
       if (records)
         // (first && ingest_no_post: the kept variables' rows from `chan`; the FIRST form stores no posterior)
         launch.cn_rec(first, vec, rec_t, g, stp, chan, (first && ingest_no_post) ? chan : post, rbuf[(it + 1) & 1], rbuf[it & 1],
-                      msg, unsat_out, rec_run, !vn_records);
+                      msg, unsat_out, rec_run, !vn_records, (cn_shape && !first) ? row_shape_kind_ : uint32_t(kRowShapeNone));
       else if (lfree)
         launch.cn_lfree(first, vec, wide_mask, cn_t, g, stp, chan, post, m_in, m_out, unsat_out);
       else if (streaming)

@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register / LDS / scratch use of the kernels in the built product library, read from the gfx950 code objects'
-metadata notes (no GPU needed).  usage: tools/kernel_resources.py [substring of the demangled kernel name ...]"""
+metadata notes (no GPU needed).  usage: tools/kernel_resources.py [substring of the demangled kernel name ...]
+       tools/kernel_resources.py --gate [library]: the resource gate of the row-shape check-node kernels, for the build"""
 import re
 import struct
 import subprocess
@@ -45,7 +46,30 @@ def kernels(lib=None):
     return [(nm,) + tuple(int(x) if x.isdigit() else -1 for x in r[1:]) for r, nm in zip(rows, names)]
 
 
+# cn_minsum_rec_kernel's row-shape form (its twelfth template argument, SHAPE, is 1 or 2): five waves per SIMD is what the
+# form was built for, and it has them only because of how its row step is laid out for the compiler (kernels_flooding.hip.h).
+# A compiler that lays it out otherwise gives 120 VGPRs or scratch and a slower kernel with the same results: no test sees it.
+SHAPE_FORM = re.compile(r"cn_minsum_rec_kernel<(?:[^,<>]+, ){11}[12][,>]")
+GATE_VGPRS, GATE_LDS = 96, 16384
+
+
+def gate(lib):
+    """The resource gate of the row-shape kernels -> process exit status (the build's last step)."""
+    rows = [k for k in kernels(lib) if SHAPE_FORM.search(k[0])]
+    bad = [k for k in rows if not (0 <= k[1] <= GATE_VGPRS and k[2] == 0 and k[4] == 0 and k[5] == 0 and 0 <= k[6] <= GATE_LDS)]
+    for k in bad:
+        print(f"kernel_resources: over the gate ({GATE_VGPRS} VGPRs, no scratch, {GATE_LDS} B of LDS): vgpr {k[1]} agpr {k[2]} "
+              f"spill {k[4]} scratch {k[5]} lds {k[6]}  {k[0][:150]}", file=sys.stderr)
+    if not rows:
+        print("kernel_resources: no row-shape instantiation of cn_minsum_rec_kernel found: the gate looked at nothing", file=sys.stderr)
+    print(f"kernel_resources: {len(rows)} row-shape kernels, {len(bad)} over the gate; most VGPRs {max([k[1] for k in rows] or [0])}")
+    return 1 if bad or not rows else 0
+
+
 def main():
+    if "--gate" in sys.argv[1:]:
+        rest = [a for a in sys.argv[1:] if a != "--gate"]
+        sys.exit(gate(rest[0] if rest else None))
     want = sys.argv[1:]
     rows = [(None,) + tuple(str(x) for x in k[1:]) + (k[0],) for k in kernels()]
     names = [r[-1] for r in rows]
