@@ -606,6 +606,96 @@ int32_t ldpc_toolbox_nr_tb_split_f64(void *tb, double *packed, const double *rx,
 int32_t ldpc_toolbox_nr_tb_split_f32_device(void *tb, float *packed, const float *rx, size_t g, size_t q, size_t batch, void *hip_stream);
 int32_t ldpc_toolbox_nr_tb_split_f64_device(void *tb, double *packed, const double *rx, size_t g, size_t q, size_t batch, void *hip_stream);
 
+/* ===================================================================================
+ * PART 8 -- batched 5G NR modulation mapper, soft demapper and scrambling on the GPU (3GPP TS 38.211 5.1.3-5.1.6: QPSK,
+ * 16QAM, 64QAM, 256QAM; 5.2.1: the length-31 Gold sequence; 6.3.1.1 / 7.3.1.1: scrambling).  It sits between PART 6 / 7
+ * and the decoder: bits and LLRs here are in TRANSMITTED order -- the `output` of ldpc_toolbox_nr_rm_match /
+ * ldpc_toolbox_nr_tb_concatenate and the `rx` of ldpc_toolbox_nr_rm_recover / ldpc_toolbox_nr_tb_split.  There is no
+ * `interleaving` argument: NR's bit interleaver is the rate matcher's.  The reference has none of it.
+ * =================================================================================== */
+
+/* spec: "nr5g-qam:QM", QM = 2, 4, 6 or 8 bits per symbol; anything else: NULL (message via ldpc_toolbox_last_error).
+ * The constructor needs no GPU (`device` is used by the first run; -1 = LDPC_TOOLBOX_DEVICE, default 0).
+ * With h = QM / 2 and norm = 2, 10, 42, 170:
+ *   Levels.  A level index u = sum_t a_t << (h-1-t) (a_0 the most significant bit) has the integer level
+ *     L_u = (1 - 2 a_0) [2^(h-1) - (1 - 2 a_1) [2^(h-2) - ... (1 - 2 a_(h-1)) [1]]]       (38.211's nested form:
+ *     h = 2: 1, 3, -1, -3;  h = 3: 3, 1, 5, 7, -3, -1, -5, -7;  h = 4: 5, 7, 3, 1, 11, 9, 13, 15 and their negatives)
+ *   Amplitudes.  a = sqrt(1.0 / norm) and A_u = L_u * a in double, each rounded once.  QM = 2 is the "QPSK" of PART 4
+ *     bit for bit.
+ *   Symbol bits.  Of the bits b_0 .. b_(QM-1) of a symbol the I axis takes a_t = b_(2t), the Q axis a_t = b_(2t+1); the
+ *     point is (A_uI, A_uQ).  Mean symbol energy 1.
+ *   Scrambling sequence.  c(n) = x1(n + 1600) ^ x2(n + 1600),  x1(n + 31) = x1(n + 3) ^ x1(n),
+ *     x2(n + 31) = x2(n + 3) ^ x2(n + 2) ^ x2(n + 1) ^ x2(n);  x1 starts 1, 0, ..., 0 and x2(i) = bit i of c_init, i < 31.
+ *     An int64_t c_init of 0 .. 2^31 - 1 selects scrambling, -1 none; anything else is LDPC_TOOLBOX_ERR_ARGUMENT.  Every row
+ *     of a batch uses the same sequence, position i of a row c(i).  The handle keeps the sequence of the last
+ *     (c_init, row length) on the device: a call with another pair generates it first, on the call's stream.
+ *   Mapper.  bits [batch][bits_len] (a byte equal to 1 is a one, anything else a zero) -> symbols [batch][bits_len / QM],
+ *     (re, im) pairs.  Bit i of a row is XORed with c(i) first.  The symbol is (A_uI, A_uQ): the doubles for _f64, each
+ *     rounded once to float for _f32.
+ *   Demapper.  Per axis, with coordinate x:  scale = 1 / sigma^2,  sx = x * scale,
+ *       d_u = sx * A_u - K_u,   K_u = (0.5 * scale) * (A_u * A_u) made on the host in double,
+ *       llr_t = F({d_u : a_t = 0}) - F({d_u : a_t = 1}),  F a left fold over ascending u starting at its first element,
+ *     with the fold step of PART 4: max* (exact) or the maximum that ignores a NaN operand and orders -0 < +0 (max_log).
+ *     Every product and sum is rounded once.  Bit 2t of the symbol gets the I axis's llr_t, bit 2t + 1 the Q axis's; the
+ *     LLR at row position i is negated when c(i) = 1.  A positive LLR means bit 0.  The bit-j sum over the 2^QM points
+ *     factorises over the axes and the other axis cancels in the LLR: this is the demapper of the whole constellation,
+ *     up to rounding (tests/test_nr_qam_reference.py compares the two).
+ *     _f64: all arithmetic in double.  _f32: exact = symbols widened to double, the double arithmetic, each LLR rounded
+ *     once; max_log = float throughout, with scale, A_u and K_u each rounded to float once.
+ * A null handle, llrs_len / bits_len != QM * symbols_len, a length above 0x7fffffff, a noise_sigma that is not finite or
+ * not > 0, a c_init out of range: LDPC_TOOLBOX_ERR_ARGUMENT before the GPU is touched, nothing written.  Without a GPU
+ * LDPC_TOOLBOX_ERR_DEVICE (there is no CPU path).  batch == 0 returns 0.  One call at a time per handle.
+ * The AWGN channel of PART 4 works on these symbols through any complex demodulator handle, e.g. "QPSK":
+ * ldpc_toolbox_awgn_run_* reads nothing of the handle's table. */
+void *ldpc_toolbox_nr_qam_ctor(const char *spec, int32_t device);
+void ldpc_toolbox_nr_qam_dtor(void *qam);
+/* key: "bits_per_symbol" (QM), "points" (2^QM), "levels" (2^h), "device" (-1 until the first run made the device state),
+ * "sequence_launches" (how often the Gold kernel has run: a repeated (c_init, length) does not run it again).
+ * returns 0, or -1 for an unknown key. */
+int32_t ldpc_toolbox_nr_qam_get(void *qam, const char *key, int64_t *value);
+/* The 2^QM points as (re, im) doubles, point V = sum_j b_j << (QM-1-j) at index V (the indexing of PART 4's tables).
+ * Written when re_im is not NULL and len (in doubles) >= 2 * 2^QM.  returns 2^QM, 0 for a null handle.  Host only. */
+size_t ldpc_toolbox_nr_qam_points(void *qam, double *re_im, size_t len);
+/* c(0) .. c(len - 1) of c_init (0 .. 2^31 - 1), one byte per bit, as the GPU generated them: the kernel writes the
+ * sequence bit-packed, one thread per run of 1024 bits, reaching the register states at the start of its run by
+ * jump-ahead (x^offset modulo each feedback polynomial), so nothing is serial in len.  len <= 0x7fffffff. */
+int32_t ldpc_toolbox_nr_qam_sequence(void *qam, uint8_t *c, size_t len, int64_t c_init);
+/* The argument order of ldpc_toolbox_mod_run_* / ldpc_toolbox_demod_run_* without `interleaving`, c_init last.  Host
+ * pointers (staged through the handle's buffers) or, _device, device pointers and a hipStream_t: a stream = enqueue and
+ * return; NULL = the handle's own stream, ordered after what the legacy default stream holds at the call, synchronised
+ * on return.  The kernels move a symbol and its QM LLRs as vectors: a device symbol buffer must be aligned to one
+ * (re, im) pair and a device LLR buffer to 16 bytes, else LDPC_TOOLBOX_ERR_ARGUMENT. */
+int32_t ldpc_toolbox_nr_qam_mod_f32(void *qam, float *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len, size_t batch,
+                                    int64_t c_init);
+int32_t ldpc_toolbox_nr_qam_mod_f64(void *qam, double *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len, size_t batch,
+                                    int64_t c_init);
+int32_t ldpc_toolbox_nr_qam_mod_f32_device(void *qam, float *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                           size_t batch, int64_t c_init, void *hip_stream);
+int32_t ldpc_toolbox_nr_qam_mod_f64_device(void *qam, double *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                           size_t batch, int64_t c_init, void *hip_stream);
+int32_t ldpc_toolbox_nr_qam_demod_f32(void *qam, float *llrs, size_t llrs_len, const float *symbols, size_t symbols_len, size_t batch,
+                                      double noise_sigma, int32_t max_log, int64_t c_init);
+int32_t ldpc_toolbox_nr_qam_demod_f64(void *qam, double *llrs, size_t llrs_len, const double *symbols, size_t symbols_len, size_t batch,
+                                      double noise_sigma, int32_t max_log, int64_t c_init);
+int32_t ldpc_toolbox_nr_qam_demod_f32_device(void *qam, float *llrs, size_t llrs_len, const float *symbols, size_t symbols_len,
+                                             size_t batch, double noise_sigma, int32_t max_log, int64_t c_init, void *hip_stream);
+int32_t ldpc_toolbox_nr_qam_demod_f64_device(void *qam, double *llrs, size_t llrs_len, const double *symbols, size_t symbols_len,
+                                             size_t batch, double noise_sigma, int32_t max_log, int64_t c_init, void *hip_stream);
+/* An NR modulation as the simulator's (PART 3).  qam: a handle of ldpc_toolbox_nr_qam_ctor; its configuration is copied,
+ * the handle may be destroyed afterwards.  NULL returns to what the "modulation" key selects.  Refused (-1 with a message,
+ * nothing changed) unless n_tx is a multiple of QM and the simulator's "interleaving" is 0; while it is set a non-zero
+ * "interleaving" is refused, and so is clearing a rate matcher when n is no multiple of QM.  With a rate matcher set
+ * (ldpc_toolbox_sim_set_rate_match) its qm need not equal QM: it is the interleaver's row count and nothing here depends
+ * on it, so the two are not compared -- a standard-conformant chain passes the same value to both.
+ * Setting it clears a constellation of ldpc_toolbox_sim_set_constellation, and setting one of those clears it.
+ * noise_sigma uses m = QM; "modulation" of ldpc_toolbox_sim_get reports QM, "nr_qam" 1 while one is set, "max_log" the
+ * fold step.  Resets the straggler-pooling budget, as "modulation" does.
+ * DEFINED RESULT: the LLRs of frame f are what ldpc_toolbox_nr_qam_mod_f64 (c_init -1) of the frame's pooled transmitted
+ * row, then ldpc_toolbox_awgn_run_f64 (the run's seed, frame f, noise_sigma), then ldpc_toolbox_nr_qam_demod_f64 (the same
+ * noise_sigma and max_log, c_init -1) give, each value rounded once to float, in transmitted order.  One fused kernel
+ * computes it, one thread per symbol; the symbols are never stored. */
+int32_t ldpc_toolbox_sim_set_nr_qam(void *sim, void *qam, int32_t max_log);
+
 /* Standard-code generator (what the reference's `dvbs2` / `5g` / `ccsds` / `ccsds-c2` CLI
  * sub-commands print, src/cli/dvbs2.rs:91, src/cli/nr5g.rs:46, src/cli/ccsds.rs:70): writes the
  * padded alist text of `spec` ("dvbs2:R1_2", "nr5g:1:384", "ar4ja:1/2:1024", "c2") into

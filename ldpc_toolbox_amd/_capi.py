@@ -96,6 +96,20 @@ SYMBOLS = [
     "ldpc_toolbox_nr_tb_split_f64",
     "ldpc_toolbox_nr_tb_split_f32_device",
     "ldpc_toolbox_nr_tb_split_f64_device",
+    "ldpc_toolbox_nr_qam_ctor",
+    "ldpc_toolbox_nr_qam_dtor",
+    "ldpc_toolbox_nr_qam_get",
+    "ldpc_toolbox_nr_qam_points",
+    "ldpc_toolbox_nr_qam_sequence",
+    "ldpc_toolbox_nr_qam_mod_f32",
+    "ldpc_toolbox_nr_qam_mod_f64",
+    "ldpc_toolbox_nr_qam_mod_f32_device",
+    "ldpc_toolbox_nr_qam_mod_f64_device",
+    "ldpc_toolbox_nr_qam_demod_f32",
+    "ldpc_toolbox_nr_qam_demod_f64",
+    "ldpc_toolbox_nr_qam_demod_f32_device",
+    "ldpc_toolbox_nr_qam_demod_f64_device",
+    "ldpc_toolbox_sim_set_nr_qam",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
     "ldpc_toolbox_device_count",
@@ -322,6 +336,31 @@ def lib():
         fd = getattr(L, "ldpc_toolbox_nr_tb_" + name + "_device")
         fd.restype = i32
         fd.argtypes = f.argtypes + [vp]
+    L.ldpc_toolbox_nr_qam_ctor.restype = vp
+    L.ldpc_toolbox_nr_qam_ctor.argtypes = [cp, i32]
+    L.ldpc_toolbox_nr_qam_dtor.restype = None
+    L.ldpc_toolbox_nr_qam_dtor.argtypes = [vp]
+    L.ldpc_toolbox_nr_qam_get.restype = i32
+    L.ldpc_toolbox_nr_qam_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
+    L.ldpc_toolbox_nr_qam_points.restype = sz
+    L.ldpc_toolbox_nr_qam_points.argtypes = [vp, vp, sz]
+    L.ldpc_toolbox_nr_qam_sequence.restype = i32
+    L.ldpc_toolbox_nr_qam_sequence.argtypes = [vp, vp, sz, C.c_int64]
+    for name in ("f32", "f64"):
+        f = getattr(L, "ldpc_toolbox_nr_qam_mod_" + name)
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, C.c_int64]
+        f = getattr(L, "ldpc_toolbox_nr_qam_mod_" + name + "_device")
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, C.c_int64, vp]
+        f = getattr(L, "ldpc_toolbox_nr_qam_demod_" + name)
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, C.c_double, i32, C.c_int64]
+        f = getattr(L, "ldpc_toolbox_nr_qam_demod_" + name + "_device")
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, sz, sz, C.c_double, i32, C.c_int64, vp]
+    L.ldpc_toolbox_sim_set_nr_qam.restype = i32
+    L.ldpc_toolbox_sim_set_nr_qam.argtypes = [vp, vp, i32]
     L.ldpc_toolbox_code_alist.restype = sz
     L.ldpc_toolbox_code_alist.argtypes = [cp, vp, sz]
     L.ldpc_toolbox_alist_normalize.restype = sz

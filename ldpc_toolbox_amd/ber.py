@@ -161,7 +161,10 @@ def format_details(a, sim, world: int) -> str:
     if a.max_frames is not None:
         lines.append(f" - Maximum number of frames per Eb/N0: {a.max_frames}")     # this build's addition
     lines += [f" - Number of GPUs: {world}", "Channel:"]
-    if getattr(a, "constellation", None):                                             # this build's additions
+    if getattr(a, "nr_qam", None):                                                    # this build's additions
+        lines += [f" - Modulation: NR {1 << a.nr_qam}QAM" if a.nr_qam > 2 else " - Modulation: NR QPSK",
+                  f" - Bits per symbol: {sim.get('modulation')}"]
+    elif getattr(a, "constellation", None):
         lines += [f" - Modulation: constellation {a.constellation}", f" - Bits per symbol: {sim.get('modulation')}"]
     else:
         lines.append(f" - Modulation: {a.modulation}")
@@ -193,7 +196,11 @@ def main(argv=None):
                     help="instead of --modulation: 2^m lines `re im` (m = 1..5), line V = the point of the bits of V, first "
                          "bit most significant; scaled to unit mean energy, demapped with the energy term when the points' "
                          "energies differ")
-    ap.add_argument("--max-log", action="store_true", help="max-log demapper (with QPSK or --constellation)")
+    ap.add_argument("--nr-qam", type=int, choices=[2, 4, 6, 8], metavar="QM",
+                    help="instead of --modulation / --constellation: the 5G NR mapping of TS 38.211 5.1.3-5.1.6 with QM = 2, 4, 6 "
+                         "or 8 bits per symbol (QPSK, 16QAM, 64QAM, 256QAM) and its per-axis demapper; no --interleaving "
+                         "(NR's bit interleaver is --nr-rate-match's QM)")
+    ap.add_argument("--max-log", action="store_true", help="max-log demapper (with QPSK, --constellation or --nr-qam)")
     ap.add_argument("--interleaving", type=int, default=0,
                     help="interleaver columns, negative = read rows backwards (cli/ber.rs:55-59)")
     ap.add_argument("--codes", help='several codes as ONE job (sweep_scheduler.py): comma-separated specs, "dvbs2:normal" = the 11 '
@@ -247,6 +254,8 @@ def main(argv=None):
         ap.error("one of --code, --alist, --codes is required")
     if a.codes and a.bch_code:
         ap.error("--bch-code names one code: it cannot be combined with --codes")
+    if a.nr_qam and (a.codes or a.modulation != "BPSK" or a.constellation or a.interleaving):
+        ap.error("--nr-qam cannot be combined with --codes, --modulation, --constellation or a non-zero --interleaving")
     rate_match = None
     if a.nr_rate_match:
         if a.codes or not (a.code or "").startswith("nr5g:") or a.puncturing:
@@ -290,7 +299,7 @@ def main(argv=None):
         return res
     alist = open(a.alist).read() if a.alist else _capi.code_alist(a.code)
     sim = Simulator(alist, a.decoder, a.puncturing, device=local, pool_size=a.pool_size, pool_seed=a.seed + 1,
-                    modulation=make_modulation(a, local), interleaving=a.interleaving, max_log=a.max_log)
+                    modulation=make_modulation(a, local), interleaving=a.interleaving, max_log=a.max_log and not a.nr_qam)
     if a.bch_code:
         from .bch import BchCode
         code = BchCode(a.bch_code, device=local)
@@ -310,6 +319,14 @@ def main(argv=None):
         except ValueError as e:
             ap.error(f"--nr-rate-match {a.nr_rate_match}: {e}")
         rm.close()
+    if a.nr_qam:                                                  # (after the rate matcher: n_tx is E by now)
+        from .nr_qam import NrQam
+        qam = NrQam(a.nr_qam, device=local)
+        try:
+            sim.set_nr_qam(qam, a.max_log)
+        except ValueError as e:
+            ap.error(f"--nr-qam {a.nr_qam}: {e}")
+        qam.close()
     out = open(a.output_file, "w") if (a.output_file and rank == 0) else None
     out_ldpc = open(a.output_file_ldpc, "w") if (a.output_file_ldpc and a.bch_max_errors > 0 and rank == 0) else None
     details = format_details(a, sim, world)

@@ -19,6 +19,7 @@
 #include "device_bch.h"
 #include "device_decoder.h"
 #include "device_encoder.h"
+#include "device_nr_qam.h"
 #include "device_nr_rm.h"
 #include "device_nr_tb.h"
 #include "encoder.h"
@@ -84,6 +85,13 @@ struct NrTbHandle {
   int device = 0;
   // the device state: made at the first batched call
   std::unique_ptr<ldpc::DeviceNrTb> dev;
+};
+
+struct NrQamHandle {
+  ldpc::nrqam::Config c;
+  int device = 0;
+  // the device state: made at the first run
+  std::unique_ptr<ldpc::DeviceNrQam> dev;
 };
 
 // a device index: decimal digits only (no sign, no trailing characters)
@@ -331,6 +339,64 @@ int32_t awgn_run(void *demod, void *symbols, size_t symbols_len, size_t batch, b
   const int rc = on_device ? h->dev->awgn_device(symbols, f64, symbols_len, batch, sigma, seed, first_frame,
                                                  static_cast<hipStream_t>(stream))
                            : h->dev->awgn_host(symbols, f64, symbols_len, batch, sigma, seed, first_frame);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+// 0 with the handle's device state made, or LDPC_TOOLBOX_ERR_DEVICE
+int32_t nr_qam_device_state(NrQamHandle *h) {
+  if (h->dev) return 0;
+  if (h->device < 0) {
+    set_error("LDPC_TOOLBOX_DEVICE is not a decimal GPU index");
+    return LDPC_TOOLBOX_ERR_DEVICE;
+  }
+  std::string err;
+  h->dev.reset(ldpc::DeviceNrQam::create(h->c, h->device, &err));
+  if (!h->dev) {
+    set_error(err);
+    return LDPC_TOOLBOX_ERR_DEVICE;
+  }
+  return 0;
+}
+
+int32_t nr_qam_refuse(const char *why) {
+  set_error(why);
+  return LDPC_TOOLBOX_ERR_ARGUMENT;
+}
+
+int32_t nr_qam_mod(void *qam, void *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len, size_t batch, bool f64,
+                   int64_t c_init, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrQamHandle *>(qam);
+  if (!h) return nr_qam_refuse("null NR modulation handle");
+  if (const char *why = ldpc::nrqam::mod_argument_error(h->c, bits_len, symbols_len, c_init)) return nr_qam_refuse(why);
+  if (batch == 0 || bits_len == 0) return 0;
+  if (!symbols || !bits) return nr_qam_refuse("null bit or symbol buffer");
+  if (on_device)
+    if (const char *why = ldpc::nrqam::device_pointer_error(symbols, nullptr, f64)) return nr_qam_refuse(why);
+  if (int32_t rc = nr_qam_device_state(h)) return rc;
+  const int rc = on_device ? h->dev->mod_device(bits, symbols, f64, bits_len, symbols_len, batch, c_init, static_cast<hipStream_t>(stream))
+                           : h->dev->mod_host(bits, symbols, f64, bits_len, symbols_len, batch, c_init);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+int32_t nr_qam_demod(void *qam, void *llrs, size_t llrs_len, const void *symbols, size_t symbols_len, size_t batch, bool f64,
+                     double sigma, int32_t max_log, int64_t c_init, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrQamHandle *>(qam);
+  if (!h) return nr_qam_refuse("null NR modulation handle");
+  if (const char *why = ldpc::nrqam::demod_argument_error(h->c, llrs_len, symbols_len, sigma, c_init)) return nr_qam_refuse(why);
+  if (batch == 0 || llrs_len == 0) return 0;
+  if (!symbols || !llrs) return nr_qam_refuse("null symbol or LLR buffer");
+  if (on_device)
+    if (const char *why = ldpc::nrqam::device_pointer_error(symbols, llrs, f64)) return nr_qam_refuse(why);
+  if (int32_t rc = nr_qam_device_state(h)) return rc;
+  const int rc = on_device ? h->dev->demod_device(symbols, llrs, f64, symbols_len, llrs_len, batch, sigma, max_log != 0, c_init,
+                                                  static_cast<hipStream_t>(stream))
+                           : h->dev->demod_host(symbols, llrs, f64, symbols_len, llrs_len, batch, sigma, max_log != 0, c_init);
   if (rc == 0) return 0;
   set_error(h->dev->last_error());
   return LDPC_TOOLBOX_ERR_DEVICE;
@@ -1021,6 +1087,8 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value) {
     *value = s->interleaving();
   else if (k == "constellation")  // 1 while ldpc_toolbox_sim_set_constellation is in force
     *value = s->has_constellation() ? 1 : 0;
+  else if (k == "nr_qam")  // 1 while ldpc_toolbox_sim_set_nr_qam is in force
+    *value = s->has_nr_qam() ? 1 : 0;
   else if (k == "max_log")
     *value = s->max_log() ? 1 : 0;
   else if (k == "bch")  // 1 while ldpc_toolbox_sim_set_bch is in force
@@ -1465,6 +1533,125 @@ int32_t ldpc_toolbox_nr_tb_split_f32_device(void *tb, float *packed, const float
 int32_t ldpc_toolbox_nr_tb_split_f64_device(void *tb, double *packed, const double *rx, size_t g, size_t q, size_t batch, void *hip_stream) {
   return nr_tb_repack(tb, packed, rx, g, q, batch, true, true, true, hip_stream);
 }
+
+// ---- PART 8: batched 5G NR modulation mapper, soft demapper and scrambling ----------------------------
+
+void *ldpc_toolbox_nr_qam_ctor(const char *spec, int32_t device) {
+  g_last_error.clear();
+  if (!spec) {
+    set_error("null NR modulation spec");
+    return nullptr;
+  }
+  auto h = std::make_unique<NrQamHandle>();
+  std::string err;
+  if (!ldpc::nrqam::parse_spec(spec, &h->c, &err)) {
+    set_error(err);
+    return nullptr;
+  }
+  h->device = device < 0 ? default_device() : device;
+  return h.release();
+}
+
+void ldpc_toolbox_nr_qam_dtor(void *qam) { delete static_cast<NrQamHandle *>(qam); }
+
+int32_t ldpc_toolbox_nr_qam_get(void *qam, const char *key, int64_t *value) {
+  auto *h = static_cast<NrQamHandle *>(qam);
+  if (!h || !key || !value) return -1;
+  const std::string k = key;
+  if (k == "bits_per_symbol")
+    *value = h->c.qm;
+  else if (k == "points")
+    *value = h->c.points();
+  else if (k == "levels")
+    *value = h->c.levels();
+  else if (k == "device")
+    *value = h->dev ? h->dev->device() : -1;
+  else if (k == "sequence_launches")  // runs of the Gold kernel so far: a repeated (c_init, length) does not add one
+    *value = h->dev ? static_cast<int64_t>(h->dev->sequence_launches()) : 0;
+  else
+    return -1;
+  return 0;
+}
+
+size_t ldpc_toolbox_nr_qam_points(void *qam, double *re_im, size_t len) {
+  auto *h = static_cast<NrQamHandle *>(qam);
+  if (!h) return 0;
+  const size_t points = h->c.points();
+  if (re_im && len >= 2 * points)
+    for (uint32_t v = 0; v < points; v++) {
+      re_im[2 * v] = h->c.amp[ldpc::nrqam::axis_index(h->c, v, 0)];
+      re_im[2 * v + 1] = h->c.amp[ldpc::nrqam::axis_index(h->c, v, 1)];
+    }
+  return points;
+}
+
+int32_t ldpc_toolbox_nr_qam_sequence(void *qam, uint8_t *c, size_t len, int64_t c_init) {
+  g_last_error.clear();
+  auto *h = static_cast<NrQamHandle *>(qam);
+  if (!h) return nr_qam_refuse("null NR modulation handle");
+  if (const char *why = ldpc::nrqam::sequence_argument_error(len, c_init)) return nr_qam_refuse(why);
+  if (len == 0) return 0;
+  if (!c) return nr_qam_refuse("null sequence buffer");
+  if (int32_t rc = nr_qam_device_state(h)) return rc;
+  if (h->dev->sequence_host(c, len, static_cast<uint32_t>(c_init)) == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+int32_t ldpc_toolbox_nr_qam_mod_f32(void *qam, float *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len, size_t batch,
+                                    int64_t c_init) {
+  return nr_qam_mod(qam, symbols, symbols_len, bits, bits_len, batch, false, c_init, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_qam_mod_f64(void *qam, double *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len, size_t batch,
+                                    int64_t c_init) {
+  return nr_qam_mod(qam, symbols, symbols_len, bits, bits_len, batch, true, c_init, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_qam_mod_f32_device(void *qam, float *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                           size_t batch, int64_t c_init, void *hip_stream) {
+  return nr_qam_mod(qam, symbols, symbols_len, bits, bits_len, batch, false, c_init, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_qam_mod_f64_device(void *qam, double *symbols, size_t symbols_len, const uint8_t *bits, size_t bits_len,
+                                           size_t batch, int64_t c_init, void *hip_stream) {
+  return nr_qam_mod(qam, symbols, symbols_len, bits, bits_len, batch, true, c_init, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_qam_demod_f32(void *qam, float *llrs, size_t llrs_len, const float *symbols, size_t symbols_len, size_t batch,
+                                      double noise_sigma, int32_t max_log, int64_t c_init) {
+  return nr_qam_demod(qam, llrs, llrs_len, symbols, symbols_len, batch, false, noise_sigma, max_log, c_init, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_qam_demod_f64(void *qam, double *llrs, size_t llrs_len, const double *symbols, size_t symbols_len, size_t batch,
+                                      double noise_sigma, int32_t max_log, int64_t c_init) {
+  return nr_qam_demod(qam, llrs, llrs_len, symbols, symbols_len, batch, true, noise_sigma, max_log, c_init, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_qam_demod_f32_device(void *qam, float *llrs, size_t llrs_len, const float *symbols, size_t symbols_len,
+                                             size_t batch, double noise_sigma, int32_t max_log, int64_t c_init, void *hip_stream) {
+  return nr_qam_demod(qam, llrs, llrs_len, symbols, symbols_len, batch, false, noise_sigma, max_log, c_init, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_qam_demod_f64_device(void *qam, double *llrs, size_t llrs_len, const double *symbols, size_t symbols_len,
+                                             size_t batch, double noise_sigma, int32_t max_log, int64_t c_init, void *hip_stream) {
+  return nr_qam_demod(qam, llrs, llrs_len, symbols, symbols_len, batch, true, noise_sigma, max_log, c_init, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_sim_set_nr_qam(void *sim, void *qam, int32_t max_log) {
+  g_last_error.clear();
+  auto *s = static_cast<ldpc::Simulator *>(sim);
+  if (!s) {
+    set_error("null argument");
+    return -1;
+  }
+  auto *h = static_cast<NrQamHandle *>(qam);
+  if (s->set_nr_qam(h ? &h->c : nullptr, max_log != 0)) return 0;
+  set_error(s->last_error());
+  return -1;
+}
+
+// ---- code tables and utilities ------------------------------------------------------------------------
 
 size_t ldpc_toolbox_code_alist(const char *spec, char *buffer, size_t buffer_len) {
   if (!spec) return 0;

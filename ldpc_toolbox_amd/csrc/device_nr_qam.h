@@ -1,0 +1,76 @@
+// Batched 5G NR modulation mapper, soft demapper and scrambling on the GPU: the device side of nrqam::Config (nr_qam.h),
+// for the ldpc_toolbox_nr_qam_* entries of the C ABI.  The kernels are in kernels_nr_qam.hip.h; the host side
+// (device_nr_qam.hip.h) is part of the simulator's translation unit, as the demapper and the rate matcher are.
+#pragma once
+#include <hip/hip_runtime_api.h>
+
+#include <cstdint>
+#include <string>
+
+#include "hip_owned.h"
+#include "nr_qam.h"
+
+namespace ldpc {
+
+// The simulator's fused generator (nrqam::qam_llr_kernel), enqueued on `s`: frames [first_frame, first_frame + frames) of
+// pooled transmitted rows tx [pool][n_tx] -> llrs [frames][n_tx] in transmitted order.
+void nr_qam_launch_generator(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t n_tx, uint64_t seed,
+                             uint64_t first_frame, uint32_t frames, double sigma, float *llrs, hipStream_t s);
+
+class DeviceNrQam {
+ public:
+  // nullptr (and *err) when there is no usable GPU: there is no CPU path.
+  static DeviceNrQam *create(const nrqam::Config &c, int device, std::string *err);
+  ~DeviceNrQam();
+  DeviceNrQam(const DeviceNrQam &) = delete;
+  DeviceNrQam &operator=(const DeviceNrQam &) = delete;
+
+  int device() const { return device_; }
+  const std::string &last_error() const { return error_; }
+  // how often the Gold kernel has run: a call with the (c_init, length) of the one before it does not run it again
+  uint64_t sequence_launches() const { return sequence_launches_; }
+
+  // bits [batch][bits_len] -> symbols [batch][symbols_len] (re, im), floats or (f64) doubles; the arguments already
+  // checked (nrqam::mod_argument_error, device_pointer_error).  0, or -2 on a HIP failure.  Device pointers; stream:
+  // launch stream (nullptr = the handle's own stream, ordered after everything queued on the legacy default stream at
+  // the time of the call, and synchronised on return).
+  int mod_device(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch, int64_t c_init,
+                 hipStream_t stream);
+  // symbols -> llrs [batch][llrs_len] (nrqam::demod_argument_error)
+  int demod_device(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
+                   bool max_log, int64_t c_init, hipStream_t stream);
+  // Host pointers: staged through device buffers of the handle, synchronous.
+  int mod_host(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch, int64_t c_init);
+  int demod_host(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
+                 bool max_log, int64_t c_init);
+  // c(0 .. len-1) as the Gold kernel wrote it, one byte per bit (nrqam::sequence_argument_error)
+  int sequence_host(uint8_t *c, size_t len, uint32_t c_init);
+
+ private:
+  DeviceNrQam() = default;
+  bool fail(const std::string &m, hipError_t e = hipSuccess);
+  int begin(hipStream_t stream, hipStream_t *s);
+  int end(hipStream_t stream, hipStream_t s, bool scrambled);
+  // the sequence of (c_init, len) in d_gold_, generated on `s` unless it is the one already there: *c = its words, or
+  // nullptr for c_init -1.  -2 on a HIP failure.
+  int sequence(int64_t c_init, size_t len, hipStream_t s, const uint32_t **c);
+
+  nrqam::Config c_;
+  int device_ = -1;
+  std::string error_;
+  // what the handle owns (hip_owned.h): the stream is declared first and so destroyed last
+  Stream stream_;
+  Event ev_default_;
+  // the cached sequence: ceil(len / 32) + 1 words; the stream that generated it, the event behind that launch, and the
+  // event behind the last launch that read it (a later generation waits for it)
+  Event ev_gold_, ev_gold_read_;
+  hipStream_t gold_stream_ = nullptr;
+  bool gold_valid_ = false, gold_read_ = false;
+  int64_t gold_c_init_ = -1;
+  size_t gold_len_ = 0;
+  uint64_t sequence_launches_ = 0;
+  DeviceBuffer d_gold_;
+  DeviceBuffer d_in_, d_out_;  // the staging buffers of the host entries
+};
+
+}  // namespace ldpc

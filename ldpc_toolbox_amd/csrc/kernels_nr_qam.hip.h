@@ -1,0 +1,271 @@
+// Kernels of the 5G NR modulation mapper, soft demapper and scrambling (nr_qam.h; include/ldpc_toolbox.h, PART 8).
+// One thread per symbol, indexed by a 64-bit id; no LDS.  Compiled with -ffp-contract=off: every product and sum below is
+// rounded once, as the definition says.
+//
+//   * gold_kernel: c(n) of 38.211 5.2.1, bit n of the sequence at bit n % 32 of word n / 32.  One thread per run of
+//     kGoldRunWords words.  It reaches the two LFSR states at the start of its run by jump-ahead -- x^(1600 + start)
+//     modulo each feedback polynomial, square-and-multiply over GF(2), applied to the first 61 bits of the register's
+//     sequence -- and then steps the run out a word at a time.  Nothing is serial in the sequence length.
+//   * map_kernel: the 2^h amplitudes are not selected from a table at all: a lane computes its integer level L_u from
+//     its h bits with 38.211's nested form (h - 1 integer subtractions) and multiplies by a in f64 -- the one product
+//     that defines A_u -- so there is neither LDS nor a lane-dependent index into the kernel arguments.
+//   * demap_kernel<H, IO, A, MAXLOG>: per axis d_u = sx * A_u - K_u and the 2h folds over ascending u; A_u and K_u travel
+//     in the kernel arguments and every index is wave-uniform (scalar loads).  The QM LLRs of a symbol leave as 8- or
+//     16-byte vector stores, nontemporal on the max-log path.
+//   * qam_llr_kernel<H, MAXLOG>: the simulator's generator, fused: pooled transmitted row -> symbol -> AWGN -> the f64
+//     demapper -> float.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+
+#include "frame_gen.hip.h"
+#include "kernels_demod.hip.h"
+
+namespace ldpc {
+namespace nrqam {
+
+constexpr int kThreads = demod::kThreads;
+
+// ---- the Gold sequence ------------------------------------------------------------------------------------------------
+
+constexpr uint32_t kGoldRunWords = 32;               // a thread's run: 1024 bits of c
+constexpr uint32_t kGoldPoly1 = 0x00000009u;         // x1(n+31) = x1(n+3) ^ x1(n):                      x^31 = x^3 + 1
+constexpr uint32_t kGoldPoly2 = 0x0000000Fu;         // x2(n+31) = x2(n+3) ^ x2(n+2) ^ x2(n+1) ^ x2(n):  x^31 = x^3 + x^2 + x + 1
+constexpr uint32_t kGoldMask31 = 0x7FFFFFFFu;
+
+// a * b modulo x^31 + poly over GF(2): a, b of degree < 31
+GEN_FN uint32_t gf2_mulmod(uint32_t a, uint32_t b, uint32_t poly) {
+  uint64_t p = 0;
+  for (int i = 0; i < 31; i++)
+    if ((b >> i) & 1u) p ^= uint64_t(a) << i;
+  for (int d = 60; d >= 31; d--)  // x^d = x^(d-31) * poly
+    if ((p >> d) & 1u) p ^= (uint64_t(1) << d) ^ (uint64_t(poly) << (d - 31));
+  return static_cast<uint32_t>(p);
+}
+
+// x^e modulo x^31 + poly, left-to-right square-and-multiply (the multiplication by x is a shift)
+GEN_FN uint32_t gf2_xpow(uint64_t e, uint32_t poly) {
+  uint32_t r = 1;
+  for (int i = e ? 63 - __builtin_clzll(e) : -1; i >= 0; i--) {
+    r = gf2_mulmod(r, r, poly);
+    if ((e >> i) & 1u) {
+      r <<= 1;
+      if (r >> 31) r = (r & kGoldMask31) ^ poly;
+    }
+  }
+  return r;
+}
+
+// the feedback of both registers reaches at most 3 positions ahead, so 28 new bits follow from 31 known ones at once
+template <bool X2>
+GEN_FN uint64_t gold_taps(uint64_t s) {
+  return X2 ? (s >> 3) ^ (s >> 2) ^ (s >> 1) ^ s : (s >> 3) ^ s;
+}
+
+// s: bits n .. n+30 of a register's sequence at bits 0..30 -> bits n .. n+63 (two steps of 28 and of 5 new bits)
+template <bool X2>
+GEN_FN uint64_t gold_extend(uint64_t s) {
+  s |= (gold_taps<X2>(s) & 0x0FFFFFFFull) << 31;  // bits 31..58 from bits 0..30 (+3)
+  s |= (gold_taps<X2>(s) >> 28) << 59;            // bits 59..63 from bits 28..35 (+3)
+  return s;
+}
+
+// bits n .. n+30 of the register's sequence from its first 61 bits: x(n+k) = sum_i r_i x(k+i), r = x^n mod the polynomial
+GEN_FN uint32_t gold_state_at(uint64_t first61, uint32_t r) {
+  uint32_t s = 0;
+  for (int k = 0; k < 31; k++) s |= (static_cast<uint32_t>(__builtin_popcount(r & static_cast<uint32_t>(first61 >> k) & kGoldMask31)) & 1u) << k;
+  return s;
+}
+
+// the first 61 bits of a register's sequence from its initial 31
+template <bool X2>
+GEN_FN uint64_t gold_first61(uint32_t init) {
+  return gold_extend<X2>(init & kGoldMask31) & ((uint64_t(1) << 61) - 1);
+}
+
+// words [run * kGoldRunWords, ...) of c, as far as `words` reaches
+GEN_FN void gold_run(uint32_t c_init, uint32_t run, uint32_t words, uint32_t *out) {
+  const uint64_t start = 1600ull + uint64_t(run) * kGoldRunWords * 32u;
+  uint64_t s1 = gold_state_at(gold_first61<false>(1u), gf2_xpow(start, kGoldPoly1));
+  uint64_t s2 = gold_state_at(gold_first61<true>(c_init), gf2_xpow(start, kGoldPoly2));
+  const uint32_t w0 = run * kGoldRunWords;
+  for (uint32_t w = w0; w < w0 + kGoldRunWords && w < words; w++) {
+    s1 = gold_extend<false>(s1);
+    s2 = gold_extend<true>(s2);
+    out[w] = static_cast<uint32_t>(s1) ^ static_cast<uint32_t>(s2);
+    s1 = (s1 >> 32) & kGoldMask31;
+    s2 = (s2 >> 32) & kGoldMask31;
+  }
+}
+
+__global__ __launch_bounds__(kThreads) void gold_kernel(uint32_t c_init, uint32_t words, uint32_t runs, uint32_t *__restrict__ out) {
+  const uint32_t run = blockIdx.x * kThreads + threadIdx.x;
+  if (run >= runs) return;
+  gold_run(c_init, run, words, out);
+}
+
+// the QM bits c(i0) .. c(i0 + QM - 1) at bits 0 .. QM-1; the buffer has one word beyond the last bit's, so a window that
+// straddles a word boundary (QM = 6, symbol 5: bits 30..35) reads both words without a bound test
+template <int QM>
+__device__ __forceinline__ uint32_t gold_window(const uint32_t *__restrict__ c, uint32_t i0) {
+  const uint32_t w = i0 >> 5;
+  const uint64_t two = (uint64_t(c[w + 1]) << 32) | c[w];
+  return static_cast<uint32_t>(two >> (i0 & 31u)) & ((1u << QM) - 1u);
+}
+
+// ---- the mapper -------------------------------------------------------------------------------------------------------
+
+// L_u of nr_qam.h from the H bits of one axis: bit t of the axis is bit 2 t + axis of the symbol, at bit 2 t + axis of `sym_bits`
+template <int H>
+__device__ __forceinline__ int32_t axis_level(uint32_t sym_bits, int axis) {
+  int32_t v = ((sym_bits >> (2 * (H - 1) + axis)) & 1u) ? -1 : 1;
+#pragma unroll
+  for (int t = H - 2; t >= 0; t--) {
+    const int32_t rest = (int32_t(1) << (H - 1 - t)) - v;
+    v = ((sym_bits >> (2 * t + axis)) & 1u) ? -rest : rest;
+  }
+  return v;
+}
+
+template <typename T>
+struct Pair {
+  typedef T type __attribute__((ext_vector_type(2)));
+};
+
+// bits [frames][bits_len] -> symbols [frames][bits_len / QM] (re, im); c: the scrambling sequence, or nullptr
+template <int QM, typename T>
+__global__ __launch_bounds__(kThreads) void map_kernel(const uint8_t *__restrict__ bits, T *__restrict__ symbols, uint32_t symbols_len,
+                                                       uint64_t total, double a, const uint32_t *__restrict__ c) {
+  const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (id >= total) return;
+  const uint8_t *b = bits + id * QM;  // (bits_len = QM * symbols_len: the rows are dense)
+  uint32_t sym_bits = 0;
+#pragma unroll
+  for (int j = 0; j < QM; j++) sym_bits |= (b[j] == 1 ? 1u : 0u) << j;
+  if (c != nullptr) {
+    const uint32_t sym = static_cast<uint32_t>(id % symbols_len);
+    sym_bits ^= gold_window<QM>(c, QM * sym);
+  }
+  typename Pair<T>::type p;
+  p.x = static_cast<T>(static_cast<double>(axis_level<QM / 2>(sym_bits, 0)) * a);
+  p.y = static_cast<T>(static_cast<double>(axis_level<QM / 2>(sym_bits, 1)) * a);
+  *reinterpret_cast<typename Pair<T>::type *>(symbols + 2 * id) = p;
+}
+
+// ---- the demapper -----------------------------------------------------------------------------------------------------
+
+// one call's per-axis table in the arithmetic type A: amp[u] = A_u, k[u] = (0.5 * scale) * (A_u * A_u), made in double
+template <typename A>
+struct Axis {
+  A amp[16], k[16];
+};
+
+// The H LLRs of one axis from its scaled coordinate.  acc1[t] starts at its first element, u = 1 << (H-1-t); acc0[t] at
+// u = 0.  Every test on u is wave-uniform.  The max-log fold is one instruction per step, and the exact fold for H <= 2 has
+// at most 4 maxstar bodies per axis: those unroll over u completely.  The exact fold for H = 3, 4 (18 and 56 maxstar
+// bodies per axis, each an f64 exp and log1p of about 4.7 KB of code) runs the loop over u at run time with H bodies in it:
+// 23 and 30 KB per loop, one axis after the other, so that a loop stays within the 64 KB instruction cache while it runs.
+template <int H, typename A, bool MAXLOG>
+__device__ __forceinline__ void axis_fold(A s, const Axis<A> &t, A (&out)[H]) {
+  A acc0[H], acc1[H];
+  const A d0 = s * t.amp[0] - t.k[0];
+#pragma unroll
+  for (int j = 0; j < H; j++) acc0[j] = acc1[j] = d0;
+#pragma unroll MAXLOG || H <= 2 ? (1 << H) - 1 : 1
+  for (uint32_t u = 1; u < (1u << H); u++) {
+    const A d = s * t.amp[u] - t.k[u];
+#pragma unroll
+    for (int j = 0; j < H; j++) {
+      const uint32_t first = 1u << (H - 1 - j);
+      if (u & first)
+        acc1[j] = u == first ? d : demod::fold_step<MAXLOG>(acc1[j], d);
+      else
+        acc0[j] = demod::fold_step<MAXLOG>(acc0[j], d);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < H; j++) out[j] = acc0[j] - acc1[j];
+}
+
+// The 2 H LLRs of a symbol from its scaled coordinates: llr[2 t] from the I axis, llr[2 t + 1] from the Q axis.
+template <int H, typename A, bool MAXLOG>
+__device__ __forceinline__ void axis_llrs(A sx, A sy, const Axis<A> &t, A (&llr)[2 * H]) {
+  A x[H], y[H];
+  axis_fold<H, A, MAXLOG>(sx, t, x);
+  axis_fold<H, A, MAXLOG>(sy, t, y);
+#pragma unroll
+  for (int j = 0; j < H; j++) {
+    llr[2 * j] = x[j];
+    llr[2 * j + 1] = y[j];
+  }
+}
+
+// N values of type T at p (aligned to the piece size) in pieces of 16 bytes, or of 8 where 16 does not divide the row of
+// a symbol (float, QM = 2 and 6)
+template <bool NT, typename T, int N>
+__device__ __forceinline__ void store_row(T *p, const T (&x)[N]) {
+  constexpr int kPiece = (N * sizeof(T)) % 16 == 0 ? 16 / sizeof(T) : 8 / sizeof(T);
+  typedef T piece __attribute__((ext_vector_type(kPiece)));
+#pragma unroll
+  for (int i = 0; i < N; i += kPiece) {
+    piece v;
+#pragma unroll
+    for (int e = 0; e < kPiece; e++) v[e] = x[i + e];
+    demod::store_llr<NT>(reinterpret_cast<piece *>(p + i), v);
+  }
+}
+
+// symbols [frames][symbols_len] (re, im) -> llrs [frames][2 H symbols_len]; c: the scrambling sequence, or nullptr
+template <int H, typename IO, typename A, bool MAXLOG>
+__global__ __launch_bounds__(kThreads) void demap_kernel(const IO *__restrict__ symbols, IO *__restrict__ llrs, uint32_t symbols_len,
+                                                         uint64_t total, A scale, const uint32_t *__restrict__ c, const Axis<A> t) {
+  const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (id >= total) return;
+  const typename Pair<IO>::type s = *reinterpret_cast<const typename Pair<IO>::type *>(symbols + 2 * id);
+  A llr[2 * H];
+  axis_llrs<H, A, MAXLOG>(static_cast<A>(s.x) * scale, static_cast<A>(s.y) * scale, t, llr);
+  uint32_t flip = 0;
+  if (c != nullptr) flip = gold_window<2 * H>(c, 2 * H * static_cast<uint32_t>(id % symbols_len));
+  IO out[2 * H];
+#pragma unroll
+  for (int j = 0; j < 2 * H; j++) {
+    const IO x = static_cast<IO>(llr[j]);
+    out[j] = ((flip >> j) & 1u) ? -x : x;
+  }
+  store_row<MAXLOG>(llrs + id * (2 * H), out);
+}
+
+// ---- the simulator's generator ----------------------------------------------------------------------------------------
+
+// Frame first_frame + f: the pooled transmitted row's 2 H bits of symbol `sym` -> (A_uI, A_uQ) -> + sigma * (double)z per
+// coordinate, z = gen::normal_pair(seed, frame, sym) -> axis_llrs in f64 -> each LLR rounded once to float, in
+// transmitted order.  No scrambling; the symbol is never stored.  (The destination may be a caller's buffer of any float
+// alignment: scalar stores.)
+template <int H, bool MAXLOG>
+__global__ __launch_bounds__(kThreads) void qam_llr_kernel(const uint8_t *__restrict__ tx_bits, uint32_t pool, uint32_t n_tx, uint64_t seed,
+                                                           uint64_t first_frame, uint64_t total, double sigma, double scale, double a,
+                                                           const Axis<double> t, float *__restrict__ llrs) {
+  const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (id >= total) return;
+  const uint32_t symbols = n_tx / (2 * H);
+  const uint64_t f = id / symbols;
+  const uint32_t sym = static_cast<uint32_t>(id - f * symbols);
+  const uint64_t frame = first_frame + f;
+  const uint8_t *b = tx_bits + size_t(gen::pool_index(seed, frame, pool)) * n_tx + size_t(2 * H) * sym;
+  uint32_t sym_bits = 0;
+#pragma unroll
+  for (int j = 0; j < 2 * H; j++) sym_bits |= (b[j] == 1 ? 1u : 0u) << j;
+  float z0, z1;
+  gen::normal_pair(seed, frame, sym, &z0, &z1);
+  const double re = static_cast<double>(axis_level<H>(sym_bits, 0)) * a + sigma * static_cast<double>(z0);
+  const double im = static_cast<double>(axis_level<H>(sym_bits, 1)) * a + sigma * static_cast<double>(z1);
+  double llr[2 * H];
+  axis_llrs<H, double, MAXLOG>(re * scale, im * scale, t, llr);
+  float *row = llrs + f * n_tx + size_t(2 * H) * sym;
+#pragma unroll
+  for (int j = 0; j < 2 * H; j++) row[j] = static_cast<float>(llr[j]);
+}
+
+}  // namespace nrqam
+}  // namespace ldpc

@@ -13,6 +13,7 @@
 #include "demodulator.h"
 #include "device_bch.h"
 #include "device_decoder.h"
+#include "device_nr_qam.h"
 #include "device_nr_rm.h"
 #include "hip_owned.h"
 #include "encoder.h"
@@ -45,8 +46,18 @@ class Simulator {
   // numbers and sigma) and the f64 demapper of this constellation give on the pooled codewords, each rounded once to float.
   bool set_constellation(const Constellation *c, bool max_log);
   bool has_constellation() const { return use_constellation_; }
-  bool max_log() const { return use_constellation_ && max_log_; }
-  int modulation() const { return use_constellation_ ? static_cast<int>(constellation_.bits) : bits_per_symbol_; }
+  bool max_log() const { return (use_constellation_ || use_nr_qam_) && max_log_; }
+  int modulation() const {
+    return use_nr_qam_ ? static_cast<int>(nr_qam_.qm) : use_constellation_ ? static_cast<int>(constellation_.bits) : bits_per_symbol_;
+  }
+  // An NR modulation (a copy of what an "nr5g-qam:QM" handle holds: nr_qam.h) in place of what set_modulation selects;
+  // nullptr returns to that.  false with nothing changed unless n_tx is a multiple of QM and the interleaving is 0
+  // (nrqam::sim_error).  It takes the place of a constellation of set_constellation, and set_constellation takes its place.
+  // The frames are then defined by composition: the LLRs of a frame are what the NR mapper without scrambling, the AWGN
+  // channel (the run's seed, frame number and sigma) and the f64 NR demapper give on the frame's pooled transmitted row,
+  // each rounded once to float, in transmitted order.  A rate matcher's qm is not compared with QM.
+  bool set_nr_qam(const nrqam::Config *c, bool max_log);
+  bool has_nr_qam() const { return use_nr_qam_; }
   int64_t interleaving() const { return interleaving_; }
   // An outer BCH code (a copy of the one a BCH handle holds) in place of the genie of run_bch; nullptr returns to the
   // genie.  false with nothing changed unless the code's n is this simulator's k.
@@ -109,6 +120,8 @@ class Simulator {
   int bits_per_symbol_ = 1;
   bool use_constellation_ = false, max_log_ = false;
   Constellation constellation_;
+  bool use_nr_qam_ = false;
+  nrqam::Config nr_qam_;
   int64_t interleaving_ = 0;
   std::vector<uint8_t> messages_, tx_bits_;
   DeviceBuffer d_messages_, d_tx_, d_bits_, d_llrs_, d_its_, d_counters_;

@@ -9,6 +9,7 @@
 #include "demodulator.hip.h"      // so does the batched soft demapper
 #include "device_bch.hip.h"       // and the batched BCH code
 #include "device_encoder.hip.h"  // the batched GPU encoder lives in this translation unit
+#include "device_nr_qam.hip.h"    // the NR modulation mapper, demapper and scrambling
 #include "device_nr_rm.hip.h"     // and the batched NR rate matcher
 #include "device_nr_tb.hip.h"     // and the NR transport block CRCs, segmentation and concatenation
 #include "frame_gen.hip.h"
@@ -168,7 +169,23 @@ bool Simulator::set_constellation(const Constellation *c, bool max_log) {
     constellation_ = *c;
   }
   use_constellation_ = c != nullptr;
-  max_log_ = c != nullptr && max_log;
+  if (c != nullptr) use_nr_qam_ = false;  // (one takes the other's place)
+  max_log_ = use_nr_qam_ ? max_log_ : c != nullptr && max_log;
+  budget_valid_ = false;  // (as in set_modulation)
+  return true;
+}
+
+bool Simulator::set_nr_qam(const nrqam::Config *c, bool max_log) {
+  if (c != nullptr) {
+    if (const char *why = nrqam::sim_error(*c, n_tx_, interleaving_)) {
+      fail(why);
+      return false;
+    }
+    nr_qam_ = *c;
+    use_constellation_ = false;  // (one takes the other's place)
+  }
+  use_nr_qam_ = c != nullptr;
+  max_log_ = use_constellation_ ? max_log_ : c != nullptr && max_log;
   budget_valid_ = false;  // (as in set_modulation)
   return true;
 }
@@ -219,6 +236,7 @@ bool Simulator::set_rate_match(const nrrm::Config *c, uint64_t e, uint32_t rv, u
     for (uint32_t p = 0; p < pool_; p++)
       for (uint32_t pos = 0; pos < plan.e; pos++) tx[size_t(p) * e + pos] = cws[size_t(p) * n_ + nrrm::column_of_position(plan, pos)];
   } else {
+    if (use_nr_qam_ && n_ % nr_qam_.qm != 0) return refuse("the codeword length is not a multiple of the NR modulation's QM: clear that first");
     tx = cws;
   }
   if (hipSetDevice(device_) != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) return refuse("the simulator's stream failed");
@@ -263,6 +281,10 @@ bool Simulator::set_interleaving(int64_t columns) {
   const uint64_t c = columns < 0 ? uint64_t(-columns) : uint64_t(columns);
   if (c > 0x7FFFFFFFull || (c != 0 && n_tx_ % c != 0)) {
     fail("interleaver columns must divide the transmitted length (interleaving.rs:44)");
+    return false;
+  }
+  if (use_nr_qam_ && columns != 0) {
+    fail("the NR mapper takes no interleaving (NR's bit interleaver is the rate matcher's)");
     return false;
   }
   interleaving_ = columns;
@@ -327,6 +349,10 @@ void Simulator::launch_table_generator(double sigma, uint64_t seed, uint64_t fir
 void Simulator::launch_generator(double ebn0_db, uint64_t seed, uint64_t first_frame, uint32_t frames, float *dst) {
   const uint32_t n_tx = static_cast<uint32_t>(n_tx_);
   if (dst == nullptr) dst = rate_match_ ? d_rx_.get<float>() : d_llrs_.get<float>();
+  if (use_nr_qam_) {
+    nr_qam_launch_generator(nr_qam_, max_log_, d_tx_.get<uint8_t>(), pool_, n_tx, seed, first_frame, frames, noise_sigma(ebn0_db), dst, stream_);
+    return;
+  }
   if (use_constellation_ && !constellation_.bpsk) {
     launch_table_generator(noise_sigma(ebn0_db), seed, first_frame, frames, dst);
     return;

@@ -369,6 +369,15 @@ class Simulator:
         if _capi.lib().ldpc_toolbox_sim_set_constellation(self._h, h, int(bool(max_log))) != 0:
             raise ValueError(_capi.last_error() or "cannot set the constellation")
 
+    def set_nr_qam(self, qam, max_log=False):
+        """`qam`: an `NrQam` whose 5G NR modulation (no scrambling) generates the frames from now on, in place of any
+        constellation of `set_constellation`, or None for what the "modulation" key selects.  ValueError (nothing changed)
+        unless n_tx is a multiple of its bits per symbol and the interleaving is 0."""
+        h = None if qam is None else qam._h
+        if _capi.lib().ldpc_toolbox_sim_set_nr_qam(self._h, h, int(bool(max_log))) != 0:
+            raise ValueError(_capi.last_error() or "cannot set the NR modulation")
+        self.bits_per_symbol = self.get("modulation")
+
     def set_bch(self, code):
         """`code`: a `BchCode` whose bounded-distance decoder gives the outer-BCH counters of `run(..., bch_max_errors=t)`
         from now on, or None for the genie ("at most bch_max_errors bit errors count as corrected").  ValueError (nothing
