@@ -168,7 +168,8 @@ int32_t ldpc_toolbox_encoder_encode_batch(void *encoder, uint8_t *output, size_t
 /* The same on buffers resident in the encoder's GPU memory (both are device pointers, and they do not overlap).
  * hip_stream: as for the ..._decode_batch_*_device entries -- a hipStream_t: enqueue and return (the caller orders the
  * call after the producers of `input`); NULL: the handle's own stream, ordered after everything queued on the legacy
- * default stream at the time of the call, and synchronised before returning. */
+ * default stream at the time of the call, and synchronised before returning.  The work buffers belong to the handle:
+ * calls on one handle on different streams are to be ordered by the caller. */
 int32_t ldpc_toolbox_encoder_encode_batch_device(void *encoder, uint8_t *output, size_t output_len,
                                                  const uint8_t *input, size_t input_len, size_t batch,
                                                  void *hip_stream);
@@ -439,7 +440,8 @@ size_t ldpc_toolbox_bch_generator(void *bch, uint8_t *coefficients, size_t len);
  * Without a GPU LDPC_TOOLBOX_ERR_DEVICE (there is no CPU path).  batch == 0 returns 0; batch is otherwise unlimited.
  * Input and output do not overlap.  One call at a time per handle.  Host pointers (staged through the handle's buffers)
  * or, _device, device pointers and a hipStream_t: a stream = enqueue and return; NULL = the handle's own stream, ordered
- * after what the legacy default stream holds at the call, synchronised on return. */
+ * after what the legacy default stream holds at the call, synchronised on return.  The decoder's list, count and
+ * syndrome buffers belong to the handle: calls on one handle on different streams are to be ordered by the caller. */
 int32_t ldpc_toolbox_bch_encode_batch(void *bch, uint8_t *output, size_t output_len, const uint8_t *input, size_t input_len,
                                       size_t batch);
 int32_t ldpc_toolbox_bch_encode_batch_device(void *bch, uint8_t *output, size_t output_len, const uint8_t *input,
@@ -488,8 +490,11 @@ int32_t ldpc_toolbox_sim_set_bch(void *sim, void *bch);
  * The constructor needs no GPU (`device` is used by the first batched call; -1 = LDPC_TOOLBOX_DEVICE, default 0). */
 void *ldpc_toolbox_nr_rm_ctor(const char *spec, int32_t device);
 void ldpc_toolbox_nr_rm_dtor(void *rm);
-/* key: "n", "k" (K), "zc", "base_graph", "fillers", "n_cb", "buffer_len" (L), "k0_0" .. "k0_3", "device" (-1 until the
- * first batched call made the device state).  returns 0, or -1 for an unknown key. */
+/* key: "n", "k" (K), "zc", "base_graph", "fillers", "n_cb", "buffer_len" (L), "k0_0" .. "k0_3", "pass_elements" (a
+ * batched call runs in passes of floor(pass_elements / row) frames, at least one; row = e for match, max(n, e) for
+ * recover), "stage_bytes" (a host entry stages floor(stage_bytes / (max(n, e) * element size)) frames on the device at a
+ * time, at least one), "device" (-1 until the first batched call made the device state).  returns 0, or -1 for an
+ * unknown key. */
 int32_t ldpc_toolbox_nr_rm_get(void *rm, const char *key, int64_t *value);
 /* codewords [batch][n] -- exactly the output of ldpc_toolbox_encoder_encode_batch_device; a byte equal to 1 is a one,
  * anything else a zero -- to output [batch][e], bytes 0 or 1 in transmitted order.
@@ -555,7 +560,11 @@ int32_t ldpc_toolbox_sim_set_rate_match(void *sim, void *rm, size_t e, uint32_t 
 void *ldpc_toolbox_nr_tb_ctor(const char *spec, int32_t device);
 void ldpc_toolbox_nr_tb_dtor(void *tb);
 /* key: "a", "base_graph", "tb_crc" (L_tb), "b", "c", "cb_crc" (L_cb), "k_prime", "k_b", "zc", "k", "fillers" (F), "n",
- * "device" (-1 until the first batched call made the device state).  returns 0, or -1 for an unknown key. */
+ * "pass_rows" (segment and desegment run in passes of floor(pass_rows / C) transport blocks, at least one),
+ * "pass_elements" (concatenate and split in passes of floor(pass_elements / G), at least one), "stage_bytes" (a host
+ * entry stages floor(stage_bytes / bytes of a transport block's longest side) transport blocks on the device at a time,
+ * at least one: C K bytes for segment and desegment, G elements for concatenate and split), "device" (-1 until the first
+ * batched call made the device state).  returns 0, or -1 for an unknown key. */
 int32_t ldpc_toolbox_nr_tb_get(void *tb, const char *key, int64_t *value);
 /* TS 38.212 7.2.2: the base graph for payload size a and target code rate `rate`: 2 if a <= 292, or a <= 3824 and
  * rate <= 0.67, or rate <= 0.25; otherwise 1. */
@@ -571,7 +580,9 @@ int32_t ldpc_toolbox_nr_tb_block_lengths(void *tb, uint64_t g, uint64_t q, uint6
  * nothing written.  Without a GPU LDPC_TOOLBOX_ERR_DEVICE (there is no CPU path).  batch == 0 returns 0; batch is
  * otherwise unlimited.  Input and output do not overlap.  One call at a time per handle.  Host pointers (staged through
  * the handle's buffers) or, _device, device pointers and a hipStream_t: a stream = enqueue and return; NULL = the
- * handle's own stream, ordered after what the legacy default stream holds at the call, synchronised on return.
+ * handle's own stream, ordered after what the legacy default stream holds at the call, synchronised on return.  The
+ * CRC parts of a call live in a buffer of the handle: calls on one handle on different streams are to be ordered by the
+ * caller.
  *
  * Segmentation: payload [batch][a], a = A, to rows [C * batch][k], k = K -- exactly the `input` of
  * ldpc_toolbox_encoder_encode_batch_device on "nr5g:BG:ZC".  Bytes 0 .. K'-L_cb-1 of block r are bits r (K'-L_cb) .. of
@@ -628,7 +639,10 @@ int32_t ldpc_toolbox_nr_tb_split_f64_device(void *tb, double *packed, const doub
  *     x2(n + 31) = x2(n + 3) ^ x2(n + 2) ^ x2(n + 1) ^ x2(n);  x1 starts 1, 0, ..., 0 and x2(i) = bit i of c_init, i < 31.
  *     An int64_t c_init of 0 .. 2^31 - 1 selects scrambling, -1 none; anything else is LDPC_TOOLBOX_ERR_ARGUMENT.  Every row
  *     of a batch uses the same sequence, position i of a row c(i).  The handle keeps the sequence of the last
- *     (c_init, row length) on the device: a call with another pair generates it first, on the call's stream.
+ *     (c_init, row length) on the device: a call with another pair generates it first, on the call's stream.  The handle
+ *     orders this cache across streams itself, with events and without waiting on the host: a call that reads the
+ *     sequence runs after the launch that generated it, and a call that generates another runs after every earlier
+ *     launch that reads the one it replaces, whatever streams those calls were given.
  *   Mapper.  bits [batch][bits_len] (a byte equal to 1 is a one, anything else a zero) -> symbols [batch][bits_len / QM],
  *     (re, im) pairs.  Bit i of a row is XORed with c(i) first.  The symbol is (A_uI, A_uQ): the doubles for _f64, each
  *     rounded once to float for _f32.

@@ -1374,6 +1374,10 @@ int32_t ldpc_toolbox_nr_rm_get(void *rm, const char *key, int64_t *value) {
     *value = h->c.l;
   else if (k.size() == 4 && k.compare(0, 3, "k0_") == 0 && k[3] >= '0' && k[3] <= '3')
     *value = ldpc::nrrm::k0_of(h->c, static_cast<uint32_t>(k[3] - '0'));
+  else if (k == "pass_elements")  // elements per pass of a batched call
+    *value = static_cast<int64_t>(ldpc::kNrRmPassElements);
+  else if (k == "stage_bytes")  // bytes of its longest rows a host entry stages on the device at a time
+    *value = static_cast<int64_t>(ldpc::kNrRmStageBytes);
   else if (k == "device")
     *value = h->dev ? h->dev->device() : -1;
   else
@@ -1473,6 +1477,12 @@ int32_t ldpc_toolbox_nr_tb_get(void *tb, const char *key, int64_t *value) {
     *value = c.fillers;
   else if (k == "n")
     *value = c.n;
+  else if (k == "pass_rows")  // code block rows per pass of segment / desegment
+    *value = static_cast<int64_t>(ldpc::kNrTbPassRows);
+  else if (k == "pass_elements")  // elements per pass of concatenate / split
+    *value = static_cast<int64_t>(ldpc::kNrTbPassElements);
+  else if (k == "stage_bytes")  // bytes of its longest side a host entry stages on the device at a time
+    *value = static_cast<int64_t>(ldpc::kNrTbStageBytes);
   else if (k == "device")
     *value = h->dev ? h->dev->device() : -1;
   else

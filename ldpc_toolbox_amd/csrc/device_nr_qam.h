@@ -62,9 +62,10 @@ class DeviceNrQam {
   Stream stream_;
   Event ev_default_;
   // the cached sequence: ceil(len / 32) + 1 words; the stream that generated it, the event behind that launch, and the
-  // event behind the last launch that read it (a later generation waits for it)
+  // event behind the last launch that read it, with that launch's stream.  A reader on another stream waits for the
+  // event before it takes it over, so the event is behind every earlier reader and a later generation waits for it alone.
   Event ev_gold_, ev_gold_read_;
-  hipStream_t gold_stream_ = nullptr;
+  hipStream_t gold_stream_ = nullptr, gold_read_stream_ = nullptr;
   bool gold_valid_ = false, gold_read_ = false;
   int64_t gold_c_init_ = -1;
   size_t gold_len_ = 0;

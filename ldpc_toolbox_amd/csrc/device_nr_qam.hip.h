@@ -172,6 +172,7 @@ int DeviceNrQam::end(hipStream_t stream, hipStream_t s, bool scrambled) {
   if (scrambled) {
     NRQAM_TRY(hipEventRecord(ev_gold_read_, s));
     gold_read_ = true;
+    gold_read_stream_ = s;
   }
   if (!stream) NRQAM_TRY(hipStreamSynchronize(s));
   return 0;
@@ -182,6 +183,9 @@ int DeviceNrQam::sequence(int64_t c_init, size_t len, hipStream_t s, const uint3
   if (c_init < 0) return 0;
   if (gold_valid_ && gold_c_init_ == c_init && gold_len_ == len) {
     if (s != gold_stream_) NRQAM_TRY(hipStreamWaitEvent(s, ev_gold_, 0));
+    // ev_gold_read_ moves to this reader: it goes behind the last one, so that the one event stays behind every reader
+    // on whatever stream, and a later generation that waits for it overwrites words nobody reads any more
+    if (gold_read_ && s != gold_read_stream_) NRQAM_TRY(hipStreamWaitEvent(s, ev_gold_read_, 0));
     *c = d_gold_.get<uint32_t>();
     return 0;
   }

@@ -68,6 +68,31 @@ def test_match_and_recover_equal_the_restatement(bg, fillers, ncb):
     rm.close()
 
 
+@pytest.mark.parametrize("rv", range(4))
+@pytest.mark.parametrize("spec", ["nr5g:1:384:40:16896", "nr5g:2:384:0"])
+def test_standard_sizes_equal_the_restatement(spec, rv):
+    """Zc = 384: BG 1 with 40 fillers and a limited buffer of two thirds of N, and BG 2 whole.  The divisors of the index
+    arithmetic are in the ten-thousands and k0 is a multiple of 384.  E = 16896 (QPSK, part of the buffer), E = 60000
+    (64QAM, some columns twice or more) and E = 2 L + 64 (256QAM, every column sent at least twice), every byte and bit."""
+    ref = rr.Config(*(int(x) for x in spec.split(":")[1:]))
+    rm = lt.NrRateMatcher(spec, device=0)
+    assert (rm.n, rm.n_cb, rm.buffer_len) == (ref.n, ref.ncb, ref.L) and [rm.k0(v) for v in range(4)] == [ref.k0(v) for v in range(4)]
+    assert ref.k0(rv) % 384 == 0 and (rv == 0 or ref.k0(rv) > 0)
+    rng = np.random.default_rng(384 * ref.bg + rv)
+    batch = 3
+    sent = ref.buffer[:ref.ncb][ref.buffer[:ref.ncb] != rr.NULL]
+    for e, qm in ((16896, 2), (60000, 6), (2 * ref.L + 8 * 8, 8)):
+        if qm == 8:
+            assert ref.repeats(e, rv)[sent].min() >= 2, "every column repeats"
+        cws = rng.choice(np.array([0, 1, 1, 2, 255], dtype=np.uint8), (batch, ref.n))
+        assert np.array_equal(rm.match(cws, e, rv, qm), ref.match(cws, e, rv, qm)), (e, qm)
+        for dtype in (np.float32, np.float64):
+            rx = soft_values(rng, (batch, e), dtype)
+            llrs = rm.recover(rx, rv, qm, filler_llr=20.0)
+            assert llrs.dtype == dtype and np.array_equal(bits_of(llrs), bits_of(ref.recover(rx, rv, qm, 20.0))), (e, qm, dtype)
+    rm.close()
+
+
 def test_k0_inside_the_filler_run():
     """BG2, Zc 2, F 4, Ncb 56, rv 1: k0 = 14 lies inside the fillers 12..15"""
     ref = rr.Config(2, 2, 4, 56)

@@ -32,6 +32,7 @@ def test_handle_needs_no_gpu_and_reports_the_configuration():
     rm = lt.NrRateMatcher("nr5g:1:384")
     assert (rm.n, rm.k, rm.zc, rm.base_graph, rm.fillers, rm.n_cb, rm.buffer_len) == (26112, 8448, 384, 1, 0, 25344, 25344)
     assert [rm.k0(rv) for rv in range(4)] == [0, 6528, 12672, 21504] and rm.get("device") == -1
+    assert (rm.get("pass_elements"), rm.get("stage_bytes")) == (1 << 30, 1 << 28)
     with pytest.raises(KeyError):
         rm.get("k0_4")
     rm.close()

@@ -102,6 +102,30 @@ def test_concatenate_and_split_equal_the_restatement(bg, a):
     tb.close()
 
 
+@pytest.mark.parametrize("bg,a", [(2, 3826), BIG])
+def test_concatenate_and_split_at_standard_sizes(bg, a):
+    """G = 11704 coded bits at q = 4 (the chain test's size: blocks of thousands of bits, divisors to match), and the G
+    below it at which all blocks but the first get the longer length (c_lo = C - 1); two blocks and 152 blocks"""
+    ref = tr.Config(bg, a)
+    tb = lt.NrTransportBlock(ref.spec, device=0)
+    rng = np.random.default_rng(a + bg)
+    q, batch, c = 4, 3, ref.c
+    g_one = q * ((11704 // q) // c * c + 1)
+    for g in (11704, g_one):
+        e = ref.block_lengths(g, q)
+        e_lo, e_hi, c_lo = tb.block_lengths(g, q)
+        assert [e_lo] * c_lo + [e_hi] * (c - c_lo) == e and sum(e) == g and (g != g_one or (c_lo == c - 1 and e_hi == e_lo + q))
+        packed = rng.choice(BYTES, batch * g)
+        assert np.array_equal(tb.concatenate(packed, g, q), ref.concatenate(packed, batch, g, q)), g
+        for dtype in (np.float32, np.float64):
+            rx = (rng.standard_normal((batch, g)) * 10.0 ** rng.integers(-3, 5, (batch, g))).astype(dtype)
+            rx[rng.random((batch, g)) < 0.05] = -0.0
+            rx[0, 0] = np.nan
+            sp = tb.split(rx, q)
+            assert sp.dtype == dtype and np.array_equal(bits_of(sp), bits_of(ref.split(rx, q))), (g, dtype)
+    tb.close()
+
+
 def expect_flags(tb, ref, rows, cleared_cb, cleared_tb, what):
     """the entry equals the restatement, and the cleared flags are exactly the given ones"""
     payload, tb_ok, cb_ok = tb.desegment(rows)

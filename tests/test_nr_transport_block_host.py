@@ -40,6 +40,7 @@ def test_handle_needs_no_gpu_and_reports_the_table(bg, a):
     assert (tb.c, tb.k_prime, tb.k_b, tb.zc, tb.k, tb.fillers) == TABLE[(bg, a)]
     assert (tb.a, tb.base_graph, tb.tb_crc, tb.b, tb.cb_crc) == (a, bg, 24 if a > 3824 else 16, a + (24 if a > 3824 else 16), 24 if c > 1 else 0)
     assert tb.n == (68 if bg == 1 else 52) * zc and tb.get("device") == -1
+    assert (tb.get("pass_rows"), tb.get("pass_elements"), tb.get("stage_bytes")) == (1 << 22, 1 << 30, 1 << 28)
     assert tb.code_spec == f"nr5g:{bg}:{zc}" and tb.rate_match_spec == f"nr5g:{bg}:{zc}:{fillers}"
     ref = tr.Config(bg, a)
     assert (ref.l_tb, ref.b, ref.l_cb, ref.n) == (tb.tb_crc, tb.b, tb.cb_crc, tb.n)
