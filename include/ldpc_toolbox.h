@@ -540,6 +540,47 @@ int32_t ldpc_toolbox_nr_rm_recover_f64_device(void *rm, double *llrs, size_t n, 
  * straggler-pooling budget, as "modulation" does. */
 int32_t ldpc_toolbox_sim_set_rate_match(void *sim, void *rm, size_t e, uint32_t rv, uint32_t qm);
 
+/* HARQ with incremental-redundancy soft combining: a sequence of `transmissions` = T transmissions (e[t], rv[t]), t < T,
+ * 1 <= T <= 8, of one qm.
+ *   Configuration.  Each (e[t], rv[t], qm) is a transmission as above, each e[t] a multiple of the modulation's bits per
+ *   symbol, and sum e[t] <= 0x7fffffff.  The modulation is the BPSK generator or an NR modulation
+ *   (ldpc_toolbox_sim_set_nr_qam) and the interleaving 0: while "8PSK" or a table constellation is in force the sequence is
+ *   refused.  The first transmission must be one that ldpc_toolbox_sim_set_rate_match accepts.
+ *   ldpc_toolbox_sim_set_harq puts the simulator into the state of ldpc_toolbox_sim_set_rate_match(sim, rm, e[0], rv[0], qm)
+ *   -- ldpc_toolbox_sim_run, _run_bch, _generate and _pool behave exactly as after that call -- and keeps the further
+ *   transmissions.  rm == NULL, and every ldpc_toolbox_sim_set_rate_match call, clears them.  A refusal returns -1 with a
+ *   message and changes nothing.  ldpc_toolbox_sim_get: "harq" (T, or 0), "harq_e0" .. "harq_e7", "harq_rv0" .. "harq_rv7".
+ *   Noise.  n_tx = e[0] and the rate k / e[0]: sigma is computed from them as for every run and is the same for all T
+ *   transmissions, so Es/N0 is constant and an Eb/N0 refers to the first transmission.
+ *   LLRs.  A frame's HARQ process is one long transmitted row: the T rate-matched rows of its pooled codeword, concatenated,
+ *   with the noise the channel puts on that row for (seed, frame).  P_t = e[0] + ... + e[t-1].  BPSK: position j of
+ *   transmission t takes the normal of pair (P_t + j) >> 1, the pair's first normal when P_t + j is even and its second
+ *   when odd.  NR modulation of QM bits: symbol s of transmission t takes pair P_t / QM + s.  Everything else is the
+ *   generator's arithmetic; transmission 0 is bit for bit what ldpc_toolbox_sim_generate returns.
+ *   ldpc_toolbox_sim_generate_harq: llrs [frames][e[transmission]] (host) and the frames' pool indices (may be NULL).
+ *   Soft buffer, attempts, stopping.  After transmission 0 the soft buffer [n] of a frame is what
+ *   ldpc_toolbox_nr_rm_recover_f32 gives with combine = 0, after each later one with combine = 1 into the same row.  After
+ *   every transmission the frame is decoded with the full max_iterations (the straggler budget has no part in a HARQ run).
+ *   A frame stops at the first attempt that converges (iteration count >= 0, right or wrong), or after transmission T-1.
+ *   ldpc_toolbox_sim_run_harq: counters[6] = the fields of ldpc_toolbox_sim_run for each frame's final attempt -- frames,
+ *   bit errors, frame errors, false decodes (the final attempt converged with bit errors), iterations over all attempts of
+ *   the frame (a failed attempt counts max_iterations), and that sum for the frames that end with no bit error.
+ *   per_tx[T][4], for each transmission: attempts, frames that stopped because the attempt converged, of those how many
+ *   have bit errors, iterations of this transmission's attempts.  (Delivered after t: the sum over s <= t of
+ *   per_tx[s][1] - per_tx[s][2]; transmitted bits: the sum of per_tx[t][0] * e[t].)  With T = 1 counters equals what
+ *   ldpc_toolbox_sim_run returns.  A frame's result depends on (seed, frame, configuration) alone: not on the chunks a
+ *   call is cut into, nor on "pooling".  "pooling" 1: the frames that need transmission t wait in a pool of that stage and
+ *   are decoded thousands at a time ("pooled_frames": the retransmission attempts of the last call); 0: every chunk's
+ *   failures go through all stages before the next chunk ("pooled_frames" 0).  "harq_flushes_t1" .. "harq_flushes_t7" and
+ *   "harq_rows_t1" .. "harq_rows_t7": how often the last call flushed the pool of transmission t, and the rows it decoded.
+ *   Without a sequence, with a BCH code set (ldpc_toolbox_sim_set_bch), or when the modulation has changed to one the
+ *   sequence does not fit: LDPC_TOOLBOX_ERR_ARGUMENT, counters zeroed.  A null argument: -1, nothing written. */
+int32_t ldpc_toolbox_sim_set_harq(void *sim, void *rm, const uint64_t *e, const uint32_t *rv, uint32_t transmissions, uint32_t qm);
+int32_t ldpc_toolbox_sim_run_harq(void *sim, double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                                  uint32_t max_iterations, uint64_t *counters /*6*/, uint64_t *per_tx /*[T][4]*/);
+int32_t ldpc_toolbox_sim_generate_harq(void *sim, double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames,
+                                       uint32_t transmission, float *llrs /*[frames][E_t]*/, uint32_t *pool_index);
+
 /* ===================================================================================
  * PART 7 -- batched 5G NR transport block processing on the GPU (3GPP TS 38.212 5.1, 6.2.1, 7.2.1: CRC attachment;
  * 5.2.2: code block segmentation with CRC24B and filler bits; 5.5 with the E_r of 5.4.2.1: code block concatenation).

@@ -81,6 +81,9 @@ SYMBOLS = [
     "ldpc_toolbox_nr_rm_recover_f32_device",
     "ldpc_toolbox_nr_rm_recover_f64_device",
     "ldpc_toolbox_sim_set_rate_match",
+    "ldpc_toolbox_sim_set_harq",
+    "ldpc_toolbox_sim_run_harq",
+    "ldpc_toolbox_sim_generate_harq",
     "ldpc_toolbox_nr_tb_ctor",
     "ldpc_toolbox_nr_tb_dtor",
     "ldpc_toolbox_nr_tb_get",
@@ -311,6 +314,12 @@ def lib():
         f.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32, C.c_double, i32, vp]
     L.ldpc_toolbox_sim_set_rate_match.restype = i32
     L.ldpc_toolbox_sim_set_rate_match.argtypes = [vp, vp, sz, u32, u32]
+    L.ldpc_toolbox_sim_set_harq.restype = i32
+    L.ldpc_toolbox_sim_set_harq.argtypes = [vp, vp, vp, vp, u32, u32]
+    L.ldpc_toolbox_sim_run_harq.restype = i32
+    L.ldpc_toolbox_sim_run_harq.argtypes = [vp, C.c_double, u64, u64, sz, u32, vp, vp]
+    L.ldpc_toolbox_sim_generate_harq.restype = i32
+    L.ldpc_toolbox_sim_generate_harq.argtypes = [vp, C.c_double, u64, u64, sz, u32, vp, vp]
     L.ldpc_toolbox_nr_tb_ctor.restype = vp
     L.ldpc_toolbox_nr_tb_ctor.argtypes = [cp, i32]
     L.ldpc_toolbox_nr_tb_dtor.restype = None

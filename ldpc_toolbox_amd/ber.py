@@ -70,9 +70,34 @@ def point_seed(seed: int, ebn0_db: float) -> int:
     return z ^ (z >> 31)
 
 
+def harq_header() -> str:
+    """--output-file-harq: one line per (Eb/N0, transmission t)"""
+    return ("  Eb/N0 |  t | rv |          E | Attempts |    Stops | Stops er | Iteratio | Res BLER | Bits/deliv\n"
+            "--------|----|----|------------|----------|----------|----------|----------|----------|-----------")
+
+
+def harq_lines(ebn0_db, sequence, per_tx, frames):
+    """The lines of one Eb/N0 point: rv and E of transmission t, its four counters (attempts, frames that stopped because the
+    attempt converged, of those with bit errors, iterations), the residual BLER after t -- the share of the frames not yet
+    delivered, delivered = stopped without bit errors at some s <= t -- and the bits transmitted up to t per frame delivered
+    up to t (nan while none is)."""
+    from .simulation import rust_fixed, rust_lower_exp
+    lines, delivered, sent = [], 0, 0
+    for t, ((e, rv), c) in enumerate(zip(sequence, per_tx)):
+        delivered += int(c[1]) - int(c[2])
+        sent += int(c[0]) * e
+        bler = 1.0 - delivered / frames if frames else 0.0
+        per = sent / delivered if delivered else float("nan")
+        lines.append(f"{rust_fixed(ebn0_db, 7, 2)} | {t:2d} | {rv:2d} | {e:10d} | {int(c[0]):8d} | {int(c[1]):8d} | {int(c[2]):8d} | "
+                     f"{int(c[3]):8d} | {rust_lower_exp(bler, 8, 2)} | {rust_fixed(per, 10, 1)}")
+    return lines
+
+
 def sweep(sim: Simulator, ebn0s_db, max_iterations=100, max_frame_errors=100, min_time=0.0, max_time=float("inf"),
           max_frames=None, frames_per_batch=None, seed=0, rank=0, world=1, device=None, report=None,
-          bch_max_errors=0):
+          bch_max_errors=0, harq=False):
+    """harq: the frames go through the simulator's HARQ sequence (Simulator.run_harq; one rank); the per-transmission
+    counters of a point are its result's `harq_per_tx`."""
     first_batch = frames_per_batch
     if not frames_per_batch:
         # eight groups of the decoder (a group: 4096 frames, more for small graphs) per simulator call: the call's
@@ -85,6 +110,7 @@ def sweep(sim: Simulator, ebn0s_db, max_iterations=100, max_frame_errors=100, mi
     err_field = 7 if bch_max_errors > 0 else 2          # ber.rs:514-520: the BCH frame errors stop the run
     for ebn0_db in ebn0s_db:
         total = np.zeros(nc, dtype=np.int64)
+        per_tx = np.zeros((sim.get("harq"), 4), dtype=np.int64) if harq else None
         start = time.perf_counter()
         first = 0
         pseed = point_seed(seed, ebn0_db)
@@ -107,6 +133,9 @@ def sweep(sim: Simulator, ebn0s_db, max_iterations=100, max_frame_errors=100, mi
             b, e = sharding.shard_range(nb, rank, world)
             if e <= b:
                 part = np.zeros(nc, dtype=np.int64)
+            elif harq:
+                part, part_tx = sim.run_harq(ebn0_db, pseed, first + b, e - b, max_iterations)
+                per_tx += part_tx
             elif bch_max_errors > 0:
                 part = sim.run(ebn0_db, pseed, first + b, e - b, max_iterations, bch_max_errors)
             else:
@@ -116,6 +145,8 @@ def sweep(sim: Simulator, ebn0s_db, max_iterations=100, max_frame_errors=100, mi
             if report and rank == 0:
                 report(statistics_from_counters(ebn0_db, sim.k, total, time.perf_counter() - start), False)
         st = statistics_from_counters(ebn0_db, sim.k, total, time.perf_counter() - start)
+        if harq:
+            st.harq_per_tx = per_tx
         results.append(st)
         if report and rank == 0:
             report(st, True)
@@ -177,6 +208,8 @@ def format_details(a, sim, world: int) -> str:
         lines.append(f" - Interleaving columns: {a.interleaving}")
     if getattr(a, "nr_rate_match", None):                                             # this build's addition
         lines.append(f" - NR rate matching (E[:RV[:QM]]): {a.nr_rate_match}")
+    if getattr(a, "nr_harq", None):                                                   # this build's addition
+        lines.append(" - NR HARQ transmissions (RV:E): " + ", ".join(f"{rv}:{e}" for e, rv in sim.harq()))
     lines += [f" - Information bits (k): {sim.k}", f" - Codeword size (N_cw): {sim.n}", f" - Frame size (N): {sim.n_tx}",
               f" - Code rate: {sim.rate:.3f}", "LDPC decoder:", f" - Implementation: {a.decoder}",
               f" - Maximum iterations: {a.max_iter}"]
@@ -243,6 +276,16 @@ def main(argv=None):
                     help="with --code nr5g:BG:ZC: 5G NR rate matching (TS 38.212 5.4.2) of every frame to E transmitted bits "
                          "with redundancy version RV (default 0) and Qm (default 1) interleaver rows, no filler bits, Ncb = N; "
                          "the code rate becomes k/E")
+    ap.add_argument("--nr-harq", metavar="RV[:E],RV[:E],...",
+                    help="with --nr-rate-match: the further transmissions of a HARQ sequence with incremental-redundancy soft "
+                         "combining, E defaulting to the first transmission's.  Every frame is decoded after each transmission "
+                         "on the soft buffer combined so far and stops at the first attempt that converges; the table carries "
+                         "the counters of the final attempts, and Eb/N0 refers to the first transmission.  BPSK or --nr-qam; "
+                         "one rank; not with --codes or the --bch options")
+    ap.add_argument("--output-file-harq", metavar="FILE",
+                    help="with --nr-harq: one line per (Eb/N0, transmission t) -- rv, E, attempts, frames that stopped because "
+                         "the attempt converged, of those with bit errors, iterations, the residual BLER after t, and the bits "
+                         "transmitted up to t per frame delivered up to t")
     ap.add_argument("--output-file-ldpc", help="LDPC-only results when --bch-max-errors is used (cli/ber.rs:102-105)")
     ap.add_argument("--share-device", action="store_true",
                     help="rehearsal of the multi-GPU sweep on a one-GPU box: every rank uses GPU 0 and the counters are "
@@ -266,6 +309,20 @@ def main(argv=None):
             rate_match = []
         if not 1 <= len(rate_match) <= 3:
             ap.error("--nr-rate-match takes E[:RV[:QM]]")
+    harq = None
+    if a.nr_harq:
+        if not rate_match or a.codes or a.bch_max_errors > 0 or a.bch_code:
+            ap.error("--nr-harq needs --nr-rate-match and cannot be combined with --codes, --bch-max-errors or --bch-code")
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            ap.error("--nr-harq runs on one rank: the per-transmission counters are not reduced over ranks yet")
+        try:
+            harq = [[int(x) for x in item.split(":")] for item in a.nr_harq.split(",")]
+        except ValueError:
+            harq = [[]]
+        if any(not 1 <= len(item) <= 2 for item in harq):
+            ap.error("--nr-harq takes RV[:E],RV[:E],...")
+    elif a.output_file_harq:
+        ap.error("--output-file-harq needs --nr-harq")
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -318,7 +375,6 @@ def main(argv=None):
             sim.set_rate_match(rm, *rate_match)
         except ValueError as e:
             ap.error(f"--nr-rate-match {a.nr_rate_match}: {e}")
-        rm.close()
     if a.nr_qam:                                                  # (after the rate matcher: n_tx is E by now)
         from .nr_qam import NrQam
         qam = NrQam(a.nr_qam, device=local)
@@ -327,8 +383,17 @@ def main(argv=None):
         except ValueError as e:
             ap.error(f"--nr-qam {a.nr_qam}: {e}")
         qam.close()
+    if harq:                                                      # (after the modulation: every E is checked against it)
+        e0, rv0, qm = rate_match + [0, 1][len(rate_match) - 1:]
+        try:
+            sim.set_harq(rm, [(e0, rv0)] + [(item[1] if len(item) > 1 else e0, item[0]) for item in harq], qm)
+        except ValueError as e:
+            ap.error(f"--nr-harq {a.nr_harq}: {e}")
+    if rate_match:
+        rm.close()
     out = open(a.output_file, "w") if (a.output_file and rank == 0) else None
     out_ldpc = open(a.output_file_ldpc, "w") if (a.output_file_ldpc and a.bch_max_errors > 0 and rank == 0) else None
+    out_harq = open(a.output_file_harq, "w") if (a.output_file_harq and rank == 0) else None
     details = format_details(a, sim, world)
     if out:
         out.write(details)                                        # cli/ber.rs:134-141
@@ -337,6 +402,8 @@ def main(argv=None):
         out.write(format_header() + "\n")
     if out_ldpc:
         out_ldpc.write(details + "\nLDPC-only results\n\n" + format_header() + "\n")  # cli/ber.rs:142-147
+    if out_harq:
+        out_harq.write(details + "\nHARQ results per transmission\n\n" + harq_header() + "\n")
 
     def report(st, final):
         if final:
@@ -347,13 +414,16 @@ def main(argv=None):
             if out_ldpc:
                 out_ldpc.write(format_progress(st, force_ldpc=True) + "\n")
                 out_ldpc.flush()
+            if out_harq:
+                out_harq.write("\n".join(harq_lines(st.ebn0_db, sim.harq(), st.harq_per_tx, st.num_frames)) + "\n")
+                out_harq.flush()
 
     if rank == 0:
         print(details, end="")
         print(format_header(), flush=True)
     res = sweep(sim, ebn0_grid(a.min_ebn0, a.max_ebn0, a.step_ebn0), a.max_iter, a.frame_errors, a.min_time,
                 a.max_time, a.max_frames, a.frames_per_batch, a.seed, rank, world, device, report,
-                bch_max_errors=a.bch_max_errors)
+                bch_max_errors=a.bch_max_errors, harq=bool(harq))
     if distributed:
         import torch.distributed as dist
         if rank == 0:

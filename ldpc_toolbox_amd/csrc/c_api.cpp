@@ -1095,6 +1095,16 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value) {
     *value = s->has_bch() ? 1 : 0;
   else if (k == "rate_match")  // 1 while ldpc_toolbox_sim_set_rate_match is in force
     *value = s->has_rate_match() ? 1 : 0;
+  else if (k == "harq")  // transmissions of the sequence of ldpc_toolbox_sim_set_harq, 0 = none
+    *value = s->harq().t;
+  else if (k.size() == 7 && k.compare(0, 6, "harq_e") == 0 && k[6] >= '0' && k[6] <= '7')  // "harq_e0" .. "harq_e7": E_t, 0 beyond the sequence
+    *value = uint32_t(k[6] - '0') < s->harq().t ? s->harq().e[k[6] - '0'] : 0;
+  else if (k.size() == 8 && k.compare(0, 7, "harq_rv") == 0 && k[7] >= '0' && k[7] <= '7')  // "harq_rv0" .. "harq_rv7"
+    *value = uint32_t(k[7] - '0') < s->harq().t ? s->harq().rv[k[7] - '0'] : 0;
+  else if (k.size() == 15 && k.compare(0, 14, "harq_flushes_t") == 0 && k[14] >= '0' && k[14] <= '7')  // of the last run_harq call
+    *value = static_cast<int64_t>(s->harq_flushes(k[14] - '0'));
+  else if (k.size() == 12 && k.compare(0, 11, "harq_rows_t") == 0 && k[11] >= '0' && k[11] <= '7')  // rows its flushes of stage t decoded
+    *value = static_cast<int64_t>(s->harq_flushed_rows(k[11] - '0'));
   else if (k == "streamed_frames" || k == "stream_iterations")  // (continuous batching: profiles/r03_continuous_batching.txt)
     *value = 0;
   else if (k == "pooled_frames")  // frames of the last run() call that went through the straggler pool
@@ -1426,6 +1436,51 @@ int32_t ldpc_toolbox_sim_set_rate_match(void *sim, void *rm, size_t e, uint32_t 
   if (s->set_rate_match(h ? &h->c : nullptr, e, rv, qm)) return 0;
   set_error(s->last_error());
   return -1;
+}
+
+int32_t ldpc_toolbox_sim_set_harq(void *sim, void *rm, const uint64_t *e, const uint32_t *rv, uint32_t transmissions, uint32_t qm) {
+  g_last_error.clear();
+  auto *s = static_cast<ldpc::Simulator *>(sim);
+  auto *h = static_cast<NrRmHandle *>(rm);
+  // (what needs no simulator comes first: a sequence that is none is refused as such on any machine)
+  if (h != nullptr)
+    if (const char *why = ldpc::nrharq::sequence_error(e, rv, transmissions, qm, 1)) {
+      set_error(why);
+      return -1;
+    }
+  if (!s) {
+    set_error("null argument");
+    return -1;
+  }
+  if (s->set_harq(h ? &h->c : nullptr, e, rv, transmissions, qm)) return 0;
+  set_error(s->last_error());
+  return -1;
+}
+
+int32_t ldpc_toolbox_sim_run_harq(void *sim, double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations,
+                                  uint64_t *counters, uint64_t *per_tx) {
+  g_last_error.clear();
+  auto *s = static_cast<ldpc::Simulator *>(sim);
+  if (!s || !counters || !per_tx) {
+    set_error("null argument");
+    return -1;
+  }
+  const int rc = s->run_harq(ebn0_db, seed, first_frame, frames, max_iterations, counters, per_tx);
+  if (rc) set_error(s->last_error());
+  return rc;
+}
+
+int32_t ldpc_toolbox_sim_generate_harq(void *sim, double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t transmission,
+                                       float *llrs, uint32_t *pool_index) {
+  g_last_error.clear();
+  auto *s = static_cast<ldpc::Simulator *>(sim);
+  if (!s || !llrs) {
+    set_error("null argument");
+    return -1;
+  }
+  const int rc = s->generate_harq(ebn0_db, seed, first_frame, frames, transmission, llrs, pool_index);
+  if (rc) set_error(s->last_error());
+  return rc;
 }
 
 // ---- PART 7: batched 5G NR transport block CRC, segmentation and concatenation -----------------------

@@ -17,6 +17,13 @@ namespace ldpc {
 void nr_qam_launch_generator(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t n_tx, uint64_t seed,
                              uint64_t first_frame, uint32_t frames, double sigma, float *llrs, hipStream_t s);
 
+// One transmission of a HARQ sequence (nrqam::qam_llr_harq_kernel; nr_harq.h): tx [pool][e] are that transmission's pooled
+// rows, row r of llrs [frames][e] is frame frame_ids[r] (a device array), or first_frame + r when it is nullptr, and
+// symbol s takes the normal pair first_symbol + s.
+void nr_qam_launch_harq_generator(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t e, uint32_t first_symbol,
+                                  uint64_t seed, uint64_t first_frame, const uint64_t *frame_ids, uint32_t frames, double sigma,
+                                  float *llrs, hipStream_t s);
+
 class DeviceNrQam {
  public:
   // nullptr (and *err) when there is no usable GPU: there is no CPU path.

@@ -156,6 +156,34 @@ void nr_qam_launch_generator(const nrqam::Config &c, bool max_log, const uint8_t
   }
 }
 
+namespace {
+template <int H>
+void nr_qam_harq_generator_pass(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t e, uint32_t first_symbol,
+                                uint64_t seed, uint64_t first_frame, const uint64_t *frame_ids, uint64_t total, double sigma, float *llrs,
+                                hipStream_t s) {
+  const double scale = 1.0 / (sigma * sigma);
+  const nrqam::Axis<double> t = nr_qam_axis<double>(c, scale);
+  if (max_log)
+    nrqam::qam_llr_harq_kernel<H, true><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(tx, pool, e, first_symbol, seed, first_frame,
+                                                                                        frame_ids, total, sigma, scale, c.a, t, llrs);
+  else
+    nrqam::qam_llr_harq_kernel<H, false><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(tx, pool, e, first_symbol, seed, first_frame,
+                                                                                         frame_ids, total, sigma, scale, c.a, t, llrs);
+}
+}  // namespace
+
+void nr_qam_launch_harq_generator(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t e, uint32_t first_symbol,
+                                  uint64_t seed, uint64_t first_frame, const uint64_t *frame_ids, uint32_t frames, double sigma,
+                                  float *llrs, hipStream_t s) {
+  const uint64_t total = uint64_t(frames) * (e / c.qm);
+  switch (c.h()) {
+    case 1: return nr_qam_harq_generator_pass<1>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, llrs, s);
+    case 2: return nr_qam_harq_generator_pass<2>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, llrs, s);
+    case 3: return nr_qam_harq_generator_pass<3>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, llrs, s);
+    default: return nr_qam_harq_generator_pass<4>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, llrs, s);
+  }
+}
+
 int DeviceNrQam::begin(hipStream_t stream, hipStream_t *s) {
   NRQAM_TRY(hipSetDevice(device_));
   *s = stream ? stream : static_cast<hipStream_t>(stream_);

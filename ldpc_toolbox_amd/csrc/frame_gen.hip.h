@@ -309,6 +309,101 @@ __global__ __launch_bounds__(256) void straggler_collect_kernel(const int32_t *_
   float *dst = pool_llrs + size_t(pos) * n_tx;
   for (uint32_t i = lane; i < n_tx; i += 64) dst[i] = src[i];
 }
+
+// ---- HARQ (nr_harq.h; Simulator::run_harq) --------------------------------------------------------------------------
+// BPSK frames of one transmission of a HARQ sequence: awgn_llr_kernel for a list of frames at a position offset.
+// tx_bits [pool][e]: this transmission's pooled transmitted rows; llrs [frames][e].  Row r is frame frame_ids[r], or
+// first_frame + r without a list.  Position j of the row is position offset + j of the frame's concatenated row and takes
+// the noise of that position: pair (offset + j) >> 1, its first normal when offset + j is even.  One thread per pair that
+// the row touches, first_pair = offset >> 1 on; a pair that straddles the seam between two transmissions is drawn by both
+// launches, and each uses the normal of its own position only.
+__global__ __launch_bounds__(256) void awgn_llr_harq_kernel(const uint8_t *__restrict__ tx_bits, uint32_t pool, uint32_t e,
+                                                            uint32_t offset, uint32_t pairs, uint64_t seed, uint64_t first_frame,
+                                                            const uint64_t *__restrict__ frame_ids, uint32_t frames, float sigma,
+                                                            float scale, float *__restrict__ llrs) {
+  const uint64_t id = uint64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+  if (id >= uint64_t(frames) * pairs) return;
+  const uint32_t f = static_cast<uint32_t>(id / pairs), q = static_cast<uint32_t>(id % pairs);
+  const uint64_t frame = frame_ids ? frame_ids[f] : first_frame + f;
+  const uint32_t pair = (offset >> 1) + q;
+  float z0, z1;
+  normal_pair(seed, frame, pair, &z0, &z1);
+  const uint8_t *cw = tx_bits + size_t(pool_index(seed, frame, pool)) * e;
+  float *row = llrs + size_t(f) * e;
+  const uint32_t g = 2 * pair;  // position of the pair's first normal in the concatenated row; g + 1 >= offset always
+  if (g >= offset) row[g - offset] = llr_from(cw[g - offset], z0, sigma, scale);
+  if (g + 1 - offset < e) row[g + 1 - offset] = llr_from(cw[g + 1 - offset], z1, sigma, scale);
+}
+
+// The frames of an attempt that did not converge go on to the next transmission: their soft rows [n], frame numbers and
+// the iterations they have spent so far (spent_in, or nothing before the first attempt, plus this attempt's
+// max_iterations) are appended to the next stage's pool.  One wavefront per frame, one atomic per frame from lane 0; a
+// position beyond the capacity is not written, and the count then shows the overflow (as in straggler_collect_kernel).
+__global__ __launch_bounds__(256) void harq_collect_kernel(const int32_t *__restrict__ iterations, uint32_t frames, uint64_t first_frame,
+                                                           const uint64_t *__restrict__ frame_ids, const uint32_t *__restrict__ spent_in,
+                                                           uint32_t max_iterations, const float *__restrict__ soft, uint32_t n,
+                                                           float *__restrict__ pool_soft, uint64_t *__restrict__ pool_frames,
+                                                           uint32_t *__restrict__ pool_spent, uint32_t *__restrict__ pool_count,
+                                                           uint32_t capacity) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t f = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (f >= frames || iterations[f] >= 0) return;
+  uint32_t pos = 0;
+  if (lane == 0) pos = atomicAdd(pool_count, 1u);
+  pos = static_cast<uint32_t>(__shfl(static_cast<int>(pos), 0, 64));
+  if (pos >= capacity) return;
+  if (lane == 0) {
+    pool_frames[pos] = frame_ids ? frame_ids[f] : first_frame + f;
+    pool_spent[pos] = (spent_in ? spent_in[f] : 0u) + max_iterations;
+  }
+  const float *src = soft + size_t(f) * n;
+  float *dst = pool_soft + size_t(pos) * n;
+  for (uint32_t i = lane; i < n; i += 64) dst[i] = src[i];
+}
+
+// The counters of one attempt (transmission t) of `frames` frames.  per_tx[4] of this transmission: [0] attempts
+// [1] frames that stop here because the attempt converged [2] of those, with bit errors [3] iterations of these attempts
+// (a failed one counts max_iterations).  counters[6] as in count_errors_kernel, for the frames whose final attempt this
+// is -- the ones that converged, or all of them when `last` -- with the iterations of all their attempts: spent_in (or
+// nothing before the first attempt) plus this one's.  One wavefront per frame, the frames as in harq_collect_kernel.
+__global__ __launch_bounds__(256) void harq_count_kernel(const uint8_t *__restrict__ decoded, const int32_t *__restrict__ iterations,
+                                                         const uint8_t *__restrict__ messages, uint32_t k, uint32_t pool, uint64_t seed,
+                                                         uint64_t first_frame, const uint64_t *__restrict__ frame_ids,
+                                                         const uint32_t *__restrict__ spent_in, uint32_t frames, uint32_t max_iterations,
+                                                         int last, unsigned long long *__restrict__ counters,
+                                                         unsigned long long *__restrict__ per_tx) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t f = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (f >= frames) return;
+  const uint8_t *msg = messages + size_t(pool_index(seed, frame_ids ? frame_ids[f] : first_frame + f, pool)) * k;
+  const uint8_t *dec = decoded + size_t(f) * k;
+  uint32_t errs = 0;
+  for (uint32_t i = lane; i < k; i += 64) errs += (dec[i] != msg[i]) ? 1u : 0u;
+  for (int off = 32; off > 0; off >>= 1) errs += __shfl_down(errs, off, 64);
+  if (lane == 0) {
+    const int32_t it = iterations[f];
+    const bool success = it >= 0;
+    const uint32_t its = success ? static_cast<uint32_t>(it) : max_iterations;
+    atomicAdd(&per_tx[0], 1ull);
+    atomicAdd(&per_tx[3], static_cast<unsigned long long>(its));
+    if (success) {
+      atomicAdd(&per_tx[1], 1ull);
+      if (errs) atomicAdd(&per_tx[2], 1ull);
+    }
+    if (success || last) {
+      const unsigned long long all = static_cast<unsigned long long>(spent_in ? spent_in[f] : 0u) + its;
+      atomicAdd(&counters[0], 1ull);
+      if (errs) {
+        atomicAdd(&counters[1], static_cast<unsigned long long>(errs));
+        atomicAdd(&counters[2], 1ull);
+        if (success) atomicAdd(&counters[3], 1ull);
+      } else {
+        atomicAdd(&counters[5], all);
+      }
+      atomicAdd(&counters[4], all);
+    }
+  }
+}
 #endif
 
 }  // namespace gen

@@ -267,5 +267,35 @@ __global__ __launch_bounds__(kThreads) void qam_llr_kernel(const uint8_t *__rest
   for (int j = 0; j < 2 * H; j++) row[j] = static_cast<float>(llr[j]);
 }
 
+// One transmission of a HARQ sequence (nr_harq.h): qam_llr_kernel for a list of frames at a pair offset.  tx_bits
+// [pool][e]: this transmission's pooled transmitted rows; row r of llrs [frames][e] is frame frame_ids[r], or
+// first_frame + r without a list; symbol s of the row takes the normal pair first_symbol + s, the pair of that symbol in
+// the frame's concatenated row.  The arithmetic is qam_llr_kernel's.
+template <int H, bool MAXLOG>
+__global__ __launch_bounds__(kThreads) void qam_llr_harq_kernel(const uint8_t *__restrict__ tx_bits, uint32_t pool, uint32_t e,
+                                                                uint32_t first_symbol, uint64_t seed, uint64_t first_frame,
+                                                                const uint64_t *__restrict__ frame_ids, uint64_t total, double sigma,
+                                                                double scale, double a, const Axis<double> t, float *__restrict__ llrs) {
+  const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (id >= total) return;
+  const uint32_t symbols = e / (2 * H);
+  const uint64_t f = id / symbols;
+  const uint32_t sym = static_cast<uint32_t>(id - f * symbols);
+  const uint64_t frame = frame_ids ? frame_ids[f] : first_frame + f;
+  const uint8_t *b = tx_bits + size_t(gen::pool_index(seed, frame, pool)) * e + size_t(2 * H) * sym;
+  uint32_t sym_bits = 0;
+#pragma unroll
+  for (int j = 0; j < 2 * H; j++) sym_bits |= (b[j] == 1 ? 1u : 0u) << j;
+  float z0, z1;
+  gen::normal_pair(seed, frame, first_symbol + sym, &z0, &z1);
+  const double re = static_cast<double>(axis_level<H>(sym_bits, 0)) * a + sigma * static_cast<double>(z0);
+  const double im = static_cast<double>(axis_level<H>(sym_bits, 1)) * a + sigma * static_cast<double>(z1);
+  double llr[2 * H];
+  axis_llrs<H, double, MAXLOG>(re * scale, im * scale, t, llr);
+  float *row = llrs + f * e + size_t(2 * H) * sym;
+#pragma unroll
+  for (int j = 0; j < 2 * H; j++) row[j] = static_cast<float>(llr[j]);
+}
+
 }  // namespace nrqam
 }  // namespace ldpc

@@ -17,6 +17,7 @@
 #include "device_nr_rm.h"
 #include "hip_owned.h"
 #include "encoder.h"
+#include "nr_harq.h"
 
 namespace ldpc {
 
@@ -71,6 +72,14 @@ class Simulator {
   // are what it gives for those rows, and the decoder sees them recovered (combine = 0) to [frames][n].
   bool set_rate_match(const nrrm::Config *c, uint64_t e, uint32_t rv, uint32_t qm);
   bool has_rate_match() const { return rate_match_; }
+  // A HARQ sequence (nr_harq.h): `transmissions` transmissions (e[t], rv[t]) of one qm.  It puts the simulator into the
+  // state of set_rate_match(c, e[0], rv[0], qm) -- run, run_bch, generate and the pool are those of that call -- and keeps
+  // the further transmissions for run_harq and generate_harq.  nullptr: set_rate_match(nullptr).  Every set_rate_match
+  // call clears the further transmissions.  false with nothing changed when set_rate_match would refuse the first
+  // transmission, when the sequence is none (nrharq::sequence_error), when the interleaving is not 0, or while 8PSK or a
+  // table constellation is in force: the sequence's generators are the BPSK one and the NR modulation's.
+  bool set_harq(const nrrm::Config *c, const uint64_t *e, const uint32_t *rv, uint32_t transmissions, uint32_t qm);
+  const nrharq::Sequence &harq() const { return harq_; }
   DeviceDecoder *decoder() { return dec_.get(); }
   // straggler pooling (run_bch): 0 = every chunk runs the full iteration budget
   void set_pooling(bool on) {
@@ -102,6 +111,24 @@ class Simulator {
   // The same frames' LLRs (host [frames][n_tx]) and pooled-codeword indices, for tests.
   int generate(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, float *llrs,
                uint32_t *pool_index);
+  // The frames through the HARQ sequence of set_harq (nr_harq.h), all on the device.  Every frame is decoded after each of
+  // its transmissions with the full max_iterations (the straggler budget has no part here), on the soft buffer recovered
+  // from all of them so far, and stops at the first attempt that converges -- right or wrong -- or after the last one.
+  // The noise sigma is that of n_tx = E_0 for every transmission.  counters[6]: the fields of run() for each frame's
+  // final attempt, the iterations summed over all its attempts (a failed one counts max_iterations).
+  // per_tx[T][4], per transmission: attempts, frames that stopped because the attempt converged, of those with bit
+  // errors, iterations of these attempts.  A frame's result depends on (seed, frame, configuration) alone.
+  // "pooling" 1: the frames that go on wait in their next stage's pool and are decoded thousands at a time
+  // (pooled_frames: the retransmission attempts); 0: every chunk's failures run through all stages before the next chunk.
+  // -4 and zeroed counters without a sequence, with a BCH code set, or when the modulation no longer fits the sequence.
+  int run_harq(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations, uint64_t counters[6],
+               uint64_t *per_tx);
+  // LLRs (host [frames][E_t]) of transmission t of the same frames, and their pooled-codeword indices, for tests.
+  int generate_harq(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t transmission, float *llrs,
+                    uint32_t *pool_index);
+  // rows per flush of stage t of the last run_harq call (a benchmark's figure)
+  uint64_t harq_flushes(uint32_t t) const { return t < nrharq::kMaxTransmissions ? harq_flushes_[t] : 0; }
+  uint64_t harq_flushed_rows(uint32_t t) const { return t < nrharq::kMaxTransmissions ? harq_flushed_rows_[t] : 0; }
 
  private:
   Simulator() = default;
@@ -153,6 +180,28 @@ class Simulator {
   std::vector<uint8_t> codewords_;
   int count_bch(const uint8_t *bits, const int32_t *its, uint64_t seed, uint64_t first_frame, uint32_t frames,
                 uint32_t max_iterations, const uint64_t *frame_ids, int skip_failed);
+  const char *rate_match_error(const nrrm::Config &c, uint64_t e, uint32_t rv, uint32_t qm) const;
+  // the sequence of set_harq (t = 0: none), its configuration and plans, and every transmission's pooled transmitted rows
+  // [pool][E_t], one after the other in d_harq_tx_ (transmission t at harq_.offset[t] * pool)
+  nrharq::Sequence harq_;
+  nrrm::Config harq_config_;
+  nrrm::Plan harq_plans_[nrharq::kMaxTransmissions] = {};
+  DeviceBuffer d_harq_tx_;
+  // Stage pools: stage t = 1 .. T-1 holds the frames that wait for transmission t -- soft rows [capacity][n], frame
+  // numbers and the iterations spent so far -- and the flush's own buffers are shared: the generated rows
+  // [capacity][max E_t], decoded bits and iteration counts.  counts: one fill count per stage; per_tx: [T][4].
+  struct HarqStage {
+    DeviceBuffer soft, frames, spent;
+  };
+  HarqStage harq_stage_[nrharq::kMaxTransmissions];
+  DeviceBuffer d_harq_rx_, d_harq_bits_, d_harq_its_, d_harq_counts_, d_harq_per_tx_;
+  size_t harq_cap_ = 0;
+  uint64_t harq_flushes_[nrharq::kMaxTransmissions] = {}, harq_flushed_rows_[nrharq::kMaxTransmissions] = {};
+  const char *harq_modulation_error() const;
+  int ensure_harq(size_t capacity);
+  void launch_harq_generator(double ebn0_db, uint64_t seed, uint32_t t, uint64_t first_frame, const uint64_t *frame_ids, uint32_t frames,
+                             float *dst);
+  int flush_harq(uint32_t t, uint32_t count, double ebn0_db, uint64_t seed, uint32_t max_iterations, size_t chunk);
   std::string error_;
 };
 

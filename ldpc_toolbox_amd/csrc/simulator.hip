@@ -213,23 +213,29 @@ bool Simulator::set_bch(const bch::Code *c) {
   return true;
 }
 
+// nullptr, or why set_rate_match refuses transmission (e, rv, qm) of configuration c
+const char *Simulator::rate_match_error(const nrrm::Config &c, uint64_t e, uint32_t rv, uint32_t qm) const {
+  if (punctured_) return "rate matching needs a simulator built with puncturing \"\"";
+  if (c.n != n_) return "the rate matcher's n is not the LDPC code's n";
+  if (c.fillers != 0) return "the simulator takes no filler bits: its pooled messages are random in all k positions";
+  if (const char *why = nrrm::transmission_error(e, rv, qm)) return why;
+  if (e % static_cast<uint64_t>(modulation()) != 0) return "E must be a multiple of the modulation's bits per symbol";
+  const uint64_t il = interleaving_ < 0 ? uint64_t(-interleaving_) : uint64_t(interleaving_);
+  if (il != 0 && e % il != 0) return "E must be a multiple of the interleaver columns";
+  return nullptr;
+}
+
 bool Simulator::set_rate_match(const nrrm::Config *c, uint64_t e, uint32_t rv, uint32_t qm) {
   auto refuse = [&](const char *why) {
     fail(why);
     return false;
   };
-  if (c == nullptr && !rate_match_) return true;
+  if (c == nullptr && !rate_match_) return true;  // (no rate matcher: no HARQ sequence either)
   const std::vector<uint8_t> &cws = rate_match_ ? codewords_ : tx_bits_;
   std::vector<uint8_t> tx;
   nrrm::Plan plan{};
   if (c != nullptr) {
-    if (punctured_) return refuse("rate matching needs a simulator built with puncturing \"\"");
-    if (c->n != n_) return refuse("the rate matcher's n is not the LDPC code's n");
-    if (c->fillers != 0) return refuse("the simulator takes no filler bits: its pooled messages are random in all k positions");
-    if (const char *why = nrrm::transmission_error(e, rv, qm)) return refuse(why);
-    if (e % static_cast<uint64_t>(modulation()) != 0) return refuse("E must be a multiple of the modulation's bits per symbol");
-    const uint64_t il = interleaving_ < 0 ? uint64_t(-interleaving_) : uint64_t(interleaving_);
-    if (il != 0 && e % il != 0) return refuse("E must be a multiple of the interleaver columns");
+    if (const char *why = rate_match_error(*c, e, rv, qm)) return refuse(why);
     plan = nrrm::make_plan(*c, static_cast<uint32_t>(e), rv, qm);
     // the pool's transmitted rows: the rate-matched pooled codewords
     tx.resize(size_t(pool_) * e);
@@ -253,7 +259,52 @@ bool Simulator::set_rate_match(const nrrm::Config *c, uint64_t e, uint32_t rv, u
     codewords_.clear();
     d_rx_ = DeviceBuffer();
   }
+  // (a HARQ sequence belongs to the set_harq call that made it: any other rate matcher ends it)
+  harq_ = nrharq::Sequence();
+  d_harq_tx_ = DeviceBuffer();
   budget_valid_ = false;  // (as in set_modulation)
+  return true;
+}
+
+// the sequence's generators are the BPSK one and the NR modulation's, both without an interleaver
+const char *Simulator::harq_modulation_error() const {
+  if (use_constellation_ && !constellation_.bpsk) return "HARQ takes BPSK or an NR modulation (set_nr_qam), not a table constellation";
+  if (!use_constellation_ && !use_nr_qam_ && bits_per_symbol_ != 1) return "HARQ takes BPSK or an NR modulation (set_nr_qam), not 8PSK";
+  if (interleaving_ != 0) return "HARQ takes no interleaving (NR's bit interleaver is the rate matcher's)";
+  return nullptr;
+}
+
+bool Simulator::set_harq(const nrrm::Config *c, const uint64_t *e, const uint32_t *rv, uint32_t transmissions, uint32_t qm) {
+  auto refuse = [&](const char *why) {
+    fail(why);
+    return false;
+  };
+  if (c == nullptr) return set_rate_match(nullptr, 0, 0, 1);
+  if (const char *why = harq_modulation_error()) return refuse(why);
+  if (const char *why = nrharq::sequence_error(e, rv, transmissions, qm, static_cast<uint32_t>(modulation()))) return refuse(why);
+  if (const char *why = rate_match_error(*c, e[0], rv[0], qm)) return refuse(why);
+  // every transmission's pooled rows, from the pooled codewords: made and uploaded before anything changes
+  const nrharq::Sequence seq = nrharq::make_sequence(e, rv, transmissions, qm);
+  const std::vector<uint8_t> &cws = rate_match_ ? codewords_ : tx_bits_;
+  std::vector<uint8_t> tx(size_t(pool_) * seq.offset[seq.t]);
+  nrrm::Plan plans[nrharq::kMaxTransmissions] = {};
+  for (uint32_t t = 0; t < seq.t; t++) {
+    plans[t] = nrharq::plan_of(*c, seq, t);
+    uint8_t *rows = &tx[size_t(pool_) * seq.offset[t]];
+    for (uint32_t p = 0; p < pool_; p++)
+      for (uint32_t pos = 0; pos < seq.e[t]; pos++)
+        rows[size_t(p) * seq.e[t] + pos] = cws[size_t(p) * n_ + nrrm::column_of_position(plans[t], pos)];
+  }
+  if (hipSetDevice(device_) != hipSuccess || hipStreamSynchronize(stream_) != hipSuccess) return refuse("the simulator's stream failed");
+  DeviceBuffer d_tx;
+  if (d_tx.ensure(tx.size()) != hipSuccess || hipMemcpy(d_tx.get(), tx.data(), tx.size(), hipMemcpyHostToDevice) != hipSuccess)
+    return refuse("device allocation for the HARQ sequence's pooled rows failed");
+  if (!set_rate_match(c, e[0], rv[0], qm)) return false;  // (it clears the sequence; what it refuses has been asked above)
+  harq_ = seq;
+  harq_config_ = *c;
+  for (uint32_t t = 0; t < seq.t; t++) harq_plans_[t] = plans[t];
+  d_harq_tx_ = std::move(d_tx);
+  harq_cap_ = 0;  // (the stage pools are sized for a sequence: run_harq makes them anew)
   return true;
 }
 
@@ -525,6 +576,206 @@ int Simulator::generate(double ebn0_db, uint64_t seed, uint64_t first_frame, siz
     launch_generator(ebn0_db, seed, first_frame, static_cast<uint32_t>(frames));
     SIM_TRY(hipMemcpyAsync(llrs, rate_match_ ? d_rx_.get() : d_llrs_.get(), frames * n_tx_ * sizeof(float), hipMemcpyDefault, stream_));
   }
+  SIM_TRY(hipStreamSynchronize(stream_));
+  SIM_TRY(hipGetLastError());
+  if (pool_index)
+    for (size_t f = 0; f < frames; f++) pool_index[f] = gen::pool_index(seed, first_frame + f, pool_);
+  return 0;
+}
+
+// ---- HARQ (nr_harq.h) ------------------------------------------------------------------------------------------------
+
+// transmission t of `frames` frames -- frame_ids (device), or first_frame on -- into dst [frames][E_t], transmitted order
+void Simulator::launch_harq_generator(double ebn0_db, uint64_t seed, uint32_t t, uint64_t first_frame, const uint64_t *frame_ids,
+                                      uint32_t frames, float *dst) {
+  const uint32_t e = harq_.e[t];
+  const uint8_t *tx = d_harq_tx_.get<uint8_t>() + size_t(pool_) * harq_.offset[t];
+  if (use_nr_qam_) {
+    nr_qam_launch_harq_generator(nr_qam_, max_log_, tx, pool_, e, nrharq::first_symbol(harq_, t, nr_qam_.qm), seed, first_frame, frame_ids,
+                                 frames, noise_sigma(ebn0_db), dst, stream_);
+    return;
+  }
+  float sigma, scale;
+  noise_params(ebn0_db, &sigma, &scale);
+  const uint32_t pairs = nrharq::pairs(harq_, t);
+  const uint64_t threads = uint64_t(frames) * pairs;
+  gen::awgn_llr_harq_kernel<<<static_cast<uint32_t>((threads + 255) / 256), 256, 0, stream_>>>(tx, pool_, e, harq_.offset[t], pairs, seed,
+                                                                                              first_frame, frame_ids, frames, sigma, scale, dst);
+}
+
+int Simulator::ensure_harq(size_t capacity) {
+  const uint32_t T = harq_.t;
+  uint32_t max_e = 1;
+  for (uint32_t t = 1; t < T; t++) max_e = std::max(max_e, harq_.e[t]);
+  SIM_TRY(d_harq_counts_.ensure(nrharq::kMaxTransmissions * sizeof(uint32_t)));
+  SIM_TRY(d_harq_per_tx_.ensure(nrharq::kMaxTransmissions * 4 * sizeof(unsigned long long)));
+  harq_cap_ = 0;
+  for (uint32_t t = 1; t < T; t++) {
+    SIM_TRY(harq_stage_[t].soft.ensure(capacity * n_ * sizeof(float)));
+    SIM_TRY(harq_stage_[t].frames.ensure(capacity * sizeof(uint64_t)));
+    SIM_TRY(harq_stage_[t].spent.ensure(capacity * sizeof(uint32_t)));
+  }
+  if (T > 1) {
+    SIM_TRY(d_harq_rx_.ensure(capacity * max_e * sizeof(float)));
+    SIM_TRY(d_harq_bits_.ensure(capacity * std::max<size_t>(k_, 1)));
+    SIM_TRY(d_harq_its_.ensure(capacity * sizeof(int32_t)));
+  }
+  harq_cap_ = capacity;
+  return 0;
+}
+
+// Stage t's pool: transmission t of its `count` frames, combined into their soft rows in place, decoded with the full
+// budget, counted, and the ones that still fail appended to stage t + 1.  Stage t's count returns to zero.
+// The decode calls are the chunks' own: `chunk` rows each, the rows behind the last pooled one set to the LLRs of the
+// all-zero codeword, which converge at once.  A call of another size makes the decoder lay out its workspace anew --
+// gigabytes freed and allocated before and after every flush, which on a busy device takes longer than the flush.
+int Simulator::flush_harq(uint32_t t, uint32_t count, double ebn0_db, uint64_t seed, uint32_t max_iterations, size_t chunk) {
+  HarqStage &st = harq_stage_[t];
+  const bool last = t + 1 == harq_.t;
+  uint32_t *counts = d_harq_counts_.get<uint32_t>();
+  launch_harq_generator(ebn0_db, seed, t, 0, st.frames.get<uint64_t>(), count, d_harq_rx_.get<float>());
+  nr_rm_launch_recover<float>(harq_plans_[t], d_harq_rx_.get<float>(), st.soft.get<float>(), count, 0.0f, true, stream_);
+  const size_t padded = (count + chunk - 1) / chunk * chunk;  // (at most the two chunks every pool has room for)
+  if (padded > count)
+    SIM_TRY(hipMemsetAsync(st.soft.get<float>() + size_t(count) * n_, 0x41 /* every float 0x41414141 = +12.08 */,
+                           (padded - count) * n_ * sizeof(float), stream_));
+  for (size_t p0 = 0; p0 < padded; p0 += chunk)
+    if (int rc = dec_->decode_device(st.soft.get<float>() + p0 * n_, false, chunk, max_iterations, d_harq_bits_.get<uint8_t>() + p0 * k_, k_,
+                                     d_harq_its_.get<int32_t>() + p0, nullptr, stream_)) {
+      error_ = dec_->last_error();
+      return rc;
+    }
+  if (!last) {
+    HarqStage &next = harq_stage_[t + 1];
+    gen::harq_collect_kernel<<<(count * 64 + 255) / 256, 256, 0, stream_>>>(
+        d_harq_its_.get<int32_t>(), count, 0, st.frames.get<uint64_t>(), st.spent.get<uint32_t>(), max_iterations, st.soft.get<float>(),
+        static_cast<uint32_t>(n_), next.soft.get<float>(), next.frames.get<uint64_t>(), next.spent.get<uint32_t>(), counts + t + 1,
+        static_cast<uint32_t>(2 * chunk));
+  }
+  gen::harq_count_kernel<<<(count * 64 + 255) / 256, 256, 0, stream_>>>(
+      d_harq_bits_.get<uint8_t>(), d_harq_its_.get<int32_t>(), d_messages_.get<uint8_t>(), static_cast<uint32_t>(k_), pool_, seed, 0,
+      st.frames.get<uint64_t>(), st.spent.get<uint32_t>(), count, max_iterations, last ? 1 : 0, d_counters_.get<unsigned long long>(),
+      d_harq_per_tx_.get<unsigned long long>() + 4 * t);
+  SIM_TRY(hipMemsetAsync(counts + t, 0, sizeof(uint32_t), stream_));
+  harq_flushes_[t]++;
+  harq_flushed_rows_[t] += count;
+  pooled_frames_ += pooling_ ? count : 0;
+  return 0;
+}
+
+int Simulator::run_harq(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations, uint64_t counters[6],
+                        uint64_t *per_tx) {
+  const uint32_t T = harq_.t;
+  for (int i = 0; i < 6; i++) counters[i] = 0;
+  for (uint32_t i = 0; i < 4 * T; i++) per_tx[i] = 0;
+  auto refuse = [&](const char *why) {
+    fail(why);
+    return -4;
+  };
+  if (T == 0) return refuse("no HARQ sequence is set (ldpc_toolbox_sim_set_harq)");
+  if (bch_) return refuse("a HARQ run takes no outer BCH code: clear it first");
+  // (the modulation may have changed since set_harq)
+  if (const char *why = harq_modulation_error()) return refuse(why);
+  for (uint32_t t = 0; t < T; t++)
+    if (harq_.e[t] % static_cast<uint32_t>(modulation()) != 0) return refuse("every E must be a multiple of the modulation's bits per symbol");
+  pooled_frames_ = 0;
+  for (uint32_t t = 0; t < nrharq::kMaxTransmissions; t++) harq_flushes_[t] = harq_flushed_rows_[t] = 0;
+  if (frames == 0) return 0;
+  SIM_TRY(hipSetDevice(device_));
+  const size_t chunk = std::min<size_t>(frames, std::max<size_t>(dec_->preferred_group(frames), 4096));  // (as in run_frames)
+  if (int rc = ensure(chunk, chunk)) return rc;
+  if (harq_cap_ < 2 * chunk)
+    if (int rc = ensure_harq(2 * chunk)) return rc;
+  const size_t cap = 2 * chunk;  // (of this call: an earlier one with larger chunks may have left larger buffers)
+  unsigned long long *d_counters = d_counters_.get<unsigned long long>(), *d_per_tx = d_harq_per_tx_.get<unsigned long long>();
+  uint32_t *d_counts = d_harq_counts_.get<uint32_t>();
+  SIM_TRY(hipMemsetAsync(d_counters, 0, 9 * sizeof(unsigned long long), stream_));
+  SIM_TRY(hipMemsetAsync(d_per_tx, 0, nrharq::kMaxTransmissions * 4 * sizeof(unsigned long long), stream_));
+  SIM_TRY(hipMemsetAsync(d_counts, 0, nrharq::kMaxTransmissions * sizeof(uint32_t), stream_));
+  // what every stage holds, read back (the stream is idle afterwards)
+  uint32_t held[nrharq::kMaxTransmissions] = {};
+  auto read_held = [&]() -> int {
+    SIM_TRY(hipMemcpyAsync(held, d_counts, sizeof(held), hipMemcpyDeviceToHost, stream_));
+    SIM_TRY(hipStreamSynchronize(stream_));
+    for (uint32_t s = 1; s < T; s++)
+      if (held[s] > cap) {
+        fail("HARQ stage pool overflow");
+        return -3;
+      }
+    return 0;
+  };
+  // Stage t flushed.  It may pass on every row it holds, so the stage behind it is flushed first when that many might
+  // not fit there, and so on down the stages: the deepest of them first, each into the room just made.
+  auto drain = [&](uint32_t t) -> int {
+    uint32_t deepest = t;
+    while (deepest + 1 < T && size_t(held[deepest + 1]) + held[deepest] > cap) deepest++;
+    for (uint32_t s = deepest;; s--) {
+      if (held[s])
+        if (int rc = flush_harq(s, held[s], ebn0_db, seed, max_iterations, chunk)) return rc;
+      if (int rc = read_held()) return rc;
+      if (s == t) return 0;
+    }
+  };
+  // between chunks with pooling: stage 1 alone is filled by a chunk, and is flushed when another chunk's failures might
+  // not fit; else, and at the end of the call: every stage in order
+  auto flush_stages = [&](bool all) -> int {
+    if (int rc = read_held()) return rc;
+    if (!all) return held[1] + chunk > cap ? drain(1) : 0;
+    for (uint32_t t = 1; t < T; t++)
+      if (held[t])
+        if (int rc = drain(t)) return rc;
+    return 0;
+  };
+  for (size_t f0 = 0; f0 < frames; f0 += chunk) {
+    const uint32_t nf = static_cast<uint32_t>(std::min(chunk, frames - f0));
+    // stage 0: the first transmission is the frame of run() -- its generator, recovered with combine = 0
+    launch_generator(ebn0_db, seed, first_frame + f0, nf);
+    nr_rm_launch_recover<float>(rm_plan_, d_rx_.get<float>(), d_llrs_.get<float>(), nf, 0.0f, false, stream_);
+    if (int rc = dec_->decode_device(d_llrs_.get(), false, nf, max_iterations, d_bits_.get<uint8_t>(), k_, d_its_.get<int32_t>(), nullptr, stream_)) {
+      error_ = dec_->last_error();
+      return rc;
+    }
+    if (T > 1)
+      gen::harq_collect_kernel<<<(nf * 64 + 255) / 256, 256, 0, stream_>>>(
+          d_its_.get<int32_t>(), nf, first_frame + f0, nullptr, nullptr, max_iterations, d_llrs_.get<float>(), static_cast<uint32_t>(n_),
+          harq_stage_[1].soft.get<float>(), harq_stage_[1].frames.get<uint64_t>(), harq_stage_[1].spent.get<uint32_t>(), d_counts + 1,
+          static_cast<uint32_t>(cap));
+    gen::harq_count_kernel<<<(nf * 64 + 255) / 256, 256, 0, stream_>>>(d_bits_.get<uint8_t>(), d_its_.get<int32_t>(), d_messages_.get<uint8_t>(),
+                                                                       static_cast<uint32_t>(k_), pool_, seed, first_frame + f0, nullptr, nullptr,
+                                                                       nf, max_iterations, T == 1 ? 1 : 0, d_counters, d_per_tx);
+    if (T > 1 && f0 + chunk < frames)
+      if (int rc = flush_stages(!pooling_)) return rc;
+  }
+  if (T > 1)
+    if (int rc = flush_stages(true)) return rc;
+  unsigned long long host[6], host_tx[nrharq::kMaxTransmissions * 4];
+  SIM_TRY(hipMemcpyAsync(host, d_counters, sizeof(host), hipMemcpyDeviceToHost, stream_));
+  SIM_TRY(hipMemcpyAsync(host_tx, d_per_tx, sizeof(host_tx), hipMemcpyDeviceToHost, stream_));
+  SIM_TRY(hipStreamSynchronize(stream_));
+  SIM_TRY(hipGetLastError());
+  for (int i = 0; i < 6; i++) counters[i] = host[i];
+  for (uint32_t i = 0; i < 4 * T; i++) per_tx[i] = host_tx[i];
+  return 0;
+}
+
+int Simulator::generate_harq(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t transmission, float *llrs,
+                             uint32_t *pool_index) {
+  auto refuse = [&](const char *why) {
+    fail(why);
+    return -4;
+  };
+  if (harq_.t == 0) return refuse("no HARQ sequence is set (ldpc_toolbox_sim_set_harq)");
+  if (transmission >= harq_.t) return refuse("the HARQ sequence has no such transmission");
+  if (const char *why = harq_modulation_error()) return refuse(why);
+  for (uint32_t t = 0; t < harq_.t; t++)
+    if (harq_.e[t] % static_cast<uint32_t>(modulation()) != 0) return refuse("every E must be a multiple of the modulation's bits per symbol");
+  if (frames == 0) return 0;
+  SIM_TRY(hipSetDevice(device_));
+  const size_t bytes = frames * harq_.e[transmission] * sizeof(float);
+  DeviceBuffer d_out;
+  SIM_TRY(d_out.ensure(bytes));
+  launch_harq_generator(ebn0_db, seed, transmission, first_frame, nullptr, static_cast<uint32_t>(frames), d_out.get<float>());
+  SIM_TRY(hipMemcpyAsync(llrs, d_out.get(), bytes, hipMemcpyDeviceToHost, stream_));
   SIM_TRY(hipStreamSynchronize(stream_));
   SIM_TRY(hipGetLastError());
   if (pool_index)

@@ -396,6 +396,54 @@ class Simulator:
         self.n_tx = self.get("n_tx")
         self.rate = self.k / self.n_tx
 
+    def set_harq(self, rm, transmissions=(), qm: int = 1):
+        """`rm`: an `NrRateMatcher` as for `set_rate_match`; `transmissions`: 1 to 8 pairs (e, rv), the HARQ sequence of
+        `run_harq` and `generate_harq`.  The simulator is then in the state of set_rate_match(rm, e_0, rv_0, qm): `run`,
+        `generate` and `pool_data` are those of that call.  None, like every `set_rate_match` call, clears the sequence.
+        ValueError (nothing changed) when the simulator refuses it."""
+        seq = [(int(e), int(rv)) for e, rv in transmissions]
+        e = np.array([x[0] for x in seq], dtype=np.uint64)
+        rv = np.array([x[1] for x in seq], dtype=np.uint32)
+        h = None if rm is None else rm._h
+        if _capi.lib().ldpc_toolbox_sim_set_harq(self._h, h, e.ctypes.data, rv.ctypes.data, len(seq), int(qm)) != 0:
+            raise ValueError(_capi.last_error() or "cannot set the HARQ sequence")
+        self.n_tx = self.get("n_tx")
+        self.rate = self.k / self.n_tx
+
+    def harq(self):
+        """the sequence in force: a list of (e, rv), empty without one"""
+        return [(self.get(f"harq_e{t}"), self.get(f"harq_rv{t}")) for t in range(self.get("harq"))]
+
+    def run_harq(self, ebn0_db, seed, first_frame, frames, max_iterations):
+        """-> (int64[6], int64[T, 4]): the counters of `run` for every frame's final attempt (iterations summed over its
+        attempts), and per transmission: attempts, frames that stopped because the attempt converged, of those with bit
+        errors, iterations of these attempts (include/ldpc_toolbox.h, ldpc_toolbox_sim_run_harq)"""
+        T = self.get("harq")
+        out = np.zeros(6, dtype=np.uint64)
+        per_tx = np.zeros((max(T, 1), 4), dtype=np.uint64)
+        rc = _capi.lib().ldpc_toolbox_sim_run_harq(self._h, float(ebn0_db), int(seed), int(first_frame), int(frames),
+                                                   int(max_iterations), out.ctypes.data, per_tx.ctypes.data)
+        if rc == -4:
+            raise ValueError(f"sim_run_harq refused ({rc}): {_capi.last_error()}")
+        if rc != 0:
+            raise RuntimeError(f"sim_run_harq failed ({rc}): {_capi.last_error()}")
+        return out.astype(np.int64), per_tx[:T].astype(np.int64)
+
+    def generate_harq(self, ebn0_db, seed, first_frame, frames, t):
+        """-> (float32 [frames][E_t], pool index per frame): transmission t of the frames"""
+        T = self.get("harq")
+        if not 0 <= int(t) < T:
+            raise ValueError(f"the HARQ sequence has {T} transmissions: no transmission {t}")
+        llrs = np.zeros((frames, self.get(f"harq_e{int(t)}")), dtype=np.float32)
+        idx = np.zeros(frames, dtype=np.uint32)
+        rc = _capi.lib().ldpc_toolbox_sim_generate_harq(self._h, float(ebn0_db), int(seed), int(first_frame), int(frames), int(t),
+                                                        llrs.ctypes.data, idx.ctypes.data)
+        if rc == -4:
+            raise ValueError(f"sim_generate_harq refused ({rc}): {_capi.last_error()}")
+        if rc != 0:
+            raise RuntimeError(f"sim_generate_harq failed ({rc}): {_capi.last_error()}")
+        return llrs, idx
+
     def get(self, key):
         v = C.c_int64(0)
         if _capi.lib().ldpc_toolbox_sim_get(self._h, key.encode(), C.byref(v)) != 0:
