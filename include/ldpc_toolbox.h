@@ -751,6 +751,69 @@ int32_t ldpc_toolbox_nr_qam_demod_f64_device(void *qam, double *llrs, size_t llr
  * computes it, one thread per symbol; the symbols are never stored. */
 int32_t ldpc_toolbox_sim_set_nr_qam(void *sim, void *qam, int32_t max_log);
 
+/* ===================================================================================
+ * PART 9 -- the 8-bit soft-bit receive path: NR demapper -> rate recovery / HARQ combining -> decoder input, one byte per
+ * soft bit throughout.  It ends in one of the 50 8-bit implementations (Minstarapproxi8*, Aminstari8*, Minsumi8*, either
+ * schedule), whose quantiser it shares.  The reference has none of it.
+ *   Unit.  One step is 1/8 of an LLR unit.  A soft bit is an int8_t in -127..127; a positive value means bit 0.
+ *   clip(v) = min(max(v, -127), 127), symmetric: an input byte of -128 is read as -127 everywhere.  (Inside the decoders
+ *     sums saturate to -128..127; the soft-bit path stays symmetric because the decoders are symmetric in the transmitted
+ *     codeword.)
+ *   Q(x) = the quantiser of the 8-bit decoders: clamp(round-half-away(8 x)) to +-127, NaN -> 0.
+ * Each entry has a host form and a _device form with a trailing hipStream_t; streams and synchronisation are those of the
+ * neighbouring _f32 entries.
+ * =================================================================================== */
+
+/* Batch decode of 8-bit soft bits: llrs [batch][llrs_len] int8_t.  Only a decoder whose implementation is one of the 8-bit
+ * names takes it, with or without a puncturing pattern; any other returns LDPC_TOOLBOX_ERR_UNSUPPORTED before the GPU is
+ * touched and writes nothing.  The other argument checks and error codes are those of the _f32 entry.
+ * RESULT: `output` and `iterations` are exactly those of ldpc_toolbox_decoder_decode_batch_f32 / _f32_device on the rows
+ * (float)clip(v) / 8.0f -- Q of that value is clip(v) for all 256 bytes.  posterior [batch][n] (may be NULL) is int16_t: the
+ * integer that the _f32 entry converts to float.  The call takes the path the _f32 entry would take for that batch, stream
+ * and option set -- groups, two lanes, the straggler pool ("pooling"), the single-launch path of small synchronised calls
+ * -- with the rows moved as bytes: no float row exists anywhere, and the ingest reads a quarter of the _f32 entry's bytes.
+ * A device `llrs` may be any byte address and `posterior` any int16_t address. */
+int32_t ldpc_toolbox_decoder_decode_batch_i8(void *decoder, uint8_t *output, size_t output_len, const int8_t *llrs, size_t llrs_len,
+                                             size_t batch, uint32_t max_iterations, int32_t *iterations, int16_t *posterior);
+int32_t ldpc_toolbox_decoder_decode_batch_i8_device(void *decoder, uint8_t *output, size_t output_len, const int8_t *llrs,
+                                                    size_t llrs_len, size_t batch, uint32_t max_iterations, int32_t *iterations,
+                                                    int16_t *posterior, void *hip_stream);
+
+/* The NR demapper of PART 8 (qam: a handle of ldpc_toolbox_nr_qam_ctor) with 8-bit output: llrs[i] = Q(the float that
+ * ldpc_toolbox_nr_qam_demod_f32 writes at i with the same arguments, descrambling included).  One kernel, one byte out per
+ * LLR; the float row is never stored.  Float symbols only.  The refusals are those of the _f32 entry, except that a device
+ * `llrs` buffer needs no alignment: any byte address is valid (the QM bytes of a symbol leave as 4- or 2-byte pieces where
+ * the buffer's address allows, as single bytes otherwise).  A device symbol buffer is aligned to one (re, im) pair. */
+int32_t ldpc_toolbox_nr_demap_i8(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, size_t symbols_len, size_t batch,
+                                 double noise_sigma, int32_t max_log, int64_t c_init);
+int32_t ldpc_toolbox_nr_demap_i8_device(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, size_t symbols_len, size_t batch,
+                                        double noise_sigma, int32_t max_log, int64_t c_init, void *hip_stream);
+
+/* Rate recovery and HARQ combining of PART 6 (rm: a handle of ldpc_toolbox_nr_rm_ctor) on 8-bit soft bits, with the p_i /
+ * t_i notation of ldpc_toolbox_nr_rm_recover_f32.  Per frame and column c:
+ *   t_i = clip(the received byte at the interleaved position of p_i);
+ *   S = t_0, then S = clip(S + t_i) for i = 1 .. R-1 in ascending selection index;
+ *   the output is `filler` in a filler column, whatever `combine` is; with R = 0: 0, or clip(old) when combine != 0;
+ *   otherwise S, or clip(clip(old) + S) when combine != 0.
+ * Saturating sums are not associative: the order is part of the definition, and no atomics are used.  filler outside
+ * 1..127 is LDPC_TOOLBOX_ERR_ARGUMENT; the other refusals are those of the _f32 entry.  It runs in passes and stages like
+ * the _f32 entry, with 1-byte elements ("pass_elements", "stage_bytes").  Any byte address is a valid device `llrs` / `rx`. */
+int32_t ldpc_toolbox_nr_rm_recover_i8(void *rm, int8_t *llrs, size_t n, const int8_t *rx, size_t e, size_t batch, uint32_t rv, uint32_t qm,
+                                      int32_t filler, int32_t combine);
+int32_t ldpc_toolbox_nr_rm_recover_i8_device(void *rm, int8_t *llrs, size_t n, const int8_t *rx, size_t e, size_t batch, uint32_t rv,
+                                             uint32_t qm, int32_t filler, int32_t combine, void *hip_stream);
+
+/* The simulator's soft buffers: the key "soft_bits" of ldpc_toolbox_sim_set takes 8 or 32 (default 32; ldpc_toolbox_sim_get
+ * reports it).  8 is accepted only when the simulator's implementation is one of the 8-bit names; a refusal returns -1 with
+ * a message and changes nothing.  It changes ldpc_toolbox_sim_run_harq only -- run, run_bch, generate and generate_harq stay
+ * as they are.  With 8 a frame's attempt after transmission t is defined by composition: the float row that
+ * ldpc_toolbox_sim_generate_harq returns for t, taken through Q; then the 8-bit rate recovery above into the frame's int8
+ * soft row, with combine = (t > 0) and the plan of transmission t; then the 8-bit decode entry with the full max_iterations.
+ * The stopping rule, counters[6], per_tx[T][4], their independence of chunking and of "pooling", and the harq_flushes_t /
+ * harq_rows_t keys are those of the float run.  The stage pools hold [capacity][n] bytes, a quarter of the float ones; the
+ * generators still write floats, which a pass of its own quantises into the int8 receive buffer recovery reads.  With 32
+ * every launch and result is what it was. */
+
 /* Standard-code generator (what the reference's `dvbs2` / `5g` / `ccsds` / `ccsds-c2` CLI
  * sub-commands print, src/cli/dvbs2.rs:91, src/cli/nr5g.rs:46, src/cli/ccsds.rs:70): writes the
  * padded alist text of `spec` ("dvbs2:R1_2", "nr5g:1:384", "ar4ja:1/2:1024", "c2") into

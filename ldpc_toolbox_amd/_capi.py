@@ -113,6 +113,12 @@ SYMBOLS = [
     "ldpc_toolbox_nr_qam_demod_f32_device",
     "ldpc_toolbox_nr_qam_demod_f64_device",
     "ldpc_toolbox_sim_set_nr_qam",
+    "ldpc_toolbox_decoder_decode_batch_i8",
+    "ldpc_toolbox_decoder_decode_batch_i8_device",
+    "ldpc_toolbox_nr_demap_i8",
+    "ldpc_toolbox_nr_demap_i8_device",
+    "ldpc_toolbox_nr_rm_recover_i8",
+    "ldpc_toolbox_nr_rm_recover_i8_device",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
     "ldpc_toolbox_device_count",
@@ -370,6 +376,19 @@ def lib():
         f.argtypes = [vp, vp, sz, vp, sz, sz, C.c_double, i32, C.c_int64, vp]
     L.ldpc_toolbox_sim_set_nr_qam.restype = i32
     L.ldpc_toolbox_sim_set_nr_qam.argtypes = [vp, vp, i32]
+    # the 8-bit soft-bit receive path (PART 9): the argument orders of the f32 entries; the filler is an int32_t soft bit
+    L.ldpc_toolbox_decoder_decode_batch_i8.restype = i32
+    L.ldpc_toolbox_decoder_decode_batch_i8.argtypes = [vp, vp, sz, vp, sz, sz, u32, vp, vp]
+    L.ldpc_toolbox_decoder_decode_batch_i8_device.restype = i32
+    L.ldpc_toolbox_decoder_decode_batch_i8_device.argtypes = [vp, vp, sz, vp, sz, sz, u32, vp, vp, vp]
+    L.ldpc_toolbox_nr_demap_i8.restype = i32
+    L.ldpc_toolbox_nr_demap_i8.argtypes = [vp, vp, sz, vp, sz, sz, C.c_double, i32, C.c_int64]
+    L.ldpc_toolbox_nr_demap_i8_device.restype = i32
+    L.ldpc_toolbox_nr_demap_i8_device.argtypes = [vp, vp, sz, vp, sz, sz, C.c_double, i32, C.c_int64, vp]
+    L.ldpc_toolbox_nr_rm_recover_i8.restype = i32
+    L.ldpc_toolbox_nr_rm_recover_i8.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32, i32, i32]
+    L.ldpc_toolbox_nr_rm_recover_i8_device.restype = i32
+    L.ldpc_toolbox_nr_rm_recover_i8_device.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32, i32, i32, vp]
     L.ldpc_toolbox_code_alist.restype = sz
     L.ldpc_toolbox_code_alist.argtypes = [cp, vp, sz]
     L.ldpc_toolbox_alist_normalize.restype = sz

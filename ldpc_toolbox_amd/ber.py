@@ -210,6 +210,8 @@ def format_details(a, sim, world: int) -> str:
         lines.append(f" - NR rate matching (E[:RV[:QM]]): {a.nr_rate_match}")
     if getattr(a, "nr_harq", None):                                                   # this build's addition
         lines.append(" - NR HARQ transmissions (RV:E): " + ", ".join(f"{rv}:{e}" for e, rv in sim.harq()))
+    if getattr(a, "nr_soft_bits", 32) == 8:                                           # this build's addition
+        lines.append(" - NR HARQ soft buffer: 8-bit soft bits")
     lines += [f" - Information bits (k): {sim.k}", f" - Codeword size (N_cw): {sim.n}", f" - Frame size (N): {sim.n_tx}",
               f" - Code rate: {sim.rate:.3f}", "LDPC decoder:", f" - Implementation: {a.decoder}",
               f" - Maximum iterations: {a.max_iter}"]
@@ -282,6 +284,10 @@ def main(argv=None):
                          "on the soft buffer combined so far and stops at the first attempt that converges; the table carries "
                          "the counters of the final attempts, and Eb/N0 refers to the first transmission.  BPSK or --nr-qam; "
                          "one rank; not with --codes or the --bch options")
+    ap.add_argument("--nr-soft-bits", type=int, choices=[8, 32], default=32,
+                    help="with --nr-harq and an 8-bit --decoder (a name with i8): 8 keeps the HARQ soft buffers as 8-bit soft "
+                         "bits, 1/8 of an LLR unit per step -- every transmission quantised, combined with saturation at +-127 "
+                         "and decoded from the bytes; 32 (default): float soft buffers")
     ap.add_argument("--output-file-harq", metavar="FILE",
                     help="with --nr-harq: one line per (Eb/N0, transmission t) -- rv, E, attempts, frames that stopped because "
                          "the attempt converged, of those with bit errors, iterations, the residual BLER after t, and the bits "
@@ -323,6 +329,8 @@ def main(argv=None):
             ap.error("--nr-harq takes RV[:E],RV[:E],...")
     elif a.output_file_harq:
         ap.error("--output-file-harq needs --nr-harq")
+    if a.nr_soft_bits == 8 and (not a.nr_harq or "i8" not in a.decoder):
+        ap.error("--nr-soft-bits 8 needs --nr-harq and an 8-bit decoder implementation (Minsumi8*, Minstarapproxi8*, Aminstari8*)")
 
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -389,6 +397,11 @@ def main(argv=None):
             sim.set_harq(rm, [(e0, rv0)] + [(item[1] if len(item) > 1 else e0, item[0]) for item in harq], qm)
         except ValueError as e:
             ap.error(f"--nr-harq {a.nr_harq}: {e}")
+        if a.nr_soft_bits == 8:
+            try:
+                sim.set("soft_bits", 8)
+            except ValueError as e:
+                ap.error(f"--nr-soft-bits 8: {e}")
     if rate_match:
         rm.close()
     out = open(a.output_file, "w") if (a.output_file and rank == 0) else None

@@ -25,6 +25,7 @@
 #include "encoder.h"
 #include "implementation.h"
 #include "simulator.h"
+#include "soft_i8.h"
 #include "sparse.h"
 
 namespace {
@@ -402,6 +403,25 @@ int32_t nr_qam_demod(void *qam, void *llrs, size_t llrs_len, const void *symbols
   return LDPC_TOOLBOX_ERR_DEVICE;
 }
 
+int32_t nr_demap_i8(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, size_t symbols_len, size_t batch, double sigma,
+                    int32_t max_log, int64_t c_init, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrQamHandle *>(qam);
+  if (!h) return nr_qam_refuse("null NR modulation handle");
+  if (const char *why = ldpc::nrqam::demod_argument_error(h->c, llrs_len, symbols_len, sigma, c_init)) return nr_qam_refuse(why);
+  if (batch == 0 || llrs_len == 0) return 0;
+  if (!symbols || !llrs) return nr_qam_refuse("null symbol or LLR buffer");
+  if (on_device)  // (the soft bits leave in pieces chosen from their address: no alignment asked of `llrs`)
+    if (const char *why = ldpc::nrqam::device_pointer_error(symbols, nullptr, false)) return nr_qam_refuse(why);
+  if (int32_t rc = nr_qam_device_state(h)) return rc;
+  const int rc = on_device ? h->dev->demap_i8_device(symbols, llrs, symbols_len, llrs_len, batch, sigma, max_log != 0, c_init,
+                                                     static_cast<hipStream_t>(stream))
+                           : h->dev->demap_i8_host(symbols, llrs, symbols_len, llrs_len, batch, sigma, max_log != 0, c_init);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
 int32_t bch_run(void *bch, bool decode, uint8_t *output, size_t output_len, const uint8_t *input, size_t input_len, size_t batch,
                 int32_t *errors, bool on_device, void *stream) {
   g_last_error.clear();
@@ -542,6 +562,34 @@ int32_t nr_rm_recover(void *rm, void *llrs, size_t n, const void *rx, size_t e, 
   return LDPC_TOOLBOX_ERR_DEVICE;
 }
 
+int32_t nr_rm_recover_i8(void *rm, int8_t *llrs, size_t n, const int8_t *rx, size_t e, size_t batch, uint32_t rv, uint32_t qm,
+                         int32_t filler, int32_t combine, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrRmHandle *>(rm);
+  if (!h) {
+    set_error("null rate matcher handle");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  const char *why = ldpc::nrrm::match_argument_error(h->c, n, e, rv, qm);
+  if (!why && (filler < 1 || filler > ldpc::soft::kSoftMax)) why = "filler soft bit must be 1 .. 127";
+  if (why) {
+    set_error(why);
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (batch == 0) return 0;
+  if (!rx || !llrs) {
+    set_error("null input or output buffer");
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  }
+  if (int32_t rc = nr_rm_device_state(h)) return rc;
+  const uint32_t e32 = static_cast<uint32_t>(e);
+  const int rc = on_device ? h->dev->recover_i8_device(rx, llrs, batch, e32, rv, qm, filler, combine != 0, static_cast<hipStream_t>(stream))
+                           : h->dev->recover_i8_host(rx, llrs, batch, e32, rv, qm, filler, combine != 0);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
 // "nr5g-tb:BG:A": decimal fields, nothing else
 bool parse_nr_tb_spec(const char *spec, ldpc::nrtb::Config *c, std::string *err) {
   const std::string text = spec;
@@ -657,7 +705,7 @@ int32_t decode_scalar(void *decoder, uint8_t *output, size_t output_len, const F
     return LDPC_TOOLBOX_ERR_ARGUMENT;
   }
   int32_t iterations = -1;
-  const int rc = h->dec->decode_host(llrs, sizeof(F) == 8, 1, max_iterations, output, output_len, &iterations,
+  const int rc = h->dec->decode_host(llrs, sizeof(F) == 8 ? ldpc::LlrType::F64 : ldpc::LlrType::F32, 1, max_iterations, output, output_len, &iterations,
                                      nullptr);
   if (rc != 0) {
     set_error(h->dec->last_error());
@@ -666,10 +714,12 @@ int32_t decode_scalar(void *decoder, uint8_t *output, size_t output_len, const F
   return iterations;
 }
 
-template <typename F>
+// F: float, double, or int8_t soft bits (PART 9: the 8-bit implementations only; P = int16_t); P: the posterior's type
+template <typename F, typename P>
 int32_t decode_batch(void *decoder, uint8_t *output, size_t output_len, const F *llrs, size_t llrs_len,
-                     size_t batch, uint32_t max_iterations, int32_t *iterations, F *posterior, bool on_device,
+                     size_t batch, uint32_t max_iterations, int32_t *iterations, P *posterior, bool on_device,
                      void *stream) {
+  constexpr ldpc::LlrType kType = sizeof(F) == 8 ? ldpc::LlrType::F64 : (sizeof(F) == 4 ? ldpc::LlrType::F32 : ldpc::LlrType::I8);
   g_last_error.clear();
   auto *h = static_cast<DecoderHandle *>(decoder);
   // one error vocabulary for the scalar and the batch entries (include/ldpc_toolbox.h, LDPC_TOOLBOX_ERR_*)
@@ -681,9 +731,13 @@ int32_t decode_batch(void *decoder, uint8_t *output, size_t output_len, const F 
     set_error("LLR or output length does not match the code");
     return LDPC_TOOLBOX_ERR_ARGUMENT;
   }
-  const int rc = on_device ? h->dec->decode_device(llrs, sizeof(F) == 8, batch, max_iterations, output, output_len,
+  if (kType == ldpc::LlrType::I8 && !h->dec->implementation().i8) {
+    set_error("8-bit soft-bit input needs a decoder with one of the 8-bit implementations");
+    return LDPC_TOOLBOX_ERR_UNSUPPORTED;
+  }
+  const int rc = on_device ? h->dec->decode_device(llrs, kType, batch, max_iterations, output, output_len,
                                                    iterations, posterior, static_cast<hipStream_t>(stream))
-                           : h->dec->decode_host(llrs, sizeof(F) == 8, batch, max_iterations, output, output_len,
+                           : h->dec->decode_host(llrs, kType, batch, max_iterations, output, output_len,
                                                  iterations, posterior);
   if (rc == 0) return 0;
   set_error(h->dec->last_error());
@@ -1107,6 +1161,8 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value) {
     *value = static_cast<int64_t>(s->harq_flushed_rows(k[11] - '0'));
   else if (k == "streamed_frames" || k == "stream_iterations")  // (continuous batching: profiles/r03_continuous_batching.txt)
     *value = 0;
+  else if (k == "soft_bits")  // 32, or 8: run_harq keeps its soft buffers as 8-bit soft bits (PART 9)
+    *value = s->soft_bits();
   else if (k == "pooled_frames")  // frames of the last run() call that went through the straggler pool
     *value = static_cast<int64_t>(s->pooled_frames());
   else if (k == "preferred_batch")  // frames per run() call that fill one group of the decoder (4096; more for small graphs)
@@ -1127,6 +1183,12 @@ int32_t ldpc_toolbox_sim_set(void *sim, const char *key, int64_t value) {
   if (k == "pooling") {  // 0: every chunk runs the full iteration budget (no straggler pool)
     s->set_pooling(value != 0);
     return 0;
+  }
+  if (k == "soft_bits") {  // 8 (the 8-bit implementations only) or 32
+    g_last_error.clear();
+    const bool ok = s->set_soft_bits(value);
+    if (!ok) set_error(s->last_error());
+    return ok ? 0 : -1;
   }
   if (k == "streaming") return 0;  // accepted, no effect (continuous batching: profiles/r03_continuous_batching.txt)
   if (k == "modulation" || k == "interleaving") {
@@ -1714,6 +1776,39 @@ int32_t ldpc_toolbox_sim_set_nr_qam(void *sim, void *qam, int32_t max_log) {
   if (s->set_nr_qam(h ? &h->c : nullptr, max_log != 0)) return 0;
   set_error(s->last_error());
   return -1;
+}
+
+// ---- PART 9: the 8-bit soft-bit receive path -----------------------------------------------------------
+
+int32_t ldpc_toolbox_decoder_decode_batch_i8(void *decoder, uint8_t *output, size_t output_len, const int8_t *llrs, size_t llrs_len,
+                                             size_t batch, uint32_t max_iterations, int32_t *iterations, int16_t *posterior) {
+  return decode_batch<int8_t>(decoder, output, output_len, llrs, llrs_len, batch, max_iterations, iterations, posterior, false, nullptr);
+}
+
+int32_t ldpc_toolbox_decoder_decode_batch_i8_device(void *decoder, uint8_t *output, size_t output_len, const int8_t *llrs,
+                                                    size_t llrs_len, size_t batch, uint32_t max_iterations, int32_t *iterations,
+                                                    int16_t *posterior, void *hip_stream) {
+  return decode_batch<int8_t>(decoder, output, output_len, llrs, llrs_len, batch, max_iterations, iterations, posterior, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_demap_i8(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, size_t symbols_len, size_t batch,
+                                 double noise_sigma, int32_t max_log, int64_t c_init) {
+  return nr_demap_i8(qam, llrs, llrs_len, symbols, symbols_len, batch, noise_sigma, max_log, c_init, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_demap_i8_device(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, size_t symbols_len, size_t batch,
+                                        double noise_sigma, int32_t max_log, int64_t c_init, void *hip_stream) {
+  return nr_demap_i8(qam, llrs, llrs_len, symbols, symbols_len, batch, noise_sigma, max_log, c_init, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_rm_recover_i8(void *rm, int8_t *llrs, size_t n, const int8_t *rx, size_t e, size_t batch, uint32_t rv, uint32_t qm,
+                                      int32_t filler, int32_t combine) {
+  return nr_rm_recover_i8(rm, llrs, n, rx, e, batch, rv, qm, filler, combine, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_rm_recover_i8_device(void *rm, int8_t *llrs, size_t n, const int8_t *rx, size_t e, size_t batch, uint32_t rv,
+                                             uint32_t qm, int32_t filler, int32_t combine, void *hip_stream) {
+  return nr_rm_recover_i8(rm, llrs, n, rx, e, batch, rv, qm, filler, combine, true, hip_stream);
 }
 
 // ---- code tables and utilities ------------------------------------------------------------------------

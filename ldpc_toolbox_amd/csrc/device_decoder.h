@@ -31,6 +31,12 @@ namespace ldpc {
 
 struct GroupCall;
 
+// Element type of a decode call's LLR rows.  The posterior it asks for is in the same precision, except that 8-bit soft bits
+// (include/ldpc_toolbox.h, PART 9; the 8-bit implementations only) get the decoder's int16_t posterior word.
+enum class LlrType : uint8_t { F32, F64, I8 };
+constexpr size_t llr_bytes(LlrType t) { return t == LlrType::F64 ? 8 : (t == LlrType::F32 ? 4 : 1); }
+constexpr size_t posterior_bytes(LlrType t) { return t == LlrType::F64 ? 8 : (t == LlrType::F32 ? 4 : 2); }
+
 struct KernelStat {
   uint64_t launches = 0;
   double total_ms = 0.0;
@@ -136,19 +142,19 @@ class DeviceDecoder {
   void reset_kernel_stats();
 
   // Device-resident batch decode.  All pointers are device pointers on device();
-  // llrs: [batch][input_len()] f32 (llrs_f64 = false) or f64, one row per codeword;
+  // llrs: [batch][input_len()] f32, f64 or int8_t soft bits (llrs_type), one row per codeword;
   // bits: [batch][out_len] u8, first out_len hard decisions of every codeword;
   // iterations: [batch] i32, -1 = failed (may be null);
-  // posterior: [batch][n] in the precision of `llrs` (may be null).
+  // posterior: [batch][n] in the precision of `llrs`, int16_t for 8-bit soft bits (may be null).
   // stream: launch stream (nullptr = the handle's own stream, ordered after everything queued on the
   // legacy default stream at the time of the call, and synchronised on return).
   // returns 0, or a negative error code (message via last_error()).
-  int decode_device(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations,
+  int decode_device(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations,
                     uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior,
                     hipStream_t stream);
 
   // Same contract with host pointers: staged through device buffers group by group.
-  int decode_host(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations,
+  int decode_host(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations,
                   uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior);
 
   // Syndrome of hard decisions (the reference's check_llrs, decoder.rs:157-164, with the parities
@@ -176,7 +182,7 @@ class DeviceDecoder {
   int ensure_row_scratch(Workspace &w, size_t bytes);
   // host-pointer entry: pinned staging rings, copy streams, batch-wide device output buffers
   struct HostPipe;
-  int ensure_pipe(size_t group, size_t out_len, size_t in_elem, bool posterior);
+  int ensure_pipe(size_t group, size_t out_len, size_t post_elem, bool posterior);
   int stage_in(const char *src, char *dst, size_t bytes);
   int drain_out(char *dst, const char *src, size_t bytes);
   // recorded by run_group right after the ingest launch (the group's input buffer is free again)
@@ -193,7 +199,7 @@ class DeviceDecoder {
   size_t edge_latency_limit() const;
   uint32_t opt_latency_edge_ = 256;  // "latency_edge": cap on that limit
   size_t edge_lanes_ = 0;           // lane slots of the edge path's message array
-  int decode_latency_edge(const void *llrs, bool llrs_f64, bool host_pointers, size_t batch, uint32_t max_iterations,
+  int decode_latency_edge(const void *llrs, LlrType llrs_type, bool host_pointers, size_t batch, uint32_t max_iterations,
                              uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior, hipStream_t stream);
   // "latency": largest batch that takes this path (0 = never).  8 codewords decode at once (one per XCD), more
   // take turns; measured against the batched kernels (tools/scalar_probe.py): ahead up to 32 (DVB-S2 1/2 at 2 dB:
@@ -201,7 +207,7 @@ class DeviceDecoder {
   uint32_t opt_latency_ = 32;
   static constexpr int kLatencyRetry = -100;  // decode_latency: redo the call with the batched kernels
   static constexpr uint32_t opt_serial_levels_default() { return 512; }
-  int decode_latency(const void *llrs, bool llrs_f64, bool host_pointers, size_t batch, uint32_t max_iterations,
+  int decode_latency(const void *llrs, LlrType llrs_type, bool host_pointers, size_t batch, uint32_t max_iterations,
                      uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior, hipStream_t stream);
   uint32_t lane_count() const;
   bool split_pays(size_t batch) const;
@@ -346,16 +352,16 @@ class DeviceDecoder {
   uint64_t last_pooled_ = 0;
   uint32_t pool_budget_ = 0, pool_budget_max_it_ = 0;  // the budget the last pooled call ended with carries over to the next one at the same limit
   struct StragglerPool;
-  int ensure_pool(size_t batch, size_t rows, size_t out_len, size_t in_elem, bool posterior, bool own_iterations);
+  int ensure_pool(size_t batch, size_t rows, size_t out_len, size_t in_elem, size_t post_elem, bool posterior, bool own_iterations);
   static uint32_t next_pool_budget(double ok, double sum_its_ok, double stragglers, double straggler_its, double failed_full,
                                    uint32_t max_it);
-  int decode_device_plain(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits, size_t out_len,
+  int decode_device_plain(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations, uint8_t *bits, size_t out_len,
                           int32_t *iterations, void *posterior, hipStream_t stream);
-  int decode_device_pooled(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits, size_t out_len,
+  int decode_device_pooled(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations, uint8_t *bits, size_t out_len,
                            int32_t *iterations, void *posterior, hipStream_t stream);
-  int decode_host_plain(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits, size_t out_len,
+  int decode_host_plain(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations, uint8_t *bits, size_t out_len,
                         int32_t *iterations, void *posterior);
-  int decode_host_pooled(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits, size_t out_len,
+  int decode_host_pooled(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations, uint8_t *bits, size_t out_len,
                          int32_t *iterations, void *posterior);
   size_t pool_chunk(size_t batch) const;
   uint32_t opt_lanes_ = 0;  // 0 = automatic (2 for the layered schedule, 1 for flooding)

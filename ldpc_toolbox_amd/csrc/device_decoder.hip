@@ -597,7 +597,8 @@ int DeviceDecoder::order_after_default_stream(hipStream_t s) {
 
 // ---- straggler pooling inside the batch entries (device_decoder.h, "pooling") -------------------------------------------
 
-int DeviceDecoder::ensure_pool(size_t batch, size_t rows, size_t out_len, size_t in_elem, bool posterior, bool own_iterations) {
+int DeviceDecoder::ensure_pool(size_t batch, size_t rows, size_t out_len, size_t in_elem, size_t post_elem, bool posterior,
+                               bool own_iterations) {
   if (!pool_) pool_ = std::make_unique<StragglerPool>();
   StragglerPool &p = *pool_;
   constexpr size_t kFloor = 256;
@@ -606,7 +607,7 @@ int DeviceDecoder::ensure_pool(size_t batch, size_t rows, size_t out_len, size_t
   HIP_TRY(p.d_llrs.ensure(rows * input_len_ * in_elem, kFloor));
   HIP_TRY(p.d_bits.ensure(rows * std::max<size_t>(out_len, 1), kFloor));
   HIP_TRY(p.d_its.ensure(rows * sizeof(int32_t), kFloor));
-  if (posterior) HIP_TRY(p.d_post.ensure(rows * n_ * in_elem, kFloor));
+  if (posterior) HIP_TRY(p.d_post.ensure(rows * n_ * post_elem, kFloor));
   if (own_iterations) HIP_TRY(p.d_its_all.ensure(batch * sizeof(int32_t), kFloor));
   return 0;
 }
@@ -628,22 +629,26 @@ uint32_t DeviceDecoder::next_pool_budget(double ok, double sum_its_ok, double st
 // frames per chunk of a pooled call: what the execution lanes decode at once
 size_t DeviceDecoder::pool_chunk(size_t batch) const { return pick_group(batch) * std::max<uint32_t>(lane_count(), 1); }
 
-int DeviceDecoder::decode_device(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits,
+int DeviceDecoder::decode_device(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations, uint8_t *bits,
                                  size_t out_len, int32_t *iterations, void *posterior, hipStream_t stream) {
+  if (llrs_type == LlrType::I8 && !impl_.i8) {
+    fail("8-bit soft-bit input needs one of the 8-bit implementations");
+    return -3;
+  }
   last_pooled_ = 0;
   last_call_edges_.store(0, std::memory_order_relaxed);
   // (a call on the CALLER's stream only enqueues -- unless "throttle" lets it wait: pooling needs every chunk's counts back)
   if (opt_pooling_ && max_iterations >= 24 && batch >= 2 * pool_chunk(batch) && (stream == nullptr || opt_throttle_) && out_len <= n_)
-    return decode_device_pooled(llrs, llrs_f64, batch, max_iterations, bits, out_len, iterations, posterior, stream);
-  return decode_device_plain(llrs, llrs_f64, batch, max_iterations, bits, out_len, iterations, posterior, stream);
+    return decode_device_pooled(llrs, llrs_type, batch, max_iterations, bits, out_len, iterations, posterior, stream);
+  return decode_device_plain(llrs, llrs_type, batch, max_iterations, bits, out_len, iterations, posterior, stream);
 }
 
-int DeviceDecoder::decode_device_pooled(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits,
+int DeviceDecoder::decode_device_pooled(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations, uint8_t *bits,
                                         size_t out_len, int32_t *iterations, void *posterior, hipStream_t stream) {
   HIP_TRY(hipSetDevice(device_));
-  const size_t in_elem = llrs_f64 ? 8 : 4, G = pick_group(batch), chunk = pool_chunk(batch);
+  const size_t in_elem = llr_bytes(llrs_type), post_elem = posterior_bytes(llrs_type), G = pick_group(batch), chunk = pool_chunk(batch);
   hipStream_t s = stream ? stream : stream_;
-  if (int rc = ensure_pool(batch, chunk, out_len, in_elem, posterior != nullptr, iterations == nullptr)) return rc;
+  if (int rc = ensure_pool(batch, chunk, out_len, in_elem, post_elem, posterior != nullptr, iterations == nullptr)) return rc;
   StragglerPool &p = *pool_;
   uint32_t *const d_idx = p.d_idx.get<uint32_t>(), *const d_stats = p.d_stats.get<uint32_t>();
   int32_t *its = iterations ? iterations : p.d_its_all.get<int32_t>();
@@ -652,10 +657,10 @@ int DeviceDecoder::decode_device_pooled(const void *llrs, bool llrs_f64, size_t 
   uint32_t budget = (pool_budget_ && pool_budget_max_it_ == max_iterations) ? std::min(pool_budget_, max_iterations) : max_iterations;
   double straggler_its = 0.0;
   uint32_t seen_stragglers = 0;
-  const size_t llr_row = input_len_ * in_elem, post_row = n_ * in_elem;
+  const size_t llr_row = input_len_ * in_elem, post_row = n_ * post_elem;
   for (size_t b0 = 0; b0 < batch; b0 += chunk) {
     const size_t nf = std::min(chunk, batch - b0);
-    if (int rc = decode_device_plain(static_cast<const char *>(llrs) + b0 * llr_row, llrs_f64, nf, budget, bits + b0 * out_len, out_len,
+    if (int rc = decode_device_plain(static_cast<const char *>(llrs) + b0 * llr_row, llrs_type, nf, budget, bits + b0 * out_len, out_len,
                                      its + b0, posterior ? static_cast<char *>(posterior) + b0 * post_row : nullptr, stream))
       return rc;
     dev::pool_select_kernel<<<static_cast<uint32_t>((nf + 255) / 256), 256, 0, s>>>(
@@ -677,16 +682,24 @@ int DeviceDecoder::decode_device_pooled(const void *llrs, bool llrs_f64, size_t 
   for (size_t p0 = 0; p0 < seen_stragglers; p0 += chunk) {
     const uint32_t np = static_cast<uint32_t>(std::min<size_t>(chunk, seen_stragglers - p0));
     const uint32_t blocks = (np * 64 + 255) / 256;
-    dev::pool_gather_kernel<<<blocks, 256, 0, s>>>(d_idx + p0, np, static_cast<const uint32_t *>(llrs), llr_row / 4,
-                                                   p.d_llrs.get<uint32_t>());
+    const bool i8 = llrs_type == LlrType::I8;
+    if (i8)
+      dev::pool_copy_rows_kernel<uint8_t, true><<<blocks, 256, 0, s>>>(d_idx + p0, np, static_cast<const uint8_t *>(llrs), llr_row,
+                                                                       p.d_llrs.get<uint8_t>());
+    else
+      dev::pool_gather_kernel<<<blocks, 256, 0, s>>>(d_idx + p0, np, static_cast<const uint32_t *>(llrs), llr_row / 4,
+                                                     p.d_llrs.get<uint32_t>());
     min_group_ = G;
-    const int rc = decode_device_plain(p.d_llrs.get(), llrs_f64, np, max_iterations, p.d_bits.get<uint8_t>(), out_len, p.d_its.get<int32_t>(),
+    const int rc = decode_device_plain(p.d_llrs.get(), llrs_type, np, max_iterations, p.d_bits.get<uint8_t>(), out_len, p.d_its.get<int32_t>(),
                                        posterior ? p.d_post.get() : nullptr, stream);
     min_group_ = keep_min;
     if (rc) return rc;
     dev::pool_scatter_kernel<<<blocks, 256, 0, s>>>(d_idx + p0, np, p.d_bits.get<uint8_t>(), static_cast<uint32_t>(out_len), p.d_its.get<int32_t>(),
-                                                    p.d_post.get<const uint32_t>(), posterior ? post_row / 4 : 0, bits,
-                                                    iterations, static_cast<uint32_t *>(posterior));
+                                                    p.d_post.get<const uint32_t>(), posterior && !i8 ? post_row / 4 : 0, bits,
+                                                    iterations, i8 ? nullptr : static_cast<uint32_t *>(posterior));
+    if (i8 && posterior)
+      dev::pool_copy_rows_kernel<int16_t, false><<<blocks, 256, 0, s>>>(d_idx + p0, np, p.d_post.get<const int16_t>(), n_,
+                                                                        static_cast<int16_t *>(posterior));
   }
   last_pooled_ = seen_stragglers;
   HIP_TRY(hipGetLastError());
@@ -694,7 +707,7 @@ int DeviceDecoder::decode_device_pooled(const void *llrs, bool llrs_f64, size_t 
   return 0;
 }
 
-int DeviceDecoder::decode_device_plain(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations,
+int DeviceDecoder::decode_device_plain(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations,
                                        uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior,
                                        hipStream_t stream) {
   if (batch == 0) return 0;
@@ -711,11 +724,11 @@ int DeviceDecoder::decode_device_plain(const void *llrs, bool llrs_f64, size_t b
   // synchronised take it (one at a time per process, see decode_latency); a call that merely enqueues on
   // the caller's stream keeps the batched kernels
   if (lat_ && batch <= opt_latency_ && own_stream) {
-    const int rc = decode_latency(llrs, llrs_f64, false, batch, max_iterations, bits, out_len, iterations, posterior, s);
+    const int rc = decode_latency(llrs, llrs_type, false, batch, max_iterations, bits, out_len, iterations, posterior, s);
     if (rc != kLatencyRetry) return rc;
   }
   if (lat_edge_ && batch <= edge_latency_limit() && own_stream) {
-    const int rc = decode_latency_edge(llrs, llrs_f64, false, batch, max_iterations, bits, out_len, iterations, posterior, s);
+    const int rc = decode_latency_edge(llrs, llrs_type, false, batch, max_iterations, bits, out_len, iterations, posterior, s);
     if (rc != kLatencyRetry) return rc;
   }
   size_t G = pick_group(batch);
@@ -731,7 +744,7 @@ int DeviceDecoder::decode_device_plain(const void *llrs, bool llrs_f64, size_t b
     HIP_TRY(hipEventRecord(ev_fork_, s));
     HIP_TRY(hipStreamWaitEvent(stream2_, ev_fork_, 0));
   }
-  const size_t in_elem = llrs_f64 ? 8 : 4;
+  const size_t in_elem = llr_bytes(llrs_type), post_elem = posterior_bytes(llrs_type);
   // The layered schedule enqueues dozens of launches per iteration and polls the group's progress word between
   // iterations: with one host thread the second lane's launches were only enqueued once the first lane's whole
   // iteration sequence had been (the lanes then overlap only when every group runs all its iterations; with early
@@ -752,8 +765,8 @@ int DeviceDecoder::decode_device_plain(const void *llrs, bool llrs_f64, size_t b
       const char *src = static_cast<const char *>(llrs) + b0 * input_len_ * in_elem;
       uint8_t *dst_bits = bits + b0 * out_len;
       int32_t *dst_it = iterations ? iterations + b0 : nullptr;
-      void *dst_post = posterior ? static_cast<char *>(posterior) + b0 * n_ * in_elem : nullptr;
-      if (int rc = run_any(*ws_[lane], GroupCall{src, llrs_f64, nb, max_iterations, dst_bits, out_len, dst_it, dst_post,
+      void *dst_post = posterior ? static_cast<char *>(posterior) + b0 * n_ * post_elem : nullptr;
+      if (int rc = run_any(*ws_[lane], GroupCall{src, llrs_type, nb, max_iterations, dst_bits, out_len, dst_it, dst_post,
                                                  lane ? stream2_ : s, may_block, threaded, lanes == 1}))
         return rc;
     }
@@ -821,7 +834,7 @@ void par_memcpy(char *dst, const char *src, size_t bytes, unsigned threads) {
 
 }  // namespace
 
-int DeviceDecoder::ensure_pipe(size_t group, size_t out_len, size_t in_elem, bool posterior) {
+int DeviceDecoder::ensure_pipe(size_t group, size_t out_len, size_t post_elem, bool posterior) {
   if (!pipe_) {
     // built aside and published only when complete: a half-built pipe must never be seen by a later call
     auto p = std::make_unique<HostPipe>();
@@ -842,7 +855,7 @@ int DeviceDecoder::ensure_pipe(size_t group, size_t out_len, size_t in_elem, boo
   for (int r = 0; r < HostPipe::kOutRing; r++) {
     HIP_TRY(p.d_bits[r].ensure(std::max<size_t>(group * out_len, 1)));
     HIP_TRY(p.d_iters[r].ensure(group * sizeof(int32_t)));
-    if (posterior) HIP_TRY(p.d_post[r].ensure(group * n_ * in_elem));
+    if (posterior) HIP_TRY(p.d_post[r].ensure(group * n_ * post_elem));
   }
   return 0;
 }
@@ -895,21 +908,25 @@ int DeviceDecoder::drain_out(char *dst, const char *src, size_t bytes) {
   return 0;
 }
 
-int DeviceDecoder::decode_host(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits,
+int DeviceDecoder::decode_host(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations, uint8_t *bits,
                                size_t out_len, int32_t *iterations, void *posterior) {
+  if (llrs_type == LlrType::I8 && !impl_.i8) {
+    fail("8-bit soft-bit input needs one of the 8-bit implementations");
+    return -3;
+  }
   last_pooled_ = 0;
   last_call_edges_.store(0, std::memory_order_relaxed);
   if (opt_pooling_ && max_iterations >= 24 && batch >= 2 * 4 * pool_chunk(batch) && out_len <= n_)
-    return decode_host_pooled(llrs, llrs_f64, batch, max_iterations, bits, out_len, iterations, posterior);
-  return decode_host_plain(llrs, llrs_f64, batch, max_iterations, bits, out_len, iterations, posterior);
+    return decode_host_pooled(llrs, llrs_type, batch, max_iterations, bits, out_len, iterations, posterior);
+  return decode_host_plain(llrs, llrs_type, batch, max_iterations, bits, out_len, iterations, posterior);
 }
 
 // Host buffers: the caller's rows stay where they are, so the pool is a list of frame indices; chunks of four times what
 // the lanes decode at once (a chunk is one pipelined call of the plain entry: its first copy in and last copy out are exposed).
-int DeviceDecoder::decode_host_pooled(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations, uint8_t *bits,
+int DeviceDecoder::decode_host_pooled(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations, uint8_t *bits,
                                       size_t out_len, int32_t *iterations, void *posterior) {
-  const size_t in_elem = llrs_f64 ? 8 : 4, chunk = 4 * pool_chunk(batch);
-  const size_t llr_row = input_len_ * in_elem, post_row = n_ * in_elem;
+  const size_t in_elem = llr_bytes(llrs_type), post_elem = posterior_bytes(llrs_type), chunk = 4 * pool_chunk(batch);
+  const size_t llr_row = input_len_ * in_elem, post_row = n_ * post_elem;
   std::vector<int32_t> own_its;
   if (!iterations) own_its.resize(batch);
   int32_t *its = iterations ? iterations : own_its.data();
@@ -918,7 +935,7 @@ int DeviceDecoder::decode_host_pooled(const void *llrs, bool llrs_f64, size_t ba
   double ok = 0, sum_ok = 0, straggler_its = 0, failed_full = 0;
   for (size_t b0 = 0; b0 < batch; b0 += chunk) {
     const size_t nf = std::min(chunk, batch - b0);
-    if (int rc = decode_host_plain(static_cast<const char *>(llrs) + b0 * llr_row, llrs_f64, nf, budget, bits + b0 * out_len, out_len,
+    if (int rc = decode_host_plain(static_cast<const char *>(llrs) + b0 * llr_row, llrs_type, nf, budget, bits + b0 * out_len, out_len,
                                    its + b0, posterior ? static_cast<char *>(posterior) + b0 * post_row : nullptr))
       return rc;
     const bool reduced = budget < max_iterations;
@@ -945,7 +962,7 @@ int DeviceDecoder::decode_host_pooled(const void *llrs, bool llrs_f64, size_t ba
     for (size_t i = 0; i < np; i++) std::memcpy(&rows[i * llr_row], static_cast<const char *>(llrs) + stragglers[i] * llr_row, llr_row);
     const size_t keep_min = min_group_;
     min_group_ = pick_group(batch);
-    const int rc = decode_host_plain(rows.data(), llrs_f64, np, max_iterations, reinterpret_cast<uint8_t *>(pbits.data()), out_len,
+    const int rc = decode_host_plain(rows.data(), llrs_type, np, max_iterations, reinterpret_cast<uint8_t *>(pbits.data()), out_len,
                                      pits.data(), posterior ? ppost.data() : nullptr);
     min_group_ = keep_min;
     if (rc) return rc;
@@ -960,7 +977,7 @@ int DeviceDecoder::decode_host_pooled(const void *llrs, bool llrs_f64, size_t ba
   return 0;
 }
 
-int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t batch, uint32_t max_iterations,
+int DeviceDecoder::decode_host_plain(const void *llrs, LlrType llrs_type, size_t batch, uint32_t max_iterations,
                                      uint8_t *bits, size_t out_len, int32_t *iterations, void *posterior) {
   if (batch == 0) return 0;
   if (out_len > n_) {
@@ -969,25 +986,25 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
   }
   HIP_TRY(hipSetDevice(device_));
   if (lat_ && batch <= opt_latency_) {
-    const int rc = decode_latency(llrs, llrs_f64, true, batch, max_iterations, bits, out_len, iterations, posterior, stream_);
+    const int rc = decode_latency(llrs, llrs_type, true, batch, max_iterations, bits, out_len, iterations, posterior, stream_);
     if (rc != kLatencyRetry) return rc;  // else: its workgroups could not all become resident -> batched kernels
   }
   if (lat_edge_ && batch <= edge_latency_limit()) {
-    const int rc = decode_latency_edge(llrs, llrs_f64, true, batch, max_iterations, bits, out_len, iterations, posterior, stream_);
+    const int rc = decode_latency_edge(llrs, llrs_type, true, batch, max_iterations, bits, out_len, iterations, posterior, stream_);
     if (rc != kLatencyRetry) return rc;
   }
   size_t G = pick_group(batch);
   // (host buffers go through pinned staging rings sized by the group: keep a ring slot within 256 MB)
-  while (!group_pref_ && G > 4096 && G * input_len_ * (llrs_f64 ? 8 : 4) > (size_t(256) << 20)) G /= 2;
+  while (!group_pref_ && G > 4096 && G * input_len_ * llr_bytes(llrs_type) > (size_t(256) << 20)) G /= 2;
   if (lane_count() == 2 && batch <= G && split_pays(batch)) G = round_up((batch + 1) / 2, 256);
   const uint32_t lanes = (batch > G && opt_lanes_ != 1) ? 2u : 1u;
   last_lanes_ = lanes;
   last_group_ = G;
-  const size_t in_elem = llrs_f64 ? 8 : 4;
+  const size_t in_elem = llr_bytes(llrs_type), post_elem = posterior_bytes(llrs_type);
   if (int rc = ensure_lanes(lanes, G)) return rc;
   for (uint32_t l = 0; l < lanes; l++)
     if (int rc = ensure_host_staging(*ws_[l], G, in_elem)) return rc;
-  if (int rc = ensure_pipe(std::min(G, batch), out_len, in_elem, posterior != nullptr)) return rc;
+  if (int rc = ensure_pipe(std::min(G, batch), out_len, post_elem, posterior != nullptr)) return rc;
   HostPipe &p = *pipe_;
   // group boundaries: a long batch opens with G/4 and 3G/4 (decoding starts after a quarter group's copy)
   std::vector<size_t> starts;
@@ -1029,7 +1046,7 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
     if (drc == 0 && iterations)
       drc = drain_out(reinterpret_cast<char *>(iterations + b0), p.d_iters[r].get<const char>(), nb * sizeof(int32_t));
     if (drc == 0 && posterior)
-      drc = drain_out(static_cast<char *>(posterior) + b0 * n_ * in_elem, p.d_post[r].get<const char>(), nb * n_ * in_elem);
+      drc = drain_out(static_cast<char *>(posterior) + b0 * n_ * post_elem, p.d_post[r].get<const char>(), nb * n_ * post_elem);
     return drc;
   };
   // The layered schedule enqueues dozens of launches per iteration: each lane's launches are enqueued by a thread of its
@@ -1153,7 +1170,7 @@ int DeviceDecoder::decode_host_plain(const void *llrs, bool llrs_f64, size_t bat
       // a single small group (the reference-style scalar call) may let the host follow the device's progress; so may
       // a lane with an enqueuing thread of its own
       // (flood_pace false: this thread stages copies between its enqueues, it does not wait on a flooding group)
-      const int erc = run_any(w, GroupCall{w.in.get(), llrs_f64, nb, max_iterations, p.d_bits[r].get<uint8_t>(), out_len, p.d_iters[r].get<int32_t>(),
+      const int erc = run_any(w, GroupCall{w.in.get(), llrs_type, nb, max_iterations, p.d_bits[r].get<uint8_t>(), out_len, p.d_iters[r].get<int32_t>(),
                                            posterior ? p.d_post[r].get() : nullptr, s, n_groups == 1 || threaded, threaded, false});
       if (erc) return erc;
       HIP_TRY(hipEventRecord(p.group_done[gi], s));

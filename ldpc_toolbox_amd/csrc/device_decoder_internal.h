@@ -167,8 +167,8 @@ inline Tiling make_tiling(uint32_t G, uint32_t tile, uint32_t slice, uint32_t no
 
 // One group's call, from the batch entries through run_any to run_group<T> / run_group_i8.
 struct GroupCall {
-  const void *llrs;  // the group's input rows (device memory), f32 or f64
-  bool llrs_f64;
+  const void *llrs;  // the group's input rows (device memory): f32, f64, or 8-bit soft bits (the 8-bit rules only)
+  LlrType llrs_type;
   size_t nb;  // codewords of this group
   uint32_t max_iterations;
   uint8_t *bits;
@@ -343,10 +343,10 @@ struct DeviceDecoder::GroupFrame {
     grp::syndrome_bits(s, synd_threads, row_ptr, edge_col, m, hard, unsat, w.n_active, w.n_slots, W, synd_rows);
   }
   void latch(uint32_t *unsat, int32_t it) const { grp::latch(s, w.done, w.iters, unsat, w.n_active, it, G); }
-  // the group's first launches: state, ingest (the rule family's kernel for f32 and for f64 input), and the pre-check on
-  // the raw input: iterations = 0 (flooding.rs:57-64)
-  template <typename K32, typename K64, typename C, typename P>
-  int begin(K32 ingest_f32, K64 ingest_f64, C *chan, P *post) const {
+  // the group's first launches: state, ingest (the rule family's kernel for f32 and for f64 input; the 8-bit rules have a
+  // third, for rows of 8-bit soft bits), and the pre-check on the raw input: iterations = 0 (flooding.rs:57-64)
+  template <typename K32, typename K64, typename C, typename P, typename K8 = std::nullptr_t>
+  int begin(K32 ingest_f32, K64 ingest_f64, C *chan, P *post, K8 ingest_i8 = nullptr) const {
     grp::init_group(s, w.done, w.iters, w.unsat0, w.unsat1, w.n_active, w.n_slots, w.slot_cw, static_cast<uint32_t>(c.nb), G);
     const dim3 grid((n + 63) / 64, W);
     const uint32_t block_size = d.pattern_len_ ? n / d.pattern_len_ : 0;
@@ -354,7 +354,14 @@ struct DeviceDecoder::GroupFrame {
       kernel<<<grid, 256, 0, s>>>(src, d.input_len_, static_cast<uint32_t>(c.nb), n, G, tile, chan, post, w.rawbits,
                                   d.d_src_block_.get<int32_t>(), block_size);
     };
-    if (c.llrs_f64)
+    if (c.llrs_type == LlrType::I8) {
+      if constexpr (std::is_same<K8, std::nullptr_t>::value) {
+        d.fail("internal error: 8-bit soft bits handed to a float rule");
+        return -3;
+      } else {
+        ingest(ingest_i8, static_cast<const int8_t *>(c.llrs));
+      }
+    } else if (c.llrs_type == LlrType::F64)
       ingest(ingest_f64, static_cast<const double *>(c.llrs));
     else
       ingest(ingest_f32, static_cast<const float *>(c.llrs));
@@ -383,7 +390,10 @@ struct DeviceDecoder::GroupFrame {
       kernel<<<grid, 256, 0, s>>>(post, w.rawbits, st, do_compact, n, G, tile, static_cast<uint32_t>(c.out_len), c.bits,
                                   c.iterations, out, zero_fill, retire_only, from_hard ? hard : nullptr, hard_ok);
     };
-    if (c.llrs_f64)
+    if constexpr (sizeof(P) == 2) {  // the 8-bit rules: soft-bit input gets the posterior word itself
+      if (c.llrs_type == LlrType::I8) return go(dev::emit_kernel<P, int16_t>, static_cast<int16_t *>(c.posterior));
+    }
+    if (c.llrs_type == LlrType::F64)
       go(dev::emit_kernel<P, double>, static_cast<double *>(c.posterior));
     else
       go(dev::emit_kernel<P, float>, static_cast<float *>(c.posterior));

@@ -46,6 +46,11 @@ class DeviceNrQam {
   // symbols -> llrs [batch][llrs_len] (nrqam::demod_argument_error)
   int demod_device(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
                    bool max_log, int64_t c_init, hipStream_t stream);
+  // float symbols -> 8-bit soft bits [batch][llrs_len] (include/ldpc_toolbox.h, PART 9); llrs: any byte address
+  int demap_i8_device(const float *symbols, int8_t *llrs, size_t symbols_len, size_t llrs_len, size_t batch, double sigma, bool max_log,
+                      int64_t c_init, hipStream_t stream);
+  int demap_i8_host(const float *symbols, int8_t *llrs, size_t symbols_len, size_t llrs_len, size_t batch, double sigma, bool max_log,
+                    int64_t c_init);
   // Host pointers: staged through device buffers of the handle, synchronous.
   int mod_host(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch, int64_t c_init);
   int demod_host(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,

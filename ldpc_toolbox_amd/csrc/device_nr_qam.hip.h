@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <memory>
+#include <type_traits>
 #include <vector>
 
 #include "device_nr_qam.h"
@@ -128,6 +129,43 @@ void nr_qam_demap(const nrqam::Config &cfg, const IO *symbols, IO *llrs, size_t 
       nr_qam_demap_h<IO, IO, true>(cfg, in, out, sl, total, scale, c, s);
     else
       nr_qam_demap_h<IO, double, false>(cfg, in, out, sl, total, scale, c, s);
+  });
+}
+
+// the 8-bit demapper: exact = double arithmetic, max-log = float, as nr_qam_demap<float>; a pass's rows begin at a multiple
+// of QM bytes from `llrs`, so the piece width follows from the address of each pass's first row
+template <int H>
+void nr_qam_demap_i8_pass(const nrqam::Config &cfg, const float *symbols, int8_t *llrs, uint32_t symbols_len, uint64_t total, double scale,
+                          bool max_log, const uint32_t *c, hipStream_t s) {
+  auto go = [&](auto wide) {
+    constexpr bool kWide = decltype(wide)::value;
+    if (max_log)
+      nrqam::demap_i8_kernel<H, float, true, kWide><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(
+          symbols, llrs, symbols_len, total, static_cast<float>(scale), c, nr_qam_axis<float>(cfg, scale));
+    else
+      nrqam::demap_i8_kernel<H, double, false, kWide><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(symbols, llrs, symbols_len, total, scale,
+                                                                                                     c, nr_qam_axis<double>(cfg, scale));
+  };
+  if (reinterpret_cast<uintptr_t>(llrs) % 4 == 0)
+    go(std::true_type{});
+  else
+    go(std::false_type{});
+}
+
+void nr_qam_demap_i8(const nrqam::Config &cfg, const float *symbols, int8_t *llrs, size_t symbols_len, size_t batch, double sigma,
+                     bool max_log, const uint32_t *c, hipStream_t s) {
+  const uint32_t sl = static_cast<uint32_t>(symbols_len);
+  const double scale = 1.0 / (sigma * sigma);
+  nr_qam_passes(batch, symbols_len, [&](size_t b0, size_t frames) {
+    const uint64_t total = uint64_t(frames) * symbols_len;
+    const float *in = symbols + 2 * b0 * symbols_len;
+    int8_t *out = llrs + b0 * symbols_len * cfg.qm;
+    switch (cfg.h()) {
+      case 1: return nr_qam_demap_i8_pass<1>(cfg, in, out, sl, total, scale, max_log, c, s);
+      case 2: return nr_qam_demap_i8_pass<2>(cfg, in, out, sl, total, scale, max_log, c, s);
+      case 3: return nr_qam_demap_i8_pass<3>(cfg, in, out, sl, total, scale, max_log, c, s);
+      default: return nr_qam_demap_i8_pass<4>(cfg, in, out, sl, total, scale, max_log, c, s);
+    }
   });
 }
 
@@ -261,6 +299,31 @@ int DeviceNrQam::demod_device(const void *symbols, void *llrs, bool f64, size_t 
   else
     nr_qam_demap(c_, static_cast<const float *>(symbols), static_cast<float *>(llrs), symbols_len, batch, sigma, max_log, c, s);
   return end(stream, s, c != nullptr);
+}
+
+int DeviceNrQam::demap_i8_device(const float *symbols, int8_t *llrs, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
+                                 bool max_log, int64_t c_init, hipStream_t stream) {
+  if (batch == 0 || llrs_len == 0) return 0;
+  hipStream_t s;
+  if (int rc = begin(stream, &s)) return rc;
+  const uint32_t *c;
+  if (int rc = sequence(c_init, llrs_len, s, &c)) return rc;
+  nr_qam_demap_i8(c_, symbols, llrs, symbols_len, batch, sigma, max_log, c, s);
+  return end(stream, s, c != nullptr);
+}
+
+int DeviceNrQam::demap_i8_host(const float *symbols, int8_t *llrs, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
+                               bool max_log, int64_t c_init) {
+  if (batch == 0 || llrs_len == 0) return 0;
+  NRQAM_TRY(hipSetDevice(device_));
+  const size_t in_bytes = batch * symbols_len * 2 * sizeof(float), out_bytes = batch * llrs_len;
+  NRQAM_TRY(d_in_.ensure(in_bytes, 256));
+  NRQAM_TRY(d_out_.ensure(out_bytes, 256));
+  NRQAM_TRY(hipMemcpyAsync(d_in_.get(), symbols, in_bytes, hipMemcpyHostToDevice, stream_));
+  if (int rc = demap_i8_device(d_in_.get<float>(), d_out_.get<int8_t>(), symbols_len, llrs_len, batch, sigma, max_log, c_init, stream_)) return rc;
+  NRQAM_TRY(hipMemcpyAsync(llrs, d_out_.get(), out_bytes, hipMemcpyDeviceToHost, stream_));
+  NRQAM_TRY(hipStreamSynchronize(stream_));
+  return 0;
 }
 
 int DeviceNrQam::mod_host(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch, int64_t c_init) {

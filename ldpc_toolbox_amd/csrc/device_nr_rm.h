@@ -22,6 +22,8 @@ constexpr size_t kNrRmStageBytes = size_t(1) << 28;
 void nr_rm_launch_match(const nrrm::Plan &p, const uint8_t *codewords, uint8_t *output, size_t batch, hipStream_t s);
 template <typename T>
 void nr_rm_launch_recover(const nrrm::Plan &p, const T *rx, T *llrs, size_t batch, T filler, bool combine, hipStream_t s);
+// 8-bit soft bits with saturating sums (include/ldpc_toolbox.h, PART 9); filler in 1..127; any byte addresses
+void nr_rm_launch_recover_i8(const nrrm::Plan &p, const int8_t *rx, int8_t *llrs, size_t batch, int32_t filler, bool combine, hipStream_t s);
 
 class DeviceNrRm {
  public:
@@ -41,11 +43,15 @@ class DeviceNrRm {
   // rx [batch][e] -> llrs [batch][n], floats or (f64) doubles
   int recover_device(const void *rx, void *llrs, bool f64, size_t batch, uint32_t e, uint32_t rv, uint32_t qm, double filler_llr,
                      bool combine, hipStream_t stream);
+  // rx [batch][e] -> llrs [batch][n], 8-bit soft bits
+  int recover_i8_device(const int8_t *rx, int8_t *llrs, size_t batch, uint32_t e, uint32_t rv, uint32_t qm, int32_t filler, bool combine,
+                        hipStream_t stream);
   // Host pointers: staged through device buffers of the handle, kNrRmStageBytes at a time, synchronous.  A HIP failure
   // in a later stage leaves the rows of the earlier ones written.
   int match_host(const uint8_t *codewords, uint8_t *output, size_t batch, uint32_t e, uint32_t rv, uint32_t qm);
   int recover_host(const void *rx, void *llrs, bool f64, size_t batch, uint32_t e, uint32_t rv, uint32_t qm, double filler_llr,
                    bool combine);
+  int recover_i8_host(const int8_t *rx, int8_t *llrs, size_t batch, uint32_t e, uint32_t rv, uint32_t qm, int32_t filler, bool combine);
 
  private:
   DeviceNrRm() = default;

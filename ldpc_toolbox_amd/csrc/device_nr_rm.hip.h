@@ -43,6 +43,20 @@ void nr_rm_launch_recover(const nrrm::Plan &p, const T *rx, T *llrs, size_t batc
 template void nr_rm_launch_recover<float>(const nrrm::Plan &, const float *, float *, size_t, float, bool, hipStream_t);
 template void nr_rm_launch_recover<double>(const nrrm::Plan &, const double *, double *, size_t, double, bool, hipStream_t);
 
+void nr_rm_launch_recover_i8(const nrrm::Plan &p, const int8_t *rx, int8_t *llrs, size_t batch, int32_t filler, bool combine, hipStream_t s) {
+  const size_t pass = nr_rm_pass_frames(std::max(p.n, p.e));
+  const dev::FastDiv div_n = dev::fast_div(p.n);
+  for (size_t b0 = 0; b0 < batch; b0 += pass) {
+    const size_t frames = std::min(pass, batch - b0);
+    int8_t *out = llrs + b0 * p.n;
+    const uint32_t total = static_cast<uint32_t>(frames * p.n);
+    const uint32_t shift = static_cast<uint32_t>(reinterpret_cast<uintptr_t>(out) & 3);
+    const uint32_t threads = static_cast<uint32_t>((uint64_t(total) + shift + 3) / 4);
+    nrrm::nr_rm_recover_i8_kernel<<<(threads + nrrm::kThreads - 1) / nrrm::kThreads, nrrm::kThreads, 0, s>>>(
+        rx + b0 * p.e, out, total, shift, p, div_n, filler, combine ? 1 : 0);
+  }
+}
+
 bool DeviceNrRm::fail(const std::string &m, hipError_t e) {
   error_ = m;
   if (e != hipSuccess) error_ += std::string(": ") + hipGetErrorString(e);
@@ -121,6 +135,15 @@ int DeviceNrRm::recover_device(const void *rx, void *llrs, bool f64, size_t batc
   return end(stream, s);
 }
 
+int DeviceNrRm::recover_i8_device(const int8_t *rx, int8_t *llrs, size_t batch, uint32_t e, uint32_t rv, uint32_t qm, int32_t filler,
+                                  bool combine, hipStream_t stream) {
+  if (batch == 0) return 0;
+  hipStream_t s;
+  if (int rc = begin(stream, &s)) return rc;
+  nr_rm_launch_recover_i8(nrrm::make_plan(c_, e, rv, qm), rx, llrs, batch, filler, combine, s);
+  return end(stream, s);
+}
+
 int DeviceNrRm::match_host(const uint8_t *codewords, uint8_t *output, size_t batch, uint32_t e, uint32_t rv, uint32_t qm) {
   if (batch == 0) return 0;
   NRRM_TRY(hipSetDevice(device_));
@@ -154,6 +177,24 @@ int DeviceNrRm::recover_host(const void *rx, void *llrs, bool f64, size_t batch,
     if (combine) NRRM_TRY(hipMemcpyAsync(d_out_.get(), dst + b0 * c_.n * el, frames * c_.n * el, hipMemcpyHostToDevice, stream_));
     if (int rc = recover_device(d_in_.get(), d_out_.get(), f64, frames, e, rv, qm, filler_llr, combine, stream_)) return rc;
     NRRM_TRY(hipMemcpyAsync(dst + b0 * c_.n * el, d_out_.get(), frames * c_.n * el, hipMemcpyDeviceToHost, stream_));
+    NRRM_TRY(hipStreamSynchronize(stream_));
+  }
+  return 0;
+}
+
+int DeviceNrRm::recover_i8_host(const int8_t *rx, int8_t *llrs, size_t batch, uint32_t e, uint32_t rv, uint32_t qm, int32_t filler,
+                                bool combine) {
+  if (batch == 0) return 0;
+  NRRM_TRY(hipSetDevice(device_));
+  const size_t stage = std::min(batch, std::max<size_t>(kNrRmStageBytes / std::max<size_t>(c_.n, e), 1));
+  NRRM_TRY(d_in_.ensure(stage * e, 256));
+  NRRM_TRY(d_out_.ensure(stage * c_.n, 256));
+  for (size_t b0 = 0; b0 < batch; b0 += stage) {
+    const size_t frames = std::min(stage, batch - b0);
+    NRRM_TRY(hipMemcpyAsync(d_in_.get(), rx + b0 * e, frames * e, hipMemcpyHostToDevice, stream_));
+    if (combine) NRRM_TRY(hipMemcpyAsync(d_out_.get(), llrs + b0 * c_.n, frames * c_.n, hipMemcpyHostToDevice, stream_));
+    if (int rc = recover_i8_device(d_in_.get<int8_t>(), d_out_.get<int8_t>(), frames, e, rv, qm, filler, combine, stream_)) return rc;
+    NRRM_TRY(hipMemcpyAsync(llrs + b0 * c_.n, d_out_.get(), frames * c_.n, hipMemcpyDeviceToHost, stream_));
     NRRM_TRY(hipStreamSynchronize(stream_));
   }
   return 0;

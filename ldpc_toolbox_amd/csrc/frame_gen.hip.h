@@ -20,6 +20,7 @@
 #include <cstdint>
 
 #include "exact_math.h"
+#include "soft_i8.h"
 
 namespace ldpc {
 namespace gen {
@@ -359,6 +360,48 @@ __global__ __launch_bounds__(256) void harq_collect_kernel(const int32_t *__rest
   const float *src = soft + size_t(f) * n;
   float *dst = pool_soft + size_t(pos) * n;
   for (uint32_t i = lane; i < n; i += 64) dst[i] = src[i];
+}
+
+// harq_collect_kernel for the 8-bit soft buffer ("soft_bits" 8): the rows are n bytes, n a multiple of 4 (52 Zc or 68 Zc) and
+// every row on a dword address, copied as row_words = n / 4 dwords.  (A kernel of its own: the float one stays as it is.)
+__global__ __launch_bounds__(256) void harq_collect_i8_kernel(const int32_t *__restrict__ iterations, uint32_t frames, uint64_t first_frame,
+                                                              const uint64_t *__restrict__ frame_ids, const uint32_t *__restrict__ spent_in,
+                                                              uint32_t max_iterations, const uint32_t *__restrict__ soft, uint32_t row_words,
+                                                              uint32_t *__restrict__ pool_soft, uint64_t *__restrict__ pool_frames,
+                                                              uint32_t *__restrict__ pool_spent, uint32_t *__restrict__ pool_count,
+                                                              uint32_t capacity) {
+  const uint32_t lane = threadIdx.x & 63u;
+  const uint32_t f = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+  if (f >= frames || iterations[f] >= 0) return;
+  uint32_t pos = 0;
+  if (lane == 0) pos = atomicAdd(pool_count, 1u);
+  pos = static_cast<uint32_t>(__shfl(static_cast<int>(pos), 0, 64));
+  if (pos >= capacity) return;
+  if (lane == 0) {
+    pool_frames[pos] = frame_ids ? frame_ids[f] : first_frame + f;
+    pool_spent[pos] = (spent_in ? spent_in[f] : 0u) + max_iterations;
+  }
+  const uint32_t *src = soft + size_t(f) * row_words;
+  uint32_t *dst = pool_soft + size_t(pos) * row_words;
+  for (uint32_t i = lane; i < row_words; i += 64) dst[i] = src[i];
+}
+
+// A generator's float rows taken through Q (soft_i8.h) into 8-bit soft bits, for the 8-bit soft buffer: a thread takes four
+// consecutive values -- one 16-byte load, one dword store; both buffers are the simulator's own, aligned -- and the last
+// thread the one to three that remain.
+__global__ __launch_bounds__(256) void quantize_i8_kernel(const float *__restrict__ src, int8_t *__restrict__ dst, uint64_t total) {
+  const uint64_t i0 = 4 * (uint64_t(blockIdx.x) * 256 + threadIdx.x);
+  if (i0 >= total) return;
+  if (i0 + 4 <= total) {
+    typedef float float4_t __attribute__((ext_vector_type(4)));
+    const float4_t x = *reinterpret_cast<const float4_t *>(src + i0);
+    uint32_t w = 0;
+#pragma unroll
+    for (int k = 0; k < 4; k++) w |= uint32_t(static_cast<uint8_t>(soft::soft_quantize(static_cast<double>(x[k])))) << (8 * k);
+    *reinterpret_cast<uint32_t *>(dst + i0) = w;
+    return;
+  }
+  for (uint64_t i = i0; i < total; i++) dst[i] = static_cast<int8_t>(soft::soft_quantize(static_cast<double>(src[i])));
 }
 
 // The counters of one attempt (transmission t) of `frames` frames.  per_tx[4] of this transmission: [0] attempts

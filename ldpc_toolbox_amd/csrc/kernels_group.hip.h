@@ -699,6 +699,18 @@ __global__ __launch_bounds__(256) void pool_scatter_kernel(const uint32_t *__res
   if (post != nullptr)
     for (size_t w = lane; w < post_words; w += 64) post[f * post_words + w] = ppost[size_t(i) * post_words + w];
 }
+// The rows of a call with 8-bit input are bytes (and its posterior rows int16_t) at any address of their type, of any
+// length: copied by element, a wavefront per row.  GATHER: dst[i] = src[idx[i]]; else dst[idx[i]] = src[i].
+template <typename E, bool GATHER>
+__global__ __launch_bounds__(256) void pool_copy_rows_kernel(const uint32_t *__restrict__ idx, uint32_t count, const E *__restrict__ src,
+                                                             size_t row_len, E *__restrict__ dst) {
+  const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 6, lane = threadIdx.x & 63u;
+  if (i >= count) return;
+  const size_t f = idx[i];
+  const E *s = src + (GATHER ? f : size_t(i)) * row_len;
+  E *d = dst + (GATHER ? size_t(i) : f) * row_len;
+  for (size_t w = lane; w < row_len; w += 64) d[w] = s[w];
+}
 #endif  // LDPC_GROUP_KERNELS_TU
 
 }  // namespace dev

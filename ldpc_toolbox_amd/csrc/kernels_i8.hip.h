@@ -12,6 +12,7 @@
 // thread, and evaluated in the reference's slot order.
 #pragma once
 #include "kernels.hip.h"
+#include "soft_i8.h"
 
 namespace ldpc {
 namespace dev {
@@ -210,6 +211,69 @@ __global__ __launch_bounds__(256) void ingest_i8_kernel(const SrcT *__restrict__
     }
   }
 }
+
+#ifdef LDPC_I8_KERNELS_TU  // not a template: compiled in ONE translation unit (run_group_i8.hip)
+// Rows of 8-bit soft bits (include/ldpc_toolbox.h, PART 9): the value is clipped (soft_i8.h), not quantised, and the ballot
+// is on v <= 0 -- clip(v) <= 0 is the same test.  The load side is wide where the rows allow: with no puncturing pattern and
+// the rows on dword addresses (`src` and the stride both multiples of 4) a lane loads four variables of one codeword as a
+// dword, 16 lanes a codeword's 64 bytes of the tile, and clips them in the word; otherwise a byte per lane, as the float
+// kernels load an element per lane.  The LDS tile's rows are 68 bytes: dword stores on the way in, and the transposed byte
+// reads of a wavefront -- lane tx reads byte r of row tx -- fall into 64 different dwords 17 apart, two per bank.
+template <>
+__global__ __launch_bounds__(256) void ingest_i8_kernel<int8_t>(const int8_t *__restrict__ src, size_t src_stride, uint32_t nb, uint32_t n,
+                                                                uint32_t G, uint32_t tile, int8_t *__restrict__ chan,
+                                                                int16_t *__restrict__ post, uint64_t *__restrict__ rawbits,
+                                                                const int32_t *__restrict__ src_block, uint32_t block_size) {
+  __shared__ __attribute__((aligned(4))) int8_t lds[64][68];
+  const uint32_t tx = threadIdx.x & 63u, ty = threadIdx.x >> 6;
+  const uint32_t v0 = blockIdx.x * 64, b0 = blockIdx.y * 64;
+  const bool wide = src_block == nullptr && ((reinterpret_cast<uintptr_t>(src) | src_stride) & 3u) == 0;  // workgroup-uniform
+  if (wide) {
+    const uint32_t d = threadIdx.x & 15u;
+    for (uint32_t r = threadIdx.x >> 4; r < 64; r += 16) {
+      const uint32_t b = b0 + r, v = v0 + 4 * d;
+      uint32_t w = 0x01010101u;
+      if (b < nb && v + 3 < n) {
+        w = soft::soft_clip4(*reinterpret_cast<const uint32_t *>(src + size_t(b) * src_stride + v));
+      } else if (b < nb && v < n) {  // (the row's last, partial dword)
+        for (uint32_t k = 0; k < 4; k++)
+          if (v + k < n) {
+            const uint32_t byte = static_cast<uint8_t>(soft::soft_clip(src[size_t(b) * src_stride + v + k]));
+            w = (w & ~(0xFFu << (8 * k))) | (byte << (8 * k));
+          }
+      }
+      *reinterpret_cast<uint32_t *>(&lds[r][4 * d]) = w;
+    }
+  } else {
+    for (uint32_t r = ty; r < 64; r += 4) {
+      const uint32_t b = b0 + r, v = v0 + tx;
+      int val = 1;
+      if (b < nb && v < n) {
+        if (src_block) {
+          const int32_t sb = src_block[v / block_size];
+          val = sb < 0 ? 0 : src[size_t(b) * src_stride + size_t(sb) * block_size + v % block_size];
+        } else {
+          val = src[size_t(b) * src_stride + v];
+        }
+      }
+      lds[r][tx] = static_cast<int8_t>(soft::soft_clip(val));
+    }
+  }
+  __syncthreads();
+  const uint32_t W = G / 64;
+  const size_t base = tile_base(b0, n, tile) + tx;
+  for (uint32_t r = ty; r < 64; r += 4) {
+    const uint32_t v = v0 + r;
+    if (v < n) {
+      const int q = lds[tx][r];
+      chan[base + size_t(v) * tile] = static_cast<int8_t>(q);
+      post[base + size_t(v) * tile] = static_cast<int16_t>(q);
+      const uint64_t bal = __builtin_amdgcn_ballot_w64(q <= 0);
+      if (tx == 0) rawbits[size_t(v) * W + blockIdx.y] = bal;
+    }
+  }
+}
+#endif  // LDPC_I8_KERNELS_TU
 
 // ---- flooding check nodes ------------------------------------------------------------------------
 // dynamic LDS: 2 * dmax * blockDim.x * 4 bytes + 32 (lookup table)

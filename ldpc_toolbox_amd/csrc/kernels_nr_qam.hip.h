@@ -12,6 +12,8 @@
 //   * demap_kernel<H, IO, A, MAXLOG>: per axis d_u = sx * A_u - K_u and the 2h folds over ascending u; A_u and K_u travel
 //     in the kernel arguments and every index is wave-uniform (scalar loads).  The QM LLRs of a symbol leave as 8- or
 //     16-byte vector stores, nontemporal on the max-log path.
+//   * demap_i8_kernel<H, A, MAXLOG, WIDE>: the same arithmetic from float symbols, each LLR quantised to an 8-bit soft bit:
+//     QM bytes out per symbol, the float row never stored.
 //   * qam_llr_kernel<H, MAXLOG>: the simulator's generator, fused: pooled transmitted row -> symbol -> AWGN -> the f64
 //     demapper -> float.
 #pragma once
@@ -21,6 +23,7 @@
 
 #include "frame_gen.hip.h"
 #include "kernels_demod.hip.h"
+#include "soft_i8.h"
 
 namespace ldpc {
 namespace nrqam {
@@ -234,6 +237,41 @@ __global__ __launch_bounds__(kThreads) void demap_kernel(const IO *__restrict__ 
     out[j] = ((flip >> j) & 1u) ? -x : x;
   }
   store_row<MAXLOG>(llrs + id * (2 * H), out);
+}
+
+// The 8-bit demapper (include/ldpc_toolbox.h, PART 9): demap_kernel<H, float, A, MAXLOG> up to the float it would store --
+// exact: double arithmetic rounded once to float -- then the descrambling sign and Q (soft_i8.h; Q(-x) = -Q(x), and the sign
+// goes first as it does in the float row).  The 2 H bytes of a symbol are packed into one 64-bit word and leave in pieces:
+// WIDE (the row buffer's address is a multiple of 4) dwords for H = 2, 4 and half-words for H = 1, 3 -- every symbol's
+// address is then a multiple of the piece -- else single bytes, for a buffer at any byte address.
+template <int H, typename A, bool MAXLOG, bool WIDE>
+__global__ __launch_bounds__(kThreads) void demap_i8_kernel(const float *__restrict__ symbols, int8_t *__restrict__ llrs, uint32_t symbols_len,
+                                                            uint64_t total, A scale, const uint32_t *__restrict__ c, const Axis<A> t) {
+  const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (id >= total) return;
+  const typename Pair<float>::type s = *reinterpret_cast<const typename Pair<float>::type *>(symbols + 2 * id);
+  A llr[2 * H];
+  axis_llrs<H, A, MAXLOG>(static_cast<A>(s.x) * scale, static_cast<A>(s.y) * scale, t, llr);
+  uint32_t flip = 0;
+  if (c != nullptr) flip = gold_window<2 * H>(c, 2 * H * static_cast<uint32_t>(id % symbols_len));
+  uint64_t w = 0;
+#pragma unroll
+  for (int j = 0; j < 2 * H; j++) {
+    const float x = static_cast<float>(llr[j]);
+    const int q = soft::soft_quantize(static_cast<double>(((flip >> j) & 1u) ? -x : x));
+    w |= uint64_t(static_cast<uint8_t>(q)) << (8 * j);
+  }
+  int8_t *row = llrs + id * (2 * H);
+  if constexpr (WIDE && H % 2 == 0) {
+#pragma unroll
+    for (int i = 0; i < 2 * H; i += 4) demod::store_llr<MAXLOG>(reinterpret_cast<uint32_t *>(row + i), static_cast<uint32_t>(w >> (8 * i)));
+  } else if constexpr (WIDE) {
+#pragma unroll
+    for (int i = 0; i < 2 * H; i += 2) demod::store_llr<MAXLOG>(reinterpret_cast<uint16_t *>(row + i), static_cast<uint16_t>(w >> (8 * i)));
+  } else {
+#pragma unroll
+    for (int i = 0; i < 2 * H; i++) row[i] = static_cast<int8_t>(w >> (8 * i));
+  }
 }
 
 // ---- the simulator's generator ----------------------------------------------------------------------------------------

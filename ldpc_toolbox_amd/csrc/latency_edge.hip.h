@@ -217,12 +217,24 @@ __device__ __forceinline__ T edge_v2c(T l, T m) {
   if constexpr (std::is_integral<T>::value) return i8_clip(l - m);
   else return l - m;
 }
-// the caller's LLR in the decoder's arithmetic (arithmetic.rs:194-196; 8-bit: :690-699)
+// the caller's LLR in the decoder's arithmetic (arithmetic.rs:194-196; 8-bit: :690-699); a row of 8-bit soft bits
+// (include/ldpc_toolbox.h, PART 9) is clipped, not quantised
 template <typename T, typename SrcT>
 __device__ __forceinline__ T edge_quantize(SrcT raw) {
-  if constexpr (std::is_integral<T>::value) return i8_quantize(static_cast<double>(raw));
+  if constexpr (std::is_same<SrcT, int8_t>::value) return soft::soft_clip(raw);
+  else if constexpr (std::is_integral<T>::value) return i8_quantize(static_cast<double>(raw));
   else return static_cast<T>(raw);
 }
+
+// the posterior a call gets: the precision of its LLR rows; int16_t, the 8-bit rules' posterior word, for 8-bit soft bits
+template <typename SrcT>
+struct EdgePosterior {
+  using type = SrcT;
+};
+template <>
+struct EdgePosterior<int8_t> {
+  using type = int16_t;
+};
 
 // parity of every row of the wavefront's chunk over `bit` (lane = edge): odd rows raise their first lane
 __device__ __forceinline__ bool chunk_has_odd_row(bool bit, uint32_t lane, uint32_t i, uint32_t d) {
@@ -244,7 +256,7 @@ __global__ __launch_bounds__(1024) void latency_edge_kernel(EdgeLatTables g, Edg
                                                    const SrcT *__restrict__ llrs, uint32_t input_len, uint32_t batch,
                                                    uint32_t max_iterations, uint8_t *__restrict__ bits,
                                                    uint32_t out_len, int32_t *__restrict__ iterations,
-                                                   SrcT *__restrict__ posterior, uint32_t *error_word,
+                                                   typename EdgePosterior<SrcT>::type *__restrict__ posterior, uint32_t *error_word,
                                                    uint32_t bundle, I8Opts o, MC... mc) {
   static_assert(is_corr_pack<T, MC...> && (sizeof...(MC) == 1) == (RULE == kRuleMinsumCorr), "mc goes with kRuleMinsumCorr");
   constexpr bool I8 = RULE == kRuleEdgeI8;
@@ -502,7 +514,7 @@ __global__ __launch_bounds__(1024) void latency_edge_kernel(EdgeLatTables g, Edg
           if (v < out_len) bits[size_t(cw0 + j) * out_len + v] = bit;
           // (8-bit: the soft output is the 8-bit LLR clip(llr), arithmetic.rs:651, 713-715)
           if constexpr (I8) {
-            if (posterior) posterior[size_t(cw0 + j) * n + v] = static_cast<SrcT>(i8_clip(val));
+            if (posterior) posterior[size_t(cw0 + j) * n + v] = static_cast<typename EdgePosterior<SrcT>::type>(i8_clip(val));
           } else {
             if (posterior) posterior[size_t(cw0 + j) * n + v] = static_cast<SrcT>(val);
           }

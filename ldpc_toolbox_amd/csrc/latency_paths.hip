@@ -35,11 +35,11 @@ struct DeviceDecoder::SmallBatchCall {
   void *d_post;
   uint32_t *o_err = nullptr;
 
-  SmallBatchCall(DeviceDecoder &dec, SmallBatchStaging &staging, const void *llrs_, bool llrs_f64, bool host, size_t batch_,
+  SmallBatchCall(DeviceDecoder &dec, SmallBatchStaging &staging, const void *llrs_, LlrType llrs_type, bool host, size_t batch_,
                  uint8_t *bits_, size_t out_len, int32_t *iterations_, void *posterior_)
       : d(dec), st(staging), host_pointers(host), batch(batch_), llrs(llrs_), bits(bits_), iterations(iterations_),
-        posterior(posterior_), in_bytes(batch_ * dec.input_len_ * (llrs_f64 ? 8 : 4)), bits_bytes(batch_ * out_len),
-        post_bytes(batch_ * dec.n_ * (llrs_f64 ? 8 : 4)), d_llrs(llrs_), d_bits(bits_), d_iters(iterations_), d_post(posterior_) {
+        posterior(posterior_), in_bytes(batch_ * dec.input_len_ * llr_bytes(llrs_type)), bits_bytes(batch_ * out_len),
+        post_bytes(batch_ * dec.n_ * posterior_bytes(llrs_type)), d_llrs(llrs_), d_bits(bits_), d_iters(iterations_), d_post(posterior_) {
     d.last_lanes_ = 1;
     d.last_group_ = batch;
     d.last_vn_records_.store(false, std::memory_order_relaxed);
@@ -62,13 +62,15 @@ struct DeviceDecoder::SmallBatchCall {
   // derives how many share an XCD at run time): the grid is what the device can hold at once of the kernel this handle
   // launches, for f32 and for f64 input -- 256 on an MI355X in SPX mode, fewer on a partitioned or smaller device --
   // and never more than 256.  Fewer than 8 cannot be co-resident in any useful number: the handle keeps the batched kernels.
-  int size_grid(const void *kernel_f32, const void *kernel_f64) {
+  // (kernel_i8: the 8-bit rules' third kernel, for rows of 8-bit soft bits; null for the float rules)
+  int size_grid(const void *kernel_f32, const void *kernel_f64, const void *kernel_i8 = nullptr) {
     if (st.grid != 0) return 0;
-    int cus = 0, per_cu_f = 0, per_cu_d = 0;
+    int cus = 0, per_cu_f = 0, per_cu_d = 0, per_cu_b = 0;
     hipError_t e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, d.device_);
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_f, kernel_f32, 1024, 0);
     if (e == hipSuccess) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_d, kernel_f64, 1024, 0);
-    const int resident = e == hipSuccess ? cus * std::min(per_cu_f, per_cu_d) : 0;
+    if (e == hipSuccess && kernel_i8) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_b, kernel_i8, 1024, 0);
+    const int resident = e == hipSuccess ? cus * std::min(std::min(per_cu_f, per_cu_d), kernel_i8 ? per_cu_b : per_cu_f) : 0;
     if (resident < 8) return retreat();
     st.grid = static_cast<uint32_t>(std::min(resident, 256));
     return 0;
@@ -115,13 +117,13 @@ struct DeviceDecoder::SmallBatchCall {
   }
 };
 
-int DeviceDecoder::decode_latency(const void *llrs, bool llrs_f64, bool host_pointers, size_t batch,
+int DeviceDecoder::decode_latency(const void *llrs, LlrType llrs_type, bool host_pointers, size_t batch,
                                   uint32_t max_iterations, uint8_t *bits, size_t out_len, int32_t *iterations,
                                   void *posterior, hipStream_t s) {
   std::lock_guard<std::mutex> one_at_a_time(g_latency_mutex);
   LatencyPath &lp = *lat_;
   const SlicedTables &tb = lp.tables;
-  SmallBatchCall call(*this, lp.staging, llrs, llrs_f64, host_pointers, batch, bits, out_len, iterations, posterior);
+  SmallBatchCall call(*this, lp.staging, llrs, llrs_type, host_pointers, batch, bits, out_len, iterations, posterior);
   const uint32_t n = static_cast<uint32_t>(n_), m = static_cast<uint32_t>(m_);
   if (!lp.uploaded) {
     hipError_t e = hipSuccess;
@@ -171,7 +173,7 @@ int DeviceDecoder::decode_latency(const void *llrs, bool llrs_f64, bool host_poi
       kernel<<<grid, 1024, 0, s>>>(t, lp.slots, d_sync, src, static_cast<uint32_t>(input_len_), static_cast<uint32_t>(batch),
                                    max_iterations, call.d_bits, static_cast<uint32_t>(out_len), call.d_iters, dst, call.o_err, c...);
     };
-    if (llrs_f64)
+    if (llrs_type == LlrType::F64)
       go(dev::latency_minsum_kernel<double, decltype(c)...>, static_cast<const double *>(call.d_llrs), static_cast<double *>(call.d_post));
     else
       go(dev::latency_minsum_kernel<float, decltype(c)...>, static_cast<const float *>(call.d_llrs), static_cast<float *>(call.d_post));
@@ -226,22 +228,26 @@ const void *edge_kernel_r(Rule rule, bool corrected, bool layered) {
   }
   return nullptr;  // (no such rule: the launch fails)
 }
-const void *edge_kernel(Rule rule, bool corrected, bool arith_i8, bool arith_f64, bool src_f64, bool layered) {
-  if (arith_i8)  // the rule (Minstarapprox / A-Min*) and its options are run-time arguments (dev::I8Opts)
+const void *edge_kernel(Rule rule, bool corrected, bool arith_i8, bool arith_f64, LlrType src, bool layered) {
+  const bool src_f64 = src == LlrType::F64;
+  if (arith_i8) {  // the rule (Minstarapprox / A-Min*) and its options are run-time arguments (dev::I8Opts)
+    if (src == LlrType::I8) return edge_kernel_s<dev::kRuleEdgeI8, int32_t, int8_t>(layered);
     return src_f64 ? edge_kernel_s<dev::kRuleEdgeI8, int32_t, double>(layered) : edge_kernel_s<dev::kRuleEdgeI8, int32_t, float>(layered);
+  }
+  if (src == LlrType::I8) return nullptr;  // (8-bit soft bits go to the 8-bit rules only: the launch fails)
   if (arith_f64)
     return src_f64 ? edge_kernel_r<double, double>(rule, corrected, layered) : edge_kernel_r<double, float>(rule, corrected, layered);
   return src_f64 ? edge_kernel_r<float, double>(rule, corrected, layered) : edge_kernel_r<float, float>(rule, corrected, layered);
 }
 }  // namespace
 
-int DeviceDecoder::decode_latency_edge(const void *llrs, bool llrs_f64, bool host_pointers, size_t batch,
+int DeviceDecoder::decode_latency_edge(const void *llrs, LlrType llrs_type, bool host_pointers, size_t batch,
                                           uint32_t max_iterations, uint8_t *bits, size_t out_len, int32_t *iterations,
                                           void *posterior, hipStream_t s) {
   std::lock_guard<std::mutex> one_at_a_time(g_latency_mutex);
   EdgeLatencyPath &lp = *lat_edge_;
   const EdgeLaneTables &tb = lp.tables;
-  SmallBatchCall call(*this, lp.staging, llrs, llrs_f64, host_pointers, batch, bits, out_len, iterations, posterior);
+  SmallBatchCall call(*this, lp.staging, llrs, llrs_type, host_pointers, batch, bits, out_len, iterations, posterior);
   const size_t elem = impl_.f64 ? 8 : 4;
   const bool corrected = impl_.correction != Correction::None;
   const uint32_t n = static_cast<uint32_t>(n_), m = static_cast<uint32_t>(m_);
@@ -268,8 +274,9 @@ int DeviceDecoder::decode_latency_edge(const void *llrs, bool llrs_f64, bool hos
     lp.uploaded = true;
   }
   // every workgroup of the persistent launch must be resident (see decode_latency)
-  if (int rc = call.size_grid(edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, false, tb.layered),
-                              edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, true, tb.layered)))
+  if (int rc = call.size_grid(edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, LlrType::F32, tb.layered),
+                              edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, LlrType::F64, tb.layered),
+                              impl_.i8 ? edge_kernel(impl_.rule, corrected, true, false, LlrType::I8, tb.layered) : nullptr))
     return rc;
   if (int rc = call.stage(EdgeLatencyPath::kPinnedGranule)) return rc;
   dev::LatencySync *d_sync = lp.sync.get<dev::LatencySync>();
@@ -288,7 +295,7 @@ int DeviceDecoder::decode_latency_edge(const void *llrs, bool llrs_f64, bool hos
   dev::MinsumCorr<double> mc_d{impl_.alpha(), impl_.beta()};
   void *args[] = {&t, &lp.slots, &d_sync, &call.d_llrs, &in_len, &nb, &max_iterations, &call.d_bits, &ol, &call.d_iters, &call.d_post,
                   &call.o_err, &bundle, &i8o, impl_.f64 ? static_cast<void *>(&mc_d) : static_cast<void *>(&mc_f)};
-  const void *kernel = edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, llrs_f64, tb.layered);
+  const void *kernel = edge_kernel(impl_.rule, corrected, impl_.i8, impl_.f64, llrs_type, tb.layered);
   if (kernel == nullptr) {
     fail("internal error: no small-batch kernel for this rule");
     return -3;

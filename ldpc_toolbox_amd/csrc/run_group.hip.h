@@ -99,7 +99,7 @@ int DeviceDecoder::run_group(Workspace &w, const GroupCall &call) {
             emit_blocks, emit_nbx, w.perm, w.slot_tmp, rest, fl, mv_t.sched.nchunks, mv_t.sched.waves_per_chunk);
       };
       auto with_out = [&](auto fw) {
-        if (call.llrs_f64)
+        if (call.llrs_type == LlrType::F64)
           retire_move(fw, static_cast<double *>(call.posterior));
         else
           retire_move(fw, static_cast<float *>(call.posterior));

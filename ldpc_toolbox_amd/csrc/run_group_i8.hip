@@ -25,7 +25,7 @@ int DeviceDecoder::run_group_i8(Workspace &w, const GroupCall &call) {
   const dev::I8MinsumOpts mo{impl_.hardlimit, impl_.correction == Correction::Normalized ? impl_.correction_int : 16,
                              impl_.correction == Correction::Offset ? impl_.correction_int : 0};
 
-  if (int rc = f.begin(dev::ingest_i8_kernel<float>, dev::ingest_i8_kernel<double>, chan, post)) return rc;
+  if (int rc = f.begin(dev::ingest_i8_kernel<float>, dev::ingest_i8_kernel<double>, chan, post, dev::ingest_i8_kernel<int8_t>)) return rc;
   const Tiling pack_t = make_tiling(G, tile, 128, n, 256, target_waves);
   auto pack = [&]() {
     dev::pack_hard_pair_kernel<int16_t><<<pack_t.blocks, pack_t.threads, 0, s>>>(post, w.hardbits, w.n_active, w.n_slots,

@@ -87,6 +87,11 @@ class Simulator {
     budget_valid_ = false;
   }
   uint64_t pooled_frames() const { return pooled_frames_; }
+  // "soft_bits": 32 (float soft buffers, the default) or 8 -- run_harq alone then keeps its soft buffers as 8-bit soft bits
+  // (include/ldpc_toolbox.h, PART 9).  false with nothing changed for any other value, and for 8 unless the decoder's
+  // implementation is one of the 8-bit names.
+  bool set_soft_bits(int64_t bits);
+  int soft_bits() const { return soft_bits_; }
   const std::vector<uint8_t> &messages() const { return messages_; }
   const std::vector<uint8_t> &tx_bits() const { return tx_bits_; }
   const std::string &last_error() const { return error_; }
@@ -114,6 +119,9 @@ class Simulator {
   // The frames through the HARQ sequence of set_harq (nr_harq.h), all on the device.  Every frame is decoded after each of
   // its transmissions with the full max_iterations (the straggler budget has no part here), on the soft buffer recovered
   // from all of them so far, and stops at the first attempt that converges -- right or wrong -- or after the last one.
+  // "soft_bits" 8: an attempt after transmission t is the generator's float row taken through Q, recovered on 8-bit soft
+  // bits with saturating sums into the frame's int8 soft row (combine = t > 0), and decoded by the 8-bit input entry; the
+  // stage pools hold [capacity][n] bytes.
   // The noise sigma is that of n_tx = E_0 for every transmission.  counters[6]: the fields of run() for each frame's
   // final attempt, the iterations summed over all its attempts (a failed one counts max_iterations).
   // per_tx[T][4], per transmission: attempts, frames that stopped because the attempt converged, of those with bit
@@ -195,6 +203,11 @@ class Simulator {
   };
   HarqStage harq_stage_[nrharq::kMaxTransmissions];
   DeviceBuffer d_harq_rx_, d_harq_bits_, d_harq_its_, d_harq_counts_, d_harq_per_tx_;
+  // "soft_bits" 8: the soft rows above are int8, and a generator's float rows (d_rx_ of stage 0, d_harq_rx_ of a flush) go
+  // through Q in a pass of their own into these receive buffers, which rate recovery reads
+  int soft_bits_ = 32;
+  DeviceBuffer d_rx_i8_, d_harq_rx_i8_;
+  void launch_quantize(const float *src, int8_t *dst, uint64_t total);
   size_t harq_cap_ = 0;
   uint64_t harq_flushes_[nrharq::kMaxTransmissions] = {}, harq_flushed_rows_[nrharq::kMaxTransmissions] = {};
   const char *harq_modulation_error() const;

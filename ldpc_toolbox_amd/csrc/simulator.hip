@@ -129,7 +129,7 @@ int Simulator::flush_pool(uint32_t count, uint64_t seed, uint32_t max_iterations
   // large for that is decoded in the chunks' group size, so that the decoder keeps the workspace it has -- a group
   // sized by the pool would free and re-allocate gigabytes before and after every flush)
   dec_->set_min_group(chunk_group);
-  const int drc = dec_->decode_device(d_pool_llrs_.get(), false, count, max_iterations, d_pool_bits_.get<uint8_t>(), k_,
+  const int drc = dec_->decode_device(d_pool_llrs_.get(), LlrType::F32, count, max_iterations, d_pool_bits_.get<uint8_t>(), k_,
                                       d_pool_its_.get<int32_t>(), nullptr, nullptr);
   dec_->set_min_group(0);
   if (drc) {
@@ -491,7 +491,7 @@ int Simulator::run_frames(double ebn0_db, uint64_t seed, uint64_t first_frame, s
     const uint32_t nf = static_cast<uint32_t>(std::min(chunk, frames - f0));
     launch_generator(ebn0_db, seed, first_frame + f0, nf);
     if (rate_match_) nr_rm_launch_recover<float>(rm_plan_, d_rx_.get<float>(), d_llrs_.get<float>(), nf, 0.0f, false, stream_);
-    if (int rc = dec_->decode_device(d_llrs_.get(), false, nf, budget, d_bits_.get<uint8_t>(), k_, d_its_.get<int32_t>(), nullptr, stream_)) {
+    if (int rc = dec_->decode_device(d_llrs_.get(), LlrType::F32, nf, budget, d_bits_.get<uint8_t>(), k_, d_its_.get<int32_t>(), nullptr, stream_)) {
       error_ = dec_->last_error();
       return rc;
     }
@@ -603,20 +603,34 @@ void Simulator::launch_harq_generator(double ebn0_db, uint64_t seed, uint32_t t,
                                                                                               first_frame, frame_ids, frames, sigma, scale, dst);
 }
 
+bool Simulator::set_soft_bits(int64_t bits) {
+  if (bits != 8 && bits != 32) return fail("soft_bits must be 8 or 32");
+  if (bits == 8 && !dec_->implementation().i8) return fail("soft_bits 8 needs one of the 8-bit implementations");
+  if (soft_bits_ != bits) harq_cap_ = 0;  // (the stage pools are laid out anew by the next run_harq call)
+  soft_bits_ = static_cast<int>(bits);
+  return true;
+}
+
+void Simulator::launch_quantize(const float *src, int8_t *dst, uint64_t total) {
+  gen::quantize_i8_kernel<<<static_cast<uint32_t>(((total + 3) / 4 + 255) / 256), 256, 0, stream_>>>(src, dst, total);
+}
+
 int Simulator::ensure_harq(size_t capacity) {
   const uint32_t T = harq_.t;
+  const size_t soft_elem = soft_bits_ == 8 ? sizeof(int8_t) : sizeof(float);
   uint32_t max_e = 1;
   for (uint32_t t = 1; t < T; t++) max_e = std::max(max_e, harq_.e[t]);
   SIM_TRY(d_harq_counts_.ensure(nrharq::kMaxTransmissions * sizeof(uint32_t)));
   SIM_TRY(d_harq_per_tx_.ensure(nrharq::kMaxTransmissions * 4 * sizeof(unsigned long long)));
   harq_cap_ = 0;
   for (uint32_t t = 1; t < T; t++) {
-    SIM_TRY(harq_stage_[t].soft.ensure(capacity * n_ * sizeof(float)));
+    SIM_TRY(harq_stage_[t].soft.ensure(capacity * n_ * soft_elem));
     SIM_TRY(harq_stage_[t].frames.ensure(capacity * sizeof(uint64_t)));
     SIM_TRY(harq_stage_[t].spent.ensure(capacity * sizeof(uint32_t)));
   }
   if (T > 1) {
     SIM_TRY(d_harq_rx_.ensure(capacity * max_e * sizeof(float)));
+    if (soft_bits_ == 8) SIM_TRY(d_harq_rx_i8_.ensure(capacity * max_e));
     SIM_TRY(d_harq_bits_.ensure(capacity * std::max<size_t>(k_, 1)));
     SIM_TRY(d_harq_its_.ensure(capacity * sizeof(int32_t)));
   }
@@ -633,19 +647,32 @@ int Simulator::flush_harq(uint32_t t, uint32_t count, double ebn0_db, uint64_t s
   HarqStage &st = harq_stage_[t];
   const bool last = t + 1 == harq_.t;
   uint32_t *counts = d_harq_counts_.get<uint32_t>();
+  const bool soft8 = soft_bits_ == 8;
+  const size_t soft_elem = soft8 ? sizeof(int8_t) : sizeof(float);
   launch_harq_generator(ebn0_db, seed, t, 0, st.frames.get<uint64_t>(), count, d_harq_rx_.get<float>());
-  nr_rm_launch_recover<float>(harq_plans_[t], d_harq_rx_.get<float>(), st.soft.get<float>(), count, 0.0f, true, stream_);
+  if (soft8) {
+    launch_quantize(d_harq_rx_.get<float>(), d_harq_rx_i8_.get<int8_t>(), uint64_t(count) * harq_.e[t]);
+    nr_rm_launch_recover_i8(harq_plans_[t], d_harq_rx_i8_.get<int8_t>(), st.soft.get<int8_t>(), count, soft::kSoftMax, true, stream_);
+  } else {
+    nr_rm_launch_recover<float>(harq_plans_[t], d_harq_rx_.get<float>(), st.soft.get<float>(), count, 0.0f, true, stream_);
+  }
   const size_t padded = (count + chunk - 1) / chunk * chunk;  // (at most the two chunks every pool has room for)
   if (padded > count)
-    SIM_TRY(hipMemsetAsync(st.soft.get<float>() + size_t(count) * n_, 0x41 /* every float 0x41414141 = +12.08 */,
-                           (padded - count) * n_ * sizeof(float), stream_));
+    SIM_TRY(hipMemsetAsync(st.soft.get<char>() + size_t(count) * n_ * soft_elem,
+                           0x41 /* every float 0x41414141 = +12.08, every soft bit +65 steps */, (padded - count) * n_ * soft_elem, stream_));
   for (size_t p0 = 0; p0 < padded; p0 += chunk)
-    if (int rc = dec_->decode_device(st.soft.get<float>() + p0 * n_, false, chunk, max_iterations, d_harq_bits_.get<uint8_t>() + p0 * k_, k_,
-                                     d_harq_its_.get<int32_t>() + p0, nullptr, stream_)) {
+    if (int rc = dec_->decode_device(st.soft.get<char>() + p0 * n_ * soft_elem, soft8 ? LlrType::I8 : LlrType::F32, chunk, max_iterations,
+                                     d_harq_bits_.get<uint8_t>() + p0 * k_, k_, d_harq_its_.get<int32_t>() + p0, nullptr, stream_)) {
       error_ = dec_->last_error();
       return rc;
     }
-  if (!last) {
+  if (!last && soft8) {
+    HarqStage &next = harq_stage_[t + 1];
+    gen::harq_collect_i8_kernel<<<(count * 64 + 255) / 256, 256, 0, stream_>>>(
+        d_harq_its_.get<int32_t>(), count, 0, st.frames.get<uint64_t>(), st.spent.get<uint32_t>(), max_iterations, st.soft.get<uint32_t>(),
+        static_cast<uint32_t>(n_ / 4), next.soft.get<uint32_t>(), next.frames.get<uint64_t>(), next.spent.get<uint32_t>(), counts + t + 1,
+        static_cast<uint32_t>(2 * chunk));
+  } else if (!last) {
     HarqStage &next = harq_stage_[t + 1];
     gen::harq_collect_kernel<<<(count * 64 + 255) / 256, 256, 0, stream_>>>(
         d_harq_its_.get<int32_t>(), count, 0, st.frames.get<uint64_t>(), st.spent.get<uint32_t>(), max_iterations, st.soft.get<float>(),
@@ -684,6 +711,9 @@ int Simulator::run_harq(double ebn0_db, uint64_t seed, uint64_t first_frame, siz
   SIM_TRY(hipSetDevice(device_));
   const size_t chunk = std::min<size_t>(frames, std::max<size_t>(dec_->preferred_group(frames), 4096));  // (as in run_frames)
   if (int rc = ensure(chunk, chunk)) return rc;
+  const bool soft8 = soft_bits_ == 8;
+  if (soft8 && n_ % 4 != 0) return refuse("soft_bits 8 needs a codeword length that is a multiple of 4");  // (every NR code's is)
+  if (soft8) SIM_TRY(d_rx_i8_.ensure(chunk * n_tx_));
   if (harq_cap_ < 2 * chunk)
     if (int rc = ensure_harq(2 * chunk)) return rc;
   const size_t cap = 2 * chunk;  // (of this call: an earlier one with larger chunks may have left larger buffers)
@@ -730,12 +760,23 @@ int Simulator::run_harq(double ebn0_db, uint64_t seed, uint64_t first_frame, siz
     const uint32_t nf = static_cast<uint32_t>(std::min(chunk, frames - f0));
     // stage 0: the first transmission is the frame of run() -- its generator, recovered with combine = 0
     launch_generator(ebn0_db, seed, first_frame + f0, nf);
-    nr_rm_launch_recover<float>(rm_plan_, d_rx_.get<float>(), d_llrs_.get<float>(), nf, 0.0f, false, stream_);
-    if (int rc = dec_->decode_device(d_llrs_.get(), false, nf, max_iterations, d_bits_.get<uint8_t>(), k_, d_its_.get<int32_t>(), nullptr, stream_)) {
+    if (soft8) {
+      launch_quantize(d_rx_.get<float>(), d_rx_i8_.get<int8_t>(), uint64_t(nf) * n_tx_);
+      nr_rm_launch_recover_i8(rm_plan_, d_rx_i8_.get<int8_t>(), d_llrs_.get<int8_t>(), nf, soft::kSoftMax, false, stream_);
+    } else {
+      nr_rm_launch_recover<float>(rm_plan_, d_rx_.get<float>(), d_llrs_.get<float>(), nf, 0.0f, false, stream_);
+    }
+    if (int rc = dec_->decode_device(d_llrs_.get(), soft8 ? LlrType::I8 : LlrType::F32, nf, max_iterations, d_bits_.get<uint8_t>(), k_,
+                                     d_its_.get<int32_t>(), nullptr, stream_)) {
       error_ = dec_->last_error();
       return rc;
     }
-    if (T > 1)
+    if (T > 1 && soft8)
+      gen::harq_collect_i8_kernel<<<(nf * 64 + 255) / 256, 256, 0, stream_>>>(
+          d_its_.get<int32_t>(), nf, first_frame + f0, nullptr, nullptr, max_iterations, d_llrs_.get<uint32_t>(), static_cast<uint32_t>(n_ / 4),
+          harq_stage_[1].soft.get<uint32_t>(), harq_stage_[1].frames.get<uint64_t>(), harq_stage_[1].spent.get<uint32_t>(), d_counts + 1,
+          static_cast<uint32_t>(cap));
+    else if (T > 1)
       gen::harq_collect_kernel<<<(nf * 64 + 255) / 256, 256, 0, stream_>>>(
           d_its_.get<int32_t>(), nf, first_frame + f0, nullptr, nullptr, max_iterations, d_llrs_.get<float>(), static_cast<uint32_t>(n_),
           harq_stage_[1].soft.get<float>(), harq_stage_[1].frames.get<uint64_t>(), harq_stage_[1].spent.get<uint32_t>(), d_counts + 1,

@@ -150,11 +150,14 @@ class LdpcDecoder:
     def decode_batch(self, llrs, max_iterations: int, output_len=None, want_posterior=False, out=None):
         """llrs [B][input_len] f32/f64 host array -> (bits [B][output_len] u8,
         iterations [B] i32 with -1 = failed, posterior [B][n] or None).
+        An int8 array holds 8-bit soft bits (1/8 of an LLR unit per step, -128 read as -127; the 8-bit implementations
+        only): the results are those of the rows clip(v) / 8 as float32, and the posterior is int16.
         out: (bits, iterations[, posterior]) arrays of those shapes to fill instead of fresh ones (a
         caller that decodes batch after batch reuses its buffers, as a C caller would)."""
         llrs = np.ascontiguousarray(llrs)
-        if llrs.dtype not in (np.float32, np.float64):
+        if llrs.dtype not in (np.float32, np.float64, np.int8):
             llrs = llrs.astype(np.float64)
+        post_dtype = np.int16 if llrs.dtype == np.int8 else llrs.dtype
         B, ln = llrs.shape
         output_len = self.n if output_len is None else output_len
         if out is not None:
@@ -162,16 +165,16 @@ class LdpcDecoder:
             post = out[2] if want_posterior else None
             ok = (bits.shape == (B, output_len) and bits.dtype == np.uint8 and bits.flags.c_contiguous
                   and its.shape == (B,) and its.dtype == np.int32 and its.flags.c_contiguous
-                  and (post is None or (post.shape == (B, self.n) and post.dtype == llrs.dtype and post.flags.c_contiguous)))
+                  and (post is None or (post.shape == (B, self.n) and post.dtype == post_dtype and post.flags.c_contiguous)))
             if not ok:
                 raise ValueError("out arrays do not match the batch")
         else:
             bits = np.zeros((B, output_len), dtype=np.uint8)
             its = np.zeros(B, dtype=np.int32)
-            post = np.zeros((B, self.n), dtype=llrs.dtype) if want_posterior else None
+            post = np.zeros((B, self.n), dtype=post_dtype) if want_posterior else None
         L = _capi.lib()
-        fn = (L.ldpc_toolbox_decoder_decode_batch_f32 if llrs.dtype == np.float32
-              else L.ldpc_toolbox_decoder_decode_batch_f64)
+        fn = {np.dtype(np.float32): L.ldpc_toolbox_decoder_decode_batch_f32, np.dtype(np.float64): L.ldpc_toolbox_decoder_decode_batch_f64,
+              np.dtype(np.int8): L.ldpc_toolbox_decoder_decode_batch_i8}[llrs.dtype]
         rc = fn(self._h, bits.ctypes.data, output_len, llrs.ctypes.data, ln, B, max_iterations,
                 its.ctypes.data, post.ctypes.data if want_posterior else None)
         if rc != 0:
@@ -180,10 +183,11 @@ class LdpcDecoder:
 
     def decode_batch_device(self, llrs_ptr: int, f64: bool, batch: int, max_iterations: int,
                             bits_ptr: int, output_len: int, iterations_ptr: int = 0,
-                            posterior_ptr: int = 0, stream: int = 0):
-        """Raw device pointers (e.g. torch tensors' data_ptr()); stream = hipStream_t handle or 0."""
+                            posterior_ptr: int = 0, stream: int = 0, i8: bool = False):
+        """Raw device pointers (e.g. torch tensors' data_ptr()); stream = hipStream_t handle or 0.  i8: the rows are 8-bit
+        soft bits (int8, any byte address) and the posterior int16; the 8-bit implementations only."""
         L = _capi.lib()
-        fn = (L.ldpc_toolbox_decoder_decode_batch_f64_device if f64
+        fn = (L.ldpc_toolbox_decoder_decode_batch_i8_device if i8 else L.ldpc_toolbox_decoder_decode_batch_f64_device if f64
               else L.ldpc_toolbox_decoder_decode_batch_f32_device)
         rc = fn(self._h, bits_ptr, output_len, llrs_ptr, self.input_len, batch, max_iterations,
                 iterations_ptr or None, posterior_ptr or None, stream or None)
@@ -451,7 +455,11 @@ class Simulator:
         return int(v.value)
 
     def set(self, key, value):
+        """"soft_bits": 8 keeps `run_harq`'s soft buffers as 8-bit soft bits (an 8-bit implementation only; ValueError and
+        nothing changed otherwise), 32 (the default) as floats."""
         if _capi.lib().ldpc_toolbox_sim_set(self._h, key.encode(), int(value)) != 0:
+            if key == "soft_bits":
+                raise ValueError(_capi.last_error() or "cannot set soft_bits")
             raise KeyError(key)
 
     def run(self, ebn0_db, seed, first_frame, frames, max_iterations, bch_max_errors: int = 0):

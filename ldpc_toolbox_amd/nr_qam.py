@@ -111,6 +111,31 @@ class NrQam:
         if rc != 0:
             self._raise("demodulate_device", rc)
 
+    def demap_i8(self, symbols, sigma, max_log: bool = False, c_init: int = -1):
+        """symbols [batch][symbols_len] complex64 host array -> 8-bit soft bits [batch][QM * symbols_len] int8: each the
+        float32 LLR of `demodulate` quantised (round-half-away(8 x) clamped to +-127), in one kernel."""
+        symbols = np.asarray(symbols)
+        if symbols.ndim != 2:
+            raise ValueError("symbols must be [batch][symbols_len]")
+        symbols = np.ascontiguousarray(symbols, dtype=np.complex64)
+        B, S = symbols.shape
+        n = S * self.bits_per_symbol
+        out = np.zeros((B, n), dtype=np.int8)
+        rc = _capi.lib().ldpc_toolbox_nr_demap_i8(self._h, out.ctypes.data, n, symbols.ctypes.data, S, B, float(sigma), int(bool(max_log)),
+                                                  int(c_init))
+        if rc != 0:
+            self._raise("demap_i8", rc)
+        return out
+
+    def demap_i8_device(self, sym_ptr: int, out_ptr: int, batch: int, symbols_len: int, sigma, max_log: bool = False, c_init: int = -1,
+                        stream: int = 0):
+        """Raw device pointers: float symbols [batch][symbols_len] -> int8 soft bits [batch][QM * symbols_len]; stream as in
+        `modulate_device`.  The symbol buffer must be aligned to one (re, im) pair; the output may be any byte address."""
+        rc = _capi.lib().ldpc_toolbox_nr_demap_i8_device(self._h, out_ptr, symbols_len * self.bits_per_symbol, sym_ptr, symbols_len, batch,
+                                                         float(sigma), int(bool(max_log)), int(c_init), stream or None)
+        if rc != 0:
+            self._raise("demap_i8_device", rc)
+
     def close(self):
         if getattr(self, "_h", None):
             _capi.lib().ldpc_toolbox_nr_qam_dtor(self._h)

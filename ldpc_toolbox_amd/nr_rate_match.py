@@ -101,6 +101,37 @@ class NrRateMatcher:
         if rc != 0:
             self._raise("recover_device", rc)
 
+    def recover_i8(self, rx, rv: int = 0, qm: int = 1, filler: int = 127, into=None):
+        """rx [batch][e] int8 host array of 8-bit soft bits (-128 read as -127) -> soft bits [batch][n] int8: per column the
+        saturating sum (to +-127) of its repeats in transmitted order, 0 for a column that was not sent, `filler` (1 .. 127)
+        for a filler column.  into: a C-contiguous int8 [batch][n] array holding the soft buffer of earlier transmissions;
+        this one is combined into it with saturation and the array returned."""
+        rx = np.ascontiguousarray(rx)
+        if rx.dtype != np.int8 or rx.ndim != 2:
+            raise ValueError("rx must be an int8 array [batch][e]")
+        B, e = rx.shape
+        n = self.n
+        if into is None:
+            out = np.zeros((B, n), dtype=np.int8)
+        else:
+            out = into
+            if not (isinstance(out, np.ndarray) and out.flags.c_contiguous and out.flags.writeable and out.dtype == np.int8
+                    and out.shape == (B, n)):
+                raise ValueError("into must be a writable C-contiguous int8 [batch][n] array")
+        rc = _capi.lib().ldpc_toolbox_nr_rm_recover_i8(self._h, out.ctypes.data, n, rx.ctypes.data, e, B, int(rv), int(qm), int(filler),
+                                                       int(into is not None))
+        if rc != 0:
+            self._raise("recover_i8", rc)
+        return out
+
+    def recover_i8_device(self, rx_ptr: int, llrs_ptr: int, batch: int, e: int, rv: int = 0, qm: int = 1, filler: int = 127,
+                          combine: bool = False, stream: int = 0, n=None):
+        """Raw device pointers, any byte addresses: rx [batch][e] -> llrs [batch][n], int8; combine: combine into llrs."""
+        rc = _capi.lib().ldpc_toolbox_nr_rm_recover_i8_device(self._h, llrs_ptr, self.n if n is None else n, rx_ptr, int(e), batch, int(rv),
+                                                              int(qm), int(filler), int(bool(combine)), stream or None)
+        if rc != 0:
+            self._raise("recover_i8_device", rc)
+
     def close(self):
         if getattr(self, "_h", None):
             _capi.lib().ldpc_toolbox_nr_rm_dtor(self._h)
