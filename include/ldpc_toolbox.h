@@ -402,6 +402,30 @@ int32_t ldpc_toolbox_awgn_run_f32_device(void *demod, float *symbols, size_t sym
                                          uint64_t seed, uint64_t first_frame, void *hip_stream);
 int32_t ldpc_toolbox_awgn_run_f64_device(void *demod, double *symbols, size_t symbols_len, size_t batch, double noise_sigma,
                                          uint64_t seed, uint64_t first_frame, void *hip_stream);
+/* Rayleigh block fading with perfect CSI behind a one-tap equaliser, in place on symbols [batch][symbols_len], writing scale
+ * [batch][symbols_len]: what ldpc_toolbox_nr_demap_csi_* (PART 10) takes.  Row r is frame first_frame + r.  The received
+ * h x + sigma z, divided by h, is x + sigma z / h; the phase of h does not change the law of z / h, so only a = |h| is drawn.
+ * Per frame f and symbol s, with q = s / block:
+ *   (w0, w1) = the normal pair above with key seed ^ 0x9E3779B97F4A7C15, frame f, pair q: one gain per `block` consecutive
+ *     symbols of a frame, from another stream than the noise's; block >= symbols_len is quasi-static fading;
+ *   gf = 0.5f * (w0 * w0 + w1 * w1), af = sqrtf(gf), in float, each operation rounded once (af > 0: w0^2 + w1^2 = -2 ln s
+ *     with 0 < s < 1; the mean of af^2 is 1, so noise_sigma keeps its meaning as the average Eb/N0);
+ *   sigma_e = noise_sigma / (double)af, scale_s = 1.0 / (sigma_e * sigma_e), in double, each operation rounded once (no f64
+ *     square root);
+ *   (z0, z1) = the AWGN channel's pair: key seed, frame f, pair s.
+ *   _f64: re += sigma_e * (double)z0, im += sigma_e * (double)z1, scale[s] = scale_s.
+ *   _f32: re += (float)sigma_e * z0, im += (float)sigma_e * z1, scale[s] = (float)scale_s.
+ * Complex handles only: a "BPSK" handle, noise_sigma not finite or not > 0, block == 0, symbols_len > 0x7fffffff, a null
+ * handle or buffer: LDPC_TOOLBOX_ERR_ARGUMENT before the GPU is touched, nothing written.  A device symbol buffer is aligned
+ * to one (re, im) pair, a device scale buffer to its element.  Other behaviour as ldpc_toolbox_awgn_run_*. */
+int32_t ldpc_toolbox_fading_run_f32(void *demod, float *symbols, float *scale, size_t symbols_len, size_t batch, double noise_sigma,
+                                    uint32_t block, uint64_t seed, uint64_t first_frame);
+int32_t ldpc_toolbox_fading_run_f64(void *demod, double *symbols, double *scale, size_t symbols_len, size_t batch, double noise_sigma,
+                                    uint32_t block, uint64_t seed, uint64_t first_frame);
+int32_t ldpc_toolbox_fading_run_f32_device(void *demod, float *symbols, float *scale, size_t symbols_len, size_t batch,
+                                           double noise_sigma, uint32_t block, uint64_t seed, uint64_t first_frame, void *hip_stream);
+int32_t ldpc_toolbox_fading_run_f64_device(void *demod, double *symbols, double *scale, size_t symbols_len, size_t batch,
+                                           double noise_sigma, uint32_t block, uint64_t seed, uint64_t first_frame, void *hip_stream);
 /* key: "bits_per_symbol", "points", "energy_term", "device" (-1 until the first run made the device state).
  * returns 0, or -1 for an unknown key. */
 int32_t ldpc_toolbox_demod_get(void *demod, const char *key, int64_t *value);
@@ -813,6 +837,58 @@ int32_t ldpc_toolbox_nr_rm_recover_i8_device(void *rm, int8_t *llrs, size_t n, c
  * harq_rows_t keys are those of the float run.  The stage pools hold [capacity][n] bytes, a quarter of the float ones; the
  * generators still write floats, which a pass of its own quantises into the int8 receive buffer recovery reads.  With 32
  * every launch and result is what it was. */
+
+/* ===================================================================================
+ * PART 10 -- the NR demapper with a scale per symbol (channel state information, CSI), and the simulator over the Rayleigh
+ * block-fading channel of PART 4.  After the one-tap equaliser of an OFDM receiver every resource element has its own
+ * noise variance; the demapper weights each symbol by it in the one pass it makes.  The reference has none of it.
+ * Each entry has a host form and a _device form with a trailing hipStream_t; streams and synchronisation are those of the
+ * PART 8 / PART 9 entries.
+ * =================================================================================== */
+
+/* The demapper of PART 8 (qam: a handle of ldpc_toolbox_nr_qam_ctor) with scale [batch][symbols_len] in place of noise_sigma:
+ * one value per symbol, 1 / sigma_s^2 with sigma_s^2 that symbol's noise variance per real coordinate after equalisation.
+ * Everything is PART 8's arithmetic with the symbol's own s (its scale value converted to the arithmetic type A) where
+ * PART 8 has the call's scale:  sx = x * s,  K_u = (0.5 * s) * Q_u,  d_u = sx * A_u - K_u,  with Q_u = A_u * A_u made on the
+ * host in double and rounded once to A, as the A_u are.  0.5 * s is exact; every other product and difference is rounded
+ * once; K_u is the same for both axes.  The folds, the bit order, the descrambling sign and the arithmetic types are PART
+ * 8's: _f64 double throughout; _f32 exact = symbol and scale widened to double, each LLR rounded once; _f32 max_log = float
+ * throughout; _i8 = Q (PART 9) of the float that the _f32 entry writes, the float row never stored.
+ * Where A is double and every s equals the double 1.0 / (sigma * sigma), the output is bit for bit that of the PART 8 entry
+ * with noise_sigma = sigma -- (0.5 * scale) * (A_u * A_u) is the expression that entry's table is made of: _f64 with either
+ * fold step, and exact _f32 when that double is also a float.  For max_log _f32 the K_u are float products, not rounded
+ * doubles, and no such identity holds.
+ * The scale values are used as given and are not checked, on the host or on the device: with finite symbols s = 0 gives
+ * LLRs of magnitude 0 (an erased symbol); a negative, infinite or NaN scale gives what the arithmetic gives.
+ * The refusals are PART 8's (PART 9's for _i8) without the sigma test, and a null scale: LDPC_TOOLBOX_ERR_ARGUMENT before the
+ * GPU is touched, nothing written.  Device buffers: the symbol and LLR rules of those entries; scale needs the alignment of
+ * its element only. */
+int32_t ldpc_toolbox_nr_demap_csi_f32(void *qam, float *llrs, size_t llrs_len, const float *symbols, const float *scale, size_t symbols_len,
+                                      size_t batch, int32_t max_log, int64_t c_init);
+int32_t ldpc_toolbox_nr_demap_csi_f64(void *qam, double *llrs, size_t llrs_len, const double *symbols, const double *scale,
+                                      size_t symbols_len, size_t batch, int32_t max_log, int64_t c_init);
+int32_t ldpc_toolbox_nr_demap_csi_i8(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, const float *scale, size_t symbols_len,
+                                     size_t batch, int32_t max_log, int64_t c_init);
+int32_t ldpc_toolbox_nr_demap_csi_f32_device(void *qam, float *llrs, size_t llrs_len, const float *symbols, const float *scale,
+                                             size_t symbols_len, size_t batch, int32_t max_log, int64_t c_init, void *hip_stream);
+int32_t ldpc_toolbox_nr_demap_csi_f64_device(void *qam, double *llrs, size_t llrs_len, const double *symbols, const double *scale,
+                                             size_t symbols_len, size_t batch, int32_t max_log, int64_t c_init, void *hip_stream);
+int32_t ldpc_toolbox_nr_demap_csi_i8_device(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, const float *scale,
+                                            size_t symbols_len, size_t batch, int32_t max_log, int64_t c_init, void *hip_stream);
+
+/* The simulator's channel: the key "fading_block" of ldpc_toolbox_sim_set takes 0 (none, the default) up to 0x7fffffff, the
+ * symbols per gain; ldpc_toolbox_sim_get reports it.  Within that range the setter always succeeds (outside it: -1 with a
+ * message, nothing changed), and it resets the straggler-pooling budget as "modulation" does.  While it is not 0, a call to
+ * run, run_bch, generate, run_harq or generate_harq without an NR modulation in force (ldpc_toolbox_sim_set_nr_qam) is
+ * refused: -1 with a message, the counters untouched -- the run, not the setter.
+ * DEFINED RESULT with fading_block B != 0: the LLRs of frame f are what ldpc_toolbox_nr_qam_mod_f64 (c_init -1) of the frame's
+ * pooled transmitted row, then ldpc_toolbox_fading_run_f64 (the run's seed, frame f, noise_sigma, block B), then
+ * ldpc_toolbox_nr_demap_csi_f64 on those symbols and that scale (the simulator's max_log, c_init -1) give, each value rounded
+ * once to float, in transmitted order.  A HARQ process's concatenated row goes through the same channel: symbol s of
+ * transmission t has index first_symbol + s, as in PART 6's simulator, and takes noise pair first_symbol + s and gain pair
+ * (first_symbol + s) / B.  One fused kernel per generator, one thread per symbol; symbols and scales are never stored.
+ * With "soft_bits" 8, run_harq stays the composition PART 9 defines over generate_harq; the counters stay independent of
+ * chunking and of "pooling".  With 0 every launch and result is what it was. */
 
 /* Standard-code generator (what the reference's `dvbs2` / `5g` / `ccsds` / `ccsds-c2` CLI
  * sub-commands print, src/cli/dvbs2.rs:91, src/cli/nr5g.rs:46, src/cli/ccsds.rs:70): writes the

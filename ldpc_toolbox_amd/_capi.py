@@ -61,6 +61,10 @@ SYMBOLS = [
     "ldpc_toolbox_awgn_run_f64",
     "ldpc_toolbox_awgn_run_f32_device",
     "ldpc_toolbox_awgn_run_f64_device",
+    "ldpc_toolbox_fading_run_f32",
+    "ldpc_toolbox_fading_run_f64",
+    "ldpc_toolbox_fading_run_f32_device",
+    "ldpc_toolbox_fading_run_f64_device",
     "ldpc_toolbox_demod_get",
     "ldpc_toolbox_bch_ctor",
     "ldpc_toolbox_bch_dtor",
@@ -119,6 +123,12 @@ SYMBOLS = [
     "ldpc_toolbox_nr_demap_i8_device",
     "ldpc_toolbox_nr_rm_recover_i8",
     "ldpc_toolbox_nr_rm_recover_i8_device",
+    "ldpc_toolbox_nr_demap_csi_f32",
+    "ldpc_toolbox_nr_demap_csi_f64",
+    "ldpc_toolbox_nr_demap_csi_i8",
+    "ldpc_toolbox_nr_demap_csi_f32_device",
+    "ldpc_toolbox_nr_demap_csi_f64_device",
+    "ldpc_toolbox_nr_demap_csi_i8_device",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
     "ldpc_toolbox_device_count",
@@ -281,6 +291,12 @@ def lib():
         f = getattr(L, "ldpc_toolbox_awgn_run_" + name + "_device")
         f.restype = i32
         f.argtypes = [vp, vp, sz, sz, C.c_double, u64, u64, vp]
+        f = getattr(L, "ldpc_toolbox_fading_run_" + name)
+        f.restype = i32
+        f.argtypes = [vp, vp, vp, sz, sz, C.c_double, u32, u64, u64]
+        f = getattr(L, "ldpc_toolbox_fading_run_" + name + "_device")
+        f.restype = i32
+        f.argtypes = [vp, vp, vp, sz, sz, C.c_double, u32, u64, u64, vp]
     L.ldpc_toolbox_demod_get.restype = i32
     L.ldpc_toolbox_demod_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
     L.ldpc_toolbox_bch_ctor.restype = vp
@@ -389,6 +405,14 @@ def lib():
     L.ldpc_toolbox_nr_rm_recover_i8.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32, i32, i32]
     L.ldpc_toolbox_nr_rm_recover_i8_device.restype = i32
     L.ldpc_toolbox_nr_rm_recover_i8_device.argtypes = [vp, vp, sz, vp, sz, sz, u32, u32, i32, i32, vp]
+    # the demapper with a scale per symbol (PART 10): the scalar entries' order, a scale pointer behind the symbols, no sigma
+    for name in ("f32", "f64", "i8"):
+        f = getattr(L, "ldpc_toolbox_nr_demap_csi_" + name)
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, vp, sz, sz, i32, C.c_int64]
+        f = getattr(L, "ldpc_toolbox_nr_demap_csi_" + name + "_device")
+        f.restype = i32
+        f.argtypes = [vp, vp, sz, vp, vp, sz, sz, i32, C.c_int64, vp]
     L.ldpc_toolbox_code_alist.restype = sz
     L.ldpc_toolbox_code_alist.argtypes = [cp, vp, sz]
     L.ldpc_toolbox_alist_normalize.restype = sz

@@ -201,6 +201,8 @@ def format_details(a, sim, world: int) -> str:
         lines.append(f" - Modulation: {a.modulation}")
     if getattr(a, "max_log", False):
         lines.append(" - Demodulator: max-log")
+    if getattr(a, "nr_fading_block", 0):                                              # this build's addition
+        lines.append(f" - Fading: Rayleigh block fading with perfect CSI, {a.nr_fading_block} symbols per block")
     lines += ["LDPC code:", f" - alist: {a.alist if a.alist else a.code}"]
     if a.puncturing:
         lines.append(f" - Puncturing pattern: {a.puncturing}")
@@ -235,6 +237,11 @@ def main(argv=None):
                     help="instead of --modulation / --constellation: the 5G NR mapping of TS 38.211 5.1.3-5.1.6 with QM = 2, 4, 6 "
                          "or 8 bits per symbol (QPSK, 16QAM, 64QAM, 256QAM) and its per-axis demapper; no --interleaving "
                          "(NR's bit interleaver is --nr-rate-match's QM)")
+    ap.add_argument("--nr-fading-block", type=int, default=0, metavar="B",
+                    help="with --nr-qam: Rayleigh block fading with perfect CSI behind a one-tap equaliser instead of AWGN, one "
+                         "gain per B consecutive symbols of a frame (B at least the symbols of a frame: quasi-static; with "
+                         "--nr-harq the blocks run on over the transmissions); the demapper weights every symbol by its own "
+                         "noise variance, and Eb/N0 is the average over the fading")
     ap.add_argument("--max-log", action="store_true", help="max-log demapper (with QPSK, --constellation or --nr-qam)")
     ap.add_argument("--interleaving", type=int, default=0,
                     help="interleaver columns, negative = read rows backwards (cli/ber.rs:55-59)")
@@ -305,6 +312,10 @@ def main(argv=None):
         ap.error("--bch-code names one code: it cannot be combined with --codes")
     if a.nr_qam and (a.codes or a.modulation != "BPSK" or a.constellation or a.interleaving):
         ap.error("--nr-qam cannot be combined with --codes, --modulation, --constellation or a non-zero --interleaving")
+    if a.nr_fading_block and not a.nr_qam:
+        ap.error("--nr-fading-block needs --nr-qam")
+    if not 0 <= a.nr_fading_block <= 0x7fffffff:
+        ap.error("--nr-fading-block takes 1 .. 2^31 - 1 symbols")
     rate_match = None
     if a.nr_rate_match:
         if a.codes or not (a.code or "").startswith("nr5g:") or a.puncturing:
@@ -391,6 +402,8 @@ def main(argv=None):
         except ValueError as e:
             ap.error(f"--nr-qam {a.nr_qam}: {e}")
         qam.close()
+        if a.nr_fading_block:
+            sim.set("fading_block", a.nr_fading_block)
     if harq:                                                      # (after the modulation: every E is checked against it)
         e0, rv0, qm = rate_match + [0, 1][len(rate_match) - 1:]
         try:

@@ -345,6 +345,29 @@ int32_t awgn_run(void *demod, void *symbols, size_t symbols_len, size_t batch, b
   return LDPC_TOOLBOX_ERR_DEVICE;
 }
 
+int32_t fading_run(void *demod, void *symbols, void *scale, size_t symbols_len, size_t batch, bool f64, double sigma, uint32_t block,
+                   uint64_t seed, uint64_t first_frame, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto refuse = [](const char *why) {
+    set_error(why);
+    return LDPC_TOOLBOX_ERR_ARGUMENT;
+  };
+  auto *h = static_cast<DemodHandle *>(demod);
+  if (!h) return refuse("null demodulator handle");
+  if (const char *why = ldpc::fading_argument_error(h->c, symbols_len, sigma, block)) return refuse(why);
+  if (batch == 0 || symbols_len == 0) return 0;
+  if (!symbols || !scale) return refuse("null symbol or scale buffer");
+  if (on_device)
+    if (const char *why = ldpc::fading_pointer_error(symbols, scale, f64)) return refuse(why);
+  if (int32_t rc = demod_device_state(h)) return rc;
+  const int rc = on_device ? h->dev->fading_device(symbols, scale, f64, symbols_len, batch, sigma, block, seed, first_frame,
+                                                   static_cast<hipStream_t>(stream))
+                           : h->dev->fading_host(symbols, scale, f64, symbols_len, batch, sigma, block, seed, first_frame);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
 // 0 with the handle's device state made, or LDPC_TOOLBOX_ERR_DEVICE
 int32_t nr_qam_device_state(NrQamHandle *h) {
   if (h->dev) return 0;
@@ -417,6 +440,36 @@ int32_t nr_demap_i8(void *qam, int8_t *llrs, size_t llrs_len, const float *symbo
   const int rc = on_device ? h->dev->demap_i8_device(symbols, llrs, symbols_len, llrs_len, batch, sigma, max_log != 0, c_init,
                                                      static_cast<hipStream_t>(stream))
                            : h->dev->demap_i8_host(symbols, llrs, symbols_len, llrs_len, batch, sigma, max_log != 0, c_init);
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+// the demappers with a scale per symbol (PART 10); out_elem: the bytes of one LLR -- 8 (double symbols), 4, or 1 (the 8-bit form)
+int32_t nr_demap_csi(void *qam, void *llrs, size_t llrs_len, const void *symbols, const void *scale, size_t symbols_len, size_t batch,
+                     size_t out_elem, int32_t max_log, int64_t c_init, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrQamHandle *>(qam);
+  if (!h) return nr_qam_refuse("null NR modulation handle");
+  if (const char *why = ldpc::nrqam::demap_csi_argument_error(h->c, llrs_len, symbols_len, c_init)) return nr_qam_refuse(why);
+  if (batch == 0 || llrs_len == 0) return 0;
+  if (!symbols || !llrs) return nr_qam_refuse("null symbol or LLR buffer");
+  if (!scale) return nr_qam_refuse("null scale buffer");
+  const bool f64 = out_elem == 8;
+  if (on_device) {  // (the soft bits of the 8-bit form leave in pieces chosen from their address)
+    if (const char *why = ldpc::nrqam::device_pointer_error(symbols, out_elem == 1 ? nullptr : llrs, f64)) return nr_qam_refuse(why);
+    if (const char *why = ldpc::nrqam::scale_pointer_error(scale, f64)) return nr_qam_refuse(why);
+  }
+  if (int32_t rc = nr_qam_device_state(h)) return rc;
+  auto *st = static_cast<hipStream_t>(stream);
+  int rc;
+  if (!on_device)
+    rc = h->dev->demap_csi_host(symbols, scale, llrs, out_elem, symbols_len, llrs_len, batch, max_log != 0, c_init);
+  else if (out_elem == 1)
+    rc = h->dev->demap_csi_i8_device(static_cast<const float *>(symbols), static_cast<const float *>(scale), static_cast<int8_t *>(llrs),
+                                     symbols_len, llrs_len, batch, max_log != 0, c_init, st);
+  else
+    rc = h->dev->demap_csi_device(symbols, scale, llrs, f64, symbols_len, llrs_len, batch, max_log != 0, c_init, st);
   if (rc == 0) return 0;
   set_error(h->dev->last_error());
   return LDPC_TOOLBOX_ERR_DEVICE;
@@ -1161,6 +1214,8 @@ int32_t ldpc_toolbox_sim_get(void *sim, const char *key, int64_t *value) {
     *value = static_cast<int64_t>(s->harq_flushed_rows(k[11] - '0'));
   else if (k == "streamed_frames" || k == "stream_iterations")  // (continuous batching: profiles/r03_continuous_batching.txt)
     *value = 0;
+  else if (k == "fading_block")  // symbols per gain of the Rayleigh block-fading channel, 0 = none (PART 10)
+    *value = s->fading_block();
   else if (k == "soft_bits")  // 32, or 8: run_harq keeps its soft buffers as 8-bit soft bits (PART 9)
     *value = s->soft_bits();
   else if (k == "pooled_frames")  // frames of the last run() call that went through the straggler pool
@@ -1187,6 +1242,12 @@ int32_t ldpc_toolbox_sim_set(void *sim, const char *key, int64_t value) {
   if (k == "soft_bits") {  // 8 (the 8-bit implementations only) or 32
     g_last_error.clear();
     const bool ok = s->set_soft_bits(value);
+    if (!ok) set_error(s->last_error());
+    return ok ? 0 : -1;
+  }
+  if (k == "fading_block") {  // 0 (none) .. 0x7fffffff symbols per gain
+    g_last_error.clear();
+    const bool ok = s->set_fading_block(value);
     if (!ok) set_error(s->last_error());
     return ok ? 0 : -1;
   }
@@ -1312,6 +1373,26 @@ int32_t ldpc_toolbox_awgn_run_f32_device(void *demod, float *symbols, size_t sym
 int32_t ldpc_toolbox_awgn_run_f64_device(void *demod, double *symbols, size_t symbols_len, size_t batch, double noise_sigma,
                                          uint64_t seed, uint64_t first_frame, void *hip_stream) {
   return awgn_run(demod, symbols, symbols_len, batch, true, noise_sigma, seed, first_frame, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_fading_run_f32(void *demod, float *symbols, float *scale, size_t symbols_len, size_t batch, double noise_sigma,
+                                    uint32_t block, uint64_t seed, uint64_t first_frame) {
+  return fading_run(demod, symbols, scale, symbols_len, batch, false, noise_sigma, block, seed, first_frame, false, nullptr);
+}
+
+int32_t ldpc_toolbox_fading_run_f64(void *demod, double *symbols, double *scale, size_t symbols_len, size_t batch, double noise_sigma,
+                                    uint32_t block, uint64_t seed, uint64_t first_frame) {
+  return fading_run(demod, symbols, scale, symbols_len, batch, true, noise_sigma, block, seed, first_frame, false, nullptr);
+}
+
+int32_t ldpc_toolbox_fading_run_f32_device(void *demod, float *symbols, float *scale, size_t symbols_len, size_t batch, double noise_sigma,
+                                           uint32_t block, uint64_t seed, uint64_t first_frame, void *hip_stream) {
+  return fading_run(demod, symbols, scale, symbols_len, batch, false, noise_sigma, block, seed, first_frame, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_fading_run_f64_device(void *demod, double *symbols, double *scale, size_t symbols_len, size_t batch, double noise_sigma,
+                                           uint32_t block, uint64_t seed, uint64_t first_frame, void *hip_stream) {
+  return fading_run(demod, symbols, scale, symbols_len, batch, true, noise_sigma, block, seed, first_frame, true, hip_stream);
 }
 
 int32_t ldpc_toolbox_demod_get(void *demod, const char *key, int64_t *value) {
@@ -1809,6 +1890,38 @@ int32_t ldpc_toolbox_nr_rm_recover_i8(void *rm, int8_t *llrs, size_t n, const in
 int32_t ldpc_toolbox_nr_rm_recover_i8_device(void *rm, int8_t *llrs, size_t n, const int8_t *rx, size_t e, size_t batch, uint32_t rv,
                                              uint32_t qm, int32_t filler, int32_t combine, void *hip_stream) {
   return nr_rm_recover_i8(rm, llrs, n, rx, e, batch, rv, qm, filler, combine, true, hip_stream);
+}
+
+// ---- PART 10: the NR demapper with a scale per symbol ----------------------------------------------------
+
+int32_t ldpc_toolbox_nr_demap_csi_f32(void *qam, float *llrs, size_t llrs_len, const float *symbols, const float *scale, size_t symbols_len,
+                                      size_t batch, int32_t max_log, int64_t c_init) {
+  return nr_demap_csi(qam, llrs, llrs_len, symbols, scale, symbols_len, batch, 4, max_log, c_init, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_demap_csi_f64(void *qam, double *llrs, size_t llrs_len, const double *symbols, const double *scale,
+                                      size_t symbols_len, size_t batch, int32_t max_log, int64_t c_init) {
+  return nr_demap_csi(qam, llrs, llrs_len, symbols, scale, symbols_len, batch, 8, max_log, c_init, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_demap_csi_i8(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, const float *scale, size_t symbols_len,
+                                     size_t batch, int32_t max_log, int64_t c_init) {
+  return nr_demap_csi(qam, llrs, llrs_len, symbols, scale, symbols_len, batch, 1, max_log, c_init, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_demap_csi_f32_device(void *qam, float *llrs, size_t llrs_len, const float *symbols, const float *scale,
+                                             size_t symbols_len, size_t batch, int32_t max_log, int64_t c_init, void *hip_stream) {
+  return nr_demap_csi(qam, llrs, llrs_len, symbols, scale, symbols_len, batch, 4, max_log, c_init, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_demap_csi_f64_device(void *qam, double *llrs, size_t llrs_len, const double *symbols, const double *scale,
+                                             size_t symbols_len, size_t batch, int32_t max_log, int64_t c_init, void *hip_stream) {
+  return nr_demap_csi(qam, llrs, llrs_len, symbols, scale, symbols_len, batch, 8, max_log, c_init, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_demap_csi_i8_device(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, const float *scale,
+                                            size_t symbols_len, size_t batch, int32_t max_log, int64_t c_init, void *hip_stream) {
+  return nr_demap_csi(qam, llrs, llrs_len, symbols, scale, symbols_len, batch, 1, max_log, c_init, true, hip_stream);
 }
 
 // ---- code tables and utilities ------------------------------------------------------------------------

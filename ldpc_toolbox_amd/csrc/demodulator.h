@@ -25,6 +25,11 @@
 //   * AWGN, in place, row r = frame first_frame + r: symbol s gets (z0, z1) = gen::normal_pair(seed, frame, s),
 //     re += sigma * z0, im += sigma * z1; BPSK position j uses pair j / 2, z0 for even j and z1 for odd j (the keying of
 //     gen::awgn_llr_kernel).  f64: x + sigma * (double)z.  f32: x + (float)sigma * z.  Each product and sum rounded once.
+//   * Rayleigh block fading with perfect CSI behind a one-tap equaliser, in place, complex symbols only: the received
+//     h x + sigma z divided by h is x + sigma z / h, and the phase of h does not change the law of z / h, so only a = |h| is
+//     drawn: one gain per `block` consecutive symbols of a frame (gen::fading_scale: af, sigma_e = sigma / af, scale =
+//     1 / sigma_e^2).  Symbol s gets the AWGN channel's pair at sigma_e, and scale[s] -- what the NR demapper with a scale per
+//     symbol takes.  f64: x + sigma_e * (double)z.  f32: x + (float)sigma_e * z, scale rounded once to float.
 #pragma once
 #include <hip/hip_runtime_api.h>
 
@@ -129,6 +134,22 @@ inline const char *awgn_argument_error(size_t symbols_len, double sigma) {
   return nullptr;
 }
 
+// ... and for a fading call (complex handles only): symbols and scale [batch][symbols_len], one gain per `block` symbols
+inline const char *fading_argument_error(const Constellation &c, size_t symbols_len, double sigma, uint32_t block) {
+  if (c.bpsk) return "the fading channel takes complex symbols, not a BPSK handle's reals";
+  if (symbols_len > 0x7fffffffu) return "frame length out of range for the channel";
+  if (!(std::isfinite(sigma) && sigma > 0.0)) return "noise_sigma must be finite and greater than 0";
+  if (block == 0) return "the fading block must be at least one symbol";
+  return nullptr;
+}
+
+// its device buffers: a symbol is one (re, im) load and store, a scale one scalar store
+inline const char *fading_pointer_error(const void *symbols, const void *scale, bool f64) {
+  if (reinterpret_cast<uintptr_t>(symbols) % (f64 ? 16 : 8) != 0) return "the symbol buffer is not aligned to one (re, im) pair";
+  if (reinterpret_cast<uintptr_t>(scale) % (f64 ? 8 : 4) != 0) return "the scale buffer is not aligned to its element";
+  return nullptr;
+}
+
 // mean symbol energy of a table: sum_V |p_V|^2 / 2^m (BPSK: 1)
 inline double mean_energy(const Constellation &c) {
   if (c.bpsk) return 1.0;
@@ -178,6 +199,11 @@ class DeviceDemodulator {
   int awgn_device(void *symbols, bool f64, size_t symbols_len, size_t batch, double sigma, uint64_t seed, uint64_t first_frame,
                   hipStream_t stream);
   int awgn_host(void *symbols, bool f64, size_t symbols_len, size_t batch, double sigma, uint64_t seed, uint64_t first_frame);
+  // Rayleigh block fading in place on symbols [batch][symbols_len], writing scale [batch][symbols_len] (fading_argument_error)
+  int fading_device(void *symbols, void *scale, bool f64, size_t symbols_len, size_t batch, double sigma, uint32_t block, uint64_t seed,
+                    uint64_t first_frame, hipStream_t stream);
+  int fading_host(void *symbols, void *scale, bool f64, size_t symbols_len, size_t batch, double sigma, uint32_t block, uint64_t seed,
+                  uint64_t first_frame);
 
  private:
   DeviceDemodulator() = default;

@@ -201,6 +201,17 @@ void awgn_launch(const Constellation &c, T *symbols, size_t symbols_len, size_t 
                                                                            static_cast<T>(sigma), seed, first_frame + b0);
   });
 }
+
+template <typename T>
+void fading_launch(T *symbols, T *scale, size_t symbols_len, size_t batch, double sigma, uint32_t block, uint64_t seed,
+                   uint64_t first_frame, hipStream_t s) {
+  const uint32_t sl = static_cast<uint32_t>(symbols_len);
+  channel_passes(batch, symbols_len, [&](size_t b0, size_t frames) {
+    const uint64_t total = uint64_t(frames) * symbols_len;
+    chan::fading_kernel<T><<<channel_blocks(total), chan::kThreads, 0, s>>>(symbols + 2 * b0 * symbols_len, scale + b0 * symbols_len, sl,
+                                                                           total, sigma, block, seed, first_frame + b0);
+  });
+}
 }  // namespace
 
 int DeviceDemodulator::mod_device(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch,
@@ -250,6 +261,33 @@ int DeviceDemodulator::awgn_host(void *symbols, bool f64, size_t symbols_len, si
   DEMOD_TRY(hipMemcpyAsync(d_in_.get(), symbols, bytes, hipMemcpyHostToDevice, stream_));
   if (int rc = awgn_device(d_in_.get(), f64, symbols_len, batch, sigma, seed, first_frame, stream_)) return rc;
   DEMOD_TRY(hipMemcpyAsync(symbols, d_in_.get(), bytes, hipMemcpyDeviceToHost, stream_));
+  DEMOD_TRY(hipStreamSynchronize(stream_));
+  return 0;
+}
+
+int DeviceDemodulator::fading_device(void *symbols, void *scale, bool f64, size_t symbols_len, size_t batch, double sigma, uint32_t block,
+                                     uint64_t seed, uint64_t first_frame, hipStream_t stream) {
+  if (batch == 0 || symbols_len == 0) return 0;
+  hipStream_t s;
+  if (int rc = begin(stream, &s)) return rc;
+  if (f64)
+    fading_launch(static_cast<double *>(symbols), static_cast<double *>(scale), symbols_len, batch, sigma, block, seed, first_frame, s);
+  else
+    fading_launch(static_cast<float *>(symbols), static_cast<float *>(scale), symbols_len, batch, sigma, block, seed, first_frame, s);
+  return end(stream, s);
+}
+
+int DeviceDemodulator::fading_host(void *symbols, void *scale, bool f64, size_t symbols_len, size_t batch, double sigma, uint32_t block,
+                                   uint64_t seed, uint64_t first_frame) {
+  if (batch == 0 || symbols_len == 0) return 0;
+  DEMOD_TRY(hipSetDevice(device_));
+  const size_t scale_bytes = batch * symbols_len * (f64 ? 8 : 4), bytes = 2 * scale_bytes;
+  DEMOD_TRY(d_in_.ensure(bytes, 256));
+  DEMOD_TRY(d_out_.ensure(scale_bytes, 256));
+  DEMOD_TRY(hipMemcpyAsync(d_in_.get(), symbols, bytes, hipMemcpyHostToDevice, stream_));
+  if (int rc = fading_device(d_in_.get(), d_out_.get(), f64, symbols_len, batch, sigma, block, seed, first_frame, stream_)) return rc;
+  DEMOD_TRY(hipMemcpyAsync(symbols, d_in_.get(), bytes, hipMemcpyDeviceToHost, stream_));
+  DEMOD_TRY(hipMemcpyAsync(scale, d_out_.get(), scale_bytes, hipMemcpyDeviceToHost, stream_));
   DEMOD_TRY(hipStreamSynchronize(stream_));
   return 0;
 }

@@ -13,16 +13,17 @@
 namespace ldpc {
 
 // The simulator's fused generator (nrqam::qam_llr_kernel), enqueued on `s`: frames [first_frame, first_frame + frames) of
-// pooled transmitted rows tx [pool][n_tx] -> llrs [frames][n_tx] in transmitted order.
+// pooled transmitted rows tx [pool][n_tx] -> llrs [frames][n_tx] in transmitted order.  fading_block: 0 = AWGN, else the
+// Rayleigh block-fading channel with one gain per that many symbols and the demapper with a scale per symbol.
 void nr_qam_launch_generator(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t n_tx, uint64_t seed,
-                             uint64_t first_frame, uint32_t frames, double sigma, float *llrs, hipStream_t s);
+                             uint64_t first_frame, uint32_t frames, double sigma, uint32_t fading_block, float *llrs, hipStream_t s);
 
 // One transmission of a HARQ sequence (nrqam::qam_llr_harq_kernel; nr_harq.h): tx [pool][e] are that transmission's pooled
 // rows, row r of llrs [frames][e] is frame frame_ids[r] (a device array), or first_frame + r when it is nullptr, and
-// symbol s takes the normal pair first_symbol + s.
+// symbol s takes the normal pair first_symbol + s -- and, with a fading_block, the gain of block (first_symbol + s) / fading_block.
 void nr_qam_launch_harq_generator(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t e, uint32_t first_symbol,
                                   uint64_t seed, uint64_t first_frame, const uint64_t *frame_ids, uint32_t frames, double sigma,
-                                  float *llrs, hipStream_t s);
+                                  uint32_t fading_block, float *llrs, hipStream_t s);
 
 class DeviceNrQam {
  public:
@@ -51,6 +52,15 @@ class DeviceNrQam {
                       int64_t c_init, hipStream_t stream);
   int demap_i8_host(const float *symbols, int8_t *llrs, size_t symbols_len, size_t llrs_len, size_t batch, double sigma, bool max_log,
                     int64_t c_init);
+  // The demappers with a scale per symbol (include/ldpc_toolbox.h, PART 10; nrqam::demap_csi_argument_error): scale
+  // [batch][symbols_len] in the symbols' type, s = 1 / sigma_s^2 of each symbol, used as given.
+  int demap_csi_device(const void *symbols, const void *scale, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch,
+                       bool max_log, int64_t c_init, hipStream_t stream);
+  int demap_csi_i8_device(const float *symbols, const float *scale, int8_t *llrs, size_t symbols_len, size_t llrs_len, size_t batch,
+                          bool max_log, int64_t c_init, hipStream_t stream);
+  // out_elem: the bytes of one LLR: 8 (double symbols), 4, or 1 (the 8-bit form)
+  int demap_csi_host(const void *symbols, const void *scale, void *llrs, size_t out_elem, size_t symbols_len, size_t llrs_len, size_t batch,
+                     bool max_log, int64_t c_init);
   // Host pointers: staged through device buffers of the handle, synchronous.
   int mod_host(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch, int64_t c_init);
   int demod_host(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
@@ -83,7 +93,7 @@ class DeviceNrQam {
   size_t gold_len_ = 0;
   uint64_t sequence_launches_ = 0;
   DeviceBuffer d_gold_;
-  DeviceBuffer d_in_, d_out_;  // the staging buffers of the host entries
+  DeviceBuffer d_in_, d_out_, d_scale_;  // the staging buffers of the host entries
 };
 
 }  // namespace ldpc

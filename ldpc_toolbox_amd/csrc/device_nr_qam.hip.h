@@ -66,6 +66,17 @@ nrqam::Axis<A> nr_qam_axis(const nrqam::Config &c, double scale) {
   return t;
 }
 
+// the table of the demappers with a scale per symbol: A_u and Q_u = A_u * A_u, made in double and rounded once to A
+template <typename A>
+nrqam::AxisCsi<A> nr_qam_axis_csi(const nrqam::Config &c) {
+  nrqam::AxisCsi<A> t;
+  for (uint32_t u = 0; u < nrqam::kMaxLevels; u++) {
+    t.amp[u] = static_cast<A>(c.amp[u]);
+    t.q[u] = static_cast<A>(c.amp[u] * c.amp[u]);
+  }
+  return t;
+}
+
 // passes of whole frames whose thread count fits a 31-bit grid: fn(first frame of the pass, its frames)
 template <typename F>
 void nr_qam_passes(size_t batch, size_t symbols_len, F fn) {
@@ -169,56 +180,152 @@ void nr_qam_demap_i8(const nrqam::Config &cfg, const float *symbols, int8_t *llr
   });
 }
 
+// ---- the demappers with a scale per symbol (PART 10): scale [batch][symbols_len] beside the symbols ----
+
+template <int H, typename IO, typename A, bool MAXLOG>
+void nr_qam_demap_csi_pass(const nrqam::Config &cfg, const IO *symbols, const IO *scale, IO *llrs, uint32_t symbols_len, uint64_t total,
+                           const uint32_t *c, hipStream_t s) {
+  nrqam::demap_csi_kernel<H, IO, A, MAXLOG><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(symbols, scale, llrs, symbols_len, total, c,
+                                                                                            nr_qam_axis_csi<A>(cfg));
+}
+
+template <typename IO, typename A, bool MAXLOG>
+void nr_qam_demap_csi_h(const nrqam::Config &cfg, const IO *symbols, const IO *scale, IO *llrs, uint32_t symbols_len, uint64_t total,
+                        const uint32_t *c, hipStream_t s) {
+  switch (cfg.h()) {
+    case 1: return nr_qam_demap_csi_pass<1, IO, A, MAXLOG>(cfg, symbols, scale, llrs, symbols_len, total, c, s);
+    case 2: return nr_qam_demap_csi_pass<2, IO, A, MAXLOG>(cfg, symbols, scale, llrs, symbols_len, total, c, s);
+    case 3: return nr_qam_demap_csi_pass<3, IO, A, MAXLOG>(cfg, symbols, scale, llrs, symbols_len, total, c, s);
+    default: return nr_qam_demap_csi_pass<4, IO, A, MAXLOG>(cfg, symbols, scale, llrs, symbols_len, total, c, s);
+  }
+}
+
+// the arithmetic types of nr_qam_demap
+template <typename IO>
+void nr_qam_demap_csi(const nrqam::Config &cfg, const IO *symbols, const IO *scale, IO *llrs, size_t symbols_len, size_t batch,
+                      bool max_log, const uint32_t *c, hipStream_t s) {
+  const uint32_t sl = static_cast<uint32_t>(symbols_len);
+  nr_qam_passes(batch, symbols_len, [&](size_t b0, size_t frames) {
+    const uint64_t total = uint64_t(frames) * symbols_len;
+    const IO *in = symbols + 2 * b0 * symbols_len, *sc = scale + b0 * symbols_len;
+    IO *out = llrs + b0 * symbols_len * cfg.qm;
+    if (max_log)
+      nr_qam_demap_csi_h<IO, IO, true>(cfg, in, sc, out, sl, total, c, s);
+    else
+      nr_qam_demap_csi_h<IO, double, false>(cfg, in, sc, out, sl, total, c, s);
+  });
+}
+
+// the piece width from the address of each pass's first row, as in nr_qam_demap_i8_pass
+template <int H>
+void nr_qam_demap_csi_i8_pass(const nrqam::Config &cfg, const float *symbols, const float *scale, int8_t *llrs, uint32_t symbols_len,
+                              uint64_t total, bool max_log, const uint32_t *c, hipStream_t s) {
+  auto go = [&](auto wide) {
+    constexpr bool kWide = decltype(wide)::value;
+    if (max_log)
+      nrqam::demap_csi_i8_kernel<H, float, true, kWide><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(symbols, scale, llrs, symbols_len, total,
+                                                                                                        c, nr_qam_axis_csi<float>(cfg));
+    else
+      nrqam::demap_csi_i8_kernel<H, double, false, kWide><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(symbols, scale, llrs, symbols_len,
+                                                                                                          total, c, nr_qam_axis_csi<double>(cfg));
+  };
+  if (reinterpret_cast<uintptr_t>(llrs) % 4 == 0)
+    go(std::true_type{});
+  else
+    go(std::false_type{});
+}
+
+void nr_qam_demap_csi_i8(const nrqam::Config &cfg, const float *symbols, const float *scale, int8_t *llrs, size_t symbols_len, size_t batch,
+                         bool max_log, const uint32_t *c, hipStream_t s) {
+  const uint32_t sl = static_cast<uint32_t>(symbols_len);
+  nr_qam_passes(batch, symbols_len, [&](size_t b0, size_t frames) {
+    const uint64_t total = uint64_t(frames) * symbols_len;
+    const float *in = symbols + 2 * b0 * symbols_len, *sc = scale + b0 * symbols_len;
+    int8_t *out = llrs + b0 * symbols_len * cfg.qm;
+    switch (cfg.h()) {
+      case 1: return nr_qam_demap_csi_i8_pass<1>(cfg, in, sc, out, sl, total, max_log, c, s);
+      case 2: return nr_qam_demap_csi_i8_pass<2>(cfg, in, sc, out, sl, total, max_log, c, s);
+      case 3: return nr_qam_demap_csi_i8_pass<3>(cfg, in, sc, out, sl, total, max_log, c, s);
+      default: return nr_qam_demap_csi_i8_pass<4>(cfg, in, sc, out, sl, total, max_log, c, s);
+    }
+  });
+}
+
+// fading_block != 0: the Rayleigh block-fading form, the table holding Q_u for the symbol's own scale
 template <int H>
 void nr_qam_generator_pass(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t n_tx, uint64_t seed,
-                           uint64_t first_frame, uint64_t total, double sigma, float *llrs, hipStream_t s) {
+                           uint64_t first_frame, uint64_t total, double sigma, uint32_t fading_block, float *llrs, hipStream_t s) {
   const double scale = 1.0 / (sigma * sigma);
+  auto go = [&](auto ml, auto fading, const auto &t) {
+    nrqam::qam_llr_kernel<H, decltype(ml)::value, decltype(fading)::value><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(
+        tx, pool, n_tx, seed, first_frame, total, sigma, scale, c.a, t, llrs, fading_block);
+  };
+  if (fading_block != 0) {
+    const nrqam::AxisCsi<double> t = nr_qam_axis_csi<double>(c);
+    if (max_log)
+      go(std::true_type{}, std::true_type{}, t);
+    else
+      go(std::false_type{}, std::true_type{}, t);
+    return;
+  }
   const nrqam::Axis<double> t = nr_qam_axis<double>(c, scale);
   if (max_log)
-    nrqam::qam_llr_kernel<H, true><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(tx, pool, n_tx, seed, first_frame, total, sigma, scale,
-                                                                                   c.a, t, llrs);
+    go(std::true_type{}, std::false_type{}, t);
   else
-    nrqam::qam_llr_kernel<H, false><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(tx, pool, n_tx, seed, first_frame, total, sigma, scale,
-                                                                                    c.a, t, llrs);
+    go(std::false_type{}, std::false_type{}, t);
 }
 }  // namespace
 
 void nr_qam_launch_generator(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t n_tx, uint64_t seed,
-                             uint64_t first_frame, uint32_t frames, double sigma, float *llrs, hipStream_t s) {
+                             uint64_t first_frame, uint32_t frames, double sigma, uint32_t fading_block, float *llrs, hipStream_t s) {
   const uint64_t total = uint64_t(frames) * (n_tx / c.qm);
   switch (c.h()) {
-    case 1: return nr_qam_generator_pass<1>(c, max_log, tx, pool, n_tx, seed, first_frame, total, sigma, llrs, s);
-    case 2: return nr_qam_generator_pass<2>(c, max_log, tx, pool, n_tx, seed, first_frame, total, sigma, llrs, s);
-    case 3: return nr_qam_generator_pass<3>(c, max_log, tx, pool, n_tx, seed, first_frame, total, sigma, llrs, s);
-    default: return nr_qam_generator_pass<4>(c, max_log, tx, pool, n_tx, seed, first_frame, total, sigma, llrs, s);
+    case 1: return nr_qam_generator_pass<1>(c, max_log, tx, pool, n_tx, seed, first_frame, total, sigma, fading_block, llrs, s);
+    case 2: return nr_qam_generator_pass<2>(c, max_log, tx, pool, n_tx, seed, first_frame, total, sigma, fading_block, llrs, s);
+    case 3: return nr_qam_generator_pass<3>(c, max_log, tx, pool, n_tx, seed, first_frame, total, sigma, fading_block, llrs, s);
+    default: return nr_qam_generator_pass<4>(c, max_log, tx, pool, n_tx, seed, first_frame, total, sigma, fading_block, llrs, s);
   }
 }
 
 namespace {
 template <int H>
 void nr_qam_harq_generator_pass(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t e, uint32_t first_symbol,
-                                uint64_t seed, uint64_t first_frame, const uint64_t *frame_ids, uint64_t total, double sigma, float *llrs,
-                                hipStream_t s) {
+                                uint64_t seed, uint64_t first_frame, const uint64_t *frame_ids, uint64_t total, double sigma,
+                                uint32_t fading_block, float *llrs, hipStream_t s) {
   const double scale = 1.0 / (sigma * sigma);
+  auto go = [&](auto ml, auto fading, const auto &t) {
+    nrqam::qam_llr_harq_kernel<H, decltype(ml)::value, decltype(fading)::value><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(
+        tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, scale, c.a, t, llrs, fading_block);
+  };
+  if (fading_block != 0) {
+    const nrqam::AxisCsi<double> t = nr_qam_axis_csi<double>(c);
+    if (max_log)
+      go(std::true_type{}, std::true_type{}, t);
+    else
+      go(std::false_type{}, std::true_type{}, t);
+    return;
+  }
   const nrqam::Axis<double> t = nr_qam_axis<double>(c, scale);
   if (max_log)
-    nrqam::qam_llr_harq_kernel<H, true><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(tx, pool, e, first_symbol, seed, first_frame,
-                                                                                        frame_ids, total, sigma, scale, c.a, t, llrs);
+    go(std::true_type{}, std::false_type{}, t);
   else
-    nrqam::qam_llr_harq_kernel<H, false><<<nr_qam_blocks(total), nrqam::kThreads, 0, s>>>(tx, pool, e, first_symbol, seed, first_frame,
-                                                                                         frame_ids, total, sigma, scale, c.a, t, llrs);
+    go(std::false_type{}, std::false_type{}, t);
 }
 }  // namespace
 
 void nr_qam_launch_harq_generator(const nrqam::Config &c, bool max_log, const uint8_t *tx, uint32_t pool, uint32_t e, uint32_t first_symbol,
                                   uint64_t seed, uint64_t first_frame, const uint64_t *frame_ids, uint32_t frames, double sigma,
-                                  float *llrs, hipStream_t s) {
+                                  uint32_t fading_block, float *llrs, hipStream_t s) {
   const uint64_t total = uint64_t(frames) * (e / c.qm);
   switch (c.h()) {
-    case 1: return nr_qam_harq_generator_pass<1>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, llrs, s);
-    case 2: return nr_qam_harq_generator_pass<2>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, llrs, s);
-    case 3: return nr_qam_harq_generator_pass<3>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, llrs, s);
-    default: return nr_qam_harq_generator_pass<4>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, llrs, s);
+    case 1:
+      return nr_qam_harq_generator_pass<1>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, fading_block, llrs, s);
+    case 2:
+      return nr_qam_harq_generator_pass<2>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, fading_block, llrs, s);
+    case 3:
+      return nr_qam_harq_generator_pass<3>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, fading_block, llrs, s);
+    default:
+      return nr_qam_harq_generator_pass<4>(c, max_log, tx, pool, e, first_symbol, seed, first_frame, frame_ids, total, sigma, fading_block, llrs, s);
   }
 }
 
@@ -321,6 +428,56 @@ int DeviceNrQam::demap_i8_host(const float *symbols, int8_t *llrs, size_t symbol
   NRQAM_TRY(d_out_.ensure(out_bytes, 256));
   NRQAM_TRY(hipMemcpyAsync(d_in_.get(), symbols, in_bytes, hipMemcpyHostToDevice, stream_));
   if (int rc = demap_i8_device(d_in_.get<float>(), d_out_.get<int8_t>(), symbols_len, llrs_len, batch, sigma, max_log, c_init, stream_)) return rc;
+  NRQAM_TRY(hipMemcpyAsync(llrs, d_out_.get(), out_bytes, hipMemcpyDeviceToHost, stream_));
+  NRQAM_TRY(hipStreamSynchronize(stream_));
+  return 0;
+}
+
+int DeviceNrQam::demap_csi_device(const void *symbols, const void *scale, void *llrs, bool f64, size_t symbols_len, size_t llrs_len,
+                                  size_t batch, bool max_log, int64_t c_init, hipStream_t stream) {
+  if (batch == 0 || llrs_len == 0) return 0;
+  hipStream_t s;
+  if (int rc = begin(stream, &s)) return rc;
+  const uint32_t *c;
+  if (int rc = sequence(c_init, llrs_len, s, &c)) return rc;
+  if (f64)
+    nr_qam_demap_csi(c_, static_cast<const double *>(symbols), static_cast<const double *>(scale), static_cast<double *>(llrs), symbols_len,
+                     batch, max_log, c, s);
+  else
+    nr_qam_demap_csi(c_, static_cast<const float *>(symbols), static_cast<const float *>(scale), static_cast<float *>(llrs), symbols_len, batch,
+                     max_log, c, s);
+  return end(stream, s, c != nullptr);
+}
+
+int DeviceNrQam::demap_csi_i8_device(const float *symbols, const float *scale, int8_t *llrs, size_t symbols_len, size_t llrs_len, size_t batch,
+                                     bool max_log, int64_t c_init, hipStream_t stream) {
+  if (batch == 0 || llrs_len == 0) return 0;
+  hipStream_t s;
+  if (int rc = begin(stream, &s)) return rc;
+  const uint32_t *c;
+  if (int rc = sequence(c_init, llrs_len, s, &c)) return rc;
+  nr_qam_demap_csi_i8(c_, symbols, scale, llrs, symbols_len, batch, max_log, c, s);
+  return end(stream, s, c != nullptr);
+}
+
+// out_elem: the bytes of one LLR -- 8, 4, or 1 for the 8-bit form (float symbols)
+int DeviceNrQam::demap_csi_host(const void *symbols, const void *scale, void *llrs, size_t out_elem, size_t symbols_len, size_t llrs_len,
+                                size_t batch, bool max_log, int64_t c_init) {
+  if (batch == 0 || llrs_len == 0) return 0;
+  NRQAM_TRY(hipSetDevice(device_));
+  const size_t elem = out_elem == 8 ? 8 : 4;
+  const size_t in_bytes = batch * symbols_len * 2 * elem, scale_bytes = batch * symbols_len * elem, out_bytes = batch * llrs_len * out_elem;
+  NRQAM_TRY(d_in_.ensure(in_bytes, 256));
+  NRQAM_TRY(d_scale_.ensure(scale_bytes, 256));
+  NRQAM_TRY(d_out_.ensure(out_bytes, 256));
+  NRQAM_TRY(hipMemcpyAsync(d_in_.get(), symbols, in_bytes, hipMemcpyHostToDevice, stream_));
+  NRQAM_TRY(hipMemcpyAsync(d_scale_.get(), scale, scale_bytes, hipMemcpyHostToDevice, stream_));
+  const int rc = out_elem == 1 ? demap_csi_i8_device(d_in_.get<float>(), d_scale_.get<float>(), d_out_.get<int8_t>(), symbols_len, llrs_len,
+                                                     batch, max_log, c_init, stream_)
+                               : demap_csi_device(d_in_.get(), d_scale_.get(), d_out_.get(), out_elem == 8, symbols_len, llrs_len, batch,
+                                                  max_log, c_init, stream_);
+  if (rc) return rc;
+  // (the only write to the caller's buffer: after an earlier failure nothing has been written)
   NRQAM_TRY(hipMemcpyAsync(llrs, d_out_.get(), out_bytes, hipMemcpyDeviceToHost, stream_));
   NRQAM_TRY(hipStreamSynchronize(stream_));
   return 0;

@@ -71,6 +71,21 @@ GEN_FN void normal_pair(uint64_t seed, uint64_t frame, uint32_t pair, float *z0,
   }
 }
 
+// Rayleigh block fading with perfect CSI behind a one-tap equaliser (include/ldpc_toolbox.h, PART 4): the gain of block
+// `block_index` of frame `frame` is af = sqrtf(0.5f * (w0^2 + w1^2)) of a normal pair keyed apart from the noise's; a symbol
+// of the block then sees the noise sigma_e = sigma / af and the demapper's scale 1 / sigma_e^2.  af > 0: w0^2 + w1^2 =
+// -2 ln s with 0 < s < 1.  No f64 square root; each operation rounded once.
+constexpr uint64_t kFadingKey = 0x9E3779B97F4A7C15ull;
+
+GEN_FN void fading_scale(uint64_t seed, uint64_t frame, uint32_t block_index, double sigma, double *sigma_e, double *scale) {
+  float w0, w1;
+  normal_pair(seed ^ kFadingKey, frame, block_index, &w0, &w1);
+  const float gf = 0.5f * (w0 * w0 + w1 * w1);
+  const float af = __builtin_sqrtf(gf);
+  *sigma_e = sigma / static_cast<double>(af);
+  *scale = 1.0 / (*sigma_e * *sigma_e);
+}
+
 // which pooled codeword frame `frame` transmits
 GEN_FN uint32_t pool_index(uint64_t seed, uint64_t frame, uint32_t pool) {
   uint32_t c[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, uint32_t(frame), uint32_t(frame >> 32)};

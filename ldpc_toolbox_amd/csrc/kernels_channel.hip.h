@@ -1,5 +1,5 @@
 // Kernels of the transmit side of a constellation handle (demodulator.h has the definitions): the batched modulator,
-// the AWGN channel, and the simulator's fused generator for any table constellation.  One thread per symbol, indexed by
+// the AWGN and the Rayleigh block-fading channel, and the simulator's fused generator for any table constellation.  One thread per symbol, indexed by
 // a 64-bit id.  Compiled with -ffp-contract=off: sigma * z and x + (sigma * z) are rounded once each.
 //
 // In the demapper the point index V is wave-uniform and the table is read from the kernel arguments with scalar loads.
@@ -106,6 +106,31 @@ __global__ __launch_bounds__(kThreads) void awgn_real_kernel(T *__restrict__ sym
   const uint32_t j = 2 * pair;
   row[j] = row[j] + sigma * static_cast<T>(z0);
   if (j + 1 < symbols_len) row[j + 1] = row[j + 1] + sigma * static_cast<T>(z1);
+}
+
+// Rayleigh block fading behind a one-tap equaliser, in place: symbol s of row r gets the noise pair (seed, first_frame + r, s)
+// of awgn_kernel at sigma_e = sigma / af, af the gain of its block s / block (gen::fading_scale), and scale[s] = 1 / sigma_e^2:
+// what the CSI demapper takes.  A wave's lanes mostly share a block; each lane computes the gain for itself -- a Philox
+// block and a logf beside the ones its noise pair costs, and no LDS or cross-lane traffic.  One (re, im) load and store.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void fading_kernel(T *__restrict__ symbols, T *__restrict__ scale, uint32_t symbols_len,
+                                                          uint64_t total, double sigma, uint32_t block, uint64_t seed,
+                                                          uint64_t first_frame) {
+  typedef T pair __attribute__((ext_vector_type(2)));
+  const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (id >= total) return;
+  const uint64_t f = id / symbols_len;
+  const uint32_t sym = static_cast<uint32_t>(id - f * symbols_len);
+  double sigma_e, scale_s;
+  gen::fading_scale(seed, first_frame + f, sym / block, sigma, &sigma_e, &scale_s);
+  float z0, z1;
+  gen::normal_pair(seed, first_frame + f, sym, &z0, &z1);
+  const T se = static_cast<T>(sigma_e);
+  pair p = *reinterpret_cast<const pair *>(symbols + 2 * id);
+  p.x = p.x + se * static_cast<T>(z0);
+  p.y = p.y + se * static_cast<T>(z1);
+  *reinterpret_cast<pair *>(symbols + 2 * id) = p;
+  scale[id] = static_cast<T>(scale_s);
 }
 
 // The simulator's generator for a table constellation of M bits, fused: pooled codeword -> the M bits of the symbol at

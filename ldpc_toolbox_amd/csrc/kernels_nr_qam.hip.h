@@ -14,8 +14,10 @@
 //     16-byte vector stores, nontemporal on the max-log path.
 //   * demap_i8_kernel<H, A, MAXLOG, WIDE>: the same arithmetic from float symbols, each LLR quantised to an 8-bit soft bit:
 //     QM bytes out per symbol, the float row never stored.
-//   * qam_llr_kernel<H, MAXLOG>: the simulator's generator, fused: pooled transmitted row -> symbol -> AWGN -> the f64
-//     demapper -> float.
+//   * demap_csi_kernel<H, IO, A, MAXLOG>, demap_csi_i8_kernel<H, A, MAXLOG, WIDE>: the two demappers with a scale per symbol
+//     (PART 10): one more coalesced load per lane, and K_u = (0.5 * s) * Q_u made from the symbol's own s.
+//   * qam_llr_kernel<H, MAXLOG, FADING>: the simulator's generator, fused: pooled transmitted row -> symbol -> AWGN, or
+//     (FADING) the Rayleigh block-fading channel -> the f64 demapper, or its per-symbol-scale form -> float.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -164,20 +166,28 @@ struct Axis {
   A amp[16], k[16];
 };
 
+// the per-axis table of the demappers with a scale per symbol: q[u] = Q_u = A_u * A_u, made in double; a symbol's
+// K_u = (0.5 * s) * Q_u follows from its own s
+template <typename A>
+struct AxisCsi {
+  A amp[16], q[16];
+};
+
 // The H LLRs of one axis from its scaled coordinate.  acc1[t] starts at its first element, u = 1 << (H-1-t); acc0[t] at
 // u = 0.  Every test on u is wave-uniform.  The max-log fold is one instruction per step, and the exact fold for H <= 2 has
 // at most 4 maxstar bodies per axis: those unroll over u completely.  The exact fold for H = 3, 4 (18 and 56 maxstar
 // bodies per axis, each an f64 exp and log1p of about 4.7 KB of code) runs the loop over u at run time with H bodies in it:
 // 23 and 30 KB per loop, one axis after the other, so that a loop stays within the 64 KB instruction cache while it runs.
-template <int H, typename A, bool MAXLOG>
-__device__ __forceinline__ void axis_fold(A s, const Axis<A> &t, A (&out)[H]) {
+// k(u) gives K_u: the call's table entry, or the product with the symbol's own half scale.
+template <int H, typename A, bool MAXLOG, typename K>
+__device__ __forceinline__ void axis_fold(A s, const A (&amp)[16], K k, A (&out)[H]) {
   A acc0[H], acc1[H];
-  const A d0 = s * t.amp[0] - t.k[0];
+  const A d0 = s * amp[0] - k(0u);
 #pragma unroll
   for (int j = 0; j < H; j++) acc0[j] = acc1[j] = d0;
 #pragma unroll MAXLOG || H <= 2 ? (1 << H) - 1 : 1
   for (uint32_t u = 1; u < (1u << H); u++) {
-    const A d = s * t.amp[u] - t.k[u];
+    const A d = s * amp[u] - k(u);
 #pragma unroll
     for (int j = 0; j < H; j++) {
       const uint32_t first = 1u << (H - 1 - j);
@@ -192,16 +202,30 @@ __device__ __forceinline__ void axis_fold(A s, const Axis<A> &t, A (&out)[H]) {
 }
 
 // The 2 H LLRs of a symbol from its scaled coordinates: llr[2 t] from the I axis, llr[2 t + 1] from the Q axis.
-template <int H, typename A, bool MAXLOG>
-__device__ __forceinline__ void axis_llrs(A sx, A sy, const Axis<A> &t, A (&llr)[2 * H]) {
+template <int H, typename A, bool MAXLOG, typename K>
+__device__ __forceinline__ void axis_llrs_k(A sx, A sy, const A (&amp)[16], K k, A (&llr)[2 * H]) {
   A x[H], y[H];
-  axis_fold<H, A, MAXLOG>(sx, t, x);
-  axis_fold<H, A, MAXLOG>(sy, t, y);
+  axis_fold<H, A, MAXLOG>(sx, amp, k, x);
+  axis_fold<H, A, MAXLOG>(sy, amp, k, y);
 #pragma unroll
   for (int j = 0; j < H; j++) {
     llr[2 * j] = x[j];
     llr[2 * j + 1] = y[j];
   }
+}
+
+// one scale per call: K_u from the table
+template <int H, typename A, bool MAXLOG>
+__device__ __forceinline__ void axis_llrs(A sx, A sy, const Axis<A> &t, A (&llr)[2 * H]) {
+  axis_llrs_k<H, A, MAXLOG>(sx, sy, t.amp, [&](uint32_t u) { return t.k[u]; }, llr);
+}
+
+// the symbol's own scale s: sx = x * s, sy = y * s, K_u = half * Q_u with half = 0.5 * s.  K_u is the same for both axes:
+// where the loop over u unrolls the compiler makes each product once per symbol, and the run-time loops of the exact
+// H = 3, 4 folds make it once per axis, beside H exp / log1p bodies.
+template <int H, typename A, bool MAXLOG>
+__device__ __forceinline__ void axis_llrs_csi(A sx, A sy, A half, const AxisCsi<A> &t, A (&llr)[2 * H]) {
+  axis_llrs_k<H, A, MAXLOG>(sx, sy, t.amp, [&](uint32_t u) { return half * t.q[u]; }, llr);
 }
 
 // N values of type T at p (aligned to the piece size) in pieces of 16 bytes, or of 8 where 16 does not divide the row of
@@ -274,16 +298,116 @@ __global__ __launch_bounds__(kThreads) void demap_i8_kernel(const float *__restr
   }
 }
 
+// ---- the demappers with a scale per symbol (include/ldpc_toolbox.h, PART 10) ---------------------------------------------
+// scale [frames][symbols_len], s = 1 / sigma_s^2 of the symbol, one coalesced load per lane beside the symbol's; sx = x * s and
+// K_u = (0.5 * s) * Q_u take the place of the call's scale and table.  Everything behind the LLRs is that of demap_kernel and
+// demap_i8_kernel, whose bodies stay as they are written above: moved into these helpers their loads are scheduled
+// differently, and a kernel that exists keeps its instructions (tools/kernel_digest.py).
+
+// the 2 H LLRs of symbol `id`, each rounded once to IO and negated where its bit of c is set, to their place in llrs
+template <int H, typename IO, typename A, bool MAXLOG>
+__device__ __forceinline__ void store_llrs(const A (&llr)[2 * H], const uint32_t *c, uint64_t id, uint32_t symbols_len, IO *llrs) {
+  uint32_t flip = 0;
+  if (c != nullptr) flip = gold_window<2 * H>(c, 2 * H * static_cast<uint32_t>(id % symbols_len));
+  IO out[2 * H];
+#pragma unroll
+  for (int j = 0; j < 2 * H; j++) {
+    const IO x = static_cast<IO>(llr[j]);
+    out[j] = ((flip >> j) & 1u) ? -x : x;
+  }
+  store_row<MAXLOG>(llrs + id * (2 * H), out);
+}
+
+// ... each rounded once to float, signed and quantised, in the pieces of demap_i8_kernel
+template <int H, typename A, bool MAXLOG, bool WIDE>
+__device__ __forceinline__ void store_soft_bits(const A (&llr)[2 * H], const uint32_t *c, uint64_t id, uint32_t symbols_len, int8_t *llrs) {
+  uint32_t flip = 0;
+  if (c != nullptr) flip = gold_window<2 * H>(c, 2 * H * static_cast<uint32_t>(id % symbols_len));
+  uint64_t w = 0;
+#pragma unroll
+  for (int j = 0; j < 2 * H; j++) {
+    const float x = static_cast<float>(llr[j]);
+    const int q = soft::soft_quantize(static_cast<double>(((flip >> j) & 1u) ? -x : x));
+    w |= uint64_t(static_cast<uint8_t>(q)) << (8 * j);
+  }
+  int8_t *row = llrs + id * (2 * H);
+  if constexpr (WIDE && H % 2 == 0) {
+#pragma unroll
+    for (int i = 0; i < 2 * H; i += 4) demod::store_llr<MAXLOG>(reinterpret_cast<uint32_t *>(row + i), static_cast<uint32_t>(w >> (8 * i)));
+  } else if constexpr (WIDE) {
+#pragma unroll
+    for (int i = 0; i < 2 * H; i += 2) demod::store_llr<MAXLOG>(reinterpret_cast<uint16_t *>(row + i), static_cast<uint16_t>(w >> (8 * i)));
+  } else {
+#pragma unroll
+    for (int i = 0; i < 2 * H; i++) row[i] = static_cast<int8_t>(w >> (8 * i));
+  }
+}
+
+template <int H, typename IO, typename A, bool MAXLOG>
+__global__ __launch_bounds__(kThreads) void demap_csi_kernel(const IO *__restrict__ symbols, const IO *__restrict__ scale,
+                                                             IO *__restrict__ llrs, uint32_t symbols_len, uint64_t total,
+                                                             const uint32_t *__restrict__ c, const AxisCsi<A> t) {
+  const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (id >= total) return;
+  const typename Pair<IO>::type s = *reinterpret_cast<const typename Pair<IO>::type *>(symbols + 2 * id);
+  const A sc = static_cast<A>(scale[id]);
+  A llr[2 * H];
+  axis_llrs_csi<H, A, MAXLOG>(static_cast<A>(s.x) * sc, static_cast<A>(s.y) * sc, static_cast<A>(0.5) * sc, t, llr);
+  store_llrs<H, IO, A, MAXLOG>(llr, c, id, symbols_len, llrs);
+}
+
+// demap_csi_kernel<H, float, A, MAXLOG> up to the float it would store, then the soft bits of demap_i8_kernel
+template <int H, typename A, bool MAXLOG, bool WIDE>
+__global__ __launch_bounds__(kThreads) void demap_csi_i8_kernel(const float *__restrict__ symbols, const float *__restrict__ scale,
+                                                                int8_t *__restrict__ llrs, uint32_t symbols_len, uint64_t total,
+                                                                const uint32_t *__restrict__ c, const AxisCsi<A> t) {
+  const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
+  if (id >= total) return;
+  const typename Pair<float>::type s = *reinterpret_cast<const typename Pair<float>::type *>(symbols + 2 * id);
+  const A sc = static_cast<A>(scale[id]);
+  A llr[2 * H];
+  axis_llrs_csi<H, A, MAXLOG>(static_cast<A>(s.x) * sc, static_cast<A>(s.y) * sc, static_cast<A>(0.5) * sc, t, llr);
+  store_soft_bits<H, A, MAXLOG, WIDE>(llr, c, id, symbols_len, llrs);
+}
+
 // ---- the simulator's generator ----------------------------------------------------------------------------------------
+
+// the per-axis table of a generator: the call's K_u, or (FADING) Q_u for the symbol's own scale
+template <bool FADING>
+struct GeneratorAxis {
+  typedef Axis<double> type;
+};
+template <>
+struct GeneratorAxis<true> {
+  typedef AxisCsi<double> type;
+};
+
+// One symbol of a generator over the Rayleigh block-fading channel: sym_bits -> (A_uI, A_uQ) -> the gain of block
+// pair / block (gen::fading_scale) gives the symbol's sigma_e and scale -> + sigma_e * (double)z per coordinate, z =
+// gen::normal_pair(seed, frame, pair) -> axis_llrs_csi in f64: ldpc_toolbox_fading_run_f64 and ldpc_toolbox_nr_demap_csi_f64 in
+// one.  The symbol and its scale are never stored.
+template <int H, bool MAXLOG>
+__device__ __forceinline__ void fading_symbol_llrs(uint32_t sym_bits, uint64_t seed, uint64_t frame, uint32_t pair, double sigma, double a,
+                                                   const AxisCsi<double> &t, uint32_t block, double (&llr)[2 * H]) {
+  float z0, z1;
+  gen::normal_pair(seed, frame, pair, &z0, &z1);
+  double sigma_e, scale_s;
+  gen::fading_scale(seed, frame, pair / block, sigma, &sigma_e, &scale_s);
+  const double re = static_cast<double>(axis_level<H>(sym_bits, 0)) * a + sigma_e * static_cast<double>(z0);
+  const double im = static_cast<double>(axis_level<H>(sym_bits, 1)) * a + sigma_e * static_cast<double>(z1);
+  axis_llrs_csi<H, double, MAXLOG>(re * scale_s, im * scale_s, 0.5 * scale_s, t, llr);
+}
 
 // Frame first_frame + f: the pooled transmitted row's 2 H bits of symbol `sym` -> (A_uI, A_uQ) -> + sigma * (double)z per
 // coordinate, z = gen::normal_pair(seed, frame, sym) -> axis_llrs in f64 -> each LLR rounded once to float, in
 // transmitted order.  No scrambling; the symbol is never stored.  (The destination may be a caller's buffer of any float
-// alignment: scalar stores.)
-template <int H, bool MAXLOG>
+// alignment: scalar stores.)  FADING: the channel and demapper of fading_symbol_llrs with `block` symbols per gain; `scale`
+// is not used and t holds Q_u.
+template <int H, bool MAXLOG, bool FADING>
 __global__ __launch_bounds__(kThreads) void qam_llr_kernel(const uint8_t *__restrict__ tx_bits, uint32_t pool, uint32_t n_tx, uint64_t seed,
                                                            uint64_t first_frame, uint64_t total, double sigma, double scale, double a,
-                                                           const Axis<double> t, float *__restrict__ llrs) {
+                                                           const typename GeneratorAxis<FADING>::type t, float *__restrict__ llrs,
+                                                           uint32_t block) {
   const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
   if (id >= total) return;
   const uint32_t symbols = n_tx / (2 * H);
@@ -294,12 +418,16 @@ __global__ __launch_bounds__(kThreads) void qam_llr_kernel(const uint8_t *__rest
   uint32_t sym_bits = 0;
 #pragma unroll
   for (int j = 0; j < 2 * H; j++) sym_bits |= (b[j] == 1 ? 1u : 0u) << j;
-  float z0, z1;
-  gen::normal_pair(seed, frame, sym, &z0, &z1);
-  const double re = static_cast<double>(axis_level<H>(sym_bits, 0)) * a + sigma * static_cast<double>(z0);
-  const double im = static_cast<double>(axis_level<H>(sym_bits, 1)) * a + sigma * static_cast<double>(z1);
   double llr[2 * H];
-  axis_llrs<H, double, MAXLOG>(re * scale, im * scale, t, llr);
+  if constexpr (FADING) {
+    fading_symbol_llrs<H, MAXLOG>(sym_bits, seed, frame, sym, sigma, a, t, block, llr);
+  } else {
+    float z0, z1;
+    gen::normal_pair(seed, frame, sym, &z0, &z1);
+    const double re = static_cast<double>(axis_level<H>(sym_bits, 0)) * a + sigma * static_cast<double>(z0);
+    const double im = static_cast<double>(axis_level<H>(sym_bits, 1)) * a + sigma * static_cast<double>(z1);
+    axis_llrs<H, double, MAXLOG>(re * scale, im * scale, t, llr);
+  }
   float *row = llrs + f * n_tx + size_t(2 * H) * sym;
 #pragma unroll
   for (int j = 0; j < 2 * H; j++) row[j] = static_cast<float>(llr[j]);
@@ -308,12 +436,14 @@ __global__ __launch_bounds__(kThreads) void qam_llr_kernel(const uint8_t *__rest
 // One transmission of a HARQ sequence (nr_harq.h): qam_llr_kernel for a list of frames at a pair offset.  tx_bits
 // [pool][e]: this transmission's pooled transmitted rows; row r of llrs [frames][e] is frame frame_ids[r], or
 // first_frame + r without a list; symbol s of the row takes the normal pair first_symbol + s, the pair of that symbol in
-// the frame's concatenated row.  The arithmetic is qam_llr_kernel's.
-template <int H, bool MAXLOG>
+// the frame's concatenated row -- and (FADING) the gain of block (first_symbol + s) / block of that row.  The arithmetic is
+// qam_llr_kernel's.
+template <int H, bool MAXLOG, bool FADING>
 __global__ __launch_bounds__(kThreads) void qam_llr_harq_kernel(const uint8_t *__restrict__ tx_bits, uint32_t pool, uint32_t e,
                                                                 uint32_t first_symbol, uint64_t seed, uint64_t first_frame,
                                                                 const uint64_t *__restrict__ frame_ids, uint64_t total, double sigma,
-                                                                double scale, double a, const Axis<double> t, float *__restrict__ llrs) {
+                                                                double scale, double a, const typename GeneratorAxis<FADING>::type t,
+                                                                float *__restrict__ llrs, uint32_t block) {
   const uint64_t id = uint64_t(blockIdx.x) * kThreads + threadIdx.x;
   if (id >= total) return;
   const uint32_t symbols = e / (2 * H);
@@ -324,12 +454,16 @@ __global__ __launch_bounds__(kThreads) void qam_llr_harq_kernel(const uint8_t *_
   uint32_t sym_bits = 0;
 #pragma unroll
   for (int j = 0; j < 2 * H; j++) sym_bits |= (b[j] == 1 ? 1u : 0u) << j;
-  float z0, z1;
-  gen::normal_pair(seed, frame, first_symbol + sym, &z0, &z1);
-  const double re = static_cast<double>(axis_level<H>(sym_bits, 0)) * a + sigma * static_cast<double>(z0);
-  const double im = static_cast<double>(axis_level<H>(sym_bits, 1)) * a + sigma * static_cast<double>(z1);
   double llr[2 * H];
-  axis_llrs<H, double, MAXLOG>(re * scale, im * scale, t, llr);
+  if constexpr (FADING) {
+    fading_symbol_llrs<H, MAXLOG>(sym_bits, seed, frame, first_symbol + sym, sigma, a, t, block, llr);
+  } else {
+    float z0, z1;
+    gen::normal_pair(seed, frame, first_symbol + sym, &z0, &z1);
+    const double re = static_cast<double>(axis_level<H>(sym_bits, 0)) * a + sigma * static_cast<double>(z0);
+    const double im = static_cast<double>(axis_level<H>(sym_bits, 1)) * a + sigma * static_cast<double>(z1);
+    axis_llrs<H, double, MAXLOG>(re * scale, im * scale, t, llr);
+  }
   float *row = llrs + f * e + size_t(2 * H) * sym;
 #pragma unroll
   for (int j = 0; j < 2 * H; j++) row[j] = static_cast<float>(llr[j]);

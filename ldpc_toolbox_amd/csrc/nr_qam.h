@@ -80,6 +80,14 @@ inline const char *demod_argument_error(const Config &c, size_t llrs_len, size_t
   return nullptr;
 }
 
+// The demappers with a scale per symbol: the same without a sigma.  The scales are used as given and are not looked at.
+inline const char *demap_csi_argument_error(const Config &c, size_t llrs_len, size_t symbols_len, int64_t c_init) {
+  if (llrs_len % c.qm != 0 || llrs_len / c.qm != symbols_len) return "llrs_len is not QM * symbols_len";
+  if (llrs_len > 0x7fffffffu) return "frame length out of range for the NR demapper";
+  if (!c_init_ok(c_init)) return "c_init must be -1 (no scrambling) or 0 .. 2^31 - 1";
+  return nullptr;
+}
+
 inline const char *mod_argument_error(const Config &c, size_t bits_len, size_t symbols_len, int64_t c_init) {
   if (bits_len % c.qm != 0 || bits_len / c.qm != symbols_len) return "bits_len is not QM * symbols_len";
   if (bits_len > 0x7fffffffu) return "frame length out of range for the NR mapper";
@@ -97,6 +105,12 @@ inline const char *sequence_argument_error(size_t len, int64_t c_init) {
 inline const char *device_pointer_error(const void *symbols, const void *llrs, bool f64) {
   if (reinterpret_cast<uintptr_t>(symbols) % (f64 ? 16 : 8) != 0) return "the symbol buffer is not aligned to one (re, im) pair";
   if (llrs != nullptr && reinterpret_cast<uintptr_t>(llrs) % 16 != 0) return "the LLR buffer is not aligned to 16 bytes";
+  return nullptr;
+}
+
+// a device scale array is one scalar load per lane: the alignment of its element
+inline const char *scale_pointer_error(const void *scale, bool f64) {
+  if (reinterpret_cast<uintptr_t>(scale) % (f64 ? 8 : 4) != 0) return "the scale buffer is not aligned to its element";
   return nullptr;
 }
 

@@ -60,6 +60,13 @@ class Simulator {
   bool set_nr_qam(const nrqam::Config *c, bool max_log);
   bool has_nr_qam() const { return use_nr_qam_; }
   int64_t interleaving() const { return interleaving_; }
+  // "fading_block": 0 (none, the default) or the symbols per gain of the Rayleigh block-fading channel with perfect CSI
+  // (include/ldpc_toolbox.h, PART 10), up to 0x7fffffff; false with nothing changed outside that range.  While it is set the
+  // channel between the NR mapper and the demapper of set_nr_qam is the fading channel, and the demapper takes each symbol's
+  // own scale.  Without an NR modulation in force every run and generate call is refused (-1, counters untouched): the run,
+  // not this setter.
+  bool set_fading_block(int64_t symbols);
+  uint32_t fading_block() const { return fading_block_; }
   // An outer BCH code (a copy of the one a BCH handle holds) in place of the genie of run_bch; nullptr returns to the
   // genie.  false with nothing changed unless the code's n is this simulator's k.
   bool set_bch(const bch::Code *c);
@@ -158,6 +165,8 @@ class Simulator {
   bool use_nr_qam_ = false;
   nrqam::Config nr_qam_;
   int64_t interleaving_ = 0;
+  uint32_t fading_block_ = 0;
+  const char *fading_error() const;
   std::vector<uint8_t> messages_, tx_bits_;
   DeviceBuffer d_messages_, d_tx_, d_bits_, d_llrs_, d_its_, d_counters_;
   // Straggler pooling: once a run() call has seen how many iterations its frames take, later chunks run a reduced

@@ -343,6 +343,22 @@ bool Simulator::set_interleaving(int64_t columns) {
   return true;
 }
 
+bool Simulator::set_fading_block(int64_t symbols) {
+  if (symbols < 0 || symbols > 0x7fffffffll) {
+    fail("fading_block must be 0 (none) or 1 .. 2^31 - 1 symbols");
+    return false;
+  }
+  fading_block_ = static_cast<uint32_t>(symbols);
+  budget_valid_ = false;  // (as in set_modulation)
+  return true;
+}
+
+// the fading channel lies between the NR mapper and its demapper: nullptr, or why a run is refused
+const char *Simulator::fading_error() const {
+  if (fading_block_ != 0 && !use_nr_qam_) return "fading_block needs an NR modulation in force (ldpc_toolbox_sim_set_nr_qam)";
+  return nullptr;
+}
+
 // ber.rs:299-302: EsN0 = rate * bits_per_symbol * EbN0, sigma = sqrt(0.5 / EsN0)
 double Simulator::noise_sigma(double ebn0_db) const {
   const double ebn0 = std::pow(10.0, 0.1 * ebn0_db);
@@ -401,7 +417,8 @@ void Simulator::launch_generator(double ebn0_db, uint64_t seed, uint64_t first_f
   const uint32_t n_tx = static_cast<uint32_t>(n_tx_);
   if (dst == nullptr) dst = rate_match_ ? d_rx_.get<float>() : d_llrs_.get<float>();
   if (use_nr_qam_) {
-    nr_qam_launch_generator(nr_qam_, max_log_, d_tx_.get<uint8_t>(), pool_, n_tx, seed, first_frame, frames, noise_sigma(ebn0_db), dst, stream_);
+    nr_qam_launch_generator(nr_qam_, max_log_, d_tx_.get<uint8_t>(), pool_, n_tx, seed, first_frame, frames, noise_sigma(ebn0_db), fading_block_,
+                            dst, stream_);
     return;
   }
   if (use_constellation_ && !constellation_.bpsk) {
@@ -426,6 +443,7 @@ void Simulator::launch_generator(double ebn0_db, uint64_t seed, uint64_t first_f
 
 int Simulator::run(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations,
                    uint64_t counters[6]) {
+  if (const char *why = fading_error()) return fail(why), -1;
   uint64_t all[9];
   const int rc = run_frames(ebn0_db, seed, first_frame, frames, max_iterations, 0, false, all);
   for (int i = 0; i < 6; i++) counters[i] = all[i];
@@ -434,6 +452,7 @@ int Simulator::run(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t f
 
 int Simulator::run_bch(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations,
                        uint64_t bch_max_errors, uint64_t counters[9]) {
+  if (const char *why = fading_error()) return fail(why), -1;
   if (bch_ && bch_max_errors != bch_code_.t) {
     for (int i = 0; i < 9; i++) counters[i] = 0;
     fail("bch_max_errors is not the t of the BCH code in force");
@@ -562,6 +581,7 @@ int Simulator::run_frames(double ebn0_db, uint64_t seed, uint64_t first_frame, s
 
 int Simulator::generate(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, float *llrs,
                         uint32_t *pool_index) {
+  if (const char *why = fading_error()) return fail(why), -1;
   if (frames == 0) return 0;
   SIM_TRY(hipSetDevice(device_));
   // `llrs` in this GPU's memory: the frames are generated in place (a multi-rank benchmark fills its gigabyte of frames
@@ -592,7 +612,7 @@ void Simulator::launch_harq_generator(double ebn0_db, uint64_t seed, uint32_t t,
   const uint8_t *tx = d_harq_tx_.get<uint8_t>() + size_t(pool_) * harq_.offset[t];
   if (use_nr_qam_) {
     nr_qam_launch_harq_generator(nr_qam_, max_log_, tx, pool_, e, nrharq::first_symbol(harq_, t, nr_qam_.qm), seed, first_frame, frame_ids,
-                                 frames, noise_sigma(ebn0_db), dst, stream_);
+                                 frames, noise_sigma(ebn0_db), fading_block_, dst, stream_);
     return;
   }
   float sigma, scale;
@@ -692,6 +712,7 @@ int Simulator::flush_harq(uint32_t t, uint32_t count, double ebn0_db, uint64_t s
 
 int Simulator::run_harq(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t max_iterations, uint64_t counters[6],
                         uint64_t *per_tx) {
+  if (const char *why = fading_error()) return fail(why), -1;
   const uint32_t T = harq_.t;
   for (int i = 0; i < 6; i++) counters[i] = 0;
   for (uint32_t i = 0; i < 4 * T; i++) per_tx[i] = 0;
@@ -801,6 +822,7 @@ int Simulator::run_harq(double ebn0_db, uint64_t seed, uint64_t first_frame, siz
 
 int Simulator::generate_harq(double ebn0_db, uint64_t seed, uint64_t first_frame, size_t frames, uint32_t transmission, float *llrs,
                              uint32_t *pool_index) {
+  if (const char *why = fading_error()) return fail(why), -1;
   auto refuse = [&](const char *why) {
     fail(why);
     return -4;

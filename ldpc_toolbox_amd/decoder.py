@@ -456,10 +456,12 @@ class Simulator:
 
     def set(self, key, value):
         """"soft_bits": 8 keeps `run_harq`'s soft buffers as 8-bit soft bits (an 8-bit implementation only; ValueError and
-        nothing changed otherwise), 32 (the default) as floats."""
+        nothing changed otherwise), 32 (the default) as floats.  "fading_block": B > 0 puts the Rayleigh block-fading channel
+        with perfect CSI, one gain per B symbols, between the NR mapper and demapper of `set_nr_qam` (without one the runs
+        are refused); 0 (the default) returns to AWGN."""
         if _capi.lib().ldpc_toolbox_sim_set(self._h, key.encode(), int(value)) != 0:
-            if key == "soft_bits":
-                raise ValueError(_capi.last_error() or "cannot set soft_bits")
+            if key in ("soft_bits", "fading_block"):
+                raise ValueError(_capi.last_error() or f"cannot set {key}")
             raise KeyError(key)
 
     def run(self, ebn0_db, seed, first_frame, frames, max_iterations, bch_max_errors: int = 0):

@@ -150,6 +150,35 @@ class Demodulator:
         if rc != 0:
             self._raise("add_noise_device", rc)
 
+    def add_fading(self, symbols, sigma, block, seed, first_frame=0):
+        """symbols [batch][symbols_len] complex64 / complex128 -> (equalised symbols, scale): Rayleigh block fading with
+        perfect CSI behind a one-tap equaliser, one gain per `block` consecutive symbols of a frame (block >= symbols_len:
+        quasi-static); row r is frame first_frame + r, its noise that of `add_noise`.  scale [batch][symbols_len] float32 /
+        float64 is each symbol's 1 / sigma_e^2 -- what `NrQam.demodulate_csi` takes.  Complex handles only."""
+        symbols = np.asarray(symbols)
+        if symbols.ndim != 2:
+            raise ValueError("symbols must be [batch][symbols_len]")
+        real = np.float32 if symbols.dtype in (np.complex64, np.float32) else np.float64
+        out = np.array(symbols, dtype=np.complex64 if real == np.float32 else np.complex128, order="C")
+        scale = np.zeros(out.shape, dtype=real)
+        B, S = out.shape
+        L = _capi.lib()
+        fn = L.ldpc_toolbox_fading_run_f32 if real == np.float32 else L.ldpc_toolbox_fading_run_f64
+        rc = fn(self._h, out.ctypes.data, scale.ctypes.data, S, B, float(sigma), int(block), int(seed), int(first_frame))
+        if rc != 0:
+            self._raise("add_fading", rc)
+        return out, scale
+
+    def add_fading_device(self, sym_ptr: int, scale_ptr: int, f64: bool, batch: int, symbols_len: int, sigma, block, seed,
+                          first_frame=0, stream: int = 0):
+        """Raw device pointers: symbols [batch][symbols_len] equalised in place, scale [batch][symbols_len] written; stream
+        as in `demodulate_device`.  The symbol buffer must be aligned to one (re, im) pair."""
+        L = _capi.lib()
+        fn = L.ldpc_toolbox_fading_run_f64_device if f64 else L.ldpc_toolbox_fading_run_f32_device
+        rc = fn(self._h, sym_ptr, scale_ptr, symbols_len, batch, float(sigma), int(block), int(seed), int(first_frame), stream or None)
+        if rc != 0:
+            self._raise("add_fading_device", rc)
+
     def close(self):
         if getattr(self, "_h", None):
             _capi.lib().ldpc_toolbox_demod_dtor(self._h)

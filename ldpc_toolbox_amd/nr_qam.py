@@ -136,6 +136,58 @@ class NrQam:
         if rc != 0:
             self._raise("demap_i8_device", rc)
 
+    def _csi_host(self, what, fn, symbols, scale, sym_t, out_t, max_log, c_init):
+        symbols = np.asarray(symbols)
+        if symbols.ndim != 2:
+            raise ValueError("symbols must be [batch][symbols_len]")
+        symbols = np.ascontiguousarray(symbols, dtype=sym_t)
+        scale = np.ascontiguousarray(scale, dtype=np.float32 if sym_t == np.complex64 else np.float64)
+        if scale.shape != symbols.shape:
+            raise ValueError("scale must be [batch][symbols_len], one value per symbol")
+        B, S = symbols.shape
+        n = S * self.bits_per_symbol
+        out = np.zeros((B, n), dtype=out_t)
+        rc = fn(self._h, out.ctypes.data, n, symbols.ctypes.data, scale.ctypes.data, S, B, int(bool(max_log)), int(c_init))
+        if rc != 0:
+            self._raise(what, rc)
+        return out
+
+    def demodulate_csi(self, symbols, scale, max_log: bool = False, c_init: int = -1):
+        """`demodulate` with a scale per symbol in place of sigma (include/ldpc_toolbox.h, PART 10): symbols
+        [batch][symbols_len] complex64 / complex128 equalised symbols, scale [batch][symbols_len] = 1 / sigma_s^2, the
+        reciprocal of each symbol's noise variance per real coordinate after equalisation -> LLRs [batch][QM * symbols_len]
+        float32 / float64.  The scales are used as given: 0 erases a symbol."""
+        symbols = np.asarray(symbols)
+        f32 = symbols.dtype in (np.complex64, np.float32)
+        L = _capi.lib()
+        return self._csi_host("demodulate_csi", L.ldpc_toolbox_nr_demap_csi_f32 if f32 else L.ldpc_toolbox_nr_demap_csi_f64, symbols, scale,
+                              np.complex64 if f32 else np.complex128, np.float32 if f32 else np.float64, max_log, c_init)
+
+    def demodulate_csi_device(self, sym_ptr: int, scale_ptr: int, out_ptr: int, f64: bool, batch: int, symbols_len: int,
+                              max_log: bool = False, c_init: int = -1, stream: int = 0):
+        """Raw device pointers: symbols and scale [batch][symbols_len] -> LLRs [batch][QM * symbols_len]; stream as in
+        `modulate_device`.  Alignment as in `demodulate_device`; the scale buffer needs only its element's."""
+        L = _capi.lib()
+        fn = L.ldpc_toolbox_nr_demap_csi_f64_device if f64 else L.ldpc_toolbox_nr_demap_csi_f32_device
+        rc = fn(self._h, out_ptr, symbols_len * self.bits_per_symbol, sym_ptr, scale_ptr, symbols_len, batch, int(bool(max_log)), int(c_init),
+                stream or None)
+        if rc != 0:
+            self._raise("demodulate_csi_device", rc)
+
+    def demap_csi_i8(self, symbols, scale, max_log: bool = False, c_init: int = -1):
+        """complex64 symbols and float32 scales [batch][symbols_len] -> 8-bit soft bits [batch][QM * symbols_len] int8: each
+        the float32 LLR of `demodulate_csi` quantised as in `demap_i8`, in one kernel."""
+        return self._csi_host("demap_csi_i8", _capi.lib().ldpc_toolbox_nr_demap_csi_i8, symbols, scale, np.complex64, np.int8, max_log, c_init)
+
+    def demap_csi_i8_device(self, sym_ptr: int, scale_ptr: int, out_ptr: int, batch: int, symbols_len: int, max_log: bool = False,
+                            c_init: int = -1, stream: int = 0):
+        """Raw device pointers: float symbols and scales [batch][symbols_len] -> int8 soft bits [batch][QM * symbols_len];
+        stream as in `modulate_device`.  The output may be any byte address."""
+        rc = _capi.lib().ldpc_toolbox_nr_demap_csi_i8_device(self._h, out_ptr, symbols_len * self.bits_per_symbol, sym_ptr, scale_ptr,
+                                                             symbols_len, batch, int(bool(max_log)), int(c_init), stream or None)
+        if rc != 0:
+            self._raise("demap_csi_i8_device", rc)
+
     def close(self):
         if getattr(self, "_h", None):
             _capi.lib().ldpc_toolbox_nr_qam_dtor(self._h)
