@@ -37,7 +37,7 @@
 #include <cstdint>
 #include <string>
 
-#include "hip_owned.h"
+#include "device_stage.h"
 
 namespace ldpc {
 
@@ -169,16 +169,11 @@ inline const char *sim_constellation_error(const Constellation &c, size_t n_tx) 
   return nullptr;
 }
 
-class DeviceDemodulator {
+class DeviceDemodulator : public DeviceStage {
  public:
   // nullptr (and *err) when there is no usable GPU: there is no CPU path here.
   static DeviceDemodulator *create(const Constellation &c, int device, std::string *err);
   ~DeviceDemodulator();
-  DeviceDemodulator(const DeviceDemodulator &) = delete;
-  DeviceDemodulator &operator=(const DeviceDemodulator &) = delete;
-
-  int device() const { return device_; }
-  const std::string &last_error() const { return error_; }
 
   // symbols [batch][symbols_len] (re, im) pairs -- reals for BPSK -- and llrs [batch][llrs_len], float or double (f64),
   // the arguments already checked (demod_argument_error).  0, or -2 on a HIP failure.
@@ -206,22 +201,12 @@ class DeviceDemodulator {
                   uint64_t first_frame);
 
  private:
-  DeviceDemodulator() = default;
-  bool fail(const std::string &m, hipError_t e = hipSuccess);
+  explicit DeviceDemodulator(int device) : DeviceStage("demodulator", device) {}
   template <typename IO>
   void launch(const IO *symbols, IO *llrs, size_t symbols_len, size_t llrs_len, size_t batch, double sigma,
               int32_t interleaving, bool max_log, hipStream_t s);
-  // the launch stream of a device entry (ordered after the legacy default stream when it is the handle's own): -2 on failure
-  int begin(hipStream_t stream, hipStream_t *s);
-  int end(hipStream_t stream, hipStream_t s);
 
   Constellation c_;
-  int device_ = -1;
-  std::string error_;
-  // what the handle owns (hip_owned.h): the stream is declared first and so destroyed last
-  Stream stream_;
-  Event ev_default_;
-  DeviceBuffer d_in_, d_out_;  // the staging buffers of the host entry
 };
 
 }  // namespace ldpc

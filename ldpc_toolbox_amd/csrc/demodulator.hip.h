@@ -1,8 +1,8 @@
-// Host side of the batched soft demapper (demodulator.h): per-call tables and launches.
+// Host side of the batched soft demapper (demodulator.h): per-call tables and launches (stream protocol and staging loop:
+// device_stage.h).
 // Included by simulator.hip -- the demodulator shares the simulator's translation unit, as the batched encoder does.
 #pragma once
 #include <algorithm>
-#include <cstdio>
 #include <memory>
 
 #include "demodulator.h"
@@ -11,51 +11,22 @@
 
 namespace ldpc {
 
-bool DeviceDemodulator::fail(const std::string &m, hipError_t e) {
-  error_ = m;
-  if (e != hipSuccess) error_ += std::string(": ") + hipGetErrorString(e);
-  std::fprintf(stderr, "ldpc_toolbox (hip): demodulator: %s\n", error_.c_str());
-  return false;
-}
-
-#define DEMOD_TRY(expr)               \
-  do {                                \
-    hipError_t _e = (expr);           \
-    if (_e != hipSuccess) {           \
-      fail(#expr, _e);                \
-      return -2;                      \
-    }                                 \
-  } while (0)
-
 DeviceDemodulator *DeviceDemodulator::create(const Constellation &c, int device, std::string *err) {
-  auto bail = [&](const std::string &m) -> DeviceDemodulator * {
-    if (err) *err = m;
-    return nullptr;
-  };
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return bail("no HIP device available: the demodulator has no CPU path");
-  if (device < 0 || device >= count) return bail("HIP device index out of range");
-  if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice failed");
-  std::unique_ptr<DeviceDemodulator> d(new DeviceDemodulator());
+  if (!select_device(device, "the demodulator has", err)) return nullptr;
+  std::unique_ptr<DeviceDemodulator> d(new DeviceDemodulator(device));
   d->c_ = c;
-  d->device_ = device;
-  if (d->stream_.create() != hipSuccess || d->ev_default_.create() != hipSuccess)
-    return bail("creating the demodulator's stream failed");
+  if (!d->create_stream("the demodulator's", err)) return nullptr;
   return d.release();
 }
 
 // (the members free what they own, the stream last)
-DeviceDemodulator::~DeviceDemodulator() {
-  (void)hipSetDevice(device_);
-  if (stream_) (void)hipStreamSynchronize(stream_);
-}
+DeviceDemodulator::~DeviceDemodulator() { wait_idle(); }
 
 namespace {
 // one pass of a table constellation: frames * symbols_len threads
-template <int M, typename IO, typename A, bool MAXLOG>
-void demod_table_pass(const IO *symbols, IO *llrs, uint32_t symbols_len, uint32_t llrs_len, uint64_t total, double scale,
-                      int32_t interleaving, const Constellation &c, hipStream_t s) {
+template <typename IO, typename A, bool MAXLOG>
+void demod_table_pass_m(uint32_t bits, const IO *symbols, IO *llrs, uint32_t symbols_len, uint32_t llrs_len, uint64_t total,
+                        double scale, int32_t interleaving, const Constellation &c, hipStream_t s) {
   demod::Table<A> t;
   const double half_scale = 0.5 * scale;
   for (uint32_t v = 0; v < 32; v++) {
@@ -64,20 +35,10 @@ void demod_table_pass(const IO *symbols, IO *llrs, uint32_t symbols_len, uint32_
     t.c[v] = static_cast<A>(half_scale * c.e[v]);
   }
   const uint32_t blocks = static_cast<uint32_t>((total + demod::kThreads - 1) / demod::kThreads);
-  demod::table_kernel<M, IO, A, MAXLOG><<<blocks, demod::kThreads, 0, s>>>(symbols, llrs, symbols_len, llrs_len, total,
-                                                                          static_cast<A>(scale), interleaving, c.energy ? 1 : 0, t);
-}
-
-template <typename IO, typename A, bool MAXLOG>
-void demod_table_pass_m(uint32_t bits, const IO *symbols, IO *llrs, uint32_t symbols_len, uint32_t llrs_len, uint64_t total,
-                        double scale, int32_t interleaving, const Constellation &c, hipStream_t s) {
-  switch (bits) {
-    case 1: return demod_table_pass<1, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
-    case 2: return demod_table_pass<2, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
-    case 3: return demod_table_pass<3, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
-    case 4: return demod_table_pass<4, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
-    default: return demod_table_pass<5, IO, A, MAXLOG>(symbols, llrs, symbols_len, llrs_len, total, scale, interleaving, c, s);
-  }
+  with_int<1, 2, 3, 4, 5>(static_cast<int>(bits), [&](auto m) {
+    demod::table_kernel<decltype(m)::value, IO, A, MAXLOG><<<blocks, demod::kThreads, 0, s>>>(
+        symbols, llrs, symbols_len, llrs_len, total, static_cast<A>(scale), interleaving, c.energy ? 1 : 0, t);
+  });
 }
 }  // namespace
 
@@ -106,23 +67,6 @@ void DeviceDemodulator::launch(const IO *symbols, IO *llrs, size_t symbols_len, 
   }
 }
 
-int DeviceDemodulator::begin(hipStream_t stream, hipStream_t *s) {
-  DEMOD_TRY(hipSetDevice(device_));
-  *s = stream ? stream : static_cast<hipStream_t>(stream_);
-  if (!stream) {
-    // (the handle's stream is non-blocking: ordered explicitly after what the legacy default stream holds now)
-    DEMOD_TRY(hipEventRecord(ev_default_, nullptr));
-    DEMOD_TRY(hipStreamWaitEvent(*s, ev_default_, 0));
-  }
-  return 0;
-}
-
-int DeviceDemodulator::end(hipStream_t stream, hipStream_t s) {
-  DEMOD_TRY(hipGetLastError());
-  if (!stream) DEMOD_TRY(hipStreamSynchronize(s));
-  return 0;
-}
-
 int DeviceDemodulator::run_device(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch,
                                   double sigma, int32_t interleaving, bool max_log, hipStream_t stream) {
   if (batch == 0 || llrs_len == 0) return 0;
@@ -140,18 +84,10 @@ int DeviceDemodulator::run_device(const void *symbols, void *llrs, bool f64, siz
 int DeviceDemodulator::run_host(const void *symbols, void *llrs, bool f64, size_t symbols_len, size_t llrs_len, size_t batch,
                                 double sigma, int32_t interleaving, bool max_log) {
   if (batch == 0 || llrs_len == 0) return 0;
-  DEMOD_TRY(hipSetDevice(device_));
   const size_t elem = f64 ? 8 : 4;
-  const size_t in_bytes = batch * symbols_len * (c_.bpsk ? 1 : 2) * elem, out_bytes = batch * llrs_len * elem;
-  DEMOD_TRY(d_in_.ensure(in_bytes, 256));
-  DEMOD_TRY(d_out_.ensure(out_bytes, 256));
-  DEMOD_TRY(hipMemcpyAsync(d_in_.get(), symbols, in_bytes, hipMemcpyHostToDevice, stream_));
-  if (int rc = run_device(d_in_.get(), d_out_.get(), f64, symbols_len, llrs_len, batch, sigma, interleaving, max_log, stream_))
-    return rc;
-  // (the only write to the caller's buffer: after an earlier failure nothing has been written)
-  DEMOD_TRY(hipMemcpyAsync(llrs, d_out_.get(), out_bytes, hipMemcpyDeviceToHost, stream_));
-  DEMOD_TRY(hipStreamSynchronize(stream_));
-  return 0;
+  return staged_rows(symbols, symbols_len * (c_.bpsk ? 1 : 2) * elem, llrs, llrs_len * elem, batch, batch, false, [&](size_t frames) {
+    return run_device(d_in_.get(), d_out_.get(), f64, symbols_len, llrs_len, frames, sigma, interleaving, max_log, stream_);
+  });
 }
 
 // ---- the transmit side: modulator and AWGN channel (kernels_channel.hip.h) ------------------------------------------
@@ -229,15 +165,9 @@ int DeviceDemodulator::mod_device(const uint8_t *bits, void *symbols, bool f64, 
 int DeviceDemodulator::mod_host(const uint8_t *bits, void *symbols, bool f64, size_t bits_len, size_t symbols_len, size_t batch,
                                 int32_t interleaving) {
   if (batch == 0 || bits_len == 0) return 0;
-  DEMOD_TRY(hipSetDevice(device_));
-  const size_t in_bytes = batch * bits_len, out_bytes = batch * symbols_len * (c_.bpsk ? 1 : 2) * (f64 ? 8 : 4);
-  DEMOD_TRY(d_in_.ensure(in_bytes, 256));
-  DEMOD_TRY(d_out_.ensure(out_bytes, 256));
-  DEMOD_TRY(hipMemcpyAsync(d_in_.get(), bits, in_bytes, hipMemcpyHostToDevice, stream_));
-  if (int rc = mod_device(d_in_.get<uint8_t>(), d_out_.get(), f64, bits_len, symbols_len, batch, interleaving, stream_)) return rc;
-  DEMOD_TRY(hipMemcpyAsync(symbols, d_out_.get(), out_bytes, hipMemcpyDeviceToHost, stream_));
-  DEMOD_TRY(hipStreamSynchronize(stream_));
-  return 0;
+  return staged_rows(bits, bits_len, symbols, symbols_len * (c_.bpsk ? 1 : 2) * (f64 ? 8 : 4), batch, batch, false, [&](size_t frames) {
+    return mod_device(d_in_.get<uint8_t>(), d_out_.get(), f64, bits_len, symbols_len, frames, interleaving, stream_);
+  });
 }
 
 int DeviceDemodulator::awgn_device(void *symbols, bool f64, size_t symbols_len, size_t batch, double sigma, uint64_t seed,
@@ -252,17 +182,17 @@ int DeviceDemodulator::awgn_device(void *symbols, bool f64, size_t symbols_len, 
   return end(stream, s);
 }
 
+// (in place: one buffer, copied in and out)
 int DeviceDemodulator::awgn_host(void *symbols, bool f64, size_t symbols_len, size_t batch, double sigma, uint64_t seed,
                                  uint64_t first_frame) {
   if (batch == 0 || symbols_len == 0) return 0;
-  DEMOD_TRY(hipSetDevice(device_));
-  const size_t bytes = batch * symbols_len * (c_.bpsk ? 1 : 2) * (f64 ? 8 : 4);
-  DEMOD_TRY(d_in_.ensure(bytes, 256));
-  DEMOD_TRY(hipMemcpyAsync(d_in_.get(), symbols, bytes, hipMemcpyHostToDevice, stream_));
-  if (int rc = awgn_device(d_in_.get(), f64, symbols_len, batch, sigma, seed, first_frame, stream_)) return rc;
-  DEMOD_TRY(hipMemcpyAsync(symbols, d_in_.get(), bytes, hipMemcpyDeviceToHost, stream_));
-  DEMOD_TRY(hipStreamSynchronize(stream_));
-  return 0;
+  const size_t row = symbols_len * (c_.bpsk ? 1 : 2) * (f64 ? 8 : 4), bytes = batch * row;
+  return staged(batch, batch, {{d_in_, row}}, [&](size_t, size_t) {
+    STAGE_TRY(hipMemcpyAsync(d_in_.get(), symbols, bytes, hipMemcpyHostToDevice, stream_));
+    if (int rc = awgn_device(d_in_.get(), f64, symbols_len, batch, sigma, seed, first_frame, stream_)) return rc;
+    STAGE_TRY(hipMemcpyAsync(symbols, d_in_.get(), bytes, hipMemcpyDeviceToHost, stream_));
+    return 0;
+  });
 }
 
 int DeviceDemodulator::fading_device(void *symbols, void *scale, bool f64, size_t symbols_len, size_t batch, double sigma, uint32_t block,
@@ -280,18 +210,14 @@ int DeviceDemodulator::fading_device(void *symbols, void *scale, bool f64, size_
 int DeviceDemodulator::fading_host(void *symbols, void *scale, bool f64, size_t symbols_len, size_t batch, double sigma, uint32_t block,
                                    uint64_t seed, uint64_t first_frame) {
   if (batch == 0 || symbols_len == 0) return 0;
-  DEMOD_TRY(hipSetDevice(device_));
-  const size_t scale_bytes = batch * symbols_len * (f64 ? 8 : 4), bytes = 2 * scale_bytes;
-  DEMOD_TRY(d_in_.ensure(bytes, 256));
-  DEMOD_TRY(d_out_.ensure(scale_bytes, 256));
-  DEMOD_TRY(hipMemcpyAsync(d_in_.get(), symbols, bytes, hipMemcpyHostToDevice, stream_));
-  if (int rc = fading_device(d_in_.get(), d_out_.get(), f64, symbols_len, batch, sigma, block, seed, first_frame, stream_)) return rc;
-  DEMOD_TRY(hipMemcpyAsync(symbols, d_in_.get(), bytes, hipMemcpyDeviceToHost, stream_));
-  DEMOD_TRY(hipMemcpyAsync(scale, d_out_.get(), scale_bytes, hipMemcpyDeviceToHost, stream_));
-  DEMOD_TRY(hipStreamSynchronize(stream_));
-  return 0;
+  const size_t scale_row = symbols_len * (f64 ? 8 : 4), scale_bytes = batch * scale_row, bytes = 2 * scale_bytes;
+  return staged(batch, batch, {{d_in_, 2 * scale_row}, {d_out_, scale_row}}, [&](size_t, size_t) {
+    STAGE_TRY(hipMemcpyAsync(d_in_.get(), symbols, bytes, hipMemcpyHostToDevice, stream_));
+    if (int rc = fading_device(d_in_.get(), d_out_.get(), f64, symbols_len, batch, sigma, block, seed, first_frame, stream_)) return rc;
+    STAGE_TRY(hipMemcpyAsync(symbols, d_in_.get(), bytes, hipMemcpyDeviceToHost, stream_));
+    STAGE_TRY(hipMemcpyAsync(scale, d_out_.get(), scale_bytes, hipMemcpyDeviceToHost, stream_));
+    return 0;
+  });
 }
-
-#undef DEMOD_TRY
 
 }  // namespace ldpc

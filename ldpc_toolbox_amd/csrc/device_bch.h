@@ -8,7 +8,7 @@
 #include <string>
 
 #include "bch.h"
-#include "hip_owned.h"
+#include "device_stage.h"
 
 namespace ldpc {
 
@@ -17,16 +17,11 @@ constexpr size_t kBchPassFrames = 16384;
 // what a host entry stages on the device at a time: at most this many frames and about this many bytes of input rows
 constexpr size_t kBchStageFrames = size_t(1) << 20, kBchStageBytes = size_t(1) << 28;
 
-class DeviceBch {
+class DeviceBch : public DeviceStage {
  public:
   // Uploads the tables of `c` to GPU `device`.  nullptr (and *err) when there is no usable GPU: there is no CPU path.
   static DeviceBch *create(const bch::Code &c, int device, std::string *err);
   ~DeviceBch();
-  DeviceBch(const DeviceBch &) = delete;
-  DeviceBch &operator=(const DeviceBch &) = delete;
-
-  int device() const { return device_; }
-  const std::string &last_error() const { return error_; }
 
   // input [batch][k] -> output [batch][n].  0, or -2 on a HIP failure.  Device pointers; stream: launch stream
   // (nullptr = the handle's own stream, ordered after everything queued on the legacy default stream at the time of
@@ -40,24 +35,17 @@ class DeviceBch {
   int decode_host(const uint8_t *input, uint8_t *output, size_t output_len, size_t batch, int32_t *errors);
 
  private:
-  DeviceBch() = default;
-  bool fail(const std::string &m, hipError_t e = hipSuccess);
-  int begin(hipStream_t stream, hipStream_t *s);
-  int end(hipStream_t stream, hipStream_t s);
+  explicit DeviceBch(int device) : DeviceStage("bch", device) {}
   size_t stage_frames() const;
 
   bch::Code c_;
   bch::Geometry enc_geo_, dec_geo_;
   uint32_t g_top_[bch::kMaxParityWords] = {};
-  int device_ = -1;
-  std::string error_;
-  // what the handle owns (hip_owned.h): the stream is declared first and so destroyed last
-  Stream stream_;
-  Event ev_default_;
+  // (beside the stream and the staging buffers of DeviceStage)
   DeviceBuffer d_antilog_, d_log_, d_enc_table_, d_dec_table_;
   // one pass's frames with a non-zero remainder, their number, their odd syndromes and their locators
   DeviceBuffer d_list_, d_count_, d_synd_, d_loc_;
-  DeviceBuffer d_in_, d_out_, d_err_;  // the staging buffers of the host entries
+  DeviceBuffer d_err_;  // the error counts of a stage of decode_host
 };
 
 }  // namespace ldpc

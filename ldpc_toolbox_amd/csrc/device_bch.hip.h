@@ -1,8 +1,7 @@
-// Host side of the batched BCH code (device_bch.h): tables and launches.
+// Host side of the batched BCH code (device_bch.h): tables and launches (stream protocol and staging loop: device_stage.h).
 // Included by simulator.hip -- it shares the simulator's translation unit, as the batched encoder does.
 #pragma once
 #include <algorithm>
-#include <cstdio>
 #include <memory>
 
 #include "device_bch.h"
@@ -10,40 +9,20 @@
 
 namespace ldpc {
 
-bool DeviceBch::fail(const std::string &m, hipError_t e) {
-  error_ = m;
-  if (e != hipSuccess) error_ += std::string(": ") + hipGetErrorString(e);
-  std::fprintf(stderr, "ldpc_toolbox (hip): bch: %s\n", error_.c_str());
-  return false;
-}
-
-#define BCH_TRY(expr)                 \
-  do {                                \
-    hipError_t _e = (expr);           \
-    if (_e != hipSuccess) {           \
-      fail(#expr, _e);                \
-      return -2;                      \
-    }                                 \
-  } while (0)
-
 DeviceBch *DeviceBch::create(const bch::Code &c, int device, std::string *err) {
   auto bail = [&](const std::string &m) -> DeviceBch * {
     if (err) *err = m;
     return nullptr;
   };
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return bail("no HIP device available: the BCH code has no CPU path");
-  if (device < 0 || device >= count) return bail("HIP device index out of range");
-  if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice failed");
-  std::unique_ptr<DeviceBch> d(new DeviceBch());
+  if (!select_device(device, "the BCH code has", err)) return nullptr;
+  std::unique_ptr<DeviceBch> d(new DeviceBch(device));
   d->c_ = c;
-  d->device_ = device;
   d->enc_geo_ = bch::geometry(c.k);
   d->dec_geo_ = bch::geometry(c.n);
   if (d->dec_geo_.staged_words > bch::kMaxStagedWords || d->dec_geo_.lanes > bch::kThreads)
     return bail("frame too long for the BCH kernels");
   bch::generator_top(c, d->g_top_);
-  if (d->stream_.create() != hipSuccess || d->ev_default_.create() != hipSuccess) return bail("creating the BCH handle's stream failed");
+  if (!d->create_stream("the BCH handle's", err)) return nullptr;
   hipError_t e = hipSuccess;
   auto up = [&](DeviceBuffer &b, const auto &v) {
     if (e == hipSuccess) b = upload(v, &e);
@@ -61,50 +40,19 @@ DeviceBch *DeviceBch::create(const bch::Code &c, int device, std::string *err) {
 }
 
 // (the members free what they own, the stream last)
-DeviceBch::~DeviceBch() {
-  (void)hipSetDevice(device_);
-  if (stream_) (void)hipStreamSynchronize(stream_);
-}
-
-int DeviceBch::begin(hipStream_t stream, hipStream_t *s) {
-  BCH_TRY(hipSetDevice(device_));
-  *s = stream ? stream : static_cast<hipStream_t>(stream_);
-  if (!stream) {
-    // (the handle's stream is non-blocking: ordered explicitly after what the legacy default stream holds now)
-    BCH_TRY(hipEventRecord(ev_default_, nullptr));
-    BCH_TRY(hipStreamWaitEvent(*s, ev_default_, 0));
-  }
-  return 0;
-}
-
-int DeviceBch::end(hipStream_t stream, hipStream_t s) {
-  BCH_TRY(hipGetLastError());
-  if (!stream) BCH_TRY(hipStreamSynchronize(s));
-  return 0;
-}
+DeviceBch::~DeviceBch() { wait_idle(); }
 
 namespace {
-template <int NW, bool DECODE>
-void bch_remainder_pass(const uint8_t *in, uint8_t *out, uint32_t frames, uint32_t copy_len, uint32_t out_stride, uint32_t parity,
-                        const bch::Geometry &geo, const uint32_t *g_top, const uint32_t *table, const bch::DecodeArgs &d,
-                        hipStream_t s) {
-  bch::GeneratorTop<NW> top;
-  for (int w = 0; w < NW; w++) top.w[w] = g_top[w];
-  bch::remainder_kernel<NW, DECODE><<<frames, bch::kThreads, 0, s>>>(in, out, copy_len, out_stride, parity, geo, top, table, d);
-}
-
 template <bool DECODE>
 void bch_remainder_pass_nw(uint32_t nw, const uint8_t *in, uint8_t *out, uint32_t frames, uint32_t copy_len, uint32_t out_stride,
                            uint32_t parity, const bch::Geometry &geo, const uint32_t *g_top, const uint32_t *table,
                            const bch::DecodeArgs &d, hipStream_t s) {
-  switch (nw) {
-    case 1: return bch_remainder_pass<1, DECODE>(in, out, frames, copy_len, out_stride, parity, geo, g_top, table, d, s);
-    case 2: return bch_remainder_pass<2, DECODE>(in, out, frames, copy_len, out_stride, parity, geo, g_top, table, d, s);
-    case 3: return bch_remainder_pass<3, DECODE>(in, out, frames, copy_len, out_stride, parity, geo, g_top, table, d, s);
-    case 4: return bch_remainder_pass<4, DECODE>(in, out, frames, copy_len, out_stride, parity, geo, g_top, table, d, s);
-    case 5: return bch_remainder_pass<5, DECODE>(in, out, frames, copy_len, out_stride, parity, geo, g_top, table, d, s);
-    default: return bch_remainder_pass<6, DECODE>(in, out, frames, copy_len, out_stride, parity, geo, g_top, table, d, s);
-  }
+  with_int<1, 2, 3, 4, 5, 6>(static_cast<int>(nw), [&](auto words) {
+    constexpr int NW = decltype(words)::value;
+    bch::GeneratorTop<NW> top;
+    for (int w = 0; w < NW; w++) top.w[w] = g_top[w];
+    bch::remainder_kernel<NW, DECODE><<<frames, bch::kThreads, 0, s>>>(in, out, copy_len, out_stride, parity, geo, top, table, d);
+  });
 }
 }  // namespace
 
@@ -131,7 +79,7 @@ int DeviceBch::decode_device(const uint8_t *input, uint8_t *output, size_t outpu
     const uint32_t frames = static_cast<uint32_t>(std::min(kBchPassFrames, batch - b0));
     uint8_t *out = output + b0 * output_len;
     int32_t *err = errors ? errors + b0 : nullptr;
-    BCH_TRY(hipMemsetAsync(d_count_.get(), 0, sizeof(uint32_t), s));
+    STAGE_TRY(hipMemsetAsync(d_count_.get(), 0, sizeof(uint32_t), s));
     const bch::DecodeArgs d{c_.m, c_.t, d_antilog_.get<uint16_t>(), err, d_list_.get<uint32_t>(), d_count_.get<uint32_t>(),
                             d_synd_.get<uint16_t>()};
     bch_remainder_pass_nw<true>(c_.parity_words(), input + b0 * c_.n, out, frames, out_len, out_len, c_.parity, dec_geo_, g_top_,
@@ -150,41 +98,23 @@ size_t DeviceBch::stage_frames() const { return std::max<size_t>(std::min(kBchSt
 
 int DeviceBch::encode_host(const uint8_t *input, uint8_t *output, size_t batch) {
   if (batch == 0) return 0;
-  BCH_TRY(hipSetDevice(device_));
-  const size_t stage = std::min(batch, stage_frames());
-  BCH_TRY(d_in_.ensure(stage * c_.k, 256));
-  BCH_TRY(d_out_.ensure(stage * c_.n, 256));
-  for (size_t b0 = 0; b0 < batch; b0 += stage) {
-    const size_t frames = std::min(stage, batch - b0);
-    BCH_TRY(hipMemcpyAsync(d_in_.get(), input + b0 * c_.k, frames * c_.k, hipMemcpyHostToDevice, stream_));
-    if (int rc = encode_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), frames, stream_)) return rc;
-    BCH_TRY(hipMemcpyAsync(output + b0 * c_.n, d_out_.get(), frames * c_.n, hipMemcpyDeviceToHost, stream_));
-    // (the next stage overwrites the buffers this one reads)
-    BCH_TRY(hipStreamSynchronize(stream_));
-  }
-  return 0;
+  return staged_rows(input, c_.k, output, c_.n, batch, std::min(batch, stage_frames()), false, [&](size_t frames) {
+    return encode_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), frames, stream_);
+  });
 }
 
 int DeviceBch::decode_host(const uint8_t *input, uint8_t *output, size_t output_len, size_t batch, int32_t *errors) {
   if (batch == 0) return 0;
-  BCH_TRY(hipSetDevice(device_));
   const size_t stage = std::min(batch, stage_frames());
-  BCH_TRY(d_in_.ensure(stage * c_.n, 256));
-  BCH_TRY(d_out_.ensure(stage * output_len, 256));
-  if (errors) BCH_TRY(d_err_.ensure(stage * sizeof(int32_t), 256));
-  for (size_t b0 = 0; b0 < batch; b0 += stage) {
-    const size_t frames = std::min(stage, batch - b0);
-    BCH_TRY(hipMemcpyAsync(d_in_.get(), input + b0 * c_.n, frames * c_.n, hipMemcpyHostToDevice, stream_));
+  return staged(batch, stage, {{d_in_, c_.n}, {d_out_, output_len}, {d_err_, errors ? sizeof(int32_t) : 0}}, [&](size_t b0, size_t frames) {
+    STAGE_TRY(hipMemcpyAsync(d_in_.get(), input + b0 * c_.n, frames * c_.n, hipMemcpyHostToDevice, stream_));
     if (int rc = decode_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), output_len, frames,
                                errors ? d_err_.get<int32_t>() : nullptr, stream_))
       return rc;
-    BCH_TRY(hipMemcpyAsync(output + b0 * output_len, d_out_.get(), frames * output_len, hipMemcpyDeviceToHost, stream_));
-    if (errors) BCH_TRY(hipMemcpyAsync(errors + b0, d_err_.get(), frames * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
-    BCH_TRY(hipStreamSynchronize(stream_));
-  }
-  return 0;
+    STAGE_TRY(hipMemcpyAsync(output + b0 * output_len, d_out_.get(), frames * output_len, hipMemcpyDeviceToHost, stream_));
+    if (errors) STAGE_TRY(hipMemcpyAsync(errors + b0, d_err_.get(), frames * sizeof(int32_t), hipMemcpyDeviceToHost, stream_));
+    return 0;
+  });
 }
-
-#undef BCH_TRY
 
 }  // namespace ldpc

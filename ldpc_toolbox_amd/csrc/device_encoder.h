@@ -13,7 +13,7 @@
 #include <vector>
 
 #include "encoder.h"
-#include "hip_owned.h"
+#include "device_stage.h"
 
 namespace ldpc {
 
@@ -30,20 +30,16 @@ constexpr int staircase_form(size_t k) {
   return kp * 4 <= kEncLdsBudget ? 0 : (kp * 2 <= kEncLdsBudget ? 1 : 2);
 }
 
-class DeviceEncoder {
+class DeviceEncoder : public DeviceStage {
  public:
   // Uploads the tables of `enc` to GPU `device`.  pattern: empty, or a pattern whose length divides n.
   // nullptr (and *err) when there is no usable GPU or an allocation fails: there is no CPU path here.
   static DeviceEncoder *create(const Encoder &enc, const std::vector<uint8_t> &pattern, int device, std::string *err);
   ~DeviceEncoder();
-  DeviceEncoder(const DeviceEncoder &) = delete;
-  DeviceEncoder &operator=(const DeviceEncoder &) = delete;
 
-  int device() const { return device_; }
   size_t k() const { return k_; }
   size_t n() const { return n_; }
   size_t output_len() const { return out_len_; }
-  const std::string &last_error() const { return error_; }
 
   // input [batch][k] (a byte equal to 1 is a one), output [batch][output_len] bytes 0/1.  0, or -2 on a HIP failure.
   // Device pointers; stream: launch stream (nullptr = the handle's own stream, ordered after everything queued on the
@@ -53,30 +49,24 @@ class DeviceEncoder {
   int encode_host(const uint8_t *input, uint8_t *output, size_t batch);
 
  private:
-  DeviceEncoder() = default;
-  bool fail(const std::string &m, hipError_t e = hipSuccess);
+  explicit DeviceEncoder(int device) : DeviceStage("encoder", device) {}
   int grow(DeviceBuffer &b, size_t need);
   int launch_staircase(const uint8_t *in, uint8_t *cw, size_t batch, hipStream_t s);
   int launch_dense(const uint8_t *in, uint8_t *cw, size_t batch, hipStream_t s);
 
-  int device_ = -1;
   size_t k_ = 0, n_ = 0, m_ = 0, out_len_ = 0;
   bool staircase_ = false;
   size_t words_ = 0, m_pad_ = 0;
   uint32_t kept_ = 0, block_ = 0;
-  std::string error_;
-  // what the handle owns (hip_owned.h): the stream is declared first and so destroyed last
-  Stream stream_;
-  Event ev_default_;
+  // (beside the stream and the staging buffers of DeviceStage)
   // staircase: H0 in CSR form
   DeviceBuffer d_h0_ptr_, d_h0_idx_;
   // dense: G0 transposed, [words][m rounded up to 64] 64-bit words (a wave reads 64 rows of one word column at once)
   DeviceBuffer d_gen_t_;
   // puncturing: kept block j of the output is block d_keep_[j] of the codeword
   DeviceBuffer d_keep_;
-  // work buffers, grown on demand: bit-packed messages, row-sum prefixes + slice totals, full codewords before
-  // puncturing, and the staging buffers of the host entry
-  DeviceBuffer d_packed_, d_prefix_, d_cw_, d_in_, d_out_;
+  // work buffers, grown on demand: bit-packed messages, row-sum prefixes + slice totals, full codewords before puncturing
+  DeviceBuffer d_packed_, d_prefix_, d_cw_;
 };
 
 }  // namespace ldpc

@@ -1,8 +1,8 @@
-// Host side of the batched GPU encoder (device_encoder.h): tables, work buffers and launches.
+// Host side of the batched GPU encoder (device_encoder.h): tables, work buffers and launches (stream protocol and staging
+// loop: device_stage.h).
 // Included by simulator.hip -- the encoder shares the simulator's translation unit.
 #pragma once
 #include <algorithm>
-#include <cstdio>
 #include <memory>
 
 #include "device_encoder.h"
@@ -15,37 +15,16 @@ namespace {
 constexpr size_t kEncPassFrames = 4096;
 }  // namespace
 
-bool DeviceEncoder::fail(const std::string &m, hipError_t e) {
-  error_ = m;
-  if (e != hipSuccess) error_ += std::string(": ") + hipGetErrorString(e);
-  std::fprintf(stderr, "ldpc_toolbox (hip): encoder: %s\n", error_.c_str());
-  return false;
-}
-
-#define ENC_TRY(expr)                 \
-  do {                                \
-    hipError_t _e = (expr);           \
-    if (_e != hipSuccess) {           \
-      fail(#expr, _e);                \
-      return -2;                      \
-    }                                 \
-  } while (0)
-
 DeviceEncoder *DeviceEncoder::create(const Encoder &enc, const std::vector<uint8_t> &pattern, int device, std::string *err) {
   auto bail = [&](const std::string &m) -> DeviceEncoder * {
     if (err) *err = m;
     return nullptr;
   };
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return bail("no HIP device available: the batched encoder has no CPU path");
-  if (device < 0 || device >= count) return bail("HIP device index out of range");
-  if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice failed");
+  if (!select_device(device, "the batched encoder has", err)) return nullptr;
   const size_t n = enc.n(), k = enc.k(), m = n - k;
   if (n == 0 || n > 0x7fffffffu) return bail("codeword length out of range for the batched encoder");
   if (!pattern.empty() && n % pattern.size() != 0) return bail("the puncturing pattern does not divide the codeword length");
-  std::unique_ptr<DeviceEncoder> d(new DeviceEncoder());
-  d->device_ = device;
+  std::unique_ptr<DeviceEncoder> d(new DeviceEncoder(device));
   d->k_ = k;
   d->n_ = n;
   d->m_ = m;
@@ -78,19 +57,16 @@ DeviceEncoder *DeviceEncoder::create(const Encoder &enc, const std::vector<uint8
     d->out_len_ = size_t(d->block_) * d->kept_;
     ok = up(keep, &d->d_keep_);
   }
-  ok = ok && d->stream_.create() == hipSuccess && d->ev_default_.create() == hipSuccess;
+  ok = ok && d->create_stream() == hipSuccess;
   if (!ok) return bail("device allocation / upload of the encoder tables failed");
   return d.release();
 }
 
 // (the members free what they own, the stream last)
-DeviceEncoder::~DeviceEncoder() {
-  (void)hipSetDevice(device_);
-  if (stream_) (void)hipStreamSynchronize(stream_);
-}
+DeviceEncoder::~DeviceEncoder() { wait_idle(); }
 
 int DeviceEncoder::grow(DeviceBuffer &b, size_t need) {
-  ENC_TRY(b.ensure(need, 256));
+  STAGE_TRY(b.ensure(need, 256));
   return 0;
 }
 
@@ -169,17 +145,12 @@ int DeviceEncoder::launch_dense(const uint8_t *in, uint8_t *cw, size_t batch, hi
 
 int DeviceEncoder::encode_device(const uint8_t *input, uint8_t *output, size_t batch, hipStream_t stream) {
   if (batch == 0) return 0;
-  ENC_TRY(hipSetDevice(device_));
-  hipStream_t s = stream ? stream : stream_;
+  hipStream_t s;
+  if (int rc = begin(stream, &s)) return rc;
   uint8_t *cw = output;
   if (d_keep_) {  // the full codewords go to a buffer of the handle, the kept blocks from there to the output
     if (int rc = grow(d_cw_, batch * n_)) return rc;
     cw = d_cw_.get<uint8_t>();
-  }
-  if (!stream) {
-    // (the handle's stream is non-blocking: ordered explicitly after what the legacy default stream holds now)
-    ENC_TRY(hipEventRecord(ev_default_, nullptr));
-    ENC_TRY(hipStreamWaitEvent(s, ev_default_, 0));
   }
   if (int rc = staircase_ ? launch_staircase(input, cw, batch, s) : launch_dense(input, cw, batch, s)) return rc;
   if (d_keep_) {
@@ -188,24 +159,13 @@ int DeviceEncoder::encode_device(const uint8_t *input, uint8_t *output, size_t b
     if (total > 0)
       enc::puncture_kernel<<<blocks, 256, 0, s>>>(cw, output, d_keep_.get<uint32_t>(), static_cast<uint32_t>(n_), block_, kept_, total);
   }
-  ENC_TRY(hipGetLastError());
-  if (!stream) ENC_TRY(hipStreamSynchronize(s));
-  return 0;
+  return end(stream, s);
 }
 
 int DeviceEncoder::encode_host(const uint8_t *input, uint8_t *output, size_t batch) {
   if (batch == 0) return 0;
-  ENC_TRY(hipSetDevice(device_));
-  if (int rc = grow(d_in_, batch * k_)) return rc;
-  if (int rc = grow(d_out_, batch * out_len_)) return rc;
-  if (k_ > 0) ENC_TRY(hipMemcpyAsync(d_in_.get(), input, batch * k_, hipMemcpyHostToDevice, stream_));
-  if (int rc = encode_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), batch, stream_)) return rc;
-  // (the only write to the caller's buffer: after an earlier failure nothing has been written)
-  if (out_len_ > 0) ENC_TRY(hipMemcpyAsync(output, d_out_.get(), batch * out_len_, hipMemcpyDeviceToHost, stream_));
-  ENC_TRY(hipStreamSynchronize(stream_));
-  return 0;
+  return staged_rows(input, k_, output, out_len_, batch, batch, false,
+                     [&](size_t frames) { return encode_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), frames, stream_); });
 }
-
-#undef ENC_TRY
 
 }  // namespace ldpc

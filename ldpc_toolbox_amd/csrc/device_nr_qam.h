@@ -7,7 +7,7 @@
 #include <cstdint>
 #include <string>
 
-#include "hip_owned.h"
+#include "device_stage.h"
 #include "nr_qam.h"
 
 namespace ldpc {
@@ -25,16 +25,11 @@ void nr_qam_launch_harq_generator(const nrqam::Config &c, bool max_log, const ui
                                   uint64_t seed, uint64_t first_frame, const uint64_t *frame_ids, uint32_t frames, double sigma,
                                   uint32_t fading_block, float *llrs, hipStream_t s);
 
-class DeviceNrQam {
+class DeviceNrQam : public DeviceStage {
  public:
   // nullptr (and *err) when there is no usable GPU: there is no CPU path.
   static DeviceNrQam *create(const nrqam::Config &c, int device, std::string *err);
   ~DeviceNrQam();
-  DeviceNrQam(const DeviceNrQam &) = delete;
-  DeviceNrQam &operator=(const DeviceNrQam &) = delete;
-
-  int device() const { return device_; }
-  const std::string &last_error() const { return error_; }
   // how often the Gold kernel has run: a call with the (c_init, length) of the one before it does not run it again
   uint64_t sequence_launches() const { return sequence_launches_; }
 
@@ -69,20 +64,15 @@ class DeviceNrQam {
   int sequence_host(uint8_t *c, size_t len, uint32_t c_init);
 
  private:
-  DeviceNrQam() = default;
-  bool fail(const std::string &m, hipError_t e = hipSuccess);
-  int begin(hipStream_t stream, hipStream_t *s);
+  explicit DeviceNrQam(int device) : DeviceStage("NR modulation", device) {}
+  // DeviceStage::end, and before its wait the record of ev_gold_read_ behind a launch that read the sequence
   int end(hipStream_t stream, hipStream_t s, bool scrambled);
   // the sequence of (c_init, len) in d_gold_, generated on `s` unless it is the one already there: *c = its words, or
   // nullptr for c_init -1.  -2 on a HIP failure.
   int sequence(int64_t c_init, size_t len, hipStream_t s, const uint32_t **c);
 
   nrqam::Config c_;
-  int device_ = -1;
-  std::string error_;
-  // what the handle owns (hip_owned.h): the stream is declared first and so destroyed last
-  Stream stream_;
-  Event ev_default_;
+  // (beside the stream and the staging buffers of DeviceStage)
   // the cached sequence: ceil(len / 32) + 1 words; the stream that generated it, the event behind that launch, and the
   // event behind the last launch that read it, with that launch's stream.  A reader on another stream waits for the
   // event before it takes it over, so the event is behind every earlier reader and a later generation waits for it alone.
@@ -93,7 +83,7 @@ class DeviceNrQam {
   size_t gold_len_ = 0;
   uint64_t sequence_launches_ = 0;
   DeviceBuffer d_gold_;
-  DeviceBuffer d_in_, d_out_, d_scale_;  // the staging buffers of the host entries
+  DeviceBuffer d_scale_;  // the scales of demap_csi_host, beside d_in_ and d_out_
 };
 
 }  // namespace ldpc

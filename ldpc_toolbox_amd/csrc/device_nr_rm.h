@@ -7,7 +7,7 @@
 #include <cstdint>
 #include <string>
 
-#include "hip_owned.h"
+#include "device_stage.h"
 #include "nr_rate_match.h"
 
 namespace ldpc {
@@ -25,16 +25,11 @@ void nr_rm_launch_recover(const nrrm::Plan &p, const T *rx, T *llrs, size_t batc
 // 8-bit soft bits with saturating sums (include/ldpc_toolbox.h, PART 9); filler in 1..127; any byte addresses
 void nr_rm_launch_recover_i8(const nrrm::Plan &p, const int8_t *rx, int8_t *llrs, size_t batch, int32_t filler, bool combine, hipStream_t s);
 
-class DeviceNrRm {
+class DeviceNrRm : public DeviceStage {
  public:
   // nullptr (and *err) when there is no usable GPU: there is no CPU path.
   static DeviceNrRm *create(const nrrm::Config &c, int device, std::string *err);
   ~DeviceNrRm();
-  DeviceNrRm(const DeviceNrRm &) = delete;
-  DeviceNrRm &operator=(const DeviceNrRm &) = delete;
-
-  int device() const { return device_; }
-  const std::string &last_error() const { return error_; }
 
   // codewords [batch][n] -> output [batch][e].  0, or -2 on a HIP failure.  Device pointers; stream: launch stream
   // (nullptr = the handle's own stream, ordered after everything queued on the legacy default stream at the time of the
@@ -54,18 +49,9 @@ class DeviceNrRm {
   int recover_i8_host(const int8_t *rx, int8_t *llrs, size_t batch, uint32_t e, uint32_t rv, uint32_t qm, int32_t filler, bool combine);
 
  private:
-  DeviceNrRm() = default;
-  bool fail(const std::string &m, hipError_t e = hipSuccess);
-  int begin(hipStream_t stream, hipStream_t *s);
-  int end(hipStream_t stream, hipStream_t s);
+  explicit DeviceNrRm(int device) : DeviceStage("nr_rm", device) {}
 
   nrrm::Config c_;
-  int device_ = -1;
-  std::string error_;
-  // what the handle owns (hip_owned.h): the stream is declared first and so destroyed last
-  Stream stream_;
-  Event ev_default_;
-  DeviceBuffer d_in_, d_out_;  // the staging buffers of the host entries
 };
 
 }  // namespace ldpc

@@ -1,8 +1,8 @@
-// Host side of the batched NR rate matcher (device_nr_rm.h): the launches and the staged host entries.
+// Host side of the batched NR rate matcher (device_nr_rm.h): the launches and the entries; their stream protocol and staging
+// loop are device_stage.h's.
 // Included by simulator.hip -- it shares the simulator's translation unit, as the BCH code does.
 #pragma once
 #include <algorithm>
-#include <cstdio>
 #include <memory>
 
 #include "device_nr_rm.h"
@@ -57,60 +57,16 @@ void nr_rm_launch_recover_i8(const nrrm::Plan &p, const int8_t *rx, int8_t *llrs
   }
 }
 
-bool DeviceNrRm::fail(const std::string &m, hipError_t e) {
-  error_ = m;
-  if (e != hipSuccess) error_ += std::string(": ") + hipGetErrorString(e);
-  std::fprintf(stderr, "ldpc_toolbox (hip): nr_rm: %s\n", error_.c_str());
-  return false;
-}
-
-#define NRRM_TRY(expr)                \
-  do {                                \
-    hipError_t _e = (expr);           \
-    if (_e != hipSuccess) {           \
-      fail(#expr, _e);                \
-      return -2;                      \
-    }                                 \
-  } while (0)
-
 DeviceNrRm *DeviceNrRm::create(const nrrm::Config &c, int device, std::string *err) {
-  auto bail = [&](const std::string &m) -> DeviceNrRm * {
-    if (err) *err = m;
-    return nullptr;
-  };
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0) return bail("no HIP device available: the rate matcher has no CPU path");
-  if (device < 0 || device >= count) return bail("HIP device index out of range");
-  if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice failed");
-  std::unique_ptr<DeviceNrRm> d(new DeviceNrRm());
+  if (!select_device(device, "the rate matcher has", err)) return nullptr;
+  std::unique_ptr<DeviceNrRm> d(new DeviceNrRm(device));
   d->c_ = c;
-  d->device_ = device;
-  if (d->stream_.create() != hipSuccess || d->ev_default_.create() != hipSuccess) return bail("creating the rate matcher's stream failed");
+  if (!d->create_stream("the rate matcher's", err)) return nullptr;
   return d.release();
 }
 
 // (the members free what they own, the stream last)
-DeviceNrRm::~DeviceNrRm() {
-  (void)hipSetDevice(device_);
-  if (stream_) (void)hipStreamSynchronize(stream_);
-}
-
-int DeviceNrRm::begin(hipStream_t stream, hipStream_t *s) {
-  NRRM_TRY(hipSetDevice(device_));
-  *s = stream ? stream : static_cast<hipStream_t>(stream_);
-  if (!stream) {
-    // (the handle's stream is non-blocking: ordered explicitly after what the legacy default stream holds now)
-    NRRM_TRY(hipEventRecord(ev_default_, nullptr));
-    NRRM_TRY(hipStreamWaitEvent(*s, ev_default_, 0));
-  }
-  return 0;
-}
-
-int DeviceNrRm::end(hipStream_t stream, hipStream_t s) {
-  NRRM_TRY(hipGetLastError());
-  if (!stream) NRRM_TRY(hipStreamSynchronize(s));
-  return 0;
-}
+DeviceNrRm::~DeviceNrRm() { wait_idle(); }
 
 int DeviceNrRm::match_device(const uint8_t *codewords, uint8_t *output, size_t batch, uint32_t e, uint32_t rv, uint32_t qm,
                              hipStream_t stream) {
@@ -146,60 +102,29 @@ int DeviceNrRm::recover_i8_device(const int8_t *rx, int8_t *llrs, size_t batch, 
 
 int DeviceNrRm::match_host(const uint8_t *codewords, uint8_t *output, size_t batch, uint32_t e, uint32_t rv, uint32_t qm) {
   if (batch == 0) return 0;
-  NRRM_TRY(hipSetDevice(device_));
   const size_t stage = std::min(batch, std::max<size_t>(kNrRmStageBytes / std::max<size_t>(c_.n, e), 1));
-  NRRM_TRY(d_in_.ensure(stage * c_.n, 256));
-  NRRM_TRY(d_out_.ensure(stage * e, 256));
-  for (size_t b0 = 0; b0 < batch; b0 += stage) {
-    const size_t frames = std::min(stage, batch - b0);
-    NRRM_TRY(hipMemcpyAsync(d_in_.get(), codewords + b0 * c_.n, frames * c_.n, hipMemcpyHostToDevice, stream_));
-    if (int rc = match_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), frames, e, rv, qm, stream_)) return rc;
-    NRRM_TRY(hipMemcpyAsync(output + b0 * e, d_out_.get(), frames * e, hipMemcpyDeviceToHost, stream_));
-    // (the next stage overwrites the buffers this one reads)
-    NRRM_TRY(hipStreamSynchronize(stream_));
-  }
-  return 0;
+  return staged_rows(codewords, c_.n, output, e, batch, stage, false, [&](size_t frames) {
+    return match_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), frames, e, rv, qm, stream_);
+  });
 }
 
 int DeviceNrRm::recover_host(const void *rx, void *llrs, bool f64, size_t batch, uint32_t e, uint32_t rv, uint32_t qm,
                              double filler_llr, bool combine) {
   if (batch == 0) return 0;
-  NRRM_TRY(hipSetDevice(device_));
   const size_t el = f64 ? sizeof(double) : sizeof(float);
   const size_t stage = std::min(batch, std::max<size_t>(kNrRmStageBytes / (std::max<size_t>(c_.n, e) * el), 1));
-  NRRM_TRY(d_in_.ensure(stage * e * el, 256));
-  NRRM_TRY(d_out_.ensure(stage * c_.n * el, 256));
-  const char *src = static_cast<const char *>(rx);
-  char *dst = static_cast<char *>(llrs);
-  for (size_t b0 = 0; b0 < batch; b0 += stage) {
-    const size_t frames = std::min(stage, batch - b0);
-    NRRM_TRY(hipMemcpyAsync(d_in_.get(), src + b0 * e * el, frames * e * el, hipMemcpyHostToDevice, stream_));
-    if (combine) NRRM_TRY(hipMemcpyAsync(d_out_.get(), dst + b0 * c_.n * el, frames * c_.n * el, hipMemcpyHostToDevice, stream_));
-    if (int rc = recover_device(d_in_.get(), d_out_.get(), f64, frames, e, rv, qm, filler_llr, combine, stream_)) return rc;
-    NRRM_TRY(hipMemcpyAsync(dst + b0 * c_.n * el, d_out_.get(), frames * c_.n * el, hipMemcpyDeviceToHost, stream_));
-    NRRM_TRY(hipStreamSynchronize(stream_));
-  }
-  return 0;
+  return staged_rows(rx, e * el, llrs, c_.n * el, batch, stage, combine, [&](size_t frames) {
+    return recover_device(d_in_.get(), d_out_.get(), f64, frames, e, rv, qm, filler_llr, combine, stream_);
+  });
 }
 
 int DeviceNrRm::recover_i8_host(const int8_t *rx, int8_t *llrs, size_t batch, uint32_t e, uint32_t rv, uint32_t qm, int32_t filler,
                                 bool combine) {
   if (batch == 0) return 0;
-  NRRM_TRY(hipSetDevice(device_));
   const size_t stage = std::min(batch, std::max<size_t>(kNrRmStageBytes / std::max<size_t>(c_.n, e), 1));
-  NRRM_TRY(d_in_.ensure(stage * e, 256));
-  NRRM_TRY(d_out_.ensure(stage * c_.n, 256));
-  for (size_t b0 = 0; b0 < batch; b0 += stage) {
-    const size_t frames = std::min(stage, batch - b0);
-    NRRM_TRY(hipMemcpyAsync(d_in_.get(), rx + b0 * e, frames * e, hipMemcpyHostToDevice, stream_));
-    if (combine) NRRM_TRY(hipMemcpyAsync(d_out_.get(), llrs + b0 * c_.n, frames * c_.n, hipMemcpyHostToDevice, stream_));
-    if (int rc = recover_i8_device(d_in_.get<int8_t>(), d_out_.get<int8_t>(), frames, e, rv, qm, filler, combine, stream_)) return rc;
-    NRRM_TRY(hipMemcpyAsync(llrs + b0 * c_.n, d_out_.get(), frames * c_.n, hipMemcpyDeviceToHost, stream_));
-    NRRM_TRY(hipStreamSynchronize(stream_));
-  }
-  return 0;
+  return staged_rows(rx, e, llrs, c_.n, batch, stage, combine, [&](size_t frames) {
+    return recover_i8_device(d_in_.get<int8_t>(), d_out_.get<int8_t>(), frames, e, rv, qm, filler, combine, stream_);
+  });
 }
-
-#undef NRRM_TRY
 
 }  // namespace ldpc

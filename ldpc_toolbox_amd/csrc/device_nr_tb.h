@@ -7,7 +7,7 @@
 #include <cstdint>
 #include <string>
 
-#include "hip_owned.h"
+#include "device_stage.h"
 #include "nr_transport_block.h"
 
 namespace ldpc {
@@ -19,16 +19,11 @@ constexpr size_t kNrTbPassElements = size_t(1) << 30;
 // what a host entry stages on the device at a time: about this many bytes of its longest side
 constexpr size_t kNrTbStageBytes = size_t(1) << 28;
 
-class DeviceNrTb {
+class DeviceNrTb : public DeviceStage {
  public:
   // nullptr (and *err) when there is no usable GPU: there is no CPU path.
   static DeviceNrTb *create(const nrtb::Config &c, int device, std::string *err);
   ~DeviceNrTb();
-  DeviceNrTb(const DeviceNrTb &) = delete;
-  DeviceNrTb &operator=(const DeviceNrTb &) = delete;
-
-  int device() const { return device_; }
-  const std::string &last_error() const { return error_; }
 
   // Device pointers; 0, or -2 on a HIP failure.  stream: launch stream (nullptr = the handle's own stream, ordered after
   // everything queued on the legacy default stream at the time of the call, and synchronised on return).  The CRC parts
@@ -48,24 +43,16 @@ class DeviceNrTb {
   int split_host(const void *rx, void *packed, bool f64, const nrtb::Lengths &l, size_t batch);
 
  private:
-  DeviceNrTb() = default;
-  bool fail(const std::string &m, hipError_t e = hipSuccess);
-  int begin(hipStream_t stream, hipStream_t *s);
-  int end(hipStream_t stream, hipStream_t s);
+  explicit DeviceNrTb(int device) : DeviceStage("nr_tb", device) {}
   // block-major rows between a host array over `batch` transport blocks and a device array over `frames` of them
   int copy_rows(char *dst, const char *src, size_t blocks, size_t row_bytes, size_t batch, size_t b0, size_t frames, bool to_device);
   int copy_packed(char *dev, char *host, const nrtb::Lengths &l, size_t el, size_t batch, size_t b0, size_t frames, bool to_device);
 
   nrtb::Config c_;
-  int device_ = -1;
-  std::string error_;
-  // what the handle owns (hip_owned.h): the stream is declared first and so destroyed last
-  Stream stream_;
-  Event ev_default_;
-  DeviceBuffer d_tables_;      // nrtb::device_tables
-  DeviceBuffer d_part_;        // the CRC parts of a pass
-  DeviceBuffer d_in_, d_out_;  // the staging buffers of the host entries
-  DeviceBuffer d_flags_;       // tb_ok and cb_ok of a stage
+  // (beside the stream and the staging buffers of DeviceStage)
+  DeviceBuffer d_tables_;  // nrtb::device_tables
+  DeviceBuffer d_part_;    // the CRC parts of a pass
+  DeviceBuffer d_flags_;   // tb_ok and cb_ok of a stage
 };
 
 }  // namespace ldpc

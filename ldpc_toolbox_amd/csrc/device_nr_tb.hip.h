@@ -1,8 +1,8 @@
-// Host side of the batched NR transport block processing (device_nr_tb.h): the launches and the staged host entries.
+// Host side of the batched NR transport block processing (device_nr_tb.h): the launches and the strided copies of the host
+// entries; their stream protocol and staging loop are device_stage.h's.
 // Included by simulator.hip -- it shares the simulator's translation unit, as the rate matcher does.
 #pragma once
 #include <algorithm>
-#include <cstdio>
 #include <memory>
 
 #include "device_nr_tb.h"
@@ -10,64 +10,22 @@
 
 namespace ldpc {
 
-bool DeviceNrTb::fail(const std::string &m, hipError_t e) {
-  error_ = m;
-  if (e != hipSuccess) error_ += std::string(": ") + hipGetErrorString(e);
-  std::fprintf(stderr, "ldpc_toolbox (hip): nr_tb: %s\n", error_.c_str());
-  return false;
-}
-
-#define NRTB_TRY(expr)                \
-  do {                                \
-    hipError_t _e = (expr);           \
-    if (_e != hipSuccess) {           \
-      fail(#expr, _e);                \
-      return -2;                      \
-    }                                 \
-  } while (0)
-
 DeviceNrTb *DeviceNrTb::create(const nrtb::Config &c, int device, std::string *err) {
-  auto bail = [&](const std::string &m) -> DeviceNrTb * {
-    if (err) *err = m;
-    return nullptr;
-  };
-  int count = 0;
-  if (hipGetDeviceCount(&count) != hipSuccess || count <= 0)
-    return bail("no HIP device available: the transport block entries have no CPU path");
-  if (device < 0 || device >= count) return bail("HIP device index out of range");
-  if (hipSetDevice(device) != hipSuccess) return bail("hipSetDevice failed");
-  std::unique_ptr<DeviceNrTb> d(new DeviceNrTb());
+  if (!select_device(device, "the transport block entries have", err)) return nullptr;
+  std::unique_ptr<DeviceNrTb> d(new DeviceNrTb(device));
   d->c_ = c;
-  d->device_ = device;
-  if (d->stream_.create() != hipSuccess || d->ev_default_.create() != hipSuccess) return bail("creating the handle's stream failed");
+  if (!d->create_stream("the handle's", err)) return nullptr;
   hipError_t e;
   d->d_tables_ = upload(nrtb::device_tables(c), &e);
-  if (e != hipSuccess) return bail(std::string("uploading the CRC tables failed: ") + hipGetErrorString(e));
+  if (e != hipSuccess) {
+    if (err) *err = std::string("uploading the CRC tables failed: ") + hipGetErrorString(e);
+    return nullptr;
+  }
   return d.release();
 }
 
 // (the members free what they own, the stream last)
-DeviceNrTb::~DeviceNrTb() {
-  (void)hipSetDevice(device_);
-  if (stream_) (void)hipStreamSynchronize(stream_);
-}
-
-int DeviceNrTb::begin(hipStream_t stream, hipStream_t *s) {
-  NRTB_TRY(hipSetDevice(device_));
-  *s = stream ? stream : static_cast<hipStream_t>(stream_);
-  if (!stream) {
-    // (the handle's stream is non-blocking: ordered explicitly after what the legacy default stream holds now)
-    NRTB_TRY(hipEventRecord(ev_default_, nullptr));
-    NRTB_TRY(hipStreamWaitEvent(*s, ev_default_, 0));
-  }
-  return 0;
-}
-
-int DeviceNrTb::end(hipStream_t stream, hipStream_t s) {
-  NRTB_TRY(hipGetLastError());
-  if (!stream) NRTB_TRY(hipStreamSynchronize(s));
-  return 0;
-}
+DeviceNrTb::~DeviceNrTb() { wait_idle(); }
 
 namespace {
 nrtb::RowArgs nr_tb_row_args(const nrtb::Config &c, const uint32_t *tables, size_t batch, size_t b0, size_t frames) {
@@ -95,7 +53,7 @@ int DeviceNrTb::segment_device(const uint8_t *payload, uint8_t *rows, size_t bat
   hipStream_t s;
   if (int rc = begin(stream, &s)) return rc;
   const size_t pass = std::max<size_t>(kNrTbPassRows / c_.c, 1);
-  NRTB_TRY(d_part_.ensure((size_t(c_.c) + 1) * std::min(pass, batch) * sizeof(uint32_t), 256));
+  STAGE_TRY(d_part_.ensure((size_t(c_.c) + 1) * std::min(pass, batch) * sizeof(uint32_t), 256));
   for (size_t b0 = 0; b0 < batch; b0 += pass) {
     const size_t frames = std::min(pass, batch - b0);
     const nrtb::RowArgs p = nr_tb_row_args(c_, d_tables_.get<uint32_t>(), batch, b0, frames);
@@ -111,7 +69,7 @@ int DeviceNrTb::desegment_device(const uint8_t *rows, uint8_t *payload, uint8_t 
   hipStream_t s;
   if (int rc = begin(stream, &s)) return rc;
   const size_t pass = std::max<size_t>(kNrTbPassRows / c_.c, 1);
-  NRTB_TRY(d_part_.ensure((size_t(c_.c) + 1) * std::min(pass, batch) * sizeof(uint32_t), 256));
+  STAGE_TRY(d_part_.ensure((size_t(c_.c) + 1) * std::min(pass, batch) * sizeof(uint32_t), 256));
   for (size_t b0 = 0; b0 < batch; b0 += pass) {
     const size_t frames = std::min(pass, batch - b0);
     const nrtb::RowArgs p = nr_tb_row_args(c_, d_tables_.get<uint32_t>(), batch, b0, frames);
@@ -161,9 +119,9 @@ int DeviceNrTb::copy_rows(char *dst, const char *src, size_t blocks, size_t row_
   for (size_t r = 0; r < blocks; r++) {
     const size_t host_at = (r * batch + b0) * row_bytes, dev_at = r * frames * row_bytes;
     if (to_device)
-      NRTB_TRY(hipMemcpyAsync(dst + dev_at, src + host_at, frames * row_bytes, hipMemcpyHostToDevice, stream_));
+      STAGE_TRY(hipMemcpyAsync(dst + dev_at, src + host_at, frames * row_bytes, hipMemcpyHostToDevice, stream_));
     else
-      NRTB_TRY(hipMemcpyAsync(dst + host_at, src + dev_at, frames * row_bytes, hipMemcpyDeviceToHost, stream_));
+      STAGE_TRY(hipMemcpyAsync(dst + host_at, src + dev_at, frames * row_bytes, hipMemcpyDeviceToHost, stream_));
   }
   return 0;
 }
@@ -180,76 +138,50 @@ int DeviceNrTb::copy_packed(char *dev, char *host, const nrtb::Lengths &l, size_
 
 int DeviceNrTb::segment_host(const uint8_t *payload, uint8_t *rows, size_t batch) {
   if (batch == 0) return 0;
-  NRTB_TRY(hipSetDevice(device_));
   const size_t per_tb = size_t(c_.c) * c_.k;
   const size_t stage = std::min(batch, std::max<size_t>(kNrTbStageBytes / per_tb, 1));
-  NRTB_TRY(d_in_.ensure(stage * c_.a, 256));
-  NRTB_TRY(d_out_.ensure(stage * per_tb, 256));
-  for (size_t b0 = 0; b0 < batch; b0 += stage) {
-    const size_t frames = std::min(stage, batch - b0);
-    NRTB_TRY(hipMemcpyAsync(d_in_.get(), payload + b0 * c_.a, frames * c_.a, hipMemcpyHostToDevice, stream_));
+  return staged(batch, stage, {{d_in_, c_.a}, {d_out_, per_tb}}, [&](size_t b0, size_t frames) {
+    STAGE_TRY(hipMemcpyAsync(d_in_.get(), payload + b0 * c_.a, frames * c_.a, hipMemcpyHostToDevice, stream_));
     if (int rc = segment_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), frames, stream_)) return rc;
-    if (int rc = copy_rows(reinterpret_cast<char *>(rows), d_out_.get<char>(), c_.c, c_.k, batch, b0, frames, false)) return rc;
-    // (the next stage overwrites the buffers this one reads)
-    NRTB_TRY(hipStreamSynchronize(stream_));
-  }
-  return 0;
+    return copy_rows(reinterpret_cast<char *>(rows), d_out_.get<char>(), c_.c, c_.k, batch, b0, frames, false);
+  });
 }
 
 int DeviceNrTb::desegment_host(const uint8_t *rows, uint8_t *payload, uint8_t *tb_ok, uint8_t *cb_ok, size_t batch) {
   if (batch == 0) return 0;
-  NRTB_TRY(hipSetDevice(device_));
   const size_t per_tb = size_t(c_.c) * c_.k;
   const size_t stage = std::min(batch, std::max<size_t>(kNrTbStageBytes / per_tb, 1));
-  NRTB_TRY(d_in_.ensure(stage * per_tb, 256));
-  NRTB_TRY(d_out_.ensure(stage * c_.a, 256));
-  NRTB_TRY(d_flags_.ensure(stage * (size_t(c_.c) + 1), 256));
-  uint8_t *d_tb = d_flags_.get<uint8_t>(), *d_cb = d_tb + stage;
-  for (size_t b0 = 0; b0 < batch; b0 += stage) {
-    const size_t frames = std::min(stage, batch - b0);
+  return staged(batch, stage, {{d_in_, per_tb}, {d_out_, c_.a}, {d_flags_, size_t(c_.c) + 1}}, [&](size_t b0, size_t frames) {
+    uint8_t *d_tb = d_flags_.get<uint8_t>(), *d_cb = d_tb + stage;
     if (int rc = copy_rows(d_in_.get<char>(), reinterpret_cast<const char *>(rows), c_.c, c_.k, batch, b0, frames, true)) return rc;
     if (int rc = desegment_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), d_tb, cb_ok ? d_cb : nullptr, frames, stream_)) return rc;
-    NRTB_TRY(hipMemcpyAsync(payload + b0 * c_.a, d_out_.get(), frames * c_.a, hipMemcpyDeviceToHost, stream_));
-    NRTB_TRY(hipMemcpyAsync(tb_ok + b0, d_tb, frames, hipMemcpyDeviceToHost, stream_));
-    if (cb_ok) NRTB_TRY(hipMemcpyAsync(cb_ok + b0 * c_.c, d_cb, frames * c_.c, hipMemcpyDeviceToHost, stream_));
-    NRTB_TRY(hipStreamSynchronize(stream_));
-  }
-  return 0;
+    STAGE_TRY(hipMemcpyAsync(payload + b0 * c_.a, d_out_.get(), frames * c_.a, hipMemcpyDeviceToHost, stream_));
+    STAGE_TRY(hipMemcpyAsync(tb_ok + b0, d_tb, frames, hipMemcpyDeviceToHost, stream_));
+    if (cb_ok) STAGE_TRY(hipMemcpyAsync(cb_ok + b0 * c_.c, d_cb, frames * c_.c, hipMemcpyDeviceToHost, stream_));
+    return 0;
+  });
 }
 
 int DeviceNrTb::concatenate_host(const uint8_t *packed, uint8_t *output, const nrtb::Lengths &l, size_t batch) {
   if (batch == 0) return 0;
-  NRTB_TRY(hipSetDevice(device_));
   const size_t stage = std::min(batch, std::max<size_t>(kNrTbStageBytes / l.g, 1));
-  NRTB_TRY(d_in_.ensure(stage * l.g, 256));
-  NRTB_TRY(d_out_.ensure(stage * l.g, 256));
-  for (size_t b0 = 0; b0 < batch; b0 += stage) {
-    const size_t frames = std::min(stage, batch - b0);
+  return staged(batch, stage, {{d_in_, l.g}, {d_out_, l.g}}, [&](size_t b0, size_t frames) {
     if (int rc = copy_packed(d_in_.get<char>(), const_cast<char *>(reinterpret_cast<const char *>(packed)), l, 1, batch, b0, frames, true)) return rc;
     if (int rc = concatenate_device(d_in_.get<uint8_t>(), d_out_.get<uint8_t>(), l, frames, stream_)) return rc;
-    NRTB_TRY(hipMemcpyAsync(output + b0 * l.g, d_out_.get(), frames * l.g, hipMemcpyDeviceToHost, stream_));
-    NRTB_TRY(hipStreamSynchronize(stream_));
-  }
-  return 0;
+    STAGE_TRY(hipMemcpyAsync(output + b0 * l.g, d_out_.get(), frames * l.g, hipMemcpyDeviceToHost, stream_));
+    return 0;
+  });
 }
 
 int DeviceNrTb::split_host(const void *rx, void *packed, bool f64, const nrtb::Lengths &l, size_t batch) {
   if (batch == 0) return 0;
-  NRTB_TRY(hipSetDevice(device_));
   const size_t el = f64 ? sizeof(double) : sizeof(float);
   const size_t stage = std::min(batch, std::max<size_t>(kNrTbStageBytes / (size_t(l.g) * el), 1));
-  NRTB_TRY(d_in_.ensure(stage * l.g * el, 256));
-  NRTB_TRY(d_out_.ensure(stage * l.g * el, 256));
-  for (size_t b0 = 0; b0 < batch; b0 += stage) {
-    const size_t frames = std::min(stage, batch - b0);
-    NRTB_TRY(hipMemcpyAsync(d_in_.get(), static_cast<const char *>(rx) + b0 * l.g * el, frames * l.g * el, hipMemcpyHostToDevice, stream_));
+  return staged(batch, stage, {{d_in_, l.g * el}, {d_out_, l.g * el}}, [&](size_t b0, size_t frames) {
+    STAGE_TRY(hipMemcpyAsync(d_in_.get(), static_cast<const char *>(rx) + b0 * l.g * el, frames * l.g * el, hipMemcpyHostToDevice, stream_));
     if (int rc = split_device(d_in_.get(), d_out_.get(), f64, l, frames, stream_)) return rc;
-    if (int rc = copy_packed(d_out_.get<char>(), static_cast<char *>(packed), l, el, batch, b0, frames, false)) return rc;
-    NRTB_TRY(hipStreamSynchronize(stream_));
-  }
-  return 0;
+    return copy_packed(d_out_.get<char>(), static_cast<char *>(packed), l, el, batch, b0, frames, false);
+  });
 }
-
-#undef NRTB_TRY
 
 }  // namespace ldpc

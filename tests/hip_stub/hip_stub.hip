@@ -13,6 +13,10 @@
 //     creation order, grid, block, dynamic LDS bytes and the kernel's demangled name (hip_stub_trace_note adds a "# ..."
 //     line) -- and "malloc <bytes>" per hipMalloc, "hostmalloc <bytes>" per hipHostMalloc, "h2d <bytes> <FNV-1a of the
 //     bytes, 64 bits>" per synchronous host-to-device hipMemcpy: what the library allocates and the tables it uploads;
+//   * HIP_STUB_TRACE_CALLS (beside HIP_STUB_TRACE) adds one line for each hipSetDevice, hipMemcpyAsync (kind, bytes, stream
+//     ordinal), hipMemsetAsync, hipEventRecord and hipStreamWaitEvent (the event's ordinal in creation order, the stream's),
+//     hipStreamSynchronize and hipGetLastError, written as the call is entered: the host's whole call sequence around its
+//     launches, so that two builds of the library can be compared call by call (`tsan_driver stages`);
 //   * hip_stub_live counts what has been created and not yet given back: device and pinned allocations, events, streams.
 // Built with the same host-only clang mode as the library objects it is linked with (it needs dev::State).
 #include <cxxabi.h>
@@ -102,7 +106,9 @@ struct EventState {
 };
 // (the handle owns a reference, and so does every queued closure: destroying an event that streams still refer to is
 // legal in HIP)
+std::atomic<unsigned> g_events{0};
 struct Event {
+  const unsigned ordinal = g_events++;  // in creation order (HIP_STUB_TRACE_CALLS)
   std::shared_ptr<EventState> st = std::make_shared<EventState>();
 };
 
@@ -141,6 +147,11 @@ void trace_line(const std::string &line) {
   std::fputs(line.c_str(), f);
   std::fputc('\n', f);
   std::fflush(f);
+}
+// HIP_STUB_TRACE_CALLS: the runtime calls around the launches as well
+bool trace_calls() {
+  static const bool on = std::getenv("HIP_STUB_TRACE_CALLS") != nullptr;
+  return on;
 }
 std::string demangled(const std::string &name) {
   int status = 0;
@@ -181,7 +192,8 @@ hipError_t hipGetDeviceCount(int *count) {
   *count = 1;
   return hipSuccess;
 }
-hipError_t hipSetDevice(int) {
+hipError_t hipSetDevice(int device) {
+  if (trace_calls()) trace_line("setdevice " + std::to_string(device));
   STUB_FAIL("hipSetDevice");
   return hipSuccess;
 }
@@ -195,7 +207,10 @@ hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int *blocks, const void 
 }
 hipError_t hipFuncSetAttribute(const void *, hipFuncAttribute, int) { return hipSuccess; }
 std::atomic<int> g_last_error{0};  // a failed kernel launch is reported by the next hipGetLastError, as in HIP
-hipError_t hipGetLastError(void) { return static_cast<hipError_t>(g_last_error.exchange(0)); }
+hipError_t hipGetLastError(void) {
+  if (trace_calls()) trace_line("getlasterror");
+  return static_cast<hipError_t>(g_last_error.exchange(0));
+}
 const char *hipGetErrorString(hipError_t e) { return e == hipSuccess ? "no error" : "injected by the HIP stub"; }
 
 static hipError_t allocate(void **p, size_t bytes, const char *what, int live) {
@@ -246,6 +261,7 @@ hipError_t hipStreamDestroy(hipStream_t s) {
   return hipSuccess;
 }
 hipError_t hipStreamSynchronize(hipStream_t s) {
+  if (trace_calls()) trace_line("streamsync " + std::to_string(as_stream(s)->ordinal));
   as_stream(s)->sync();
   STUB_FAIL("hipStreamSynchronize");
   return hipSuccess;
@@ -265,6 +281,8 @@ hipError_t hipEventDestroy(hipEvent_t e) {
   return hipSuccess;
 }
 hipError_t hipEventRecord(hipEvent_t ev, hipStream_t s) {
+  if (trace_calls())
+    trace_line("eventrecord " + std::to_string(reinterpret_cast<Event *>(ev)->ordinal) + " " + std::to_string(as_stream(s)->ordinal));
   STUB_FAIL("hipEventRecord");
   std::shared_ptr<EventState> e = reinterpret_cast<Event *>(ev)->st;
   uint64_t gen;
@@ -282,6 +300,8 @@ hipError_t hipEventRecord(hipEvent_t ev, hipStream_t s) {
   return hipSuccess;
 }
 hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t ev, unsigned int) {
+  if (trace_calls())
+    trace_line("streamwaitevent " + std::to_string(as_stream(s)->ordinal) + " " + std::to_string(reinterpret_cast<Event *>(ev)->ordinal));
   STUB_FAIL("hipStreamWaitEvent");
   std::shared_ptr<EventState> e = reinterpret_cast<Event *>(ev)->st;
   uint64_t target;
@@ -306,7 +326,11 @@ hipError_t hipEventElapsedTime(float *ms, hipEvent_t, hipEvent_t) {
   return hipSuccess;
 }
 
-hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind, hipStream_t s) {
+hipError_t hipMemcpyAsync(void *dst, const void *src, size_t bytes, hipMemcpyKind kind, hipStream_t s) {
+  if (trace_calls()) {
+    const char *k = kind == hipMemcpyHostToDevice ? "h2d" : kind == hipMemcpyDeviceToHost ? "d2h" : kind == hipMemcpyDeviceToDevice ? "d2d" : "other";
+    trace_line(std::string("memcpyasync ") + k + " " + std::to_string(bytes) + " " + std::to_string(as_stream(s)->ordinal));
+  }
   STUB_FAIL("hipMemcpyAsync");
   as_stream(s)->push([=] { std::memcpy(dst, src, bytes); });
   return hipSuccess;
@@ -325,6 +349,7 @@ hipError_t hipMemcpy(void *dst, const void *src, size_t bytes, hipMemcpyKind kin
   return hipSuccess;
 }
 hipError_t hipMemsetAsync(void *dst, int value, size_t bytes, hipStream_t s) {
+  if (trace_calls()) trace_line("memsetasync " + std::to_string(bytes) + " " + std::to_string(as_stream(s)->ordinal));
   as_stream(s)->push([=] { std::memset(dst, value, bytes); });
   return hipSuccess;
 }

@@ -123,6 +123,58 @@ def test_host_threads_are_clean_under_tsan(tmp_path_factory):
         assert r.returncode == 0 and "tsan driver: ok" in r.stdout, (extra, text[-3000:])
 
 
+def test_stage_handles_under_tsan(tmp_path_factory, tmp_path):
+    """The six stage handles beside the decoder (rate matcher, transport block, NR modulation, BCH, demodulator, batched
+    encoder; csrc/device_stage.h holds what they share) and the simulator's NR generators, driven through the C ABI by
+    `tsan_driver stages`: host entry and _device entry of every call, single-stage shapes.  Plainly: no report, nothing
+    live at the end.  Then with one HIP call failing inside a stage-handle call -- the ordinals are read from the plain
+    run's call trace (HIP_STUB_TRACE_CALLS), by the driver's note of the call they fall into:
+      hipMalloc             the Gold sequence buffer of the first scrambled 16QAM call (DeviceNrQam::sequence);
+      hipMemcpyAsync        the first strided copy to the device of a two-block transport block's desegment (copy_rows);
+      hipStreamSynchronize  the wait that closes the stage of a BCH decode_host (the staging loop of device_stage.h);
+      hipEventRecord        the record behind a 64QAM launch that read the cached sequence (DeviceNrQam::end), the second
+                            record of that call after begin()'s.
+    Each must surface as LDPC_TOOLBOX_ERR_DEVICE from that call alone, with the failed expression as the message, the
+    calls after it succeeding and nothing live at the end."""
+    exe = _tsan_driver(tmp_path_factory)
+    trace = tmp_path / "stages.txt"
+    base = dict(os.environ, TSAN_OPTIONS="halt_on_error=0 exitcode=66")
+    nothing_live = "live after the last handle: device 0 pinned 0 events 0 streams 0"
+
+    r = subprocess.run([exe, "stages"], capture_output=True, text=True, timeout=600,
+                       env=dict(base, HIP_STUB_TRACE=str(trace), HIP_STUB_TRACE_CALLS="1"))
+    text = r.stdout + r.stderr
+    assert "ThreadSanitizer" not in text, text[-6000:]
+    assert r.returncode == 0 and "stages: ok" in r.stdout and nothing_live in r.stdout, text[-3000:]
+    lines = trace.read_text().splitlines()
+
+    def ordinal(note, prefix, nth=1):
+        """of all `prefix` lines of the trace, the 1-based position of the nth one within the call `note`"""
+        at = lines.index("# " + note)
+        end = next(i for i in range(at + 1, len(lines)) if lines[i].startswith("# "))
+        inside = [i for i in range(at + 1, end) if lines[i].startswith(prefix)]
+        return sum(1 for line in lines[:inside[nth - 1] + 1] if line.startswith(prefix))
+
+    failures = [
+        ("hipMalloc", ordinal("nr_qam QM=4 mod f32 host c_init=7", "malloc "),
+         "nr_qam QM=4 mod f32 host c_init=7", "d_gold_.ensure("),
+        ("hipMemcpyAsync", ordinal("nr_tb C=2 desegment host cb_ok", "memcpyasync "),
+         "nr_tb C=2 desegment host cb_ok", "hipMemcpyAsync(dst + dev_at, src + host_at"),
+        ("hipStreamSynchronize", ordinal("bch decode host, errors", "streamsync "),
+         "bch decode host, errors", "hipStreamSynchronize(stream_)"),
+        ("hipEventRecord", ordinal("nr_qam QM=6 demod f64 device max-log c_init=7", "eventrecord ", 2),
+         "nr_qam QM=6 demod f64 device max-log c_init=7", "hipEventRecord(ev_gold_read_, s)"),
+    ]
+    for function, n, note, expression in failures:
+        r = subprocess.run([exe, "stages", "1"], capture_output=True, text=True, timeout=600,
+                           env=dict(base, HIP_STUB_FAIL="%s:%d" % (function, n)))
+        text = r.stdout + r.stderr
+        assert "ThreadSanitizer" not in text, (function, n, text[-6000:])
+        assert r.returncode == 0 and "stages: ok" in r.stdout and nothing_live in r.stdout, (function, n, text[-3000:])
+        failed = [line for line in r.stdout.splitlines() if line.startswith("stages: ") and ": rc " in line]
+        assert len(failed) == 1 and failed[0].startswith("stages: %s: rc -2: %s" % (note, expression)), (function, n, failed)
+
+
 def test_launch_trace_keeps_the_arithmetic_and_the_pack_width(tmp_path_factory, tmp_path):
     """Which kernel a launch names decides the arithmetic (normalized / offset min-sum: the x_kernel<..., MinsumCorr<T>>
     instantiations) and must respect the pack width of the type (f64: at most two codewords per lane).  `tsan_driver

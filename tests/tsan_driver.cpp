@@ -10,7 +10,11 @@
 // every launch choice the host makes from run-time values, with the host's enqueue order a function of the inputs alone
 // ("poll" 0, "lane_threads" 0): the stub writes the launches down, test_launch_trace_* reads them.  The same file lists
 // every allocation and every uploaded table (size and hash), so two builds of the library can be compared line by line.
-// Both modes end with the stub's count of live device allocations, pinned allocations, events and streams: all zero once
+// `tsan_driver stages [1]` drives the six stage handles beside the decoder -- rate matcher, transport block, NR modulation,
+// BCH, demodulator, batched encoder -- and the simulator's NR generators through the C ABI, a note line per call; with
+// HIP_STUB_TRACE_CALLS the stub writes every runtime call of theirs down.  1: a failure is injected (HIP_STUB_FAIL) and
+// must surface as LDPC_TOOLBOX_ERR_DEVICE.
+// All modes end with the stub's count of live device allocations, pinned allocations, events and streams: all zero once
 // the last handle is gone, also after an injected failure.
 #include <atomic>
 #include <cstdio>
@@ -257,8 +261,239 @@ static int trace_main() {
   return bad ? 1 : 0;
 }
 
+// ---- stages mode -----------------------------------------------------------------------------------------------------
+
+// One call of a stage handle: the note goes into the trace before the call, so the stub's lines of the call follow it.  A
+// return code other than 0 is written out with the library's message; it counts as a fault unless a failure was injected
+// and the code is LDPC_TOOLBOX_ERR_DEVICE (-2).
+struct StageRun {
+  bool expect_error;
+  int bad = 0, errors = 0;
+  template <typename F>
+  void operator()(const std::string &what, F call) {
+    hip_stub_trace_note(what.c_str());
+    const int rc = call();
+    if (rc == 0) return;
+    std::printf("stages: %s: rc %d: %s\n", what.c_str(), rc, ldpc_toolbox_last_error());
+    if (expect_error && rc == LDPC_TOOLBOX_ERR_DEVICE)
+      errors++;
+    else
+      bad++;
+  }
+};
+
+static int64_t tb_get(void *tb, const char *key) {
+  int64_t v = -1;
+  ldpc_toolbox_nr_tb_get(tb, key, &v);
+  return v;
+}
+
+// Every stage handle (rate matcher, transport block, NR modulation, BCH, demodulator, batched encoder) through its host
+// entry and its _device entry with a null stream, at the smallest shapes that reach every branch of the launch plumbing,
+// then the simulator's two NR generators.  Under the stub every pointer is host memory, so the _device entries take the
+// same buffers.  All stages are single: the multi-stage loops need 2^28-byte buffers and are covered on the GPU.
+static int stages_main(bool expect_error) {
+  StageRun run{expect_error};
+  const size_t batch = 3;
+  // (16-byte aligned storage for every element type)
+  std::vector<double> store_a(1 << 14), store_b(1 << 14), store_c(1 << 14);
+  void *const a = store_a.data(), *const b = store_b.data(), *const c = store_c.data();
+  uint8_t *const a8 = static_cast<uint8_t *>(a), *const b8 = static_cast<uint8_t *>(b), *const c8 = static_cast<uint8_t *>(c);
+  float *const af = static_cast<float *>(a), *const bf = static_cast<float *>(b), *const cf = static_cast<float *>(c);
+  double *const ad = static_cast<double *>(a), *const bd = static_cast<double *>(b), *const cd = static_cast<double *>(c);
+  int8_t *const ai = static_cast<int8_t *>(a), *const bi = static_cast<int8_t *>(b);
+
+  {  // rate matcher: n = 104
+    void *rm = ldpc_toolbox_nr_rm_ctor("nr5g:2:2", 0);
+    if (!rm) return 1;
+    const size_t n = 104, e = 96;
+    run("nr_rm match host", [&] { return ldpc_toolbox_nr_rm_match(rm, b8, e, a8, n, batch, 0, 2); });
+    run("nr_rm match device", [&] { return ldpc_toolbox_nr_rm_match_device(rm, b8, e, a8, n, batch, 0, 2, nullptr); });
+    for (int combine : {0, 1}) {
+      const std::string tail = combine ? " combine" : "";
+      run("nr_rm recover f32 host" + tail, [&] { return ldpc_toolbox_nr_rm_recover_f32(rm, bf, n, af, e, batch, 2, 2, 20.0, combine); });
+      run("nr_rm recover f64 host" + tail, [&] { return ldpc_toolbox_nr_rm_recover_f64(rm, bd, n, ad, e, batch, 2, 2, 20.0, combine); });
+      run("nr_rm recover f32 device" + tail,
+          [&] { return ldpc_toolbox_nr_rm_recover_f32_device(rm, bf, n, af, e, batch, 2, 2, 20.0, combine, nullptr); });
+      run("nr_rm recover f64 device" + tail,
+          [&] { return ldpc_toolbox_nr_rm_recover_f64_device(rm, bd, n, ad, e, batch, 2, 2, 20.0, combine, nullptr); });
+      run("nr_rm recover i8 host" + tail, [&] { return ldpc_toolbox_nr_rm_recover_i8(rm, bi, n, ai, e, batch, 0, 2, 100, combine); });
+      // (an odd address: the kernel's pieces follow the address)
+      run("nr_rm recover i8 device" + tail,
+          [&] { return ldpc_toolbox_nr_rm_recover_i8_device(rm, bi + 1, n, ai, e, batch, 0, 2, 100, combine, nullptr); });
+    }
+    ldpc_toolbox_nr_rm_dtor(rm);
+  }
+
+  for (const char *spec : {"nr5g-tb:2:100", "nr5g-tb:2:4000"}) {  // transport block: C = 1 and C = 2
+    void *tb = ldpc_toolbox_nr_tb_ctor(spec, 0);
+    if (!tb) return 1;
+    const size_t ta = size_t(tb_get(tb, "a")), tc = size_t(tb_get(tb, "c")), tk = size_t(tb_get(tb, "k"));
+    const size_t q = 2, g = q * (50 * tc + tc - 1);  // (C = 2: one block of 100 and one of 102)
+    const std::string name = std::string("nr_tb C=") + std::to_string(tc) + " ";
+    run(name + "segment host", [&] { return ldpc_toolbox_nr_tb_segment(tb, b8, tk, a8, ta, batch); });
+    run(name + "segment device", [&] { return ldpc_toolbox_nr_tb_segment_device(tb, b8, tk, a8, ta, batch, nullptr); });
+    for (int flags : {1, 0}) {
+      uint8_t *const tb_ok = c8, *const cb_ok = flags ? c8 + 64 : nullptr;
+      const std::string tail = flags ? " cb_ok" : "";
+      run(name + "desegment host" + tail, [&] { return ldpc_toolbox_nr_tb_desegment(tb, a8, ta, tb_ok, cb_ok, b8, tk, batch); });
+      run(name + "desegment device" + tail,
+          [&] { return ldpc_toolbox_nr_tb_desegment_device(tb, a8, ta, tb_ok, cb_ok, b8, tk, batch, nullptr); });
+    }
+    run(name + "concatenate host", [&] { return ldpc_toolbox_nr_tb_concatenate(tb, b8, g, a8, q, batch); });
+    run(name + "concatenate device", [&] { return ldpc_toolbox_nr_tb_concatenate_device(tb, b8 + 1, g, a8, q, batch, nullptr); });
+    run(name + "split f32 host", [&] { return ldpc_toolbox_nr_tb_split_f32(tb, bf, af, g, q, batch); });
+    run(name + "split f64 host", [&] { return ldpc_toolbox_nr_tb_split_f64(tb, bd, ad, g, q, batch); });
+    run(name + "split f32 device", [&] { return ldpc_toolbox_nr_tb_split_f32_device(tb, bf, af, g, q, batch, nullptr); });
+    run(name + "split f64 device", [&] { return ldpc_toolbox_nr_tb_split_f64_device(tb, bd, ad, g, q, batch, nullptr); });
+    ldpc_toolbox_nr_tb_dtor(tb);
+  }
+
+  for (int qm : {2, 4, 6, 8}) {  // NR modulation: 5 symbols
+    void *qam = ldpc_toolbox_nr_qam_ctor(("nr5g-qam:" + std::to_string(qm)).c_str(), 0);
+    if (!qam) return 1;
+    const size_t sl = 5, ll = sl * size_t(qm);
+    const std::string name = "nr_qam QM=" + std::to_string(qm) + " ";
+    for (int64_t c_init : {int64_t(-1), int64_t(7)}) {
+      const std::string ci = " c_init=" + std::to_string(c_init);
+      run(name + "mod f32 host" + ci, [&] { return ldpc_toolbox_nr_qam_mod_f32(qam, bf, sl, a8, ll, batch, c_init); });
+      run(name + "mod f64 host" + ci, [&] { return ldpc_toolbox_nr_qam_mod_f64(qam, bd, sl, a8, ll, batch, c_init); });
+      run(name + "mod f32 device" + ci, [&] { return ldpc_toolbox_nr_qam_mod_f32_device(qam, bf, sl, a8, ll, batch, c_init, nullptr); });
+      run(name + "mod f64 device" + ci, [&] { return ldpc_toolbox_nr_qam_mod_f64_device(qam, bd, sl, a8, ll, batch, c_init, nullptr); });
+      for (int max_log : {0, 1}) {
+        const std::string tail = std::string(max_log ? " max-log" : " exact") + ci;
+        run(name + "demod f32 host" + tail, [&] { return ldpc_toolbox_nr_qam_demod_f32(qam, bf, ll, af, sl, batch, 0.5, max_log, c_init); });
+        run(name + "demod f64 host" + tail, [&] { return ldpc_toolbox_nr_qam_demod_f64(qam, bd, ll, ad, sl, batch, 0.5, max_log, c_init); });
+        run(name + "demod f32 device" + tail,
+            [&] { return ldpc_toolbox_nr_qam_demod_f32_device(qam, bf, ll, af, sl, batch, 0.5, max_log, c_init, nullptr); });
+        run(name + "demod f64 device" + tail,
+            [&] { return ldpc_toolbox_nr_qam_demod_f64_device(qam, bd, ll, ad, sl, batch, 0.5, max_log, c_init, nullptr); });
+        run(name + "demap_i8 host" + tail, [&] { return ldpc_toolbox_nr_demap_i8(qam, bi, ll, af, sl, batch, 0.5, max_log, c_init); });
+        run(name + "demap_i8 device, aligned" + tail,
+            [&] { return ldpc_toolbox_nr_demap_i8_device(qam, bi, ll, af, sl, batch, 0.5, max_log, c_init, nullptr); });
+        run(name + "demap_i8 device, odd address" + tail,
+            [&] { return ldpc_toolbox_nr_demap_i8_device(qam, bi + 1, ll, af, sl, batch, 0.5, max_log, c_init, nullptr); });
+        run(name + "demap_csi f32 host" + tail, [&] { return ldpc_toolbox_nr_demap_csi_f32(qam, bf, ll, af, cf, sl, batch, max_log, c_init); });
+        run(name + "demap_csi f64 host" + tail, [&] { return ldpc_toolbox_nr_demap_csi_f64(qam, bd, ll, ad, cd, sl, batch, max_log, c_init); });
+        run(name + "demap_csi i8 host" + tail, [&] { return ldpc_toolbox_nr_demap_csi_i8(qam, bi, ll, af, cf, sl, batch, max_log, c_init); });
+        run(name + "demap_csi f32 device" + tail,
+            [&] { return ldpc_toolbox_nr_demap_csi_f32_device(qam, bf, ll, af, cf, sl, batch, max_log, c_init, nullptr); });
+        run(name + "demap_csi f64 device" + tail,
+            [&] { return ldpc_toolbox_nr_demap_csi_f64_device(qam, bd, ll, ad, cd, sl, batch, max_log, c_init, nullptr); });
+        run(name + "demap_csi i8 device, aligned" + tail,
+            [&] { return ldpc_toolbox_nr_demap_csi_i8_device(qam, bi, ll, af, cf, sl, batch, max_log, c_init, nullptr); });
+        run(name + "demap_csi i8 device, odd address" + tail,
+            [&] { return ldpc_toolbox_nr_demap_csi_i8_device(qam, bi + 1, ll, af, cf, sl, batch, max_log, c_init, nullptr); });
+      }
+    }
+    // the cached sequence: (7, ll) is there; another c_init and another length generate it again
+    run(name + "demod f32 host, the same sequence", [&] { return ldpc_toolbox_nr_qam_demod_f32(qam, bf, ll, af, sl, batch, 0.5, 1, 7); });
+    run(name + "demod f32 host, another c_init", [&] { return ldpc_toolbox_nr_qam_demod_f32(qam, bf, ll, af, sl, batch, 0.5, 1, 9); });
+    run(name + "mod f32 device, another length",
+        [&] { return ldpc_toolbox_nr_qam_mod_f32_device(qam, bf, sl - 1, a8, ll - size_t(qm), batch, 9, nullptr); });
+    run(name + "sequence", [&] { return ldpc_toolbox_nr_qam_sequence(qam, b8, 100, 9); });
+    ldpc_toolbox_nr_qam_dtor(qam);
+  }
+
+  {  // BCH: n = 15, k = 7, t = 2
+    void *bch = ldpc_toolbox_bch_ctor("bch:4:13:2:15", 0);
+    if (!bch) return 1;
+    int32_t *const errs = static_cast<int32_t *>(c);
+    run("bch encode host", [&] { return ldpc_toolbox_bch_encode_batch(bch, b8, 15, a8, 7, batch); });
+    run("bch encode device", [&] { return ldpc_toolbox_bch_encode_batch_device(bch, b8, 15, a8, 7, batch, nullptr); });
+    run("bch decode host", [&] { return ldpc_toolbox_bch_decode_batch(bch, a8, 7, b8, 15, batch, nullptr); });
+    run("bch decode host, errors", [&] { return ldpc_toolbox_bch_decode_batch(bch, a8, 15, b8, 15, batch, errs); });
+    run("bch decode device", [&] { return ldpc_toolbox_bch_decode_batch_device(bch, a8, 7, b8, 15, batch, nullptr, nullptr); });
+    run("bch decode device, errors", [&] { return ldpc_toolbox_bch_decode_batch_device(bch, a8, 15, b8, 15, batch, errs, nullptr); });
+    ldpc_toolbox_bch_dtor(bch);
+  }
+
+  for (const char *modulation : {"BPSK", "8PSK"}) {  // demodulator: reals, and a table constellation
+    void *demod = ldpc_toolbox_demod_ctor(modulation, 0);
+    if (!demod) return 1;
+    const bool bpsk = std::strcmp(modulation, "BPSK") == 0;
+    const size_t sl = 5, ll = bpsk ? sl : 3 * sl;
+    const std::string name = std::string("demod ") + modulation + " ";
+    for (int max_log : {0, 1}) {
+      const std::string tail = max_log ? " max-log" : " exact";
+      run(name + "run f32 host" + tail, [&] { return ldpc_toolbox_demod_run_f32(demod, bf, ll, af, sl, batch, 0.5, 0, max_log); });
+      run(name + "run f64 host" + tail, [&] { return ldpc_toolbox_demod_run_f64(demod, bd, ll, ad, sl, batch, 0.5, 0, max_log); });
+      run(name + "run f32 device" + tail, [&] { return ldpc_toolbox_demod_run_f32_device(demod, bf, ll, af, sl, batch, 0.5, 0, max_log, nullptr); });
+      run(name + "run f64 device" + tail, [&] { return ldpc_toolbox_demod_run_f64_device(demod, bd, ll, ad, sl, batch, 0.5, 0, max_log, nullptr); });
+    }
+    run(name + "mod f32 host", [&] { return ldpc_toolbox_mod_run_f32(demod, bf, sl, a8, ll, batch, 0); });
+    run(name + "mod f64 host", [&] { return ldpc_toolbox_mod_run_f64(demod, bd, sl, a8, ll, batch, 0); });
+    run(name + "mod f32 device", [&] { return ldpc_toolbox_mod_run_f32_device(demod, bf, sl, a8, ll, batch, 0, nullptr); });
+    run(name + "mod f64 device", [&] { return ldpc_toolbox_mod_run_f64_device(demod, bd, sl, a8, ll, batch, 0, nullptr); });
+    run(name + "awgn f32 host", [&] { return ldpc_toolbox_awgn_run_f32(demod, bf, sl, batch, 0.5, 1, 0); });
+    run(name + "awgn f64 host", [&] { return ldpc_toolbox_awgn_run_f64(demod, bd, sl, batch, 0.5, 1, 0); });
+    run(name + "awgn f32 device", [&] { return ldpc_toolbox_awgn_run_f32_device(demod, bf, sl, batch, 0.5, 1, 0, nullptr); });
+    run(name + "awgn f64 device", [&] { return ldpc_toolbox_awgn_run_f64_device(demod, bd, sl, batch, 0.5, 1, 0, nullptr); });
+    if (!bpsk) {  // (the fading channel takes complex symbols)
+      run(name + "fading f32 host", [&] { return ldpc_toolbox_fading_run_f32(demod, bf, cf, sl, batch, 0.5, 2, 1, 0); });
+      run(name + "fading f64 host", [&] { return ldpc_toolbox_fading_run_f64(demod, bd, cd, sl, batch, 0.5, 2, 1, 0); });
+      run(name + "fading f32 device", [&] { return ldpc_toolbox_fading_run_f32_device(demod, bf, cf, sl, batch, 0.5, 2, 1, 0, nullptr); });
+      run(name + "fading f64 device", [&] { return ldpc_toolbox_fading_run_f64_device(demod, bd, cd, sl, batch, 0.5, 2, 1, 0, nullptr); });
+    }
+    ldpc_toolbox_demod_dtor(demod);
+  }
+
+  // batched encoder: a staircase code and a dense one, without and with a puncturing pattern
+  for (const char *spec : {"dvbs2:R1_2short", "nr5g:2:2"})
+    for (const char *pattern : {"", "1,1,1,0"}) {
+      const std::string alist = alist_of(spec);
+      void *enc = ldpc_toolbox_encoder_ctor_alist_string_on_device(alist.c_str(), pattern, 0);
+      if (!enc) {
+        std::fprintf(stderr, "%s [%s]: encoder ctor failed: %s\n", spec, pattern, ldpc_toolbox_last_error());
+        return 1;
+      }
+      int64_t k = 0, out_len = 0;
+      ldpc_toolbox_encoder_get(enc, "k", &k);
+      ldpc_toolbox_encoder_get(enc, "output_len", &out_len);
+      const std::string name = std::string("encoder ") + spec + " [" + pattern + "] ";
+      run(name + "host", [&] { return ldpc_toolbox_encoder_encode_batch(enc, b8, size_t(out_len), a8, size_t(k), batch); });
+      run(name + "device", [&] { return ldpc_toolbox_encoder_encode_batch_device(enc, b8, size_t(out_len), a8, size_t(k), batch, nullptr); });
+      ldpc_toolbox_encoder_dtor(enc);
+    }
+
+  {  // the simulator's two NR generators, over AWGN and over the block-fading channel, either fold step
+    const std::string alist = alist_of("nr5g:2:2");
+    void *sim = ldpc_toolbox_sim_ctor(alist.c_str(), "Minsumf32", "", 0, 4, 1);
+    void *qam = ldpc_toolbox_nr_qam_ctor("nr5g-qam:4", 0);
+    void *rm = ldpc_toolbox_nr_rm_ctor("nr5g:2:2", 0);
+    if (!sim || !qam || !rm) {
+      std::fprintf(stderr, "simulator: ctor failed: %s\n", ldpc_toolbox_last_error());
+      return 1;
+    }
+    const uint64_t e[2] = {96, 48};
+    const uint32_t rv[2] = {0, 2};
+    for (int max_log : {0, 1}) {
+      run("sim set_nr_qam", [&] { return ldpc_toolbox_sim_set_nr_qam(sim, qam, max_log); });
+      run("sim set_harq", [&] { return ldpc_toolbox_sim_set_harq(sim, rm, e, rv, 2, 4); });
+      for (int fading_block : {0, 3}) {
+        const std::string tail = std::string(max_log ? " max-log" : " exact") + " fading_block=" + std::to_string(fading_block);
+        run("sim set fading_block", [&] { return ldpc_toolbox_sim_set(sim, "fading_block", fading_block); });
+        run("sim generate" + tail, [&] { return ldpc_toolbox_sim_generate(sim, 3.0, 1, 0, batch, af, nullptr); });
+        run("sim generate_harq" + tail, [&] { return ldpc_toolbox_sim_generate_harq(sim, 3.0, 1, 0, batch, 1, af, nullptr); });
+      }
+    }
+    ldpc_toolbox_nr_rm_dtor(rm);
+    ldpc_toolbox_nr_qam_dtor(qam);
+    ldpc_toolbox_sim_dtor(sim);
+  }
+
+  if (expect_error && run.errors == 0) {
+    std::fprintf(stderr, "the injected failure never surfaced\n");
+    run.bad++;
+  }
+  run.bad += leaked();
+  std::printf("stages: %s (%llu kernel launches through the stub)\n", run.bad ? "FAILED" : "ok", hip_stub_launches());
+  return run.bad ? 1 : 0;
+}
+
 int main(int argc, char **argv) {
   if (argc > 1 && std::strcmp(argv[1], "trace") == 0) return trace_main();
+  if (argc > 1 && std::strcmp(argv[1], "stages") == 0) return stages_main(argc > 2 && std::atoi(argv[2]) != 0);
   const int expect_error = argc > 1 ? std::atoi(argv[1]) : 0;
   int bad = 0;
   bad += drive("nr5g:1:8", "HLMinsumf32", 2048, 2, expect_error);   // layered: lane threads
