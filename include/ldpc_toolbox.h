@@ -890,6 +890,101 @@ int32_t ldpc_toolbox_nr_demap_csi_i8_device(void *qam, int8_t *llrs, size_t llrs
  * With "soft_bits" 8, run_harq stays the composition PART 9 defines over generate_harq; the counters stay independent of
  * chunking and of "pooling".  With 0 every launch and result is what it was. */
 
+/* ===================================================================================
+ * PART 11 -- the 5G NR link handle: one shared-channel configuration, transport blocks in one call each way, and HARQ
+ * soft buffers that stay on the GPU.  It owns one handle of every stage above -- PART 7, the encoder and decoder of PART 2,
+ * PART 6, PART 8 / PART 10 -- and is DEFINED BY THEIR COMPOSITION; what it adds is the bookkeeping a caller of the twelve
+ * stage calls does by hand, a fused kernel for code block de-concatenation and rate recovery, and a decoder that runs only on
+ * the code blocks that have not passed their CRC yet.  The reference has none of it.
+ * =================================================================================== */
+
+/* spec: "nr5g-link:BG:A:G:QM[:NL]", decimal.  BG and A as in "nr5g-tb:BG:A" (PART 7): C, K', Zc, K, F and n follow from them.
+ * G = coded bits per transmission; QM = 2, 4, 6 or 8 bits per symbol; NL = 1 .. 4 layers (default 1); q = QM NL.  The blocks'
+ * lengths (e_lo, e_hi, c_lo) are those of ldpc_toolbox_nr_tb_block_lengths for (G, q); a transmission is G / QM symbols.
+ * implementation: a decoder implementation name as PART 2 takes it, without a device suffix; the link decodes float LLRs.
+ * slots: the HARQ slots, each the state of one transport block: per code block a soft row of n floats, the K hard decisions
+ * and the iteration count of its last decode, and a done flag.
+ * NULL (message via ldpc_toolbox_last_error) for whatever the PART 7 constructor, the block lengths entry, the PART 6
+ * constructor "nr5g:BG:ZC:F" with a transmission of e_lo or e_hi bits, or the PART 8 constructor would refuse; for slots == 0
+ * or slots * C > 0x7fffffff; and for an unknown implementation name.
+ * The constructor needs no GPU: the device state, the slots included, is made by the first batched call (`device`: -1 =
+ * LDPC_TOOLBOX_DEVICE, default 0), and a slot reads as zeros until something is received into it. */
+void *ldpc_toolbox_nr_link_ctor(const char *spec, const char *implementation, uint32_t slots, int32_t device);
+void ldpc_toolbox_nr_link_dtor(void *link);
+/* key: the keys of ldpc_toolbox_nr_tb_get for (BG, A) except its pass and stage sizes; "g", "qm", "layers", "q", "e_lo",
+ * "e_hi", "c_lo", "symbols" (G / QM), "slots"; "max_log"; "pass_elements" (the fused recover kernel runs in launches of at
+ * most this many elements (transport block, block, column); a launch may begin and end inside a transport block),
+ * "stage_bytes" (a transmit call takes floor(stage_bytes / (C n)) transport blocks, at least one, through the handle's
+ * buffers at a time), "device" (-1 until the first batched call made the device state); "decoded_rows" and "skipped_rows":
+ * the code blocks the last receive call gave to the decoder and the ones it left alone, 0 before the first.
+ * returns 0, or -1 for an unknown key. */
+int32_t ldpc_toolbox_nr_link_get(void *link, const char *key, int64_t *value);
+/* key: "max_log" (0, the default: the exact demapper; 1: max-log), "pass_elements" (1 .. 2^30, the default).  Results never
+ * depend on "pass_elements".  returns 0, or LDPC_TOOLBOX_ERR_ARGUMENT with a message and nothing changed. */
+int32_t ldpc_toolbox_nr_link_set(void *link, const char *key, int64_t value);
+/* The LLR of the filler columns in the soft rows, converted to float: positive, +inf allowed (the default, as PART 6's
+ * recover entries are usually called); 0, a negative value or NaN: LDPC_TOOLBOX_ERR_ARGUMENT, nothing changed. */
+int32_t ldpc_toolbox_nr_link_set_filler_llr(void *link, double filler_llr);
+/* Conventions: those of PART 7 and PART 8.  Bytes hold one bit each (1 is a one on input, outputs are 0 or 1); symbols are
+ * (re, im) float pairs; c_init is the scrambling seed 0 .. 2^31 - 1, or -1 for no scrambling; a = A and symbols_len = G / QM.
+ * A null handle or buffer, a length that is not the handle's, rv > 3, a c_init out of range: LDPC_TOOLBOX_ERR_ARGUMENT
+ * before the GPU is touched, nothing written.  Without a GPU LDPC_TOOLBOX_ERR_DEVICE (there is no CPU path).  batch == 0
+ * returns 0.  One call at a time per handle.  Host pointers (symbols staged in, results staged out; the soft rows never
+ * leave the device) or, _device, device pointers and a hipStream_t: a stream = enqueue and return, NULL = the handle's own
+ * stream, ordered after what the legacy default stream holds at the call, synchronised on return.  Device symbol buffers
+ * are aligned to one (re, im) pair, scale and iterations to their element.
+ *
+ * Transmit: payload [batch][a] to symbols [batch][symbols_len].  Bit for bit what this chain gives: ldpc_toolbox_nr_tb_segment;
+ * ldpc_toolbox_encoder_encode_batch on "nr5g:BG:ZC"; ldpc_toolbox_nr_rm_match on "nr5g:BG:ZC:F" with (rv, QM), the first
+ * c_lo * batch rows at e_lo bits and, written behind them, the other rows at e_hi; ldpc_toolbox_nr_tb_concatenate for (G, q);
+ * ldpc_toolbox_nr_qam_mod_f32 on "nr5g-qam:QM" with c_init.  batch is unlimited. */
+int32_t ldpc_toolbox_nr_link_transmit_f32(void *link, float *symbols, size_t symbols_len, const uint8_t *payload, size_t a, size_t batch,
+                                          uint32_t rv, int64_t c_init);
+int32_t ldpc_toolbox_nr_link_transmit_f32_device(void *link, float *symbols, size_t symbols_len, const uint8_t *payload, size_t a,
+                                                 size_t batch, uint32_t rv, int64_t c_init, void *hip_stream);
+/* Receive: symbols [batch][symbols_len] to payload [batch][a], tb_ok [batch], and cb_ok and iterations [batch][C] (either
+ * may be NULL), through the slots first_slot .. first_slot + batch - 1: transport block b of the call lives in slot
+ * first_slot + b.  scale == NULL: the PART 8 demapper with noise_sigma (finite and positive); otherwise scale
+ * [batch][symbols_len] and the PART 10 demapper, and noise_sigma is not read.  Further refusals: first_slot + batch > slots;
+ * combine != 0 with a slot in the range that has never been received into (the handle knows this per slot).
+ *
+ * combine == 0, a first transmission, resets the slots of the range -- no block of them is done -- and is then bit for bit
+ * this chain: ldpc_toolbox_nr_qam_demod_f32 (or ldpc_toolbox_nr_demap_csi_f32), exact or max-log per "max_log", with c_init;
+ * ldpc_toolbox_nr_tb_split_f32 for (G, q); ldpc_toolbox_nr_rm_recover_f32 with (rv, QM), combine 0 and the handle's filler
+ * LLR, at e_lo and at e_hi, into the slots' soft rows; ldpc_toolbox_decoder_decode_batch_f32 with max_iterations on all
+ * C * batch rows, output_len = K; ldpc_toolbox_nr_tb_desegment.  The slots keep the soft rows, the hard decisions, the
+ * iteration counts and the done flags: a block is DONE when its cb_ok is 1 (with C = 1: when tb_ok is 1).
+ * combine != 0, a retransmission.  A block that is not done: its soft row becomes what ldpc_toolbox_nr_rm_recover_f32 with
+ * combine 1 makes of the row the slot holds; it is decoded with the full max_iterations, and its hard decisions and
+ * iteration count replace the slot's.  A block that is done: its soft row, hard decisions and iteration count stay as they
+ * are, bit for bit, and the decoder does not see it.  Then ldpc_toolbox_nr_tb_desegment runs over the slots' hard decisions as
+ * they stand, and iterations reports the slots' counts.  The rows to decode are listed and counted on the device; the count
+ * reaches the host in one 4-byte copy, which is the one time a _device call with combine != 0 waits for its stream before it
+ * returns (a combine == 0 call on a caller's stream does not wait).  With no row to decode the decoder is not called.
+ * Per block the outcome is that of decoding it alone: the decoder is deterministic per codeword whatever batch surrounds it.
+ * A transport block whose blocks all pass CRC24B while the transport block CRC fails -- a block has converged to another
+ * codeword that happens to pass -- has nothing left to decode: it stays failed until a combine == 0 call.  And as in PART 7
+ * an all-zero block passes every CRC: a receiver that may see all-zero hard decisions has to test for them itself. */
+int32_t ldpc_toolbox_nr_link_receive_f32(void *link, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok, int32_t *iterations,
+                                         const float *symbols, const float *scale, size_t symbols_len, size_t batch, double noise_sigma,
+                                         uint32_t rv, int64_t c_init, uint32_t first_slot, int32_t combine, uint32_t max_iterations);
+int32_t ldpc_toolbox_nr_link_receive_f32_device(void *link, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok,
+                                                int32_t *iterations, const float *symbols, const float *scale, size_t symbols_len,
+                                                size_t batch, double noise_sigma, uint32_t rv, int64_t c_init, uint32_t first_slot,
+                                                int32_t combine, uint32_t max_iterations, void *hip_stream);
+/* The rate recovery step of receive alone, for a receiver with a demapper of its own: rx [batch][g], g = G, device LLRs in
+ * transmitted order (what the demapper entries write) into the soft rows of the slots, by the fused kernel: combine == 0
+ * resets the slots of the range as above, combine != 0 adds to the rows of the blocks that are not done.  Nothing is decoded
+ * and no verdict changes.  The refusals are receive's; the stream rules those of the _device entries. */
+int32_t ldpc_toolbox_nr_link_recover_f32_device(void *link, const float *rx, size_t g, size_t batch, uint32_t rv, uint32_t first_slot,
+                                                int32_t combine, void *hip_stream);
+/* Host copies of the state of the slots first_slot .. first_slot + batch - 1, for tests and for a receiver that migrates a
+ * HARQ process: soft [C * batch][n] floats, done [batch][C], rows [C * batch][K] hard decisions; soft and rows block-major
+ * as in PART 7 (row r * batch + b is block r of slot first_slot + b).  Any of the three may be NULL.  Synchronous, on the
+ * handle's own stream: a _device call on a caller's stream has to be complete.  first_slot + batch > slots:
+ * LDPC_TOOLBOX_ERR_ARGUMENT. */
+int32_t ldpc_toolbox_nr_link_slot_state(void *link, float *soft, uint8_t *done, uint8_t *rows, uint32_t first_slot, size_t batch);
+
 /* Standard-code generator (what the reference's `dvbs2` / `5g` / `ccsds` / `ccsds-c2` CLI
  * sub-commands print, src/cli/dvbs2.rs:91, src/cli/nr5g.rs:46, src/cli/ccsds.rs:70): writes the
  * padded alist text of `spec` ("dvbs2:R1_2", "nr5g:1:384", "ar4ja:1/2:1024", "c2") into

@@ -129,6 +129,17 @@ SYMBOLS = [
     "ldpc_toolbox_nr_demap_csi_f32_device",
     "ldpc_toolbox_nr_demap_csi_f64_device",
     "ldpc_toolbox_nr_demap_csi_i8_device",
+    "ldpc_toolbox_nr_link_ctor",
+    "ldpc_toolbox_nr_link_dtor",
+    "ldpc_toolbox_nr_link_get",
+    "ldpc_toolbox_nr_link_set",
+    "ldpc_toolbox_nr_link_set_filler_llr",
+    "ldpc_toolbox_nr_link_transmit_f32",
+    "ldpc_toolbox_nr_link_transmit_f32_device",
+    "ldpc_toolbox_nr_link_receive_f32",
+    "ldpc_toolbox_nr_link_receive_f32_device",
+    "ldpc_toolbox_nr_link_recover_f32_device",
+    "ldpc_toolbox_nr_link_slot_state",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
     "ldpc_toolbox_device_count",
@@ -413,6 +424,29 @@ def lib():
         f = getattr(L, "ldpc_toolbox_nr_demap_csi_" + name + "_device")
         f.restype = i32
         f.argtypes = [vp, vp, sz, vp, vp, sz, sz, i32, C.c_int64, vp]
+    # the NR link handle (PART 11): one call each way, HARQ slots on the device
+    L.ldpc_toolbox_nr_link_ctor.restype = vp
+    L.ldpc_toolbox_nr_link_ctor.argtypes = [cp, cp, u32, i32]
+    L.ldpc_toolbox_nr_link_dtor.restype = None
+    L.ldpc_toolbox_nr_link_dtor.argtypes = [vp]
+    L.ldpc_toolbox_nr_link_get.restype = i32
+    L.ldpc_toolbox_nr_link_get.argtypes = [vp, cp, C.POINTER(C.c_int64)]
+    L.ldpc_toolbox_nr_link_set.restype = i32
+    L.ldpc_toolbox_nr_link_set.argtypes = [vp, cp, C.c_int64]
+    L.ldpc_toolbox_nr_link_set_filler_llr.restype = i32
+    L.ldpc_toolbox_nr_link_set_filler_llr.argtypes = [vp, C.c_double]
+    L.ldpc_toolbox_nr_link_transmit_f32.restype = i32
+    L.ldpc_toolbox_nr_link_transmit_f32.argtypes = [vp, vp, sz, vp, sz, sz, u32, C.c_int64]
+    L.ldpc_toolbox_nr_link_transmit_f32_device.restype = i32
+    L.ldpc_toolbox_nr_link_transmit_f32_device.argtypes = L.ldpc_toolbox_nr_link_transmit_f32.argtypes + [vp]
+    L.ldpc_toolbox_nr_link_receive_f32.restype = i32
+    L.ldpc_toolbox_nr_link_receive_f32.argtypes = [vp, vp, sz, vp, vp, vp, vp, vp, sz, sz, C.c_double, u32, C.c_int64, u32, i32, u32]
+    L.ldpc_toolbox_nr_link_receive_f32_device.restype = i32
+    L.ldpc_toolbox_nr_link_receive_f32_device.argtypes = L.ldpc_toolbox_nr_link_receive_f32.argtypes + [vp]
+    L.ldpc_toolbox_nr_link_recover_f32_device.restype = i32
+    L.ldpc_toolbox_nr_link_recover_f32_device.argtypes = [vp, vp, sz, sz, u32, u32, i32, vp]
+    L.ldpc_toolbox_nr_link_slot_state.restype = i32
+    L.ldpc_toolbox_nr_link_slot_state.argtypes = [vp, vp, vp, vp, u32, sz]
     L.ldpc_toolbox_code_alist.restype = sz
     L.ldpc_toolbox_code_alist.argtypes = [cp, vp, sz]
     L.ldpc_toolbox_alist_normalize.restype = sz

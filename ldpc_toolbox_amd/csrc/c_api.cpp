@@ -9,9 +9,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
+#include <limits>
 #include <memory>
 #include <sstream>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "codes.h"
@@ -19,6 +21,7 @@
 #include "device_bch.h"
 #include "device_decoder.h"
 #include "device_encoder.h"
+#include "device_nr_link.h"
 #include "device_nr_qam.h"
 #include "device_nr_rm.h"
 #include "device_nr_tb.h"
@@ -93,6 +96,19 @@ struct NrQamHandle {
   int device = 0;
   // the device state: made at the first run
   std::unique_ptr<ldpc::DeviceNrQam> dev;
+};
+
+struct NrLinkHandle {
+  ldpc::nrlink::Config c;
+  ldpc::Implementation impl;
+  uint32_t slots = 0;
+  int device = 0;
+  // what the setters hold until the device state exists, and then hand on
+  bool max_log = false;
+  uint64_t pass_elements = ldpc::nrlink::kPassElements;
+  double filler_llr = 0.0;  // (the constructor entry sets +inf)
+  // the device state, the HARQ slots included: made at the first batched call
+  std::unique_ptr<ldpc::DeviceNrLink> dev;
 };
 
 // a device index: decimal digits only (no sign, no trailing characters)
@@ -739,6 +755,84 @@ int32_t nr_tb_repack(void *tb, void *output, const void *input, size_t g, size_t
     rc = on_device ? h->dev->concatenate_device(static_cast<const uint8_t *>(input), static_cast<uint8_t *>(output), l, batch, s)
                    : h->dev->concatenate_host(static_cast<const uint8_t *>(input), static_cast<uint8_t *>(output), l, batch);
   return nr_tb_result(h, rc);
+}
+
+int32_t nr_link_refuse(const char *why) {
+  set_error(why);
+  return LDPC_TOOLBOX_ERR_ARGUMENT;
+}
+
+// 0 with the handle's device state made, or LDPC_TOOLBOX_ERR_DEVICE
+int32_t nr_link_device_state(NrLinkHandle *h) {
+  if (!h->dev) {
+    if (h->device < 0) {
+      set_error("LDPC_TOOLBOX_DEVICE is not a decimal GPU index");
+      return LDPC_TOOLBOX_ERR_DEVICE;
+    }
+    std::string err;
+    h->dev.reset(ldpc::DeviceNrLink::create(h->c, h->impl, h->slots, h->device, &err));
+    if (!h->dev) {
+      set_error(err);
+      return LDPC_TOOLBOX_ERR_DEVICE;
+    }
+  }
+  h->dev->set_max_log(h->max_log);
+  h->dev->set_pass_elements(h->pass_elements);
+  h->dev->set_filler_llr(static_cast<float>(h->filler_llr));
+  return 0;
+}
+
+int32_t nr_link_result(NrLinkHandle *h, int rc) {
+  if (rc == 0) return 0;
+  set_error(h->dev->last_error());
+  return LDPC_TOOLBOX_ERR_DEVICE;
+}
+
+int32_t nr_link_transmit(void *link, float *symbols, size_t symbols_len, const uint8_t *payload, size_t a, size_t batch, uint32_t rv,
+                         int64_t c_init, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrLinkHandle *>(link);
+  if (!h) return nr_link_refuse("null link handle");
+  if (const char *why = ldpc::nrlink::transmit_argument_error(h->c, symbols_len, a, rv, c_init)) return nr_link_refuse(why);
+  if (batch == 0) return 0;
+  if (!payload || !symbols) return nr_link_refuse("null payload or symbol buffer");
+  if (on_device)
+    if (const char *why = ldpc::nrqam::device_pointer_error(symbols, nullptr, false)) return nr_link_refuse(why);
+  if (int32_t rc = nr_link_device_state(h)) return rc;
+  return nr_link_result(h, on_device ? h->dev->transmit_device(payload, symbols, batch, rv, c_init, static_cast<hipStream_t>(stream))
+                                     : h->dev->transmit_host(payload, symbols, batch, rv, c_init));
+}
+
+// what every call into the slots checks: the range, and with `combine` that each slot of it holds a reception
+const char *nr_link_slots_error(NrLinkHandle *h, uint32_t first_slot, size_t batch, int32_t combine) {
+  if (const char *why = ldpc::nrlink::slots_error(first_slot, batch, h->slots)) return why;
+  if (combine != 0 && batch > 0 && !(h->dev && h->dev->slots_used(first_slot, batch))) return "combine with a slot that has never been received into";
+  return nullptr;
+}
+
+int32_t nr_link_receive(void *link, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok, int32_t *iterations, const float *symbols,
+                        const float *scale, size_t symbols_len, size_t batch, double noise_sigma, uint32_t rv, int64_t c_init,
+                        uint32_t first_slot, int32_t combine, uint32_t max_iterations, bool on_device, void *stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrLinkHandle *>(link);
+  if (!h) return nr_link_refuse("null link handle");
+  if (const char *why = ldpc::nrlink::receive_argument_error(h->c, symbols_len, a, rv, c_init, scale != nullptr, noise_sigma, first_slot,
+                                                             batch, h->slots))
+    return nr_link_refuse(why);
+  if (const char *why = nr_link_slots_error(h, first_slot, batch, combine)) return nr_link_refuse(why);
+  if (batch == 0) return 0;
+  if (!payload || !tb_ok || !symbols) return nr_link_refuse("null payload, tb_ok or symbol buffer");
+  if (on_device) {
+    if (const char *why = ldpc::nrqam::device_pointer_error(symbols, nullptr, false)) return nr_link_refuse(why);
+    if (scale)
+      if (const char *why = ldpc::nrqam::scale_pointer_error(scale, false)) return nr_link_refuse(why);
+    if (reinterpret_cast<uintptr_t>(iterations) % sizeof(int32_t) != 0) return nr_link_refuse("the iterations buffer is not aligned to its element");
+  }
+  if (int32_t rc = nr_link_device_state(h)) return rc;
+  return nr_link_result(h, on_device ? h->dev->receive_device(symbols, scale, payload, tb_ok, cb_ok, iterations, batch, noise_sigma, rv, c_init,
+                                                              first_slot, combine != 0, max_iterations, static_cast<hipStream_t>(stream))
+                                     : h->dev->receive_host(symbols, scale, payload, tb_ok, cb_ok, iterations, batch, noise_sigma, rv, c_init,
+                                                            first_slot, combine != 0, max_iterations));
 }
 
 template <typename F>
@@ -1922,6 +2016,131 @@ int32_t ldpc_toolbox_nr_demap_csi_f64_device(void *qam, double *llrs, size_t llr
 int32_t ldpc_toolbox_nr_demap_csi_i8_device(void *qam, int8_t *llrs, size_t llrs_len, const float *symbols, const float *scale,
                                             size_t symbols_len, size_t batch, int32_t max_log, int64_t c_init, void *hip_stream) {
   return nr_demap_csi(qam, llrs, llrs_len, symbols, scale, symbols_len, batch, 1, max_log, c_init, true, hip_stream);
+}
+
+// ---- PART 11: the 5G NR link handle: one-call transport blocks with HARQ slots --------------------------
+
+void *ldpc_toolbox_nr_link_ctor(const char *spec, const char *implementation, uint32_t slots, int32_t device) {
+  g_last_error.clear();
+  auto refuse = [](const std::string &why) -> void * {
+    set_error(why);
+    return nullptr;
+  };
+  if (!spec) return refuse("null link spec");
+  if (!implementation) return refuse("invalid decoder implementation");
+  auto h = std::make_unique<NrLinkHandle>();
+  if (const char *why = ldpc::nrlink::parse_spec(spec, &h->c)) return refuse(why);
+  if (slots == 0) return refuse("a link handle has at least one HARQ slot");
+  if (uint64_t(slots) * h->c.tb.c > 0x7fffffffu) return refuse("slots * C above 0x7fffffff");
+  std::string err;
+  if (!ldpc::parse_implementation(implementation, &h->impl, &err)) return refuse(err);
+  h->slots = slots;
+  h->filler_llr = std::numeric_limits<double>::infinity();
+  h->device = device < 0 ? default_device() : device;
+  return h.release();
+}
+
+void ldpc_toolbox_nr_link_dtor(void *link) { delete static_cast<NrLinkHandle *>(link); }
+
+int32_t ldpc_toolbox_nr_link_get(void *link, const char *key, int64_t *value) {
+  auto *h = static_cast<NrLinkHandle *>(link);
+  if (!h || !key || !value) return -1;
+  const std::string k = key;
+  const ldpc::nrtb::Config &c = h->c.tb;
+  const std::pair<const char *, int64_t> table[] = {
+      {"a", c.a}, {"base_graph", c.bg}, {"tb_crc", c.l_tb}, {"b", c.b}, {"c", c.c}, {"cb_crc", c.l_cb}, {"k_prime", c.k_prime},
+      {"k_b", c.kb}, {"zc", c.zc}, {"k", c.k}, {"fillers", c.fillers}, {"n", c.n},
+      {"g", h->c.len.g}, {"qm", h->c.qm}, {"layers", h->c.layers}, {"q", h->c.q}, {"e_lo", h->c.len.e_lo}, {"e_hi", h->c.len.e_hi},
+      {"c_lo", h->c.len.c_lo}, {"symbols", h->c.symbols}, {"slots", h->slots},
+      {"max_log", h->max_log ? 1 : 0},
+      {"pass_elements", static_cast<int64_t>(h->pass_elements)},  // elements (transport block, block, column) per launch of the fused recover kernel
+      {"stage_bytes", static_cast<int64_t>(ldpc::nrlink::kStageBytes)},  // codeword bytes a transmit call takes through the handle's buffers at a time
+      {"device", h->dev ? h->dev->device() : -1},
+      {"decoded_rows", h->dev ? static_cast<int64_t>(h->dev->decoded_rows()) : 0},
+      {"skipped_rows", h->dev ? static_cast<int64_t>(h->dev->skipped_rows()) : 0},
+  };
+  for (const auto &entry : table)
+    if (k == entry.first) {
+      *value = entry.second;
+      return 0;
+    }
+  return -1;
+}
+
+int32_t ldpc_toolbox_nr_link_set(void *link, const char *key, int64_t value) {
+  g_last_error.clear();
+  auto *h = static_cast<NrLinkHandle *>(link);
+  if (!h || !key) return nr_link_refuse("null link handle or key");
+  const std::string k = key;
+  if (k == "max_log") {
+    if (value != 0 && value != 1) return nr_link_refuse("max_log must be 0 or 1");
+    h->max_log = value != 0;
+  } else if (k == "pass_elements") {
+    if (const char *why = ldpc::nrlink::pass_elements_error(value)) return nr_link_refuse(why);
+    h->pass_elements = static_cast<uint64_t>(value);
+  } else {
+    return nr_link_refuse("unknown key");
+  }
+  return 0;
+}
+
+int32_t ldpc_toolbox_nr_link_set_filler_llr(void *link, double filler_llr) {
+  g_last_error.clear();
+  auto *h = static_cast<NrLinkHandle *>(link);
+  if (!h) return nr_link_refuse("null link handle");
+  if (const char *why = ldpc::nrlink::filler_llr_error(filler_llr)) return nr_link_refuse(why);
+  h->filler_llr = filler_llr;
+  return 0;
+}
+
+int32_t ldpc_toolbox_nr_link_transmit_f32(void *link, float *symbols, size_t symbols_len, const uint8_t *payload, size_t a, size_t batch,
+                                          uint32_t rv, int64_t c_init) {
+  return nr_link_transmit(link, symbols, symbols_len, payload, a, batch, rv, c_init, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_link_transmit_f32_device(void *link, float *symbols, size_t symbols_len, const uint8_t *payload, size_t a, size_t batch,
+                                                 uint32_t rv, int64_t c_init, void *hip_stream) {
+  return nr_link_transmit(link, symbols, symbols_len, payload, a, batch, rv, c_init, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_link_receive_f32(void *link, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok, int32_t *iterations,
+                                         const float *symbols, const float *scale, size_t symbols_len, size_t batch, double noise_sigma,
+                                         uint32_t rv, int64_t c_init, uint32_t first_slot, int32_t combine, uint32_t max_iterations) {
+  return nr_link_receive(link, payload, a, tb_ok, cb_ok, iterations, symbols, scale, symbols_len, batch, noise_sigma, rv, c_init, first_slot,
+                         combine, max_iterations, false, nullptr);
+}
+
+int32_t ldpc_toolbox_nr_link_receive_f32_device(void *link, uint8_t *payload, size_t a, uint8_t *tb_ok, uint8_t *cb_ok, int32_t *iterations,
+                                                const float *symbols, const float *scale, size_t symbols_len, size_t batch,
+                                                double noise_sigma, uint32_t rv, int64_t c_init, uint32_t first_slot, int32_t combine,
+                                                uint32_t max_iterations, void *hip_stream) {
+  return nr_link_receive(link, payload, a, tb_ok, cb_ok, iterations, symbols, scale, symbols_len, batch, noise_sigma, rv, c_init, first_slot,
+                         combine, max_iterations, true, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_link_recover_f32_device(void *link, const float *rx, size_t g, size_t batch, uint32_t rv, uint32_t first_slot,
+                                                int32_t combine, void *hip_stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrLinkHandle *>(link);
+  if (!h) return nr_link_refuse("null link handle");
+  if (g != h->c.len.g) return nr_link_refuse("row length is not the handle's G");
+  if (rv > 3) return nr_link_refuse("rv must be 0 .. 3");
+  if (const char *why = nr_link_slots_error(h, first_slot, batch, combine)) return nr_link_refuse(why);
+  if (batch == 0) return 0;
+  if (!rx) return nr_link_refuse("null LLR buffer");
+  if (reinterpret_cast<uintptr_t>(rx) % sizeof(float) != 0) return nr_link_refuse("the LLR buffer is not aligned to its element");
+  if (int32_t rc = nr_link_device_state(h)) return rc;
+  return nr_link_result(h, h->dev->recover_device(rx, batch, rv, first_slot, combine != 0, static_cast<hipStream_t>(hip_stream)));
+}
+
+int32_t ldpc_toolbox_nr_link_slot_state(void *link, float *soft, uint8_t *done, uint8_t *rows, uint32_t first_slot, size_t batch) {
+  g_last_error.clear();
+  auto *h = static_cast<NrLinkHandle *>(link);
+  if (!h) return nr_link_refuse("null link handle");
+  if (const char *why = ldpc::nrlink::slots_error(first_slot, batch, h->slots)) return nr_link_refuse(why);
+  if (batch == 0 || (!soft && !done && !rows)) return 0;
+  if (int32_t rc = nr_link_device_state(h)) return rc;
+  return nr_link_result(h, h->dev->slot_state_host(soft, done, rows, first_slot, batch));
 }
 
 // ---- code tables and utilities ------------------------------------------------------------------------

@@ -12,6 +12,7 @@
 #include "device_nr_qam.hip.h"    // the NR modulation mapper, demapper and scrambling
 #include "device_nr_rm.hip.h"     // and the batched NR rate matcher
 #include "device_nr_tb.hip.h"     // and the NR transport block CRCs, segmentation and concatenation
+#include "device_nr_link.hip.h"   // and the NR link handle that drives those stages
 #include "frame_gen.hip.h"
 #include "implementation.h"
 #include "sparse.h"
