@@ -985,6 +985,50 @@ int32_t ldpc_toolbox_nr_link_recover_f32_device(void *link, const float *rx, siz
  * LDPC_TOOLBOX_ERR_ARGUMENT. */
 int32_t ldpc_toolbox_nr_link_slot_state(void *link, float *soft, uint8_t *done, uint8_t *rows, uint32_t first_slot, size_t batch);
 
+/* ===================================================================================
+ * PART 12 -- 8-bit HARQ soft buffers in the link handle of PART 11: one byte per soft bit (PART 9) from the demapper through
+ * the slots to the decoder input.  DEFINED BY THE COMPOSITION of the _i8 stage entries of PART 9 and PART 10, as PART 11 is by
+ * the float ones.  No float LLR row exists in this mode: the demapper output is batch * G bytes, the slots' soft rows are
+ * [C * slots][n] int8_t, and so is the decoder's input.
+ * =================================================================================== */
+
+/* The mode is the key "soft_bits" of ldpc_toolbox_nr_link_set: 32 (the default: PART 11 as it stands) or 8;
+ * ldpc_toolbox_nr_link_get reports it, and "soft_bytes", the bytes of the slots' soft rows, C * slots * n * (soft_bits / 8),
+ * which follows from the configuration and needs no GPU.  The setter returns LDPC_TOOLBOX_ERR_ARGUMENT, with a message and
+ * nothing changed: for a value other than 8 or 32; for 8 when the handle's implementation is not one of the 8-bit names of
+ * PART 9; for 8 when the filler LLR quantises to the soft bit 0; and for a value other than the current one once the device
+ * state exists ("device" is not -1) -- the slots are allocated by the first batched call, so the mode is chosen before it.
+ * Setting the current value always returns 0.  The mode never follows from the implementation name: an 8-bit implementation
+ * on float slots sums and then quantises, this mode quantises and then sums with saturation.
+ * The filler soft bit of an 8-bit handle is Q(filler_llr), PART 9's quantiser: 127 for the default +inf and for every LLR
+ * from 15.8125 on.  On an 8-bit handle ldpc_toolbox_nr_link_set_filler_llr also refuses a value with Q(filler_llr) == 0.
+ *
+ * Receive with soft_bits 8 -- ldpc_toolbox_nr_link_receive_f32[_device], signatures unchanged, symbols and scale floats.
+ * combine == 0 resets the slots of the range and is then byte for byte this chain: ldpc_toolbox_nr_demap_i8 (or
+ * ldpc_toolbox_nr_demap_csi_i8 when scale != NULL) per "max_log", with c_init; the bytes of block r of transport block b are
+ * positions start(r) .. start(r) + E_r - 1 of row b, start(r) = r e_lo + max(r - c_lo, 0) (e_hi - e_lo) -- what
+ * ldpc_toolbox_nr_tb_split_f32 does to floats, a copy; ldpc_toolbox_nr_rm_recover_i8 with (rv, QM), combine 0 and filler
+ * Q(filler_llr), at e_lo and at e_hi, into the slots' soft rows; ldpc_toolbox_decoder_decode_batch_i8 with max_iterations on
+ * all C * batch rows, output_len = K; ldpc_toolbox_nr_tb_desegment.
+ * combine != 0 is PART 11's rule with these entries: a block that is not done gets ldpc_toolbox_nr_rm_recover_i8 with combine 1
+ * on the row its slot holds -- saturating, in the fixed order of PART 9 -- and is decoded with the full budget; a done block's
+ * row, hard decisions and iteration count stay as they are, byte for byte, and the decoder does not see it.  The done rule,
+ * the one 4-byte count copy, "decoded_rows" / "skipped_rows", the refusals and the stream rules are PART 11's.
+ * The fused recover kernel owns four columns and one dword of a soft row per thread, so its launches are whole dwords:
+ * "pass_elements" rounded down to a multiple of 4, and 4 below that; results never depend on it. */
+
+/* ldpc_toolbox_nr_link_recover_f32_device for a receiver with an 8-bit demapper of its own: rx [batch][g], g = G, device soft
+ * bits in transmitted order at any byte address, -128 read as -127, into the slots' int8 soft rows by the fused kernel;
+ * nothing is decoded and no verdict changes.  On a float handle LDPC_TOOLBOX_ERR_UNSUPPORTED, as
+ * ldpc_toolbox_nr_link_recover_f32_device on an 8-bit handle; both before the GPU is touched.  Otherwise the refusals and the
+ * stream rules are those of the float entry. */
+int32_t ldpc_toolbox_nr_harq_slots_recover_i8_device(void *link, const int8_t *rx, size_t g, size_t batch, uint32_t rv,
+                                                     uint32_t first_slot, int32_t combine, void *hip_stream);
+/* ldpc_toolbox_nr_link_slot_state with the soft rows as the bytes an 8-bit handle's slots hold: soft [C * batch][n] int8_t.  On
+ * a float handle with soft != NULL LDPC_TOOLBOX_ERR_UNSUPPORTED, as ldpc_toolbox_nr_link_slot_state with soft != NULL on an
+ * 8-bit handle; with soft == NULL either entry works on either handle. */
+int32_t ldpc_toolbox_nr_harq_slots_state_i8(void *link, int8_t *soft, uint8_t *done, uint8_t *rows, uint32_t first_slot, size_t batch);
+
 /* Standard-code generator (what the reference's `dvbs2` / `5g` / `ccsds` / `ccsds-c2` CLI
  * sub-commands print, src/cli/dvbs2.rs:91, src/cli/nr5g.rs:46, src/cli/ccsds.rs:70): writes the
  * padded alist text of `spec` ("dvbs2:R1_2", "nr5g:1:384", "ar4ja:1/2:1024", "c2") into

@@ -140,6 +140,8 @@ SYMBOLS = [
     "ldpc_toolbox_nr_link_receive_f32_device",
     "ldpc_toolbox_nr_link_recover_f32_device",
     "ldpc_toolbox_nr_link_slot_state",
+    "ldpc_toolbox_nr_harq_slots_recover_i8_device",
+    "ldpc_toolbox_nr_harq_slots_state_i8",
     "ldpc_toolbox_code_alist",
     "ldpc_toolbox_alist_normalize",
     "ldpc_toolbox_device_count",
@@ -447,6 +449,11 @@ def lib():
     L.ldpc_toolbox_nr_link_recover_f32_device.argtypes = [vp, vp, sz, sz, u32, u32, i32, vp]
     L.ldpc_toolbox_nr_link_slot_state.restype = i32
     L.ldpc_toolbox_nr_link_slot_state.argtypes = [vp, vp, vp, vp, u32, sz]
+    # the 8-bit forms of the last two (PART 12)
+    L.ldpc_toolbox_nr_harq_slots_recover_i8_device.restype = i32
+    L.ldpc_toolbox_nr_harq_slots_recover_i8_device.argtypes = L.ldpc_toolbox_nr_link_recover_f32_device.argtypes
+    L.ldpc_toolbox_nr_harq_slots_state_i8.restype = i32
+    L.ldpc_toolbox_nr_harq_slots_state_i8.argtypes = L.ldpc_toolbox_nr_link_slot_state.argtypes
     L.ldpc_toolbox_code_alist.restype = sz
     L.ldpc_toolbox_code_alist.argtypes = [cp, vp, sz]
     L.ldpc_toolbox_alist_normalize.restype = sz

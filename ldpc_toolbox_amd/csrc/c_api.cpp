@@ -107,6 +107,7 @@ struct NrLinkHandle {
   bool max_log = false;
   uint64_t pass_elements = ldpc::nrlink::kPassElements;
   double filler_llr = 0.0;  // (the constructor entry sets +inf)
+  uint32_t soft_bits = 32;  // 8: the PART 12 mode; fixed once the device state exists
   // the device state, the HARQ slots included: made at the first batched call
   std::unique_ptr<ldpc::DeviceNrLink> dev;
 };
@@ -770,7 +771,7 @@ int32_t nr_link_device_state(NrLinkHandle *h) {
       return LDPC_TOOLBOX_ERR_DEVICE;
     }
     std::string err;
-    h->dev.reset(ldpc::DeviceNrLink::create(h->c, h->impl, h->slots, h->device, &err));
+    h->dev.reset(ldpc::DeviceNrLink::create(h->c, h->impl, h->slots, h->soft_bits, h->device, &err));
     if (!h->dev) {
       set_error(err);
       return LDPC_TOOLBOX_ERR_DEVICE;
@@ -779,7 +780,15 @@ int32_t nr_link_device_state(NrLinkHandle *h) {
   h->dev->set_max_log(h->max_log);
   h->dev->set_pass_elements(h->pass_elements);
   h->dev->set_filler_llr(static_cast<float>(h->filler_llr));
+  if (h->soft_bits == 8) h->dev->set_filler_soft_bit(ldpc::nrlink::filler_soft_bit(h->filler_llr));
   return 0;
+}
+
+// the entries that take or give soft rows of one mode, called on a handle of the other
+int32_t nr_link_wrong_mode(const NrLinkHandle *h) {
+  set_error(h->soft_bits == 8 ? "the handle's soft rows are 8-bit soft bits (soft_bits 8): use the _i8 entry"
+                              : "the handle's soft rows are floats (soft_bits 32): use the float entry");
+  return LDPC_TOOLBOX_ERR_UNSUPPORTED;
 }
 
 int32_t nr_link_result(NrLinkHandle *h, int rc) {
@@ -833,6 +842,26 @@ int32_t nr_link_receive(void *link, uint8_t *payload, size_t a, uint8_t *tb_ok, 
                                                               first_slot, combine != 0, max_iterations, static_cast<hipStream_t>(stream))
                                      : h->dev->receive_host(symbols, scale, payload, tb_ok, cb_ok, iterations, batch, noise_sigma, rv, c_init,
                                                             first_slot, combine != 0, max_iterations));
+}
+
+// rx: floats (soft_bits 32) or bytes (8), already known to be the handle's kind
+int32_t nr_link_recover(NrLinkHandle *h, const void *rx, size_t elem, size_t g, size_t batch, uint32_t rv, uint32_t first_slot, int32_t combine,
+                        void *stream) {
+  if (g != h->c.len.g) return nr_link_refuse("row length is not the handle's G");
+  if (rv > 3) return nr_link_refuse("rv must be 0 .. 3");
+  if (const char *why = nr_link_slots_error(h, first_slot, batch, combine)) return nr_link_refuse(why);
+  if (batch == 0) return 0;
+  if (!rx) return nr_link_refuse("null LLR buffer");
+  if (reinterpret_cast<uintptr_t>(rx) % elem != 0) return nr_link_refuse("the LLR buffer is not aligned to its element");
+  if (int32_t rc = nr_link_device_state(h)) return rc;
+  return nr_link_result(h, h->dev->recover_device(rx, batch, rv, first_slot, combine != 0, static_cast<hipStream_t>(stream)));
+}
+
+int32_t nr_link_slot_state(NrLinkHandle *h, void *soft, uint8_t *done, uint8_t *rows, uint32_t first_slot, size_t batch) {
+  if (const char *why = ldpc::nrlink::slots_error(first_slot, batch, h->slots)) return nr_link_refuse(why);
+  if (batch == 0 || (!soft && !done && !rows)) return 0;
+  if (int32_t rc = nr_link_device_state(h)) return rc;
+  return nr_link_result(h, h->dev->slot_state_host(soft, done, rows, first_slot, batch));
 }
 
 template <typename F>
@@ -2053,6 +2082,8 @@ int32_t ldpc_toolbox_nr_link_get(void *link, const char *key, int64_t *value) {
       {"g", h->c.len.g}, {"qm", h->c.qm}, {"layers", h->c.layers}, {"q", h->c.q}, {"e_lo", h->c.len.e_lo}, {"e_hi", h->c.len.e_hi},
       {"c_lo", h->c.len.c_lo}, {"symbols", h->c.symbols}, {"slots", h->slots},
       {"max_log", h->max_log ? 1 : 0},
+      {"soft_bits", h->soft_bits},
+      {"soft_bytes", static_cast<int64_t>(ldpc::nrlink::soft_bytes(h->c, h->slots, h->soft_bits))},  // of the slots' soft rows
       {"pass_elements", static_cast<int64_t>(h->pass_elements)},  // elements (transport block, block, column) per launch of the fused recover kernel
       {"stage_bytes", static_cast<int64_t>(ldpc::nrlink::kStageBytes)},  // codeword bytes a transmit call takes through the handle's buffers at a time
       {"device", h->dev ? h->dev->device() : -1},
@@ -2078,6 +2109,9 @@ int32_t ldpc_toolbox_nr_link_set(void *link, const char *key, int64_t value) {
   } else if (k == "pass_elements") {
     if (const char *why = ldpc::nrlink::pass_elements_error(value)) return nr_link_refuse(why);
     h->pass_elements = static_cast<uint64_t>(value);
+  } else if (k == "soft_bits") {
+    if (const char *why = ldpc::nrlink::soft_bits_error(value, h->soft_bits, h->impl.i8, h->filler_llr, h->dev != nullptr)) return nr_link_refuse(why);
+    h->soft_bits = static_cast<uint32_t>(value);
   } else {
     return nr_link_refuse("unknown key");
   }
@@ -2089,6 +2123,8 @@ int32_t ldpc_toolbox_nr_link_set_filler_llr(void *link, double filler_llr) {
   auto *h = static_cast<NrLinkHandle *>(link);
   if (!h) return nr_link_refuse("null link handle");
   if (const char *why = ldpc::nrlink::filler_llr_error(filler_llr)) return nr_link_refuse(why);
+  if (h->soft_bits == 8)
+    if (const char *why = ldpc::nrlink::filler_soft_bit_error(filler_llr)) return nr_link_refuse(why);
   h->filler_llr = filler_llr;
   return 0;
 }
@@ -2123,24 +2159,35 @@ int32_t ldpc_toolbox_nr_link_recover_f32_device(void *link, const float *rx, siz
   g_last_error.clear();
   auto *h = static_cast<NrLinkHandle *>(link);
   if (!h) return nr_link_refuse("null link handle");
-  if (g != h->c.len.g) return nr_link_refuse("row length is not the handle's G");
-  if (rv > 3) return nr_link_refuse("rv must be 0 .. 3");
-  if (const char *why = nr_link_slots_error(h, first_slot, batch, combine)) return nr_link_refuse(why);
-  if (batch == 0) return 0;
-  if (!rx) return nr_link_refuse("null LLR buffer");
-  if (reinterpret_cast<uintptr_t>(rx) % sizeof(float) != 0) return nr_link_refuse("the LLR buffer is not aligned to its element");
-  if (int32_t rc = nr_link_device_state(h)) return rc;
-  return nr_link_result(h, h->dev->recover_device(rx, batch, rv, first_slot, combine != 0, static_cast<hipStream_t>(hip_stream)));
+  if (h->soft_bits != 32) return nr_link_wrong_mode(h);
+  return nr_link_recover(h, rx, sizeof(float), g, batch, rv, first_slot, combine, hip_stream);
 }
 
 int32_t ldpc_toolbox_nr_link_slot_state(void *link, float *soft, uint8_t *done, uint8_t *rows, uint32_t first_slot, size_t batch) {
   g_last_error.clear();
   auto *h = static_cast<NrLinkHandle *>(link);
   if (!h) return nr_link_refuse("null link handle");
-  if (const char *why = ldpc::nrlink::slots_error(first_slot, batch, h->slots)) return nr_link_refuse(why);
-  if (batch == 0 || (!soft && !done && !rows)) return 0;
-  if (int32_t rc = nr_link_device_state(h)) return rc;
-  return nr_link_result(h, h->dev->slot_state_host(soft, done, rows, first_slot, batch));
+  if (soft && h->soft_bits != 32) return nr_link_wrong_mode(h);
+  return nr_link_slot_state(h, soft, done, rows, first_slot, batch);
+}
+
+// ---- PART 12: 8-bit HARQ soft buffers in the NR link handle ----------------------------------------------
+
+int32_t ldpc_toolbox_nr_harq_slots_recover_i8_device(void *link, const int8_t *rx, size_t g, size_t batch, uint32_t rv, uint32_t first_slot,
+                                                     int32_t combine, void *hip_stream) {
+  g_last_error.clear();
+  auto *h = static_cast<NrLinkHandle *>(link);
+  if (!h) return nr_link_refuse("null link handle");
+  if (h->soft_bits != 8) return nr_link_wrong_mode(h);
+  return nr_link_recover(h, rx, 1, g, batch, rv, first_slot, combine, hip_stream);
+}
+
+int32_t ldpc_toolbox_nr_harq_slots_state_i8(void *link, int8_t *soft, uint8_t *done, uint8_t *rows, uint32_t first_slot, size_t batch) {
+  g_last_error.clear();
+  auto *h = static_cast<NrLinkHandle *>(link);
+  if (!h) return nr_link_refuse("null link handle");
+  if (soft && h->soft_bits != 8) return nr_link_wrong_mode(h);
+  return nr_link_slot_state(h, soft, done, rows, first_slot, batch);
 }
 
 // ---- code tables and utilities ------------------------------------------------------------------------

@@ -25,12 +25,14 @@ DeviceNrLink::DeviceNrLink(int device) : DeviceStage("nr_link", device) {}
 // (the stages go first, each after waiting for its own work; then the buffers, the stream last)
 DeviceNrLink::~DeviceNrLink() { wait_idle(); }
 
-DeviceNrLink *DeviceNrLink::create(const nrlink::Config &c, const Implementation &impl, uint32_t slots, int device, std::string *err) {
+DeviceNrLink *DeviceNrLink::create(const nrlink::Config &c, const Implementation &impl, uint32_t slots, uint32_t soft_bits, int device,
+                                   std::string *err) {
   if (err) err->clear();
   if (!select_device(device, "the link handle has", err)) return nullptr;
   std::unique_ptr<DeviceNrLink> d(new DeviceNrLink(device));
   d->c_ = c;
   d->slots_ = slots;
+  d->soft_bytes_ = soft_bits / 8;
   d->filler_ = std::numeric_limits<float>::infinity();
   d->used_.assign(slots, 0);
   if (!d->create_stream("the link handle's", err)) return nullptr;
@@ -50,13 +52,13 @@ DeviceNrLink *DeviceNrLink::create(const nrlink::Config &c, const Implementation
   if (d->qam_) d->dec_.reset(DeviceDecoder::create(h, impl, {}, device, err));
   if (!d->dec_) return nullptr;
   const size_t rows = size_t(c.tb.c) * slots;
-  hipError_t e = d->d_soft_.ensure(rows * c.tb.n * sizeof(float), 256);
+  hipError_t e = d->d_soft_.ensure(rows * c.tb.n * d->soft_bytes_, 256);
   if (e == hipSuccess) e = d->d_hard_.ensure(rows * c.tb.k, 256);
   if (e == hipSuccess) e = d->d_its_.ensure(rows * sizeof(int32_t), 256);
   if (e == hipSuccess) e = d->d_done_.ensure(rows, 256);
   if (e == hipSuccess) e = d->d_count_.ensure(sizeof(uint32_t), 256);
   // a slot that nothing has been received into reads as zeros (ldpc_toolbox_nr_link_slot_state)
-  if (e == hipSuccess) e = hipMemsetAsync(d->d_soft_.get(), 0, rows * c.tb.n * sizeof(float), d->stream_);
+  if (e == hipSuccess) e = hipMemsetAsync(d->d_soft_.get(), 0, rows * c.tb.n * d->soft_bytes_, d->stream_);
   if (e == hipSuccess) e = hipMemsetAsync(d->d_hard_.get(), 0, rows * c.tb.k, d->stream_);
   if (e == hipSuccess) e = hipMemsetAsync(d->d_its_.get(), 0, rows * sizeof(int32_t), d->stream_);
   if (e == hipSuccess) e = hipMemsetAsync(d->d_done_.get(), 0, rows, d->stream_);
@@ -106,7 +108,7 @@ int DeviceNrLink::transmit_device(const uint8_t *payload, float *symbols, size_t
   return end(stream, s);
 }
 
-int DeviceNrLink::recover_into_slots(const float *rx, size_t batch, uint32_t rv, uint32_t first_slot, bool combine, hipStream_t s) {
+int DeviceNrLink::recover_into_slots(const void *rx, size_t batch, uint32_t rv, uint32_t first_slot, bool combine, hipStream_t s) {
   const nrlink::Geometry k = nrlink::make_geometry(c_);
   const nrrm::Plan p_lo = nrrm::make_plan(c_.rm, c_.len.e_lo, rv, c_.qm), p_hi = nrrm::make_plan(c_.rm, c_.len.e_hi, rv, c_.qm);
   const nrlink::SlotArgs sl{c_.tb.c, slots_, first_slot, static_cast<uint32_t>(batch)};
@@ -114,15 +116,25 @@ int DeviceNrLink::recover_into_slots(const float *rx, size_t batch, uint32_t rv,
   if (!combine) STAGE_TRY(hipMemsetAsync(d_done_.get<uint8_t>() + size_t(first_slot) * k.c, 0, batch * k.c, s));
   std::fill(used_.begin() + first_slot, used_.begin() + first_slot + batch, uint8_t(1));
   const uint64_t elements = uint64_t(batch) * k.per_tb;
+  if (soft_i8()) {
+    // four columns and one dword per thread: passes of whole dwords
+    const uint64_t per_pass = nrlink::dword_pass_elements(pass_elements_);
+    for (uint64_t first = 0; first < elements; first += per_pass) {
+      const nrlink::Pass pass = nrlink::make_pass(c_, first, std::min<uint64_t>(per_pass, elements - first));
+      nrlink::recover_i8_kernel<<<(pass.total / 4 + nrlink::kThreads - 1) / nrlink::kThreads, nrlink::kThreads, 0, s>>>(
+          static_cast<const int8_t *>(rx), d_soft_.get<int8_t>(), d_done_.get<uint8_t>(), k, pass, sl, p_lo, p_hi, filler_soft_bit_, combine ? 1 : 0);
+    }
+    return 0;
+  }
   for (uint64_t first = 0; first < elements; first += pass_elements_) {
     const nrlink::Pass pass = nrlink::make_pass(c_, first, std::min<uint64_t>(pass_elements_, elements - first));
     nrlink::recover_kernel<<<(pass.total + nrlink::kThreads - 1) / nrlink::kThreads, nrlink::kThreads, 0, s>>>(
-        rx, d_soft_.get<float>(), d_done_.get<uint8_t>(), k, pass, sl, p_lo, p_hi, filler_, combine ? 1 : 0);
+        static_cast<const float *>(rx), d_soft_.get<float>(), d_done_.get<uint8_t>(), k, pass, sl, p_lo, p_hi, filler_, combine ? 1 : 0);
   }
   return 0;
 }
 
-int DeviceNrLink::recover_device(const float *rx, size_t batch, uint32_t rv, uint32_t first_slot, bool combine, hipStream_t stream) {
+int DeviceNrLink::recover_device(const void *rx, size_t batch, uint32_t rv, uint32_t first_slot, bool combine, hipStream_t stream) {
   if (batch == 0) return 0;
   hipStream_t s;
   if (int rc = begin(stream, &s)) return rc;
@@ -141,7 +153,7 @@ int DeviceNrLink::receive_device(const float *symbols, const float *scale, uint8
   const nrlink::SlotArgs sl{t.c, slots_, first_slot, static_cast<uint32_t>(batch)};
   uint8_t *done = d_done_.get<uint8_t>() + size_t(first_slot) * t.c;
   int32_t *its = d_its_.get<int32_t>() + size_t(first_slot) * t.c;
-  STAGE_TRY(d_llrs_.ensure(batch * c_.len.g * sizeof(float), 256));
+  STAGE_TRY(d_llrs_.ensure(batch * c_.len.g * soft_bytes_, 256));
   STAGE_TRY(d_list_.ensure(rows * sizeof(uint32_t), 256));
   STAGE_TRY(d_bits_.ensure(rows * t.k, 256));
   auto stage = [&](DeviceStage &h, int rc) {
@@ -149,10 +161,15 @@ int DeviceNrLink::receive_device(const float *symbols, const float *scale, uint8
     return rc;
   };
   decoded_rows_ = skipped_rows_ = 0;
-  int rc = scale ? qam_->demap_csi_device(symbols, scale, d_llrs_.get(), false, c_.symbols, c_.len.g, batch, max_log_, c_init, s)
-                 : qam_->demod_device(symbols, d_llrs_.get(), false, c_.symbols, c_.len.g, batch, noise_sigma, max_log_, c_init, s);
+  int rc;
+  if (soft_i8())
+    rc = scale ? qam_->demap_csi_i8_device(symbols, scale, d_llrs_.get<int8_t>(), c_.symbols, c_.len.g, batch, max_log_, c_init, s)
+               : qam_->demap_i8_device(symbols, d_llrs_.get<int8_t>(), c_.symbols, c_.len.g, batch, noise_sigma, max_log_, c_init, s);
+  else
+    rc = scale ? qam_->demap_csi_device(symbols, scale, d_llrs_.get(), false, c_.symbols, c_.len.g, batch, max_log_, c_init, s)
+               : qam_->demod_device(symbols, d_llrs_.get(), false, c_.symbols, c_.len.g, batch, noise_sigma, max_log_, c_init, s);
   if (stage(*qam_, rc)) return rc;
-  if ((rc = recover_into_slots(d_llrs_.get<float>(), batch, rv, first_slot, combine, s)) != 0) return rc;
+  if ((rc = recover_into_slots(d_llrs_.get(), batch, rv, first_slot, combine, s)) != 0) return rc;
   nrlink::active_list_kernel<<<1, 64, 0, s>>>(d_done_.get<uint8_t>(), d_list_.get<uint32_t>(), d_count_.get<uint32_t>(), sl,
                                               dev::fast_div(sl.batch));
   // a first reception decodes every row; a retransmission the rows the list holds, and the host has to know how many
@@ -162,12 +179,18 @@ int DeviceNrLink::receive_device(const float *symbols, const float *scale, uint8
     STAGE_TRY(hipStreamSynchronize(s));
   }
   if (active > 0) {
-    STAGE_TRY(d_dec_in_.ensure(size_t(active) * t.n * sizeof(float), 256));
+    STAGE_TRY(d_dec_in_.ensure(size_t(active) * t.n * soft_bytes_, 256));
     STAGE_TRY(d_dec_bits_.ensure(size_t(active) * t.k, 256));
     STAGE_TRY(d_dec_its_.ensure(size_t(active) * sizeof(int32_t), 256));
-    nrlink::gather_soft_kernel<<<active, nrlink::kThreads, 0, s>>>(d_soft_.get<float4>(), d_list_.get<uint32_t>(), d_dec_in_.get<float4>(),
-                                                                   t.n / 4);
-    rc = dec_->decode_device(d_dec_in_.get(), LlrType::F32, active, max_iterations, d_dec_bits_.get<uint8_t>(), t.k,
+    // rows of 16-byte units, or of dwords where 8-bit rows begin on a dword only
+    const uint32_t row_bytes = t.n * static_cast<uint32_t>(soft_bytes_);
+    if (row_bytes % 16 == 0)
+      nrlink::gather_soft_kernel<<<active, nrlink::kThreads, 0, s>>>(d_soft_.get<float4>(), d_list_.get<uint32_t>(), d_dec_in_.get<float4>(),
+                                                                     row_bytes / 16);
+    else
+      nrlink::gather_soft_dword_kernel<<<active, nrlink::kThreads, 0, s>>>(d_soft_.get<uint32_t>(), d_list_.get<uint32_t>(),
+                                                                           d_dec_in_.get<uint32_t>(), row_bytes / 4);
+    rc = dec_->decode_device(d_dec_in_.get(), soft_i8() ? LlrType::I8 : LlrType::F32, active, max_iterations, d_dec_bits_.get<uint8_t>(), t.k,
                              d_dec_its_.get<int32_t>(), nullptr, s);
     if (rc != 0) {
       fail(dec_->last_error());
@@ -221,7 +244,7 @@ int DeviceNrLink::receive_host(const float *symbols, const float *scale, uint8_t
                 });
 }
 
-int DeviceNrLink::slot_state_host(float *soft, uint8_t *done, uint8_t *rows, uint32_t first_slot, size_t batch) {
+int DeviceNrLink::slot_state_host(void *soft, uint8_t *done, uint8_t *rows, uint32_t first_slot, size_t batch) {
   if (batch == 0) return 0;
   STAGE_TRY(hipSetDevice(device_));
   const size_t c = c_.tb.c, n = c_.tb.n, k = c_.tb.k;
@@ -229,7 +252,8 @@ int DeviceNrLink::slot_state_host(float *soft, uint8_t *done, uint8_t *rows, uin
   for (size_t r = 0; r < c; r++) {
     const size_t from = r * slots_ + first_slot;
     if (soft)
-      STAGE_TRY(hipMemcpyAsync(soft + r * batch * n, d_soft_.get<float>() + from * n, batch * n * sizeof(float), hipMemcpyDeviceToHost, stream_));
+      STAGE_TRY(hipMemcpyAsync(static_cast<uint8_t *>(soft) + r * batch * n * soft_bytes_, d_soft_.get<uint8_t>() + from * n * soft_bytes_,
+                               batch * n * soft_bytes_, hipMemcpyDeviceToHost, stream_));
     if (rows) STAGE_TRY(hipMemcpyAsync(rows + r * batch * k, d_hard_.get<uint8_t>() + from * k, batch * k, hipMemcpyDeviceToHost, stream_));
   }
   if (done) STAGE_TRY(hipMemcpyAsync(done, d_done_.get<uint8_t>() + size_t(first_slot) * c, batch * c, hipMemcpyDeviceToHost, stream_));

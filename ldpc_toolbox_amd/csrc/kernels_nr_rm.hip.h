@@ -68,18 +68,27 @@ __global__ __launch_bounds__(kThreads) void nr_rm_recover_kernel(const T *__rest
 
 // ---- 8-bit soft bits (include/ldpc_toolbox.h, PART 9; soft_i8.h) --------------------------------------------------------
 
-// the soft bit of output element g of the pass; old: the byte there now (read only when `combine` is set)
-__device__ __forceinline__ int recover_i8_column(const int8_t *__restrict__ rx, const Plan &p, const FastDiv &div_n, uint32_t g,
-                                                 int filler, int32_t combine, int old) {
-  const uint32_t frame = dev::fdiv_q(g, div_n);
-  const uint32_t r = first_selection_of_column(p, g - frame * p.n);
+// The soft bit of one column of a soft row, which every 8-bit recover kernel computes through this function (the link
+// handle's fused one, kernels_nr_link.hip.h, included).  row: the E received bytes of the column's frame or block, at any
+// byte address, read only where a selection index carries the column; old: the byte there now (read only when `combine` is
+// set).  The filler; else clip(old) or 0 on top of the left-to-right saturating sum of the column's repeats in ascending
+// selection index, every received byte clipped first.
+__device__ __forceinline__ int recover_i8_value(const int8_t *__restrict__ row, const Plan &p, uint32_t column, int filler, int32_t combine,
+                                                int old) {
+  const uint32_t r = first_selection_of_column(p, column);
   if (r == kFiller) return filler;
   const int kept = combine ? soft::soft_clip(old) : 0;
   if (r >= p.e) return kept;  // (kNotSent included)
-  const int8_t *row = rx + size_t(frame) * p.e;
   int s = soft::soft_clip(row[position_of_selection(p, r)]);
   for (uint32_t j = r + p.l; j < p.e; j += p.l) s = soft::soft_accumulate(s, soft::soft_clip(row[position_of_selection(p, j)]));
   return combine ? soft::soft_accumulate(kept, s) : s;
+}
+
+// the soft bit of output element g of the pass
+__device__ __forceinline__ int recover_i8_column(const int8_t *__restrict__ rx, const Plan &p, const FastDiv &div_n, uint32_t g,
+                                                 int filler, int32_t combine, int old) {
+  const uint32_t frame = dev::fdiv_q(g, div_n);
+  return recover_i8_value(rx + size_t(frame) * p.e, p, g - frame * p.n, filler, combine, old);
 }
 
 // rx [frames][E] -> llrs [frames][n], one byte per soft bit.  A thread owns four consecutive output bytes, aligned to a dword

@@ -23,6 +23,7 @@
 #include "fast_div.h"
 #include "nr_rate_match.h"
 #include "nr_transport_block.h"
+#include "soft_i8.h"
 
 namespace ldpc {
 namespace nrlink {
@@ -116,6 +117,33 @@ inline const char *receive_argument_error(const Config &c, uint64_t symbols_len,
 inline const char *pass_elements_error(int64_t v) {
   return v >= 1 && uint64_t(v) <= kPassElements ? nullptr : "pass_elements must be 1 .. 2^30";
 }
+
+
+// ---- the 8-bit mode (include/ldpc_toolbox.h, PART 12): "soft_bits" 8, one byte per soft bit from the demapper to the decoder ----
+
+// the filler soft bit of an 8-bit handle, Q(filler_llr): 127 for +inf and for 20.0
+inline int filler_soft_bit(double filler_llr) { return soft::soft_quantize(filler_llr); }
+inline const char *filler_soft_bit_error(double filler_llr) {
+  return filler_soft_bit(filler_llr) != 0 ? nullptr : "the filler LLR quantises to the soft bit 0 (an 8-bit handle needs 8 * filler_llr >= 0.5)";
+}
+// nullptr, or why "soft_bits" cannot become `value`; implementation_i8: the handle's implementation is one of the 8-bit
+// names; device_state: the slots exist
+inline const char *soft_bits_error(int64_t value, int64_t current, bool implementation_i8, double filler_llr, bool device_state) {
+  if (value != 8 && value != 32) return "soft_bits must be 8 or 32";
+  if (value == current) return nullptr;
+  if (value == 8 && !implementation_i8) return "soft_bits 8 needs one of the 8-bit implementations";
+  if (value == 8)
+    if (const char *why = filler_soft_bit_error(filler_llr)) return why;
+  if (device_state) return "soft_bits is chosen before the first batched call: the HARQ slots exist";
+  return nullptr;
+}
+// bytes of the slots' soft rows
+inline uint64_t soft_bytes(const Config &c, uint64_t slots, uint32_t soft_bits) {
+  return uint64_t(c.tb.c) * slots * c.tb.n * (soft_bits / 8);
+}
+// A pass of the 8-bit recover kernel is a whole number of dwords: pass_elements rounded down to a multiple of 4, and 4
+// below that.  C n is a multiple of 4, so every such pass begins and ends on a dword of a soft row.
+inline uint64_t dword_pass_elements(uint64_t pass_elements) { return pass_elements < 4 ? 4 : pass_elements / 4 * 4; }
 
 // One pass of the fused recover kernel: elements first .. first + total - 1 of the call's [batch][C][n], as
 // (tb0, within): element i of the pass is x = within + i < 2^31 elements behind the beginning of transport block tb0.

@@ -1,7 +1,8 @@
 """The 5G NR link handle on the GPU (include/ldpc_toolbox.h, PART 11): one shared-channel configuration, payload to symbols
 and symbols to payload in one call each, with HARQ soft buffers that stay on the device and a decoder that runs only on the
 code blocks that have not passed their CRC.  It is defined by the composition of `NrTransportBlock`, `Encoder`,
-`NrRateMatcher`, `NrQam` and `LdpcDecoder`.  There is no CPU fallback."""
+`NrRateMatcher`, `NrQam` and `LdpcDecoder`.  With soft_bits=8 (PART 12) the soft bits are one byte each from the demapper
+through the slots to the decoder input, by the composition of the stages' 8-bit entries.  There is no CPU fallback."""
 import ctypes as C
 
 import numpy as np
@@ -14,9 +15,10 @@ class NrLink:
     """`NrLink("nr5g-link:BG:A:G:QM[:NL]", "Minsumf32", slots)`: base graph, payload bits, coded bits per transmission, bits
     per symbol and layers; the decoder implementation; the number of HARQ slots.  Transport block b of a receive call lives
     in slot first_slot + b.  Bytes hold one bit each.  The handle needs no GPU until the first batched call (device=None: GPU
-    LDPC_TOOLBOX_DEVICE)."""
+    LDPC_TOOLBOX_DEVICE).  soft_bits=8: the HARQ slots hold 8-bit soft bits (an 8-bit implementation only; ValueError
+    otherwise); 32, the default: floats."""
 
-    def __init__(self, spec: str, implementation: str, slots: int, device=0):
+    def __init__(self, spec: str, implementation: str, slots: int, device=0, soft_bits: int = 32):
         if not 0 <= int(slots) < 2 ** 32:
             raise ValueError("slots must be 1 .. 2^32 - 1")
         h = _capi.lib().ldpc_toolbox_nr_link_ctor(spec.encode(), str(implementation).encode(), int(slots), -1 if device is None else int(device))
@@ -24,6 +26,11 @@ class NrLink:
             raise ValueError(_capi.last_error() or "link constructor returned NULL")
         self._h = h
         self.spec = spec
+        try:
+            self.set("soft_bits", soft_bits)
+        except Exception:
+            self.close()
+            raise
 
     def get(self, key: str) -> int:
         v = C.c_int64(0)
@@ -32,13 +39,15 @@ class NrLink:
         return int(v.value)
 
     def set(self, key: str, value: int):
-        """"max_log" (0 / 1) or "pass_elements" (elements per launch of the fused recover kernel)"""
+        """"max_log" (0 / 1), "pass_elements" (elements per launch of the fused recover kernel) or "soft_bits" (8 / 32, before
+        the first batched call)"""
         rc = _capi.lib().ldpc_toolbox_nr_link_set(self._h, key.encode(), int(value))
         if rc != 0:
             self._raise("set", rc)
 
     def set_filler_llr(self, value: float):
-        """the LLR of the filler columns in the soft rows: positive, +inf (the default) allowed"""
+        """the LLR of the filler columns in the soft rows: positive, +inf (the default) allowed; an 8-bit handle writes its
+        quantised value, which must not be 0"""
         rc = _capi.lib().ldpc_toolbox_nr_link_set_filler_llr(self._h, float(value))
         if rc != 0:
             self._raise("set_filler_llr", rc)
@@ -57,6 +66,8 @@ class NrLink:
     q = property(lambda self: self.get("q"))
     symbols = property(lambda self: self.get("symbols"), doc="complex symbols per transmission, G / QM")
     slots = property(lambda self: self.get("slots"))
+    soft_bits = property(lambda self: self.get("soft_bits"), doc="8: the slots hold 8-bit soft bits; 32: floats")
+    soft_bytes = property(lambda self: self.get("soft_bytes"), doc="bytes of the slots' soft rows, C * slots * n * (soft_bits / 8)")
     block_lengths = property(lambda self: (self.get("e_lo"), self.get("e_hi"), self.get("c_lo")),
                              doc="(e_lo, e_hi, c_lo): the first c_lo blocks are rate-matched to e_lo bits, the others to e_hi")
     decoded_rows = property(lambda self: self.get("decoded_rows"), doc="code blocks the last receive call gave to the decoder")
@@ -117,16 +128,19 @@ class NrLink:
 
     def slot_state(self, first_slot: int = 0, batch=None):
         """host copies of the slots first_slot .. first_slot + batch - 1 (default: all behind first_slot): (soft rows
-        [C * batch][n] float32, done flags [batch][C], kept hard decisions [C * batch][K]); the rows are block-major, row
-        r * batch + b is block r of slot first_slot + b"""
+        [C * batch][n] float32, or int8 on an 8-bit handle, done flags [batch][C], kept hard decisions [C * batch][K]); the
+        rows are block-major, row r * batch + b is block r of slot first_slot + b"""
         B = self.slots - int(first_slot) if batch is None else int(batch)
         if B < 0:
             raise ValueError("first_slot is above the handle's slots")
         c = self.c
-        soft = np.zeros((c * B, self.n), dtype=np.float32)
+        i8 = self.soft_bits == 8
+        soft = np.zeros((c * B, self.n), dtype=np.int8 if i8 else np.float32)
         done = np.zeros((B, c), dtype=np.uint8)
         rows = np.zeros((c * B, self.k), dtype=np.uint8)
-        rc = _capi.lib().ldpc_toolbox_nr_link_slot_state(self._h, soft.ctypes.data, done.ctypes.data, rows.ctypes.data, int(first_slot), B)
+        L = _capi.lib()
+        entry = L.ldpc_toolbox_nr_harq_slots_state_i8 if i8 else L.ldpc_toolbox_nr_link_slot_state
+        rc = entry(self._h, soft.ctypes.data, done.ctypes.data, rows.ctypes.data, int(first_slot), B)
         if rc != 0:
             self._raise("slot_state", rc)
         return soft, done, rows
@@ -158,6 +172,14 @@ class NrLink:
                                                                  stream or None)
         if rc != 0:
             self._raise("recover_device", rc)
+
+    def recover_i8_device(self, rx_ptr: int, batch: int, rv: int = 0, first_slot: int = 0, combine: bool = False, stream: int = 0):
+        """`recover_device` of an 8-bit handle: soft bits [batch][G] int8 in transmitted order, at any byte address (-128 reads
+        as -127) -> the slots' int8 soft rows; RuntimeError on a float handle, as `recover_device` on an 8-bit one"""
+        rc = _capi.lib().ldpc_toolbox_nr_harq_slots_recover_i8_device(self._h, rx_ptr, self.g, batch, int(rv), int(first_slot),
+                                                                      int(bool(combine)), stream or None)
+        if rc != 0:
+            self._raise("recover_i8_device", rc)
 
     def close(self):
         if getattr(self, "_h", None):
